@@ -2,7 +2,7 @@
 """bench.py -- CODON x4 forward on MI355X: HR depth maps/s at batch 32/GPU, 480x640, fp32
 (BASELINE.json configs[1]).  One "step" = one CODONNet forward over one synthetic batch.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,9 +10,14 @@ With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) this script sta
 makes no GPU call, spawns N fresh `python bench.py` children with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set
 (rendezvous on 127.0.0.1), forwards rank 0's JSON line and exits non-zero if any child fails.
 
-The BASELINE metric has two halves -- "HR depth maps/sec (fwd) + iters/sec (fwd+bwd)": the default line's `value` is
-the exact-fp32 forward (configs[1]); the same line carries `fwd_bwd`: a short training leg at configs[2]'s per-GPU
-shape (x4, batch 32/GPU, 480x640, bf16 activations, fp32 accumulate + master weights, L1+SSIM loss, one RCCL
+A plain run sets up, runs W warm-up and K timed steps of the headline workload, writes the last timed step's outputs
+if --dump-outputs DIR is given (DIR/<name>.npy, float32, rank 0's shard) and prints the line.  Everything else the line
+can carry -- the legs below, the CPU baseline, the one-image latencies, the script loop, the strong-scaling shards, the
+opt-in f16x3 leg and the N > 1 gradient-equality self-check -- runs only with --full.
+
+The BASELINE metric has two halves -- "HR depth maps/sec (fwd) + iters/sec (fwd+bwd)": the line's `value` is
+the exact-fp32 forward (configs[1]); with --full the same line carries `fwd_bwd`: a short training leg at configs[2]'s
+per-GPU shape (x4, batch 32/GPU, 480x640, bf16 activations, fp32 accumulate + master weights, L1+SSIM loss, one RCCL
 all-reduce of the flat gradient per step when N > 1, Adam).
 
 Images are independent units (no op mixes samples), so ranks shard the batch with NO data-path
@@ -20,7 +25,7 @@ collective in forward ("scaling": "weak": 32 images per GPU whatever N; `--scali
 total, split over the ranks -- SURVEY.md 8e -- with the label in "scaling").  Rank 0 prints ONE JSON
 line.  `roofline` is measured live for the dominant kernel (the 5x5 128->128 fp32 MFMA conv,
 71.7 % of the FLOPs) with HIP events recorded on the launch stream around each of its launches
-inside the timed region.  `cpu_baseline` times the CPU oracle (a port of the reference's
+inside the timed region.  `cpu_baseline` (--full) times the CPU oracle (a port of the reference's
 eager-PyTorch path, validated against the imported reference) on a bounded sample, rank 0, N=1 only.
 """
 import argparse
@@ -198,6 +203,29 @@ def step_stats(events):
             "min_ms": ms[0], "max_ms": ms[-1], "n": len(ms)}
 
 
+DUMP_BYTES = 64_000_000          # --dump-outputs: all .npy files of one run together (headers included)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write each tensor of `arrays` (name -> tensor, in order) as DIR/<name>.npy in float32.  If they would
+    exceed DUMP_BYTES together, every array above its even share is replaced by a fixed, seeded sample of its flattened
+    elements (the same indices on every run of the same arguments).  Returns {name: [shape written, sampled]}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = (DUMP_BYTES - 256 * len(arrays)) // 4 // max(len(arrays), 1)
+    total = sum(t.numel() for t in arrays.values())
+    done = {}
+    for i, (name, t) in enumerate(arrays.items()):
+        a = t.detach().float().cpu().numpy()
+        sampled = total * 4 > DUMP_BYTES - 256 * len(arrays) and a.size > share
+        if sampled:
+            idx = np.sort(np.random.default_rng(1000 + i).integers(0, a.size, size=share))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        done[name] = [list(a.shape), bool(sampled)]
+    return done
+
+
 def cpu_baseline(H, W):
     """Oracle forward on the host cores for ONE image of the workload (bounded: ~10-30 s)."""
     from oracle import codon_oracle as orc
@@ -371,10 +399,11 @@ def script_loop_throughput(dev):
 
 
 def train_leg(model, x, y, dev, dist, rank, world, barrier, steps, warmup, dtype, scale, scaling="weak", ctrl=None,
-              data=None):
+              data=None, outputs=None):
     """One step = zero_grad, forward, L1 + (1 - SSIM) loss (HIP kernels, forward and backward), backward (HIP
     dgrad/wgrad/CAC kernels), ONE all-reduce of the flat gradient buffer (RCCL when world > 1), Adam step.
-    Nothing is skipped.  Returns the result dict on rank 0 (None elsewhere)."""
+    Nothing is skipped.  Returns the result dict on rank 0 (None elsewhere).  A dict passed as `outputs` receives
+    what the last timed step computed: its loss, the model output and the updated parameters (flat)."""
     from codon_amd.dist import GradSync
     from codon_amd.metrics import L1SSIMLoss
     B, _, H, W = x.shape
@@ -394,12 +423,12 @@ def train_leg(model, x, y, dev, dist, rank, world, barrier, steps, warmup, dtype
         gs.backward(loss)                # the direct route: the backward's kernels add into the flat all-reduce buffer
         gs.all_reduce_grads()
         opt.step()
-        return loss
+        return loss, out
 
     from codon_amd import ops
     torch.cuda.reset_peak_memory_stats(dev)
     for _ in range(warmup):
-        loss = step()
+        loss, out = step()
     # live roofline of the dominant backward kernel: HIP events around every conv5x5 128->128 weight-gradient launch
     ops.PROFILE = {"key": None, "events": [], "wgrad_key": (5, 128, 128), "wgrad_events": []}
     evs = []
@@ -410,7 +439,7 @@ def train_leg(model, x, y, dev, dist, rank, world, barrier, steps, warmup, dtype
     for _ in range(steps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(torch.cuda.current_stream(dev))
-        loss = step()
+        loss, out = step()
         e1.record(torch.cuda.current_stream(dev))
         evs.append((e0, e1))
     barrier()
@@ -418,6 +447,10 @@ def train_leg(model, x, y, dev, dist, rank, world, barrier, steps, warmup, dtype
     hw_train = hw.stop(single_rank=(world == 1))
     prof, ops.PROFILE = ops.PROFILE, None
     assert torch.isfinite(loss)
+    if outputs is not None:
+        outputs.update(loss=loss.detach().reshape(1), out=out.detach(),
+                       params=torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]))
+    del out
     # one all-reduce of the flat gradient, timed on its own (latency-bound: 7.46 MB over xGMI)
     ar_us = None
     if dist is not None:
@@ -712,7 +745,7 @@ def main():
     ap.add_argument("--scale", type=int, default=4, choices=[4, 8, 16])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fwd-bwd", action="store_true",
-                    help="skip the bf16 forward+backward leg (iters/s half of the metric) of the default forward line")
+                    help="skip the bf16 forward+backward leg (iters/s half of the metric) of a --full forward line")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default). gloo only to rehearse the multi-rank path on one GPU")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
@@ -731,12 +764,21 @@ def main():
                          "N ranks (SURVEY.md 8e); the label goes into the JSON line")
     ap.add_argument("--rccl-selfcheck", choices=["auto", "on", "off"], default="auto",
                     help="before timing, run SURVEY 8(e)'s gradient-equality check on the product kernels over the process "
-                         "group (codon_amd.dist.grad_equality_selfcheck): `grad_equal` in rank 0's line.  auto = when N > 1")
+                         "group (codon_amd.dist.grad_equality_selfcheck): `grad_equal` in rank 0's line.  auto = with --full when N > 1")
     ap.add_argument("--no-strong-shards", action="store_true",
-                    help="skip the strong-scaling shard timings (b16 / b8 / b4 on one GPU) of the N = 1 default line")
+                    help="skip the strong-scaling shard timings (b16 / b8 / b4 on one GPU) of the N = 1 --full line")
     ap.add_argument("--no-script-pattern", action="store_true",
-                    help="skip the single-image latencies at the reference script's image sizes (N = 1 default line only)")
+                    help="skip the single-image latencies at the reference script's image sizes (N = 1 --full line only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the fwd+bwd leg, the opt-in f16x3 leg, the one-image "
+                         "latencies and script loop, the strong-scaling shards and (N > 1) the gradient-equality self-check; "
+                         "the --no-* switches above trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's shard) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed, seeded sample of a larger output)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit(f"bench.py: --steps must be >= 1 and --warmup >= 0 (got {a.steps}, {a.warmup})")
     if os.environ.get("CODON_BENCH_DUMP_S"):
         # diagnostics: every N seconds every thread's Python stack goes to stderr (where is a slow or hung rank?)
         import faulthandler
@@ -787,7 +829,7 @@ def main():
     from codon_amd import BaseNet_RMCR_fuseRMCR, CODONNet, CODONNet16, ops
     B, H, W = (a.batch // world if a.scaling == "strong" else a.batch), a.height, a.width
     selfcheck = None
-    if a.rccl_selfcheck == "on" or (a.rccl_selfcheck == "auto" and world > 1):
+    if a.rccl_selfcheck == "on" or (a.rccl_selfcheck == "auto" and world > 1 and a.full):
         # first contact with the multi-rank path: is the averaged gradient the single-process gradient?  (never fatal:
         # the line is still printed, with grad_equal false and the reason)
         from codon_amd.dist import grad_equality_selfcheck
@@ -820,9 +862,14 @@ def main():
         torch.cuda.synchronize(dev)
 
     if a.mode == "train":
+        last = {} if a.dump_outputs else None
         res = train_leg(model, x, y, dev, dist, rank, world, barrier, a.steps, a.warmup, a.dtype, a.scale, a.scaling,
-                        ctrl=ctrl, data=data)
+                        ctrl=ctrl, data=data, outputs=last)
         if rank == 0:
+            if last is not None:
+                written = dump_outputs(a.dump_outputs, last)
+                print(f"bench.py: outputs written to {a.dump_outputs}: {written}", file=sys.stderr)
+                del last
             for r_, st_, hw_ in zip(ranks, res["per_rank_step_ms"], res["per_rank_hwmon"]):
                 r_["train_step_ms"] = st_
                 r_["train_power_w_p50"], r_["train_sclk_mhz_p50"] = hw_["power_w_p50"], hw_["sclk_mhz_p50"]
@@ -862,6 +909,9 @@ def main():
         hw_fwd = hw.stop(single_rank=(world == 1))
         prof, ops.PROFILE = ops.PROFILE, None
     assert torch.isfinite(out).all()
+    if a.dump_outputs and rank == 0:
+        written = dump_outputs(a.dump_outputs, {"out": out})
+        print(f"bench.py: outputs written to {a.dump_outputs}: {written}", file=sys.stderr)
 
     dt = max_over_ranks(dt, dist, ctrl)
     fwd_per_rank = gather_rank_info(step_stats(step_ev), dist, rank, world, ctrl)   # a straggler GPU shows up per rank
@@ -914,9 +964,9 @@ def main():
                               "mpx_per_s": world * P / step_s / 1e6},
         }
         default_line = world == 1 and (B, H, W, a.scale) == (32, 480, 640, 4) and not bf16 and not split and not rmcr
-        if default_line and not a.no_strong_shards:
+        if default_line and a.full and not a.no_strong_shards:
             res["strong_shards"] = {"fwd_fp32": _optional("strong_shards.fwd_fp32", lambda: strong_shards_fwd(model, x, y, dev, step_s * 1e3))}
-        if world == 1 and not bf16 and not split and a.mode == "fwd" and not rmcr:
+        if a.full and world == 1 and not bf16 and not split and a.mode == "fwd" and not rmcr:
             # OPT-IN mode, reported beside (never instead of) the exact-fp32 headline: same inputs, same K steps
             model.set_conv_precision("f16x3")
             with torch.no_grad():
@@ -958,7 +1008,7 @@ def main():
                                      "frac_hbm_peak": el_ * esize * B * H * W / step_s_ / 1e9 / PEAK_HBM_GBS})
         res["config"]["workload"] = res["config"]["workload"].replace("CODON x", "BaseNet_RMCR_fuseRMCR (conv-only ablation, no CAC gates) x")
         res["metric"] = "HR depth maps/sec (fwd), conv-only ablation"
-    if not bf16 and not split and not a.no_fwd_bwd and not rmcr:
+    if a.full and not bf16 and not split and not a.no_fwd_bwd and not rmcr:
         # second half of the BASELINE metric, every rank takes part (the step holds the RCCL all-reduce): configs[2]'s
         # per-GPU shape -- same net, same batch/GPU and image size, bf16 activations, fp32 accumulate + master weights
         del out
@@ -1009,7 +1059,7 @@ def main():
                 r_["train_step_ms"] = st_
                 r_["train_power_w_p50"], r_["train_sclk_mhz_p50"] = hw_["power_w_p50"], hw_["sclk_mhz_p50"]
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = _optional("cpu_baseline", lambda: cpu_baseline(H, W))
             if not bf16 and not split and not rmcr:
                 res["config0_on_gpu"] = _optional("config0_on_gpu", lambda: config0_gpu_latency(dev))

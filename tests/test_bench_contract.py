@@ -24,7 +24,7 @@ def _run(args, timeout=600):
 
 @pytest.mark.gpu
 def test_bench_line_single_gpu_small_shape():
-    d = _run(["--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "96"])
+    d = _run(["--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "96", "--full"])
     assert REQUIRED <= set(d)
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert d["value"] > 0 and d["higher_is_better"] is True and d["data"] == "synthetic" and "workload" in d["config"]
@@ -40,7 +40,7 @@ def test_bench_line_single_gpu_small_shape():
 @pytest.mark.gpu
 def test_bench_self_launches_two_ranks():
     d = _run(["--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64",
-              "--width", "96"])
+              "--width", "96", "--full"])
     assert REQUIRED <= set(d) and d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["backend"] == "gloo"
     assert "cpu_baseline" not in d                      # rank 0 at N = 1 only
     assert d["grad_equal"] is True, d.get("rccl_selfcheck")
@@ -56,8 +56,8 @@ def test_bench_survives_an_rccl_that_cannot_form_a_communicator():
     to the gloo control group, and the line -- forward throughput, self-check, training leg -- is still printed."""
     env = dict(os.environ, CODON_BENCH_SHARE_GPU="1", CODON_RCCL_TIMEOUT_S="120")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "nccl", "--steps", "2",
-                        "--warmup", "1", "--batch", "2", "--height", "64", "--width", "96"], capture_output=True, text=True,
-                       timeout=900, env={k: v for k, v in env.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
+                        "--warmup", "1", "--batch", "2", "--height", "64", "--width", "96", "--full"], capture_output=True,
+                       text=True, timeout=900, env={k: v for k, v in env.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -82,7 +82,7 @@ def test_bench_under_the_drivers_torchrun_line():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend",
                         "gloo", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "96",
-                        "--no-fwd-bwd"], capture_output=True, text=True, timeout=600, env=env)
+                        "--no-fwd-bwd", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -98,7 +98,7 @@ def test_bench_four_ranks_strong_scaling_and_diagnostics():
     # (48 x 64: with 64 x 96 images this rehearsal runs in 6 s or, sporadically -- under pytest always --, in ~190 s: four processes
     # time-slicing one card, every rank waiting in the gradient all-reduce; profiles/r06_rehearsal_4rank_variants.txt)
     d = _run(["--gpus", "4", "--backend", "gloo", "--scaling", "strong", "--steps", "2", "--warmup", "1", "--batch", "8",
-              "--height", "48", "--width", "64"])
+              "--height", "48", "--width", "64", "--full"])
     assert d["n_gpus"] == 4 and d["scaling"] == "strong" and d["rccl_ranks"] == 4
     assert d["config"]["batch_per_gpu"] == 2 and d["config"]["global_batch"] == 8
     assert abs(d["value"] - 8 * d["steps"] / (d["ms_per_step"] * d["steps"] / 1e3)) / d["value"] < 1e-6
@@ -120,6 +120,50 @@ def test_bench_four_ranks_strong_scaling_and_diagnostics():
         assert r["train_step_ms"]["min_ms"] <= r["train_step_ms"]["median_ms"]
 
 
+SIDE_LEGS = {"fwd_bwd", "cpu_baseline", "optin_f16x3", "config0_on_gpu", "script_pattern_on_gpu", "strong_shards", "grad_equal",
+             "rccl_selfcheck"}
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_alone_and_dumps_the_last_steps_output(tmp_path):
+    """Without --full the run is set-up, warm-up, the K timed steps and the line; --dump-outputs writes the forward's output of
+    the last timed step, and two runs with the same arguments write the same array (seeded inputs, fixed-order kernels)."""
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "96"]
+    d = _run(args + ["--dump-outputs", str(tmp_path / "a")])
+    assert REQUIRED <= set(d) and not SIDE_LEGS & set(d), sorted(set(d))
+    assert d["steps"] == 3 and d["step_events"]["n"] == 3 and d["ms_per_step"] > 0 and d["metric"] == "HR depth maps/sec (fwd)"
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-6
+    out = np.load(tmp_path / "a" / "out.npy")
+    assert out.dtype == np.float32 and out.shape == (2, 1, 64, 96) and np.isfinite(out).all() and out.std() > 0
+    _run(args + ["--dump-outputs", str(tmp_path / "b")])
+    assert np.array_equal(out, np.load(tmp_path / "b" / "out.npy"))
+    t = _run(["--mode", "train", "--dtype", "bf16", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64",
+              "--width", "96", "--dump-outputs", str(tmp_path / "t")])
+    assert t["steps"] == 2 and t["step_events"]["n"] == 2
+    loss, o, p = (np.load(tmp_path / "t" / f"{n}.npy") for n in ("loss", "out", "params"))
+    assert loss.shape == (1,) and abs(float(loss[0]) - t["loss"]) < 1e-6 and o.shape == (2, 1, 64, 96)
+    assert p.dtype == np.float32 and p.size == 1866136 and np.isfinite(p).all()
+
+
+def test_dump_outputs_stays_within_its_budget_with_a_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    small, big = torch.arange(10, dtype=torch.bfloat16), torch.rand(3, 5000, dtype=torch.float64)
+    got = bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big})
+    assert got == {"small": [[10], False], "big": [[3, 5000], False]}
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy"), big.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40_000)
+    for sub in ("b", "c"):
+        got = bench.dump_outputs(str(tmp_path / sub), {"small": small, "big": big})
+        assert got["small"] == [[10], False] and got["big"][1] is True
+    b, c = (np.load(tmp_path / sub / "big.npy") for sub in ("b", "c"))
+    assert np.array_equal(b, c) and b.dtype == np.float32 and np.isin(b, big.float().numpy()).all()
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 40_000
+
+
 HW_KEYS = {"power_w_p50", "power_w_p95", "sclk_mhz_p50", "power_cap_w", "hwmon_samples", "hwmon_matched_by"}
 
 
@@ -131,7 +175,7 @@ def test_bench_six_ranks_weak_scaling_rehearsal_of_the_eight_gpu_line():
     rank's record carries its socket power and shader clock over the timed regions (hwmon), so that a node-level power
     budget on the 8-GPU node reads as eight lower clocks in SCALE_rNN.json rather than as an unexplained efficiency loss."""
     d = _run(["--gpus", "6", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", "1", "--height", "48",
-              "--width", "64"], timeout=900)
+              "--width", "64", "--full"], timeout=900)
     assert REQUIRED <= set(d) and d["n_gpus"] == 6 and d["rccl_ranks"] == 6 and d["scaling"] == "weak"
     assert d["config"]["batch_per_gpu"] == 1 and d["config"]["global_batch"] == 6
     assert abs(d["value"] - 6 * d["steps"] / (d["ms_per_step"] * d["steps"] / 1e3)) / d["value"] < 1e-6
@@ -150,7 +194,8 @@ def test_bench_six_ranks_weak_scaling_rehearsal_of_the_eight_gpu_line():
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line_carries_power_and_clock_and_the_profile_hash():
-    d = _run(["--steps", "3", "--warmup", "1", "--batch", "4", "--height", "96", "--width", "128", "--no-cpu-baseline"])
+    d = _run(["--steps", "3", "--warmup", "1", "--batch", "4", "--height", "96", "--width", "128", "--no-cpu-baseline",
+              "--full"])
     r0 = d["ranks"][0]
     assert HW_KEYS <= set(r0) and "train_power_w_p50" in r0
     if r0["hwmon_samples"]:                  # sysfs visible on this box: plausible numbers for an MI355X under load

@@ -104,21 +104,12 @@ def test_edited_attributes_are_caught_by_the_forward_audit():
         c.check_supported()
 
 
-REF = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the read-only reference tree (build container only)")
-def test_pickled_reference_module_with_other_pools_is_refused_at_the_audit(tmp_path):
+def test_pickled_reference_module_with_other_pools_is_refused_at_the_audit():
     """A whole-module pickle (test.py:56-59) bypasses the constructors: a reference CODONNet whose gate was configured with
     pool_types=['avg','max','lp'] unpickles into the compat classes and must be refused by the audit every forward runs;
-    the default reference module passes it."""
-    import subprocess
-    good, bad = str(tmp_path / "good.pth"), str(tmp_path / "bad.pth")
-    code = ("import sys; sys.dont_write_bytecode = True; import torch; import CODON_x4; m = CODON_x4.CODONNet(); "
-            f"torch.save({{'epoch': 1, 'model': m}}, {good!r}); m.attention_c2.pool_types = ['avg', 'max', 'lp']; "
-            f"torch.save({{'epoch': 1, 'model': m}}, {bad!r})")
-    subprocess.run([sys.executable, "-c", code], check=True, cwd=os.path.join(REF, "CODON_X4"), timeout=300,
-                   env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
+    the default reference module passes it.  Both pickles were saved by the imported reference (tools/make_golden_refckpt.py)."""
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    good, bad = os.path.join(gold, "refckpt_CODON_x4.pth"), os.path.join(gold, "refckpt_CODON_x4_lp_pools.pth")
     compat = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "codon_amd", "compat")
     sys.path.insert(0, compat)
     try:

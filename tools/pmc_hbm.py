@@ -1,9 +1,9 @@
 """Post-process two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; separate runs of the same bench command, as
 MI355X_MICROARCH.md's HBM section prescribes) into profiles/rNN_*_pmc_hbm.json: HBM bytes per launch per kernel.
 
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
-  python tools/pmc_hbm.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/r01_fwd_b32_480x640_pmc_hbm.json
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d OUT/pmc_fetch -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d OUT/pmc_write -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
+  python tools/pmc_hbm.py OUT/pmc_fetch OUT/pmc_write profiles/r01_fwd_b32_480x640_pmc_hbm.json
 
 gfx950 corrections: FETCH_SIZE and WRITE_SIZE are reported in KiB-like units of 1024 B? -- no: rocprofv3 reports both
 in KB (x1024 to bytes); FETCH_SIZE tallies 128-B requests at 64 B, so it is doubled; WRITE_SIZE is exact.  The
@@ -46,7 +46,7 @@ def main():
                  "avg_ms_write_pass": (wr[k][2] / max(wr[k][0], 1) / 1e6) if k in wr else None,
                  "fetch_bytes_corrected": fb, "write_bytes": wb, "hbm_bytes_per_launch": fb + wb}
     doc = {"command": "rocprofv3 --kernel-trace --pmc {FETCH_SIZE|WRITE_SIZE} --output-format csv -- python3 bench.py "
-                      "--steps 1 --warmup 0 --no-cpu-baseline",
+                      "--full --steps 1 --warmup 0 --no-cpu-baseline",
            "note": "FETCH_SIZE on gfx950 counts 128-B requests at 64 B (MI355X_MICROARCH.md, HBM section): corrected x2; "
                    "WRITE_SIZE exact.  Per launch = counter summed over launches / launches.",
            "kernels": ks}

@@ -5,7 +5,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-base = ["--gpus", "4", "--backend", "gloo", "--steps", "2", "--warmup", "1"]
+base = ["--gpus", "4", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--full"]
 variants = {
     "strong b8 64x96": ["--scaling", "strong", "--batch", "8", "--height", "64", "--width", "96"],
     "strong b4 48x64": ["--scaling", "strong", "--batch", "4", "--height", "48", "--width", "64"],

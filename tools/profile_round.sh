@@ -11,7 +11,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py"
+B="python3 $ROOT/bench.py --full"
 run() {   # run <name> <bench args...>: JSON line -> <tag>_<name>.json, stderr -> <tag>_<name>.err
   local name=$1; shift
   echo "== $name"; $B "$@" > $OUT/${tag}_${name}.json 2> $OUT/${tag}_${name}.err
@@ -22,17 +22,17 @@ pmc3() {  # pmc3 <label> <out.json> <mode> <esize> <bench args...>: FETCH / WRIT
   local shape=${PMC_SHAPE:-32 480 640}
   for c in FETCH_SIZE WRITE_SIZE; do
     echo "== $label: pmc $c"
-    rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/${tag}_${label}_$c -- python3 $ROOT/bench.py "$@" --steps 1 --warmup 0 > $OUT/${tag}_${label}_$c.log 2>&1
+    rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/${tag}_${label}_$c -- python3 $ROOT/bench.py --full "$@" --steps 1 --warmup 0 > $OUT/${tag}_${label}_$c.log 2>&1
   done
   echo "== $label: pmc clock + matrix-pipe busy"
-  rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $OUT/${tag}_${label}_busy -- python3 $ROOT/bench.py "$@" --steps 1 --warmup 0 > $OUT/${tag}_${label}_busy.log 2>&1
+  rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $OUT/${tag}_${label}_busy -- python3 $ROOT/bench.py --full "$@" --steps 1 --warmup 0 > $OUT/${tag}_${label}_busy.log 2>&1
   python3 $ROOT/tools/pmc_report.py $OUT/${tag}_${label}_FETCH_SIZE $OUT/${tag}_${label}_WRITE_SIZE $OUT/${tag}_${label}_busy $OUT/$out $shape $mode $es | tee $OUT/${tag}_${label}_pmc.txt
   find $OUT/${tag}_${label}_FETCH_SIZE $OUT/${tag}_${label}_WRITE_SIZE $OUT/${tag}_${label}_busy -name "*.csv" -size +8M -delete
 }
 trace() { # trace <label> <stats.csv name> <bench args...>
   local label=$1 out=$2; shift 2
   echo "== $label: kernel trace"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${tag}_${label}_trace -- python3 $ROOT/bench.py "$@" > $OUT/${tag}_${label}_trace.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${tag}_${label}_trace -- python3 $ROOT/bench.py --full "$@" > $OUT/${tag}_${label}_trace.log 2>&1
   f=$(find $OUT/${tag}_${label}_trace -name "*kernel_stats.csv" | head -1); test -n "$f"; cp "$f" $OUT/$out
   find $OUT/${tag}_${label}_trace -name "*kernel_trace.csv" -delete
 }
