@@ -57,6 +57,18 @@ class AdamDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("param", C.c_void_p * ADAM_MAX), ("count", C.c_int64 * ADAM_MAX)]
 
 
+TRAIN_MAX_BATCH = 64                                # CODON_TRAIN_MAX_BATCH
+
+
+class CropSample(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("height", C.c_int32), ("width", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32),
+                ("op", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CropDesc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("crop", C.c_int32), ("s", CropSample * TRAIN_MAX_BATCH)]
+
+
 class CastDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("src", C.c_void_p * CAST_MAX), ("count", C.c_int64 * CAST_MAX),
                 ("dtype", C.c_int32 * CAST_MAX)]
@@ -131,6 +143,9 @@ SIGNATURES = {
     "codon_cast_multi": (C.c_int, [C.POINTER(CastDesc), _P, _P]),
     "codon_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),
     "codon_reduce_multi": (C.c_int, [C.POINTER(ReduceItem), _I, _P]),
+    "codon_train_crops": (C.c_int, [C.POINTER(CropDesc), _P, C.c_int64, _P, _P, _P, _P]),
+    "codon_bicubic_downsample": (C.c_int, [_I, _I, _I, _P, _P, _P, _P]),
+    "codon_quantize_u8": (C.c_int, [C.c_int64, _P, _P, _P]),
     "codon_weight_checksum_workspace_bytes": (_S, []),
     "codon_weight_checksum": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P]),
 }

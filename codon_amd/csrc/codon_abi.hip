@@ -112,6 +112,9 @@ int ssim_l1_bwd(int, int, int, const float*, const float*, const float*, float*,
 int reduce_multi(const codon_reduce_item*, int, hipStream_t);
 int cast_multi(const codon_cast_desc*, float*, hipStream_t);
 int adam_step(const codon_adam_desc*, const float*, float*, float*, float, float, float, float, float, int, hipStream_t);
+int train_crops(const codon_crop_desc*, const unsigned char*, const float*, float*, float*, hipStream_t);
+int bicubic_downsample(int, int, int, const float*, const float*, float*, hipStream_t);
+int quantize_u8(long, float*, const float*, hipStream_t);
 size_t weight_checksum_workspace_bytes();
 int weight_checksum(const codon_wsum_desc*, void*, unsigned long long*, int, int*, hipStream_t);
 
@@ -763,6 +766,40 @@ int codon_bicubic_upsample(int32_t batch, int32_t lr_height, int32_t lr_width, i
   CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "bicubic_upsample: scale %d", scale);
   CODON_REQUIRE(shape_ok(batch, lr_height * scale, lr_width * scale), CODON_ERR_BAD_ARG, "bicubic_upsample: bad shape");
   return bicubic_upsample(batch, lr_height, lr_width, scale, lr, phase_weights, out, (hipStream_t)stream);
+}
+
+int codon_train_crops(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, const float* lut, float* target,
+                      float* guide, codon_stream_t stream) {
+  CODON_REQUIRE(desc && pool && lut && target && guide, CODON_ERR_BAD_ARG, "train_crops: null pointer");
+  CODON_REQUIRE(desc->n >= 1 && desc->n <= CODON_TRAIN_MAX_BATCH, CODON_ERR_BAD_ARG, "train_crops: batch %d (1..%d)", desc->n,
+                CODON_TRAIN_MAX_BATCH);
+  const int P = desc->crop;
+  CODON_REQUIRE(P >= 1 && P <= 2048, CODON_ERR_BAD_ARG, "train_crops: crop %d (1..2048)", P);
+  for (int b = 0; b < desc->n; ++b) {
+    const codon_crop_sample& c = desc->s[b];
+    CODON_REQUIRE(c.height >= P && c.width >= P && c.y0 >= 0 && c.x0 >= 0 && c.y0 <= c.height - P && c.x0 <= c.width - P &&
+                      c.op >= 0 && c.op <= 7,
+                  CODON_ERR_BAD_ARG, "train_crops: sample %d: %dx%d crop at (%d, %d) op %d outside the image", b, c.height,
+                  c.width, c.y0, c.x0, c.op);
+    CODON_REQUIRE(c.offset >= 0 && c.offset <= pool_bytes - 2 * (int64_t)c.height * c.width, CODON_ERR_BAD_ARG,
+                  "train_crops: sample %d: images at offset %lld run past the %lld-byte pool", b, (long long)c.offset,
+                  (long long)pool_bytes);
+  }
+  return train_crops(desc, pool, lut, target, guide, (hipStream_t)stream);
+}
+
+int codon_bicubic_downsample(int32_t batch, int32_t size, int32_t scale, const float* hr, const float* weights, float* out,
+                             codon_stream_t stream) {
+  CODON_REQUIRE(hr && weights && out, CODON_ERR_BAD_ARG, "bicubic_downsample: null pointer");
+  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "bicubic_downsample: scale %d", scale);
+  CODON_REQUIRE(batch >= 1 && batch < 65536 && size >= 4 * scale && size <= 2048 && size % scale == 0, CODON_ERR_BAD_ARG,
+                "bicubic_downsample: batch %d, size %d at scale %d", batch, size, scale);
+  return bicubic_downsample(batch, size, scale, hr, weights, out, (hipStream_t)stream);
+}
+
+int codon_quantize_u8(int64_t n, float* x, const float* lut, codon_stream_t stream) {
+  CODON_REQUIRE(x && lut && n >= 1, CODON_ERR_BAD_ARG, "quantize_u8: null pointer or empty");
+  return quantize_u8((long)n, x, lut, (hipStream_t)stream);
 }
 
 size_t codon_weight_checksum_workspace_bytes(void) { return weight_checksum_workspace_bytes(); }

@@ -169,6 +169,25 @@ class FlatAdam:
         for p in gs.params:                        # written through raw pointers: make the new values visible to version keys
             torch.autograd.graph.increment_version(p)
 
+    def state_dict(self) -> dict:
+        """The moments (host copies), the step count and the hyper-parameters: what a resumed run needs to continue bit for
+        bit (codon_amd.train checkpoints)."""
+        return {"exp_avg": self.exp_avg.detach().cpu().clone(), "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(),
+                "t": int(self.t), "lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay}
+
+    def load_state_dict(self, state: dict):
+        """Inverse of state_dict(); refuses moments whose flat length is not this GradSync's."""
+        for k in ("exp_avg", "exp_avg_sq"):
+            v = state[k]
+            if not isinstance(v, torch.Tensor) or v.dim() != 1 or v.numel() != self.gs.numel:
+                raise ValueError(f"FlatAdam.load_state_dict: {k} has {getattr(v, 'shape', None)} values, the GradSync holds "
+                                 f"{self.gs.numel}")
+        self.exp_avg.copy_(state["exp_avg"])
+        self.exp_avg_sq.copy_(state["exp_avg_sq"])
+        self.t = int(state["t"])
+        self.lr, self.eps, self.weight_decay = float(state["lr"]), float(state["eps"]), float(state["weight_decay"])
+        self.betas = (float(state["betas"][0]), float(state["betas"][1]))
+
 
 def shard_batch(n_images: int, rank: int, world: int):
     """Contiguous, balanced image range of `rank` (units = images; no image is split)."""

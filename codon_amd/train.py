@@ -1,0 +1,375 @@
+"""python -m codon_amd.train -- fine-tune CODONNet on a directory of depth maps and grey guidance images.
+
+The reference ships only a test script and weights; its depth inputs were degraded offline (bicubic down, bicubic up, saved
+as 8-bit PNGs: the reference's CODON_X4/test.py:70-79,116-123) by a script it does not ship.  Here every training batch is
+built ON THE DEVICE from HR depth maps and guidance images uploaded once (codon_amd/csrc/train_data.hip):
+    random crop + D4 op (crop, u8 -> fp32)  ->  antialiased bicubic x1/s  ->  bicubic xs (upsample.hip)  ->  8-bit quantise
+The degradation is a definition of this project, NOT pinned to the reference (its script is not shipped); it is restated in
+numpy in tests/train_data_ref.py and the two agree bit for bit.
+
+One step: GradSync.zero_grad -> synthesize -> forward -> L1SSIMLoss(out.float(), t) -> GradSync.backward ->
+all_reduce_grads -> FlatAdam.step, the sequence of bench.py's training leg.  Under torchrun every rank draws the whole
+global batch from the same seeded generator and keeps its shard (codon_amd.dist.shard_batch); the loss is read back on log
+steps only.  Checkpoints are {"epoch": step, "model", "optimizer", "rng", "args"}: io.load_checkpoint and
+`python -m codon_amd.infer --weights` read them as they are, and --resume continues a run bit for bit.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import functools
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import CODONNet, CODONNet16, io
+from . import _lib as L
+from . import ops
+from .upsample import _keys, phase_weights
+
+DTYPES = {"bf16": torch.bfloat16, "f32": None}
+RESUME_KEYS = ("scale", "crop", "batch", "dtype")
+
+
+# ---- the degradation's host-side tables -------------------------------------------------------------------------------------
+
+def u8_lut() -> np.ndarray:
+    """256 fp32 values: io.to_input's conversion of every code (float64 divide by 255, then float32)."""
+    return (np.arange(256, dtype=np.float64) / 255).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def down_weights(size: int, scale: int) -> np.ndarray:
+    """(size/scale, 4*scale) fp32: row o weighs input taps i = o*scale - 3*scale/2 + k (PIL's BICUBIC reduce: Keys a = -0.5
+    stretched by scale, centre (o + 0.5) * scale, tap weight k((i + 0.5 - centre) / scale); taps outside [0, size) get 0 and
+    the rest are renormalised).  fp64, rounded once to fp32."""
+    p, taps = size // scale, 4 * scale
+    tab = np.zeros((p, taps), dtype=np.float64)
+    for o in range(p):
+        c = (o + 0.5) * scale
+        for k in range(taps):
+            i = o * scale - 3 * scale // 2 + k
+            if 0 <= i < size:
+                tab[o, k] = _keys((i + 0.5 - c) / scale, a=-0.5)
+        tab[o] /= tab[o].sum()
+    return tab.astype(np.float32)
+
+
+_dev_tabs: dict = {}
+
+
+def _on_device(key, make, dev):
+    k = (key, str(dev))
+    t = _dev_tabs.get(k)
+    if t is None:
+        t = _dev_tabs[k] = torch.from_numpy(np.ascontiguousarray(make())).to(dev)
+    return t
+
+
+# ---- the dataset --------------------------------------------------------------------------------------------------------------
+
+class TrainSet:
+    """Every (depth, guidance) pair of two directories, paired by file name (infer.list_pairs), read with io.read_gray and
+    cropped to their common size (as infer._load_host does), in ONE flat uint8 pool on `device`: pair i's depth map at
+    offsets[i], its guidance right behind it.  Uploaded once; a step reads nothing from the host.  `crop`: refuse images
+    smaller than it."""
+
+    def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None):
+        from .infer import list_pairs
+        self.files = list_pairs(depth_dir, color_dir)
+        if not self.files:
+            raise ValueError(f"TrainSet: no file of {color_dir} has a namesake in {depth_dir}")
+        chunks, offsets, sizes, off = [], [], [], 0
+        for f in self.files:
+            d = io.read_gray(os.path.join(depth_dir, f))
+            g = io.read_gray(os.path.join(color_dir, f))
+            h, w = min(d.shape[0], g.shape[0]), min(d.shape[1], g.shape[1])
+            if crop is not None and (h < crop or w < crop):
+                raise ValueError(f"TrainSet: {f} is {h}x{w}, smaller than the {crop}x{crop} crop")
+            chunks += [np.ascontiguousarray(d[:h, :w]).reshape(-1), np.ascontiguousarray(g[:h, :w]).reshape(-1)]
+            offsets.append(off)
+            sizes.append((h, w))
+            off += 2 * h * w
+        self.offsets = np.asarray(offsets, dtype=np.int64)
+        self.sizes = np.asarray(sizes, dtype=np.int64)
+        self.pool = torch.from_numpy(np.concatenate(chunks)).to(device)
+
+    def __len__(self):
+        return len(self.files)
+
+
+def draw(rng: np.random.Generator, trainset: TrainSet, batch: int, crop: int, rank: int = 0, world: int = 1) -> np.ndarray:
+    """This rank's share of one global batch: (batch/world, 6) int64 rows (pool offset, H, W, y0, x0, D4 op).  Every rank
+    draws the WHOLE batch (the generators stay in step) and keeps shard_batch(batch, rank, world)."""
+    from .dist import shard_batch
+    if batch < 1 or world < 1 or batch % world:
+        raise ValueError(f"draw: a batch of {batch} does not split evenly over {world} ranks")
+    if crop < 1 or (trainset.sizes < crop).any():
+        raise ValueError(f"draw: crop {crop} does not fit the smallest image "
+                         f"({int(trainset.sizes[:, 0].min())}x{int(trainset.sizes[:, 1].min())})")
+    idx = rng.integers(0, len(trainset.offsets), size=batch)
+    hw = trainset.sizes[idx]
+    y0 = rng.integers(0, hw[:, 0] - crop + 1)
+    x0 = rng.integers(0, hw[:, 1] - crop + 1)
+    op = rng.integers(0, 8, size=batch)
+    d = np.stack([trainset.offsets[idx], hw[:, 0], hw[:, 1], y0, x0, op], axis=1).astype(np.int64)
+    lo, hi = shard_batch(batch, rank, world)
+    return d[lo:hi]
+
+
+def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int):
+    """(x, y, t), each (B,1,crop,crop) fp32 on the pool's device: the network's depth input (crop -> bicubic down by `scale`
+    -> bicubic up -> 8-bit), the guidance and the HR target.  Four launches on the caller's stream, no host synchronisation."""
+    lib = L.load()
+    B = len(descs)
+    if not 1 <= B <= L.TRAIN_MAX_BATCH:
+        raise ValueError(f"synthesize: {B} samples per launch (1..{L.TRAIN_MAX_BATCH})")
+    if crop % scale or crop // scale < 4:
+        raise ValueError(f"synthesize: crop {crop} must be a multiple of the scale {scale} and at least 4 * scale")
+    dev = trainset.pool.device
+    d = L.CropDesc()
+    d.n, d.crop = B, crop
+    for b, (off, h, w, y0, x0, op) in enumerate(np.asarray(descs, dtype=np.int64).tolist()):
+        s = d.s[b]
+        s.offset, s.height, s.width, s.y0, s.x0, s.op = off, h, w, y0, x0, op
+    lut = _on_device("lut", u8_lut, dev)
+    wdown = _on_device(("down", crop, scale), lambda: down_weights(crop, scale), dev)
+    wup = _on_device(("up", scale), lambda: phase_weights(scale), dev)
+    p = crop // scale
+    t = torch.empty((B, 1, crop, crop), dtype=torch.float32, device=dev)
+    y = torch.empty_like(t)
+    lr = torch.empty((B, 1, p, p), dtype=torch.float32, device=dev)
+    x = torch.empty_like(t)
+    P_ = C.c_void_p
+    with ops._on(dev):
+        st = ops._stream(dev)
+        L.check(lib.codon_train_crops(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(), P_(lut.data_ptr()),
+                                      P_(t.data_ptr()), P_(y.data_ptr()), st), "train_crops")
+        L.check(lib.codon_bicubic_downsample(B, crop, scale, P_(t.data_ptr()), P_(wdown.data_ptr()), P_(lr.data_ptr()), st),
+                "bicubic_downsample")
+        L.check(lib.codon_bicubic_upsample(B, p, p, scale, P_(lr.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()), st),
+                "bicubic_upsample")
+        L.check(lib.codon_quantize_u8(x.numel(), P_(x.data_ptr()), P_(lut.data_ptr()), st), "quantize_u8")
+    return x, y, t
+
+
+# ---- training -----------------------------------------------------------------------------------------------------------------
+
+def _world(group):
+    import torch.distributed as dist
+    if not dist.is_initialized():
+        return 0, 1
+    return dist.get_rank(group), dist.get_world_size(group)
+
+
+def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, args: dict):
+    """Atomically (tmp file, then os.replace): a reader never sees half a checkpoint."""
+    ck = {"epoch": int(step), "model": {k: v.detach().cpu() for k, v in model.state_dict().items()},
+          "optimizer": opt.state_dict(), "rng": rng.bit_generator.state, "args": dict(args)}
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    tmp = f"{path}.tmp{os.getpid()}"
+    torch.save(ck, tmp)
+    os.replace(tmp, path)
+
+
+def load_resume(path: str, args: dict) -> dict:
+    """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype."""
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    if not isinstance(ck, dict) or not all(k in ck for k in ("epoch", "model", "optimizer", "rng", "args")):
+        raise ValueError(f"--resume {path}: not a codon_amd.train checkpoint (use --weights to start from other weights)")
+    bad = [f"{k} {ck['args'].get(k)!r} != {args.get(k)!r}" for k in RESUME_KEYS if ck["args"].get(k) != args.get(k)]
+    if bad:
+        raise ValueError(f"--resume {path}: the checkpoint was trained with other arguments: {', '.join(bad)}")
+    return ck
+
+
+def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, batch: int = 16, lr: float = 1e-4,
+        dtype: str = "bf16", rng: np.random.Generator = None, seed: int = 0, log_every: int = 10, process_group=None,
+        val: dict = None, ckpt: dict = None, start_step: int = 0, opt_state: dict = None, fixed: np.ndarray = None,
+        args: dict = None, time_synth: bool = False, emit=print) -> dict:
+    """Train `model` (fp32 parameters on the pool's device) from step start_step + 1 to step `steps`.
+    val:   {"depth", "color", "label", "every"} -- rank 0 runs infer.run_loop every `every` steps and prints the means;
+    ckpt:  {"path", "every"} -- rank 0 saves every `every` steps and after the last one;
+    fixed: descriptors (draw's rows of this rank) used for EVERY step instead of drawing (overfit checks);
+    time_synth: HIP events around synthesize and around each whole step (result["synth_ms"], ["step_ms"]).
+    Returns {"losses": [(step, loss)], "gs", "opt", "rng", "step", ...}."""
+    from .dist import FlatAdam, GradSync
+    from .metrics import L1SSIMLoss
+    if dtype not in DTYPES:
+        raise ValueError(f"fit: dtype {dtype!r} (training runs in {', '.join(DTYPES)}; fp16 is inference-only)")
+    rank, world = _world(process_group)
+    if batch % world:
+        raise ValueError(f"fit: a batch of {batch} does not split evenly over {world} ranks")
+    rng = np.random.default_rng(seed) if rng is None else rng
+    dev = trainset.pool.device
+    model.set_compute_dtype(DTYPES[dtype])
+    model.train()
+    gs = GradSync(model, process_group=process_group)
+    gs.broadcast_parameters(0)
+    opt = FlatAdam(gs, lr=lr)
+    if opt_state is not None:
+        opt.load_state_dict(opt_state)
+    crit = L1SSIMLoss(1.0, 1.0)
+    args = dict(args or {}, scale=scale, crop=crop, batch=batch, dtype=dtype)
+    stream = torch.cuda.current_stream(dev)
+    losses, val_log, ev = [], [], []
+    t_log, s_log = time.perf_counter(), start_step
+    step = start_step
+    for step in range(start_step + 1, steps + 1):
+        descs = fixed if fixed is not None else draw(rng, trainset, batch, crop, rank, world)
+        if time_synth:
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            e[0].record(stream)
+        gs.zero_grad()
+        if time_synth:
+            e[1].record(stream)
+        x, y, t = synthesize(trainset, descs, scale, crop)
+        if time_synth:
+            e[2].record(stream)
+        out = model(x, y)
+        loss = crit(out.float(), t)
+        gs.backward(loss)
+        gs.all_reduce_grads()
+        opt.step()
+        if time_synth:
+            e[3].record(stream)
+            ev.append(e)
+        if step % log_every == 0 or step == steps:
+            lv = loss.detach().double().reshape(1)
+            if world > 1:
+                import torch.distributed as dist
+                if dist.get_backend(process_group) == "gloo":
+                    lv = lv.cpu()
+                dist.all_reduce(lv, op=dist.ReduceOp.SUM, group=process_group)
+                lv = lv / world                     # equal shards: the mean of the shard losses is the batch loss
+            lv = float(lv.item())
+            now = time.perf_counter()
+            sps = (step - s_log) / (now - t_log)
+            t_log, s_log = now, step
+            losses.append((step, lv))
+            if rank == 0:
+                emit(f"step {step} loss {lv:.6f} steps/s {sps:.2f} images/s {sps * batch:.1f}")
+        if val and rank == 0 and step % val["every"] == 0:
+            val_log.append((step, validate(model, dev, val, emit)))
+            t_log = time.perf_counter()             # validation time is not training time
+        if ckpt and rank == 0 and (step % ckpt["every"] == 0 or step == steps):
+            save_checkpoint(ckpt["path"], step, model, opt, rng, args)
+    res = {"losses": losses, "val": val_log, "gs": gs, "opt": opt, "rng": rng, "step": step, "rank": rank, "world": world}
+    if time_synth and ev:
+        torch.cuda.synchronize(dev)
+        res["synth_ms"] = [e[1].elapsed_time(e[2]) for e in ev]
+        res["step_ms"] = [e[0].elapsed_time(e[3]) for e in ev]
+    return res
+
+
+def validate(model, dev, val: dict, emit=print) -> dict:
+    """infer.run_loop over the validation set in eval mode at the training compute dtype; prints the mean masked RMSE and
+    SSIM (the numbers the reference's test.py prints), then returns the model to train()."""
+    from .infer import run_loop
+    model.eval()
+    try:
+        with torch.no_grad():
+            r = run_loop(model, dev, torch.float32, val["depth"], val["color"], val.get("label"), emit=lambda s: None)
+    finally:
+        model.train()
+    emit(f"val {r['n']} images rmse {r['rmse_mean']} ssim {r['ssim_mean']}")
+    return r
+
+
+# ---- the command line ---------------------------------------------------------------------------------------------------------
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--scale", type=int, required=True, choices=[4, 8, 16])
+    ap.add_argument("--train-depth", required=True, help="HR depth maps (PNG, 8-bit)")
+    ap.add_argument("--train-color", required=True, help="guidance images, paired with the depth maps by file name")
+    ap.add_argument("--crop", type=int, default=128)
+    ap.add_argument("--batch", type=int, default=16, help="global batch (split over the ranks under torchrun)")
+    ap.add_argument("--steps", type=int, default=1000, help="total steps (a resumed run continues up to this step)")
+    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "f16"], help="f16 is refused: inference-only")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--log-every", type=int, default=10)
+    ap.add_argument("--save", default=None)
+    ap.add_argument("--save-every", type=int, default=1000)
+    ap.add_argument("--resume", default=None,
+                    help="a checkpoint of this script: model, optimizer (its lr included) and generator state")
+    ap.add_argument("--weights", default=None, help="initial weights: any checkpoint io.load_checkpoint reads")
+    ap.add_argument("--val-depth", default=None)
+    ap.add_argument("--val-color", default=None)
+    ap.add_argument("--val-label", default=None)
+    ap.add_argument("--val-every", type=int, default=1000)
+    ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
+    a = ap.parse_args(argv)
+    if a.dtype == "f16":
+        ap.error("--dtype f16: fp16 training is not supported (inference-only, as in the reference); use bf16 or f32")
+    if a.crop % a.scale or a.crop // a.scale < 4:
+        ap.error(f"--crop {a.crop} must be a multiple of --scale {a.scale} and at least 4 * scale")
+    if a.batch < 1 or a.steps < 1 or a.log_every < 1 or a.save_every < 1 or a.val_every < 1:
+        ap.error("--batch, --steps, --log-every, --save-every and --val-every must be positive")
+    if a.resume and a.weights:
+        ap.error("--resume and --weights exclude each other")
+    if (a.val_depth is None) != (a.val_color is None):
+        ap.error("--val-depth and --val-color go together")
+    return a
+
+
+def run_args(a) -> dict:
+    return {"scale": a.scale, "crop": a.crop, "batch": a.batch, "dtype": a.dtype, "lr": a.lr, "seed": a.seed}
+
+
+def main(argv=None, emit=print) -> dict:
+    a = parse_args(argv)
+    args = run_args(a)
+    resume = load_resume(a.resume, args) if a.resume else None     # refused before any GPU work
+    import torch.distributed as dist
+    group = None
+    if "RANK" in os.environ and "WORLD_SIZE" in os.environ and not dist.is_initialized():
+        local = int(os.environ.get("LOCAL_RANK", "0"))
+        torch.cuda.set_device(local)
+        dist.init_process_group(a.dist_backend)
+    if not torch.cuda.is_available():
+        raise SystemExit("No GPU found, codon_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rank, world = _world(group)
+    if a.batch % world:
+        raise SystemExit(f"--batch {a.batch} does not split evenly over {world} ranks")
+    if a.batch // world > L.TRAIN_MAX_BATCH:
+        raise SystemExit(f"--batch {a.batch}: at most {L.TRAIN_MAX_BATCH} images per rank")
+    ts = TrainSet(a.train_depth, a.train_color, dev, crop=a.crop)
+    torch.manual_seed(a.seed)
+    model = (CODONNet16 if a.scale == 16 else CODONNet)()
+    rng = np.random.default_rng(a.seed)
+    start, opt_state = 0, None
+    if resume is not None:
+        model.load_state_dict(resume["model"], strict=True)
+        rng.bit_generator.state = resume["rng"]
+        start, opt_state = int(resume["epoch"]), resume["optimizer"]
+        if rank == 0:
+            emit(f"resumed {a.resume} at step {start}")
+    elif a.weights:
+        ep = io.load_checkpoint(a.weights, model)
+        if rank == 0:
+            emit(f"loaded {a.weights} (epoch {ep})")
+    model = model.to(dev)
+    if rank == 0:
+        emit(f"{len(ts)} training pairs, x{a.scale}, crop {a.crop}, batch {a.batch} over {world} rank(s), {a.dtype}, "
+             f"steps {start + 1}..{a.steps}")
+    val = ({"depth": a.val_depth, "color": a.val_color, "label": a.val_label, "every": a.val_every}
+           if a.val_depth else None)
+    ckpt = {"path": a.save, "every": a.save_every} if a.save else None
+    res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,
+              log_every=a.log_every, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,
+              args=args, emit=emit)
+    res["model"] = model
+    return res
+
+
+if __name__ == "__main__":
+    main()
+    import torch.distributed as _dist
+    if _dist.is_initialized():
+        _dist.destroy_process_group()

@@ -510,6 +510,41 @@ typedef struct codon_adam_desc {
 int codon_adam_step(const codon_adam_desc* desc, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int32_t step, codon_stream_t stream);
 
+/* ---- training-batch synthesis (codon_amd.train) -------------------------------------------------------------------------
+ * No reference counterpart: the reference ships no training code and its depth inputs were degraded offline (bicubic down,
+ * bicubic up, 8-bit PNG: CODON_X4/test.py:70-79,116-123) by a script it does not ship -- this pipeline is a DEFINITION, not
+ * pinned to the reference.  Defined in codon_amd/csrc/train_data.hip, restated in numpy in tests/train_data_ref.py, required
+ * to agree bit for bit.
+ *
+ * codon_train_crops: one launch for a batch of n <= CODON_TRAIN_MAX_BATCH samples of one crop size P.  `pool` is a flat u8
+ * buffer of pool_bytes bytes; sample b's HR depth map (height x width, row-major) starts at s[b].offset and its grey guidance
+ * image of the same size follows at s[b].offset + height * width.  The P x P window at (y0, x0) of both is taken through the
+ * D4 op s[b].op (numpy: c = img[y0:y0+P, x0:x0+P]; op&1: c = c.T; op&2: c = c[::-1]; op&4: c = c[:, ::-1]) and written as
+ * lut[u8] (a 256-entry fp32 table, device memory) to target and guide, (n,1,P,P) fp32 each.  Every window must lie inside
+ * its image and every image inside the pool. */
+#define CODON_TRAIN_MAX_BATCH 64
+typedef struct codon_crop_sample {
+  int64_t offset;
+  int32_t height, width, y0, x0, op, reserved;
+} codon_crop_sample;
+typedef struct codon_crop_desc {
+  int32_t n;
+  int32_t crop;
+  codon_crop_sample s[CODON_TRAIN_MAX_BATCH];
+} codon_crop_desc;
+int codon_train_crops(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, const float* lut, float* target,
+                      float* guide, codon_stream_t stream);
+/* codon_bicubic_downsample: antialiased integer-factor reduction (PIL BICUBIC reduce; F.interpolate(mode="bicubic",
+ * antialias=True, align_corners=False)) of hr (batch,1,size,size) fp32 by scale 4 / 8 / 16 to out (batch,1,size/scale,
+ * size/scale).  weights: (size/scale) x (4*scale) fp32 -- row o holds the weights of input taps o*scale - 3*scale/2 + k,
+ * k = 0 .. 4*scale-1 (taps outside the image: weight 0).  A horizontal pass, then a vertical pass, each a sequential fp32 sum
+ * over k with an fp32 intermediate.  size % scale == 0, size / scale >= 4, size <= 2048. */
+int codon_bicubic_downsample(int32_t batch, int32_t size, int32_t scale, const float* hr, const float* weights, float* out,
+                             codon_stream_t stream);
+/* codon_quantize_u8: in place, x[i] = lut[rint(clamp(x[i], 0, 1) * 255f)] (round half to even): the 8-bit PNG the network's
+ * depth input is read from at test time. */
+int codon_quantize_u8(int64_t n, float* x, const float* lut, codon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
