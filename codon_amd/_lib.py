@@ -21,6 +21,7 @@ F32, BF16, F16 = 0, 1, 2
 CONV_RELU, CONV_ADD_RESIDUAL, CONV_ACCUM_OUT, CONV_MASK_RELU, CONV_F16X3, CONV_MASK_SUM = 1, 2, 4, 8, 16, 32
 PACK_FWD, PACK_DGRAD, PACK_FWD_F16X3, PACK_CHAIN1X1, PACK_CHAIN1X1_F16X3 = 0, 1, 2, 3, 4
 TILING_8X32, TILING_4X32, TILING_4X32_SOLO, TILING_2X32_COUT_SPLIT = 0, 1, 2, 3      # codon_conv_tiling_f32
+C8_FORM_STAGED, C8_FORM_RESIDENT = 0, 1                                             # codon_conv_form_c8
 CAC_FOLDS = 16   # CODON_CAC_FOLDS
 
 
@@ -140,6 +141,7 @@ SIGNATURES = {
     "codon_conv_pair_begin": (C.c_int, []),
     "codon_conv_pair_end": (C.c_int, [_P]),
     "codon_conv_tiling_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int]),
+    "codon_conv_form_c8": (C.c_int, [C.POINTER(ConvDesc)]),
     "codon_cast_multi": (C.c_int, [C.POINTER(CastDesc), _P, _P]),
     "codon_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),
     "codon_reduce_multi": (C.c_int, [C.POINTER(ReduceItem), _I, _P]),

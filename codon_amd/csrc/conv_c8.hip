@@ -973,6 +973,17 @@ static int c8_resident_blocks(K kernel, int threads) {
 // path wants many short workgroups).  (The tile loop with STAGED weights, for the plain 3x3 and 5x5 64->64 convs, was
 // measured as a loss and is gone: tools/probes/conv_c8_persist_staged_experiment.patch, profiles/HISTORY.md.)
 constexpr int C8_RESIDENT_MIN_TILES = 8;
+constexpr int C8_NWR = 16;                                   // waves of the resident-filter workgroup: 32 x 32 tiles
+constexpr int C8_THR = C8_NWR * ConvC8Pseg<3, 64>::value;
+// THE rule that sends a plain 16-bit conv3x3 64->64 of this shape to the resident-filter form, asked by launch_conv_c8 and by
+// codon_conv_form_c8 (include/codon_hip.h) so that the launch and the query cannot drift apart.  Returns the workgroups of the
+// resident generation, or 0 for the staged one-tile-per-workgroup form (also when the occupancy query fails: so does the launch).
+template <class E>
+static int c8_resident_grid(const codon_conv_desc* d) {
+  const int res = c8_resident_blocks(conv_c8_kernel<E, 3, 64, 64, false, C8_NWR, false, true, true>, 64 * C8_NWR);
+  const long nblkr = (long)((d->width + 31) / 32) * ((d->height + C8_THR - 1) / C8_THR) * d->batch;
+  return (res > 0 && nblkr >= (long)res * C8_RESIDENT_MIN_TILES) ? res : 0;
+}
 template <class E, int KS, int CIN, int COUT, bool FUSE, int NW, bool GATE>
 static int launch_single_c8(const void* pv, hipStream_t stream) {
   const ConvC8Params& p = *static_cast<const ConvC8Params*>(pv);
@@ -1009,17 +1020,12 @@ static int launch_conv_c8(ConvC8Params& p, const codon_conv_desc* d, hipStream_t
   p.nblk = (int)nblk;
   if constexpr (KS == 3 && CIN == 64 && COUT == 64 && !FUSE && !GATE && C8_DMA) {
     // resident-filter persistent form: 16 waves, 32 x 32 tiles, one workgroup per CU
-    constexpr int NWR = 16, THR = NWR * ConvC8Pseg<KS, COUT>::value;
-    constexpr bool RW = true;
-    const int res = c8_resident_blocks(conv_c8_kernel<E, KS, CIN, COUT, FUSE, NWR, GATE, true, RW>, 64 * NWR);
-    const int tyr = (d->height + THR - 1) / THR;
-    const long nblkr = (long)p.tiles_x * tyr * d->batch;
-    if (res > 0 && nblkr >= (long)res * C8_RESIDENT_MIN_TILES) {
+    if (const int res = c8_resident_grid<E>(d)) {
       ConvC8Params pr = p;
-      pr.tiles_y = tyr;
-      pr.nblk = (int)nblkr;
-      hipLaunchKernelGGL((conv_c8_kernel<E, KS, CIN, COUT, FUSE, NWR, GATE, true, RW>), dim3((unsigned)res), dim3(64 * NWR), 0,
-                         stream, pr);
+      pr.tiles_y = (d->height + C8_THR - 1) / C8_THR;
+      pr.nblk = (int)((long)p.tiles_x * pr.tiles_y * d->batch);
+      hipLaunchKernelGGL((conv_c8_kernel<E, KS, CIN, COUT, FUSE, C8_NWR, GATE, true, true>), dim3((unsigned)res),
+                         dim3(64 * C8_NWR), 0, stream, pr);
       return check_launch("conv_c8_kernel<resident>");
     }
   }
@@ -1052,6 +1058,21 @@ static int conv2d_fwd_c8(const codon_conv_desc* d, const void* x, const void* w,
     case 1064128: return launch_conv1x1_c8<E, 64, 128>(d, x, w, y, res, stream);
     default:
       set_error("conv2d_fwd: no 16-bit kernel for k=%d cin=%d cout=%d", d->ksize, d->cin, d->cout);
+      return CODON_ERR_UNSUPPORTED;
+  }
+}
+
+// codon_conv_form_c8 (include/codon_hip.h): the form conv2d_fwd_c8 gives a launch of this shape, without launching it
+int conv_form_c8(const codon_conv_desc* d) {
+  const int key = d->ksize * 1000000 + d->cin * 1000 + d->cout;
+  switch (key) {
+    case 3064064:
+      return (d->dtype == CODON_F16 ? c8_resident_grid<C8F16>(d) : c8_resident_grid<C8Bf16>(d)) ? CODON_C8_FORM_RESIDENT
+                                                                                                : CODON_C8_FORM_STAGED;
+    case 5128128: case 5064064: case 3128064: case 3064128: case 1128064: case 1064128:
+      return CODON_C8_FORM_STAGED;
+    default:
+      set_error("conv_form_c8: no 16-bit kernel for k=%d cin=%d cout=%d", d->ksize, d->cin, d->cout);
       return CODON_ERR_UNSUPPORTED;
   }
 }

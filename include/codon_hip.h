@@ -40,7 +40,8 @@ typedef enum codon_status {
 
 /* dtype of the 64/128-channel activations (and of the packed conv weights): storage + MFMA operand type;
  * accumulation is always fp32.  CODON_F16 is the reference script's own inference precision
- * (model.cuda().half(), /root/reference/CODON_X4/test.py:52,122-123). */
+ * (model.cuda().half(), /root/reference/CODON_X4/test.py:52,122-123).  A 16-bit conv stores its fp32 result rounded once to
+ * nearest even; fp16 subnormal operands and results are kept, as the reference's CPU .half() keeps them. */
 typedef enum codon_dtype { CODON_F32 = 0, CODON_BF16 = 1, CODON_F16 = 2 } codon_dtype;
 
 enum {
@@ -198,6 +199,20 @@ int codon_conv_pair_end(codon_stream_t stream);
 #define CODON_TILING_4X32_SOLO 2
 #define CODON_TILING_2X32_COUT_SPLIT 3
 int codon_conv_tiling_f32(const codon_conv_desc* desc, int chained, int in_pair);
+
+/* Which form codon_conv2d_fwd gives a 16-bit (CODON_BF16 / CODON_F16) conv of this shape, asked of the same rule the launch
+ * follows (nothing is launched): diagnostics, and the tests whose premise is the form.  The plain conv3x3 64->64 of a LARGE
+ * launch runs as one resident generation of 16-wave workgroups, each holding the whole packed filter in LDS and walking
+ * 32 x 32 pixel tiles: taken when the grid has at least 8 such tiles per resident workgroup, the number of resident
+ * workgroups coming from the current device's occupancy query (no usable device: staged, as the launch would be).  Every
+ * other shape, and every smaller launch, is staged: one 8 x 32 (5x5 64->64: 16 x 32) tile per workgroup.  Same MFMAs on
+ * the same operands in the same order per pixel: results do not depend on the form.  The flags and slices of d are not
+ * looked at.  Returns CODON_C8_FORM_STAGED / _RESIDENT, or CODON_ERR_UNSUPPORTED for an fp32 dtype or a (k, cin, cout)
+ * with no 16-bit kernel.  Replaces nothing in the reference (eager PyTorch leaves the kernel choice to cuDNN,
+ * CODON_x4.py:75-84). */
+#define CODON_C8_FORM_STAGED 0
+#define CODON_C8_FORM_RESIDENT 1
+int codon_conv_form_c8(const codon_conv_desc* desc);
 
 /* A conv whose input is the CAC gate-apply of the producing block, formed while the input tile is staged instead of
  * being written to HBM and read back (inference):   x = pre * (ch * sp) + inputs ,  y = conv(x) [ReLU]

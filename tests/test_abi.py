@@ -77,6 +77,19 @@ def test_fp32_launch_rule_without_gpu():
     assert lib.codon_conv_tiling_f32(None, 0, 0) == -1 and b"conv_tiling_f32" in lib.codon_last_error_string()
 
 
+def test_16bit_form_query_refusals_without_gpu():
+    """codon_conv_form_c8 validates before it asks the device anything: no descriptor / a bad shape is BAD_ARG, an fp32
+    dtype or a (k, cin, cout) with no 16-bit kernel UNSUPPORTED."""
+    import ctypes as C
+    from codon_amd import _lib as L
+    lib = L.load()
+    d = lambda B=1, k=3, ci=64, co=64, dt=L.BF16: C.byref(L.ConvDesc(B, 8, 8, ci, co, k, ci, 0, co, 0, 0, 0, 0, dt))
+    assert lib.codon_conv_form_c8(None) == -1 and b"conv_form_c8" in lib.codon_last_error_string()
+    assert lib.codon_conv_form_c8(d(B=0)) == -1
+    assert lib.codon_conv_form_c8(d(dt=L.F32)) == -2
+    assert lib.codon_conv_form_c8(d(k=5, ci=64, co=128, dt=L.F16)) == -2 and b"no 16-bit kernel" in lib.codon_last_error_string()
+
+
 def test_module_surface_matches_reference_contract(golden_dir):
     from codon_amd import CODONNet, CODONNet16
     ref = {}

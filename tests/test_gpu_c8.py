@@ -160,11 +160,15 @@ def test_resident_filter_conv3x3_equals_the_staged_kernel(hw, dtype):
     Same MFMAs on the same operands in the same order: a batch of 8 (resident form) must equal its four batches of 2 (staged
     form) bit for bit -- forward with ReLU, and the dgrad epilogues (ReLU mask, accumulate, mask over the sum); ragged image
     sizes put partial tiles on both edges."""
+    import ctypes as C
     from codon_amd import _lib as L, ops
     from codon_amd.ops import Slice
     dev = _dev()
     H, W = hw
     B = 8
+    form = lambda b: L.load().codon_conv_form_c8(C.byref(L.ConvDesc(b, H, W, 64, 64, 3, 64, 0, 64, 0, 0, 0, 0,
+                                                                    L.BF16 if dtype == torch.bfloat16 else L.F16)))
+    assert form(B) == L.C8_FORM_RESIDENT and form(2) == L.C8_FORM_STAGED     # the premise: resident batch, staged parts
     x = ops.from_nchw(torch.relu(_rand((B, 64, H, W), 1)).to(dev), dtype)
     act = ops.from_nchw(_rand((B, 64, H, W), 4).to(dev), dtype)
     prev = ops.from_nchw(_rand((B, 64, H, W), 5).to(dev), dtype)
