@@ -144,6 +144,10 @@ SIGNATURES = {
     "codon_conv_form_c8": (C.c_int, [C.POINTER(ConvDesc)]),
     "codon_cast_multi": (C.c_int, [C.POINTER(CastDesc), _P, _P]),
     "codon_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),
+    "codon_grad_norm_workspace_bytes": (_S, []),
+    "codon_grad_norm": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "codon_adam_step_guarded": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I,
+                                          C.c_double, _I, C.c_double, _P]),
     "codon_reduce_multi": (C.c_int, [C.POINTER(ReduceItem), _I, _P]),
     "codon_train_crops": (C.c_int, [C.POINTER(CropDesc), _P, C.c_int64, _P, _P, _P, _P]),
     "codon_bicubic_downsample": (C.c_int, [_I, _I, _I, _P, _P, _P, _P]),

@@ -113,6 +113,10 @@ int ssim_l1_bwd(int, int, int, const float*, const float*, const float*, float*,
 int reduce_multi(const codon_reduce_item*, int, hipStream_t);
 int cast_multi(const codon_cast_desc*, float*, hipStream_t);
 int adam_step(const codon_adam_desc*, const float*, float*, float*, float, float, float, float, float, int, hipStream_t);
+size_t grad_norm_workspace_bytes();
+int grad_norm(const float*, long, void*, hipStream_t);
+int adam_step_guarded(const codon_adam_desc*, const float*, float*, float*, float*, void*, float, float, float, float, float, int,
+                      double, int, double, hipStream_t);
 int train_crops(const codon_crop_desc*, const unsigned char*, const float*, float*, float*, hipStream_t);
 int bicubic_downsample(int, int, int, const float*, const float*, float*, hipStream_t);
 int quantize_u8(long, float*, const float*, hipStream_t);
@@ -620,6 +624,21 @@ int codon_adam_step(const codon_adam_desc* desc, const float* grad, float* exp_a
                     float beta2, float eps, float weight_decay, int32_t step, codon_stream_t stream) {
   CODON_REQUIRE(desc && grad && exp_avg && exp_avg_sq, CODON_ERR_BAD_ARG, "adam_step: null pointer");
   return adam_step(desc, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
+}
+
+size_t codon_grad_norm_workspace_bytes(void) { return grad_norm_workspace_bytes(); }
+
+int codon_grad_norm(const float* grad, int64_t n, void* state, codon_stream_t stream) {
+  CODON_REQUIRE(grad && state, CODON_ERR_BAD_ARG, "grad_norm: null pointer");
+  return grad_norm(grad, (long)n, state, (hipStream_t)stream);
+}
+
+int codon_adam_step_guarded(const codon_adam_desc* desc, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                            void* state, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                            double max_norm, int32_t skip_nonfinite, double ema_decay, codon_stream_t stream) {
+  CODON_REQUIRE(desc && grad && exp_avg && exp_avg_sq && state, CODON_ERR_BAD_ARG, "adam_step_guarded: null pointer");
+  return adam_step_guarded(desc, grad, exp_avg, exp_avg_sq, ema, state, lr, beta1, beta2, eps, weight_decay, step, max_norm,
+                           skip_nonfinite, ema_decay, (hipStream_t)stream);
 }
 
 int codon_reduce_multi(const codon_reduce_item* items, int32_t n_items, codon_stream_t stream) {

@@ -138,9 +138,17 @@ class FlatAdam:
     """torch.optim.Adam (amsgrad=False, maximize=False) over a GradSync's parameters as ONE launch per step
     (codon_adam_step): the gradients are read from the flat all-reduce buffer, the two moments live in flat buffers of the
     same layout, the fp32 parameters are updated in place (and their Tensor._version bumped: the packed-weight cache and
-    GraphedCODON.stale() see the new values).  Same update as torch.optim.Adam to fp32 rounding (tests/test_gpu_reduce.py)."""
+    GraphedCODON.stale() see the new values).  Same update as torch.optim.Adam to fp32 rounding (tests/test_gpu_reduce.py).
 
-    def __init__(self, gs: GradSync, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+    Off by default, each turning the step into two launches (codon_grad_norm + codon_adam_step_guarded; still no host
+    synchronisation):
+      max_norm:       clip the global gradient norm (torch's clip_grad_norm_ formula, the norm accumulated in float64);
+      skip_nonfinite: a step whose gradient holds an Inf / NaN changes nothing (it still consumes its step number `t`);
+      ema_decay:      `ema` (flat, the gradient's layout; starts as a copy of the parameters) follows them,
+                      ema += (1 - decay) (p - ema), in the same pass."""
+
+    def __init__(self, gs: GradSync, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 max_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_decay: Optional[float] = None):
         import ctypes as C
         from . import _lib as L
         if gs.flat.dtype != torch.float32 or not gs.flat.is_cuda or any(not p.is_contiguous() for p in gs.params):
@@ -151,33 +159,91 @@ class FlatAdam:
         self.exp_avg, self.exp_avg_sq = torch.zeros_like(gs.flat), torch.zeros_like(gs.flat)
         self.t = 0
         self._C, self._L = C, L
+        self.ema, self._state = None, None
+        self._set_guards(max_norm, skip_nonfinite, ema_decay)
 
-    def step(self):
+    def _set_guards(self, max_norm, skip_nonfinite, ema_decay):
+        if max_norm is not None and not float(max_norm) > 0:                      # NaN fails too
+            raise ValueError(f"FlatAdam: max_norm {max_norm} (> 0, or None)")
+        if ema_decay is not None and not 0 <= float(ema_decay) < 1:
+            raise ValueError(f"FlatAdam: ema_decay {ema_decay} (0 <= decay < 1, or None)")
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.guarded = self.max_norm is not None or self.skip_nonfinite or self.ema_decay is not None
+        if self.guarded and self._state is None:   # [0] last norm (float64 bits), [1..3] applied / skipped / clipped, then scratch
+            self._state = torch.zeros(self._L.load().codon_grad_norm_workspace_bytes() // 8, dtype=torch.int64,
+                                      device=self.gs.flat.device)
+        if self.ema_decay is None:
+            self.ema = None
+        elif self.ema is None:
+            self.ema = torch.cat([p.detach().reshape(-1) for p in self.gs.params])
+
+    def step(self, lr: Optional[float] = None):
+        """One step from the flat gradient buffer; `lr`: this step's learning rate (a schedule), kept as self.lr."""
         C, L, gs = self._C, self._L, self.gs
         gs._install_views()                        # a dropped / foreign .grad is adopted into the flat buffer first
+        if lr is not None:
+            self.lr = float(lr)
         d = L.AdamDesc()
         d.n = len(gs.params)
         for i, p in enumerate(gs.params):
             d.param[i], d.count[i] = p.data_ptr(), p.numel()
         self.t += 1
         dev = gs.flat.device
+        P_ = C.c_void_p
         with torch.cuda.device(dev):
-            L.check(L.load().codon_adam_step(C.byref(d), C.c_void_p(gs.flat.data_ptr()), C.c_void_p(self.exp_avg.data_ptr()),
-                                             C.c_void_p(self.exp_avg_sq.data_ptr()), self.lr, self.betas[0], self.betas[1],
-                                             self.eps, self.weight_decay, self.t,
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "adam_step")
+            st = P_(torch.cuda.current_stream(dev).cuda_stream)
+            if not self.guarded:
+                L.check(L.load().codon_adam_step(C.byref(d), P_(gs.flat.data_ptr()), P_(self.exp_avg.data_ptr()),
+                                                 P_(self.exp_avg_sq.data_ptr()), self.lr, self.betas[0], self.betas[1],
+                                                 self.eps, self.weight_decay, self.t, st), "adam_step")
+            else:
+                L.check(L.load().codon_grad_norm(P_(gs.flat.data_ptr()), gs.numel, P_(self._state.data_ptr()), st), "grad_norm")
+                L.check(L.load().codon_adam_step_guarded(
+                    C.byref(d), P_(gs.flat.data_ptr()), P_(self.exp_avg.data_ptr()), P_(self.exp_avg_sq.data_ptr()),
+                    None if self.ema is None else P_(self.ema.data_ptr()), P_(self._state.data_ptr()), self.lr, self.betas[0],
+                    self.betas[1], self.eps, self.weight_decay, self.t, float("inf") if self.max_norm is None else self.max_norm,
+                    int(self.skip_nonfinite), 0.0 if self.ema_decay is None else self.ema_decay, st), "adam_step_guarded")
         for p in gs.params:                        # written through raw pointers: make the new values visible to version keys
             torch.autograd.graph.increment_version(p)
 
+    def stats(self) -> dict:
+        """{"norm": the last step's gradient norm, "applied", "skipped", "clipped": step counts}: ONE device-to-host read of
+        the state block.  The only call here that synchronises; step() never calls it."""
+        if self._state is None:
+            return {"norm": float("nan"), "applied": int(self.t), "skipped": 0, "clipped": 0}
+        h = self._state[:4].cpu()
+        return {"norm": float(h[:1].view(torch.float64).item()), "applied": int(h[1]), "skipped": int(h[2]), "clipped": int(h[3])}
+
+    def ema_state_dict(self, model) -> dict:
+        """The EMA weights as a state_dict of `model` (its keys, order and shapes; host tensors): the used tensors from
+        `ema`, the tensors no gradient reaches (attention_c5 / attention_s5) copied from the model."""
+        if self.ema is None:
+            raise ValueError("FlatAdam.ema_state_dict: built without ema_decay")
+        off, view = 0, {}
+        for n, p in self.gs.named:
+            view[n] = self.ema[off:off + p.numel()].view_as(p)
+            off += p.numel()
+        return {k: view.get(k, v).detach().cpu().clone() for k, v in model.state_dict().items()}
+
     def state_dict(self) -> dict:
         """The moments (host copies), the step count and the hyper-parameters: what a resumed run needs to continue bit for
-        bit (codon_amd.train checkpoints)."""
-        return {"exp_avg": self.exp_avg.detach().cpu().clone(), "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(),
-                "t": int(self.t), "lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay}
+        bit (codon_amd.train checkpoints).  With a guard on also its options, the three counters and `ema`."""
+        sd = {"exp_avg": self.exp_avg.detach().cpu().clone(), "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone(),
+              "t": int(self.t), "lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay}
+        if self.guarded:
+            st = self.stats()
+            sd.update(max_norm=self.max_norm, skip_nonfinite=self.skip_nonfinite, ema_decay=self.ema_decay,
+                      applied=st["applied"], skipped=st["skipped"], clipped=st["clipped"])
+            if self.ema is not None:
+                sd["ema"] = self.ema.detach().cpu().clone()
+        return sd
 
     def load_state_dict(self, state: dict):
-        """Inverse of state_dict(); refuses moments whose flat length is not this GradSync's."""
-        for k in ("exp_avg", "exp_avg_sq"):
+        """Inverse of state_dict(); refuses moments (and an `ema`) whose flat length is not this GradSync's.  Guard keys a
+        state does not carry (one saved before the guards existed) mean that guard is off."""
+        for k in ("exp_avg", "exp_avg_sq") + (("ema",) if state.get("ema") is not None else ()):
             v = state[k]
             if not isinstance(v, torch.Tensor) or v.dim() != 1 or v.numel() != self.gs.numel:
                 raise ValueError(f"FlatAdam.load_state_dict: {k} has {getattr(v, 'shape', None)} values, the GradSync holds "
@@ -187,6 +253,11 @@ class FlatAdam:
         self.t = int(state["t"])
         self.lr, self.eps, self.weight_decay = float(state["lr"]), float(state["eps"]), float(state["weight_decay"])
         self.betas = (float(state["betas"][0]), float(state["betas"][1]))
+        self._set_guards(state.get("max_norm"), state.get("skip_nonfinite", False), state.get("ema_decay"))
+        if self.ema is not None and state.get("ema") is not None:
+            self.ema.copy_(state["ema"])
+        if self._state is not None:
+            self._state[1:4].copy_(torch.tensor([int(state.get(k, 0)) for k in ("applied", "skipped", "clipped")]))
 
 
 def shard_batch(n_images: int, rank: int, world: int):

@@ -218,15 +218,18 @@ def main(argv=None):
     ap.add_argument("--out", default=None)
     ap.add_argument("--weights", default=None, help="X4.pth-style checkpoint; random reference init if absent")
     ap.add_argument("--dtype", default="f16", choices=["f32", "bf16", "f16"], help="the reference script runs .half()")
+    ap.add_argument("--ema", action="store_true", help="load the EMA weights of a codon_amd.train --ema checkpoint")
     ap.add_argument("--serial", action="store_true", help="the reference's own serial loop (decode, upload, forward, download, "
                                                           "encode one after the other per image) instead of the pipeline")
     a = ap.parse_args(argv)
+    if a.ema and not a.weights:
+        ap.error("--ema needs --weights")
     if not torch.cuda.is_available():
         raise SystemExit("No GPU found, codon_amd has no CPU path")          # test.py:37-38
     dev = torch.device("cuda:0")
     model = (CODONNet16 if a.scale == 16 else CODONNet)()
     if a.weights:
-        print("loaded epoch", io.load_checkpoint(a.weights, model))
+        print("loaded epoch", io.load_checkpoint(a.weights, model, ema=a.ema))
     else:
         print("WARNING: no --weights given (the reference's X*.pth are not shipped): random init")
     tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[a.dtype]

@@ -35,16 +35,19 @@ def _compat_on_path():
         sys.path.insert(0, d)
 
 
-def load_checkpoint(path: str, model: torch.nn.Module, strict: bool = True) -> int:
+def load_checkpoint(path: str, model: torch.nn.Module, strict: bool = True, ema: bool = False) -> int:
     """Load the reference's checkpoint formats into `model`; returns the stored epoch (or -1).
-    Whole-module pickles name the classes CODON_x4.CODONNet / CAC_module.*: codon_amd/compat provides them."""
+    Whole-module pickles name the classes CODON_x4.CODONNet / CAC_module.*: codon_amd/compat provides them.
+    ema: load "model_ema" (the EMA weights a `codon_amd.train --ema` checkpoint carries) instead of "model"."""
     from .model import strip_module_prefix
     _compat_on_path()
     ck = torch.load(path, map_location="cpu", weights_only=False)
     epoch = -1
+    if ema and not (isinstance(ck, dict) and "model_ema" in ck):
+        raise ValueError(f"{path}: the checkpoint holds no EMA weights (\"model_ema\": written by codon_amd.train --ema)")
     if isinstance(ck, dict) and "model" in ck:
         epoch = int(ck.get("epoch", -1))
-        ck = ck["model"]
+        ck = ck["model_ema" if ema else "model"]
     sd = ck.state_dict() if isinstance(ck, torch.nn.Module) else ck
     model.load_state_dict(strip_module_prefix(sd), strict=strict)
     return epoch

@@ -8,16 +8,19 @@ The degradation is a definition of this project, NOT pinned to the reference (it
 numpy in tests/train_data_ref.py and the two agree bit for bit.
 
 One step: GradSync.zero_grad -> synthesize -> forward -> L1SSIMLoss(out.float(), t) -> GradSync.backward ->
-all_reduce_grads -> FlatAdam.step, the sequence of bench.py's training leg.  Under torchrun every rank draws the whole
-global batch from the same seeded generator and keeps its shard (codon_amd.dist.shard_batch); the loss is read back on log
-steps only.  Checkpoints are {"epoch": step, "model", "optimizer", "rng", "args"}: io.load_checkpoint and
-`python -m codon_amd.infer --weights` read them as they are, and --resume continues a run bit for bit.
+all_reduce_grads -> FlatAdam.step, the sequence of bench.py's training leg (optionally with gradient clipping, skipping of
+non-finite steps, EMA weights and a learning-rate schedule, all on the device: DESIGN 12.1).  Under torchrun every rank
+draws the whole global batch from the same seeded generator and keeps its shard (codon_amd.dist.shard_batch); the loss is
+read back on log steps only.  Checkpoints are {"epoch": step, "model", "optimizer", "rng", "args"}: io.load_checkpoint and
+`python -m codon_amd.infer --weights` read them as they are (with --ema also "model_ema", read by `infer --ema`), and --resume
+continues a run bit for bit.
 """
 from __future__ import annotations
 
 import argparse
 import ctypes as C
 import functools
+import math
 import os
 import time
 
@@ -30,7 +33,12 @@ from . import ops
 from .upsample import _keys, phase_weights
 
 DTYPES = {"bf16": torch.bfloat16, "f32": None}
-RESUME_KEYS = ("scale", "crop", "batch", "dtype")
+RESUME_KEYS = ("scale", "crop", "batch", "dtype", "clip_norm", "skip_nonfinite", "ema", "lr_schedule", "warmup_steps", "lr_min",
+               "lr_steps")
+# what a key compares as when a checkpoint's args do not carry it (one written before the option existed)
+RESUME_DEFAULTS = {"clip_norm": None, "skip_nonfinite": False, "ema": None, "lr_schedule": "constant", "warmup_steps": 0,
+                   "lr_min": 0.0, "lr_steps": None}
+LR_SCHEDULES = ("constant", "cosine")
 
 
 # ---- the degradation's host-side tables -------------------------------------------------------------------------------------
@@ -164,10 +172,31 @@ def _world(group):
     return dist.get_rank(group), dist.get_world_size(group)
 
 
+def lr_at(step: int, *, lr: float, schedule: str = "constant", warmup: int = 0, lr_min: float = 0.0, lr_steps: int = None) -> float:
+    """The learning rate of step 1, 2, ...: a pure function of the step number (float64 on the host), so a resumed run needs
+    nothing but the step.  Either schedule with warmup > 0: lr * step / warmup up to step `warmup`.  constant: lr.  cosine:
+    from lr at step `warmup` down half a cosine to lr_min at step lr_steps, lr_min beyond.  lr_steps is the length of the
+    CURVE, not of one invocation."""
+    if schedule not in LR_SCHEDULES:
+        raise ValueError(f"lr_at: schedule {schedule!r} ({', '.join(LR_SCHEDULES)})")
+    lr, lr_min = float(lr), float(lr_min)
+    if warmup > 0 and step <= warmup:
+        return lr * step / warmup
+    if schedule == "constant":
+        return lr
+    if lr_steps is None or lr_steps <= warmup:
+        raise ValueError(f"lr_at: the cosine curve needs lr_steps > warmup (lr_steps {lr_steps}, warmup {warmup})")
+    if step > lr_steps:
+        return lr_min
+    return lr_min + (lr - lr_min) * 0.5 * (1.0 + math.cos(math.pi * (step - warmup) / (lr_steps - warmup)))
+
+
 def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, args: dict):
     """Atomically (tmp file, then os.replace): a reader never sees half a checkpoint."""
     ck = {"epoch": int(step), "model": {k: v.detach().cpu() for k, v in model.state_dict().items()},
           "optimizer": opt.state_dict(), "rng": rng.bit_generator.state, "args": dict(args)}
+    if opt.ema is not None:
+        ck["model_ema"] = opt.ema_state_dict(model)
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)
     tmp = f"{path}.tmp{os.getpid()}"
@@ -176,11 +205,13 @@ def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, 
 
 
 def load_resume(path: str, args: dict) -> dict:
-    """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype."""
+    """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype, or with
+    other options that change the trajectory (RESUME_KEYS; a key the checkpoint's args lack compares as its default)."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(ck, dict) or not all(k in ck for k in ("epoch", "model", "optimizer", "rng", "args")):
         raise ValueError(f"--resume {path}: not a codon_amd.train checkpoint (use --weights to start from other weights)")
-    bad = [f"{k} {ck['args'].get(k)!r} != {args.get(k)!r}" for k in RESUME_KEYS if ck["args"].get(k) != args.get(k)]
+    was, now = ({k: a.get(k, RESUME_DEFAULTS.get(k)) for k in RESUME_KEYS} for a in (ck["args"], args))
+    bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in RESUME_KEYS if was[k] != now[k]]
     if bad:
         raise ValueError(f"--resume {path}: the checkpoint was trained with other arguments: {', '.join(bad)}")
     return ck
@@ -189,12 +220,19 @@ def load_resume(path: str, args: dict) -> dict:
 def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, batch: int = 16, lr: float = 1e-4,
         dtype: str = "bf16", rng: np.random.Generator = None, seed: int = 0, log_every: int = 10, process_group=None,
         val: dict = None, ckpt: dict = None, start_step: int = 0, opt_state: dict = None, fixed: np.ndarray = None,
-        args: dict = None, time_synth: bool = False, emit=print) -> dict:
+        args: dict = None, time_synth: bool = False, emit=print, clip_norm: float = None, skip_nonfinite: bool = False,
+        ema_decay: float = None, lr_schedule: str = "constant", warmup: int = 0, lr_min: float = 0.0, lr_steps: int = None,
+        grad_hook=None) -> dict:
     """Train `model` (fp32 parameters on the pool's device) from step start_step + 1 to step `steps`.
     val:   {"depth", "color", "label", "every"} -- rank 0 runs infer.run_loop every `every` steps and prints the means;
     ckpt:  {"path", "every"} -- rank 0 saves every `every` steps and after the last one;
     fixed: descriptors (draw's rows of this rank) used for EVERY step instead of drawing (overfit checks);
-    time_synth: HIP events around synthesize and around each whole step (result["synth_ms"], ["step_ms"]).
+    time_synth: HIP events around synthesize and around each whole step (result["synth_ms"], ["step_ms"]);
+    clip_norm, skip_nonfinite, ema_decay: FlatAdam's max_norm, skip_nonfinite, ema_decay (all off by default); with one on,
+           the log lines gain `gnorm .. skipped N clipped N` and the result "stats" (FlatAdam.stats());
+    lr_schedule, warmup, lr_min, lr_steps: lr_at's curve (lr_steps defaults to `steps`); with the constant schedule and no
+           warm-up no learning rate is passed to the optimizer, so the one a resumed optimizer state carries rules;
+    grad_hook(step, gs): called between gs.backward and gs.all_reduce_grads (gradient noise, freezing a tensor, tests).
     Returns {"losses": [(step, loss)], "gs", "opt", "rng", "step", ...}."""
     from .dist import FlatAdam, GradSync
     from .metrics import L1SSIMLoss
@@ -209,11 +247,17 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     model.train()
     gs = GradSync(model, process_group=process_group)
     gs.broadcast_parameters(0)
-    opt = FlatAdam(gs, lr=lr)
+    opt = FlatAdam(gs, lr=lr, max_norm=clip_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
     if opt_state is not None:
         opt.load_state_dict(opt_state)
+    scheduled = lr_schedule != "constant" or warmup > 0
+    if lr_schedule == "cosine" and lr_steps is None:
+        lr_steps = steps
+    lr_at(1, lr=lr, schedule=lr_schedule, warmup=warmup, lr_min=lr_min, lr_steps=lr_steps)       # refuses a bad curve up front
     crit = L1SSIMLoss(1.0, 1.0)
-    args = dict(args or {}, scale=scale, crop=crop, batch=batch, dtype=dtype)
+    args = dict(args or {}, scale=scale, crop=crop, batch=batch, dtype=dtype, clip_norm=clip_norm,
+                skip_nonfinite=bool(skip_nonfinite), ema=ema_decay, lr_schedule=lr_schedule, warmup_steps=warmup, lr_min=lr_min,
+                lr_steps=lr_steps if lr_schedule == "cosine" else None)
     stream = torch.cuda.current_stream(dev)
     losses, val_log, ev = [], [], []
     t_log, s_log = time.perf_counter(), start_step
@@ -232,8 +276,13 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         out = model(x, y)
         loss = crit(out.float(), t)
         gs.backward(loss)
+        if grad_hook is not None:
+            grad_hook(step, gs)
         gs.all_reduce_grads()
-        opt.step()
+        if scheduled:
+            opt.step(lr_at(step, lr=lr, schedule=lr_schedule, warmup=warmup, lr_min=lr_min, lr_steps=lr_steps))
+        else:
+            opt.step()
         if time_synth:
             e[3].record(stream)
             ev.append(e)
@@ -250,14 +299,20 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
             sps = (step - s_log) / (now - t_log)
             t_log, s_log = now, step
             losses.append((step, lv))
+            line = f"step {step} loss {lv:.6f} steps/s {sps:.2f} images/s {sps * batch:.1f}"
+            if opt.guarded:                         # the loss read-back has synchronised already
+                st = opt.stats()
+                line += f" gnorm {st['norm']:.6g} skipped {st['skipped']} clipped {st['clipped']}"
             if rank == 0:
-                emit(f"step {step} loss {lv:.6f} steps/s {sps:.2f} images/s {sps * batch:.1f}")
+                emit(line)
         if val and rank == 0 and step % val["every"] == 0:
             val_log.append((step, validate(model, dev, val, emit)))
             t_log = time.perf_counter()             # validation time is not training time
         if ckpt and rank == 0 and (step % ckpt["every"] == 0 or step == steps):
             save_checkpoint(ckpt["path"], step, model, opt, rng, args)
     res = {"losses": losses, "val": val_log, "gs": gs, "opt": opt, "rng": rng, "step": step, "rank": rank, "world": world}
+    if opt.guarded:
+        res["stats"] = opt.stats()
     if time_synth and ev:
         torch.cuda.synchronize(dev)
         res["synth_ms"] = [e[1].elapsed_time(e[2]) for e in ev]
@@ -303,6 +358,16 @@ def parse_args(argv=None):
     ap.add_argument("--val-label", default=None)
     ap.add_argument("--val-every", type=int, default=1000)
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
+    ap.add_argument("--clip-norm", type=float, default=None, help="clip the global gradient norm to this (on the device)")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="a step whose gradient holds an Inf or NaN changes nothing (it still counts as a step)")
+    ap.add_argument("--ema", type=float, default=None,
+                    help="keep EMA weights with this decay: saved as \"model_ema\", read by `codon_amd.infer --ema`")
+    ap.add_argument("--lr-schedule", default="constant", choices=list(LR_SCHEDULES))
+    ap.add_argument("--warmup-steps", type=int, default=0, help="linear warm-up from lr / N to lr over the first N steps")
+    ap.add_argument("--lr-min", type=float, default=None, help="cosine: the learning rate at and after --lr-steps (default 0)")
+    ap.add_argument("--lr-steps", type=int, default=None,
+                    help="cosine: the length of the curve (default --steps); give it when a run is cut into --resume legs")
     a = ap.parse_args(argv)
     if a.dtype == "f16":
         ap.error("--dtype f16: fp16 training is not supported (inference-only, as in the reference); use bf16 or f32")
@@ -314,11 +379,29 @@ def parse_args(argv=None):
         ap.error("--resume and --weights exclude each other")
     if (a.val_depth is None) != (a.val_color is None):
         ap.error("--val-depth and --val-color go together")
+    if a.clip_norm is not None and not a.clip_norm > 0:
+        ap.error(f"--clip-norm {a.clip_norm} must be positive")
+    if a.ema is not None and not 0 <= a.ema < 1:
+        ap.error(f"--ema {a.ema} must lie in [0, 1)")
+    if a.lr_schedule == "constant" and (a.lr_min is not None or a.lr_steps is not None):
+        ap.error("--lr-min and --lr-steps belong to --lr-schedule cosine")
+    if a.lr_steps is not None and a.lr_steps < 1:
+        ap.error(f"--lr-steps {a.lr_steps} must be positive")
+    if a.lr_min is not None and not 0 <= a.lr_min <= a.lr:
+        ap.error(f"--lr-min {a.lr_min} must lie in [0, --lr {a.lr}]")
+    if a.lr_schedule == "cosine":
+        a.lr_steps = a.steps if a.lr_steps is None else a.lr_steps       # resolved: the curve's length, not this invocation's
+    a.lr_min = 0.0 if a.lr_min is None else a.lr_min
+    curve = a.lr_steps if a.lr_steps is not None else a.steps
+    if a.warmup_steps < 0 or a.warmup_steps >= curve:
+        ap.error(f"--warmup-steps {a.warmup_steps} must lie in [0, {curve}): shorter than the run's {curve} steps")
     return a
 
 
 def run_args(a) -> dict:
-    return {"scale": a.scale, "crop": a.crop, "batch": a.batch, "dtype": a.dtype, "lr": a.lr, "seed": a.seed}
+    return {"scale": a.scale, "crop": a.crop, "batch": a.batch, "dtype": a.dtype, "lr": a.lr, "seed": a.seed,
+            "clip_norm": a.clip_norm, "skip_nonfinite": a.skip_nonfinite, "ema": a.ema, "lr_schedule": a.lr_schedule,
+            "warmup_steps": a.warmup_steps, "lr_min": a.lr_min, "lr_steps": a.lr_steps}
 
 
 def main(argv=None, emit=print) -> dict:
@@ -363,7 +446,8 @@ def main(argv=None, emit=print) -> dict:
     ckpt = {"path": a.save, "every": a.save_every} if a.save else None
     res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,
               log_every=a.log_every, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,
-              args=args, emit=emit)
+              args=args, emit=emit, clip_norm=a.clip_norm, skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema,
+              lr_schedule=a.lr_schedule, warmup=a.warmup_steps, lr_min=a.lr_min, lr_steps=a.lr_steps)
     res["model"] = model
     return res
 

@@ -525,6 +525,32 @@ typedef struct codon_adam_desc {
 int codon_adam_step(const codon_adam_desc* desc, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int32_t step, codon_stream_t stream);
 
+/* ---- the guarded Adam step: global-norm clipping, non-finite skipping, EMA (codon_amd.dist.FlatAdam's options) -------------
+ * No reference counterpart: the reference ships no training code.  Two launches per step on the caller's stream, no host
+ * synchronisation, no float atomics, every reduction in a fixed order (a resumed run continues bit for bit, and N ranks reach
+ * the same decision from their identical all-reduced gradients).  `state`: codon_grad_norm_workspace_bytes() of device
+ * memory, 8-byte aligned, ZEROED once by the caller and private to one stream; its first four 8-byte words are
+ * last_norm (double), applied, skipped, clipped (uint64 counts), the rest is scratch.
+ *
+ * codon_grad_norm: reads the flat fp32 gradient (n elements, 16-byte aligned) once and leaves per-workgroup partial sums of
+ * g * g, accumulated in float64 (the product of two fp32 values is exact there), and counts of non-finite elements in `state`.
+ *
+ * codon_adam_step_guarded: codon_adam_step's update after folding those partials, block-uniformly:
+ *   norm = sqrt(sum g g);  coef = min(1, max_norm / (norm + 1e-6)) in float64, rounded once to fp32 (torch's clip_grad_norm_;
+ *   max_norm = +inf: no clipping, coef = 1 exactly);  the gradient used is coef * g (then + weight_decay * p as in
+ *   codon_adam_step); `grad` itself is left unscaled.
+ *   skip_nonfinite != 0 and any non-finite element: the WHOLE step is a no-op -- param, exp_avg, exp_avg_sq and ema keep their
+ *   bits, `skipped` goes up by one.  Otherwise `applied` goes up by one, and `clipped` when coef < 1.  With skip_nonfinite = 0
+ *   nothing is hidden: a NaN norm gives a NaN coef, an Inf norm coef = 0 and 0 * Inf = NaN.
+ *   ema (flat fp32 in the gradient's layout, or null):  ema += (1 - ema_decay) * (param_new - ema), in the same pass.
+ * `step` is a host argument and counts ATTEMPTED steps: a skipped step consumes its number (no read-back decides the bias
+ * correction), so the guarded step with nothing firing equals codon_adam_step bit for bit. */
+size_t codon_grad_norm_workspace_bytes(void);
+int codon_grad_norm(const float* grad, int64_t n, void* state, codon_stream_t stream);
+int codon_adam_step_guarded(const codon_adam_desc* desc, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                            void* state, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                            double max_norm, int32_t skip_nonfinite, double ema_decay, codon_stream_t stream);
+
 /* ---- training-batch synthesis (codon_amd.train) -------------------------------------------------------------------------
  * No reference counterpart: the reference ships no training code and its depth inputs were degraded offline (bicubic down,
  * bicubic up, 8-bit PNG: CODON_X4/test.py:70-79,116-123) by a script it does not ship -- this pipeline is a DEFINITION, not
