@@ -109,6 +109,10 @@ SIGNATURES = {
     "codon_stem_pair_fwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     "codon_head_fwd": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P]),
     "codon_head_fwd_y16": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P]),
+    "codon_stem_fwd_guarded": (C.c_int, [_I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "codon_stem_pair_fwd_guarded": (C.c_int, [_I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "codon_head_fwd_guarded": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "codon_head_fwd_y16_guarded": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P]),
     "codon_cac_stats_tiles": (_I, [_I, _I]),
     "codon_cac_stats_fwd": (C.c_int, [_I, _I, _I, _TP, _TP, _P, _P, _I, _P]),
     "codon_cac_stats_scaled_fwd": (C.c_int, [_I, _I, _I, _TP, _TP, _P, _P, _P, _I, _P]),
@@ -154,6 +158,7 @@ SIGNATURES = {
     "codon_quantize_u8": (C.c_int, [C.c_int64, _P, _P, _P]),
     "codon_weight_checksum_workspace_bytes": (_S, []),
     "codon_weight_checksum": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P]),
+    "codon_weight_checksum_clear": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P, _I, _P]),
 }
 
 _lock = threading.Lock()

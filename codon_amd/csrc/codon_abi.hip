@@ -68,9 +68,9 @@ int conv_chain1x1_fwd_f32(const codon_conv_desc*, const float*, const float*, fl
 bool conv_f32x3_supported(const codon_conv_desc*);
 int conv2d_fwd_f32x3(const codon_conv_desc*, const float*, const void*, float*, const float*, hipStream_t);
 int pack_weight_f32x3(const float*, void*, int, int, int, hipStream_t);
-int stem_fwd(int, int, int, const float*, const float*, void*, int, int, int, const void*, int, int, int, hipStream_t);
+int stem_fwd(int, int, int, const float*, const float*, void*, int, int, int, const void*, int, int, int, int*, int*, hipStream_t);
 int stem_pair_fwd(int, int, int, const float*, const float*, void*, int, int, const float*, const float*, void*, int, int, int,
-                  hipStream_t);
+                  int*, int*, int*, hipStream_t);
 size_t conv1ch_wgrad_workspace_bytes(int, int, int);
 int conv1ch_wgrad(int, int, int, const void*, int, int, const float*, float*, int, float*, size_t, int, hipStream_t);
 int cac_bwd_tiles(int, int);
@@ -87,7 +87,7 @@ int cac_bwd_apply(int, int, int, const codon_tensor*, const codon_tensor*, const
 int ew_add_mask(int, int, int, int, const codon_tensor*, const codon_tensor*, const codon_tensor*, int, int,
                 hipStream_t);
 int ew_sum_mask(int, int, int, int, const codon_tensor*, int, const codon_tensor* const*, const codon_tensor*, int, hipStream_t);
-int head_fwd(int, int, int, const void*, int, int, const float*, const float*, void*, bool, int, hipStream_t);
+int head_fwd(int, int, int, const void*, int, int, const float*, const float*, void*, bool, int, const int*, hipStream_t);
 int cac_stats_tiles(int, int);
 int cac_stats_fwd(int, int, int, const codon_tensor*, const codon_tensor*, float*, float*, int, hipStream_t, const float*);
 int ew_sq_scale(int, int, int, const codon_tensor*, const float*, const codon_tensor*, int, hipStream_t);
@@ -121,7 +121,7 @@ int train_crops(const codon_crop_desc*, const unsigned char*, const float*, floa
 int bicubic_downsample(int, int, int, const float*, const float*, float*, hipStream_t);
 int quantize_u8(long, float*, const float*, hipStream_t);
 size_t weight_checksum_workspace_bytes();
-int weight_checksum(const codon_wsum_desc*, void*, unsigned long long*, int, int*, hipStream_t);
+int weight_checksum(const codon_wsum_desc*, void*, unsigned long long*, int, int*, int*, int, hipStream_t);
 
 static thread_local PairRecorder g_pair;
 PairRecorder* pair_recorder() { return g_pair.active ? &g_pair : nullptr; }
@@ -432,17 +432,31 @@ int codon_conv1x1_bwd_gated(const codon_conv_desc* d, const void* x, const void*
 
 int codon_stem_fwd(int32_t batch, int32_t height, int32_t width, const float* x, const float* w_oihw, void* y,
                    int32_t y_ctotal, int32_t y_coff, int32_t dtype, codon_stream_t stream) {
+  return codon_stem_fwd_guarded(batch, height, width, x, w_oihw, y, y_ctotal, y_coff, dtype, nullptr, nullptr, stream);
+}
+
+int codon_stem_fwd_guarded(int32_t batch, int32_t height, int32_t width, const float* x, const float* w_oihw, void* y,
+                           int32_t y_ctotal, int32_t y_coff, int32_t dtype, int32_t* bad, int32_t* host_word,
+                           codon_stream_t stream) {
   CODON_REQUIRE(x && w_oihw && y, CODON_ERR_BAD_ARG, "stem_fwd: null pointer");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "stem_fwd: bad shape");
   CODON_REQUIRE(y_coff >= 0 && y_coff + 64 <= y_ctotal, CODON_ERR_BAD_ARG, "stem_fwd: output slice outside buffer");
   CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "stem_fwd: dtype %d", dtype);
-  return stem_fwd(batch, height, width, x, w_oihw, y, y_ctotal, y_coff, 1, nullptr, 0, 0, dtype,
+  return stem_fwd(batch, height, width, x, w_oihw, y, y_ctotal, y_coff, 1, nullptr, 0, 0, dtype, bad, host_word,
                   (hipStream_t)stream);
 }
 
 int codon_stem_pair_fwd(int32_t batch, int32_t height, int32_t width, const float* xa, const float* wa_oihw, void* ya,
                         int32_t ya_ctotal, int32_t ya_coff, const float* xb, const float* wb_oihw, void* yb,
                         int32_t yb_ctotal, int32_t yb_coff, int32_t dtype, codon_stream_t stream) {
+  return codon_stem_pair_fwd_guarded(batch, height, width, xa, wa_oihw, ya, ya_ctotal, ya_coff, xb, wb_oihw, yb, yb_ctotal,
+                                     yb_coff, dtype, nullptr, nullptr, nullptr, stream);
+}
+
+int codon_stem_pair_fwd_guarded(int32_t batch, int32_t height, int32_t width, const float* xa, const float* wa_oihw, void* ya,
+                                int32_t ya_ctotal, int32_t ya_coff, const float* xb, const float* wb_oihw, void* yb,
+                                int32_t yb_ctotal, int32_t yb_coff, int32_t dtype, int32_t* bad, int32_t* host_word_a,
+                                int32_t* host_word_b, codon_stream_t stream) {
   CODON_REQUIRE(xa && wa_oihw && ya && xb && wb_oihw && yb, CODON_ERR_BAD_ARG, "stem_pair_fwd: null pointer");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "stem_pair_fwd: bad shape");
   CODON_REQUIRE(ya_coff >= 0 && ya_coff + 64 <= ya_ctotal && yb_coff >= 0 && yb_coff + 64 <= yb_ctotal, CODON_ERR_BAD_ARG,
@@ -451,27 +465,39 @@ int codon_stem_pair_fwd(int32_t batch, int32_t height, int32_t width, const floa
                 "stem_pair_fwd: the two output slices overlap");
   CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "stem_pair_fwd: dtype %d", dtype);
   return stem_pair_fwd(batch, height, width, xa, wa_oihw, ya, ya_ctotal, ya_coff, xb, wb_oihw, yb, yb_ctotal, yb_coff, dtype,
-                       (hipStream_t)stream);
+                       bad, host_word_a, host_word_b, (hipStream_t)stream);
 }
 
 int codon_head_fwd(int32_t batch, int32_t height, int32_t width, const void* x, int32_t x_ctotal, int32_t x_coff,
                    const float* w_oihw, const float* residual, float* y, int32_t dtype, codon_stream_t stream) {
+  return codon_head_fwd_guarded(batch, height, width, x, x_ctotal, x_coff, w_oihw, residual, y, dtype, nullptr, stream);
+}
+
+int codon_head_fwd_guarded(int32_t batch, int32_t height, int32_t width, const void* x, int32_t x_ctotal, int32_t x_coff,
+                           const float* w_oihw, const float* residual, float* y, int32_t dtype, const int32_t* bad,
+                           codon_stream_t stream) {
   CODON_REQUIRE(x && w_oihw && residual && y, CODON_ERR_BAD_ARG, "head_fwd: null pointer");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "head_fwd: bad shape");
   CODON_REQUIRE(x_coff >= 0 && x_coff + 64 <= x_ctotal, CODON_ERR_BAD_ARG, "head_fwd: input slice outside buffer");
   CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "head_fwd: dtype %d", dtype);
-  return head_fwd(batch, height, width, x, x_ctotal, x_coff, w_oihw, residual, y, false, dtype, (hipStream_t)stream);
+  return head_fwd(batch, height, width, x, x_ctotal, x_coff, w_oihw, residual, y, false, dtype, bad, (hipStream_t)stream);
 }
 
 int codon_head_fwd_y16(int32_t batch, int32_t height, int32_t width, const void* x, int32_t x_ctotal, int32_t x_coff,
                        const float* w_oihw, const float* residual, void* y16, int32_t dtype, codon_stream_t stream) {
+  return codon_head_fwd_y16_guarded(batch, height, width, x, x_ctotal, x_coff, w_oihw, residual, y16, dtype, nullptr, stream);
+}
+
+int codon_head_fwd_y16_guarded(int32_t batch, int32_t height, int32_t width, const void* x, int32_t x_ctotal, int32_t x_coff,
+                               const float* w_oihw, const float* residual, void* y16, int32_t dtype, const int32_t* bad,
+                               codon_stream_t stream) {
   CODON_REQUIRE(x && w_oihw && residual && y16, CODON_ERR_BAD_ARG, "head_fwd_y16: null pointer");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "head_fwd_y16: bad shape");
   CODON_REQUIRE(x_coff >= 0 && x_coff + 64 <= x_ctotal, CODON_ERR_BAD_ARG, "head_fwd_y16: input slice outside buffer");
   CODON_REQUIRE((dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED,
                 "head_fwd_y16: dtype %d (the 16-bit output exists for 16-bit activations)", dtype);
   CODON_REQUIRE(((uintptr_t)y16 % 2) == 0, CODON_ERR_BAD_ARG, "head_fwd_y16: output not 2-byte aligned");
-  return head_fwd(batch, height, width, x, x_ctotal, x_coff, w_oihw, residual, y16, true, dtype, (hipStream_t)stream);
+  return head_fwd(batch, height, width, x, x_ctotal, x_coff, w_oihw, residual, y16, true, dtype, bad, (hipStream_t)stream);
 }
 
 int32_t codon_cac_stats_tiles(int32_t height, int32_t width) {
@@ -545,7 +571,7 @@ int codon_stencil_1to64(int32_t batch, int32_t height, int32_t width, const floa
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "stencil_1to64: bad shape");
   CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "stencil_1to64: dtype %d", dtype);
   return stem_fwd(batch, height, width, x, w_64x9, y->data, y->ctotal, y->coff, flags, mask ? mask->data : nullptr,
-                  mask ? mask->ctotal : 0, mask ? mask->coff : 0, dtype, (hipStream_t)stream);
+                  mask ? mask->ctotal : 0, mask ? mask->coff : 0, dtype, nullptr, nullptr, (hipStream_t)stream);
 }
 
 size_t codon_conv1ch_wgrad_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
@@ -833,7 +859,13 @@ size_t codon_weight_checksum_workspace_bytes(void) { return weight_checksum_work
 
 int codon_weight_checksum(const codon_wsum_desc* desc, void* ws, uint64_t* ref, int32_t mode, int32_t* flag,
                           codon_stream_t stream) {
+  return codon_weight_checksum_clear(desc, ws, ref, mode, flag, nullptr, 0, stream);
+}
+
+int codon_weight_checksum_clear(const codon_wsum_desc* desc, void* ws, uint64_t* ref, int32_t mode, int32_t* flag,
+                                int32_t* clear, int32_t nclear, codon_stream_t stream) {
   CODON_REQUIRE(desc && ws && ref && flag, CODON_ERR_BAD_ARG, "weight_checksum: null pointer");
+  CODON_REQUIRE(nclear >= 0 && (clear || nclear == 0), CODON_ERR_BAD_ARG, "weight_checksum: %d words to clear at a null pointer", nclear);
   CODON_REQUIRE(desc->n > 0 && desc->n <= CODON_WSUM_MAX && (mode == 0 || mode == 1), CODON_ERR_BAD_ARG,
                 "weight_checksum: n %d (1..%d), mode %d (0, 1)", desc->n, CODON_WSUM_MAX, mode);
   uint64_t total = 0;
@@ -843,7 +875,7 @@ int codon_weight_checksum(const codon_wsum_desc* desc, void* ws, uint64_t* ref, 
     total += desc->bytes[t];
   }
   CODON_REQUIRE(total / 16 < (1ull << 32), CODON_ERR_UNSUPPORTED, "weight_checksum: more than 64 GiB of weights");
-  return weight_checksum(desc, ws, (unsigned long long*)ref, mode, flag, (hipStream_t)stream);
+  return weight_checksum(desc, ws, (unsigned long long*)ref, mode, flag, clear, nclear, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -47,10 +47,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t c8_rsrc(const C8Slice& s, int 
 // A wave owns (image, row, segment of 64 * VEC columns); a lane owns the VEC pixels seg0 + lane + 64 v, so every store
 // instruction covers 64 consecutive pixels of one plane.  Weights live in LDS as [plane][tap][8 ch]: two broadcast
 // ds_read_b128 feed 8 * VEC FMAs.  flags: 1 = ReLU, 2 = spatially flipped taps (dL/dt11 of the head conv).
+// bad / host (optional, the forward's stems only): the non-finite input guard of stencil.hip over the VEC centre pixels
+// (tap 4) this lane owns -- "exponent all ones"; the lane marks bad[b], one lane of the wave stores 1 to the host word.
 template <class E, int VEC>
 __device__ __forceinline__ void stem_c8_body(const float* __restrict__ x, const float* __restrict__ w,
                                              C8Slice y, C8Slice mask, int has_mask, int H, int W, int nseg,
-                                             long nwave, int flags, long blk) {
+                                             long nwave, int flags, long blk, int* __restrict__ bad = nullptr,
+                                             int* __restrict__ host = nullptr) {
   __shared__ float wsh[8 * 9 * 8];
   for (int i = threadIdx.x; i < 576; i += 256) {
     const int co = i / 9, t = i % 9;
@@ -79,6 +82,16 @@ __device__ __forceinline__ void stem_c8_body(const float* __restrict__ x, const 
       const bool ok = in && yy >= 0 && yy < H && xx >= 0 && xx < W;
       const float q = xb[ok ? (long)yy * W + xx : 0];
       xin[v][t] = ok ? q : 0.f;
+    }
+  }
+  if (bad || host) {
+    bool nf = false;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) nf |= (__float_as_uint(xin[v][4]) & 0x7f800000u) == 0x7f800000u;   // off-image lanes hold 0
+    const unsigned long long m = __ballot(nf);
+    if (m != 0) {
+      if (nf && bad) bad[b] = 1;
+      if (host && lane == __ffsll(m) - 1) __hip_atomic_store(host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
   const __amdgpu_buffer_rsrc_t yr = c8_rsrc(y, b, 8, HW16);
@@ -121,8 +134,8 @@ __device__ __forceinline__ void stem_c8_body(const float* __restrict__ x, const 
 template <class E, int VEC>
 __global__ __launch_bounds__(256) void stem_c8_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                       C8Slice y, C8Slice mask, int has_mask, int H, int W, int nseg,
-                                                      long nwave, int flags) {
-  stem_c8_body<E, VEC>(x, w, y, mask, has_mask, H, W, nseg, nwave, flags, (long)blockIdx.x);
+                                                      long nwave, int flags, int* __restrict__ bad, int* __restrict__ host) {
+  stem_c8_body<E, VEC>(x, w, y, mask, has_mask, H, W, nseg, nwave, flags, (long)blockIdx.x, bad, host);
 }
 
 // the depth and the guidance stem of a forward as ONE launch (round 6; see stem_pair_kernel in stencil.hip): workgroups
@@ -130,58 +143,60 @@ __global__ __launch_bounds__(256) void stem_c8_kernel(const float* __restrict__ 
 template <class E, int VEC>
 __global__ __launch_bounds__(256) void stem_c8_pair_kernel(const float* __restrict__ xa, const float* __restrict__ wa, C8Slice ya,
                                                            const float* __restrict__ xb, const float* __restrict__ wb, C8Slice yb,
-                                                           int H, int W, int nseg, long nwave, unsigned nblk) {
-  if (blockIdx.x < nblk) stem_c8_body<E, VEC>(xa, wa, ya, ya, 0, H, W, nseg, nwave, 1, (long)blockIdx.x);
-  else stem_c8_body<E, VEC>(xb, wb, yb, yb, 0, H, W, nseg, nwave, 1, (long)(blockIdx.x - nblk));
+                                                           int H, int W, int nseg, long nwave, unsigned nblk, int* __restrict__ bad,
+                                                           int* __restrict__ host_a, int* __restrict__ host_b) {
+  if (blockIdx.x < nblk) stem_c8_body<E, VEC>(xa, wa, ya, ya, 0, H, W, nseg, nwave, 1, (long)blockIdx.x, bad, host_a);
+  else stem_c8_body<E, VEC>(xb, wb, yb, yb, 0, H, W, nseg, nwave, 1, (long)(blockIdx.x - nblk), bad, host_b);
 }
 
 template <class E>
 static int stem_c8_pair_launch(int B, int H, int W, const float* xa, const float* wa, C8Slice ya, const float* xb,
-                               const float* wb, C8Slice yb, hipStream_t stream) {
+                               const float* wb, C8Slice yb, int* bad, int* host_a, int* host_b, hipStream_t stream) {
   constexpr int VEC = 2;
   const int nseg = (W + 64 * VEC - 1) / (64 * VEC);
   const long nwave = (long)B * H * nseg;
   const long blocks = (nwave + 3) / 4;
   CODON_REQUIRE(2 * blocks < (1L << 31), CODON_ERR_UNSUPPORTED, "stem_pair_fwd: grid too large");
   hipLaunchKernelGGL((stem_c8_pair_kernel<E, VEC>), dim3((unsigned)(2 * blocks)), dim3(256), 0, stream, xa, wa, ya, xb, wb, yb,
-                     H, W, nseg, nwave, (unsigned)blocks);
+                     H, W, nseg, nwave, (unsigned)blocks, bad, host_a, host_b);
   return check_launch("stem_c8_pair_kernel");
 }
 
 int stem_pair_fwd_c8(int B, int H, int W, const float* xa, const float* wa, void* ya, int ya_ctotal, int ya_coff,
-                     const float* xb, const float* wb, void* yb, int yb_ctotal, int yb_coff, int dtype, hipStream_t stream) {
+                     const float* xb, const float* wb, void* yb, int yb_ctotal, int yb_coff, int dtype, int* bad, int* host_a,
+                     int* host_b, hipStream_t stream) {
   CODON_REQUIRE(c8_slice_ok(ya_ctotal, ya_coff, 64) && c8_slice_ok(yb_ctotal, yb_coff, 64), CODON_ERR_BAD_ARG,
                 "stem_pair: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
   const long HW = (long)H * W;
   CODON_REQUIRE(HW * 2 * 64 < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "stem_pair: image too large for 32-bit buffer offsets");
   const C8Slice sa = c8_mk(ya, ya_ctotal, ya_coff, HW), sb = c8_mk(yb, yb_ctotal, yb_coff, HW);
-  return dtype == CODON_F16 ? stem_c8_pair_launch<C8F16>(B, H, W, xa, wa, sa, xb, wb, sb, stream)
-                            : stem_c8_pair_launch<C8Bf16>(B, H, W, xa, wa, sa, xb, wb, sb, stream);
+  return dtype == CODON_F16 ? stem_c8_pair_launch<C8F16>(B, H, W, xa, wa, sa, xb, wb, sb, bad, host_a, host_b, stream)
+                            : stem_c8_pair_launch<C8Bf16>(B, H, W, xa, wa, sa, xb, wb, sb, bad, host_a, host_b, stream);
 }
 
 template <class E>
 static int stem_c8_launch(int B, int H, int W, const float* x, const float* w, C8Slice y, C8Slice mask, int has_mask,
-                          int flags, hipStream_t stream) {
+                          int flags, int* bad, int* host, hipStream_t stream) {
   constexpr int VEC = 2;
   const int nseg = (W + 64 * VEC - 1) / (64 * VEC);
   const long nwave = (long)B * H * nseg;
   const long blocks = (nwave + 3) / 4;
   CODON_REQUIRE(blocks < (1L << 31), CODON_ERR_UNSUPPORTED, "stem_fwd: grid too large");
   hipLaunchKernelGGL((stem_c8_kernel<E, VEC>), dim3((unsigned)blocks), dim3(256), 0, stream, x, w, y, mask, has_mask, H,
-                     W, nseg, nwave, flags);
+                     W, nseg, nwave, flags, bad, host);
   return check_launch("stem_c8_kernel");
 }
 
 int stem_fwd_c8(int B, int H, int W, const float* x, const float* w, void* y, int y_ctotal, int y_coff, int flags,
-                const void* mask, int m_ctotal, int m_coff, int dtype, hipStream_t stream) {
+                const void* mask, int m_ctotal, int m_coff, int dtype, int* bad, int* host, hipStream_t stream) {
   CODON_REQUIRE(c8_slice_ok(y_ctotal, y_coff, 64) && (!mask || c8_slice_ok(m_ctotal, m_coff, 64)), CODON_ERR_BAD_ARG,
                 "stem: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
   const long HW = (long)H * W;
   CODON_REQUIRE(HW * 2 * 64 < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "stem: image too large for 32-bit buffer offsets");
   const C8Slice ys = c8_mk(y, y_ctotal, y_coff, HW);
   const C8Slice ms = mask ? c8_mk(mask, m_ctotal, m_coff, HW) : ys;
-  return dtype == CODON_F16 ? stem_c8_launch<C8F16>(B, H, W, x, w, ys, ms, mask ? 1 : 0, flags, stream)
-                            : stem_c8_launch<C8Bf16>(B, H, W, x, w, ys, ms, mask ? 1 : 0, flags, stream);
+  return dtype == CODON_F16 ? stem_c8_launch<C8F16>(B, H, W, x, w, ys, ms, mask ? 1 : 0, flags, bad, host, stream)
+                            : stem_c8_launch<C8Bf16>(B, H, W, x, w, ys, ms, mask ? 1 : 0, flags, bad, host, stream);
 }
 
 // ---- head: y = conv3x3_{64->1}(x) + res -------------------------------------------------------------------------------
@@ -193,10 +208,11 @@ int stem_fwd_c8(int B, int H, int W, const float* x, const float* w, void* y, in
 // carry an out-of-range offset, off-image rows a zero-length descriptor (wave-uniform select).
 // Y16: the output map is stored in the activations' 16-bit type (a model cast as a whole, test.py:52, returns 16 bits): the
 // fp32 sum rounded once -- the value an fp32 store followed by a conversion pass gives, without the pass.
+// bad (optional, the forward's head only): bad[b] != 0 stores a quiet NaN of the output's type in every element of image b.
 template <class E, int R, bool Y16 = false>
 __global__ __launch_bounds__(256) void head_c8_kernel(C8Slice x, const float* __restrict__ w,
                                                       const float* __restrict__ res, void* __restrict__ yv, int H, int W,
-                                                      int nband, int nseg, long nwave, int nblk) {
+                                                      int nband, int nseg, long nwave, int nblk, const int* __restrict__ bad) {
   __shared__ float wsh[8 * 9 * 8];                      // [plane][tap][8 ch]
   for (int i = threadIdx.x; i < 576; i += 256) {
     const int c = i / 9, t = i % 9;
@@ -256,13 +272,14 @@ __global__ __launch_bounds__(256) void head_c8_kernel(C8Slice x, const float* __
     }
   }
   const bool act = lane >= 1 && lane <= 62 && col < W;
+  const bool poison = bad && bad[b] != 0;               // wave-uniform
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const float left = __shfl_up(V[r][0], 1, 64), right = __shfl_down(V[r][2], 1, 64);
     const int gy = gy0 + r;
     if (act && gy < H) {
       const long off = (long)b * HW + (long)gy * W + col;
-      const float v = (left + V[r][1] + right) + res[off];
+      const float v = poison ? __uint_as_float(0x7fc00000u) : (left + V[r][1] + right) + res[off];
       if constexpr (Y16) reinterpret_cast<unsigned short*>(yv)[off] = (unsigned short)(E::pack2(v, 0.f) & 0xffffu);
       else reinterpret_cast<float*>(yv)[off] = v;
     }
@@ -270,7 +287,8 @@ __global__ __launch_bounds__(256) void head_c8_kernel(C8Slice x, const float* __
 }
 
 template <class E, int R>
-static int head_c8_launch(int B, int H, int W, C8Slice x, const float* w, const float* res, void* y, bool y16, hipStream_t stream) {
+static int head_c8_launch(int B, int H, int W, C8Slice x, const float* w, const float* res, void* y, bool y16, const int* bad,
+                          hipStream_t stream) {
   const int nband = (H + R - 1) / R;
   const int nseg = (W + 61) / 62;
   const long nwave = (long)B * nband * nseg;
@@ -278,15 +296,15 @@ static int head_c8_launch(int B, int H, int W, C8Slice x, const float* w, const 
   CODON_REQUIRE(blocks < (1L << 31), CODON_ERR_UNSUPPORTED, "head_fwd: grid too large");
   if (y16)
     hipLaunchKernelGGL((head_c8_kernel<E, R, true>), dim3((unsigned)blocks), dim3(256), 0, stream, x, w, res, y, H, W, nband,
-                       nseg, nwave, (int)blocks);
+                       nseg, nwave, (int)blocks, bad);
   else
     hipLaunchKernelGGL((head_c8_kernel<E, R, false>), dim3((unsigned)blocks), dim3(256), 0, stream, x, w, res, y, H, W, nband,
-                       nseg, nwave, (int)blocks);
+                       nseg, nwave, (int)blocks, bad);
   return check_launch("head_c8_kernel");
 }
 
 int head_fwd_c8(int B, int H, int W, const void* x, int x_ctotal, int x_coff, const float* w, const float* res, void* y,
-                bool y16, int dtype, hipStream_t stream) {
+                bool y16, int dtype, const int* bad, hipStream_t stream) {
   CODON_REQUIRE(c8_slice_ok(x_ctotal, x_coff, 64), CODON_ERR_BAD_ARG,
                 "head_fwd: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
   const long HW = (long)H * W;
@@ -294,8 +312,8 @@ int head_fwd_c8(int B, int H, int W, const void* x, int x_ctotal, int x_coff, co
   const C8Slice xs = c8_mk(x, x_ctotal, x_coff, HW);
   const bool big = (long)B * H * W >= (1L << 22);
   if (dtype == CODON_F16)
-    return big ? head_c8_launch<C8F16, 8>(B, H, W, xs, w, res, y, y16, stream) : head_c8_launch<C8F16, 4>(B, H, W, xs, w, res, y, y16, stream);
-  return big ? head_c8_launch<C8Bf16, 8>(B, H, W, xs, w, res, y, y16, stream) : head_c8_launch<C8Bf16, 4>(B, H, W, xs, w, res, y, y16, stream);
+    return big ? head_c8_launch<C8F16, 8>(B, H, W, xs, w, res, y, y16, bad, stream) : head_c8_launch<C8F16, 4>(B, H, W, xs, w, res, y, y16, bad, stream);
+  return big ? head_c8_launch<C8Bf16, 8>(B, H, W, xs, w, res, y, y16, bad, stream) : head_c8_launch<C8Bf16, 4>(B, H, W, xs, w, res, y, y16, bad, stream);
 }
 
 // ---- weight gradient of the 1->64 / 64->1 3x3 convs ------------------------------------------------------------------

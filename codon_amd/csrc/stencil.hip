@@ -51,14 +51,31 @@ __device__ __forceinline__ void load_row(const T* __restrict__ plane, int gy, in
   v[VEC + 1] = gx0 + VEC < W ? ldx(row + gx0 + VEC) : 0.f;
 }
 
+// Non-finite input guard: "exponent all ones" on the raw fp32 word -- NaN, +Inf, -Inf; denormals, zeros and
+// +-FLT_MAX pass.
+__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// A lane that saw a non-finite CENTRE pixel marks its image's word in device memory; one lane of the wave reports to the
+// host-visible word the way wsum.hip reports a stale weight (relaxed system-scope store of 1, no read-modify-write over the
+// bus).  Either pointer may be NULL; with both NULL (every backward caller) nothing is tested.
+__device__ __forceinline__ void report_nonfinite(bool nf, int b, int* __restrict__ bad, int* __restrict__ host) {
+  const unsigned long long m = __ballot(nf);
+  if (m == 0) return;
+  if (nf && bad) bad[b] = 1;
+  if (host && (int)(threadIdx.x & 63) == __ffsll(m) - 1) __hip_atomic_store(host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // flags: 1 = ReLU on the output; 2 = use the spatially flipped taps (w[c][8-t]): with w = output.weight
 // this is dL/dt of the head conv (y = sum_c conv3x3(t_c, w_c)) given dL/dy.
 // mask (optional, 64 channels): out = mask > 0 ? out : 0 (backward through conv11's ReLU).
+// bad / host (optional, the forward's stems only): the non-finite input guard over the VEC centre pixels this thread owns
+// (the halo belongs to its neighbours: every input pixel is judged exactly once).
 template <int VEC, typename T>
 __device__ __forceinline__ void stem_body(const float* __restrict__ x, const float* __restrict__ w,
                                           T* __restrict__ y, int H, int W, long y_img,
                                           long y_base, long total, int flags,
-                                          const T* __restrict__ mask, long m_img, long m_base, long blk) {
+                                          const T* __restrict__ mask, long m_img, long m_base, long blk,
+                                          int* __restrict__ bad = nullptr, int* __restrict__ host = nullptr) {
   __shared__ float wsh[64 * 9];
   for (int i = threadIdx.x; i < 576; i += 256) wsh[i] = (flags & 2) ? w[(i / 9) * 9 + 8 - (i % 9)] : w[i];
   __syncthreads();
@@ -75,6 +92,12 @@ __device__ __forceinline__ void stem_body(const float* __restrict__ x, const flo
   load_row<VEC, float>(plane, gy - 1, gx0, H, W, r0);
   load_row<VEC, float>(plane, gy, gx0, H, W, r1);
   load_row<VEC, float>(plane, gy + 1, gx0, H, W, r2);
+  if (bad || host) {
+    bool nf = false;
+#pragma unroll
+    for (int i = 1; i <= VEC; ++i) nf |= nonfinite(r1[i]);
+    report_nonfinite(nf, b, bad, host);
+  }
   const long HW = (long)H * W;
   T* yo = y + (long)b * y_img + y_base + (long)gy * W + gx0;
   const T* mo = mask ? mask + (long)b * m_img + m_base + (long)gy * W + gx0 : nullptr;
@@ -115,8 +138,9 @@ template <int VEC, typename T>
 __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                    T* __restrict__ y, int H, int W, long y_img,
                                                    long y_base, long total, int flags,
-                                                   const T* __restrict__ mask, long m_img, long m_base) {
-  stem_body<VEC, T>(x, w, y, H, W, y_img, y_base, total, flags, mask, m_img, m_base, (long)blockIdx.x);
+                                                   const T* __restrict__ mask, long m_img, long m_base,
+                                                   int* __restrict__ bad, int* __restrict__ host) {
+  stem_body<VEC, T>(x, w, y, H, W, y_img, y_base, total, flags, mask, m_img, m_base, (long)blockIdx.x, bad, host);
 }
 
 // The depth and the guidance stem of a forward (/root/reference/CODON_X4/CODON_x4.py:68,71) as ONE launch (round 6: at one
@@ -127,9 +151,10 @@ __global__ __launch_bounds__(256) void stem_pair_kernel(const float* __restrict_
                                                         T* __restrict__ ya, long ya_img, long ya_base,
                                                         const float* __restrict__ xb, const float* __restrict__ wb,
                                                         T* __restrict__ yb, long yb_img, long yb_base, int H, int W,
-                                                        long total, unsigned nblk) {
-  if (blockIdx.x < nblk) stem_body<VEC, T>(xa, wa, ya, H, W, ya_img, ya_base, total, 1, nullptr, 0, 0, (long)blockIdx.x);
-  else stem_body<VEC, T>(xb, wb, yb, H, W, yb_img, yb_base, total, 1, nullptr, 0, 0, (long)(blockIdx.x - nblk));
+                                                        long total, unsigned nblk, int* __restrict__ bad,
+                                                        int* __restrict__ host_a, int* __restrict__ host_b) {
+  if (blockIdx.x < nblk) stem_body<VEC, T>(xa, wa, ya, H, W, ya_img, ya_base, total, 1, nullptr, 0, 0, (long)blockIdx.x, bad, host_a);
+  else stem_body<VEC, T>(xb, wb, yb, H, W, yb_img, yb_base, total, 1, nullptr, 0, 0, (long)(blockIdx.x - nblk), bad, host_b);
 }
 
 // head: y = sum_c conv3x3(x_c, w_c) + res.  One thread owns VEC consecutive pixels of R consecutive rows (a band): per
@@ -140,11 +165,13 @@ __global__ __launch_bounds__(256) void stem_pair_kernel(const float* __restrict_
 // DEPTH channels are fetched before the first of them is used: one 128 x 128 image is 32 waves, and a wave that waits for
 // every channel's rows before it asks for the next one's is 64 memory round trips long (57 us; 4 in flight: 37 us).  The
 // channels are still accumulated one after the other in the same order: same bits.
+// bad (optional, the forward's head only): with bad[b] != 0 -- a stem saw a non-finite pixel in image b -- every element of
+// the image is stored as a quiet NaN (what the reference's pools and gates make of it); else the sums as before.
 template <int VEC, int R, typename T, int DEPTH = 1>
 __global__ __launch_bounds__(256) void head_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                    const float* __restrict__ res, float* __restrict__ y, int H,
                                                    int W, long x_img, long x_base, int nband, int nseg, int nwave,
-                                                   int nblk) {
+                                                   int nblk, const int* __restrict__ bad) {
   __shared__ float wsh[64 * 9];
   for (int i = threadIdx.x; i < 576; i += 256) wsh[i] = w[i];
   __syncthreads();
@@ -246,6 +273,8 @@ __global__ __launch_bounds__(256) void head_kernel(const T* __restrict__ x, cons
     for (int d = 0; d < DEPTH; ++d) accumulate(c + d, ra[d]);
   }
   if (!act) return;
+  const bool poison = bad && bad[b] != 0;                         // wave-uniform (b is): one scalar load
+  const float qnan = __uint_as_float(0x7fc00000u);
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int gy = gy0 + r;
@@ -255,21 +284,22 @@ __global__ __launch_bounds__(256) void head_kernel(const T* __restrict__ x, cons
 #pragma unroll
       for (int q = 0; q < VEC / 4; ++q) {
         const float4 rr = *reinterpret_cast<const float4*>(res + off + 4 * q);
-        *reinterpret_cast<float4*>(y + off + 4 * q) = make_float4(o[r][4 * q] + rr.x, o[r][4 * q + 1] + rr.y,
-                                                                  o[r][4 * q + 2] + rr.z, o[r][4 * q + 3] + rr.w);
+        *reinterpret_cast<float4*>(y + off + 4 * q) =
+            poison ? make_float4(qnan, qnan, qnan, qnan)
+                   : make_float4(o[r][4 * q] + rr.x, o[r][4 * q + 1] + rr.y, o[r][4 * q + 2] + rr.z, o[r][4 * q + 3] + rr.w);
       }
     } else if constexpr (VEC == 2) {
       const float2 rr = *reinterpret_cast<const float2*>(res + off);
-      *reinterpret_cast<float2*>(y + off) = make_float2(o[r][0] + rr.x, o[r][1] + rr.y);
+      *reinterpret_cast<float2*>(y + off) = poison ? make_float2(qnan, qnan) : make_float2(o[r][0] + rr.x, o[r][1] + rr.y);
     } else {
-      y[off] = o[r][0] + res[off];
+      y[off] = poison ? qnan : o[r][0] + res[off];
     }
   }
 }
 
 template <typename T>
 static int stem_launch(int B, int H, int W, const float* x, const float* w, T* y, int y_ctotal, int y_coff, int flags,
-                       const T* mask, int m_ctotal, int m_coff, hipStream_t stream) {
+                       const T* mask, int m_ctotal, int m_coff, int* bad, int* host, hipStream_t stream) {
   const long HW = (long)H * W;
   // images of a few thousand pixels (one 128 x 128 pair per call, BASELINE configs[0]): the four-pixel form is 16 workgroups
   // on 256 CUs, each thread 64 dependent row stores long -- the one-pixel form has four times the threads.  Same fma chain
@@ -282,34 +312,36 @@ static int stem_launch(int B, int H, int W, const float* x, const float* w, T* y
   CODON_REQUIRE(blocks < (1L << 31), CODON_ERR_UNSUPPORTED, "stem_fwd: grid too large");
   if (v4)
     hipLaunchKernelGGL((stem_kernel<4, T>), dim3((unsigned)blocks), dim3(256), 0, stream, x, w, y, H, W,
-                       y_ctotal * HW, y_coff * HW, total, flags, mask, m_ctotal * HW, m_coff * HW);
+                       y_ctotal * HW, y_coff * HW, total, flags, mask, m_ctotal * HW, m_coff * HW, bad, host);
   else
     hipLaunchKernelGGL((stem_kernel<1, T>), dim3((unsigned)blocks), dim3(256), 0, stream, x, w, y, H, W,
-                       y_ctotal * HW, y_coff * HW, total, flags, mask, m_ctotal * HW, m_coff * HW);
+                       y_ctotal * HW, y_coff * HW, total, flags, mask, m_ctotal * HW, m_coff * HW, bad, host);
   return check_launch("stem_kernel");
 }
 
 // ew_c8.hip: the same stencils over channel-blocked 16-bit tensors
-int stem_fwd_c8(int, int, int, const float*, const float*, void*, int, int, int, const void*, int, int, int, hipStream_t);
-int head_fwd_c8(int, int, int, const void*, int, int, const float*, const float*, void*, bool, int, hipStream_t);
+int stem_fwd_c8(int, int, int, const float*, const float*, void*, int, int, int, const void*, int, int, int, int*, int*, hipStream_t);
+int head_fwd_c8(int, int, int, const void*, int, int, const float*, const float*, void*, bool, int, const int*, hipStream_t);
 size_t conv1ch_wgrad_c8_workspace_bytes(int, int, int);
 int conv1ch_wgrad_c8(int, int, int, const void*, int, int, const float*, float*, int, float*, size_t, int, hipStream_t);
 
 int stem_fwd(int B, int H, int W, const float* x, const float* w, void* y, int y_ctotal, int y_coff, int flags,
-             const void* mask, int m_ctotal, int m_coff, int dtype, hipStream_t stream) {
+             const void* mask, int m_ctotal, int m_coff, int dtype, int* bad, int* host, hipStream_t stream) {
   if (dtype != CODON_F32)
-    return stem_fwd_c8(B, H, W, x, w, y, y_ctotal, y_coff, flags, mask, m_ctotal, m_coff, dtype, stream);
+    return stem_fwd_c8(B, H, W, x, w, y, y_ctotal, y_coff, flags, mask, m_ctotal, m_coff, dtype, bad, host, stream);
   return stem_launch<float>(B, H, W, x, w, (float*)y, y_ctotal, y_coff, flags, (const float*)mask, m_ctotal, m_coff,
-                            stream);
+                            bad, host, stream);
 }
 
 int stem_pair_fwd_c8(int, int, int, const float*, const float*, void*, int, int, const float*, const float*, void*, int, int,
-                     int, hipStream_t);
+                     int, int*, int*, int*, hipStream_t);
 
 int stem_pair_fwd(int B, int H, int W, const float* xa, const float* wa, void* ya, int ya_ctotal, int ya_coff,
-                  const float* xb, const float* wb, void* yb, int yb_ctotal, int yb_coff, int dtype, hipStream_t stream) {
+                  const float* xb, const float* wb, void* yb, int yb_ctotal, int yb_coff, int dtype, int* bad, int* host_a,
+                  int* host_b, hipStream_t stream) {
   if (dtype != CODON_F32)
-    return stem_pair_fwd_c8(B, H, W, xa, wa, ya, ya_ctotal, ya_coff, xb, wb, yb, yb_ctotal, yb_coff, dtype, stream);
+    return stem_pair_fwd_c8(B, H, W, xa, wa, ya, ya_ctotal, ya_coff, xb, wb, yb, yb_ctotal, yb_coff, dtype, bad, host_a, host_b,
+                            stream);
   const long HW = (long)H * W;
   const bool tiny = (long)B * H * W <= 65536;                    // as stem_launch: same form, same bits as the lone launches
   const bool v4 = !tiny && (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(xa) | reinterpret_cast<uintptr_t>(ya) |
@@ -319,16 +351,18 @@ int stem_pair_fwd(int B, int H, int W, const float* xa, const float* wa, void* y
   CODON_REQUIRE(2 * blocks < (1L << 31), CODON_ERR_UNSUPPORTED, "stem_pair_fwd: grid too large");
   if (v4)
     hipLaunchKernelGGL((stem_pair_kernel<4, float>), dim3((unsigned)(2 * blocks)), dim3(256), 0, stream, xa, wa, (float*)ya,
-                       ya_ctotal * HW, ya_coff * HW, xb, wb, (float*)yb, yb_ctotal * HW, yb_coff * HW, H, W, total, (unsigned)blocks);
+                       ya_ctotal * HW, ya_coff * HW, xb, wb, (float*)yb, yb_ctotal * HW, yb_coff * HW, H, W, total, (unsigned)blocks,
+                       bad, host_a, host_b);
   else
     hipLaunchKernelGGL((stem_pair_kernel<1, float>), dim3((unsigned)(2 * blocks)), dim3(256), 0, stream, xa, wa, (float*)ya,
-                       ya_ctotal * HW, ya_coff * HW, xb, wb, (float*)yb, yb_ctotal * HW, yb_coff * HW, H, W, total, (unsigned)blocks);
+                       ya_ctotal * HW, ya_coff * HW, xb, wb, (float*)yb, yb_ctotal * HW, yb_coff * HW, H, W, total, (unsigned)blocks,
+                       bad, host_a, host_b);
   return check_launch("stem_pair_kernel");
 }
 
 template <int VEC, int R, typename T, int DEPTH = 1>
 static int head_launch_v(int B, int H, int W, const T* x, int x_ctotal, int x_coff, const float* w, const float* res,
-                         float* y, hipStream_t stream) {
+                         float* y, const int* bad, hipStream_t stream) {
   const long HW = (long)H * W;
   const int nband = (H + R - 1) / R;
   const int nseg = (W / VEC + 63) / 64;
@@ -336,13 +370,13 @@ static int head_launch_v(int B, int H, int W, const T* x, int x_ctotal, int x_co
   const long blocks = (nwave + 3) / 4;
   CODON_REQUIRE(nwave < (1L << 31), CODON_ERR_UNSUPPORTED, "head_fwd: grid too large");
   hipLaunchKernelGGL((head_kernel<VEC, R, T, DEPTH>), dim3((unsigned)blocks), dim3(256), 0, stream, x, w, res, y, H, W,
-                     x_ctotal * HW, x_coff * HW, nband, nseg, (int)nwave, (int)blocks);
+                     x_ctotal * HW, x_coff * HW, nband, nseg, (int)nwave, (int)blocks, bad);
   return check_launch("head_kernel");
 }
 
 template <typename T>
 static int head_launch(int B, int H, int W, const T* x, int x_ctotal, int x_coff, const float* w, const float* res,
-                       float* y, hipStream_t stream) {
+                       float* y, const int* bad, hipStream_t stream) {
   const long HW = (long)H * W;
   CODON_REQUIRE(64 * HW * (long)sizeof(T) < 0xFFFFFFF0L, CODON_ERR_UNSUPPORTED,
                 "head_fwd: %dx%d image: 64 channel planes exceed the 4 GiB buffer-descriptor range", H, W);
@@ -354,7 +388,7 @@ static int head_launch(int B, int H, int W, const T* x, int x_ctotal, int x_coff
 #ifdef CODON_TUNE
   if (const char* e = getenv("CODON_HEAD_BAND")) {
     const int r = atoi(e);
-#define HV(v_, r_) if (r == v_ * 100 + r_) return head_launch_v<v_, r_, T>(B, H, W, x, x_ctotal, x_coff, w, res, y, stream);
+#define HV(v_, r_) if (r == v_ * 100 + r_) return head_launch_v<v_, r_, T>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream);
     if constexpr (sizeof(T) == 2) { HV(8, 2) HV(8, 4) HV(8, 8) }
     HV(2, 4) HV(2, 8) HV(2, 16) HV(4, 2) HV(4, 4) HV(4, 8) HV(4, 16)
 #undef HV
@@ -366,19 +400,19 @@ static int head_launch(int B, int H, int W, const T* x, int x_ctotal, int x_coff
   const bool big = (long)B * H * W >= (1L << 22);
   // a few thousand pixels (one 128 x 128 image: 32 waves of the 4-pixel form, each 16 memory round trips long): one row and
   // 64 pixels per wave, 16 channels' rows in flight -- 256 waves, 4 round trips.  Same accumulation order: same bits.
-  if ((long)B * H * W <= 65536) return head_launch_v<1, 1, T, 16>(B, H, W, x, x_ctotal, x_coff, w, res, y, stream);
+  if ((long)B * H * W <= 65536) return head_launch_v<1, 1, T, 16>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream);
   if (v4)
-    return big ? head_launch_v<4, 16, T>(B, H, W, x, x_ctotal, x_coff, w, res, y, stream)
-               : head_launch_v<4, 4, T, 4>(B, H, W, x, x_ctotal, x_coff, w, res, y, stream);
-  return big ? head_launch_v<1, 4, T>(B, H, W, x, x_ctotal, x_coff, w, res, y, stream)
-             : head_launch_v<1, 4, T, 8>(B, H, W, x, x_ctotal, x_coff, w, res, y, stream);
+    return big ? head_launch_v<4, 16, T>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream)
+               : head_launch_v<4, 4, T, 4>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream);
+  return big ? head_launch_v<1, 4, T>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream)
+             : head_launch_v<1, 4, T, 8>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream);
 }
 
 // y16 (16-bit activations only): y is stored in the activations' type instead of fp32
 int head_fwd(int B, int H, int W, const void* x, int x_ctotal, int x_coff, const float* w, const float* res, void* y,
-             bool y16, int dtype, hipStream_t stream) {
-  if (dtype != CODON_F32) return head_fwd_c8(B, H, W, x, x_ctotal, x_coff, w, res, y, y16, dtype, stream);
-  return head_launch<float>(B, H, W, (const float*)x, x_ctotal, x_coff, w, res, (float*)y, stream);
+             bool y16, int dtype, const int* bad, hipStream_t stream) {
+  if (dtype != CODON_F32) return head_fwd_c8(B, H, W, x, x_ctotal, x_coff, w, res, y, y16, dtype, bad, stream);
+  return head_launch<float>(B, H, W, (const float*)x, x_ctotal, x_coff, w, res, (float*)y, bad, stream);
 }
 
 // ---- weight gradient of the 1->64 / 64->1 3x3 convs ----------------------------------------------

@@ -40,12 +40,16 @@ __device__ __forceinline__ unsigned long long wsum_wave_sum(unsigned long long v
 
 __global__ __launch_bounds__(WS_THREADS) void wsum_kernel(const WsumArgs a, unsigned long long* __restrict__ ws,
                                                            unsigned long long* __restrict__ ref, int mode,
-                                                           int* __restrict__ flag) {
+                                                           int* __restrict__ flag, int* __restrict__ zero, int nzero) {
   __shared__ unsigned long long red[WS_THREADS / 64];
   __shared__ unsigned s_nvec[CODON_WSUM_MAX + 1];
   __shared__ const u32x4* s_data[CODON_WSUM_MAX];
   __shared__ bool last;
   const int tid = threadIdx.x;
+  // this launch opens every forward on the forward's stream: it also clears the per-image words of the non-finite input
+  // guard (stencil.hip) -- no launch of their own, and inside a captured graph with the rest
+  if (zero && blockIdx.x == 0)
+    for (int i = tid; i < nzero; i += WS_THREADS) zero[i] = 0;
   if (tid <= CODON_WSUM_MAX) s_nvec[tid] = a.nvec[tid];
   if (tid < CODON_WSUM_MAX) s_data[tid] = a.data[tid];
   __syncthreads();
@@ -103,7 +107,8 @@ __global__ __launch_bounds__(WS_THREADS) void wsum_kernel(const WsumArgs a, unsi
 
 size_t weight_checksum_workspace_bytes() { return (size_t)(WS_BLOCKS + 2) * sizeof(unsigned long long); }
 
-int weight_checksum(const codon_wsum_desc* d, void* ws, unsigned long long* ref, int mode, int* flag, hipStream_t s) {
+int weight_checksum(const codon_wsum_desc* d, void* ws, unsigned long long* ref, int mode, int* flag, int* zero, int nzero,
+                    hipStream_t s) {
   WsumArgs a;
   a.n = d->n;
   a.nvec[0] = 0;
@@ -115,7 +120,7 @@ int weight_checksum(const codon_wsum_desc* d, void* ws, unsigned long long* ref,
     a.data[t] = nullptr;
     a.nvec[t + 1] = a.nvec[d->n];
   }
-  hipLaunchKernelGGL(wsum_kernel, dim3(WS_BLOCKS), dim3(WS_THREADS), 0, s, a, (unsigned long long*)ws, ref, mode, flag);
+  hipLaunchKernelGGL(wsum_kernel, dim3(WS_BLOCKS), dim3(WS_THREADS), 0, s, a, (unsigned long long*)ws, ref, mode, flag, zero, nzero);
   return check_launch("weight_checksum");
 }
 

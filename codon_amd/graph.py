@@ -44,6 +44,15 @@ class GraphedCODON:
         g = getattr(self.model, "_wguard", None)
         self._guard_refs = (g.flag, list(g.states.values())) if g is not None else None
         self._flag_np = g.flag_np if g is not None else None
+        # ... and of the non-finite input guard (model._InputGuard): the captured stems store into the model's two pinned host
+        # words (only ever zeroed in place, so the captured address stays the live one) and into per-image device words from
+        # the graph's pool, which the captured checksum launch (or memset) zeroes on every replay
+        ig = self.model.__dict__.get("_iguard")
+        self._nf_mode = self.model._nf_mode() if hasattr(self.model, "_nf_mode") else "ignore"
+        self._nf_guard = ig
+        self._nf_refs = (ig.words, list(ig.captured)) if ig is not None else None
+        if ig is not None:
+            ig.captured.clear()
 
     def _weight_tags(self):
         return [(p.data_ptr(), p._version) for p in self.model.parameters()]
@@ -70,6 +79,10 @@ class GraphedCODON:
         if self.stale():
             raise RuntimeError("GraphedCODON: the model's parameters changed after capture (visibly, or through `.data`: "
                                "stale packed weights were replayed); build a new GraphedCODON")
+        if self._nf_mode == "raise" and self._nf_guard is not None:
+            # a replay (or an eager forward of the model) since the last report ran on a non-finite input: one host read per
+            # word, no synchronisation -- the offending replay has been enqueued by then, this call raises
+            self._nf_guard.report(False, " [GraphedCODON replay]")
         self.x.copy_(x)
         self.y.copy_(y)
         self.graph.replay()

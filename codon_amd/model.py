@@ -144,7 +144,9 @@ class _WeightGuard:
         self.flag = None
         self.flag_np = None
 
-    def run(self, model, dev):
+    def run(self, model, dev, clear=None, nclear: int = 0) -> bool:
+        """clear / nclear: int32 words on `dev` the launch also zeroes (the input guard's per-image words).  True when the
+        launch went out (False: guard disabled for these weights -- the caller zeroes them itself)."""
         import ctypes as C
         import threading
         if self.tripped():
@@ -159,7 +161,7 @@ class _WeightGuard:
             self.disabled = any((w.data_ptr() % 16) or ((w.numel() * w.element_size()) % 16) or not w.is_contiguous()
                                 for w in ws)
         if self.disabled:
-            return
+            return False
         if self.flag is None:
             self.flag = torch.zeros(1, dtype=torch.int32).pin_memory()
             self.flag_np = self.flag.numpy()
@@ -193,10 +195,176 @@ class _WeightGuard:
             st[3], mode = (donor[3], 1) if donor is not None else (st[1], 0)
         ref = st[3]
         with torch.cuda.device(dev):
-            L.check(lib.codon_weight_checksum(C.byref(st[2]), C.c_void_p(st[1].data_ptr()),
-                                              C.c_void_p(ref.data_ptr() + 8 * (ref.numel() - 1)), mode,
-                                              C.c_void_p(self.flag.data_ptr()), C.c_void_p(stream.cuda_stream)),
+            L.check(lib.codon_weight_checksum_clear(C.byref(st[2]), C.c_void_p(st[1].data_ptr()),
+                                                    C.c_void_p(ref.data_ptr() + 8 * (ref.numel() - 1)), mode,
+                                                    C.c_void_p(self.flag.data_ptr()),
+                                                    C.c_void_p(clear.data_ptr()) if clear is not None else None,
+                                                    nclear if clear is not None else 0, C.c_void_p(stream.cuda_stream)),
                     "weight_checksum")
+        return True
+
+
+# the non-finite input guard of the stems; 0 = "ignore" is the default mode (A/B of its cost only)
+INPUT_GUARD = _os.environ.get("CODON_INPUT_GUARD", "1") != "0"
+NONFINITE_MODES = ("raise", "propagate", "ignore")
+
+
+def default_nonfinite_mode() -> str:
+    return "raise" if INPUT_GUARD else "ignore"
+
+
+class NonFiniteInputError(RuntimeError):
+    """A forward ran on an input that holds NaN, +Inf or -Inf.  .depth / .guidance: which input (x / y) the stems saw it in."""
+
+    def __init__(self, depth: bool, guidance: bool, where: str = ""):
+        self.depth, self.guidance = bool(depth), bool(guidance)
+        which = " and ".join(n for n, f in (("the depth input x", depth), ("the guidance input y", guidance)) if f)
+        super().__init__(
+            f"codon_amd: {which} of the previous forward(s) held a non-finite value (NaN or +-Inf){where} -- the forward(s) "
+            "enqueued since the last check ran on it and returned an all-NaN map for every image that held one.  Mask such "
+            "pixels before the call, or choose model.set_nonfinite_inputs('propagate') (all-NaN maps, "
+            "nothing raised) or 'ignore' (no detection)")
+
+
+class _InputGuard:
+    """State of the non-finite input guard of one model.  `words`: two int32 words in pinned host memory --
+    [0] depth, [1] guidance -- that the stems store 1 to; allocated once and only ever zeroed IN PLACE, so the address a
+    captured hipGraph carries stays valid.  `bad`: the per-image device words the stems mark and the head reads, private to
+    a (thread, stream) like the weight guard's workspace, because they are ordered by the stream they are used on."""
+
+    def __init__(self):
+        self.words = None
+        self.words_np = None
+        self.words_ptr = None
+        self.bad = {}              # (thread id, stream handle) -> int32 tensor on the launch device
+        self.devices = set()       # every device a guarded launch went to
+        self.home = None           # device of the words' owner (nn.DataParallel replicas elsewhere run unguarded)
+        self.captured = []         # `bad` tensors allocated under a hipGraph capture (GraphedCODON keeps them)
+
+    def host_words(self):
+        if self.words is None:
+            self.words = torch.zeros(2, dtype=torch.int32).pin_memory()
+            self.words_np = self.words.numpy()
+            self.words_ptr = self.words.data_ptr()
+        return self.words
+
+    def bad_words(self, dev, B: int) -> torch.Tensor:
+        import threading
+        self.devices.add(dev)
+        if torch.cuda.is_current_stream_capturing():
+            # the graph's own pool, never cached (see _tail_counters); no fill launch: the captured checksum launch (or memset)
+            # zeroes it on every replay.  Held here so that the pool cannot hand the words to a later tensor of the capture.
+            t = torch.empty((B,), dtype=torch.int32, device=dev)
+            self.captured.append(t)
+            del self.captured[:-8]
+            return t
+        key = (threading.get_ident(), ops._stream(dev))      # the raw handle: no Stream object per forward
+        t = self.bad.get(key)
+        if t is None or t.numel() < B or t.device != dev:
+            _prune_dead_threads(self.bad, 0)
+            t = self.bad[key] = torch.zeros((max(B, 64),), dtype=torch.int32, device=dev)
+        return t
+
+    def tripped(self):
+        w = self.words_np
+        return (bool(w[0]), bool(w[1])) if w is not None else (False, False)
+
+    def report(self, synchronize: bool, where: str = ""):
+        """Raise NonFiniteInputError if a word is set.  Reporting consumes the trip: the devices are synchronised first (no
+        stem of a forward enqueued so far can store after the words are cleared), the words are zeroed in place."""
+        if self.words_np is None:
+            return
+        if synchronize and torch.cuda.is_available():
+            for d in self.devices:
+                torch.cuda.synchronize(d)
+        d, g = self.tripped()
+        if not (d or g):
+            return
+        if torch.cuda.is_available():
+            for dv in self.devices:
+                torch.cuda.synchronize(dv)
+        d2, g2 = self.tripped()
+        self.words_np[:] = 0
+        raise NonFiniteInputError(d or d2, g or g2, where)
+
+
+class _NonFiniteMixin:
+    """set_nonfinite_inputs / check_inputs and the per-forward plumbing, shared by CODONNet, CODONNet16 and the ablation nets."""
+
+    def set_nonfinite_inputs(self, mode: str):
+        """What a forward does with an input image that holds NaN, +Inf or -Inf (depth sensors and .npy / EXR depth files mark
+        holes that way).  The reference returns an all-NaN map for such an image and leaves the rest of the batch untouched.
+          "raise" (default): the stems detect it on the device, the head stores the all-NaN map, and the NEXT forward, graph
+              replay or check_inputs() raises NonFiniteInputError (no synchronisation: the offending forward has been enqueued
+              by then, as with the weight guard);
+          "propagate": the all-NaN map for every such image, bit-identical maps for the others, nothing raised or read on the host;
+          "ignore": no detection (the behaviour before this guard: a finite-looking, wrong map).
+        On finite inputs the three modes return the same bits.  CODON_INPUT_GUARD=0 makes "ignore" the default."""
+        if mode not in NONFINITE_MODES:
+            raise ValueError(f"codon_amd: set_nonfinite_inputs({mode!r}): one of {NONFINITE_MODES}")
+        self.__dict__["_nonfinite_mode"] = mode
+        return self
+
+    @property
+    def nonfinite_inputs(self) -> str:
+        """The mode in force: what set_nonfinite_inputs chose, else the default ("raise"; "ignore" with CODON_INPUT_GUARD=0)."""
+        return self._nf_mode()
+
+    def _nf_mode(self) -> str:
+        return self.__dict__.get("_nonfinite_mode") or default_nonfinite_mode()
+
+    def _nf_state(self) -> "_InputGuard":
+        g = self.__dict__.get("_iguard")
+        if g is None:
+            g = self.__dict__["_iguard"] = _InputGuard()
+        return g
+
+    def check_inputs(self, synchronize: bool = True):
+        """Raise NonFiniteInputError if a forward since the last report ran on a non-finite input ("raise" mode).
+        synchronize=True waits for the devices first, so every forward enqueued so far has been judged."""
+        g = self.__dict__.get("_iguard")
+        if g is not None:
+            g.report(synchronize)
+        return self
+
+    def _nf_check(self):
+        """Start of every public forward: report a trip of an earlier forward (one host read per word, no synchronisation).
+        Never called under a hipGraph capture (GraphedCODON drives _forward_impl)."""
+        g = self.__dict__.get("_iguard")
+        if g is None:
+            return
+        w = g.words_np
+        if w is None or not (w[0] or w[1]):
+            return                            # the whole cost on the usual path: two reads of host memory
+        if self._nf_mode() == "raise" and not torch.cuda.is_current_stream_capturing():
+            g.report(False)
+
+    def _nf_begin(self, dev, B: int):
+        """(bad, address of the depth word, address of the guidance word) for this forward's stems and head -- (None, None,
+        None) in "ignore" mode and for nn.DataParallel replicas on another device than the module's own.  `bad` still has to
+        be zeroed on the forward's stream: _nf_zero."""
+        mode = self._nf_mode()
+        if mode == "ignore":
+            return None, None, None
+        g = self._nf_state()
+        if self.__dict__.get("_no_guard", False) and g.home is not None and torch.device(dev) != g.home:
+            return None, None, None          # an nn.DataParallel replica on another device than the module's own
+        bad = g.bad_words(dev, B)
+        if mode != "raise":
+            return bad, None, None
+        p = g.words_ptr
+        if p is None:
+            g.host_words()
+            p = g.words_ptr
+        return bad, p, p + 4
+
+    def _nf_open(self, dev, B: int):
+        """The guard launches that open a forward: the weight checksum -- which also zeroes `bad` -- or, where that launch is
+        absent (CODON_WEIGHT_GUARD=0, nn.DataParallel replicas, a guard disabled for unaligned weights), a memset."""
+        bad, wd, wg = self._nf_begin(dev, B)
+        if not self._guard(dev, clear=bad, nclear=B) and bad is not None:
+            bad[:B].zero_()
+        return bad, wd, wg
 
 
 class Conv2dParams(nn.Module):
@@ -362,7 +530,7 @@ _MAIN_CONVS = [  # (name, cin, cout, k) in the reference's registration order, C
 _MFMA_CONVS = [n for n, ci, co, k in _MAIN_CONVS if ci > 1 and co > 1]
 
 
-class _CODONBase(nn.Module):
+class _CODONBase(_NonFiniteMixin, nn.Module):
     _HAS_UNUSED_GATE5 = True
     _warned_fp16_eval = False
 
@@ -472,14 +640,15 @@ class _CODONBase(nn.Module):
             g.reset()
         return self
 
-    def _guard(self, dev):
-        """One checksum launch per forward over the 17 MFMA conv weights (see _WeightGuard)."""
+    def _guard(self, dev, clear=None, nclear: int = 0) -> bool:
+        """One checksum launch per forward over the 17 MFMA conv weights (see _WeightGuard); it also zeroes the `clear` words
+        (the input guard's).  False when no launch went out."""
         if not WEIGHT_GUARD or self.__dict__.get("_no_guard", False):
-            return
+            return False
         g = self.__dict__.get("_wguard")
         if g is None:
             g = self._wguard = _WeightGuard()
-        g.run(self, dev)
+        return g.run(self, dev, clear, nclear)
 
     def check_packed(self, synchronize: bool = True):
         """Raise if a forward since the last (re)pack ran on stale packed weights (a `.data` write the cache key cannot
@@ -514,6 +683,7 @@ class _CODONBase(nn.Module):
         d = self.__dict__.copy()
         d["_pack_cache"] = {}
         d["_wguard"] = None
+        d.pop("_iguard", None)               # pinned words, device words: per process, per object (the mode itself stays)
         d.pop("_grad_sink", None)            # a weakref to the GradSync that owns the gradients: per process, per object
         return d
 
@@ -525,6 +695,17 @@ class _CODONBase(nn.Module):
         # nn.DataParallel builds fresh replicas (fresh weight copies, empty pack cache) for EVERY forward: nothing can be
         # stale in one, and a guard per call would cost a pinned allocation each time
         r._no_guard = True
+        # the input guard: replicas share THIS module's state (no pinned allocation per call); the replica on the module's own
+        # device reports into its words, replicas on other devices run unguarded (_nf_begin)
+        if self._nf_mode() != "ignore" and torch.cuda.is_available():
+            g = self._nf_state()
+            w = self._modules["input"]._parameters.get("weight")
+            g.home = w.device if (w is not None and w.is_cuda) else torch.device("cuda", torch.cuda.current_device())
+            if self._nf_mode() == "raise":
+                g.host_words()
+            r.__dict__["_iguard"] = g
+        else:
+            r.__dict__.pop("_iguard", None)
         return r
 
     # -- forward ---------------------------------------------------------------------------
@@ -537,6 +718,7 @@ class _CODONBase(nn.Module):
         adt = self._act_dtype()
         if x.dtype not in (torch.float32, torch.bfloat16, torch.float16) or y.dtype != x.dtype:
             raise NotImplementedError(f"codon_amd.CODONNet: input dtype {x.dtype} not supported (fp32, bf16, fp16)")
+        self._nf_check()
         if x.shape[0] == 0:
             return self._empty_batch(x, y)
         if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad or
@@ -584,7 +766,8 @@ class _CODONBase(nn.Module):
         B, _, H, W = x.shape
         dev = x.device
         self.check_supported()
-        self._guard(dev)
+        # the weight checksum opens the forward and zeroes the input guard's per-image words on the way
+        nf_bad, nf_wd, nf_wg = self._nf_open(dev, B)
         adt = self._act_dtype()
         new = lambda c: ops.new_act(B, c, H, W, adt, dev)
         P = self._packed
@@ -650,13 +833,13 @@ class _CODONBase(nn.Module):
         pair = lambda: ops.conv_pair(dev, pairs)
         t64c = new(64) if (keep or pairs) else t64
         if pairs:
-            ops.stem_pair(x, w_in, Slice(t64), y, w_in_c, Slice(t64c))      # both stems as one launch
+            ops.stem_pair(x, w_in, Slice(t64), y, w_in_c, Slice(t64c), nf_bad, nf_wd, nf_wg)      # both stems as one launch
         else:
-            ops.stem(x, w_in, Slice(t64))
+            ops.stem(x, w_in, Slice(t64), nf_bad, nf_wd)
         with pair():
             conv(Slice(t64), "conv_input", Slice(in2, 0, 64), 3, relu=True)
             if not pairs:
-                ops.stem(y, w_in_c, Slice(t64c))
+                ops.stem(y, w_in_c, Slice(t64c), nf_bad, nf_wg)
             conv(Slice(t64c), "conv_input_c", Slice(in2, 64, 64), 3, relu=True)
         inputs, inputs_c = Slice(in2, 0, 64), Slice(in2, 64, 64)
         if keep:
@@ -829,10 +1012,10 @@ class _CODONBase(nn.Module):
         conv(Slice(f), "conv11", Slice(t), 3, relu=True)
         if out_dtype is not None and out_dtype != torch.float32 and out_dtype == adt:
             outp = torch.empty(x.shape, dtype=out_dtype, device=dev)     # the head rounds once, in its store
-            ops.head(Slice(t), w_out, x, outp)
+            ops.head(Slice(t), w_out, x, outp, nf_bad)
         else:
             outp = torch.empty_like(x)
-            ops.head(Slice(t), w_out, x, outp)
+            ops.head(Slice(t), w_out, x, outp, nf_bad)
             if out_dtype is not None and out_dtype != torch.float32:
                 outp = outp.to(out_dtype)     # e.g. bf16 inputs to an fp32 model: not the reference's use, one ATen cast
         if keep:
@@ -850,7 +1033,7 @@ class CODONNet16(_CODONBase):
     _HAS_UNUSED_GATE5 = False
 
 
-class BaseNet_RMCR_fuseRMCR(nn.Module):
+class BaseNet_RMCR_fuseRMCR(_NonFiniteMixin, nn.Module):
     """Conv-only ablation of the paper (no CAC gates, the two streams never interact before conv7):
     /root/reference/CODON_X16/CODON_x16.py:16-90.  Same 19 bias-free convs, same kernels; inference only."""
 
@@ -891,10 +1074,11 @@ class BaseNet_RMCR_fuseRMCR(nn.Module):
             raise NotImplementedError("BaseNet_RMCR_fuseRMCR: inference only; call under torch.no_grad()")
         if x.shape[0] == 0:
             return x.new_zeros(x.shape)         # empty batch: an empty map, as the reference's ops return
+        self._nf_check()
         idt = x.dtype
         x, y = x.float().contiguous(), y.float().contiguous()
         B, _, H, W = x.shape
-        self._guard(x.device)
+        nf_bad, nf_wd, nf_wg = self._nf_open(x.device, B)
         adt = self._act_dtype()
         new = lambda c: ops.new_act(B, c, H, W, adt, x.device)
         f32 = lambda t: t if t.dtype == torch.float32 else t.float()
@@ -905,7 +1089,7 @@ class BaseNet_RMCR_fuseRMCR(nn.Module):
 
         def stream(img, w_in, n_ci, c3x3, c5x5, first5, n3, nconf, out_slice):      # :53-74
             inputs = new(64)
-            ops.stem(img, f32(getattr(self, w_in).weight), Slice(t64))
+            ops.stem(img, f32(getattr(self, w_in).weight), Slice(t64), nf_bad, nf_wd if img is x else nf_wg)
             ops.conv2d(Slice(t64), P(n_ci), Slice(inputs), 3, relu=True, f16x3=S3)
             cur = Slice(inputs)
             for i in range(5):
@@ -928,7 +1112,7 @@ class BaseNet_RMCR_fuseRMCR(nn.Module):
             f = fA
         ops.conv2d(Slice(f), P("conv11"), Slice(t64), 3, relu=True, f16x3=S3)                 # :87
         out = torch.empty_like(x)
-        ops.head(Slice(t64), f32(self.output.weight), x, out)                       # :88-89
+        ops.head(Slice(t64), f32(self.output.weight), x, out, nf_bad)               # :88-89
         return out if idt == torch.float32 else out.to(idt)
 
 
@@ -951,12 +1135,13 @@ class BaseNet_RMCR_fuseRMCR_cross(_CODONBase):
             raise NotImplementedError("BaseNet_RMCR_fuseRMCR_cross: inference only; call under torch.no_grad()")
         if x.shape[0] == 0:
             return x.new_zeros(x.shape)         # empty batch: an empty map, as the reference's ops return
+        self._nf_check()
         idt = x.dtype
         x, y = x.float().contiguous(), y.float().contiguous()
         B, _, H, W = x.shape
         dev = x.device
         self.check_supported()
-        self._guard(dev)
+        nf_bad, nf_wd, nf_wg = self._nf_open(dev, B)
         adt = self._act_dtype()
         new = lambda c: ops.new_act(B, c, H, W, adt, dev)
         f32 = lambda t: t if t.dtype == torch.float32 else t.float()
@@ -967,9 +1152,9 @@ class BaseNet_RMCR_fuseRMCR_cross(_CODONBase):
         conv = lambda xs, name, ys, k, **kw: ops.conv2d(xs, P(name), ys, k, f16x3=self._split(k), **kw)
 
         in2, t64, stage, pre2, oc = new(128), new(64), new(128), new(128), new(128)
-        ops.stem(x, f32(self.input.weight), Slice(t64))
+        ops.stem(x, f32(self.input.weight), Slice(t64), nf_bad, nf_wd)
         conv(Slice(t64), "conv_input", Slice(in2, 0, 64), 3, relu=True)
-        ops.stem(y, f32(self.input_c.weight), Slice(t64))
+        ops.stem(y, f32(self.input_c.weight), Slice(t64), nf_bad, nf_wg)
         conv(Slice(t64), "conv_input_c", Slice(in2, 64, 64), 3, relu=True)
         nt = ops.cac_stats_tiles(H, W)
         pooled = torch.empty((B, 2, H, W), **fz)
@@ -1017,7 +1202,7 @@ class BaseNet_RMCR_fuseRMCR_cross(_CODONBase):
             f = fA
         conv(Slice(f), "conv11", Slice(t64), 3, relu=True)
         out = torch.empty_like(x)
-        ops.head(Slice(t64), f32(self.output.weight), x, out)
+        ops.head(Slice(t64), f32(self.output.weight), x, out, nf_bad)
         return out if idt == torch.float32 else out.to(idt)
 
 

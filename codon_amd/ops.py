@@ -420,33 +420,68 @@ def conv1x1_bwd(x: Slice, gy: Slice, w_packed_dgrad: torch.Tensor, gx: Slice, dw
         defer[0].add_wgrad(defer[1], ws, gy.c, x.c, 1)
 
 
-def stem(x: torch.Tensor, w: torch.Tensor, y: Slice):
+def _bad_ptr(bad: Optional[torch.Tensor], B: int, dev):
+    """The per-image words of the non-finite input guard: (>= B) int32 on the launch's device, or None."""
+    if bad is None:
+        return None
+    assert bad.dtype == torch.int32 and bad.is_contiguous() and bad.numel() >= B and bad.device == dev
+    return bad.data_ptr()
+
+
+def stem(x: torch.Tensor, w: torch.Tensor, y: Slice, bad: Optional[torch.Tensor] = None, host_word: Optional[int] = None):
+    """bad / host_word: the non-finite input guard (codon_stem_fwd_guarded) -- bad = the per-image int32 words on the device
+    (zero on entry), host_word = the ADDRESS of one int32 word in pinned host memory; both None = the plain stem."""
     lib = L.load()
     dev = _dev(x, w, y.buf)
     B, _, H, W = x.shape
     assert y.c == 64 and x.dtype == torch.float32 and w.dtype == torch.float32
     with _on(dev):
-        L.check(lib.codon_stem_fwd(B, H, W, _ptr(x), _ptr(w), _ptr(y.buf), y.ctotal, y.coff, _dt(y.buf),
-                                   _stream(dev)), "stem_fwd")
+        if bad is None and host_word is None:
+            L.check(lib.codon_stem_fwd(B, H, W, _ptr(x), _ptr(w), _ptr(y.buf), y.ctotal, y.coff, _dt(y.buf),
+                                       _stream(dev)), "stem_fwd")
+        else:
+            L.check(lib.codon_stem_fwd_guarded(B, H, W, _ptr(x), _ptr(w), _ptr(y.buf), y.ctotal, y.coff, _dt(y.buf),
+                                               _bad_ptr(bad, B, dev), host_word, _stream(dev)), "stem_fwd_guarded")
 
 
-def stem_pair(xa: torch.Tensor, wa: torch.Tensor, ya: Slice, xb: torch.Tensor, wb: torch.Tensor, yb: Slice):
-    """stem(xa, wa, ya) and stem(xb, wb, yb) as one launch (codon_stem_pair_fwd): same bits."""
+def stem_pair(xa: torch.Tensor, wa: torch.Tensor, ya: Slice, xb: torch.Tensor, wb: torch.Tensor, yb: Slice,
+              bad: Optional[torch.Tensor] = None, host_word_a: Optional[int] = None, host_word_b: Optional[int] = None):
+    """stem(xa, wa, ya) and stem(xb, wb, yb) as one launch (codon_stem_pair_fwd): same bits.  bad / host_word_a / _b: as
+    stem() -- one set of per-image words for both image sets, one host word each."""
     lib = L.load()
     dev = _dev(xa, wa, ya.buf, xb, wb, yb.buf)
     B, _, H, W = xa.shape
     assert xb.shape == xa.shape and ya.c == 64 and yb.c == 64 and ya.buf.dtype == yb.buf.dtype
     assert all(t.dtype == torch.float32 for t in (xa, wa, xb, wb))
     with _on(dev):
-        L.check(lib.codon_stem_pair_fwd(B, H, W, _ptr(xa), _ptr(wa), _ptr(ya.buf), ya.ctotal, ya.coff, _ptr(xb), _ptr(wb),
-                                        _ptr(yb.buf), yb.ctotal, yb.coff, _dt(ya.buf), _stream(dev)), "stem_pair_fwd")
+        if bad is None and host_word_a is None and host_word_b is None:
+            L.check(lib.codon_stem_pair_fwd(B, H, W, _ptr(xa), _ptr(wa), _ptr(ya.buf), ya.ctotal, ya.coff, _ptr(xb), _ptr(wb),
+                                            _ptr(yb.buf), yb.ctotal, yb.coff, _dt(ya.buf), _stream(dev)), "stem_pair_fwd")
+        else:
+            L.check(lib.codon_stem_pair_fwd_guarded(B, H, W, _ptr(xa), _ptr(wa), _ptr(ya.buf), ya.ctotal, ya.coff, _ptr(xb),
+                                                    _ptr(wb), _ptr(yb.buf), yb.ctotal, yb.coff, _dt(ya.buf),
+                                                    _bad_ptr(bad, B, dev), host_word_a, host_word_b, _stream(dev)),
+                    "stem_pair_fwd_guarded")
 
 
-def head(x: Slice, w: torch.Tensor, residual: torch.Tensor, y: torch.Tensor):
+def head(x: Slice, w: torch.Tensor, residual: torch.Tensor, y: torch.Tensor, bad: Optional[torch.Tensor] = None):
+    """bad: the per-image words the guarded stems left -- images with a set word are stored as all-NaN
+    (codon_head_fwd_guarded / _y16_guarded); None = the plain head (every backward use)."""
     lib = L.load()
     dev = _dev(x.buf, w, residual, y)
     B, H, W = _bhw(x.buf)
     assert x.c == 64 and w.dtype == torch.float32 and residual.dtype == torch.float32
+    if bad is not None:
+        bp = _bad_ptr(bad, B, dev)
+        with _on(dev):
+            if y.dtype != torch.float32:
+                assert is_c8(x.buf.dtype) and y.dtype == x.buf.dtype and y.is_contiguous()
+                L.check(lib.codon_head_fwd_y16_guarded(B, H, W, _ptr(x.buf), x.ctotal, x.coff, _ptr(w), _ptr(residual),
+                                                       _ptr(y), _dt(x.buf), bp, _stream(dev)), "head_fwd_y16_guarded")
+            else:
+                L.check(lib.codon_head_fwd_guarded(B, H, W, _ptr(x.buf), x.ctotal, x.coff, _ptr(w), _ptr(residual), _ptr(y),
+                                                   _dt(x.buf), bp, _stream(dev)), "head_fwd_guarded")
+        return
     if y.dtype != torch.float32:
         # 16-bit output map of a 16-bit model (codon_head_fwd_y16): the fp32 result rounded once in the store
         assert is_c8(x.buf.dtype) and y.dtype == x.buf.dtype and y.is_contiguous()

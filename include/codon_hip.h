@@ -290,6 +290,35 @@ int codon_head_fwd_y16(int32_t batch, int32_t height, int32_t width, const void*
                        int32_t x_coff, const float* w_oihw, const float* residual, void* y16,
                        int32_t dtype, codon_stream_t stream);
 
+/* ---- non-finite input guard: the stems detect, the head poisons -------------------------------------------------------
+ * The reference turns ONE NaN / +Inf / -Inf pixel of x or y into an all-NaN map for that image and leaves the other images
+ * of the batch untouched (torch's ReLU keeps NaN; the global pools of the first CAC block, CAC_module.py:43,47, spread it
+ * over every channel; the gate, CODON_x4.py:89-91, over every pixel).  The kernels' ReLUs and pools are IEEE maxNum and
+ * would drop it.  The stems read every input pixel exactly once as a centre pixel, so they test it there ("exponent all
+ * ones" on the fp32 word: denormals, zeros, +-FLT_MAX pass) and report to
+ *   bad:        (batch) int32 words in DEVICE memory; bad[b] = 1 for the image the pixel belongs to.  ZERO on entry:
+ *               cleared by the caller, or by codon_weight_checksum_clear, the launch that opens a forward;
+ *   host_word*: ONE int32 word each in HOST-VISIBLE (pinned, device-mapped) memory -- a relaxed system-scope store of 1, as
+ *               codon_weight_checksum's flag; polled by the caller without synchronising, never cleared by a kernel.
+ * Either pointer may be NULL; with all of them NULL the guarded entry IS the plain one (which is defined that way).  The
+ * stems' outputs are the plain entries' bit for bit in every case.
+ * Heads: with bad != NULL and bad[b] != 0 every element of image b is stored as a quiet NaN of the output's type; images
+ * with bad[b] == 0 are stored as by the plain entry.  Gradients are no inputs of the network: the backward's uses of these
+ * kernels (codon_stencil_1to64, codon_head_fwd on dL/dy) go through the plain entries. */
+int codon_stem_fwd_guarded(int32_t batch, int32_t height, int32_t width, const float* x, const float* w_oihw, void* y,
+                           int32_t y_ctotal, int32_t y_coff, int32_t dtype, int32_t* bad, int32_t* host_word,
+                           codon_stream_t stream);
+int codon_stem_pair_fwd_guarded(int32_t batch, int32_t height, int32_t width, const float* xa, const float* wa_oihw, void* ya,
+                                int32_t ya_ctotal, int32_t ya_coff, const float* xb, const float* wb_oihw, void* yb,
+                                int32_t yb_ctotal, int32_t yb_coff, int32_t dtype, int32_t* bad, int32_t* host_word_a,
+                                int32_t* host_word_b, codon_stream_t stream);
+int codon_head_fwd_guarded(int32_t batch, int32_t height, int32_t width, const void* x, int32_t x_ctotal, int32_t x_coff,
+                           const float* w_oihw, const float* residual, float* y, int32_t dtype, const int32_t* bad,
+                           codon_stream_t stream);
+int codon_head_fwd_y16_guarded(int32_t batch, int32_t height, int32_t width, const void* x, int32_t x_ctotal,
+                               int32_t x_coff, const float* w_oihw, const float* residual, void* y16, int32_t dtype,
+                               const int32_t* bad, codon_stream_t stream);
+
 /* ---- CAC gate (HBM-bound) -----------------------------------------------------------------
  * Fcat = cat(out_c, out) is never materialised: pre_c (colour, channels 0..63 of Fcat) and pre
  * (depth, channels 64..127) are passed separately (CODON_x4.py:85).
@@ -494,6 +523,10 @@ typedef struct codon_wsum_desc {
 size_t codon_weight_checksum_workspace_bytes(void);
 int codon_weight_checksum(const codon_wsum_desc* desc, void* ws, uint64_t* ref, int32_t mode, int32_t* flag,
                           codon_stream_t stream);
+/* the same launch, which also stores 0 to clear[0 .. nclear): the `bad` words of the non-finite input guard above are
+ * zeroed by the launch that opens the forward anyway, not by one of their own.  clear may be NULL (nclear = 0). */
+int codon_weight_checksum_clear(const codon_wsum_desc* desc, void* ws, uint64_t* ref, int32_t mode, int32_t* flag,
+                                int32_t* clear, int32_t nclear, codon_stream_t stream);
 
 /* ---- the small fp32-arithmetic parameters of a 16-bit model as one flat fp32 buffer ------------------------------------
  * `model.cuda().half()` (/root/reference/CODON_X4/test.py:52) keeps the stems, the head and the gate tensors in 16 bits;
