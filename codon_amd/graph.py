@@ -39,12 +39,15 @@ class GraphedCODON:
         # they were packed from, so a replay after a weight update is refused instead of silently stale
         self._packed_refs = [v[1] for v in self.model._pack_cache.values()]
         self._tags = self._weight_tags()
-        # ... and of the weight guard's workspace, reference slot and host-visible flag word (model._WeightGuard): the captured
-        # checksum launch compares on every replay and reports into THIS flag word, whatever the model's guard does later
+        # ... and of the weight guard's workspace, reference slot and host-visible flag word (guards._WeightGuard): the captured
+        # checksum launch compares on every replay and reports into THIS flag word, whatever the model's guard does later.
+        # The capture's own state comes from the graph's pool and is never cached (guards.PerStream): `captured` hands it over
         g = getattr(self.model, "_wguard", None)
-        self._guard_refs = (g.flag, list(g.states.values())) if g is not None else None
+        self._guard_refs = (g.flag, list(g.states.values()) + list(g.captured)) if g is not None else None
+        if g is not None:
+            g.captured.clear()
         self._flag_np = g.flag_np if g is not None else None
-        # ... and of the non-finite input guard (model._InputGuard): the captured stems store into the model's two pinned host
+        # ... and of the non-finite input guard (guards._InputGuard): the captured stems store into the model's two pinned host
         # words (only ever zeroed in place, so the captured address stays the live one) and into per-image device words from
         # the graph's pool, which the captured checksum launch (or memset) zeroes on every replay
         ig = self.model.__dict__.get("_iguard")

@@ -8,22 +8,26 @@ Mirrors (names, constructor, forward signature, state_dict keys/shapes/order, in
 
 The sub-modules below hold PARAMETERS ONLY.  All arithmetic of forward() runs in
 libcodon_hip.so (see include/codon_hip.h); there is no eager / CPU fallback -- CPU tensors raise.
+
+Here: the A/B switches, the schedule plan (plan_forward), the parameter holders, the four nets; guards.py: the two device-side
+guards and the per-stream cache.
 """
 from __future__ import annotations
 
+import contextlib
 import math
+import os as _os
 import warnings
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .guards import (NONFINITE_MODES, NonFiniteInputError, PerStream, _InputGuard, _NonFiniteMixin, _STALE_MSG,  # noqa: F401
+                     _WeightGuard, default_nonfinite_mode)
 from .ops import Slice
-
-
-import os as _os
 
 # inference, 16-bit tensors: form the gate-apply in the consuming convs' staging (True) or as a pass (False); A/B switch
 GATED_16BIT = _os.environ.get("CODON_GATED16", "1") != "0"
@@ -50,321 +54,94 @@ CAC_TAIL = _os.environ.get("CODON_CAC_TAIL", "1") != "0"
 # fp32, images of at most 32 768 pixels: the CAC statistics out of the chained conv's epilogue; 0 = the statistics pass (A/B)
 FUSED_STATS_F32 = _os.environ.get("CODON_FUSED_STATS_F32", "1") != "0"
 CAC_TAIL_MAX_PIXELS = 1 << 21
-_HALF_STREAMS: Dict[tuple, tuple] = {}
-_TAIL_COUNTERS: Dict[tuple, torch.Tensor] = {}
-
-
-def _tail_counters(dev, B: int) -> torch.Tensor:
-    """The arrival counters of codon_cac_tail_fwd: zero on entry, left at zero by every launch -- so ONE zeroed buffer per
-    (device, calling stream, host thread) serves every forward instead of a torch.zeros (an ATen fill launch, 5 us of a 2 ms
-    one-image forward) per call.  Private to the (stream, thread) like the side streams above: launches of independent
-    callers never count in each other's words; a larger batch replaces the buffer."""
-    import threading
-    i = dev.index if dev.index is not None else torch.cuda.current_device()
-    key = (i, torch.cuda.current_stream(dev).cuda_stream, threading.get_ident())
-    t = _TAIL_COUNTERS.get(key)
-    if t is None or t.numel() < B:
-        if torch.cuda.is_current_stream_capturing():
-            # never cache an allocation made inside a hipGraph capture (it belongs to the graph's pool)
-            return torch.zeros((B,), dtype=torch.int32, device=dev)
-        _prune_dead_threads(_TAIL_COUNTERS, 2)
-        t = _TAIL_COUNTERS[key] = torch.zeros((max(B, 64),), dtype=torch.int32, device=dev)
-    return t
-
-
-def _half_chip_streams(dev, main_stream):
-    """Two side streams for the two halves of a block, private to (device, calling stream, host thread): independent
-    callers -- DataParallel replica threads, a hipGraph capture in one thread beside eager launches in another -- never
-    share a side stream, so they get neither false cross-dependencies nor a stream that is in capture mode under them.
-    (Streams created with hipExtStreamCreateWithCUMask were tried to keep the two launches on disjoint CUs: 6.0 ms
-    instead of 4.4 with ANY mask, also the full one -- the external streams' event traffic; what separates the launches
-    instead is the LDS request of the small-grid kernels, conv_mfma_f32.hip.)"""
-    import threading
-    i = dev.index if dev.index is not None else torch.cuda.current_device()
-    key = (i, main_stream.cuda_stream, threading.get_ident())
-    if key not in _HALF_STREAMS:
-        _prune_dead_threads(_HALF_STREAMS, 2)
-        _HALF_STREAMS[key] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
-    return _HALF_STREAMS[key]
-
-
-def _prune_dead_threads(table: dict, tid_index: int, keep: int = 16):
-    """Per-(thread, stream) tables -- the side streams above, _WeightGuard.states -- would grow by one entry per short-lived
-    caller thread (thread pools, nn.DataParallel's per-forward threads): before a new entry goes in, entries of threads that
-    no longer exist are dropped once the table holds more than `keep`.  Their device memory returns to the caching
-    allocator, which orders its reuse behind the work already enqueued on the stream it was used on."""
-    if len(table) < keep:
-        return
-    import threading
-    alive = {t.ident for t in threading.enumerate()}
-    for k in [k for k in table if k[tid_index] not in alive]:
-        del table[k]
-
-
 # debug: re-pack on every cache hit and compare, so a write through `.data` after the first forward (the reference's own
 # init idiom is m.weight.data.normal_(), CODON_x4.py:50-53) raises IN THE SAME CALL instead of one call later (_WeightGuard)
 VERIFY_PACKED = _os.environ.get("CODON_VERIFY_PACKED", "0") != "0"
 # the per-forward checksum launch of _WeightGuard; 0 = off (A/B of its cost only)
 WEIGHT_GUARD = _os.environ.get("CODON_WEIGHT_GUARD", "1") != "0"
-
-_STALE_MSG = ("codon_amd: a conv weight was written through `.data` (or another path that does not bump Tensor._version, "
-              "e.g. `m.weight.data.normal_()`) after its packed MFMA image was built -- the forward(s) since then used the "
-              "stale packed weights; call model.invalidate_packed() after such writes")
-
-
-class _WeightGuard:
-    """Default-on detector of stale packed weights.  The pack cache is keyed on (data_ptr, Tensor._version) of each weight,
-    which a write through `.data` does not change.  Every forward launches ONE small kernel (codon_weight_checksum) over
-    the raw bytes of the 17 MFMA conv weights: the first launch after the host-visible key changed records the checksum the
-    packed images are built from, every later one compares and, on a mismatch, sets a flag in pinned host memory.  The
-    host reads that word (no synchronisation) at the start of every forward / graph replay and in check_packed(): the
-    stale forward itself has already been enqueued by then, the NEXT call raises.  Per (thread, stream) state, because
-    the kernel's workspace and reference slot are ordered by the stream they are used on."""
-
-    def __init__(self):
-        self.tag = None            # host-visible key of all 17 weights the pack cache was last valid for
-        self.flag = None           # pinned int32[1], written by the kernel
-        self.flag_np = None
-        self.states = {}           # (thread id, stream handle) -> [tag, workspace, desc, tensor whose last word is the reference]
-        self.disabled = False
-        self._retired = []         # flag words / workspaces of earlier epochs (see reset)
-
-    def tripped(self) -> bool:
-        return self.flag_np is not None and bool(self.flag_np[0])
-
-    def reset(self):
-        """Forget the recorded checksums and the tripped state.  A checksum launch of the stale forward may still be in
-        flight and a captured hipGraph may still hold the addresses: the old flag word and workspaces are retired (kept
-        alive, never reused), not cleared or freed -- a late store cannot trip the NEW flag, a replay cannot write into
-        memory someone else now owns."""
-        self.tag = None
-        self._retired.append((self.flag, list(self.states.values())))
-        del self._retired[:-8]                 # bounded: each entry is a few KB
-        self.states = {}
-        self.flag = None
-        self.flag_np = None
-
-    def run(self, model, dev, clear=None, nclear: int = 0) -> bool:
-        """clear / nclear: int32 words on `dev` the launch also zeroes (the input guard's per-image words).  True when the
-        launch went out (False: guard disabled for these weights -- the caller zeroes them itself)."""
-        import ctypes as C
-        import threading
-        if self.tripped():
-            raise RuntimeError(_STALE_MSG)
-        ws = [getattr(model, n).weight for n in _MFMA_CONVS]
-        tag = tuple((w.data_ptr(), w._version, w.dtype) for w in ws) + (dev,)
-        if tag != self.tag:
-            # some weight changed visibly: EVERY packed image is rebuilt, so that all of them belong to the checksum
-            # recorded below (a partial rebuild could fold an earlier invisible write into the new reference)
-            model._pack_cache.clear()
-            self.tag = tag
-            self.disabled = any((w.data_ptr() % 16) or ((w.numel() * w.element_size()) % 16) or not w.is_contiguous()
-                                for w in ws)
-        if self.disabled:
-            return False
-        if self.flag is None:
-            self.flag = torch.zeros(1, dtype=torch.int32).pin_memory()
-            self.flag_np = self.flag.numpy()
-        stream = torch.cuda.current_stream(dev)
-        key = (threading.get_ident(), stream.cuda_stream)
-        st = self.states.get(key)
-        lib = L.load()
-        if st is None or st[1].device != dev:
-            _prune_dead_threads(self.states, 0)
-            n = lib.codon_weight_checksum_workspace_bytes() // 8 + 1          # + the reference slot (last word)
-            st = self.states[key] = [None, torch.zeros(n, dtype=torch.int64, device=dev), None, None]
-        mode = 1
-        if st[0] != tag:
-            d = L.WsumDesc()
-            d.n = len(ws)
-            for i, w in enumerate(ws):
-                d.data[i] = w.data_ptr()
-                d.bytes[i] = w.numel() * w.element_size()
-            # under hipGraph capture a recording launch would be replayed as a recording launch and never compare: take
-            # the reference another stream recorded for these very weights (GraphedCODON's warm-up runs; they are joined
-            # before the capture starts) and capture a COMPARING launch
-            donor = None
-            if torch.cuda.is_current_stream_capturing():
-                donor = next((o for o in self.states.values() if o is not st and o[0] == tag and o[1].device == dev), None)
-                if donor is None:
-                    del self.states[key]
-                    raise RuntimeError("codon_amd: hipGraph capture of a forward whose weights no eager forward has seen "
-                                       "yet -- the captured weight-checksum launch would RECORD on every replay and never "
-                                       "compare; run one forward outside the capture first (GraphedCODON does: warmup >= 1)")
-            st[0], st[2] = tag, d
-            st[3], mode = (donor[3], 1) if donor is not None else (st[1], 0)
-        ref = st[3]
-        with torch.cuda.device(dev):
-            L.check(lib.codon_weight_checksum_clear(C.byref(st[2]), C.c_void_p(st[1].data_ptr()),
-                                                    C.c_void_p(ref.data_ptr() + 8 * (ref.numel() - 1)), mode,
-                                                    C.c_void_p(self.flag.data_ptr()),
-                                                    C.c_void_p(clear.data_ptr()) if clear is not None else None,
-                                                    nclear if clear is not None else 0, C.c_void_p(stream.cuda_stream)),
-                    "weight_checksum")
-        return True
-
-
 # the non-finite input guard of the stems; 0 = "ignore" is the default mode (A/B of its cost only)
 INPUT_GUARD = _os.environ.get("CODON_INPUT_GUARD", "1") != "0"
-NONFINITE_MODES = ("raise", "propagate", "ignore")
 
 
-def default_nonfinite_mode() -> str:
-    return "raise" if INPUT_GUARD else "ignore"
+_F32, _BF16, _F16 = torch.float32, torch.bfloat16, torch.float16
 
 
-class NonFiniteInputError(RuntimeError):
-    """A forward ran on an input that holds NaN, +Inf or -Inf.  .depth / .guidance: which input (x / y) the stems saw it in."""
-
-    def __init__(self, depth: bool, guidance: bool, where: str = ""):
-        self.depth, self.guidance = bool(depth), bool(guidance)
-        which = " and ".join(n for n, f in (("the depth input x", depth), ("the guidance input y", guidance)) if f)
-        super().__init__(
-            f"codon_amd: {which} of the previous forward(s) held a non-finite value (NaN or +-Inf){where} -- the forward(s) "
-            "enqueued since the last check ran on it and returned an all-NaN map for every image that held one.  Mask such "
-            "pixels before the call, or choose model.set_nonfinite_inputs('propagate') (all-NaN maps, "
-            "nothing raised) or 'ignore' (no detection)")
+ForwardPlan = NamedTuple("ForwardPlan", [(f, bool) for f in ("fused_stats", "gated", "emit16", "pairs", "two", "tail")])
 
 
-class _InputGuard:
-    """State of the non-finite input guard of one model.  `words`: two int32 words in pinned host memory --
-    [0] depth, [1] guidance -- that the stems store 1 to; allocated once and only ever zeroed IN PLACE, so the address a
-    captured hipGraph carries stays valid.  `bad`: the per-image device words the stems mark and the head reads, private to
-    a (thread, stream) like the weight guard's workspace, because they are ordered by the stream they are used on."""
-
-    def __init__(self):
-        self.words = None
-        self.words_np = None
-        self.words_ptr = None
-        self.bad = {}              # (thread id, stream handle) -> int32 tensor on the launch device
-        self.devices = set()       # every device a guarded launch went to
-        self.home = None           # device of the words' owner (nn.DataParallel replicas elsewhere run unguarded)
-        self.captured = []         # `bad` tensors allocated under a hipGraph capture (GraphedCODON keeps them)
-
-    def host_words(self):
-        if self.words is None:
-            self.words = torch.zeros(2, dtype=torch.int32).pin_memory()
-            self.words_np = self.words.numpy()
-            self.words_ptr = self.words.data_ptr()
-        return self.words
-
-    def bad_words(self, dev, B: int) -> torch.Tensor:
-        import threading
-        self.devices.add(dev)
-        if torch.cuda.is_current_stream_capturing():
-            # the graph's own pool, never cached (see _tail_counters); no fill launch: the captured checksum launch (or memset)
-            # zeroes it on every replay.  Held here so that the pool cannot hand the words to a later tensor of the capture.
-            t = torch.empty((B,), dtype=torch.int32, device=dev)
-            self.captured.append(t)
-            del self.captured[:-8]
-            return t
-        key = (threading.get_ident(), ops._stream(dev))      # the raw handle: no Stream object per forward
-        t = self.bad.get(key)
-        if t is None or t.numel() < B or t.device != dev:
-            _prune_dead_threads(self.bad, 0)
-            t = self.bad[key] = torch.zeros((max(B, 64),), dtype=torch.int32, device=dev)
-        return t
-
-    def tripped(self):
-        w = self.words_np
-        return (bool(w[0]), bool(w[1])) if w is not None else (False, False)
-
-    def report(self, synchronize: bool, where: str = ""):
-        """Raise NonFiniteInputError if a word is set.  Reporting consumes the trip: the devices are synchronised first (no
-        stem of a forward enqueued so far can store after the words are cleared), the words are zeroed in place."""
-        if self.words_np is None:
-            return
-        if synchronize and torch.cuda.is_available():
-            for d in self.devices:
-                torch.cuda.synchronize(d)
-        d, g = self.tripped()
-        if not (d or g):
-            return
-        if torch.cuda.is_available():
-            for dv in self.devices:
-                torch.cuda.synchronize(dv)
-        d2, g2 = self.tripped()
-        self.words_np[:] = 0
-        raise NonFiniteInputError(d or d2, g or g2, where)
+def plan_forward(B: int, H: int, W: int, adt, keep: bool, split5: bool, profiling: bool, on_gpu: bool = True) -> ForwardPlan:
+    """The schedule of one CODONNet forward as a value: which launches _forward_impl issues for a (B,1,H,W) batch with
+    activations of dtype `adt`.  keep = training (every activation the backward needs is saved), split5 = the opt-in f16x3
+    convs, profiling = bench.py brackets single conv launches (ops.PROFILE is set), on_gpu = the inputs are on a HIP device.
+    Pure: the switches above are read at call time; no library call, no allocation.
+    fused_stats  the CAC statistics of a block come out of the two conv5x5 + 1x1 epilogues (no pass over Fcat).  16-bit:
+                 always.  fp32 (round 6): images of at most 32 768 pixels -- chosen by H x W ONLY, and the per-row-strip
+                 partials are tiling-invariant, so an image's bits do not depend on the batch it arrives in; larger images
+                 keep the pass (0.87 ms of a 988 ms forward at 32 x 480 x 640, against 5 x 22 us of 2.2 ms at 1 x 128 x 128).
+    gated        the gate-apply `out*ad_CAC + inputs` (:89-91,117-118) is formed inside the staging of the convs that consume
+                 it (codon_conv2d_gated_fwd) instead of a 15 GB HBM pass per block: inference in exact fp32 and (GATED_16BIT)
+                 in 16 bits; training only with emit16.
+    emit16       the conv5x5 of a sibling pair applies the gate and EMITS the gated tensor, the conv3x3 runs plain on it.
+                 16-bit training takes this route too: the emitted tensor IS the block input the backward needs, bit-identical
+                 to cac_apply's output, and the 7.5 GB apply pass is gone there as well.  Implies `gated`.
+    pairs        inference on a small grid (16-bit: at most PAIR_MAX16 tiles of 8 x 32 pixels; fp32: the small-grid kernels,
+                 fewer than 384): the depth and the colour conv of every stage as ONE launch.  Not while bench.py brackets
+                 single conv launches with HIP events: a held launch has no duration of its own.
+    two          small grids (inference) that do not pair: two HIP streams, fork before the streams of a block, join at its
+                 gate.  With the default switches a grid small enough for it (16-bit: <= 256 tiles of 8 x 32; fp32: <= 256 of
+                 4 x 32, which is <= 383 of 8 x 32) also pairs: `two` is True ONLY WHILE PROFILING, or by switch (PAIR_MAX* = 0).
+    tail         the whole gate of a block in one launch (codon_cac_tail_fwd).  fp32: it folds the tiles before it finishes
+                 the pools -- the serial order of cac_gate_kernel while every fold holds one tile, and the ONLY sensible form
+                 for the many 256-pixel tiles of a small image -- so for H W <= 32768 (above, a tile is 2048 pixels, cac.hip:
+                 more than L.CAC_FOLDS tiles), and always with fused statistics: by H x W only, never by the batch.  16-bit:
+                 bit-identical to the separate launches at any size and FASTER only while the grid is small (12 vs 25 us for
+                 one 370 x 463 image; 210 vs 147 us at 32 x 480 x 640, where the combine inside the spatial tiles re-reads
+                 four maps' halos): chosen by size, B H W <= CAC_TAIL_MAX_PIXELS."""
+    f32 = adt is _F32
+    c8 = adt is _BF16 or adt is _F16          # ops.is_c8(adt)
+    fused_stats = c8 or (FUSED_STATS_F32 and CAC_TAIL and f32 and not split5 and H * W <= 32768)
+    emit16 = GATED_EMIT and not split5 and ((c8 and GATED_16BIT) or (f32 and not keep))
+    gated = not split5 and (((not keep) and (f32 or GATED_16BIT)) or (keep and emit16))
+    emit16 = emit16 and gated
+    tiles8 = B * ((H + 7) // 8) * ((W + 31) // 32)
+    pairs = (not keep) and not profiling and tiles8 <= (PAIR_MAX16 if c8 else min(PAIR_MAX32, 383))
+    two = TWO_STREAMS and (not keep) and (not pairs) and on_gpu and (
+        tiles8 <= TWO_STREAMS_MAX16 if c8 else B * ((H + 3) // 4) * ((W + 31) // 32) <= TWO_STREAMS_MAX32)
+    tail = CAC_TAIL and ((B * H * W <= CAC_TAIL_MAX_PIXELS or f32) if fused_stats else H * W <= 32768)
+    return ForwardPlan(fused_stats, gated, emit16, pairs, two, tail)
 
 
-class _NonFiniteMixin:
-    """set_nonfinite_inputs / check_inputs and the per-forward plumbing, shared by CODONNet, CODONNet16 and the ablation nets."""
+_TAIL_COUNTERS = PerStream()
+_HALF_STREAMS = PerStream()
 
-    def set_nonfinite_inputs(self, mode: str):
-        """What a forward does with an input image that holds NaN, +Inf or -Inf (depth sensors and .npy / EXR depth files mark
-        holes that way).  The reference returns an all-NaN map for such an image and leaves the rest of the batch untouched.
-          "raise" (default): the stems detect it on the device, the head stores the all-NaN map, and the NEXT forward, graph
-              replay or check_inputs() raises NonFiniteInputError (no synchronisation: the offending forward has been enqueued
-              by then, as with the weight guard);
-          "propagate": the all-NaN map for every such image, bit-identical maps for the others, nothing raised or read on the host;
-          "ignore": no detection (the behaviour before this guard: a finite-looking, wrong map).
-        On finite inputs the three modes return the same bits.  CODON_INPUT_GUARD=0 makes "ignore" the default."""
-        if mode not in NONFINITE_MODES:
-            raise ValueError(f"codon_amd: set_nonfinite_inputs({mode!r}): one of {NONFINITE_MODES}")
-        self.__dict__["_nonfinite_mode"] = mode
-        return self
 
-    @property
-    def nonfinite_inputs(self) -> str:
-        """The mode in force: what set_nonfinite_inputs chose, else the default ("raise"; "ignore" with CODON_INPUT_GUARD=0)."""
-        return self._nf_mode()
+def _tail_counters(dev, B: int) -> torch.Tensor:
+    """The arrival counters of codon_cac_tail_fwd: zero on entry, left at zero by every launch -- so ONE zeroed buffer per
+    (device, calling stream, host thread) serves every forward instead of a torch.zeros (an ATen fill launch, 5 us of a 2 ms
+    one-image forward) per call; a larger batch replaces it.  Under capture: fresh words, held by the forward till it returns."""
+    return _TAIL_COUNTERS.get(dev, lambda capturing: torch.zeros((B if capturing else max(B, 64),), dtype=torch.int32,
+                                                                 device=dev), need=B)
 
-    def _nf_mode(self) -> str:
-        return self.__dict__.get("_nonfinite_mode") or default_nonfinite_mode()
 
-    def _nf_state(self) -> "_InputGuard":
-        g = self.__dict__.get("_iguard")
-        if g is None:
-            g = self.__dict__["_iguard"] = _InputGuard()
-        return g
+def _half_chip_streams(dev, main_stream):
+    """Two side streams for the two halves of a block, private to (device, calling stream, host thread).
+    (Streams created with hipExtStreamCreateWithCUMask were tried to keep the two launches on disjoint CUs: 6.0 ms
+    instead of 4.4 with ANY mask, also the full one -- the external streams' event traffic; what separates the launches
+    instead is the LDS request of the small-grid kernels, conv_mfma_f32.hip.)"""
+    return _HALF_STREAMS.get(dev, lambda capturing: (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)),
+                             stream=main_stream.cuda_stream)
 
-    def check_inputs(self, synchronize: bool = True):
-        """Raise NonFiniteInputError if a forward since the last report ran on a non-finite input ("raise" mode).
-        synchronize=True waits for the devices first, so every forward enqueued so far has been judged."""
-        g = self.__dict__.get("_iguard")
-        if g is not None:
-            g.report(synchronize)
-        return self
 
-    def _nf_check(self):
-        """Start of every public forward: report a trip of an earlier forward (one host read per word, no synchronisation).
-        Never called under a hipGraph capture (GraphedCODON drives _forward_impl)."""
-        g = self.__dict__.get("_iguard")
-        if g is None:
-            return
-        w = g.words_np
-        if w is None or not (w[0] or w[1]):
-            return                            # the whole cost on the usual path: two reads of host memory
-        if self._nf_mode() == "raise" and not torch.cuda.is_current_stream_capturing():
-            g.report(False)
-
-    def _nf_begin(self, dev, B: int):
-        """(bad, address of the depth word, address of the guidance word) for this forward's stems and head -- (None, None,
-        None) in "ignore" mode and for nn.DataParallel replicas on another device than the module's own.  `bad` still has to
-        be zeroed on the forward's stream: _nf_zero."""
-        mode = self._nf_mode()
-        if mode == "ignore":
-            return None, None, None
-        g = self._nf_state()
-        if self.__dict__.get("_no_guard", False) and g.home is not None and torch.device(dev) != g.home:
-            return None, None, None          # an nn.DataParallel replica on another device than the module's own
-        bad = g.bad_words(dev, B)
-        if mode != "raise":
-            return bad, None, None
-        p = g.words_ptr
-        if p is None:
-            g.host_words()
-            p = g.words_ptr
-        return bad, p, p + 4
-
-    def _nf_open(self, dev, B: int):
-        """The guard launches that open a forward: the weight checksum -- which also zeroes `bad` -- or, where that launch is
-        absent (CODON_WEIGHT_GUARD=0, nn.DataParallel replicas, a guard disabled for unaligned weights), a memset."""
-        bad, wd, wg = self._nf_begin(dev, B)
-        if not self._guard(dev, clear=bad, nclear=B) and bad is not None:
-            bad[:B].zero_()
-        return bad, wd, wg
+@contextlib.contextmanager
+def _on_half(halves, main_s, k):
+    """`with _on_half(halves, main_s, k):` runs the body on half-chip stream k, ordered after everything issued so far on the
+    main one; halves = None (one stream): on the caller's stream."""
+    if halves is None:
+        yield
+    else:
+        halves[k].wait_stream(main_s)
+        with torch.cuda.stream(halves[k]):
+            yield
 
 
 class Conv2dParams(nn.Module):
@@ -530,41 +307,23 @@ _MAIN_CONVS = [  # (name, cin, cout, k) in the reference's registration order, C
 _MFMA_CONVS = [n for n, ci, co, k in _MAIN_CONVS if ci > 1 and co > 1]
 
 
-class _CODONBase(_NonFiniteMixin, nn.Module):
-    _HAS_UNUSED_GATE5 = True
-    _warned_fp16_eval = False
+def _f32(t):
+    return t if t.dtype == torch.float32 else t.float()
+
+
+class _ConvNet(_NonFiniteMixin, nn.Module):
+    """What the four nets share: the 19 bias-free convs in the reference's registration order, their packed-weight cache with
+    its stale-weight guard, the compute-dtype / conv-precision switches, and the front door and trunk of the forwards."""
 
     def __init__(self):
         super().__init__()
         for name, ci, co, k in _MAIN_CONVS:
             setattr(self, name, Conv2dParams(ci, co, k, he_init=True))
         self.relu = nn.ReLU()
-        for i in range(5):
-            setattr(self, f"attention_c{i}", CAC_channel(128))
-        for i in range(5):
-            setattr(self, f"attention_s{i}", CAC_spatial())
-        if self._HAS_UNUSED_GATE5:  # CODON_x4.py:64-65: registered, never called
-            self.attention_c5 = ChannelGate(64)
-            self.attention_s5 = CAC_spatial()
         self._pack_cache: Dict[str, tuple] = {}
         self._wguard: Optional[_WeightGuard] = None
         self.compute_dtype: Optional[torch.dtype] = None
         self.conv_precision: str = "exact"
-        self.recompute: bool = False
-
-    def check_supported(self):
-        """Raise NotImplementedError if a gate sub-module is configured for something the kernels do not implement
-        (pool_types other than avg + max, BatchNorm / ReLU / bias in the spatial conv, other MLP shapes): run by every
-        forward on the modules as they are -- a whole-module pickle of the reference bypasses the constructors."""
-        _check_gates(self, gate5=isinstance(self, BaseNet_RMCR_fuseRMCR_cross))
-        return self
-
-    def set_recompute(self, on: bool = True):
-        """Training memory switch: do not keep the 13 `stage` tensors (cat(relu(conv1), relu(conv2)) and siblings,
-        CODON_x4.py:79,80,125 -- 128 channels each); the backward re-runs the two sibling convs from the saved block
-        input instead.  fp32 at batch 32, 480x640: 232 GB -> 167 GB of the 288 GB, for 26 extra small convs per step."""
-        self.recompute = bool(on)
-        return self
 
     def set_conv_precision(self, mode: str):
         """fp32 path only.  "exact" (default): v_mfma_f32_32x32x2_f32, bitwise fp32 fmaf chains.
@@ -593,6 +352,10 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
         if dt not in (torch.float32, torch.bfloat16, torch.float16):
             raise NotImplementedError(f"codon_amd.CODONNet: dtype {dt} not supported (fp32, bf16, fp16)")
         return dt
+
+    def _split(self, ksize: int) -> bool:
+        return (getattr(self, "conv_precision", "exact") == "f16x3" and ksize in (3, 5)
+                and self._act_dtype() == torch.float32)
 
     # -- packed weights -------------------------------------------------------------------
     def _packed(self, name: str, mode: int = L.PACK_FWD) -> torch.Tensor:
@@ -629,11 +392,10 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
         if g is not None:
             # a forward that ran on stale packed weights and has not been reported yet (the trip is seen one call late) must
             # not be forgotten with the guard's state: wait for the checksum launches enqueued so far and say so
-            if g.states and torch.cuda.is_available():
-                for d in {st[1].device for st in g.states.values()}:
+            if torch.cuda.is_available():
+                for d in g.devices():
                     torch.cuda.synchronize(d)
             if g.tripped():
-                import warnings
                 warnings.warn(_STALE_MSG + " [reported while the packed-weight cache is being invalidated: at least one "
                               "forward BEFORE this point used stale packed weights and its output is wrong]", RuntimeWarning,
                               stacklevel=2)
@@ -648,7 +410,7 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
         g = self.__dict__.get("_wguard")
         if g is None:
             g = self._wguard = _WeightGuard()
-        return g.run(self, dev, clear, nclear)
+        return g.run(self, [getattr(self, n).weight for n in _MFMA_CONVS], dev, clear, nclear)
 
     def check_packed(self, synchronize: bool = True):
         """Raise if a forward since the last (re)pack ran on stale packed weights (a `.data` write the cache key cannot
@@ -659,7 +421,7 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
             return self
         if synchronize and torch.cuda.is_available():
             # every device a checksum launch went to (the module may live on another device than the current one)
-            for d in {st[1].device for st in g.states.values()} or {torch.device("cuda", torch.cuda.current_device())}:
+            for d in g.devices() or {torch.device("cuda", torch.cuda.current_device())}:
                 torch.cuda.synchronize(d)
         if g.tripped():
             raise RuntimeError(_STALE_MSG)
@@ -674,10 +436,6 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
     def _load_from_state_dict(self, *a, **k):
         self.invalidate_packed()
         return super()._load_from_state_dict(*a, **k)
-
-    def _split(self, ksize: int) -> bool:
-        return (getattr(self, "conv_precision", "exact") == "f16x3" and ksize in (3, 5)
-                and self._act_dtype() == torch.float32)
 
     def __getstate__(self):  # pickle / deepcopy: drop the device-side cache
         d = self.__dict__.copy()
@@ -708,13 +466,87 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
             r.__dict__.pop("_iguard", None)
         return r
 
+    # -- the forwards' shared parts ---------------------------------------------------------
+    @staticmethod
+    def _check_io(x, y, who: str, no_cpu: str):
+        """The front door of every forward; who / no_cpu: the class's own wording."""
+        if x.shape != y.shape or x.dim() != 4 or x.shape[1] != 1:
+            raise RuntimeError(f"{who}expects two (B,1,H,W) tensors, got {tuple(x.shape)} and {tuple(y.shape)}")
+        if not x.is_cuda:
+            raise RuntimeError(no_cpu)
+
+    def check_supported(self):
+        return self
+
+    def _inference_only(self, x, y, schedule):
+        """The forward of the two inference-only nets: front door, fp32 inputs, opened guards (_nf_open) and launch helpers;
+        then schedule(x, y, nf, new, conv, chain) -> (f, stage, t64), the net's own part up to the fusion trunk's input f
+        (also the trunk's residual); then the trunk x 3, conv11 and the head."""
+        self._check_io(x, y, "", "codon_amd runs on MI355X only (there is no CPU fallback)")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError(f"{type(self).__name__}: inference only; call under torch.no_grad()")
+        if x.shape[0] == 0:
+            return x.new_zeros(x.shape)         # empty batch: an empty map, as the reference's ops return
+        self._nf_check()
+        idt = x.dtype
+        x, y = x.float().contiguous(), y.float().contiguous()
+        B, _, H, W = x.shape
+        dev = x.device
+        self.check_supported()
+        nf = self._nf_open(dev, B)
+        adt = self._act_dtype()
+        P = self._packed
+        S5 = self._split(5)
+        CM = L.PACK_CHAIN1X1_F16X3 if S5 else L.PACK_CHAIN1X1
+        new = lambda c: ops.new_act(B, c, H, W, adt, dev)
+        conv = lambda xs, name, ys, k, **kw: ops.conv2d(xs, P(name), ys, k, f16x3=self._split(k), **kw)
+        chain = lambda xs, n5, n1, out, residual=None: ops.conv_chain1x1(xs, P(n5), P(n1, CM), out, residual=residual, f16x3=S5)
+        f, stage, t64 = schedule(x, y, nf, new, conv, chain)
+        res, fA = f, new(64)
+        for _ in range(3):
+            conv(Slice(f), "conv8", Slice(stage, 0, 64), 5, relu=True)
+            conv(Slice(f), "conv9", Slice(stage, 64, 64), 3, relu=True)
+            chain(Slice(stage), "conv10", "confuse_fuse", Slice(fA), residual=Slice(res))
+            f = fA
+        conv(Slice(f), "conv11", Slice(t64), 3, relu=True)
+        out = torch.empty_like(x)
+        ops.head(Slice(t64), _f32(self.output.weight), x, out, nf[0])
+        return out if idt == torch.float32 else out.to(idt)
+
+
+class _CODONBase(_ConvNet):
+    _HAS_UNUSED_GATE5 = True
+    _warned_fp16_eval = False
+
+    def __init__(self):
+        super().__init__()
+        for i in range(5):
+            setattr(self, f"attention_c{i}", CAC_channel(128))
+        for i in range(5):
+            setattr(self, f"attention_s{i}", CAC_spatial())
+        if self._HAS_UNUSED_GATE5:  # CODON_x4.py:64-65: registered, never called
+            self.attention_c5 = ChannelGate(64)
+            self.attention_s5 = CAC_spatial()
+        self.recompute: bool = False
+
+    def check_supported(self):
+        """Raise NotImplementedError if a gate sub-module is configured for something the kernels do not implement
+        (pool_types other than avg + max, BatchNorm / ReLU / bias in the spatial conv, other MLP shapes): run by every
+        forward on the modules as they are -- a whole-module pickle of the reference bypasses the constructors."""
+        _check_gates(self, gate5=isinstance(self, BaseNet_RMCR_fuseRMCR_cross))
+        return self
+
+    def set_recompute(self, on: bool = True):
+        """Training memory switch: do not keep the 13 `stage` tensors (cat(relu(conv1), relu(conv2)) and siblings,
+        CODON_x4.py:79,80,125 -- 128 channels each); the backward re-runs the two sibling convs from the saved block
+        input instead.  fp32 at batch 32, 480x640: 232 GB -> 167 GB of the 288 GB, for 26 extra small convs per step."""
+        self.recompute = bool(on)
+        return self
+
     # -- forward ---------------------------------------------------------------------------
     def forward(self, x, y):  # x: HR-sized depth, y: grey guidance  (CODON_x4.py:66)
-        if x.shape != y.shape or x.dim() != 4 or x.shape[1] != 1:
-            raise RuntimeError(f"CODONNet expects two (B,1,H,W) tensors, got {tuple(x.shape)} and {tuple(y.shape)}")
-        if not x.is_cuda:
-            raise RuntimeError("codon_amd.CODONNet runs on MI355X only: move the module and inputs to 'cuda' "
-                               "(there is no CPU fallback)")
+        self._check_io(x, y, "CODONNet ", "codon_amd.CODONNet runs on MI355X only: move the module and inputs to 'cuda' "
+                                          "(there is no CPU fallback)")
         adt = self._act_dtype()
         if x.dtype not in (torch.float32, torch.bfloat16, torch.float16) or y.dtype != x.dtype:
             raise NotImplementedError(f"codon_amd.CODONNet: input dtype {x.dtype} not supported (fp32, bf16, fp16)")
@@ -762,7 +594,8 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
         """Kernel schedule of CODONNet.forward.  With `save` (a dict) every activation the
         backward needs is kept in fresh buffers; without it buffers are reused across blocks.
         x, y: fp32, or 16-bit (converted here, in the launch that converts a 16-bit model's small parameters);
-        out_dtype: dtype of the returned map (default fp32; a 16-bit type only with 16-bit activations of that type)."""
+        out_dtype: dtype of the returned map (default fp32; a 16-bit type only with 16-bit activations of that type).
+        Which launches go out is decided once, by plan_forward."""
         B, _, H, W = x.shape
         dev = x.device
         self.check_supported()
@@ -772,11 +605,13 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
         new = lambda c: ops.new_act(B, c, H, W, adt, dev)
         P = self._packed
         keep = save is not None
+        split5 = self._split(5)
+        fused_stats, gated, emit16, pairs, two, tail = plan_forward(B, H, W, adt, keep, split5, ops.PROFILE is not None,
+                                                                    dev.type == "cuda")
 
         def conv(xs, name, ys, k, **kw):   # one MFMA conv; 3x3 / 5x5 take the split-precision kernel when opted in
             ops.conv2d(xs, P(name), ys, k, f16x3=self._split(k), **kw)
 
-        split5 = self._split(5)
         chain_mode = L.PACK_CHAIN1X1_F16X3 if split5 else L.PACK_CHAIN1X1
 
         def conv5_1x1(xs, name5, name1, mid, ys, residual=None, stats=None):
@@ -785,20 +620,6 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
             ops.conv_chain1x1(xs, P(name5), P(name1, chain_mode), ys, mid=mid if keep else None, residual=residual,
                               f16x3=split5, stats=stats)
 
-        # 16-bit tensors: the CAC statistics of a block come out of the two conv5x5 + 1x1 epilogues (no pass over Fcat).
-        # fp32 (round 6): the same for images of at most 32 768 pixels -- chosen by H x W ONLY, and the per-row-strip partials
-        # are tiling-invariant, so an image's bits do not depend on the batch it arrives in; larger fp32 images keep the
-        # statistics pass (0.87 ms of a 988 ms forward at 32 x 480 x 640, against 5 x 22 us of 2.2 ms at 1 x 128 x 128)
-        fused_stats = ops.is_c8(adt) or (FUSED_STATS_F32 and CAC_TAIL and adt == torch.float32 and not split5 and H * W <= 32768)
-
-        # inference, exact fp32: the gate-apply `out*ad_CAC + inputs` (:89-91,117-118) is formed inside the staging of
-        # the convs that consume it (codon_conv2d_gated_fwd) instead of a 15 GB HBM pass per block
-        # 16-bit: with the emitting conv5x5 (GATED_EMIT) the training forward takes the same route -- the emitted tensor IS
-        # the block input the backward needs, bit-identical to cac_apply's output, and the 7.5 GB apply pass is gone there too
-        emit16 = GATED_EMIT and not split5 and ((ops.is_c8(adt) and GATED_16BIT) or (adt == torch.float32 and not keep))
-        gated = not split5 and (((not keep) and (adt == torch.float32 or GATED_16BIT)) or (keep and emit16))
-
-        emit16 = emit16 and gated
         xg = new(128) if (emit16 and not keep) else None      # [out | out_c] as emitted by the gated conv5x5s of a block
 
         def gconv(gate, pre_s, in_s, plain_s, name, ys, k, emit=None, emitted=None):
@@ -825,12 +646,7 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
         # heads: inputs = in2[:, :64] (depth), inputs_c = in2[:, 64:] (colour)     :68-72
         in2 = new(128)
         t64 = new(64)
-        # inference on a small grid (16-bit: at most PAIR_MAX16 tiles; fp32: the small-grid kernels): the depth and the colour
-        # conv of every stage as ONE launch
-        # (not while bench.py brackets individual conv launches with HIP events: a held launch has no duration of its own)
-        pairs = (not keep) and ops.PROFILE is None and \
-            B * ((H + 7) // 8) * ((W + 31) // 32) <= (PAIR_MAX16 if ops.is_c8(adt) else min(PAIR_MAX32, 383))
-        pair = lambda: ops.conv_pair(dev, pairs)
+        pair = lambda: ops.conv_pair(dev, pairs)      # the two convs of the body as ONE launch (plan.pairs), else in order
         t64c = new(64) if (keep or pairs) else t64
         if pairs:
             ops.stem_pair(x, w_in, Slice(t64), y, w_in_c, Slice(t64c), nf_bad, nf_wd, nf_wg)      # both stems as one launch
@@ -845,10 +661,7 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
         if keep:
             save["stem"], save["stem_c"], save["in2"] = t64, t64c, in2
 
-        # small grids (inference): two HIP streams, fork before the streams of a block, join at its gate
-        two = TWO_STREAMS and (not keep) and (not pairs) and dev.type == "cuda" and (
-            B * ((H + 7) // 8) * ((W + 31) // 32) <= TWO_STREAMS_MAX16 if ops.is_c8(adt) else
-            B * ((H + 3) // 4) * ((W + 31) // 32) <= TWO_STREAMS_MAX32)
+        # plan.two: fork before the streams of a block, join at its gate
         main_s = torch.cuda.current_stream(dev) if two else None
         halves = _half_chip_streams(dev, main_s) if two else None
         if two:
@@ -861,19 +674,6 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
                 P(n5_)
                 P(n1_, chain_mode)
 
-        class _on_half:
-            """`with _on_half(k):` runs the body on half-chip stream k, ordered after everything issued so far on the main one."""
-            def __init__(self_, k):
-                self_.k = k
-            def __enter__(self_):
-                if two:
-                    halves[self_.k].wait_stream(main_s)
-                    self_.ctx = torch.cuda.stream(halves[self_.k])
-                    self_.ctx.__enter__()
-            def __exit__(self_, *a):
-                if two:
-                    self_.ctx.__exit__(*a)
-
         def join():
             if two:
                 main_s.wait_stream(halves[0])
@@ -881,14 +681,6 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
 
         nt = ops.cac_fused_parts(H, W, adt) if fused_stats else ops.cac_stats_tiles(H, W)
         fz = dict(dtype=torch.float32, device=dev)
-        # fp32: the one-launch gate folds the tiles before it finishes the pools -- the serial order of cac_gate_kernel while every
-        # fold holds one tile (nt <= 16), and the ONLY sensible form for the many small tiles of a small image (H W <= 32768:
-        # 256-pixel tiles, cac.hip), where a serial walk would take longer than the pass itself
-        # 16-bit: bit-identical to the separate launches at any size, and FASTER only while the grid is small (12 vs 25 us for
-        # one 370 x 463 image; 210 vs 147 us at 32 x 480 x 640, where the combine inside the spatial tiles re-reads four maps'
-        # halos) -- so it is chosen by size there; fp32: by H x W only, so that an image's bits never depend on its batch
-        tail = CAC_TAIL and ((B * H * W <= CAC_TAIL_MAX_PIXELS or adt == torch.float32) if fused_stats
-                             else (nt <= L.CAC_FOLDS or H * W <= 32768))
         if fused_stats:
             pool_c, pool_d = torch.empty((B, 2, H, W), **fz), torch.empty((B, 2, H, W), **fz)
         if fused_stats or tail:
@@ -914,37 +706,32 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
             gate = prev_gate if (gated and i > 0) else None      # (ch, sp) of block i-1: its apply runs in our staging
             # ... on block i-1's [pre | pre_c]: the same buffer at inference, the previous block's saved one in training
             gpre, gpre_c = (Slice(prev_pre2, 0, 64), Slice(prev_pre2, 64, 64)) if gate is not None else (None, None)
-            # colour stream: stage_c = [conv4 5x5 | conv5 3x3]                       :76,78,80   (side stream on small grids)
             if emit16 and keep and gate is not None:
                 xg = new(128)           # training: the emitted tensor is this block's saved input
             xg_d, xg_c = (Slice(xg, 0, 64), Slice(xg, 64, 64)) if (emit16 and gate is not None) else (None, None)
+            # the six convs of the block, in launch order per stream.  colour: stage_c = [conv4 5x5 | conv5 3x3]  :76,78,80,82,83
+            colour = (lambda: gconv(gate, gpre_c, inputs_c, out_c, "conv4", Slice(stage_c, 0, 64), 5, emit=xg_c),
+                      lambda: gconv(gate, gpre_c, inputs_c, out_c, "conv5", Slice(stage_c, 64, 64), 3, emitted=xg_c),
+                      lambda: conv5_1x1(Slice(stage_c), "conv6", "confuse_c", Slice(r2_c), pre_c,
+                                        stats=(pool_c, partials, 0) if fused_stats else None))
+            # depth: stage = [conv1 3x3 | conv2 5x5]                                                             :75,77,79,81,84
+            depth = (lambda: gconv(gate, gpre, inputs, out, "conv2", Slice(stage, 64, 64), 5, emit=xg_d),
+                     lambda: gconv(gate, gpre, inputs, out, "conv1", Slice(stage, 0, 64), 3, emitted=xg_d),
+                     lambda: conv5_1x1(Slice(stage), "conv3", "confuse", Slice(r2), pre,
+                                       stats=(pool_d, partials, 64) if fused_stats else None))
             if pairs:
                 # stage by stage, colour | depth as one launch each (same kernel variant on the same grid)
-                with pair():
-                    gconv(gate, gpre_c, inputs_c, out_c, "conv4", Slice(stage_c, 0, 64), 5, emit=xg_c)
-                    gconv(gate, gpre, inputs, out, "conv2", Slice(stage, 64, 64), 5, emit=xg_d)
-                with pair():
-                    gconv(gate, gpre_c, inputs_c, out_c, "conv5", Slice(stage_c, 64, 64), 3, emitted=xg_c)
-                    gconv(gate, gpre, inputs, out, "conv1", Slice(stage, 0, 64), 3, emitted=xg_d)
-                with pair():
-                    conv5_1x1(Slice(stage_c), "conv6", "confuse_c", Slice(r2_c), pre_c,
-                              stats=(pool_c, partials, 0) if fused_stats else None)
-                    conv5_1x1(Slice(stage), "conv3", "confuse", Slice(r2), pre,
-                              stats=(pool_d, partials, 64) if fused_stats else None)
-            with _on_half(1):
-                if not pairs:
-                    gconv(gate, gpre_c, inputs_c, out_c, "conv4", Slice(stage_c, 0, 64), 5, emit=xg_c)
-                    gconv(gate, gpre_c, inputs_c, out_c, "conv5", Slice(stage_c, 64, 64), 3, emitted=xg_c)
-                    conv5_1x1(Slice(stage_c), "conv6", "confuse_c", Slice(r2_c), pre_c,
-                              stats=(pool_c, partials, 0) if fused_stats else None)   # :82,83
-            # depth stream: stage = [conv1 3x3 | conv2 5x5]                          :75,77,79
-            with _on_half(0):
-                if not pairs:
-                    gconv(gate, gpre, inputs, out, "conv2", Slice(stage, 64, 64), 5, emit=xg_d)
-                    gconv(gate, gpre, inputs, out, "conv1", Slice(stage, 0, 64), 3, emitted=xg_d)
-                    conv5_1x1(Slice(stage), "conv3", "confuse", Slice(r2), pre,
-                              stats=(pool_d, partials, 64) if fused_stats else None)   # :81,84
-            join()
+                for launch_c, launch_d in zip(colour, depth):
+                    with pair():
+                        launch_c()
+                        launch_d()
+            else:
+                # each stream's three in order: on its half-chip stream (plan.two), else one after the other
+                for k, launches in ((1, colour), (0, depth)):
+                    with _on_half(halves, main_s, k):
+                        for launch in launches:
+                            launch()
+                join()
             # CAC gate on Fcat = [pre_c | pre]                                       :85-91
             w1_, b1_, w2_, b2_, ws_ = gparams[i]
             if not fused_stats:
@@ -991,17 +778,18 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
             if keep:
                 stage = stage if (drop_stage and stage is not None) else new(128)
                 r2, fA = new(128), new(64)
+            conv8 = lambda: conv(Slice(f), "conv8", Slice(stage, 0, 64), 5, relu=True)    # :123
+            conv9 = lambda: conv(Slice(f), "conv9", Slice(stage, 64, 64), 3, relu=True)   # :124
             if pairs:
                 # conv8 (5x5) | conv9 (3x3) on the same input: two different kernel bodies as ONE grid (mix53) when the launcher
                 # has that form for this dtype and grid, else two launches in order
                 with pair():
-                    conv(Slice(f), "conv8", Slice(stage, 0, 64), 5, relu=True)    # :123
-                    conv(Slice(f), "conv9", Slice(stage, 64, 64), 3, relu=True)   # :124
+                    conv8()
+                    conv9()
             else:
-                with _on_half(1):
-                    conv(Slice(f), "conv9", Slice(stage, 64, 64), 3, relu=True)   # :124
-                with _on_half(0):
-                    conv(Slice(f), "conv8", Slice(stage, 0, 64), 5, relu=True)    # :123
+                for k, launch in ((1, conv9), (0, conv8)):
+                    with _on_half(halves, main_s, k):
+                        launch()
                 join()
             conv5_1x1(Slice(stage), "conv10", "confuse_fuse", Slice(r2), Slice(fA), residual=Slice(fuse))  # :126-128
             if keep:
@@ -1010,14 +798,11 @@ class _CODONBase(_NonFiniteMixin, nn.Module):
         # tail                                                                       :129-132
         t = new(64) if keep else t64
         conv(Slice(f), "conv11", Slice(t), 3, relu=True)
-        if out_dtype is not None and out_dtype != torch.float32 and out_dtype == adt:
-            outp = torch.empty(x.shape, dtype=out_dtype, device=dev)     # the head rounds once, in its store
-            ops.head(Slice(t), w_out, x, outp, nf_bad)
-        else:
-            outp = torch.empty_like(x)
-            ops.head(Slice(t), w_out, x, outp, nf_bad)
-            if out_dtype is not None and out_dtype != torch.float32:
-                outp = outp.to(out_dtype)     # e.g. bf16 inputs to an fp32 model: not the reference's use, one ATen cast
+        y16 = out_dtype is not None and out_dtype != torch.float32 and out_dtype == adt
+        outp = torch.empty(x.shape, dtype=out_dtype, device=dev) if y16 else torch.empty_like(x)
+        ops.head(Slice(t), w_out, x, outp, nf_bad)          # a 16-bit map of 16-bit activations: rounded once, in the head's store
+        if not y16 and out_dtype is not None and out_dtype != torch.float32:
+            outp = outp.to(out_dtype)     # e.g. bf16 inputs to an fp32 model: not the reference's use, one ATen cast
         if keep:
             save["f_last"], save["t11"] = f, t
         return outp
@@ -1033,87 +818,35 @@ class CODONNet16(_CODONBase):
     _HAS_UNUSED_GATE5 = False
 
 
-class BaseNet_RMCR_fuseRMCR(_NonFiniteMixin, nn.Module):
+class BaseNet_RMCR_fuseRMCR(_ConvNet):
     """Conv-only ablation of the paper (no CAC gates, the two streams never interact before conv7):
     /root/reference/CODON_X16/CODON_x16.py:16-90.  Same 19 bias-free convs, same kernels; inference only."""
 
-    def __init__(self):
-        super().__init__()
-        for name, ci, co, k in _MAIN_CONVS:
-            setattr(self, name, Conv2dParams(ci, co, k, he_init=True))
-        self.relu = nn.ReLU()
-        self._pack_cache: Dict[str, tuple] = {}
-        self._wguard: Optional[_WeightGuard] = None
-        self.compute_dtype: Optional[torch.dtype] = None
-        self.conv_precision: str = "exact"
-
-    set_compute_dtype = _CODONBase.set_compute_dtype
-    _guard = _CODONBase._guard
-    check_packed = _CODONBase.check_packed
-    set_conv_precision = _CODONBase.set_conv_precision
-    _act_dtype = _CODONBase._act_dtype
-    _packed = _CODONBase._packed
-    _split = _CODONBase._split
-    __getstate__ = _CODONBase.__getstate__
-    invalidate_packed = _CODONBase.invalidate_packed
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate_packed()
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self.invalidate_packed()
-        return super()._load_from_state_dict(*a, **k)
-
     def forward(self, x, y):
-        if x.shape != y.shape or x.dim() != 4 or x.shape[1] != 1:
-            raise RuntimeError(f"expects two (B,1,H,W) tensors, got {tuple(x.shape)} and {tuple(y.shape)}")
-        if not x.is_cuda:
-            raise RuntimeError("codon_amd runs on MI355X only (there is no CPU fallback)")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("BaseNet_RMCR_fuseRMCR: inference only; call under torch.no_grad()")
-        if x.shape[0] == 0:
-            return x.new_zeros(x.shape)         # empty batch: an empty map, as the reference's ops return
-        self._nf_check()
-        idt = x.dtype
-        x, y = x.float().contiguous(), y.float().contiguous()
-        B, _, H, W = x.shape
-        nf_bad, nf_wd, nf_wg = self._nf_open(x.device, B)
-        adt = self._act_dtype()
-        new = lambda c: ops.new_act(B, c, H, W, adt, x.device)
-        f32 = lambda t: t if t.dtype == torch.float32 else t.float()
-        P = self._packed
-        S3, S5 = self._split(3), self._split(5)
-        CM = L.PACK_CHAIN1X1_F16X3 if S5 else L.PACK_CHAIN1X1
+        return self._inference_only(x, y, self._two_streams)
+
+    def _two_streams(self, x, y, nf, new, conv, chain):
+        nf_bad, nf_wd, nf_wg = nf
         t64, stage, oc = new(64), new(128), new(128)
 
         def stream(img, w_in, n_ci, c3x3, c5x5, first5, n3, nconf, out_slice):      # :53-74
             inputs = new(64)
-            ops.stem(img, f32(getattr(self, w_in).weight), Slice(t64), nf_bad, nf_wd if img is x else nf_wg)
-            ops.conv2d(Slice(t64), P(n_ci), Slice(inputs), 3, relu=True, f16x3=S3)
+            ops.stem(img, _f32(getattr(self, w_in).weight), Slice(t64), nf_bad, nf_wd if img is x else nf_wg)
+            conv(Slice(t64), n_ci, Slice(inputs), 3, relu=True)
             cur = Slice(inputs)
             for i in range(5):
                 a, b = (c5x5, c3x3) if first5 else (c3x3, c5x5)
-                ops.conv2d(cur, P(a), Slice(stage, 0, 64), 5 if first5 else 3, relu=True, f16x3=S5 if first5 else S3)
-                ops.conv2d(cur, P(b), Slice(stage, 64, 64), 3 if first5 else 5, relu=True, f16x3=S3 if first5 else S5)
+                conv(cur, a, Slice(stage, 0, 64), 5 if first5 else 3, relu=True)
+                conv(cur, b, Slice(stage, 64, 64), 3 if first5 else 5, relu=True)
                 dst = out_slice if i == 4 else Slice(new(64))
-                ops.conv_chain1x1(Slice(stage), P(n3), P(nconf, CM), dst, residual=Slice(inputs), f16x3=S5)  # confuse(relu(conv3)) + inputs
+                chain(Slice(stage), n3, nconf, dst, residual=Slice(inputs))         # confuse(relu(conv3)) + inputs
                 cur = dst
 
         stream(x, "input", "conv_input", "conv1", "conv2", False, "conv3", "confuse", Slice(oc, 0, 64))
         stream(y, "input_c", "conv_input_c", "conv5", "conv4", True, "conv6", "confuse_c", Slice(oc, 64, 64))
-        fuse, fA = new(64), new(64)
-        ops.conv2d(Slice(oc), P("conv7"), Slice(fuse), 3, relu=True, f16x3=S3)                # :76-77
-        f = fuse
-        for _ in range(3):                                                          # :79-85
-            ops.conv2d(Slice(f), P("conv8"), Slice(stage, 0, 64), 5, relu=True, f16x3=S5)
-            ops.conv2d(Slice(f), P("conv9"), Slice(stage, 64, 64), 3, relu=True, f16x3=S3)
-            ops.conv_chain1x1(Slice(stage), P("conv10"), P("confuse_fuse", CM), Slice(fA), residual=Slice(fuse), f16x3=S5)
-            f = fA
-        ops.conv2d(Slice(f), P("conv11"), Slice(t64), 3, relu=True, f16x3=S3)                 # :87
-        out = torch.empty_like(x)
-        ops.head(Slice(t64), f32(self.output.weight), x, out, nf_bad)               # :88-89
-        return out if idt == torch.float32 else out.to(idt)
+        fuse = new(64)
+        conv(Slice(oc), "conv7", Slice(fuse), 3, relu=True)                         # :76-77
+        return fuse, stage, t64                                                    # trunk and head: :79-89
 
 
 class BaseNet_RMCR_fuseRMCR_cross(_CODONBase):
@@ -1127,34 +860,16 @@ class BaseNet_RMCR_fuseRMCR_cross(_CODONBase):
     _HAS_UNUSED_GATE5 = True
 
     def forward(self, x, y):
-        if x.shape != y.shape or x.dim() != 4 or x.shape[1] != 1:
-            raise RuntimeError(f"expects two (B,1,H,W) tensors, got {tuple(x.shape)} and {tuple(y.shape)}")
-        if not x.is_cuda:
-            raise RuntimeError("codon_amd runs on MI355X only (there is no CPU fallback)")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("BaseNet_RMCR_fuseRMCR_cross: inference only; call under torch.no_grad()")
-        if x.shape[0] == 0:
-            return x.new_zeros(x.shape)         # empty batch: an empty map, as the reference's ops return
-        self._nf_check()
-        idt = x.dtype
-        x, y = x.float().contiguous(), y.float().contiguous()
-        B, _, H, W = x.shape
-        dev = x.device
-        self.check_supported()
-        nf_bad, nf_wd, nf_wg = self._nf_open(dev, B)
-        adt = self._act_dtype()
-        new = lambda c: ops.new_act(B, c, H, W, adt, dev)
-        f32 = lambda t: t if t.dtype == torch.float32 else t.float()
-        fz = dict(dtype=torch.float32, device=dev)
-        P = self._packed
-        S3, S5 = self._split(3), self._split(5)
-        CM = L.PACK_CHAIN1X1_F16X3 if S5 else L.PACK_CHAIN1X1
-        conv = lambda xs, name, ys, k, **kw: ops.conv2d(xs, P(name), ys, k, f16x3=self._split(k), **kw)
+        return self._inference_only(x, y, self._gated_blocks)
 
+    def _gated_blocks(self, x, y, nf, new, conv, chain):
+        nf_bad, nf_wd, nf_wg = nf
+        B, _, H, W = x.shape
+        fz = dict(dtype=torch.float32, device=x.device)
         in2, t64, stage, pre2, oc = new(128), new(64), new(128), new(128), new(128)
-        ops.stem(x, f32(self.input.weight), Slice(t64), nf_bad, nf_wd)
+        ops.stem(x, _f32(self.input.weight), Slice(t64), nf_bad, nf_wd)
         conv(Slice(t64), "conv_input", Slice(in2, 0, 64), 3, relu=True)
-        ops.stem(y, f32(self.input_c.weight), Slice(t64), nf_bad, nf_wg)
+        ops.stem(y, _f32(self.input_c.weight), Slice(t64), nf_bad, nf_wg)
         conv(Slice(t64), "conv_input_c", Slice(in2, 64, 64), 3, relu=True)
         nt = ops.cac_stats_tiles(H, W)
         pooled = torch.empty((B, 2, H, W), **fz)
@@ -1167,16 +882,16 @@ class BaseNet_RMCR_fuseRMCR_cross(_CODONBase):
             pre, pre_c = Slice(pre2, 0, 64), Slice(pre2, 64, 64)
             conv(out, "conv1", Slice(stage, 0, 64), 3, relu=True)
             conv(out, "conv2", Slice(stage, 64, 64), 5, relu=True)
-            ops.conv_chain1x1(Slice(stage), P("conv3"), P("confuse", CM), pre, f16x3=S5)
+            chain(Slice(stage), "conv3", "confuse", pre)
             conv(out_c, "conv4", Slice(stage, 0, 64), 5, relu=True)
             conv(out_c, "conv5", Slice(stage, 64, 64), 3, relu=True)
-            ops.conv_chain1x1(Slice(stage), P("conv6"), P("confuse_c", CM), pre_c, f16x3=S5)
+            chain(Slice(stage), "conv6", "confuse_c", pre_c)
             ac, asp = getattr(self, f"attention_c{i}"), getattr(self, f"attention_s{i}")
             ops.cac_stats(pre_c, pre, pooled, partials)
-            ops.cac_gate(B, H, W, partials, f32(ac.mlp[1].weight), f32(ac.mlp[1].bias), f32(ac.mlp[3].weight),
-                         f32(ac.mlp[3].bias), ch)
+            ops.cac_gate(B, H, W, partials, _f32(ac.mlp[1].weight), _f32(ac.mlp[1].bias), _f32(ac.mlp[3].weight),
+                         _f32(ac.mlp[3].bias), ch)
             ops.cac_stats_scaled(pre_c, pre, ch, pooled, partials)      # ChannelPool of the channel-gated features
-            ops.cac_spatial(pooled, f32(asp.spatial.conv.weight), sp)
+            ops.cac_spatial(pooled, _f32(asp.spatial.conv.weight), sp)
             ops.cac_apply(pre, pre_c, ch, sp, Slice(in2, 0, 64), Slice(in2, 64, 64), Slice(oc, 0, 64), Slice(oc, 64, 64))
             cur = oc
         fuse, fuse2, fuse_g, dump = new(64), new(64), new(64), t64
@@ -1184,26 +899,17 @@ class BaseNet_RMCR_fuseRMCR_cross(_CODONBase):
         # ChannelGate(64) = Linear(64,4) / Linear(4,64): run on the 128 -> 8 -> 64 gate kernel with zero-padded weights
         # over the statistics of (fuse | fuse) -- every padded term is an exact zero
         g5 = self.attention_c5
-        w1 = torch.zeros((8, 128), **fz); w1[:4, :64] = f32(g5.mlp[1].weight)
-        b1 = torch.zeros((8,), **fz); b1[:4] = f32(g5.mlp[1].bias)
-        w2 = torch.zeros((64, 8), **fz); w2[:, :4] = f32(g5.mlp[3].weight)
+        w1 = torch.zeros((8, 128), **fz); w1[:4, :64] = _f32(g5.mlp[1].weight)
+        b1 = torch.zeros((8,), **fz); b1[:4] = _f32(g5.mlp[1].bias)
+        w2 = torch.zeros((64, 8), **fz); w2[:, :4] = _f32(g5.mlp[3].weight)
         ops.cac_stats(Slice(fuse), Slice(fuse), pooled, partials)
-        ops.cac_gate(B, H, W, partials, w1, b1, w2, f32(g5.mlp[3].bias), ch)
+        ops.cac_gate(B, H, W, partials, w1, b1, w2, _f32(g5.mlp[3].bias), ch)
         ops.ew_sq_scale(Slice(fuse), ch, Slice(fuse2))                  # fuse * (fuse * scale)
         ops.cac_stats(Slice(fuse2), Slice(fuse2), pooled, partials)
-        ops.cac_spatial(pooled, f32(self.attention_s5.spatial.conv.weight), sp)
+        ops.cac_spatial(pooled, _f32(self.attention_s5.spatial.conv.weight), sp)
         ones = torch.ones((B, 64), **fz)
         ops.cac_apply(Slice(fuse2), Slice(fuse2), ones, sp, Slice(fuse), Slice(fuse), Slice(fuse_g), Slice(dump))
-        f, fA = fuse_g, new(64)
-        for _ in range(3):
-            conv(Slice(f), "conv8", Slice(stage, 0, 64), 5, relu=True)
-            conv(Slice(f), "conv9", Slice(stage, 64, 64), 3, relu=True)
-            ops.conv_chain1x1(Slice(stage), P("conv10"), P("confuse_fuse", CM), Slice(fA), residual=Slice(fuse_g), f16x3=S5)
-            f = fA
-        conv(Slice(f), "conv11", Slice(t64), 3, relu=True)
-        out = torch.empty_like(x)
-        ops.head(Slice(t64), f32(self.output.weight), x, out, nf_bad)
-        return out if idt == torch.float32 else out.to(idt)
+        return fuse_g, stage, t64
 
 
 def strip_module_prefix(state_dict):

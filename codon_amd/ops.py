@@ -73,6 +73,13 @@ def _ptr(t: Optional[torch.Tensor]):
 PROFILE = None
 
 
+def _event(dev):
+    """One end of PROFILE's bracket around a launch: a timing event recorded now on the launch stream."""
+    e = torch.cuda.Event(enable_timing=True)
+    e.record(torch.cuda.current_stream(dev))
+    return e
+
+
 def is_c8(dtype: torch.dtype) -> bool:
     """16-bit activations are stored channel-blocked, [B][C/8][H][W][8] (csrc/c8.h); fp32 ones NCHW."""
     return dtype in (torch.bfloat16, torch.float16)
@@ -205,14 +212,11 @@ def conv2d(x: Slice, w_packed: torch.Tensor, y: Slice, ksize: int, relu: bool = 
         assert residual.c == y.c and _bhw(residual.buf) == (B, H, W)
     prof = PROFILE if (PROFILE is not None and PROFILE["key"] == (ksize, x.c, y.c)) else None
     with _on(dev):
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(dev))
+        e0 = _event(dev) if prof is not None else None
         L.check(lib.codon_conv2d_fwd(C.byref(d), _ptr(x.buf), _ptr(w_packed), _ptr(y.buf),
                                      _ptr(residual.buf if residual else None), _stream(dev)), "conv2d_fwd")
         if prof is not None:
-            e1.record(torch.cuda.current_stream(dev))
-            prof["events"].append((e0, e1))
+            prof["events"].append((e0, _event(dev)))
 
 
 def conv2d_sum_into(x: Slice, w_packed: torch.Tensor, y: Slice, ksize: int, total: Slice, accumulate: bool = False):
@@ -230,14 +234,11 @@ def conv2d_sum_into(x: Slice, w_packed: torch.Tensor, y: Slice, ksize: int, tota
                    L.CONV_ACCUM_OUT if accumulate else 0, _dt(x.buf))
     prof = PROFILE if (PROFILE is not None and PROFILE["key"] == (ksize, x.c, y.c)) else None
     with _on(dev):
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(dev))
+        e0 = _event(dev) if prof is not None else None
         L.check(lib.codon_conv2d_sum_into_fwd(C.byref(d), _ptr(x.buf), _ptr(w_packed), _ptr(y.buf), _ptr(total.buf),
                                               _stream(dev)), "conv2d_sum_into_fwd")
         if prof is not None:
-            e1.record(torch.cuda.current_stream(dev))
-            prof["events"].append((e0, e1))
+            prof["events"].append((e0, _event(dev)))
 
 
 def conv_chain1x1(x: Slice, w_packed: torch.Tensor, w_chain: torch.Tensor, out: Slice, mid: Optional[Slice] = None,
@@ -259,9 +260,7 @@ def conv_chain1x1(x: Slice, w_packed: torch.Tensor, w_chain: torch.Tensor, out: 
                    0, 0, flags, _dt(x.buf))
     prof = PROFILE if (PROFILE is not None and PROFILE["key"] == (5, x.c, 128)) else None
     with _on(dev):
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(dev))
+        e0 = _event(dev) if prof is not None else None
         ot, rt = out.ct(), (residual.ct() if residual else None)
         if stats is not None:
             pool, partials, choff = stats
@@ -276,8 +275,7 @@ def conv_chain1x1(x: Slice, w_packed: torch.Tensor, w_chain: torch.Tensor, out: 
                                                 _ptr(w_chain), C.byref(ot), C.byref(rt) if rt is not None else None,
                                                 _stream(dev)), "conv_chain1x1_fwd")
         if prof is not None:
-            e1.record(torch.cuda.current_stream(dev))
-            prof["events"].append((e0, e1))
+            prof["events"].append((e0, _event(dev)))
             prof["chained"] = True
 
 
@@ -382,15 +380,12 @@ def conv2d_wgrad(x: Slice, gy: Slice, dw: Optional[torch.Tensor], ksize: int, ac
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     prof = PROFILE if (PROFILE is not None and PROFILE.get("wgrad_key") == (ksize, x.c, gy.c)) else None
     with _on(dev):
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(dev))
+        e0 = _event(dev) if prof is not None else None
         mode = L.WGRAD_DEFER if defer is not None else (1 if accumulate else 0)
         L.check(lib.codon_conv2d_wgrad(C.byref(d), _ptr(x.buf), _ptr(gy.buf), None if defer is not None else _ptr(dw),
                                        _ptr(ws), nbytes, mode, _stream(dev)), "conv2d_wgrad")
         if prof is not None:
-            e1.record(torch.cuda.current_stream(dev))
-            prof["wgrad_events"].append((e0, e1))
+            prof["wgrad_events"].append((e0, _event(dev)))
     if defer is not None:
         defer[0].add_wgrad(defer[1], ws, gy.c, x.c, ksize * ksize)
 
@@ -435,13 +430,11 @@ def stem(x: torch.Tensor, w: torch.Tensor, y: Slice, bad: Optional[torch.Tensor]
     dev = _dev(x, w, y.buf)
     B, _, H, W = x.shape
     assert y.c == 64 and x.dtype == torch.float32 and w.dtype == torch.float32
+    guarded = bad is not None or host_word is not None
+    fn, guard = (lib.codon_stem_fwd_guarded, (_bad_ptr(bad, B, dev), host_word)) if guarded else (lib.codon_stem_fwd, ())
     with _on(dev):
-        if bad is None and host_word is None:
-            L.check(lib.codon_stem_fwd(B, H, W, _ptr(x), _ptr(w), _ptr(y.buf), y.ctotal, y.coff, _dt(y.buf),
-                                       _stream(dev)), "stem_fwd")
-        else:
-            L.check(lib.codon_stem_fwd_guarded(B, H, W, _ptr(x), _ptr(w), _ptr(y.buf), y.ctotal, y.coff, _dt(y.buf),
-                                               _bad_ptr(bad, B, dev), host_word, _stream(dev)), "stem_fwd_guarded")
+        L.check(fn(B, H, W, _ptr(x), _ptr(w), _ptr(y.buf), y.ctotal, y.coff, _dt(y.buf), *guard, _stream(dev)),
+                "stem_fwd_guarded" if guarded else "stem_fwd")
 
 
 def stem_pair(xa: torch.Tensor, wa: torch.Tensor, ya: Slice, xb: torch.Tensor, wb: torch.Tensor, yb: Slice,
@@ -453,45 +446,32 @@ def stem_pair(xa: torch.Tensor, wa: torch.Tensor, ya: Slice, xb: torch.Tensor, w
     B, _, H, W = xa.shape
     assert xb.shape == xa.shape and ya.c == 64 and yb.c == 64 and ya.buf.dtype == yb.buf.dtype
     assert all(t.dtype == torch.float32 for t in (xa, wa, xb, wb))
+    guarded = not (bad is None and host_word_a is None and host_word_b is None)
+    fn, guard = ((lib.codon_stem_pair_fwd_guarded, (_bad_ptr(bad, B, dev), host_word_a, host_word_b)) if guarded else
+                 (lib.codon_stem_pair_fwd, ()))
     with _on(dev):
-        if bad is None and host_word_a is None and host_word_b is None:
-            L.check(lib.codon_stem_pair_fwd(B, H, W, _ptr(xa), _ptr(wa), _ptr(ya.buf), ya.ctotal, ya.coff, _ptr(xb), _ptr(wb),
-                                            _ptr(yb.buf), yb.ctotal, yb.coff, _dt(ya.buf), _stream(dev)), "stem_pair_fwd")
-        else:
-            L.check(lib.codon_stem_pair_fwd_guarded(B, H, W, _ptr(xa), _ptr(wa), _ptr(ya.buf), ya.ctotal, ya.coff, _ptr(xb),
-                                                    _ptr(wb), _ptr(yb.buf), yb.ctotal, yb.coff, _dt(ya.buf),
-                                                    _bad_ptr(bad, B, dev), host_word_a, host_word_b, _stream(dev)),
-                    "stem_pair_fwd_guarded")
+        L.check(fn(B, H, W, _ptr(xa), _ptr(wa), _ptr(ya.buf), ya.ctotal, ya.coff, _ptr(xb), _ptr(wb), _ptr(yb.buf), yb.ctotal,
+                   yb.coff, _dt(ya.buf), *guard, _stream(dev)), "stem_pair_fwd_guarded" if guarded else "stem_pair_fwd")
 
 
 def head(x: Slice, w: torch.Tensor, residual: torch.Tensor, y: torch.Tensor, bad: Optional[torch.Tensor] = None):
     """bad: the per-image words the guarded stems left -- images with a set word are stored as all-NaN
-    (codon_head_fwd_guarded / _y16_guarded); None = the plain head (every backward use)."""
+    (codon_head_fwd_guarded / _y16_guarded); None = the plain head (every backward use).  A 16-bit y (the output map of a
+    16-bit model, codon_head_fwd_y16): the fp32 result rounded once in the store."""
     lib = L.load()
     dev = _dev(x.buf, w, residual, y)
     B, H, W = _bhw(x.buf)
     assert x.c == 64 and w.dtype == torch.float32 and residual.dtype == torch.float32
-    if bad is not None:
-        bp = _bad_ptr(bad, B, dev)
-        with _on(dev):
-            if y.dtype != torch.float32:
-                assert is_c8(x.buf.dtype) and y.dtype == x.buf.dtype and y.is_contiguous()
-                L.check(lib.codon_head_fwd_y16_guarded(B, H, W, _ptr(x.buf), x.ctotal, x.coff, _ptr(w), _ptr(residual),
-                                                       _ptr(y), _dt(x.buf), bp, _stream(dev)), "head_fwd_y16_guarded")
-            else:
-                L.check(lib.codon_head_fwd_guarded(B, H, W, _ptr(x.buf), x.ctotal, x.coff, _ptr(w), _ptr(residual), _ptr(y),
-                                                   _dt(x.buf), bp, _stream(dev)), "head_fwd_guarded")
-        return
+    name = "head_fwd"
     if y.dtype != torch.float32:
-        # 16-bit output map of a 16-bit model (codon_head_fwd_y16): the fp32 result rounded once in the store
         assert is_c8(x.buf.dtype) and y.dtype == x.buf.dtype and y.is_contiguous()
-        with _on(dev):
-            L.check(lib.codon_head_fwd_y16(B, H, W, _ptr(x.buf), x.ctotal, x.coff, _ptr(w), _ptr(residual), _ptr(y),
-                                           _dt(x.buf), _stream(dev)), "head_fwd_y16")
-        return
+        name += "_y16"
+    guard = ()
+    if bad is not None:
+        name, guard = name + "_guarded", (_bad_ptr(bad, B, dev),)
     with _on(dev):
-        L.check(lib.codon_head_fwd(B, H, W, _ptr(x.buf), x.ctotal, x.coff, _ptr(w), _ptr(residual), _ptr(y),
-                                   _dt(x.buf), _stream(dev)), "head_fwd")
+        L.check(getattr(lib, "codon_" + name)(B, H, W, _ptr(x.buf), x.ctotal, x.coff, _ptr(w), _ptr(residual), _ptr(y),
+                                              _dt(x.buf), *guard, _stream(dev)), name)
 
 
 def cac_stats_tiles(H: int, W: int) -> int:
@@ -504,8 +484,7 @@ def cac_fused_tiles(H: int, W: int) -> int:
 
 def cac_fused_parts(H: int, W: int, dtype) -> int:
     """Rows per image of the fused-statistics partials for activations of `dtype` (codon_cac_fused_parts)."""
-    code = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}[dtype]
-    return L.load().codon_cac_fused_parts(H, W, code)
+    return L.load().codon_cac_fused_parts(H, W, _DT_CODE[dtype])
 
 
 def params_f32(tensors):

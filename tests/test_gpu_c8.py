@@ -723,7 +723,9 @@ def test_fused_cac_backward_against_oracle_autograd(shape, dtype):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_two_stream_schedule_is_bit_identical(dtype):
     """Small grids (one 128 x 128 image: BASELINE configs[0]) run the depth and the colour stream of a block on two HIP
-    streams; same kernels, same operands: the output must not change, eager and under hipGraph capture."""
+    streams; same kernels, same operands: the output must not change, eager and under hipGraph capture.  With the default
+    switches such a grid leaves as pair launches, so the pair thresholds are zeroed for the two legs that compare the
+    schedules; a third leg runs the default switches."""
     import codon_amd
     from codon_amd import model as M
     dev = _dev()
@@ -733,23 +735,35 @@ def test_two_stream_schedule_is_bit_identical(dtype):
         net.set_compute_dtype(dtype)
     x = torch.rand((1, 1, 128, 128), device=dev)
     y = torch.rand((1, 1, 128, 128), device=dev)
-    old = M.TWO_STREAMS
+    plan = lambda: M.plan_forward(1, 128, 128, dtype, False, False, False, True)
+    old = (M.TWO_STREAMS, M.PAIR_MAX16, M.PAIR_MAX32)
     outs = []
     try:
+        M.PAIR_MAX16 = M.PAIR_MAX32 = 0
         for two in (True, False):
             M.TWO_STREAMS = two
+            assert plan().two == two and not plan().pairs
             with torch.no_grad():
                 for _ in range(3):                       # repeated: a missing join would show as a race
                     outs.append(net(x, y).clone())
         M.TWO_STREAMS = True
+        assert plan().two
         from codon_amd.graph import GraphedCODON
         g = GraphedCODON(net, x, y)
         outs.append(g(x, y).clone())
         outs.append(g(x, y).clone())
+        M.TWO_STREAMS, M.PAIR_MAX16, M.PAIR_MAX32 = old           # third leg: the default switches (pair launches)
+        assert plan().pairs and not plan().two
+        with torch.no_grad():
+            for _ in range(3):
+                outs.append(net(x, y).clone())
+        g = GraphedCODON(net, x, y)
+        outs.append(g(x, y).clone())
+        outs.append(g(x, y).clone())
     finally:
-        M.TWO_STREAMS = old
+        M.TWO_STREAMS, M.PAIR_MAX16, M.PAIR_MAX32 = old
     torch.cuda.synchronize()
-    assert torch.isfinite(outs[0]).all()
+    assert len(outs) == 13 and torch.isfinite(outs[0]).all()
     for o in outs[1:]:
         assert torch.equal(outs[0], o)
 

@@ -264,8 +264,7 @@ def test_propagate_single_stem_launches_and_odd_width(dtype):
     if dtype != torch.float32:
         m.set_compute_dtype(dtype)
     B, H, W = (50, 32, 62) if dtype == torch.float32 else (88, 96, 126)
-    tiles = B * ((H + 7) // 8) * ((W + 31) // 32)
-    assert tiles > (M.PAIR_MAX16 if dtype != torch.float32 else min(M.PAIR_MAX32, 383)), "not past the pair-launch path"
+    assert not M.plan_forward(B, H, W, dtype, False, False, False, True).pairs, "not past the pair-launch path"
     assert W % 4 != 0
     x, y = _rand((B, 1, H, W), 41), _rand((B, 1, H, W), 42)
     with torch.no_grad():
