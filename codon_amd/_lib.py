@@ -137,6 +137,8 @@ SIGNATURES = {
     "codon_ssim_fwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "codon_l1_fwd": (C.c_int, [C.c_int64, _P, _P, _P, _I, _P, _P]),
     "codon_ssim_l1_bwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P, C.c_float, C.c_float, _P]),
+    "codon_masked_l1_ssim_fwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
+    "codon_masked_l1_ssim_bwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "codon_bicubic_upsample": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P]),
     "codon_cac_apply_fwd": (C.c_int, [_I, _I, _I, _TP, _TP, _P, _P, _TP, _TP, _TP, _TP, _I, _P]),
     "codon_ew_sum_mask": (C.c_int, [_I, _I, _I, _I, _TP, _I, _TP, _TP, _TP, _TP, _TP, _I, _P]),
@@ -154,6 +156,7 @@ SIGNATURES = {
                                           C.c_double, _I, C.c_double, _P]),
     "codon_reduce_multi": (C.c_int, [C.POINTER(ReduceItem), _I, _P]),
     "codon_train_crops": (C.c_int, [C.POINTER(CropDesc), _P, C.c_int64, _P, _P, _P, _P]),
+    "codon_train_crops_labeled": (C.c_int, [C.POINTER(CropDesc), _P, C.c_int64, _P, _P, _P, _P, _P]),
     "codon_bicubic_downsample": (C.c_int, [_I, _I, _I, _P, _P, _P, _P]),
     "codon_quantize_u8": (C.c_int, [C.c_int64, _P, _P, _P]),
     "codon_weight_checksum_workspace_bytes": (_S, []),

@@ -109,6 +109,10 @@ int ssim_tiles(int, int, int);
 int ssim_fwd(int, int, int, const float*, const float*, float*, float*, double*, hipStream_t);
 int l1_fwd(long, const float*, const float*, float*, int, double*, hipStream_t);
 int ssim_l1_bwd(int, int, int, const float*, const float*, const float*, float*, float*, float, float, hipStream_t);
+int masked_l1_ssim_fwd(int, int, int, const float*, const float*, const unsigned char*, float*, float*, double, double,
+                       long long*, double*, float*, double*, hipStream_t);
+int masked_l1_ssim_bwd(int, int, int, const float*, const float*, const unsigned char*, const float*, const float*, const float*,
+                       float*, float*, hipStream_t);
 
 int reduce_multi(const codon_reduce_item*, int, hipStream_t);
 int cast_multi(const codon_cast_desc*, float*, hipStream_t);
@@ -118,6 +122,7 @@ int grad_norm(const float*, long, void*, hipStream_t);
 int adam_step_guarded(const codon_adam_desc*, const float*, float*, float*, float*, void*, float, float, float, float, float, int,
                       double, int, double, hipStream_t);
 int train_crops(const codon_crop_desc*, const unsigned char*, const float*, float*, float*, hipStream_t);
+int train_crops_labeled(const codon_crop_desc*, const unsigned char*, const float*, float*, float*, float*, hipStream_t);
 int bicubic_downsample(int, int, int, const float*, const float*, float*, hipStream_t);
 int quantize_u8(long, float*, const float*, hipStream_t);
 size_t weight_checksum_workspace_bytes();
@@ -813,6 +818,26 @@ int codon_ssim_l1_bwd(int32_t batch, int32_t height, int32_t width, const float*
   return ssim_l1_bwd(batch, height, width, a, b, dmaps, tmp, ga, ssim_scale, l1_scale, (hipStream_t)stream);
 }
 
+int codon_masked_l1_ssim_fwd(int32_t batch, int32_t height, int32_t width, const float* pred, const float* target,
+                             const uint8_t* valid, float* ws, float* dmaps, double w_l1, double w_ssim, int64_t* counts,
+                             double* per_image, float* scales, double* value, codon_stream_t stream) {
+  CODON_REQUIRE(pred && target && ws && counts && per_image && scales && value, CODON_ERR_BAD_ARG,
+                "masked_l1_ssim_fwd: null pointer");
+  CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "masked_l1_ssim_fwd: bad shape");
+  return masked_l1_ssim_fwd(batch, height, width, pred, target, valid, ws, dmaps, w_l1, w_ssim, (long long*)counts, per_image,
+                            scales, value, (hipStream_t)stream);
+}
+
+int codon_masked_l1_ssim_bwd(int32_t batch, int32_t height, int32_t width, const float* pred, const float* target,
+                             const uint8_t* valid, const float* dmaps, const float* scales, const float* upstream, float* tmp,
+                             float* ga, codon_stream_t stream) {
+  CODON_REQUIRE(pred && target && dmaps && scales && upstream && tmp && ga, CODON_ERR_BAD_ARG,
+                "masked_l1_ssim_bwd: null pointer");
+  CODON_REQUIRE(shape_ok(batch, height, width) && height >= 7 && width >= 7, CODON_ERR_UNSUPPORTED,
+                "masked_l1_ssim_bwd: needs H, W >= 7 (got %dx%d)", height, width);
+  return masked_l1_ssim_bwd(batch, height, width, pred, target, valid, dmaps, scales, upstream, tmp, ga, (hipStream_t)stream);
+}
+
 int codon_bicubic_upsample(int32_t batch, int32_t lr_height, int32_t lr_width, int32_t scale, const float* lr,
                            const float* phase_weights, float* out, codon_stream_t stream) {
   CODON_REQUIRE(lr && phase_weights && out, CODON_ERR_BAD_ARG, "bicubic_upsample: null pointer");
@@ -839,6 +864,26 @@ int codon_train_crops(const codon_crop_desc* desc, const uint8_t* pool, int64_t 
                   (long long)pool_bytes);
   }
   return train_crops(desc, pool, lut, target, guide, (hipStream_t)stream);
+}
+
+int codon_train_crops_labeled(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, const float* lut,
+                              float* source, float* guide, float* target, codon_stream_t stream) {
+  CODON_REQUIRE(desc && pool && lut && source && guide && target, CODON_ERR_BAD_ARG, "train_crops_labeled: null pointer");
+  CODON_REQUIRE(desc->n >= 1 && desc->n <= CODON_TRAIN_MAX_BATCH, CODON_ERR_BAD_ARG, "train_crops_labeled: batch %d (1..%d)",
+                desc->n, CODON_TRAIN_MAX_BATCH);
+  const int P = desc->crop;
+  CODON_REQUIRE(P >= 1 && P <= 2048, CODON_ERR_BAD_ARG, "train_crops_labeled: crop %d (1..2048)", P);
+  for (int b = 0; b < desc->n; ++b) {
+    const codon_crop_sample& c = desc->s[b];
+    CODON_REQUIRE(c.height >= P && c.width >= P && c.y0 >= 0 && c.x0 >= 0 && c.y0 <= c.height - P && c.x0 <= c.width - P &&
+                      c.op >= 0 && c.op <= 7,
+                  CODON_ERR_BAD_ARG, "train_crops_labeled: sample %d: %dx%d crop at (%d, %d) op %d outside the image", b,
+                  c.height, c.width, c.y0, c.x0, c.op);
+    CODON_REQUIRE(c.offset >= 0 && c.offset <= pool_bytes - 3 * (int64_t)c.height * c.width, CODON_ERR_BAD_ARG,
+                  "train_crops_labeled: sample %d: images at offset %lld run past the %lld-byte pool", b, (long long)c.offset,
+                  (long long)pool_bytes);
+  }
+  return train_crops_labeled(desc, pool, lut, source, guide, target, (hipStream_t)stream);
 }
 
 int codon_bicubic_downsample(int32_t batch, int32_t size, int32_t scale, const float* hr, const float* weights, float* out,

@@ -296,4 +296,227 @@ int ssim_l1_bwd(int B, int H, int W, const float* a, const float* b, const float
   return check_launch("ssim_l1_bwd_kernel");
 }
 
+// ---- hole-aware L1 + SSIM ------------------------------------------------------------------
+// Validity v: valid[idx] != 0, or (valid == null) t != 0 -- masked_rmse's rule.  Invalid pixels of BOTH images are loaded as 0
+// (a select, so that no value there -- NaN and Inf included -- reaches anything).  E = pixels whose whole 13x13 window, under
+// the same reflect indexing, is valid; there the SSIM value is ssim_fwd_kernel's.  Per tile: sum of ssim over E, sum of
+// |a - b| over valid pixels (floats) and the two counts (integers).  The derivative maps are 0 outside E.
+__device__ __forceinline__ bool px_valid(const unsigned char* __restrict__ valid, const float* __restrict__ t, long i) {
+  return valid ? valid[i] != 0 : t[i] != 0.0f;
+}
+
+// ws: 4 * ntiles words -- [0, nt) ssim sums, [nt, 2nt) L1 sums (float), [2nt, 3nt) valid counts, [3nt, 4nt) |E| (int32)
+__global__ __launch_bounds__(256) void masked_ssim_l1_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                 const unsigned char* __restrict__ valid,
+                                                                 float* __restrict__ ws, float* __restrict__ dmaps, int H,
+                                                                 int W, int tiles_x, int tiles_y, int ntiles, GaussW g,
+                                                                 float C1, float C2) {
+  __shared__ float ta[SS_P][SS_P + 1], tb[SS_P][SS_P + 1];
+  __shared__ float hz[5][SS_P][SS_T + 1];
+  __shared__ unsigned char tv[SS_P][SS_P + 4], hv[SS_P][SS_T + 4];   // validity; invalid pixels in the 13 horizontal taps
+  __shared__ float red[2][4];
+  __shared__ int redi[2][4];
+  const int tid = threadIdx.x;
+  const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, img = blockIdx.x / (tiles_x * tiles_y);
+  const int x0 = tx * SS_T, y0 = ty * SS_T;
+  const long ibase = (long)img * H * W;
+  for (int e = tid; e < SS_P * SS_P; e += 256) {
+    const int r = e / SS_P, c = e % SS_P;
+    const int yy = reflect_idx(y0 + r - SS_R, H), xx = reflect_idx(x0 + c - SS_R, W);
+    const long i = ibase + (long)yy * W + xx;
+    const float bv = b[i];
+    const bool v = valid ? valid[i] != 0 : bv != 0.0f;
+    const float av = a[i];
+    ta[r][c] = v ? av : 0.f;
+    tb[r][c] = v ? bv : 0.f;
+    tv[r][c] = v ? 1 : 0;
+  }
+  __syncthreads();
+  const float ca = ta[SS_P / 2][SS_P / 2], cb = tb[SS_P / 2][SS_P / 2];
+  for (int e = tid; e < SS_P * SS_T; e += 256) {   // horizontal pass of the 5 moments and of the invalid count
+    const int r = e / SS_T, c = e % SS_T;
+    float s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
+    int bad = 0;
+#pragma unroll
+    for (int k = 0; k <= 2 * SS_R; ++k) {
+      const float u = ta[r][c + k] - ca, v = tb[r][c + k] - cb, w = g.w[k];
+      s0 = fmaf(w, u, s0); s1 = fmaf(w, v, s1); s2 = fmaf(w, u * u, s2); s3 = fmaf(w, v * v, s3);
+      s4 = fmaf(w, u * v, s4);
+      bad += 1 - (int)tv[r][c + k];
+    }
+    hz[0][r][c] = s0; hz[1][r][c] = s1; hz[2][r][c] = s2; hz[3][r][c] = s3; hz[4][r][c] = s4;
+    hv[r][c] = (unsigned char)bad;
+  }
+  __syncthreads();
+  float lss = 0.f, ll1 = 0.f;
+  int nv = 0, ne = 0;
+  for (int e = tid; e < SS_T * SS_T; e += 256) {
+    const int r = e / SS_T, c = e % SS_T;
+    const int gy = y0 + r, gx = x0 + c;
+    float m[5] = {0, 0, 0, 0, 0};
+    int bad = 0;
+#pragma unroll
+    for (int k = 0; k <= 2 * SS_R; ++k) {
+      const float w = g.w[k];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) m[q] = fmaf(w, hz[q][r + k][c], m[q]);
+      bad += hv[r + k][c];
+    }
+    if (gy < H && gx < W) {
+      if (tv[r + SS_R][c + SS_R]) {
+        ll1 += fabsf(ta[r + SS_R][c + SS_R] - tb[r + SS_R][c + SS_R]);
+        nv += 1;
+      }
+      const bool in_e = bad == 0;
+      const float mu1 = m[0] + ca, mu2 = m[1] + cb;
+      const float s1 = m[2] - m[0] * m[0], s2 = m[3] - m[1] * m[1], s12 = m[4] - m[0] * m[1];
+      const float A1 = 2.f * mu1 * mu2 + C1, A2 = 2.f * s12 + C2;
+      const float B1 = mu1 * mu1 + mu2 * mu2 + C1, B2 = s1 + s2 + C2;
+      const float ssim = (A1 * A2) / (B1 * B2);
+      if (in_e) {
+        lss += ssim;
+        ne += 1;
+      }
+      if (dmaps) {
+        const float inv = 1.f / (B1 * B2);
+        const float dA1 = A2 * inv, dA2 = A1 * inv, dB1 = -ssim / B1, dB2 = -ssim / B2;
+        const float d_s11 = dB2;
+        const float d_s12 = 2.f * dA2;
+        const float d_mu1 = dA1 * 2.f * mu2 + dB1 * 2.f * mu1 + dA2 * (-2.f * mu2) + dB2 * (-2.f * mu1);
+        const long o = (long)img * 3 * H * W + (long)gy * W + gx;
+        dmaps[o] = in_e ? d_mu1 : 0.f;
+        dmaps[o + (long)H * W] = in_e ? d_s11 : 0.f;
+        dmaps[o + 2L * H * W] = in_e ? d_s12 : 0.f;
+      }
+    }
+  }
+#pragma unroll
+  for (int mm = 32; mm >= 1; mm >>= 1) {
+    lss += __shfl_xor(lss, mm, 64);
+    ll1 += __shfl_xor(ll1, mm, 64);
+    nv += __shfl_xor(nv, mm, 64);
+    ne += __shfl_xor(ne, mm, 64);
+  }
+  if ((tid & 63) == 0) {
+    red[0][tid >> 6] = lss; red[1][tid >> 6] = ll1;
+    redi[0][tid >> 6] = nv; redi[1][tid >> 6] = ne;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    ws[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    ws[ntiles + blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    int* wi = (int*)ws;
+    wi[2 * ntiles + blockIdx.x] = redi[0][0] + redi[0][1] + redi[0][2] + redi[0][3];
+    wi[3 * ntiles + blockIdx.x] = redi[1][0] + redi[1][1] + redi[1][2] + redi[1][3];
+  }
+}
+
+// One workgroup; image b is folded by wave b % 4: each lane sums a contiguous run of the image's tiles in index order, lane 0
+// then adds the runs in order -- float64 sums, integer counts, an order that depends on the image's size alone (an image's
+// partials are the same in any batch).  counts[b] = {n_b, e_b}; per_image[b] = {L1_b, SSIM_b} (SSIM_b = 1 when e_b = 0);
+// scales[b] = {-w_ssim / (B e_b), w_l1 / (B n_b)} rounded once to fp32 (0 for an empty set) for the backward;
+// value = (1/B) sum_b [w_l1 L1_b + w_ssim (1 - SSIM_b)], added in the order of b.
+__global__ __launch_bounds__(256) void masked_loss_finish_kernel(const float* __restrict__ ws, int B, int tpi, int ntiles,
+                                                                 double w_l1, double w_ssim, long long* __restrict__ counts,
+                                                                 double* per_image, float* __restrict__ scales,
+                                                                 double* __restrict__ value) {
+  __shared__ double rs[4][64], rl[4][64];
+  __shared__ long long rn[4][64], re[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int* wi = (const int*)ws;
+  const int per = (tpi + 63) / 64, runs = (tpi + per - 1) / per;
+  for (int b0 = 0; b0 < B; b0 += 4) {
+    const int b = b0 + wave;
+    if (b < B) {
+      const int i0 = b * tpi + lane * per, i1 = b * tpi + min(lane * per + per, tpi);
+      double ss = 0.0, sl = 0.0;
+      long long n = 0, e = 0;
+      for (int i = i0; i < i1; ++i) {
+        ss += (double)ws[i];
+        sl += (double)ws[ntiles + i];
+        n += wi[2 * ntiles + i];
+        e += wi[3 * ntiles + i];
+      }
+      rs[wave][lane] = ss; rl[wave][lane] = sl; rn[wave][lane] = n; re[wave][lane] = e;
+    }
+    __syncthreads();
+    if (b < B && lane == 0) {
+      double ss = 0.0, sl = 0.0;
+      long long n = 0, e = 0;
+      for (int k = 0; k < runs; ++k) { ss += rs[wave][k]; sl += rl[wave][k]; n += rn[wave][k]; e += re[wave][k]; }
+      counts[2 * b] = n;
+      counts[2 * b + 1] = e;
+      per_image[2 * b] = sl / (double)(n > 0 ? n : 1);
+      per_image[2 * b + 1] = e > 0 ? ss / (double)e : 1.0;
+      scales[2 * b] = e > 0 ? (float)(-w_ssim / ((double)B * (double)e)) : 0.f;
+      scales[2 * b + 1] = n > 0 ? (float)(w_l1 / ((double)B * (double)n)) : 0.f;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {            // this thread's own stores and, through the barriers above, the other waves'
+    double t = 0.0;
+    for (int b = 0; b < B; ++b) t += w_l1 * per_image[2 * b] + w_ssim * (1.0 - per_image[2 * b + 1]);
+    value[0] = t / (double)B;
+  }
+}
+
+// ssim_l1_bwd_kernel with the per-image scales read from the device, the upstream gradient applied here (gup[0]) and
+// exactly +0.0f SELECTED at every invalid pixel (a NaN there, or a negative upstream gradient, cannot leave a mark)
+__global__ __launch_bounds__(256) void masked_ssim_l1_bwd_kernel(const float* __restrict__ tmp, const float* __restrict__ a,
+                                                                 const float* __restrict__ b,
+                                                                 const unsigned char* __restrict__ valid,
+                                                                 const float* __restrict__ scales,
+                                                                 const float* __restrict__ gup, float* __restrict__ ga, int H,
+                                                                 int W, long total, GaussW g) {
+  const long idx = blockIdx.x * 256L + threadIdx.x;  // over (img, y, x)
+  if (idx >= total) return;
+  if (!px_valid(valid, b, idx)) {
+    ga[idx] = 0.f;
+    return;
+  }
+  const int x = (int)(idx % W);
+  const long t = idx / W;
+  const int y = (int)(t % H);
+  const long img = t / H;
+  const long HW = (long)H * W;
+  const float ssim_scale = scales[2 * img], l1_scale = scales[2 * img + 1];
+  const float* base = tmp + img * 3 * HW + x;
+  const float g_mu = adj_axis(base, H, W, y, g);
+  const float g_s11 = adj_axis(base + HW, H, W, y, g);
+  const float g_s12 = adj_axis(base + 2 * HW, H, W, y, g);
+  const float av = a[idx], bv = b[idx];
+  float r = ssim_scale * (g_mu + 2.f * av * g_s11 + bv * g_s12);
+  const float df = av - bv;
+  r += l1_scale * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f));
+  ga[idx] = r * gup[0];
+}
+
+int masked_l1_ssim_fwd(int B, int H, int W, const float* a, const float* b, const unsigned char* valid, float* ws,
+                       float* dmaps, double w_l1, double w_ssim, long long* counts, double* per_image, float* scales,
+                       double* value, hipStream_t stream) {
+  const int tx = (W + SS_T - 1) / SS_T, ty = (H + SS_T - 1) / SS_T;
+  const int nt = B * tx * ty;
+  const GaussW g = make_gauss(1.5);
+  hipLaunchKernelGGL(masked_ssim_l1_fwd_kernel, dim3(nt), dim3(256), 0, stream, a, b, valid, ws, dmaps, H, W, tx, ty, nt, g,
+                     0.01f * 0.01f, 0.03f * 0.03f);
+  int st = check_launch("masked_ssim_l1_fwd_kernel");
+  if (st != CODON_OK) return st;
+  hipLaunchKernelGGL(masked_loss_finish_kernel, dim3(1), dim3(256), 0, stream, ws, B, tx * ty, nt, w_l1, w_ssim, counts,
+                     per_image, scales, value);
+  return check_launch("masked_loss_finish_kernel");
+}
+
+int masked_l1_ssim_bwd(int B, int H, int W, const float* a, const float* b, const unsigned char* valid, const float* dmaps,
+                       const float* scales, const float* gup, float* tmp, float* ga, hipStream_t stream) {
+  const GaussW g = make_gauss(1.5);
+  const long t3 = (long)B * 3 * H * W, t1 = (long)B * H * W;
+  hipLaunchKernelGGL(gauss_adj_rows_kernel, dim3((unsigned)((t3 + 255) / 256)), dim3(256), 0, stream, dmaps, tmp, H, W,
+                     t3, g);
+  int st = check_launch("gauss_adj_rows_kernel");
+  if (st != CODON_OK) return st;
+  hipLaunchKernelGGL(masked_ssim_l1_bwd_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, stream, tmp, a, b, valid,
+                     scales, gup, ga, H, W, t1, g);
+  return check_launch("masked_ssim_l1_bwd_kernel");
+}
+
 }  // namespace codon

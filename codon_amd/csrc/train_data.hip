@@ -8,6 +8,7 @@
 // crops:      t[b][i][j] = lut[pool[off + (y0 + i')*W + (x0 + j')]],  y[b][i][j] the same from the guidance (at off + H*W),
 //             (i', j') = D4 op of (i, j) -- numpy: c = img[y0:y0+P, x0:x0+P]; op&1: c = c.T; op&2: c = c[::-1];
 //             op&4: c = c[:, ::-1]
+//             labeled: a third plane, the label, at off + 2*H*W -- source from the depth map, target from the label
 // downsample: PIL BICUBIC reduce (Keys a = -0.5 stretched by s, 4s taps per axis, out-of-image taps dropped and the rest
 //             renormalised): weights from the host, one row of 4s per output index; a horizontal pass, then a vertical pass,
 //             each a sequential fp32 sum over k = 0 .. 4s-1 of w[k] * v[clamp(o*s - 3s/2 + k)] (dropped taps have w = 0).
@@ -41,6 +42,28 @@ __global__ __launch_bounds__(256) void train_crops_kernel(const CropArgs a, cons
   const long o = (long)blockIdx.y * P * P + idx;
   target[o] = lut[pool[src]];
   guide[o] = lut[pool[src + hw]];
+}
+
+// the same window, op and table with a third plane: the degradation source from the depth map, the target from the label that
+// follows the guidance (at off + 2*H*W)
+__global__ __launch_bounds__(256) void train_crops_labeled_kernel(const CropArgs a, const unsigned char* __restrict__ pool,
+                                                                  const float* __restrict__ lut, float* __restrict__ source,
+                                                                  float* __restrict__ guide, float* __restrict__ target,
+                                                                  int P) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= P * P) return;
+  const codon_crop_sample d = a.s[blockIdx.y];
+  const int i = idx / P, j = idx - i * P;
+  int si = i, sj = j;
+  if (d.op & 4) sj = P - 1 - sj;
+  if (d.op & 2) si = P - 1 - si;
+  if (d.op & 1) { const int t = si; si = sj; sj = t; }
+  const long hw = (long)d.height * d.width;
+  const long src = d.offset + (long)(d.y0 + si) * d.width + (d.x0 + sj);
+  const long o = (long)blockIdx.y * P * P + idx;
+  source[o] = lut[pool[src]];
+  guide[o] = lut[pool[src + hw]];
+  target[o] = lut[pool[src + 2 * hw]];
 }
 
 // one workgroup per (output row oy, sample b): the horizontal pass of the 4s input rows that row reads goes to LDS, then
@@ -86,6 +109,17 @@ int train_crops(const codon_crop_desc* d, const unsigned char* pool, const float
   hipLaunchKernelGGL(train_crops_kernel, dim3((unsigned)((P * P + 255) / 256), (unsigned)d->n), dim3(256), 0, stream, a, pool,
                      lut, target, guide, P);
   return check_launch("train_crops_kernel");
+}
+
+int train_crops_labeled(const codon_crop_desc* d, const unsigned char* pool, const float* lut, float* source, float* guide,
+                        float* target, hipStream_t stream) {
+  CropArgs a;
+  for (int b = 0; b < d->n; ++b) a.s[b] = d->s[b];
+  for (int b = d->n; b < CODON_TRAIN_MAX_BATCH; ++b) a.s[b] = codon_crop_sample{};
+  const int P = d->crop;
+  hipLaunchKernelGGL(train_crops_labeled_kernel, dim3((unsigned)((P * P + 255) / 256), (unsigned)d->n), dim3(256), 0, stream, a,
+                     pool, lut, source, guide, target, P);
+  return check_launch("train_crops_labeled_kernel");
 }
 
 int bicubic_downsample(int B, int P, int s, const float* hr, const float* wtab, float* out, hipStream_t stream) {

@@ -3,7 +3,8 @@
   masked_rmse     RMSE over label != 0, exact integer sums   /root/reference/CODON_X4/test.py:148-164
   ssim            ssim_exact(img1, img2)                     /root/reference/CODON_X4/ssim_2.py:36-52
   L1SSIMLoss      w_l1 * mean|p - t| + w_ssim * (1 - SSIM(p, t)) with a HIP backward (the reference ships no
-                  loss -- SURVEY D8 -- so the combination is this repo's; the SSIM value is pinned)."""
+                  loss -- SURVEY D8 -- so the combination is this repo's; the SSIM value is pinned).
+  MaskedL1SSIMLoss  the same loss over the valid pixels only (holes = target 0, masked_rmse's rule)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -125,3 +126,82 @@ class L1SSIMLoss(torch.nn.Module):
 
     def forward(self, pred, target):
         return _L1SSIMFn.apply(pred, target, self.w_l1, self.w_ssim)
+
+
+# ---- hole-aware L1 + SSIM ---------------------------------------------------------------------------------------
+
+def _valid_u8(valid, like):
+    if valid is None:
+        return None
+    if valid.shape != like.shape:
+        raise ValueError(f"valid mask of shape {tuple(valid.shape)} for images of shape {tuple(like.shape)}")
+    if valid.dtype == torch.bool:
+        valid = valid.to(torch.uint8)
+    if valid.dtype != torch.uint8:
+        raise ValueError(f"valid mask must be uint8 or bool (nonzero = valid), got {valid.dtype}")
+    return valid.contiguous()
+
+
+def _masked_forward(p, t, valid, w_l1, w_ssim, want_maps):
+    """-> (value f64[1], counts i64 (B,2), per_image f64 (B,2), scales f32 (B,2), dmaps | None): two launches, no synchronisation."""
+    lib = L.load()
+    dev = ops._dev(p, t)
+    assert p.shape == t.shape and p.dim() == 4 and p.shape[1] == 1 and p.dtype == t.dtype == torch.float32
+    B, _, H, W = p.shape
+    ws = torch.empty(4 * lib.codon_ssim_tiles(B, H, W), dtype=torch.float32, device=dev)
+    dmaps = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if want_maps else None
+    val = torch.empty(1, dtype=torch.float64, device=dev)
+    counts = torch.empty((B, 2), dtype=torch.int64, device=dev)
+    per_image = torch.empty((B, 2), dtype=torch.float64, device=dev)
+    scales = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.codon_masked_l1_ssim_fwd(B, H, W, _p(p), _p(t), _p(valid), _p(ws), _p(dmaps), float(w_l1), float(w_ssim),
+                                             _p(counts), _p(per_image), _p(scales), _p(val), ops._stream(dev)),
+                "masked_l1_ssim_fwd")
+    return val, counts, per_image, scales, dmaps
+
+
+def masked_counts(target: torch.Tensor, valid: torch.Tensor = None) -> torch.Tensor:
+    """(B,2) int64 on the device: {n_b, e_b} -- valid pixels of image b, and pixels whose whole 13x13 SSIM window is valid.
+    valid: u8 / bool (B,1,H,W), nonzero = valid; None: target != 0."""
+    t = target.float().contiguous()
+    return _masked_forward(t, t, _valid_u8(valid, t), 1.0, 1.0, False)[1]
+
+
+class _MaskedL1SSIMFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, valid, w_l1, w_ssim):
+        p, t = pred.float().contiguous(), target.float().contiguous()
+        v = _valid_u8(valid, t)
+        val, _, _, scales, dmaps = _masked_forward(p, t, v, w_l1, w_ssim, ctx.needs_input_grad[0])
+        if dmaps is not None:
+            ctx.save_for_backward(p, t, dmaps, scales, *(() if v is None else (v,)))
+        return val.to(torch.float32).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        p, t, dmaps, scales, *v = ctx.saved_tensors
+        v = v[0] if v else None
+        dev = p.device
+        B, _, H, W = p.shape
+        tmp = torch.empty_like(dmaps)
+        ga = torch.empty_like(p)
+        up = g.to(torch.float32).reshape(1).contiguous()       # stays on the device: the kernel multiplies by it
+        with torch.cuda.device(dev):
+            L.check(lib.codon_masked_l1_ssim_bwd(B, H, W, _p(p), _p(t), _p(v), _p(dmaps), _p(scales), _p(up), _p(tmp), _p(ga),
+                                                 ops._stream(dev)), "masked_l1_ssim_bwd")
+        return ga, None, None, None, None
+
+
+class MaskedL1SSIMLoss(torch.nn.Module):
+    """(1/B) sum_b [ w_l1 * mean_valid |p - t| + w_ssim * (1 - mean_E ssim) ], the means per image: valid = the caller's mask or
+    target != 0, E = the pixels whose whole SSIM window is valid.  Nothing stored at an invalid pixel of either image reaches
+    the loss, and the gradient there is exactly +0."""
+
+    def __init__(self, w_l1: float = 1.0, w_ssim: float = 1.0):
+        super().__init__()
+        self.w_l1, self.w_ssim = w_l1, w_ssim
+
+    def forward(self, pred, target, valid=None):
+        return _MaskedL1SSIMFn.apply(pred, target, valid, self.w_l1, self.w_ssim)

@@ -7,7 +7,8 @@ built ON THE DEVICE from HR depth maps and guidance images uploaded once (codon_
 The degradation is a definition of this project, NOT pinned to the reference (its script is not shipped); it is restated in
 numpy in tests/train_data_ref.py and the two agree bit for bit.
 
-One step: GradSync.zero_grad -> synthesize -> forward -> L1SSIMLoss(out.float(), t) -> GradSync.backward ->
+One step: GradSync.zero_grad -> synthesize -> forward -> L1SSIMLoss(out.float(), t) (--mask-holes: MaskedL1SSIMLoss, which
+leaves the target's holes -- code 0 -- out of the loss; --train-label: targets from a third directory) -> GradSync.backward ->
 all_reduce_grads -> FlatAdam.step, the sequence of bench.py's training leg (optionally with gradient clipping, skipping of
 non-finite steps, EMA weights and a learning-rate schedule, all on the device: DESIGN 12.1).  Under torchrun every rank
 draws the whole global batch from the same seeded generator and keeps its shard (codon_amd.dist.shard_batch); the loss is
@@ -34,10 +35,11 @@ from .upsample import _keys, phase_weights
 
 DTYPES = {"bf16": torch.bfloat16, "f32": None}
 RESUME_KEYS = ("scale", "crop", "batch", "dtype", "clip_norm", "skip_nonfinite", "ema", "lr_schedule", "warmup_steps", "lr_min",
-               "lr_steps")
+               "lr_steps", "mask_holes", "min_valid", "train_label")
 # what a key compares as when a checkpoint's args do not carry it (one written before the option existed)
 RESUME_DEFAULTS = {"clip_norm": None, "skip_nonfinite": False, "ema": None, "lr_schedule": "constant", "warmup_steps": 0,
-                   "lr_min": 0.0, "lr_steps": None}
+                   "lr_min": 0.0, "lr_steps": None, "mask_holes": False, "min_valid": 0.0, "train_label": False}
+MAX_REDRAWS = 64                                    # draw(min_valid=): per sample, before it gives up
 LR_SCHEDULES = ("constant", "cosine")
 
 
@@ -82,54 +84,106 @@ class TrainSet:
     """Every (depth, guidance) pair of two directories, paired by file name (infer.list_pairs), read with io.read_gray and
     cropped to their common size (as infer._load_host does), in ONE flat uint8 pool on `device`: pair i's depth map at
     offsets[i], its guidance right behind it.  Uploaded once; a step reads nothing from the host.  `crop`: refuse images
-    smaller than it."""
+    smaller than it.  `label_dir`: a third plane per pair, the label (the target, which may carry holes coded 0 that the depth
+    map -- the degradation's source -- has filled in), behind the guidance; every pair needs a namesake there."""
 
-    def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None):
+    def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None, label_dir: str = None):
         from .infer import list_pairs
         self.files = list_pairs(depth_dir, color_dir)
         if not self.files:
             raise ValueError(f"TrainSet: no file of {color_dir} has a namesake in {depth_dir}")
+        self.has_label = label_dir is not None
+        self.planes = 3 if self.has_label else 2
         chunks, offsets, sizes, off = [], [], [], 0
         for f in self.files:
-            d = io.read_gray(os.path.join(depth_dir, f))
-            g = io.read_gray(os.path.join(color_dir, f))
-            h, w = min(d.shape[0], g.shape[0]), min(d.shape[1], g.shape[1])
+            planes = [io.read_gray(os.path.join(depth_dir, f)), io.read_gray(os.path.join(color_dir, f))]
+            if self.has_label:
+                if not os.path.isfile(os.path.join(label_dir, f)):
+                    raise ValueError(f"TrainSet: {f} has no namesake in {label_dir}")
+                planes.append(io.read_gray(os.path.join(label_dir, f)))
+            h, w = min(p.shape[0] for p in planes), min(p.shape[1] for p in planes)
             if crop is not None and (h < crop or w < crop):
                 raise ValueError(f"TrainSet: {f} is {h}x{w}, smaller than the {crop}x{crop} crop")
-            chunks += [np.ascontiguousarray(d[:h, :w]).reshape(-1), np.ascontiguousarray(g[:h, :w]).reshape(-1)]
+            chunks += [np.ascontiguousarray(p[:h, :w]).reshape(-1) for p in planes]
             offsets.append(off)
             sizes.append((h, w))
-            off += 2 * h * w
+            off += self.planes * h * w
         self.offsets = np.asarray(offsets, dtype=np.int64)
         self.sizes = np.asarray(sizes, dtype=np.int64)
         self.pool = torch.from_numpy(np.concatenate(chunks)).to(device)
+        self._integrals = None
 
     def __len__(self):
         return len(self.files)
 
+    def valid_integrals(self) -> dict:
+        """{pool offset: (H+1, W+1) int32 integral image of validity (code != 0)} of the TARGET plane -- the label if there is
+        one, else the depth map.  Built on first use (masking in force) from one read of the pool, kept on the host: a crop's
+        valid count is then four lookups and no step reads the device for it."""
+        if self._integrals is None:
+            pool = self.pool.cpu().numpy()
+            plane = 2 if self.has_label else 0
+            self._integrals = {}
+            for off, (h, w) in zip(self.offsets.tolist(), self.sizes.tolist()):
+                v = pool[off + plane * h * w:off + (plane + 1) * h * w].reshape(h, w) != 0
+                ii = np.zeros((h + 1, w + 1), dtype=np.int32)
+                ii[1:, 1:] = v.cumsum(0, dtype=np.int32).cumsum(1, dtype=np.int32)
+                self._integrals[off] = ii
+        return self._integrals
 
-def draw(rng: np.random.Generator, trainset: TrainSet, batch: int, crop: int, rank: int = 0, world: int = 1) -> np.ndarray:
+
+def valid_counts(trainset: TrainSet, descs: np.ndarray, crop: int) -> np.ndarray:
+    """Valid pixels of each descriptor's crop (a D4 op moves none in or out), from the host-side integral images."""
+    ii = trainset.valid_integrals()
+    out = np.empty(len(descs), dtype=np.int64)
+    for b, (off, _, _, y0, x0, _) in enumerate(np.asarray(descs, dtype=np.int64).tolist()):
+        t = ii[off]
+        out[b] = int(t[y0 + crop, x0 + crop]) - int(t[y0, x0 + crop]) - int(t[y0 + crop, x0]) + int(t[y0, x0])
+    return out
+
+
+def draw(rng: np.random.Generator, trainset: TrainSet, batch: int, crop: int, rank: int = 0, world: int = 1,
+         min_valid: float = 0.0) -> np.ndarray:
     """This rank's share of one global batch: (batch/world, 6) int64 rows (pool offset, H, W, y0, x0, D4 op).  Every rank
-    draws the WHOLE batch (the generators stay in step) and keeps shard_batch(batch, rank, world)."""
+    draws the WHOLE batch (the generators stay in step) and keeps shard_batch(batch, rank, world).
+    min_valid > 0: a sample whose crop holds fewer than min_valid * crop^2 valid pixels (TrainSet.valid_integrals) is drawn
+    again from the same generator -- index, y0, x0 and op together, at most MAX_REDRAWS times, then ValueError.  With
+    min_valid == 0 the generator is consumed exactly as without the option."""
     from .dist import shard_batch
     if batch < 1 or world < 1 or batch % world:
         raise ValueError(f"draw: a batch of {batch} does not split evenly over {world} ranks")
     if crop < 1 or (trainset.sizes < crop).any():
         raise ValueError(f"draw: crop {crop} does not fit the smallest image "
                          f"({int(trainset.sizes[:, 0].min())}x{int(trainset.sizes[:, 1].min())})")
+    if not 0.0 <= min_valid <= 1.0:
+        raise ValueError(f"draw: min_valid {min_valid} must lie in [0, 1]")
     idx = rng.integers(0, len(trainset.offsets), size=batch)
     hw = trainset.sizes[idx]
     y0 = rng.integers(0, hw[:, 0] - crop + 1)
     x0 = rng.integers(0, hw[:, 1] - crop + 1)
     op = rng.integers(0, 8, size=batch)
     d = np.stack([trainset.offsets[idx], hw[:, 0], hw[:, 1], y0, x0, op], axis=1).astype(np.int64)
+    if min_valid > 0:
+        need = min_valid * crop * crop
+        for b in np.flatnonzero(valid_counts(trainset, d, crop) < need).tolist():
+            for _ in range(MAX_REDRAWS):
+                i = int(rng.integers(0, len(trainset.offsets)))
+                h, w = trainset.sizes[i].tolist()
+                d[b] = [trainset.offsets[i], h, w, rng.integers(0, h - crop + 1), rng.integers(0, w - crop + 1),
+                        rng.integers(0, 8)]
+                if valid_counts(trainset, d[b:b + 1], crop)[0] >= need:
+                    break
+            else:
+                raise ValueError(f"draw: no crop with at least min_valid = {min_valid} of its {crop}x{crop} pixels valid in "
+                                 f"{MAX_REDRAWS} redraws of sample {b}: lower the threshold")
     lo, hi = shard_batch(batch, rank, world)
     return d[lo:hi]
 
 
 def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int):
     """(x, y, t), each (B,1,crop,crop) fp32 on the pool's device: the network's depth input (crop -> bicubic down by `scale`
-    -> bicubic up -> 8-bit), the guidance and the HR target.  Four launches on the caller's stream, no host synchronisation."""
+    -> bicubic up -> 8-bit), the guidance and the HR target.  Four launches on the caller's stream, no host synchronisation.
+    A TrainSet with labels: x is degraded from the depth plane, t comes from the label plane (codon_train_crops_labeled)."""
     lib = L.load()
     B = len(descs)
     if not 1 <= B <= L.TRAIN_MAX_BATCH:
@@ -148,14 +202,20 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int):
     p = crop // scale
     t = torch.empty((B, 1, crop, crop), dtype=torch.float32, device=dev)
     y = torch.empty_like(t)
+    src = torch.empty_like(t) if trainset.has_label else t        # what the degradation reads
     lr = torch.empty((B, 1, p, p), dtype=torch.float32, device=dev)
     x = torch.empty_like(t)
     P_ = C.c_void_p
     with ops._on(dev):
         st = ops._stream(dev)
-        L.check(lib.codon_train_crops(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(), P_(lut.data_ptr()),
-                                      P_(t.data_ptr()), P_(y.data_ptr()), st), "train_crops")
-        L.check(lib.codon_bicubic_downsample(B, crop, scale, P_(t.data_ptr()), P_(wdown.data_ptr()), P_(lr.data_ptr()), st),
+        if trainset.has_label:
+            L.check(lib.codon_train_crops_labeled(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(),
+                                                  P_(lut.data_ptr()), P_(src.data_ptr()), P_(y.data_ptr()), P_(t.data_ptr()), st),
+                    "train_crops_labeled")
+        else:
+            L.check(lib.codon_train_crops(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(), P_(lut.data_ptr()),
+                                          P_(t.data_ptr()), P_(y.data_ptr()), st), "train_crops")
+        L.check(lib.codon_bicubic_downsample(B, crop, scale, P_(src.data_ptr()), P_(wdown.data_ptr()), P_(lr.data_ptr()), st),
                 "bicubic_downsample")
         L.check(lib.codon_bicubic_upsample(B, p, p, scale, P_(lr.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()), st),
                 "bicubic_upsample")
@@ -222,7 +282,7 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         val: dict = None, ckpt: dict = None, start_step: int = 0, opt_state: dict = None, fixed: np.ndarray = None,
         args: dict = None, time_synth: bool = False, emit=print, clip_norm: float = None, skip_nonfinite: bool = False,
         ema_decay: float = None, lr_schedule: str = "constant", warmup: int = 0, lr_min: float = 0.0, lr_steps: int = None,
-        grad_hook=None) -> dict:
+        grad_hook=None, mask_holes: bool = False, min_valid: float = 0.0) -> dict:
     """Train `model` (fp32 parameters on the pool's device) from step start_step + 1 to step `steps`.
     val:   {"depth", "color", "label", "every"} -- rank 0 runs infer.run_loop every `every` steps and prints the means;
     ckpt:  {"path", "every"} -- rank 0 saves every `every` steps and after the last one;
@@ -233,14 +293,20 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     lr_schedule, warmup, lr_min, lr_steps: lr_at's curve (lr_steps defaults to `steps`); with the constant schedule and no
            warm-up no learning rate is passed to the optimizer, so the one a resumed optimizer state carries rules;
     grad_hook(step, gs): called between gs.backward and gs.all_reduce_grads (gradient noise, freezing a tensor, tests).
+    mask_holes: the criterion is MaskedL1SSIMLoss with valid = (t != 0) -- holes of the target (the label plane if the
+           TrainSet has one) carry no loss and no gradient; the log lines gain ` valid 0.xxx`, the global batch's
+           valid fraction, computed on the host from the descriptors (no device read);
+    min_valid: draw's threshold (needs mask_holes).
     Returns {"losses": [(step, loss)], "gs", "opt", "rng", "step", ...}."""
     from .dist import FlatAdam, GradSync
-    from .metrics import L1SSIMLoss
+    from .metrics import L1SSIMLoss, MaskedL1SSIMLoss
     if dtype not in DTYPES:
         raise ValueError(f"fit: dtype {dtype!r} (training runs in {', '.join(DTYPES)}; fp16 is inference-only)")
     rank, world = _world(process_group)
     if batch % world:
         raise ValueError(f"fit: a batch of {batch} does not split evenly over {world} ranks")
+    if not 0.0 <= min_valid <= 1.0 or (min_valid > 0 and not mask_holes):
+        raise ValueError(f"fit: min_valid {min_valid} must lie in [0, 1] and needs mask_holes")
     rng = np.random.default_rng(seed) if rng is None else rng
     dev = trainset.pool.device
     model.set_compute_dtype(DTYPES[dtype])
@@ -254,16 +320,27 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     if lr_schedule == "cosine" and lr_steps is None:
         lr_steps = steps
     lr_at(1, lr=lr, schedule=lr_schedule, warmup=warmup, lr_min=lr_min, lr_steps=lr_steps)       # refuses a bad curve up front
-    crit = L1SSIMLoss(1.0, 1.0)
+    crit = MaskedL1SSIMLoss(1.0, 1.0) if mask_holes else L1SSIMLoss(1.0, 1.0)
+    if mask_holes:
+        trainset.valid_integrals()                  # the one read of the pool, before the first step
     args = dict(args or {}, scale=scale, crop=crop, batch=batch, dtype=dtype, clip_norm=clip_norm,
                 skip_nonfinite=bool(skip_nonfinite), ema=ema_decay, lr_schedule=lr_schedule, warmup_steps=warmup, lr_min=lr_min,
                 lr_steps=lr_steps if lr_schedule == "cosine" else None)
+    args.update(mask_holes=bool(mask_holes), min_valid=float(min_valid), train_label=bool(trainset.has_label))
     stream = torch.cuda.current_stream(dev)
     losses, val_log, ev = [], [], []
     t_log, s_log = time.perf_counter(), start_step
     step = start_step
     for step in range(start_step + 1, steps + 1):
-        descs = fixed if fixed is not None else draw(rng, trainset, batch, crop, rank, world)
+        if fixed is not None:
+            descs = all_descs = fixed
+        elif mask_holes:
+            from .dist import shard_batch
+            all_descs = draw(rng, trainset, batch, crop, min_valid=min_valid)      # the whole batch, as every rank draws it
+            lo, hi = shard_batch(batch, rank, world)
+            descs = all_descs[lo:hi]
+        else:
+            descs = draw(rng, trainset, batch, crop, rank, world)
         if time_synth:
             e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             e[0].record(stream)
@@ -303,6 +380,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
             if opt.guarded:                         # the loss read-back has synchronised already
                 st = opt.stats()
                 line += f" gnorm {st['norm']:.6g} skipped {st['skipped']} clipped {st['clipped']}"
+            if mask_holes:
+                line += f" valid {valid_counts(trainset, all_descs, crop).sum() / (len(all_descs) * crop * crop):.3f}"
             if rank == 0:
                 emit(line)
         if val and rank == 0 and step % val["every"] == 0:
@@ -341,6 +420,13 @@ def parse_args(argv=None):
     ap.add_argument("--scale", type=int, required=True, choices=[4, 8, 16])
     ap.add_argument("--train-depth", required=True, help="HR depth maps (PNG, 8-bit)")
     ap.add_argument("--train-color", required=True, help="guidance images, paired with the depth maps by file name")
+    ap.add_argument("--train-label", default=None,
+                    help="targets, paired by file name: the depth maps are then only degraded into inputs (hole-filled depth "
+                         "with holey labels, as the reference's data)")
+    ap.add_argument("--mask-holes", action="store_true",
+                    help="pixels whose target is 0 carry no loss and no gradient (the rule of the printed RMSE)")
+    ap.add_argument("--min-valid", type=float, default=0.0,
+                    help="with --mask-holes: redraw a crop with less than this fraction of valid pixels")
     ap.add_argument("--crop", type=int, default=128)
     ap.add_argument("--batch", type=int, default=16, help="global batch (split over the ranks under torchrun)")
     ap.add_argument("--steps", type=int, default=1000, help="total steps (a resumed run continues up to this step)")
@@ -379,6 +465,10 @@ def parse_args(argv=None):
         ap.error("--resume and --weights exclude each other")
     if (a.val_depth is None) != (a.val_color is None):
         ap.error("--val-depth and --val-color go together")
+    if not 0.0 <= a.min_valid <= 1.0:
+        ap.error(f"--min-valid {a.min_valid} must lie in [0, 1]")
+    if a.min_valid > 0 and not a.mask_holes:
+        ap.error("--min-valid needs --mask-holes")
     if a.clip_norm is not None and not a.clip_norm > 0:
         ap.error(f"--clip-norm {a.clip_norm} must be positive")
     if a.ema is not None and not 0 <= a.ema < 1:
@@ -401,7 +491,8 @@ def parse_args(argv=None):
 def run_args(a) -> dict:
     return {"scale": a.scale, "crop": a.crop, "batch": a.batch, "dtype": a.dtype, "lr": a.lr, "seed": a.seed,
             "clip_norm": a.clip_norm, "skip_nonfinite": a.skip_nonfinite, "ema": a.ema, "lr_schedule": a.lr_schedule,
-            "warmup_steps": a.warmup_steps, "lr_min": a.lr_min, "lr_steps": a.lr_steps}
+            "warmup_steps": a.warmup_steps, "lr_min": a.lr_min, "lr_steps": a.lr_steps, "mask_holes": bool(a.mask_holes),
+            "min_valid": float(a.min_valid), "train_label": a.train_label is not None}
 
 
 def main(argv=None, emit=print) -> dict:
@@ -422,7 +513,7 @@ def main(argv=None, emit=print) -> dict:
         raise SystemExit(f"--batch {a.batch} does not split evenly over {world} ranks")
     if a.batch // world > L.TRAIN_MAX_BATCH:
         raise SystemExit(f"--batch {a.batch}: at most {L.TRAIN_MAX_BATCH} images per rank")
-    ts = TrainSet(a.train_depth, a.train_color, dev, crop=a.crop)
+    ts = TrainSet(a.train_depth, a.train_color, dev, crop=a.crop, label_dir=a.train_label)
     torch.manual_seed(a.seed)
     model = (CODONNet16 if a.scale == 16 else CODONNet)()
     rng = np.random.default_rng(a.seed)
@@ -447,7 +538,8 @@ def main(argv=None, emit=print) -> dict:
     res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,
               log_every=a.log_every, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,
               args=args, emit=emit, clip_norm=a.clip_norm, skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema,
-              lr_schedule=a.lr_schedule, warmup=a.warmup_steps, lr_min=a.lr_min, lr_steps=a.lr_steps)
+              lr_schedule=a.lr_schedule, warmup=a.warmup_steps, lr_min=a.lr_min, lr_steps=a.lr_steps,
+              mask_holes=a.mask_holes, min_valid=a.min_valid)
     res["model"] = model
     return res
 

@@ -494,6 +494,27 @@ int codon_ssim_l1_bwd(int32_t batch, int32_t height, int32_t width, const float*
                       const float* dmaps, float* tmp, float* ga, float ssim_scale, float l1_scale,
                       codon_stream_t stream);
 
+/* ---- hole-aware L1 + SSIM loss (codon_amd.metrics.MaskedL1SSIMLoss) ----------------------------------------
+ * No reference counterpart (it ships no loss); the validity rule is EvaluationResults' (CODON_X4/test.py:148-164:
+ * label == 0 is a hole).  pred p, target t: (B,1,H,W) fp32.  valid: u8 (B,1,H,W), nonzero = valid, or NULL for v = (t != 0).
+ *   n_b = #valid pixels of image b;  E_b = pixels whose whole 13x13 window is valid (reflect indexing), e_b = |E_b|
+ *   L1_b = sum_v |p - t| / max(n_b, 1);  SSIM_b = sum_{E_b} ssim / max(e_b, 1), 1 when e_b = 0 (ssim: ssim_fwd's per-pixel value)
+ *   value[0] (double) = (1/B) sum_b [ w_l1 L1_b + w_ssim (1 - SSIM_b) ]
+ * Invalid pixels of p and t are read as 0, so nothing stored there (NaN, Inf) reaches any result.  Two launches, no float
+ * atomics, every sum in a fixed order that depends on H and W alone, counts in integers, sums in float64.
+ *   ws: 4 * codon_ssim_tiles(B,H,W) 4-byte words of scratch;  dmaps: NULL or (B,3,H,W) derivative maps (0 outside E_b)
+ *   counts: int64 (B,2) {n_b, e_b};  per_image: double (B,2) {L1_b, SSIM_b};
+ *   scales: float (B,2) {-w_ssim / (B e_b), w_l1 / (B n_b)} (0 for an empty set), read by the backward.
+ * masked_l1_ssim_bwd: ga = upstream[0] * ( scales[b][0] d(sum_E ssim)/dp + scales[b][1] sign(p - t) ) at valid pixels and
+ * exactly +0.0f (selected, not multiplied) at invalid ones; upstream: one float in device memory; tmp: (B,3,H,W) scratch;
+ * H, W >= 7.  Two launches. */
+int codon_masked_l1_ssim_fwd(int32_t batch, int32_t height, int32_t width, const float* pred, const float* target,
+                             const uint8_t* valid, float* ws, float* dmaps, double w_l1, double w_ssim, int64_t* counts,
+                             double* per_image, float* scales, double* value, codon_stream_t stream);
+int codon_masked_l1_ssim_bwd(int32_t batch, int32_t height, int32_t width, const float* pred, const float* target,
+                             const uint8_t* valid, const float* dmaps, const float* scales, const float* upstream, float* tmp,
+                             float* ga, codon_stream_t stream);
+
 /* ---- synthetic-input generator: x4 / x8 / x16 bicubic upsample ---------------------------------
  * No reference counterpart (the reference's depth inputs are upsampled offline,
  * CODON_X4/test.py:70-77); defined in codon_amd/csrc/upsample.hip, restated in
@@ -608,6 +629,11 @@ typedef struct codon_crop_desc {
 } codon_crop_desc;
 int codon_train_crops(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, const float* lut, float* target,
                       float* guide, codon_stream_t stream);
+/* codon_train_crops_labeled: the same window, D4 op and table for records of THREE planes -- depth map, guidance, label (at
+ * s[b].offset + 2 * height * width): `source` (what the degradation reads) comes from the depth map, `target` from the label,
+ * which may carry holes (code 0) the hole-filled depth map does not.  Every record (3 * height * width bytes) inside the pool. */
+int codon_train_crops_labeled(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, const float* lut,
+                              float* source, float* guide, float* target, codon_stream_t stream);
 /* codon_bicubic_downsample: antialiased integer-factor reduction (PIL BICUBIC reduce; F.interpolate(mode="bicubic",
  * antialias=True, align_corners=False)) of hr (batch,1,size,size) fp32 by scale 4 / 8 / 16 to out (batch,1,size/scale,
  * size/scale).  weights: (size/scale) x (4*scale) fp32 -- row o holds the weights of input taps o*scale - 3*scale/2 + k,
