@@ -1,13 +1,19 @@
 """tests/bounds.py checks itself: round16 against single-rounded conversions known to be correct, and assert_rounded
 accepts a correctly rounded conv and rejects the wrong ones a whole-tensor RMSE bar lets through (a truncating store, one
-element 2 ulps off, one element never written, a tau so wide that the check decides nothing).  CPU only."""
+element 2 ulps off, one element never written, a tau so wide that the check decides nothing).  The weight-gradient helpers:
+the restated band planner equals the library's, the probe pixels cover the seams, the one-hot expectation equals float64
+conv2d_weight, and assert_wgrad passes torch's fp32 result, fails ONE removed product at the largest K, refuses K over its cap.
+CPU only."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from codon_amd import _lib as L
-from tests.bounds import assert_rounded, conv_ref, round16, tau_of, ulp
+from tests.bounds import (WGRAD_K_CAP, assert_rounded, assert_wgrad, conv_ref, round16, tau_of, ulp, wgrad_bands,
+                          wgrad_impulse_diff, wgrad_impulse_expect, wgrad_one_hot, wgrad_probe_pixels, wgrad_ref)
 
 DT16 = [torch.bfloat16, torch.float16]
 
@@ -167,3 +173,175 @@ def test_rejects_an_uninformative_tau(dtype):
     assert_rounded(got, ref, 2.0 ** -18 * S, dtype, "sim tau 2^-18 S")          # the widest tau the issue allows
     with pytest.raises(AssertionError, match="single allowed value"):
         assert_rounded(got, ref, 2.0 ** -8 * S, dtype, "sim tau 2^-8 S")
+
+
+# ---- weight gradients -------------------------------------------------------------------------------------------------
+
+WGRAD_FORMS = [(5, 128, 128), (5, 64, 64), (3, 64, 64), (3, 128, 64), (1, 128, 64)]
+
+
+def test_wgrad_bands_restates_the_library_planners():
+    """nsplit of wgrad_bands == codon_conv_wgrad_workspace_bytes / (4 cout cin k^2) (a host function: no GPU) over a grid of
+    batches and image sizes, 16-bit and fp32, W % 4 == 0 and not; the bands tile the tile rows."""
+    lib = L.load()
+    for dtype, code in ((torch.bfloat16, L.BF16), (torch.float16, L.F16), (torch.float32, L.F32)):
+        for k, cin, cout in WGRAD_FORMS:
+            for B in (1, 2, 3, 7, 11, 16, 32, 65, 128, 257, 512):
+                for H in (1, 3, 9, 20, 41, 44, 61, 128, 130, 480):
+                    for W in (33, 40, 63, 640):
+                        d = L.ConvDesc(B, H, W, cin, cout, k, cin + 64, 64, cout + 64, 64, 0, 0, 0, code)
+                        n = lib.codon_conv_wgrad_workspace_bytes(C.byref(d)) // (4 * cout * cin * k * k)
+                        for aligned in (True, False):
+                            p = wgrad_bands(dtype, k, cin, cout, B, H, W, aligned=aligned)
+                            assert p["nsplit"] == n, (dtype, k, cin, cout, B, H, W, n, p)
+                            assert sum(p["rows_per_band"]) == p["tiles"] == -(-H // p["th"]) and min(p["rows_per_band"]) >= 1
+    # the plans the issue names: the CLI default and bench.py --mode train, 5x5 128 -> 128 in bf16
+    assert wgrad_bands(torch.bfloat16, 5, 128, 128, 16, 128, 128)["rows_per_band"] == [6, 7]
+    assert wgrad_bands(torch.bfloat16, 5, 128, 128, 32, 480, 640)["rows_per_band"] == [48]
+    assert wgrad_bands(torch.bfloat16, 1, 128, 64, 32, 480, 640)["rows_per_band"] == [15] * 8
+    assert wgrad_bands(torch.bfloat16, 5, 64, 64, 1, 130, 40)["rows_per_band"] == [1] * 13       # test_conv2d_wgrad_slices_and_bands
+
+
+@pytest.mark.parametrize("dtype,k,shape,aligned", [(torch.bfloat16, 5, (16, 128, 128), True), (torch.bfloat16, 3, (65, 49, 33), True),
+                                                   (torch.float32, 1, (20, 53, 40), True), (torch.float32, 5, (11, 25, 40), False),
+                                                   (torch.float16, 1, (3, 7, 63), True)])
+def test_wgrad_probe_pixels_cover_the_seams(dtype, k, shape, aligned):
+    B, H, W = shape
+    cin, cout = (128, 128) if k == 5 else (64, 64) if k == 3 else (128, 64)
+    plan = wgrad_bands(dtype, k, cin, cout, B, H, W, aligned=aligned)
+    rounds = wgrad_probe_pixels(plan, B, H, W, cout)
+    assert all(len(r) == cout for r in rounds)
+    pix = [p for r in rounds for p in r]
+    assert all(0 <= b < B and 0 <= h < H and 0 <= w < W for b, h, w in pix)
+    rows, cols, imgs = {h for _, h, _ in pix}, {w for _, _, w in pix}, {b for b, _, _ in pix}
+    for t in range(1, plan["tiles"]):                                     # both sides of every tile-row seam, band seams included
+        assert t * plan["th"] - 1 in rows and t * plan["th"] in rows, (t, sorted(rows))
+    assert {0, H - 1} <= rows and {0, W - 1, (W - 1) // 32 * 32} <= cols and {0, B // 2, B - 1} <= imgs
+    if W > 32:
+        assert {31, 32} <= cols
+    assert {(h, w) for _, h, w in pix} >= {(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1)}
+
+
+@pytest.mark.parametrize("k", [1, 3, 5])
+def test_wgrad_impulse_expect_equals_float64_conv2d_weight(k):
+    B, H, W, cin, cout = 3, 9, 37, 8, 16
+    plan = wgrad_bands(torch.float32, k, 128, 64, B, H, W)
+    x, gy = _rand((B, cin, H, W), 1).double(), _rand((B, cout, H, W), 2).double()
+    pix = wgrad_probe_pixels(plan, B, H, W, cout)[0]
+    hot = wgrad_one_hot(pix, B, H, W).double()
+    ref, _ = wgrad_ref(x, hot, k)
+    assert torch.equal(wgrad_impulse_expect(x, pix, k, "gy"), ref)
+    pix = pix[:cin]
+    hot = wgrad_one_hot(pix, B, H, W).double()
+    ref, _ = wgrad_ref(hot, gy, k)
+    exp = wgrad_impulse_expect(gy, pix, k, "x")
+    assert exp.shape == ref.shape and torch.equal(exp, ref)
+    assert wgrad_impulse_diff(ref, exp, pix, k, "x", plan) is None
+
+
+def test_wgrad_impulse_diff_names_the_seam():
+    """A band that drops the first halo row of its second tile row: the message names the element, the pixel, its band and
+    tile row, and that the product is missing."""
+    k, B, H, W = 5, 16, 128, 128
+    plan = wgrad_bands(torch.bfloat16, 5, 128, 128, B, H, W)
+    x = _rand((B, 4, H, W), 3)
+    pix = wgrad_probe_pixels(plan, B, H, W, 128)[0]
+    exp = wgrad_impulse_expect(x, pix, k, "gy")
+    co = next(i for i, (_, h, _) in enumerate(pix) if h == 70)           # first row of tile row 7 = the first of band 1
+    b, h, w = pix[co]
+    got = exp.clone()
+    got[co, :, 0, :] = 0                                                  # x row h - 2: the first halo row
+    msg = wgrad_impulse_diff(got, exp, pix, k, "gy", plan)
+    assert f"(co,ci)=({co}, 0) tap (dy,dx)=(0, " in msg and "product missing" in msg, msg
+    assert f"gy pixel (b,h,w)=({b}, 70, {w})" in msg and "band 1 of 2 (tile rows 6..12), tile row 7 (rows 70..79)" in msg, msg
+    got = exp.clone()
+    got[co] *= 2
+    assert "product counted twice" in wgrad_impulse_diff(got, exp, pix, k, "gy", plan)
+    got = exp.clone()
+    got[co, :, 1, 1] = exp[co, :, 1, 2]
+    assert "the value expected at tap (1, 2)" in wgrad_impulse_diff(got, exp, pix, k, "gy", plan)
+
+
+@pytest.mark.parametrize("dtype", DT16 + [torch.float32])
+def test_assert_wgrad_passes_torch_fp32(dtype):
+    B, H, W, k = 32, 44, 40, 5
+    q = (lambda t: t.to(dtype).float()) if dtype != torch.float32 else (lambda t: t)
+    x, gy = q(_rand((B, 16, H, W), 1)), q(_rand((B, 8, H, W), 2))
+    ref, S = wgrad_ref(x, gy, k)
+    assert ref.dtype == torch.float64 and tuple(ref.shape) == (8, 16, 5, 5) and (S >= ref.abs()).all()
+    got = torch.nn.grad.conv2d_weight(x, (8, 16, k, k), gy, padding=2)
+    s = assert_wgrad(got, ref, S, f"torch fp32 {dtype}", K=B * H * W)
+    assert s["max_err_over_S"] < 2.0 ** -22                              # fp32 summation: a few units of 2^-24 S
+    bad = got.clone()
+    bad[3, 5, 2, 2] = float("nan")
+    with pytest.raises(AssertionError, match=r"(?s)1 of .*\(co,ci,dy,dx\)=\(3, 5, 2, 2\): got nan"):
+        assert_wgrad(bad, ref, S, "sim nan", K=B * H * W)
+
+
+def test_assert_wgrad_fails_one_removed_product_at_the_largest_K():
+    """K = 16 x 128 x 128 = 2^18, exactly on the cap (the largest GPU case): the float64 reference with ONE product of
+    median size taken out of one element must fail, and the message must name the element."""
+    B, H, W, k, cin, cout = 16, 128, 128, 5, 4, 4
+    assert B * H * W == WGRAD_K_CAP
+    x, gy = _rand((B, cin, H, W), 1).bfloat16().float(), _rand((B, cout, H, W), 2).bfloat16().float()
+    ref, S = wgrad_ref(x, gy, k)
+    assert_wgrad(ref.float(), ref, S, "sim fp32-rounded reference", K=B * H * W)
+    for co, ci, dy, dx in [(0, 0, 0, 0), (3, 1, 2, 2), (1, 3, 4, 1)]:
+        xs = F.pad(x[:, ci].double(), (2, 2, 2, 2))[:, dy:dy + H, dx:dx + W]
+        prod = (gy[:, co].double() * xs).flatten()
+        assert abs(float(prod.sum()) - float(ref[co, ci, dy, dx])) < 1e-9
+        med = prod.abs().median()
+        i = int((prod.abs() - med).abs().argmin())
+        for scale in (-1.0, 1.0):                                        # the product dropped; the product counted twice
+            got = ref.clone()
+            got[co, ci, dy, dx] += scale * prod[i]
+            with pytest.raises(AssertionError, match=rf"(?s)1 of .*\(co,ci,dy,dx\)=\({co}, {ci}, {dy}, {dx}\)"):
+                assert_wgrad(got, ref, S, "sim one product", K=B * H * W)
+
+
+def test_assert_wgrad_refuses_a_case_over_the_K_cap():
+    ref = torch.ones((2, 2, 1, 1), dtype=torch.float64)
+    assert_wgrad(ref, ref, ref, "sim on the cap", K=WGRAD_K_CAP)
+    with pytest.raises(AssertionError, match="cannot see one dropped product"):
+        assert_wgrad(ref, ref, ref, "sim over the cap", K=WGRAD_K_CAP + 1)
+
+
+def test_wgrad_cases_cover_every_plan_class_per_form_and_dtype():
+    """The case table itself: per kernel family, dtype and form one band of >= 3 tile rows, uneven bands, and nsplit below 8,
+    a multiple of 8 and 8 n + r; W % 32 takes 1, 8 and 31 (8 alone where the kernel needs W % 4 == 0).  The planner is a host
+    function, so a planner change that empties a plan class shows here, without a GPU."""
+    from tests import test_gpu_wgrad_plans as P
+    seen = {}
+    for prm in P._cases():
+        fam, dtype, form, cls, shape, aligned = prm.values
+        plan = wgrad_bands(dtype, *form, *shape, aligned=aligned)
+        assert plan["nsplit"] == P._nsplit(dtype, *form, *shape)
+        s = seen.setdefault((fam, dtype, form), {"rows3": False, "uneven": False, "ns": set(), "wmod": set()})
+        s["rows3"] |= max(plan["rows_per_band"]) >= 3
+        s["uneven"] |= len(set(plan["rows_per_band"])) > 1
+        s["ns"].add("<8" if plan["nsplit"] < 8 else "8n" if plan["nsplit"] % 8 == 0 else "8n+r")
+        s["wmod"].add(shape[2] % 32)
+    assert len(seen) == 4 * len(P.FORMS)
+    for key, s in seen.items():
+        assert s["rows3"] and s["uneven"] and s["ns"] == {"<8", "8n", "8n+r"}, (key, s)
+    for fam, want in (("c8", {1, 8, 31}), ("f32_t16", {8}), ("f32_r1", {1, 31, 8})):
+        got = set().union(*(s["wmod"] for (f, _, _), s in seen.items() if f == fam))
+        assert want <= got, (fam, got)
+
+
+def test_wgrad_impulse_diff_calls_a_pixel_past_the_ragged_edge_outside():
+    """One-hot x on the last row: the taps whose gy pixel lies below the image (rows H .. tiles th - 1 of the ragged last
+    tile row) or right of it are 'outside the image', not given a band."""
+    k, B, H, W = 5, 3, 19, 33
+    plan = wgrad_bands(torch.bfloat16, 5, 128, 128, B, H, W)
+    assert plan["tiles"] * plan["th"] > H
+    gy = _rand((B, 4, H, W), 5)
+    pix = [(1, H - 1, W - 1)]
+    exp = wgrad_impulse_expect(gy, pix, k, "x")
+    got = exp.clone()
+    got[0, 0, 0, 4] = 1.0                                                 # gy pixel (H + 1, W - 3): below the image
+    got[0, 0, 4, 0] = 2.0                                                 # gy pixel (H - 3, W + 1): right of it
+    got[0, 0, 2, 2] += 1.0                                                # gy pixel (H - 1, W - 1): the last tile row
+    lines = wgrad_impulse_diff(got, exp, pix, k, "x", plan).splitlines()
+    assert len(lines) == 4 and lines[1].endswith("outside the image") and lines[3].endswith("outside the image"), lines
+    assert f"tile row {plan['tiles'] - 1} " in lines[2] and "tile column 1" in lines[2], lines

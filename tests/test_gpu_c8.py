@@ -565,8 +565,28 @@ def test_conv_sum_into_equals_conv_then_add(shape, dtype, accumulate):
     assert torch.equal(ops.to_nchw(t1)[:, 128:].float(), ref_t.to(dtype).float())
 
 
+# shapes whose shared band plan (wgrad16_plan, k = 1: 4-row tiles) gives every band at least two tile rows; at B <= 3 on small
+# images every band is one tile row.  (64, 44, 40): 4 bands of 2, 3, 3, 3; (16, 128, 128): 16 bands of 2
+MULTIROW_1X1 = [(64, 44, 40), (16, 128, 128)]
+
+
+def _assert_1x1_plan(shape, dtype, ctx, cty, cox, coy):
+    """The premise of a MULTIROW_1X1 shape, read from the workspace size of the launch the fused 1x1 backward shares."""
+    import ctypes as C
+    from codon_amd import _lib as L
+    from tests.bounds import wgrad_bands
+    B, H, W = shape
+    d = L.ConvDesc(B, H, W, 128, 64, 1, ctx, cox, cty, coy, 0, 0, 0, L.BF16 if dtype == torch.bfloat16 else L.F16)
+    nsplit = L.load().codon_conv_wgrad_workspace_bytes(C.byref(d)) // (4 * 64 * 128)
+    plan = wgrad_bands(dtype, 1, 128, 64, B, H, W)
+    print(f"[plan] conv1x1_bwd {B}x{H}x{W}: nsplit {nsplit}, nbands {nsplit // B}, tile rows per band {plan['rows_per_band']}")
+    assert nsplit == plan["nsplit"], (shape, nsplit, plan)
+    if shape in MULTIROW_1X1:
+        assert min(plan["rows_per_band"]) >= 2, (shape, plan)
+
+
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("shape", [(2, 19, 45), (1, 1, 1), (1, 33, 70), (2, 64, 96)])
+@pytest.mark.parametrize("shape", [(2, 19, 45), (1, 1, 1), (1, 33, 70), (2, 64, 96)] + MULTIROW_1X1)
 def test_conv1x1_bwd_equals_wgrad_plus_masked_dgrad(shape, dtype):
     """codon_conv1x1_bwd (dW and the ReLU-masked dX of a 128 -> 64 1x1 conv from one pass over x and gy) == codon_conv2d_wgrad
     + codon_conv2d_fwd(PACK_DGRAD, MASK_RELU), bit for bit, including accumulation into dW and slices of wider buffers."""
@@ -575,6 +595,7 @@ def test_conv1x1_bwd_equals_wgrad_plus_masked_dgrad(shape, dtype):
     from codon_amd.ops import Slice
     dev = _dev()
     B, H, W = shape
+    _assert_1x1_plan(shape, dtype, 192, 128, 64, 64)
     x = ops.from_nchw(torch.relu(_rand((B, 192, H, W), 1)).to(dev), dtype)       # the conv input = channels 64..191
     g = ops.from_nchw(_rand((B, 128, H, W), 2).to(dev), dtype)                  # gy = channels 64..127
     w = _rand((64, 128, 1, 1), 3, 0.1).to(dev)
@@ -600,7 +621,7 @@ def test_conv1x1_bwd_equals_wgrad_plus_masked_dgrad(shape, dtype):
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("shape", [(2, 19, 45), (1, 1, 1), (1, 50, 70), (2, 64, 96)])
+@pytest.mark.parametrize("shape", [(2, 19, 45), (1, 1, 1), (1, 50, 70), (2, 64, 96)] + MULTIROW_1X1)
 @pytest.mark.parametrize("accumulate_in", [False, True])
 def test_fused_cac_backward_equals_the_apply_pass(shape, dtype, accumulate_in):
     """Round 4: the CAC gate backward without its apply pass.  codon_cac_bwd_reduce_acc (pass A that also records every
@@ -613,6 +634,7 @@ def test_fused_cac_backward_equals_the_apply_pass(shape, dtype, accumulate_in):
     from codon_amd.ops import Slice
     dev = _dev()
     B, H, W = shape
+    _assert_1x1_plan(shape, dtype, 128, 128, 0, 0)
     # coarse values: many exact ties across channels and pixels
     q = lambda seed, s=1.0: ops.from_nchw(((_rand((B, 128, H, W), seed, s) * 4).round() / 4).to(dev), dtype)
     g_oc, pre2, g_in0 = q(1, 0.5), q(2), q(3, 0.5)
