@@ -133,6 +133,8 @@ SIGNATURES = {
     "codon_postprocess_u8": (C.c_int, [C.c_int64, _P, _P, _P]),
     "codon_postprocess_u8_dt": (C.c_int, [C.c_int64, _P, C.c_int32, _P, _P]),
     "codon_masked_sqerr": (C.c_int, [C.c_int64, _P, _P, _P, _P]),
+    "codon_postprocess_u16_dt": (C.c_int, [C.c_int64, _P, C.c_int32, C.c_int32, _P, _P]),
+    "codon_masked_sqerr_u16": (C.c_int, [C.c_int64, _P, _P, _P, _P]),
     "codon_ssim_tiles": (_I, [_I, _I, _I]),
     "codon_ssim_fwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "codon_l1_fwd": (C.c_int, [C.c_int64, _P, _P, _P, _I, _P, _P]),
@@ -159,6 +161,8 @@ SIGNATURES = {
     "codon_train_crops_labeled": (C.c_int, [C.POINTER(CropDesc), _P, C.c_int64, _P, _P, _P, _P, _P]),
     "codon_bicubic_downsample": (C.c_int, [_I, _I, _I, _P, _P, _P, _P]),
     "codon_quantize_u8": (C.c_int, [C.c_int64, _P, _P, _P]),
+    "codon_train_crops_u16": (C.c_int, [C.POINTER(CropDesc), _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "codon_quantize_levels": (C.c_int, [C.c_int64, _P, _P, _I, _P]),
     "codon_weight_checksum_workspace_bytes": (_S, []),
     "codon_weight_checksum": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P]),
     "codon_weight_checksum_clear": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P, _I, _P]),

@@ -105,6 +105,8 @@ int bicubic_upsample(int, int, int, int, const float*, const float*, float*, hip
 int postprocess_u8(const float*, unsigned char*, long, hipStream_t);
 int postprocess_u8_f16(const void*, unsigned char*, long, hipStream_t);
 int masked_sqerr(const unsigned char*, const unsigned char*, long, unsigned long long*, hipStream_t);
+int postprocess_u16(const void*, int, int, unsigned short*, long, hipStream_t);
+int masked_sqerr_u16(const unsigned short*, const unsigned short*, long, unsigned long long*, hipStream_t);
 int ssim_tiles(int, int, int);
 int ssim_fwd(int, int, int, const float*, const float*, float*, float*, double*, hipStream_t);
 int l1_fwd(long, const float*, const float*, float*, int, double*, hipStream_t);
@@ -125,6 +127,8 @@ int train_crops(const codon_crop_desc*, const unsigned char*, const float*, floa
 int train_crops_labeled(const codon_crop_desc*, const unsigned char*, const float*, float*, float*, float*, hipStream_t);
 int bicubic_downsample(int, int, int, const float*, const float*, float*, hipStream_t);
 int quantize_u8(long, float*, const float*, hipStream_t);
+int train_crops_u16(const codon_crop_desc*, const unsigned char*, const float*, const float*, float*, float*, float*, hipStream_t);
+int quantize_levels(long, float*, const float*, int, hipStream_t);
 size_t weight_checksum_workspace_bytes();
 int weight_checksum(const codon_wsum_desc*, void*, unsigned long long*, int, int*, int*, int, hipStream_t);
 
@@ -792,6 +796,23 @@ int codon_masked_sqerr(int64_t n, const uint8_t* label, const uint8_t* out, uint
   return masked_sqerr(label, out, (long)n, (unsigned long long*)acc, (hipStream_t)stream);
 }
 
+int codon_postprocess_u16_dt(int64_t n, const void* x, int32_t dtype, int32_t depth_max, uint16_t* out, codon_stream_t stream) {
+  CODON_REQUIRE(x && out && n > 0, CODON_ERR_BAD_ARG, "postprocess_u16_dt: null pointer or n <= 0");
+  CODON_REQUIRE(dtype == CODON_F32 || dtype == CODON_F16 || dtype == CODON_BF16, CODON_ERR_UNSUPPORTED,
+                "postprocess_u16_dt: dtype %d (fp32, fp16 or bf16)", dtype);
+  CODON_REQUIRE(depth_max >= 1 && depth_max <= 65535, CODON_ERR_BAD_ARG, "postprocess_u16_dt: depth_max %d (1..65535)",
+                depth_max);
+  CODON_REQUIRE(((uintptr_t)out & 1) == 0, CODON_ERR_BAD_ARG, "postprocess_u16_dt: out is not 2-byte aligned");
+  return postprocess_u16(x, dtype, depth_max, out, (long)n, (hipStream_t)stream);
+}
+
+int codon_masked_sqerr_u16(int64_t n, const uint16_t* label, const uint16_t* out, uint64_t* acc, codon_stream_t stream) {
+  CODON_REQUIRE(label && out && acc && n > 0, CODON_ERR_BAD_ARG, "masked_sqerr_u16: null pointer or n <= 0");
+  CODON_REQUIRE(n <= ((int64_t)1 << 26), CODON_ERR_UNSUPPORTED, "masked_sqerr_u16: %lld pixels (at most 2^26)", (long long)n);
+  CODON_REQUIRE((((uintptr_t)label | (uintptr_t)out) & 1) == 0, CODON_ERR_BAD_ARG, "masked_sqerr_u16: unaligned plane");
+  return masked_sqerr_u16(label, out, (long)n, (unsigned long long*)acc, (hipStream_t)stream);
+}
+
 int32_t codon_ssim_tiles(int32_t batch, int32_t height, int32_t width) {
   return shape_ok(batch, height, width) ? ssim_tiles(batch, height, width) : 0;
 }
@@ -898,6 +919,37 @@ int codon_bicubic_downsample(int32_t batch, int32_t size, int32_t scale, const f
 int codon_quantize_u8(int64_t n, float* x, const float* lut, codon_stream_t stream) {
   CODON_REQUIRE(x && lut && n >= 1, CODON_ERR_BAD_ARG, "quantize_u8: null pointer or empty");
   return quantize_u8((long)n, x, lut, (hipStream_t)stream);
+}
+
+int codon_train_crops_u16(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, const float* lut16,
+                          const float* lut8, float* source, float* guide, float* target, codon_stream_t stream) {
+  CODON_REQUIRE(desc && pool && lut16 && lut8 && source && guide, CODON_ERR_BAD_ARG, "train_crops_u16: null pointer");
+  CODON_REQUIRE(((uintptr_t)pool & 1) == 0, CODON_ERR_BAD_ARG, "train_crops_u16: the pool is not 2-byte aligned");
+  CODON_REQUIRE(desc->n >= 1 && desc->n <= CODON_TRAIN_MAX_BATCH, CODON_ERR_BAD_ARG, "train_crops_u16: batch %d (1..%d)", desc->n,
+                CODON_TRAIN_MAX_BATCH);
+  const int P = desc->crop;
+  CODON_REQUIRE(P >= 1 && P <= 2048, CODON_ERR_BAD_ARG, "train_crops_u16: crop %d (1..2048)", P);
+  const int64_t per_pixel = target ? 5 : 3;              // u16 depth (+ u16 label) + u8 guidance
+  for (int b = 0; b < desc->n; ++b) {
+    const codon_crop_sample& c = desc->s[b];
+    CODON_REQUIRE(c.height >= P && c.width >= P && c.y0 >= 0 && c.x0 >= 0 && c.y0 <= c.height - P && c.x0 <= c.width - P &&
+                      c.op >= 0 && c.op <= 7,
+                  CODON_ERR_BAD_ARG, "train_crops_u16: sample %d: %dx%d crop at (%d, %d) op %d outside the image", b, c.height,
+                  c.width, c.y0, c.x0, c.op);
+    CODON_REQUIRE(c.offset >= 0 && c.offset % 2 == 0, CODON_ERR_BAD_ARG,
+                  "train_crops_u16: sample %d: offset %lld is odd or negative (u16 planes start at even bytes)", b,
+                  (long long)c.offset);
+    CODON_REQUIRE(c.offset <= pool_bytes - per_pixel * (int64_t)c.height * c.width, CODON_ERR_BAD_ARG,
+                  "train_crops_u16: sample %d: images at offset %lld run past the %lld-byte pool", b, (long long)c.offset,
+                  (long long)pool_bytes);
+  }
+  return train_crops_u16(desc, pool, lut16, lut8, source, guide, target, (hipStream_t)stream);
+}
+
+int codon_quantize_levels(int64_t n, float* x, const float* lut16, int32_t depth_max, codon_stream_t stream) {
+  CODON_REQUIRE(x && lut16 && n >= 1, CODON_ERR_BAD_ARG, "quantize_levels: null pointer or empty");
+  CODON_REQUIRE(depth_max >= 1 && depth_max <= 65535, CODON_ERR_BAD_ARG, "quantize_levels: depth_max %d (1..65535)", depth_max);
+  return quantize_levels((long)n, x, lut16, depth_max, (hipStream_t)stream);
 }
 
 size_t codon_weight_checksum_workspace_bytes(void) { return weight_checksum_workspace_bytes(); }

@@ -63,6 +63,49 @@ __global__ __launch_bounds__(256) void masked_sqerr_kernel(const unsigned char* 
   }
 }
 
+// ---- 16-bit depth codes ------------------------------------------------------------------
+// code = rint(clamp(x, 0, 1) * float32(depth_max)), round half to even; the product in fp32 whatever the input's dtype (fp16
+// and bf16 are upcast first, exactly); NaN -> 0 (fmaxf returns its other operand).  No reference counterpart: the
+// reference's outputs are 8-bit.  One multiply, one rounding: nothing for the compiler to contract.
+template <typename T> __device__ __forceinline__ float load_f32(const T* p, long i) { return (float)p[i]; }
+struct bf16_bits { unsigned short u; };
+template <> __device__ __forceinline__ float load_f32<bf16_bits>(const bf16_bits* p, long i) {
+  return __uint_as_float((unsigned)p[i].u << 16);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void postprocess_u16_kernel(const T* __restrict__ x, unsigned short* __restrict__ o,
+                                                              float levels, long n) {
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= n) return;
+  const float v = fminf(fmaxf(load_f32<T>(x, i), 0.f), 1.f) * levels;
+  o[i] = (unsigned short)(int)rintf(v);
+}
+
+// masked_sqerr_kernel over u16 codes: |d| <= 65535, d * d < 2^32, formed in 64 bits.
+__global__ __launch_bounds__(256) void masked_sqerr_u16_kernel(const unsigned short* __restrict__ label,
+                                                               const unsigned short* __restrict__ out, long n,
+                                                               unsigned long long* __restrict__ acc /* [2] */) {
+  unsigned long long s = 0, c = 0;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int l = label[i];
+    if (l != 0) {
+      const long long d = l - (int)out[i];
+      s += (unsigned long long)(d * d);
+      c += 1;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    s += __shfl_xor(s, m, 64);
+    c += __shfl_xor(c, m, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&acc[0], s);
+    atomicAdd(&acc[1], c);
+  }
+}
+
 // ---- SSIM ----------------------------------------------------------------------------------------------
 constexpr int SS_R = 6, SS_T = 32, SS_P = SS_T + 2 * SS_R;  // radius, tile, padded tile
 
@@ -257,6 +300,27 @@ int masked_sqerr(const unsigned char* label, const unsigned char* out, long n, u
   const unsigned blocks = (unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256);
   hipLaunchKernelGGL(masked_sqerr_kernel, dim3(blocks), dim3(256), 0, stream, label, out, n, acc);
   return check_launch("masked_sqerr_kernel");
+}
+
+int postprocess_u16(const void* x, int dtype, int depth_max, unsigned short* o, long n, hipStream_t stream) {
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  const float levels = (float)depth_max;
+  if (dtype == CODON_F16)
+    hipLaunchKernelGGL(postprocess_u16_kernel<_Float16>, grid, block, 0, stream, (const _Float16*)x, o, levels, n);
+  else if (dtype == CODON_BF16)
+    hipLaunchKernelGGL(postprocess_u16_kernel<bf16_bits>, grid, block, 0, stream, (const bf16_bits*)x, o, levels, n);
+  else
+    hipLaunchKernelGGL(postprocess_u16_kernel<float>, grid, block, 0, stream, (const float*)x, o, levels, n);
+  return check_launch("postprocess_u16_kernel");
+}
+
+int masked_sqerr_u16(const unsigned short* label, const unsigned short* out, long n, unsigned long long* acc,
+                     hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), stream);
+  if (e != hipSuccess) { set_error("masked_sqerr_u16: memset: %s", hipGetErrorString(e)); return CODON_ERR_LAUNCH; }
+  const unsigned blocks = (unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256);
+  hipLaunchKernelGGL(masked_sqerr_u16_kernel, dim3(blocks), dim3(256), 0, stream, label, out, n, acc);
+  return check_launch("masked_sqerr_u16_kernel");
 }
 
 int ssim_tiles(int B, int H, int W) { return B * ((W + SS_T - 1) / SS_T) * ((H + SS_T - 1) / SS_T); }

@@ -13,6 +13,10 @@
 //             renormalised): weights from the host, one row of 4s per output index; a horizontal pass, then a vertical pass,
 //             each a sequential fp32 sum over k = 0 .. 4s-1 of w[k] * v[clamp(o*s - 3s/2 + k)] (dropped taps have w = 0).
 // quantize:   x = lut[rint(clamp(x, 0, 1) * 255f)]  (round half to even)
+//
+// 16-bit depth: the same window and D4 op over records of little-endian u16 depth (and label) planes followed by
+// the u8 guidance; code c is lut16[c] = float32(float64(c) / depth_max), a 65 536-entry table, and the degraded input goes back
+// onto the data set's own grid: x = lut16[rint(clamp(x, 0, 1) * (float)depth_max)].
 
 #include "codon_common.h"
 
@@ -66,6 +70,33 @@ __global__ __launch_bounds__(256) void train_crops_labeled_kernel(const CropArgs
   target[o] = lut[pool[src + 2 * hw]];
 }
 
+// 16-bit records: depth plane (H*W u16) at the even byte offset `offset`, then -- labeled -- the label plane (H*W u16), then
+// the guidance (H*W u8).  target == nullptr: the unlabeled record, `source` is the HR target too.  Uniform branch.
+__global__ __launch_bounds__(256) void train_crops_u16_kernel(const CropArgs a, const unsigned char* __restrict__ pool,
+                                                              const float* __restrict__ lut16, const float* __restrict__ lut8,
+                                                              float* __restrict__ source, float* __restrict__ guide,
+                                                              float* __restrict__ target, int P) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= P * P) return;
+  const codon_crop_sample d = a.s[blockIdx.y];
+  const int i = idx / P, j = idx - i * P;
+  int si = i, sj = j;
+  if (d.op & 4) sj = P - 1 - sj;
+  if (d.op & 2) si = P - 1 - si;
+  if (d.op & 1) { const int t = si; si = sj; sj = t; }
+  const long hw = (long)d.height * d.width;
+  const long px = (long)(d.y0 + si) * d.width + (d.x0 + sj);
+  const unsigned short* depth = reinterpret_cast<const unsigned short*>(pool + d.offset);      // offset is even (ABI check)
+  const long o = (long)blockIdx.y * P * P + idx;
+  source[o] = lut16[depth[px]];
+  if (target != nullptr) {
+    target[o] = lut16[depth[hw + px]];
+    guide[o] = lut8[pool[d.offset + 4 * hw + px]];
+  } else {
+    guide[o] = lut8[pool[d.offset + 2 * hw + px]];
+  }
+}
+
 // one workgroup per (output row oy, sample b): the horizontal pass of the 4s input rows that row reads goes to LDS, then
 // each thread finishes output columns from it
 __global__ __launch_bounds__(256) void bicubic_down_kernel(const float* __restrict__ hr, const float* __restrict__ wtab,
@@ -100,6 +131,14 @@ __global__ __launch_bounds__(256) void quantize_u8_kernel(float* __restrict__ x,
   }
 }
 
+__global__ __launch_bounds__(256) void quantize_levels_kernel(float* __restrict__ x, const float* __restrict__ lut16,
+                                                              float levels, long n) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float v = fminf(fmaxf(x[i], 0.f), 1.f) * levels;       // NaN: fmaxf gives 0
+    x[i] = lut16[(int)rintf(v)];
+  }
+}
+
 int train_crops(const codon_crop_desc* d, const unsigned char* pool, const float* lut, float* target, float* guide,
                 hipStream_t stream) {
   CropArgs a;
@@ -122,6 +161,17 @@ int train_crops_labeled(const codon_crop_desc* d, const unsigned char* pool, con
   return check_launch("train_crops_labeled_kernel");
 }
 
+int train_crops_u16(const codon_crop_desc* d, const unsigned char* pool, const float* lut16, const float* lut8, float* source,
+                    float* guide, float* target, hipStream_t stream) {
+  CropArgs a;
+  for (int b = 0; b < d->n; ++b) a.s[b] = d->s[b];
+  for (int b = d->n; b < CODON_TRAIN_MAX_BATCH; ++b) a.s[b] = codon_crop_sample{};
+  const int P = d->crop;
+  hipLaunchKernelGGL(train_crops_u16_kernel, dim3((unsigned)((P * P + 255) / 256), (unsigned)d->n), dim3(256), 0, stream, a, pool,
+                     lut16, lut8, source, guide, target, P);
+  return check_launch("train_crops_u16_kernel");
+}
+
 int bicubic_downsample(int B, int P, int s, const float* hr, const float* wtab, float* out, hipStream_t stream) {
   const size_t lds = (size_t)4 * P * sizeof(float);     // 4s rows of P/s values
   hipLaunchKernelGGL(bicubic_down_kernel, dim3((unsigned)(P / s), (unsigned)B), dim3(256), lds, stream, hr, wtab, out, P, s);
@@ -132,6 +182,13 @@ int quantize_u8(long n, float* x, const float* lut, hipStream_t stream) {
   const long blocks = (n + 255) / 256;
   hipLaunchKernelGGL(quantize_u8_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, x, lut, n);
   return check_launch("quantize_u8_kernel");
+}
+
+int quantize_levels(long n, float* x, const float* lut16, int depth_max, hipStream_t stream) {
+  const long blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(quantize_levels_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, x, lut16,
+                     (float)depth_max, n);
+  return check_launch("quantize_levels_kernel");
 }
 
 }  // namespace codon

@@ -30,19 +30,23 @@ def list_pairs(input_depth: str, input_color: str):
     return [f for f in sorted(os.listdir(input_color)) if os.path.exists(os.path.join(input_depth, f))]
 
 
-def _load_host(a_depth, a_color, a_label, f, tdt):
+def _load_host(a_depth, a_color, a_label, f, tdt, depth_bits=8, depth_max=65535):
     """Host side of one image: decode, grey, /255 (float64 divide, then float32: test.py:116-123), crop both to the common
-    size, cast to the model's dtype (the rounding `.cuda().half()` does on the device, done here on half the bytes)."""
+    size, cast to the model's dtype (the rounding `.cuda().half()` does on the device, done here on half the bytes).
+    depth_bits=16: depth and label are 16-bit codes (train.read_depth_plane: an 8-bit file or a code above
+    depth_max is refused), the depth input is float32(float64(c) / depth_max) before the same cast, the label is returned as
+    an int16 view of its u16 bits; the guidance stays 8-bit.  depth_bits=8 refuses a 16-bit depth or label file."""
     # numpy only (single-threaded): torch's CPU ops fan a 170 k-element conversion out over every host core, which costs
     # milliseconds per call on a 128-core box; the values are io.to_input()'s -- float64 divide, float32, then the dtype's
     # round-to-nearest-even -- bit for bit
-    px = io.read_gray(os.path.join(a_depth, f))
+    from .train import read_depth_plane
+    px = read_depth_plane(os.path.join(a_depth, f), depth_bits, depth_max)
     py = io.read_gray(os.path.join(a_color, f))
     h, w = min(px.shape[0], py.shape[0]), min(px.shape[1], py.shape[1])
     ndt = {torch.float32: np.float32, torch.float16: np.float16}.get(tdt)
 
-    def conv(p_):
-        v = (np.asarray(p_[:h, :w]) / 255).astype(np.float32)
+    def conv(p_, top=255):
+        v = (np.asarray(p_[:h, :w]) / top).astype(np.float32)
         if ndt is not None:
             return torch.from_numpy(np.ascontiguousarray(v.astype(ndt)))[None, None]
         # bf16 has no numpy type: round to nearest even on the bit pattern (finite, non-negative inputs)
@@ -50,8 +54,11 @@ def _load_host(a_depth, a_color, a_label, f, tdt):
         b16 = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
         return torch.from_numpy(b16.view(np.int16)).view(torch.bfloat16)[None, None]
 
-    lab = torch.from_numpy(io.read_gray(os.path.join(a_label, f)).copy()) if a_label else None
-    return conv(px), conv(py), lab, h, w
+    lab = None
+    if a_label:
+        lab = read_depth_plane(os.path.join(a_label, f), depth_bits, depth_max).copy()
+        lab = torch.from_numpy(lab.view(np.int16) if depth_bits == 16 else lab)
+    return conv(px, depth_max if depth_bits == 16 else 255), conv(py), lab, h, w
 
 
 READERS = int(os.environ.get("CODON_INFER_READERS", "3"))
@@ -69,20 +76,37 @@ def _pinned_copy(t: torch.Tensor) -> torch.Tensor:
     return hp
 
 
-def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None):
-    """The test loop over every image pair.  Returns {"n", "rmse_mean", "ssim_mean", "seconds", "images_per_s"}."""
+def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None,
+             depth_bits=8, depth_max=65535, depth_unit=1.0):
+    """The test loop over every image pair.  Returns {"n", "rmse_mean", "ssim_mean", "seconds", "images_per_s"}.
+    depth_bits=16: 16-bit depth and label files with codes 0 .. depth_max, outputs through metrics.postprocess_u16 into 16-bit
+    PNGs, RMSE (metrics.masked_rmse_u16) in codes times depth_unit, SSIM of label / depth_max against out / depth_max."""
     files = list_pairs(input_depth, input_color) if files is None else files
+    if depth_bits not in (8, 16):
+        raise ValueError(f"run_loop: depth_bits {depth_bits!r} (8 or 16)")
+    deep = depth_bits == 16
+    if deep:
+        from .train import check_depth_max
+        check_depth_max(depth_max)
+        post = lambda o: metrics.postprocess_u16(o, depth_max)                                   # noqa: E731
+        sqerr, write, top = metrics.masked_sqerr_u16_dev, io.write_depth16, float(depth_max)
+        unit = lambda t: metrics.codes_to_float(t) / top                                         # noqa: E731
+    else:
+        post, sqerr, write = metrics.postprocess_u8, metrics.masked_sqerr_dev, io.write_gray
+        unit = lambda t: t.float() / 255                                                         # noqa: E731
+    scale_rm = float(depth_unit) if deep else None
     t0 = time.perf_counter()
     rm_sum = ss_sum = 0.0
     n = 0
 
     def finish(f, out, lab, h, w):
         nonlocal rm_sum, ss_sum, n
-        out_u8 = metrics.postprocess_u8(out[0, 0])
+        out_u8 = post(out[0, 0])
         line = f
         if lab is not None:
-            rm = metrics.masked_rmse(lab, out_u8)
-            ss = metrics.ssim(lab[:h, :w].float() / 255, out_u8.float() / 255)
+            s_, c_ = (int(v) for v in sqerr(lab, out_u8).cpu())
+            rm = math.sqrt(s_ / c_) if scale_rm is None else math.sqrt(s_ / c_) * scale_rm
+            ss = metrics.ssim(unit(lab[:h, :w]), unit(out_u8))
             rm_sum += rm; ss_sum += ss
             line += f" {rm} {ss}"
         n += 1
@@ -90,12 +114,12 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
 
     if not pipelined:
         for f in files:
-            x, y, lab, h, w = _load_host(input_depth, input_color, label, f, tdt)
+            x, y, lab, h, w = _load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max)
             with torch.no_grad():
                 out = model(x.to(dev), y.to(dev))
             out_u8, line = finish(f, out, lab.to(dev) if lab is not None else None, h, w)
             if out_dir:
-                io.write_gray(os.path.join(out_dir, f), out_u8.cpu().numpy())
+                write(os.path.join(out_dir, f), out_u8.cpu().numpy())
             emit(line)
     else:
         main_s = torch.cuda.current_stream(dev)
@@ -114,7 +138,7 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                 for f in files[k::READERS]:
                     if stop.is_set():
                         break
-                    x, y, lab, h, w = _load_host(input_depth, input_color, label, f, tdt)
+                    x, y, lab, h, w = _load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max)
                     host = [_pinned_copy(t) for t in ((x, y) if lab is None else (x, y, lab))]
                     with torch.cuda.stream(up_s):
                         devs = [t.to(dev, non_blocking=True) for t in host]
@@ -135,7 +159,7 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                     f, host_u8, ev = item
                     ev.synchronize()                               # the download of this image has landed
                     if out_dir:
-                        io.write_gray(os.path.join(out_dir, f), host_u8.numpy())
+                        write(os.path.join(out_dir, f), host_u8.numpy())
             except BaseException as e:      # noqa: BLE001
                 errs.append(e)
 
@@ -148,7 +172,7 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
             if h_acc is not None:
                 ev.synchronize()
                 s_, c_ = (int(v) for v in h_acc)
-                rm, ss = math.sqrt(s_ / c_), float(h_ss.item())
+                rm, ss = math.sqrt(s_ / c_) if scale_rm is None else math.sqrt(s_ / c_) * scale_rm, float(h_ss.item())
                 rm_sum += rm; ss_sum += ss
                 line += f" {rm} {ss}"
             n += 1
@@ -170,17 +194,17 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                     t.record_stream(main_s)                        # allocated on the upload stream, consumed on this one
                 with torch.no_grad():
                     out = model(devs[0], devs[1])
-                out_u8 = metrics.postprocess_u8(out[0, 0])
+                out_u8 = post(out[0, 0])
                 h_acc = h_ss = None
                 if len(devs) > 2:                                  # metrics stay on the device; read back one image later
                     lab = devs[2]
-                    acc = metrics.masked_sqerr_dev(lab, out_u8)
-                    ssv = metrics.ssim_dev(lab[:h, :w].float() / 255, out_u8.float() / 255)
+                    acc = sqerr(lab, out_u8)
+                    ssv = metrics.ssim_dev(unit(lab[:h, :w]), unit(out_u8))
                     h_acc = torch.empty(2, dtype=torch.int64, pin_memory=True)
                     h_ss = torch.empty(1, dtype=torch.float64, pin_memory=True)
                     h_acc.copy_(acc, non_blocking=True)
                     h_ss.copy_(ssv, non_blocking=True)
-                host_u8 = torch.empty(out_u8.shape, dtype=torch.uint8, pin_memory=True)
+                host_u8 = torch.empty(out_u8.shape, dtype=out_u8.dtype, pin_memory=True)
                 host_u8.copy_(out_u8, non_blocking=True)
                 dv = torch.cuda.Event()
                 dv.record(main_s)
@@ -217,13 +241,25 @@ def main(argv=None):
     ap.add_argument("--label", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--weights", default=None, help="X4.pth-style checkpoint; random reference init if absent")
-    ap.add_argument("--dtype", default="f16", choices=["f32", "bf16", "f16"], help="the reference script runs .half()")
+    ap.add_argument("--dtype", default="f16", choices=["f32", "bf16", "f16"],
+                    help="the reference script runs .half(); fp16 and bf16 carry 11 and 8 significant bits, so f32 is the "
+                         "sensible choice for 16-bit data (--depth-bits 16)")
     ap.add_argument("--ema", action="store_true", help="load the EMA weights of a codon_amd.train --ema checkpoint")
     ap.add_argument("--serial", action="store_true", help="the reference's own serial loop (decode, upload, forward, download, "
                                                           "encode one after the other per image) instead of the pipeline")
+    ap.add_argument("--depth-bits", type=int, default=8, choices=[8, 16],
+                    help="16: depth maps and labels are 16-bit PNGs of codes 0 .. --depth-max (0 a hole), and so are the outputs")
+    ap.add_argument("--depth-max", type=int, default=None, help="with --depth-bits 16: the code of 1.0 (default 65535)")
+    ap.add_argument("--depth-unit", type=float, default=1.0,
+                    help="with --depth-bits 16: the printed RMSE is in codes times this (0.1: centimetres from millimetre codes)")
     a = ap.parse_args(argv)
     if a.ema and not a.weights:
         ap.error("--ema needs --weights")
+    if a.depth_bits != 16 and (a.depth_max is not None or a.depth_unit != 1.0):
+        ap.error("--depth-max and --depth-unit belong to --depth-bits 16")
+    a.depth_max = 65535 if a.depth_max is None else a.depth_max
+    if not 1 <= a.depth_max <= 65535:
+        ap.error(f"--depth-max {a.depth_max} must lie in [1, 65535]")
     if not torch.cuda.is_available():
         raise SystemExit("No GPU found, codon_amd has no CPU path")          # test.py:37-38
     dev = torch.device("cuda:0")
@@ -236,7 +272,8 @@ def main(argv=None):
     model = model.to(dev).to(tdt).eval()
     if a.out:
         os.makedirs(a.out, exist_ok=True)
-    r = run_loop(model, dev, tdt, a.input_depth, a.input_color, a.label, a.out, pipelined=not a.serial)
+    r = run_loop(model, dev, tdt, a.input_depth, a.input_color, a.label, a.out, pipelined=not a.serial,
+                 depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit)
     print(r["n"])
     if a.label and r["n"]:
         print(r["rmse_mean"], r["ssim_mean"])

@@ -24,6 +24,30 @@ def write_gray(path: str, img_u8: np.ndarray):
     Image.fromarray(np.asarray(img_u8, dtype=np.uint8), mode="L").save(path)
 
 
+DEPTH16_MODES = ("I;16", "I;16B", "I;16L", "I")
+
+
+def read_depth(path: str) -> np.ndarray:
+    """A depth map or label with its own bit depth: uint16 codes for PIL's 16-bit greyscale modes (I;16, I;16B, I;16L) and for
+    mode I (32-bit integers, refused if a value lies outside [0, 65535]); uint8 exactly as read_gray for everything else.
+    convert("L") CLIPS a 16-bit image at 255, which is why read_gray must not be used on one."""
+    from PIL import Image
+    im = Image.open(path)
+    if im.mode not in DEPTH16_MODES:
+        return np.asarray(im.convert("L"), dtype=np.uint8)
+    a = np.asarray(im)
+    if im.mode == "I" and a.size and (int(a.min()) < 0 or int(a.max()) > 65535):
+        raise ValueError(f"{path}: mode I image with values outside [0, 65535] (min {int(a.min())}, max {int(a.max())})")
+    return np.ascontiguousarray(a.astype(np.uint16))
+
+
+def write_depth16(path: str, arr_u16: np.ndarray):
+    """A 16-bit greyscale PNG of uint16 codes."""
+    from PIL import Image
+    a = np.ascontiguousarray(np.asarray(arr_u16, dtype=np.uint16))
+    Image.frombytes("I;16", (a.shape[1], a.shape[0]), a.astype("<u2").tobytes()).save(path)
+
+
 def to_input(pic_u8: np.ndarray) -> torch.Tensor:
     """torch.from_numpy(pic / 255).float().unsqueeze(0).unsqueeze(0)   (float64 divide, then float32)."""
     return torch.from_numpy(np.asarray(pic_u8) / 255).float().unsqueeze(0).unsqueeze(0)

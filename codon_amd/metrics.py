@@ -1,6 +1,7 @@
 """Either side of the network in the reference's script, on device:
   postprocess_u8  clip -> *255 -> truncating uint8          /root/reference/CODON_X4/test.py:127-132
   masked_rmse     RMSE over label != 0, exact integer sums   /root/reference/CODON_X4/test.py:148-164
+  postprocess_u16, masked_rmse_u16   their 16-bit counterparts: definitions of this project, no reference
   ssim            ssim_exact(img1, img2)                     /root/reference/CODON_X4/ssim_2.py:36-52
   L1SSIMLoss      w_l1 * mean|p - t| + w_ssim * (1 - SSIM(p, t)) with a HIP backward (the reference ships no
                   loss -- SURVEY D8 -- so the combination is this repo's; the SSIM value is pinned).
@@ -23,7 +24,8 @@ def _p(t):
 def postprocess_u8(x: torch.Tensor) -> torch.Tensor:
     """np.clip(out, 0, 1); (out * 255).astype(np.uint8) with the product formed in the array's dtype, as numpy
     does: an fp16 network output (the reference script's default) is rounded to fp16 before the truncating cast
-    (test.py:125-132).  bf16 has no numpy counterpart: it is upcast to fp32."""
+    (test.py:125-132).  bf16 has no numpy counterpart: it is upcast to fp32.  This rule (truncation) is the reference's and is
+    pinned to it; the 16-bit rule, postprocess_u16, rounds to nearest and is pinned to nothing."""
     lib = L.load()
     if x.dtype not in (torch.float32, torch.float16):
         x = x.float()
@@ -54,6 +56,56 @@ def masked_rmse(label_u8: torch.Tensor, out_u8: torch.Tensor) -> float:
     """test.py::EvaluationResults: label is cropped to the output's size (:151); pixels with label == 0 are
     excluded from both the error and the count."""
     s, c = (int(v) for v in masked_sqerr_dev(label_u8, out_u8).cpu())
+    return math.sqrt(s / c)
+
+
+def _as_u16(t: torch.Tensor) -> torch.Tensor:
+    """u16 codes are held as torch.uint16, or as an int16 view of the same bits where an op lacks uint16."""
+    if t.dtype == torch.int16:
+        return t.view(torch.uint16)
+    assert t.dtype == torch.uint16, t.dtype
+    return t
+
+
+def codes_to_float(t_u16: torch.Tensor) -> torch.Tensor:
+    """fp32 of u16 codes (exact), through int32: not every device op takes uint16."""
+    return (_as_u16(t_u16).view(torch.int16).to(torch.int32) & 0xFFFF).float()
+
+
+def postprocess_u16(x: torch.Tensor, depth_max: int = 65535) -> torch.Tensor:
+    """code = rint(clamp(out, 0, 1) * float32(depth_max)) as torch.uint16: round half to even, the product formed in fp32
+    (fp16 and bf16 outputs are upcast first, in the kernel), NaN -> 0.  UNPINNED by nature: the reference writes 8-bit images
+    only (postprocess_u8 is its rule), so this is the project's definition, restated in tests/train_data16_ref.py."""
+    lib = L.load()
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        x = x.float()
+    x = x.contiguous()
+    dev = ops._dev(x)
+    out = torch.empty(x.shape, dtype=torch.uint16, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.codon_postprocess_u16_dt(x.numel(), _p(x), ops._dt(x), int(depth_max), _p(out), ops._stream(dev)),
+                "postprocess_u16")
+    return out
+
+
+def masked_sqerr_u16_dev(label_u16: torch.Tensor, out_u16: torch.Tensor) -> torch.Tensor:
+    """masked_sqerr_dev over u16 codes: a DEVICE tensor int64[2] = { sum of squared errors, count over label != 0 }."""
+    lib = L.load()
+    label_u16, out_u16 = _as_u16(label_u16), _as_u16(out_u16)
+    assert out_u16.dim() == 2
+    label_u16 = label_u16.view(torch.int16)[:out_u16.shape[0], :out_u16.shape[1]].contiguous()
+    out_u16 = out_u16.contiguous()
+    dev = ops._dev(label_u16, out_u16)
+    acc = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.codon_masked_sqerr_u16(out_u16.numel(), _p(label_u16), _p(out_u16), _p(acc), ops._stream(dev)),
+                "masked_sqerr_u16")
+    return acc
+
+
+def masked_rmse_u16(label_u16: torch.Tensor, out_u16: torch.Tensor) -> float:
+    """masked_rmse in 16-bit codes: label cropped to the output's size, label == 0 excluded."""
+    s, c = (int(v) for v in masked_sqerr_u16_dev(label_u16, out_u16).cpu())
     return math.sqrt(s / c)
 
 

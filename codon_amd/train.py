@@ -5,7 +5,9 @@ as 8-bit PNGs: the reference's CODON_X4/test.py:70-79,116-123) by a script it do
 built ON THE DEVICE from HR depth maps and guidance images uploaded once (codon_amd/csrc/train_data.hip):
     random crop + D4 op (crop, u8 -> fp32)  ->  antialiased bicubic x1/s  ->  bicubic xs (upsample.hip)  ->  8-bit quantise
 The degradation is a definition of this project, NOT pinned to the reference (its script is not shipped); it is restated in
-numpy in tests/train_data_ref.py and the two agree bit for bit.
+numpy in tests/train_data_ref.py and the two agree bit for bit.  --depth-bits 16: depth maps and labels are
+16-bit PNGs of codes 0 .. --depth-max (0 a hole, value = code / depth-max, guidance stays 8-bit); the crop reads u16 planes
+through a 65 536-entry table and the last step quantises onto the data set's own code grid (tests/train_data16_ref.py).
 
 One step: GradSync.zero_grad -> synthesize -> forward -> L1SSIMLoss(out.float(), t) (--mask-holes: MaskedL1SSIMLoss, which
 leaves the target's holes -- code 0 -- out of the loss; --train-label: targets from a third directory) -> GradSync.backward ->
@@ -39,6 +41,9 @@ RESUME_KEYS = ("scale", "crop", "batch", "dtype", "clip_norm", "skip_nonfinite",
 # what a key compares as when a checkpoint's args do not carry it (one written before the option existed)
 RESUME_DEFAULTS = {"clip_norm": None, "skip_nonfinite": False, "ema": None, "lr_schedule": "constant", "warmup_steps": 0,
                    "lr_min": 0.0, "lr_steps": None, "mask_holes": False, "min_valid": 0.0, "train_label": False}
+# compared on --resume like RESUME_KEYS, but written by a 16-bit run ONLY: an 8-bit checkpoint keeps exactly the
+# args it always had, and one without these keys compares as 8-bit
+DEPTH_DEFAULTS = {"depth_bits": 8, "depth_max": 65535}
 MAX_REDRAWS = 64                                    # draw(min_valid=): per sample, before it gives up
 LR_SCHEDULES = ("constant", "cosine")
 
@@ -48,6 +53,37 @@ LR_SCHEDULES = ("constant", "cosine")
 def u8_lut() -> np.ndarray:
     """256 fp32 values: io.to_input's conversion of every code (float64 divide by 255, then float32)."""
     return (np.arange(256, dtype=np.float64) / 255).astype(np.float32)
+
+
+def lut16(depth_max: int = 65535) -> np.ndarray:
+    """65 536 fp32 values: code c of a 16-bit depth map as float32(float64(c) / depth_max) -- u8_lut's conversion on the data
+    set's own scale (lut16(65535)[257 * k] == u8_lut()[k] bit for bit).  Codes above depth_max are refused at load time; their
+    entries exist only so that no u16 indexes out of the table."""
+    check_depth_max(depth_max)
+    return (np.arange(65536, dtype=np.float64) / depth_max).astype(np.float32)
+
+
+def check_depth_max(depth_max):
+    if not isinstance(depth_max, (int, np.integer)) or not 1 <= depth_max <= 65535:
+        raise ValueError(f"depth_max {depth_max!r} must be an integer in [1, 65535]")
+
+
+def read_depth_plane(path: str, depth_bits: int, depth_max: int = 65535) -> np.ndarray:
+    """One depth map or label under the data set's bit depth: 8 -> io.read_gray's uint8, and a 16-bit file is
+    REFUSED (convert("L") would clip it at 255 without a word); 16 -> uint16 codes, an 8-bit file refused (no mixing) and so
+    is a code above depth_max.  Every ValueError names the file."""
+    a = io.read_depth(path)
+    if depth_bits == 8:
+        if a.dtype != np.uint8:
+            raise ValueError(f"{path}: a 16-bit image (codes up to {int(a.max())}) in an 8-bit data set; it would be clipped at "
+                             "255 -- pass --depth-bits 16 (and --depth-max)")
+        return a
+    if a.dtype != np.uint16:
+        raise ValueError(f"{path}: an 8-bit image in a 16-bit data set (--depth-bits 16): depth maps and labels must all be "
+                         "16-bit")
+    if a.size and int(a.max()) > depth_max:
+        raise ValueError(f"{path}: code {int(a.max())} lies above depth_max {depth_max}")
+    return a
 
 
 @functools.lru_cache(maxsize=None)
@@ -85,22 +121,34 @@ class TrainSet:
     cropped to their common size (as infer._load_host does), in ONE flat uint8 pool on `device`: pair i's depth map at
     offsets[i], its guidance right behind it.  Uploaded once; a step reads nothing from the host.  `crop`: refuse images
     smaller than it.  `label_dir`: a third plane per pair, the label (the target, which may carry holes coded 0 that the depth
-    map -- the degradation's source -- has filled in), behind the guidance; every pair needs a namesake there."""
+    map -- the degradation's source -- has filled in), behind the guidance; every pair needs a namesake there.
+    depth_bits=16 (DESIGN 12.3): depth maps and labels are 16-bit PNGs of codes 0 .. depth_max (0 a hole, v = c / depth_max);
+    the pool stays a BYTE pool and pair i's record at the even byte offset offsets[i] is the depth plane (H*W little-endian
+    u16), the label plane if there is one (H*W u16), then the u8 guidance; a record of odd length is padded by one byte.  With
+    depth_bits=8 a 16-bit depth or label file is refused (it used to be clipped at 255), with 16 an 8-bit one."""
 
-    def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None, label_dir: str = None):
+    def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None, label_dir: str = None, depth_bits: int = 8,
+                 depth_max: int = 65535):
         from .infer import list_pairs
+        if depth_bits not in (8, 16):
+            raise ValueError(f"TrainSet: depth_bits {depth_bits!r} (8 or 16)")
+        check_depth_max(depth_max)
+        self.depth_bits, self.depth_max = depth_bits, int(depth_max)
         self.files = list_pairs(depth_dir, color_dir)
         if not self.files:
             raise ValueError(f"TrainSet: no file of {color_dir} has a namesake in {depth_dir}")
         self.has_label = label_dir is not None
         self.planes = 3 if self.has_label else 2
+        if depth_bits == 16:
+            self._init16(depth_dir, color_dir, device, crop, label_dir)
+            return
         chunks, offsets, sizes, off = [], [], [], 0
         for f in self.files:
-            planes = [io.read_gray(os.path.join(depth_dir, f)), io.read_gray(os.path.join(color_dir, f))]
+            planes = [read_depth_plane(os.path.join(depth_dir, f), 8), io.read_gray(os.path.join(color_dir, f))]
             if self.has_label:
                 if not os.path.isfile(os.path.join(label_dir, f)):
                     raise ValueError(f"TrainSet: {f} has no namesake in {label_dir}")
-                planes.append(io.read_gray(os.path.join(label_dir, f)))
+                planes.append(read_depth_plane(os.path.join(label_dir, f), 8))
             h, w = min(p.shape[0] for p in planes), min(p.shape[1] for p in planes)
             if crop is not None and (h < crop or w < crop):
                 raise ValueError(f"TrainSet: {f} is {h}x{w}, smaller than the {crop}x{crop} crop")
@@ -108,6 +156,31 @@ class TrainSet:
             offsets.append(off)
             sizes.append((h, w))
             off += self.planes * h * w
+        self.offsets = np.asarray(offsets, dtype=np.int64)
+        self.sizes = np.asarray(sizes, dtype=np.int64)
+        self.pool = torch.from_numpy(np.concatenate(chunks)).to(device)
+        self._integrals = None
+
+    def _init16(self, depth_dir, color_dir, device, crop, label_dir):
+        chunks, offsets, sizes, off = [], [], [], 0
+        for f in self.files:
+            deep = [read_depth_plane(os.path.join(depth_dir, f), 16, self.depth_max)]
+            if self.has_label:
+                if not os.path.isfile(os.path.join(label_dir, f)):
+                    raise ValueError(f"TrainSet: {f} has no namesake in {label_dir}")
+                deep.append(read_depth_plane(os.path.join(label_dir, f), 16, self.depth_max))
+            guide = io.read_gray(os.path.join(color_dir, f))
+            h, w = min(p.shape[0] for p in deep + [guide]), min(p.shape[1] for p in deep + [guide])
+            if crop is not None and (h < crop or w < crop):
+                raise ValueError(f"TrainSet: {f} is {h}x{w}, smaller than the {crop}x{crop} crop")
+            chunks += [np.ascontiguousarray(p[:h, :w]).astype("<u2").reshape(-1).view(np.uint8) for p in deep]
+            chunks.append(np.ascontiguousarray(guide[:h, :w]).reshape(-1))
+            offsets.append(off)
+            sizes.append((h, w))
+            off += (2 * len(deep) + 1) * h * w
+            if off % 2:                                 # the next record's u16 planes start at an even byte
+                chunks.append(np.zeros(1, dtype=np.uint8))
+                off += 1
         self.offsets = np.asarray(offsets, dtype=np.int64)
         self.sizes = np.asarray(sizes, dtype=np.int64)
         self.pool = torch.from_numpy(np.concatenate(chunks)).to(device)
@@ -125,7 +198,11 @@ class TrainSet:
             plane = 2 if self.has_label else 0
             self._integrals = {}
             for off, (h, w) in zip(self.offsets.tolist(), self.sizes.tolist()):
-                v = pool[off + plane * h * w:off + (plane + 1) * h * w].reshape(h, w) != 0
+                if self.depth_bits == 16:               # the label follows the depth plane; both are u16
+                    lo = off + (2 * h * w if self.has_label else 0)
+                    v = pool[lo:lo + 2 * h * w].view("<u2").reshape(h, w) != 0
+                else:
+                    v = pool[off + plane * h * w:off + (plane + 1) * h * w].reshape(h, w) != 0
                 ii = np.zeros((h + 1, w + 1), dtype=np.int32)
                 ii[1:, 1:] = v.cumsum(0, dtype=np.int32).cumsum(1, dtype=np.int32)
                 self._integrals[off] = ii
@@ -183,7 +260,9 @@ def draw(rng: np.random.Generator, trainset: TrainSet, batch: int, crop: int, ra
 def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int):
     """(x, y, t), each (B,1,crop,crop) fp32 on the pool's device: the network's depth input (crop -> bicubic down by `scale`
     -> bicubic up -> 8-bit), the guidance and the HR target.  Four launches on the caller's stream, no host synchronisation.
-    A TrainSet with labels: x is degraded from the depth plane, t comes from the label plane (codon_train_crops_labeled)."""
+    A TrainSet with labels: x is degraded from the depth plane, t comes from the label plane (codon_train_crops_labeled).
+    A 16-bit TrainSet: codon_train_crops_u16 (labeled or not) and codon_quantize_levels onto the set's own code grid, the
+    down and up kernels between them unchanged -- four launches as well."""
     lib = L.load()
     B = len(descs)
     if not 1 <= B <= L.TRAIN_MAX_BATCH:
@@ -206,9 +285,16 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int):
     lr = torch.empty((B, 1, p, p), dtype=torch.float32, device=dev)
     x = torch.empty_like(t)
     P_ = C.c_void_p
+    deep = getattr(trainset, "depth_bits", 8) == 16
+    if deep:
+        lut_deep = _on_device(("lut16", trainset.depth_max), lambda: lut16(trainset.depth_max), dev)
     with ops._on(dev):
         st = ops._stream(dev)
-        if trainset.has_label:
+        if deep:
+            L.check(lib.codon_train_crops_u16(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(),
+                                              P_(lut_deep.data_ptr()), P_(lut.data_ptr()), P_(src.data_ptr()), P_(y.data_ptr()),
+                                              P_(t.data_ptr()) if trainset.has_label else None, st), "train_crops_u16")
+        elif trainset.has_label:
             L.check(lib.codon_train_crops_labeled(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(),
                                                   P_(lut.data_ptr()), P_(src.data_ptr()), P_(y.data_ptr()), P_(t.data_ptr()), st),
                     "train_crops_labeled")
@@ -219,7 +305,11 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int):
                 "bicubic_downsample")
         L.check(lib.codon_bicubic_upsample(B, p, p, scale, P_(lr.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()), st),
                 "bicubic_upsample")
-        L.check(lib.codon_quantize_u8(x.numel(), P_(x.data_ptr()), P_(lut.data_ptr()), st), "quantize_u8")
+        if deep:
+            L.check(lib.codon_quantize_levels(x.numel(), P_(x.data_ptr()), P_(lut_deep.data_ptr()), trainset.depth_max, st),
+                    "quantize_levels")
+        else:
+            L.check(lib.codon_quantize_u8(x.numel(), P_(x.data_ptr()), P_(lut.data_ptr()), st), "quantize_u8")
     return x, y, t
 
 
@@ -266,12 +356,14 @@ def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, 
 
 def load_resume(path: str, args: dict) -> dict:
     """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype, or with
-    other options that change the trajectory (RESUME_KEYS; a key the checkpoint's args lack compares as its default)."""
+    other options that change the trajectory (RESUME_KEYS and DEPTH_DEFAULTS' keys; a key the checkpoint's args lack compares
+    as its default)."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(ck, dict) or not all(k in ck for k in ("epoch", "model", "optimizer", "rng", "args")):
         raise ValueError(f"--resume {path}: not a codon_amd.train checkpoint (use --weights to start from other weights)")
-    was, now = ({k: a.get(k, RESUME_DEFAULTS.get(k)) for k in RESUME_KEYS} for a in (ck["args"], args))
-    bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in RESUME_KEYS if was[k] != now[k]]
+    absent, keys = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS}, RESUME_KEYS + tuple(DEPTH_DEFAULTS)
+    was, now = ({k: a.get(k, absent.get(k)) for k in keys} for a in (ck["args"], args))
+    bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in keys if was[k] != now[k]]
     if bad:
         raise ValueError(f"--resume {path}: the checkpoint was trained with other arguments: {', '.join(bad)}")
     return ck
@@ -327,6 +419,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
                 skip_nonfinite=bool(skip_nonfinite), ema=ema_decay, lr_schedule=lr_schedule, warmup_steps=warmup, lr_min=lr_min,
                 lr_steps=lr_steps if lr_schedule == "cosine" else None)
     args.update(mask_holes=bool(mask_holes), min_valid=float(min_valid), train_label=bool(trainset.has_label))
+    if getattr(trainset, "depth_bits", 8) == 16:    # only then: an 8-bit checkpoint keeps the keys it always had
+        args.update(depth_bits=16, depth_max=int(trainset.depth_max))
     stream = torch.cuda.current_stream(dev)
     losses, val_log, ev = [], [], []
     t_log, s_log = time.perf_counter(), start_step
@@ -401,12 +495,14 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
 
 def validate(model, dev, val: dict, emit=print) -> dict:
     """infer.run_loop over the validation set in eval mode at the training compute dtype; prints the mean masked RMSE and
-    SSIM (the numbers the reference's test.py prints), then returns the model to train()."""
+    SSIM (the numbers the reference's test.py prints), then returns the model to train().  val["depth_bits"] == 16: the set
+    is read as 16-bit with val["depth_max"], and the RMSE is in codes."""
     from .infer import run_loop
     model.eval()
     try:
         with torch.no_grad():
-            r = run_loop(model, dev, torch.float32, val["depth"], val["color"], val.get("label"), emit=lambda s: None)
+            deep = {"depth_bits": 16, "depth_max": val.get("depth_max", 65535)} if val.get("depth_bits", 8) == 16 else {}
+            r = run_loop(model, dev, torch.float32, val["depth"], val["color"], val.get("label"), emit=lambda s: None, **deep)
     finally:
         model.train()
     emit(f"val {r['n']} images rmse {r['rmse_mean']} ssim {r['ssim_mean']}")
@@ -418,7 +514,7 @@ def validate(model, dev, val: dict, emit=print) -> dict:
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scale", type=int, required=True, choices=[4, 8, 16])
-    ap.add_argument("--train-depth", required=True, help="HR depth maps (PNG, 8-bit)")
+    ap.add_argument("--train-depth", required=True, help="HR depth maps (PNG, 8-bit; 16-bit with --depth-bits 16)")
     ap.add_argument("--train-color", required=True, help="guidance images, paired with the depth maps by file name")
     ap.add_argument("--train-label", default=None,
                     help="targets, paired by file name: the depth maps are then only degraded into inputs (hole-filled depth "
@@ -427,6 +523,10 @@ def parse_args(argv=None):
                     help="pixels whose target is 0 carry no loss and no gradient (the rule of the printed RMSE)")
     ap.add_argument("--min-valid", type=float, default=0.0,
                     help="with --mask-holes: redraw a crop with less than this fraction of valid pixels")
+    ap.add_argument("--depth-bits", type=int, default=8, choices=[8, 16],
+                    help="16: depth maps and labels (training and validation) are 16-bit PNGs of codes 0 .. --depth-max, 0 a "
+                         "hole, value = code / depth-max; guidance stays 8-bit")
+    ap.add_argument("--depth-max", type=int, default=None, help="with --depth-bits 16: the code of 1.0 (default 65535)")
     ap.add_argument("--crop", type=int, default=128)
     ap.add_argument("--batch", type=int, default=16, help="global batch (split over the ranks under torchrun)")
     ap.add_argument("--steps", type=int, default=1000, help="total steps (a resumed run continues up to this step)")
@@ -469,6 +569,11 @@ def parse_args(argv=None):
         ap.error(f"--min-valid {a.min_valid} must lie in [0, 1]")
     if a.min_valid > 0 and not a.mask_holes:
         ap.error("--min-valid needs --mask-holes")
+    if a.depth_max is not None and a.depth_bits != 16:
+        ap.error("--depth-max belongs to --depth-bits 16")
+    a.depth_max = 65535 if a.depth_max is None else a.depth_max
+    if not 1 <= a.depth_max <= 65535:
+        ap.error(f"--depth-max {a.depth_max} must lie in [1, 65535]")
     if a.clip_norm is not None and not a.clip_norm > 0:
         ap.error(f"--clip-norm {a.clip_norm} must be positive")
     if a.ema is not None and not 0 <= a.ema < 1:
@@ -489,7 +594,8 @@ def parse_args(argv=None):
 
 
 def run_args(a) -> dict:
-    return {"scale": a.scale, "crop": a.crop, "batch": a.batch, "dtype": a.dtype, "lr": a.lr, "seed": a.seed,
+    deep = {"depth_bits": 16, "depth_max": a.depth_max} if a.depth_bits == 16 else {}
+    return {**deep, "scale": a.scale, "crop": a.crop, "batch": a.batch, "dtype": a.dtype, "lr": a.lr, "seed": a.seed,
             "clip_norm": a.clip_norm, "skip_nonfinite": a.skip_nonfinite, "ema": a.ema, "lr_schedule": a.lr_schedule,
             "warmup_steps": a.warmup_steps, "lr_min": a.lr_min, "lr_steps": a.lr_steps, "mask_holes": bool(a.mask_holes),
             "min_valid": float(a.min_valid), "train_label": a.train_label is not None}
@@ -513,7 +619,8 @@ def main(argv=None, emit=print) -> dict:
         raise SystemExit(f"--batch {a.batch} does not split evenly over {world} ranks")
     if a.batch // world > L.TRAIN_MAX_BATCH:
         raise SystemExit(f"--batch {a.batch}: at most {L.TRAIN_MAX_BATCH} images per rank")
-    ts = TrainSet(a.train_depth, a.train_color, dev, crop=a.crop, label_dir=a.train_label)
+    ts = TrainSet(a.train_depth, a.train_color, dev, crop=a.crop, label_dir=a.train_label, depth_bits=a.depth_bits,
+                  depth_max=a.depth_max)
     torch.manual_seed(a.seed)
     model = (CODONNet16 if a.scale == 16 else CODONNet)()
     rng = np.random.default_rng(a.seed)
@@ -532,8 +639,8 @@ def main(argv=None, emit=print) -> dict:
     if rank == 0:
         emit(f"{len(ts)} training pairs, x{a.scale}, crop {a.crop}, batch {a.batch} over {world} rank(s), {a.dtype}, "
              f"steps {start + 1}..{a.steps}")
-    val = ({"depth": a.val_depth, "color": a.val_color, "label": a.val_label, "every": a.val_every}
-           if a.val_depth else None)
+    val = ({"depth": a.val_depth, "color": a.val_color, "label": a.val_label, "every": a.val_every,
+            "depth_bits": a.depth_bits, "depth_max": a.depth_max} if a.val_depth else None)
     ckpt = {"path": a.save, "every": a.save_every} if a.save else None
     res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,
               log_every=a.log_every, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,

@@ -485,6 +485,16 @@ int codon_postprocess_u8(int64_t n, const float* x, uint8_t* out, codon_stream_t
 int codon_postprocess_u8_dt(int64_t n, const void* x, int32_t dtype, uint8_t* out, codon_stream_t stream);
 int codon_masked_sqerr(int64_t n, const uint8_t* label, const uint8_t* out, uint64_t* acc,
                        codon_stream_t stream);
+/* 16-bit depth codes.  No reference counterpart -- the reference's outputs are 8-bit -- so these are
+ * DEFINITIONS, restated in numpy in tests/train_data16_ref.py.
+ * postprocess_u16_dt : out[i] = (uint16)rint(clamp(x[i], 0, 1) * (float)depth_max), round half to even; x of dtype CODON_F32 /
+ *                      CODON_F16 / CODON_BF16 is upcast to fp32 (exactly) and the product is formed in fp32; NaN -> 0 (fmaxf);
+ *                      depth_max in [1, 65535].
+ * masked_sqerr_u16   : codon_masked_sqerr over u16 codes: acc[0] = sum_{label!=0} (label-out)^2, acc[1] = #{label!=0}, exact
+ *                      64-bit integers.  Bound: one term is at most 65535^2 < 2^32, and n <= 2^26 pixels is required, so
+ *                      acc[0] <= 65535^2 * 2^26 < 2^58 fits a uint64 with room to spare. */
+int codon_postprocess_u16_dt(int64_t n, const void* x, int32_t dtype, int32_t depth_max, uint16_t* out, codon_stream_t stream);
+int codon_masked_sqerr_u16(int64_t n, const uint16_t* label, const uint16_t* out, uint64_t* acc, codon_stream_t stream);
 int32_t codon_ssim_tiles(int32_t batch, int32_t height, int32_t width);
 int codon_ssim_fwd(int32_t batch, int32_t height, int32_t width, const float* a, const float* b,
                    float* partial, float* dmaps, double* value, codon_stream_t stream);
@@ -644,6 +654,20 @@ int codon_bicubic_downsample(int32_t batch, int32_t size, int32_t scale, const f
 /* codon_quantize_u8: in place, x[i] = lut[rint(clamp(x[i], 0, 1) * 255f)] (round half to even): the 8-bit PNG the network's
  * depth input is read from at test time. */
 int codon_quantize_u8(int64_t n, float* x, const float* lut, codon_stream_t stream);
+/* codon_train_crops_u16: codon_train_crops / _labeled for 16-bit depth, same window, same D4 op, same
+ * descriptor.  A record in the byte pool is the depth plane (height * width little-endian u16) at s[b].offset, which must be
+ * EVEN, then -- when target != NULL -- the label plane (height * width u16), then the guidance plane (height * width u8):
+ * 3 or 5 bytes per pixel, every record inside the pool, the pool itself 2-byte aligned.  Depth and label codes c go through
+ * lut16 (65 536 fp32 entries, device memory: lut16[c] = float32(float64(c) / depth_max)), guidance codes through lut8 (the
+ * 256-entry table of codon_train_crops).  source / guide / target: (n,1,P,P) fp32.  target == NULL: two-plane records, and
+ * `source` is the HR target too, as in codon_train_crops.  Codes above depth_max are the caller's to refuse (the table has an
+ * entry for every u16, so nothing is read out of bounds). */
+int codon_train_crops_u16(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, const float* lut16,
+                          const float* lut8, float* source, float* guide, float* target, codon_stream_t stream);
+/* codon_quantize_levels: in place, x[i] = lut16[(int)rintf(clamp(x[i], 0, 1) * (float)depth_max)] (round half to even; NaN
+ * -> lut16[0]): codon_quantize_u8's counterpart at the same point of the degradation, onto the data set's own code grid.
+ * depth_max in [1, 65535]. */
+int codon_quantize_levels(int64_t n, float* x, const float* lut16, int32_t depth_max, codon_stream_t stream);
 
 #ifdef __cplusplus
 }
