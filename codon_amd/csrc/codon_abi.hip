@@ -129,6 +129,9 @@ int bicubic_downsample(int, int, int, const float*, const float*, float*, hipStr
 int quantize_u8(long, float*, const float*, hipStream_t);
 int train_crops_u16(const codon_crop_desc*, const unsigned char*, const float*, const float*, float*, float*, float*, hipStream_t);
 int quantize_levels(long, float*, const float*, int, hipStream_t);
+int bicubic_upsample_masked(int, int, int, int, const float*, const float*, float*, unsigned char*, hipStream_t);
+int bicubic_downsample_masked(int, int, int, const float*, const float*, const float*, int, float*, hipStream_t);
+int lr_codes_to_input(int, int, int, int, const void*, int, const float*, int, const float*, void*, int, hipStream_t);
 size_t weight_checksum_workspace_bytes();
 int weight_checksum(const codon_wsum_desc*, void*, unsigned long long*, int, int*, int*, int, hipStream_t);
 
@@ -950,6 +953,46 @@ int codon_quantize_levels(int64_t n, float* x, const float* lut16, int32_t depth
   CODON_REQUIRE(x && lut16 && n >= 1, CODON_ERR_BAD_ARG, "quantize_levels: null pointer or empty");
   CODON_REQUIRE(depth_max >= 1 && depth_max <= 65535, CODON_ERR_BAD_ARG, "quantize_levels: depth_max %d (1..65535)", depth_max);
   return quantize_levels((long)n, x, lut16, depth_max, (hipStream_t)stream);
+}
+
+int codon_bicubic_upsample_masked(int32_t batch, int32_t lr_height, int32_t lr_width, int32_t scale, const float* lr,
+                                  const float* phase_weights, float* out, uint8_t* valid, codon_stream_t stream) {
+  CODON_REQUIRE(lr && phase_weights && out, CODON_ERR_BAD_ARG, "bicubic_upsample_masked: null pointer");
+  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "bicubic_upsample_masked: scale %d", scale);
+  CODON_REQUIRE(lr_height >= 1 && lr_width >= 1 && lr_height <= 65536 && lr_width <= 65536 &&
+                    shape_ok(batch, lr_height * scale, lr_width * scale),
+                CODON_ERR_BAD_ARG, "bicubic_upsample_masked: bad shape");
+  return bicubic_upsample_masked(batch, lr_height, lr_width, scale, lr, phase_weights, out, valid, (hipStream_t)stream);
+}
+
+int codon_bicubic_downsample_masked(int32_t batch, int32_t size, int32_t scale, const float* hr, const float* weights,
+                                    const float* lut, int32_t levels, float* out, codon_stream_t stream) {
+  CODON_REQUIRE(hr && weights && lut && out, CODON_ERR_BAD_ARG, "bicubic_downsample_masked: null pointer");
+  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "bicubic_downsample_masked: scale %d", scale);
+  CODON_REQUIRE(batch >= 1 && batch < 65536 && size >= 4 * scale && size <= 1024 && size % scale == 0, CODON_ERR_BAD_ARG,
+                "bicubic_downsample_masked: batch %d, size %d at scale %d (size: a multiple of the scale, 4 * scale .. 1024)",
+                batch, size, scale);
+  CODON_REQUIRE(levels >= 1 && levels <= 65535, CODON_ERR_BAD_ARG, "bicubic_downsample_masked: levels %d (1..65535)", levels);
+  return bicubic_downsample_masked(batch, size, scale, hr, weights, lut, levels, out, (hipStream_t)stream);
+}
+
+int codon_lr_codes_to_input(int32_t batch, int32_t lr_height, int32_t lr_width, int32_t scale, const void* codes,
+                            int32_t code_bits, const float* lut, int32_t depth_max, const float* phase_weights, void* out,
+                            int32_t dtype, codon_stream_t stream) {
+  CODON_REQUIRE(codes && lut && phase_weights && out, CODON_ERR_BAD_ARG, "lr_codes_to_input: null pointer");
+  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "lr_codes_to_input: scale %d", scale);
+  CODON_REQUIRE(dtype == CODON_F32 || dtype == CODON_F16 || dtype == CODON_BF16, CODON_ERR_UNSUPPORTED,
+                "lr_codes_to_input: dtype %d (fp32, fp16 or bf16)", dtype);
+  CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "lr_codes_to_input: code_bits %d (8 or 16)", code_bits);
+  CODON_REQUIRE(code_bits == 16 ? (depth_max >= 1 && depth_max <= 65535) : depth_max == 255, CODON_ERR_BAD_ARG,
+                "lr_codes_to_input: depth_max %d (255 for 8-bit codes, 1..65535 for 16-bit codes)", depth_max);
+  CODON_REQUIRE(lr_height >= 1 && lr_width >= 1 && lr_height <= 65536 && lr_width <= 65536 &&
+                    shape_ok(batch, lr_height * scale, lr_width * scale),
+                CODON_ERR_BAD_ARG, "lr_codes_to_input: bad shape");
+  CODON_REQUIRE(((uintptr_t)out & 15) == 0 && (code_bits == 8 || ((uintptr_t)codes & 1) == 0), CODON_ERR_BAD_ARG,
+                "lr_codes_to_input: out must be 16-byte aligned and u16 codes 2-byte aligned");
+  return lr_codes_to_input(batch, lr_height, lr_width, scale, codes, code_bits, lut, depth_max, phase_weights, out, dtype,
+                           (hipStream_t)stream);
 }
 
 size_t codon_weight_checksum_workspace_bytes(void) { return weight_checksum_workspace_bytes(); }

@@ -10,7 +10,11 @@ conversion, the upload, the download and the PNG encode take several times that 
   main thread   : forward + post-processing + metrics of image i on the caller's stream (waits for the upload's event)
   writer thread : download of image i-1 has landed in pinned memory (event) -> PNG encode + write
 Same arithmetic per image in the same order: outputs are byte-identical to the serial loop (`--serial`, kept for the A/B
-and the test)."""
+and the test).
+
+--lr-depth DIR instead of --input-depth: the depth files are LOW-RESOLUTION maps as a sensor writes them, code 0 a
+hole.  The reader uploads the codes and the main stream turns them into the network's input with one launch
+(codes_to_input: the training degradation's own hole-aware bicubic x--scale, back onto the code grid, cast), then the forward."""
 from __future__ import annotations
 
 import argparse
@@ -43,22 +47,92 @@ def _load_host(a_depth, a_color, a_label, f, tdt, depth_bits=8, depth_max=65535)
     px = read_depth_plane(os.path.join(a_depth, f), depth_bits, depth_max)
     py = io.read_gray(os.path.join(a_color, f))
     h, w = min(px.shape[0], py.shape[0]), min(px.shape[1], py.shape[1])
-    ndt = {torch.float32: np.float32, torch.float16: np.float16}.get(tdt)
-
-    def conv(p_, top=255):
-        v = (np.asarray(p_[:h, :w]) / top).astype(np.float32)
-        if ndt is not None:
-            return torch.from_numpy(np.ascontiguousarray(v.astype(ndt)))[None, None]
-        # bf16 has no numpy type: round to nearest even on the bit pattern (finite, non-negative inputs)
-        u = np.ascontiguousarray(v).view(np.uint32)
-        b16 = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
-        return torch.from_numpy(b16.view(np.int16)).view(torch.bfloat16)[None, None]
-
     lab = None
     if a_label:
         lab = read_depth_plane(os.path.join(a_label, f), depth_bits, depth_max).copy()
         lab = torch.from_numpy(lab.view(np.int16) if depth_bits == 16 else lab)
-    return conv(px, depth_max if depth_bits == 16 else 255), conv(py), lab, h, w
+    return _plane(px[:h, :w], depth_max if depth_bits == 16 else 255, tdt), _plane(py[:h, :w], 255, tdt), lab, h, w
+
+
+def _plane(p_, top, tdt):
+    """(1,1,h,w) host tensor of dtype tdt: codes / top in float64, float32, then the dtype's round-to-nearest-even."""
+    ndt = {torch.float32: np.float32, torch.float16: np.float16}.get(tdt)
+    v = (np.asarray(p_) / top).astype(np.float32)
+    if ndt is not None:
+        return torch.from_numpy(np.ascontiguousarray(v.astype(ndt)))[None, None]
+    # bf16 has no numpy type: round to nearest even on the bit pattern (finite, non-negative inputs)
+    u = np.ascontiguousarray(v).view(np.uint32)
+    b16 = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+    return torch.from_numpy(b16.view(np.int16)).view(torch.bfloat16)[None, None]
+
+
+def _load_host_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits=8, depth_max=65535):
+    """Host side of one image under --lr-depth: the depth file is a LOW-RESOLUTION map of codes (0 a hole), read
+    through train.read_depth_plane and returned AS CODES -- (h,w) uint8, or the u16 bits as int16 -- for codes_to_input; the
+    HR size is (h * scale, w * scale), and the guidance and the label are cropped top-left to it.  A smaller guidance or label
+    raises ValueError naming the file."""
+    from .train import read_depth_plane
+    px = read_depth_plane(os.path.join(a_lr, f), depth_bits, depth_max)
+    py = io.read_gray(os.path.join(a_color, f))
+    h, w = px.shape[0] * scale, px.shape[1] * scale
+    if py.shape[0] < h or py.shape[1] < w:
+        raise ValueError(f"{os.path.join(a_color, f)}: {py.shape[0]}x{py.shape[1]}, smaller than the {h}x{w} that "
+                         f"{os.path.join(a_lr, f)} gives at x{scale}")
+    lab = None
+    if a_label:
+        lab = read_depth_plane(os.path.join(a_label, f), depth_bits, depth_max)
+        if lab.shape[0] < h or lab.shape[1] < w:
+            raise ValueError(f"{os.path.join(a_label, f)}: {lab.shape[0]}x{lab.shape[1]}, smaller than the {h}x{w} that "
+                             f"{os.path.join(a_lr, f)} gives at x{scale}")
+        lab = np.array(lab[:h, :w])                # a writable, contiguous copy of the crop
+        lab = torch.from_numpy(lab.view(np.int16) if depth_bits == 16 else lab)
+    px = np.array(px)
+    codes = torch.from_numpy(px.view(np.int16) if depth_bits == 16 else px)
+    return codes, _plane(py[:h, :w], 255, tdt), lab, h, w
+
+
+def codes_to_input(codes: torch.Tensor, scale: int, tdt, depth_max: int = None) -> torch.Tensor:
+    """The network's depth input from a low-resolution code plane on the device, ONE launch (codon_lr_codes_to_input):
+    codes (h,w) or (B,h,w), uint8 (value = code / 255) or the bits of u16 codes as int16 / uint16 (value = code / depth_max,
+    default 65535), code 0 a hole -> the mask-normalised bicubic x`scale` (upsample.bicubic_upsample_masked) -> back onto the
+    code grid -> tdt, as (B,1,h*scale,w*scale).  Bit for bit what train.synthesize(degrade_holes=True) builds from the same
+    low-resolution values."""
+    from . import _lib as L
+    from . import ops
+    from .train import _on_device, check_depth_max, lut16, u8_lut
+    from .upsample import phase_weights
+    import ctypes as C
+    if codes.dim() == 2:
+        codes = codes[None]
+    if codes.dim() != 3 or codes.dtype not in (torch.uint8, torch.int16, torch.uint16):
+        raise RuntimeError("codes_to_input expects (h,w) or (B,h,w) uint8 codes, or u16 codes as int16 / uint16")
+    if scale not in (4, 8, 16):
+        raise ValueError(f"codes_to_input: scale {scale!r} (4, 8 or 16)")
+    if tdt not in _ABI_DTYPE:
+        raise ValueError(f"codes_to_input: dtype {tdt!r} (float32, float16 or bfloat16)")
+    lib = L.load()
+    codes = codes.contiguous()
+    dev = ops._dev(codes)
+    if codes.dtype == torch.uint8:
+        if depth_max not in (None, 255):
+            raise ValueError(f"codes_to_input: depth_max {depth_max!r} with 8-bit codes")
+        bits, top, lut = 8, 255, _on_device("lut", u8_lut, dev)
+    else:
+        top = 65535 if depth_max is None else depth_max
+        check_depth_max(top)
+        bits, lut = 16, _on_device(("lut16", int(top)), lambda: lut16(int(top)), dev)
+    wt = _on_device(("up", scale), lambda: phase_weights(scale), dev)
+    B, h, w = codes.shape
+    out = torch.empty((B, 1, h * scale, w * scale), dtype=tdt, device=dev)
+    P_ = C.c_void_p
+    with ops._on(dev):
+        L.check(lib.codon_lr_codes_to_input(B, h, w, scale, P_(codes.data_ptr()), bits, P_(lut.data_ptr()), int(top),
+                                            P_(wt.data_ptr()), P_(out.data_ptr()), _ABI_DTYPE[tdt], ops._stream(dev)),
+                "lr_codes_to_input")
+    return out
+
+
+_ABI_DTYPE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}      # codon_dtype
 
 
 READERS = int(os.environ.get("CODON_INFER_READERS", "3"))
@@ -77,11 +151,17 @@ def _pinned_copy(t: torch.Tensor) -> torch.Tensor:
 
 
 def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None,
-             depth_bits=8, depth_max=65535, depth_unit=1.0):
+             depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None):
     """The test loop over every image pair.  Returns {"n", "rmse_mean", "ssim_mean", "seconds", "images_per_s"}.
     depth_bits=16: 16-bit depth and label files with codes 0 .. depth_max, outputs through metrics.postprocess_u16 into 16-bit
-    PNGs, RMSE (metrics.masked_rmse_u16) in codes times depth_unit, SSIM of label / depth_max against out / depth_max."""
-    files = list_pairs(input_depth, input_color) if files is None else files
+    PNGs, RMSE (metrics.masked_rmse_u16) in codes times depth_unit, SSIM of label / depth_max against out / depth_max.
+    lr_depth (with scale; instead of input_depth): a directory of LOW-RESOLUTION depth maps, code 0 a hole -- the
+    reader uploads the codes, and the main stream turns them into the depth input with codes_to_input ahead of the forward."""
+    if (lr_depth is None) == (input_depth is None):
+        raise ValueError("run_loop: exactly one of input_depth and lr_depth")
+    if lr_depth is not None and scale not in (4, 8, 16):
+        raise ValueError(f"run_loop: lr_depth needs scale 4, 8 or 16 (got {scale!r})")
+    files = list_pairs(lr_depth or input_depth, input_color) if files is None else files
     if depth_bits not in (8, 16):
         raise ValueError(f"run_loop: depth_bits {depth_bits!r} (8 or 16)")
     deep = depth_bits == 16
@@ -95,6 +175,12 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
         post, sqerr, write = metrics.postprocess_u8, metrics.masked_sqerr_dev, io.write_gray
         unit = lambda t: t.float() / 255                                                         # noqa: E731
     scale_rm = float(depth_unit) if deep else None
+    if lr_depth is not None:
+        load = lambda f: _load_host_lr(lr_depth, input_color, label, f, tdt, scale, depth_bits, depth_max)      # noqa: E731
+        to_x = lambda c: codes_to_input(c, scale, tdt, depth_max if deep else None)                            # noqa: E731
+    else:
+        load = lambda f: _load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max)             # noqa: E731
+        to_x = lambda x: x                                                                                     # noqa: E731
     t0 = time.perf_counter()
     rm_sum = ss_sum = 0.0
     n = 0
@@ -114,9 +200,9 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
 
     if not pipelined:
         for f in files:
-            x, y, lab, h, w = _load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max)
+            x, y, lab, h, w = load(f)
             with torch.no_grad():
-                out = model(x.to(dev), y.to(dev))
+                out = model(to_x(x.to(dev)), y.to(dev))
             out_u8, line = finish(f, out, lab.to(dev) if lab is not None else None, h, w)
             if out_dir:
                 write(os.path.join(out_dir, f), out_u8.cpu().numpy())
@@ -138,7 +224,7 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                 for f in files[k::READERS]:
                     if stop.is_set():
                         break
-                    x, y, lab, h, w = _load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max)
+                    x, y, lab, h, w = load(f)
                     host = [_pinned_copy(t) for t in ((x, y) if lab is None else (x, y, lab))]
                     with torch.cuda.stream(up_s):
                         devs = [t.to(dev, non_blocking=True) for t in host]
@@ -193,7 +279,7 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                 for t in devs:
                     t.record_stream(main_s)                        # allocated on the upload stream, consumed on this one
                 with torch.no_grad():
-                    out = model(devs[0], devs[1])
+                    out = model(to_x(devs[0]), devs[1])
                 out_u8 = post(out[0, 0])
                 h_acc = h_ss = None
                 if len(devs) > 2:                                  # metrics stay on the device; read back one image later
@@ -236,7 +322,11 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scale", type=int, default=4, choices=[4, 8, 16])
-    ap.add_argument("--input-depth", required=True)
+    ap.add_argument("--input-depth", default=None, help="depth maps already at the output size (this or --lr-depth)")
+    ap.add_argument("--lr-depth", default=None,
+                    help="LOW-RESOLUTION depth maps as a sensor writes them, code 0 a hole: upsampled by --scale on the device "
+                         "with the training degradation's own hole-aware bicubic; guidance and label are cropped to "
+                         "(h * scale, w * scale)")
     ap.add_argument("--input-color", required=True)
     ap.add_argument("--label", default=None)
     ap.add_argument("--out", default=None)
@@ -253,6 +343,8 @@ def main(argv=None):
     ap.add_argument("--depth-unit", type=float, default=1.0,
                     help="with --depth-bits 16: the printed RMSE is in codes times this (0.1: centimetres from millimetre codes)")
     a = ap.parse_args(argv)
+    if (a.input_depth is None) == (a.lr_depth is None):
+        ap.error("exactly one of --input-depth and --lr-depth is required")
     if a.ema and not a.weights:
         ap.error("--ema needs --weights")
     if a.depth_bits != 16 and (a.depth_max is not None or a.depth_unit != 1.0):
@@ -273,7 +365,8 @@ def main(argv=None):
     if a.out:
         os.makedirs(a.out, exist_ok=True)
     r = run_loop(model, dev, tdt, a.input_depth, a.input_color, a.label, a.out, pipelined=not a.serial,
-                 depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit)
+                 depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit,
+                 **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}))
     print(r["n"])
     if a.label and r["n"]:
         print(r["rmse_mean"], r["ssim_mean"])

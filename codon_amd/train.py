@@ -44,6 +44,8 @@ RESUME_DEFAULTS = {"clip_norm": None, "skip_nonfinite": False, "ema": None, "lr_
 # compared on --resume like RESUME_KEYS, but written by a 16-bit run ONLY: an 8-bit checkpoint keeps exactly the
 # args it always had, and one without these keys compares as 8-bit
 DEPTH_DEFAULTS = {"depth_bits": 8, "depth_max": 65535}
+# the same for --degrade-holes: a resume key with default False, written by a run that sets it ONLY
+DEGRADE_DEFAULTS = {"degrade_holes": False}
 MAX_REDRAWS = 64                                    # draw(min_valid=): per sample, before it gives up
 LR_SCHEDULES = ("constant", "cosine")
 
@@ -257,18 +259,26 @@ def draw(rng: np.random.Generator, trainset: TrainSet, batch: int, crop: int, ra
     return d[lo:hi]
 
 
-def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int):
+def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, degrade_holes: bool = False,
+               return_lr: bool = False):
     """(x, y, t), each (B,1,crop,crop) fp32 on the pool's device: the network's depth input (crop -> bicubic down by `scale`
     -> bicubic up -> 8-bit), the guidance and the HR target.  Four launches on the caller's stream, no host synchronisation.
     A TrainSet with labels: x is degraded from the depth plane, t comes from the label plane (codon_train_crops_labeled).
     A 16-bit TrainSet: codon_train_crops_u16 (labeled or not) and codon_quantize_levels onto the set's own code grid, the
-    down and up kernels between them unchanged -- four launches as well."""
+    down and up kernels between them unchanged -- four launches as well.
+    degrade_holes: the source's holes (0.0) are left out of both bicubics instead of being smeared through them --
+    codon_bicubic_downsample_masked (whose result is a low-resolution map on the code grid, holes 0.0, as a sensor's file holds
+    it) and codon_bicubic_upsample_masked take the place of the down and up launches, the quantise launch follows unchanged:
+    four launches still, no host synchronisation; x is bit for bit what infer.codes_to_input builds from that map's codes.
+    return_lr: (x, y, t, lr) with lr the (B,1,crop/scale,crop/scale) low-resolution map."""
     lib = L.load()
     B = len(descs)
     if not 1 <= B <= L.TRAIN_MAX_BATCH:
         raise ValueError(f"synthesize: {B} samples per launch (1..{L.TRAIN_MAX_BATCH})")
     if crop % scale or crop // scale < 4:
         raise ValueError(f"synthesize: crop {crop} must be a multiple of the scale {scale} and at least 4 * scale")
+    if degrade_holes and crop > 1024:
+        raise ValueError(f"synthesize: degrade_holes takes crops up to 1024 (crop {crop})")
     dev = trainset.pool.device
     d = L.CropDesc()
     d.n, d.crop = B, crop
@@ -301,16 +311,24 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int):
         else:
             L.check(lib.codon_train_crops(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(), P_(lut.data_ptr()),
                                           P_(t.data_ptr()), P_(y.data_ptr()), st), "train_crops")
-        L.check(lib.codon_bicubic_downsample(B, crop, scale, P_(src.data_ptr()), P_(wdown.data_ptr()), P_(lr.data_ptr()), st),
-                "bicubic_downsample")
-        L.check(lib.codon_bicubic_upsample(B, p, p, scale, P_(lr.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()), st),
-                "bicubic_upsample")
+        if degrade_holes:
+            snap, levels = (lut_deep, trainset.depth_max) if deep else (lut, 255)
+            L.check(lib.codon_bicubic_downsample_masked(B, crop, scale, P_(src.data_ptr()), P_(wdown.data_ptr()),
+                                                        P_(snap.data_ptr()), levels, P_(lr.data_ptr()), st),
+                    "bicubic_downsample_masked")
+            L.check(lib.codon_bicubic_upsample_masked(B, p, p, scale, P_(lr.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()),
+                                                      None, st), "bicubic_upsample_masked")
+        else:
+            L.check(lib.codon_bicubic_downsample(B, crop, scale, P_(src.data_ptr()), P_(wdown.data_ptr()), P_(lr.data_ptr()),
+                                                 st), "bicubic_downsample")
+            L.check(lib.codon_bicubic_upsample(B, p, p, scale, P_(lr.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()), st),
+                    "bicubic_upsample")
         if deep:
             L.check(lib.codon_quantize_levels(x.numel(), P_(x.data_ptr()), P_(lut_deep.data_ptr()), trainset.depth_max, st),
                     "quantize_levels")
         else:
             L.check(lib.codon_quantize_u8(x.numel(), P_(x.data_ptr()), P_(lut.data_ptr()), st), "quantize_u8")
-    return x, y, t
+    return (x, y, t, lr) if return_lr else (x, y, t)
 
 
 # ---- training -----------------------------------------------------------------------------------------------------------------
@@ -356,12 +374,13 @@ def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, 
 
 def load_resume(path: str, args: dict) -> dict:
     """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype, or with
-    other options that change the trajectory (RESUME_KEYS and DEPTH_DEFAULTS' keys; a key the checkpoint's args lack compares
-    as its default)."""
+    other options that change the trajectory (RESUME_KEYS, DEPTH_DEFAULTS' and DEGRADE_DEFAULTS' keys; a key the checkpoint's
+    args lack compares as its default)."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(ck, dict) or not all(k in ck for k in ("epoch", "model", "optimizer", "rng", "args")):
         raise ValueError(f"--resume {path}: not a codon_amd.train checkpoint (use --weights to start from other weights)")
-    absent, keys = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS}, RESUME_KEYS + tuple(DEPTH_DEFAULTS)
+    absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS}
+    keys = RESUME_KEYS + tuple(DEPTH_DEFAULTS) + tuple(DEGRADE_DEFAULTS)
     was, now = ({k: a.get(k, absent.get(k)) for k in keys} for a in (ck["args"], args))
     bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in keys if was[k] != now[k]]
     if bad:
@@ -374,7 +393,7 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         val: dict = None, ckpt: dict = None, start_step: int = 0, opt_state: dict = None, fixed: np.ndarray = None,
         args: dict = None, time_synth: bool = False, emit=print, clip_norm: float = None, skip_nonfinite: bool = False,
         ema_decay: float = None, lr_schedule: str = "constant", warmup: int = 0, lr_min: float = 0.0, lr_steps: int = None,
-        grad_hook=None, mask_holes: bool = False, min_valid: float = 0.0) -> dict:
+        grad_hook=None, mask_holes: bool = False, min_valid: float = 0.0, degrade_holes: bool = False) -> dict:
     """Train `model` (fp32 parameters on the pool's device) from step start_step + 1 to step `steps`.
     val:   {"depth", "color", "label", "every"} -- rank 0 runs infer.run_loop every `every` steps and prints the means;
     ckpt:  {"path", "every"} -- rank 0 saves every `every` steps and after the last one;
@@ -389,6 +408,7 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
            TrainSet has one) carry no loss and no gradient; the log lines gain ` valid 0.xxx`, the global batch's
            valid fraction, computed on the host from the descriptors (no device read);
     min_valid: draw's threshold (needs mask_holes).
+    degrade_holes: synthesize's hole-aware degradation; needs no other option.
     Returns {"losses": [(step, loss)], "gs", "opt", "rng", "step", ...}."""
     from .dist import FlatAdam, GradSync
     from .metrics import L1SSIMLoss, MaskedL1SSIMLoss
@@ -419,6 +439,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
                 skip_nonfinite=bool(skip_nonfinite), ema=ema_decay, lr_schedule=lr_schedule, warmup_steps=warmup, lr_min=lr_min,
                 lr_steps=lr_steps if lr_schedule == "cosine" else None)
     args.update(mask_holes=bool(mask_holes), min_valid=float(min_valid), train_label=bool(trainset.has_label))
+    if degrade_holes:                               # only then: a checkpoint of a run without it keeps the keys it always had
+        args.update(degrade_holes=True)
     if getattr(trainset, "depth_bits", 8) == 16:    # only then: an 8-bit checkpoint keeps the keys it always had
         args.update(depth_bits=16, depth_max=int(trainset.depth_max))
     stream = torch.cuda.current_stream(dev)
@@ -441,7 +463,7 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         gs.zero_grad()
         if time_synth:
             e[1].record(stream)
-        x, y, t = synthesize(trainset, descs, scale, crop)
+        x, y, t = synthesize(trainset, descs, scale, crop, degrade_holes=degrade_holes)
         if time_synth:
             e[2].record(stream)
         out = model(x, y)
@@ -502,7 +524,9 @@ def validate(model, dev, val: dict, emit=print) -> dict:
     try:
         with torch.no_grad():
             deep = {"depth_bits": 16, "depth_max": val.get("depth_max", 65535)} if val.get("depth_bits", 8) == 16 else {}
-            r = run_loop(model, dev, torch.float32, val["depth"], val["color"], val.get("label"), emit=lambda s: None, **deep)
+            if val.get("lr_depth"):                 # low-resolution validation maps, upsampled as infer --lr-depth does
+                deep.update(lr_depth=val["lr_depth"], scale=val["scale"])
+            r = run_loop(model, dev, torch.float32, val.get("depth"), val["color"], val.get("label"), emit=lambda s: None, **deep)
     finally:
         model.train()
     emit(f"val {r['n']} images rmse {r['rmse_mean']} ssim {r['ssim_mean']}")
@@ -539,7 +563,13 @@ def parse_args(argv=None):
     ap.add_argument("--resume", default=None,
                     help="a checkpoint of this script: model, optimizer (its lr included) and generator state")
     ap.add_argument("--weights", default=None, help="initial weights: any checkpoint io.load_checkpoint reads")
+    ap.add_argument("--degrade-holes", action="store_true",
+                    help="holes (code 0) of the depth maps are left out of the degradation's two bicubics instead of being "
+                         "smeared through them; the low-resolution map keeps them as holes, as a sensor's file does")
     ap.add_argument("--val-depth", default=None)
+    ap.add_argument("--val-lr-depth", default=None,
+                    help="low-resolution validation depth maps, upsampled by --scale as `codon_amd.infer --lr-depth` does "
+                         "(instead of --val-depth)")
     ap.add_argument("--val-color", default=None)
     ap.add_argument("--val-label", default=None)
     ap.add_argument("--val-every", type=int, default=1000)
@@ -563,8 +593,12 @@ def parse_args(argv=None):
         ap.error("--batch, --steps, --log-every, --save-every and --val-every must be positive")
     if a.resume and a.weights:
         ap.error("--resume and --weights exclude each other")
-    if (a.val_depth is None) != (a.val_color is None):
-        ap.error("--val-depth and --val-color go together")
+    if a.val_depth is not None and a.val_lr_depth is not None:
+        ap.error("--val-depth and --val-lr-depth exclude each other")
+    if (a.val_depth is None and a.val_lr_depth is None) != (a.val_color is None):
+        ap.error("--val-depth (or --val-lr-depth) and --val-color go together")
+    if a.degrade_holes and a.crop > 1024:
+        ap.error(f"--degrade-holes takes crops up to 1024 (--crop {a.crop})")
     if not 0.0 <= a.min_valid <= 1.0:
         ap.error(f"--min-valid {a.min_valid} must lie in [0, 1]")
     if a.min_valid > 0 and not a.mask_holes:
@@ -598,7 +632,8 @@ def run_args(a) -> dict:
     return {**deep, "scale": a.scale, "crop": a.crop, "batch": a.batch, "dtype": a.dtype, "lr": a.lr, "seed": a.seed,
             "clip_norm": a.clip_norm, "skip_nonfinite": a.skip_nonfinite, "ema": a.ema, "lr_schedule": a.lr_schedule,
             "warmup_steps": a.warmup_steps, "lr_min": a.lr_min, "lr_steps": a.lr_steps, "mask_holes": bool(a.mask_holes),
-            "min_valid": float(a.min_valid), "train_label": a.train_label is not None}
+            "min_valid": float(a.min_valid), "train_label": a.train_label is not None,
+            **({"degrade_holes": True} if a.degrade_holes else {})}
 
 
 def main(argv=None, emit=print) -> dict:
@@ -640,13 +675,15 @@ def main(argv=None, emit=print) -> dict:
         emit(f"{len(ts)} training pairs, x{a.scale}, crop {a.crop}, batch {a.batch} over {world} rank(s), {a.dtype}, "
              f"steps {start + 1}..{a.steps}")
     val = ({"depth": a.val_depth, "color": a.val_color, "label": a.val_label, "every": a.val_every,
-            "depth_bits": a.depth_bits, "depth_max": a.depth_max} if a.val_depth else None)
+            "depth_bits": a.depth_bits, "depth_max": a.depth_max} if a.val_depth or a.val_lr_depth else None)
+    if a.val_lr_depth:
+        val.update(lr_depth=a.val_lr_depth, scale=a.scale)
     ckpt = {"path": a.save, "every": a.save_every} if a.save else None
     res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,
               log_every=a.log_every, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,
               args=args, emit=emit, clip_norm=a.clip_norm, skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema,
               lr_schedule=a.lr_schedule, warmup=a.warmup_steps, lr_min=a.lr_min, lr_steps=a.lr_steps,
-              mask_holes=a.mask_holes, min_valid=a.min_valid)
+              mask_holes=a.mask_holes, min_valid=a.min_valid, degrade_holes=a.degrade_holes)
     res["model"] = model
     return res
 

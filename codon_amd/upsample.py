@@ -43,3 +43,23 @@ def bicubic_upsample(lr: torch.Tensor, scale: int) -> torch.Tensor:
         L.check(lib.codon_bicubic_upsample(B, h, w, scale, C.c_void_p(lr.data_ptr()), C.c_void_p(wt.data_ptr()),
                                            C.c_void_p(out.data_ptr()), ops._stream(dev)), "bicubic_upsample")
     return out
+
+
+def bicubic_upsample_masked(lr: torch.Tensor, scale: int):
+    """(hr, valid): bicubic_upsample of a map in which 0.0 marks a hole, mask-normalised -- a pixel none of whose
+    16 taps is a hole gets bicubic_upsample's bits, one whose valid taps weigh at least 0.5 the ratio of the two sums, any
+    other is a hole again (0.0, valid 0).  valid: (B,1,h*scale,w*scale) uint8."""
+    lib = L.load()
+    if lr.dim() != 4 or lr.shape[1] != 1 or lr.dtype != torch.float32:
+        raise RuntimeError("bicubic_upsample_masked expects a (B,1,h,w) fp32 tensor")
+    lr = lr.contiguous()
+    dev = ops._dev(lr)
+    B, _, h, w = lr.shape
+    wt = torch.from_numpy(phase_weights(scale)).to(dev)
+    out = torch.empty((B, 1, h * scale, w * scale), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, 1, h * scale, w * scale), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.codon_bicubic_upsample_masked(B, h, w, scale, C.c_void_p(lr.data_ptr()), C.c_void_p(wt.data_ptr()),
+                                                  C.c_void_p(out.data_ptr()), C.c_void_p(valid.data_ptr()), ops._stream(dev)),
+                "bicubic_upsample_masked")
+    return out, valid

@@ -669,6 +669,32 @@ int codon_train_crops_u16(const codon_crop_desc* desc, const uint8_t* pool, int6
  * depth_max in [1, 65535]. */
 int codon_quantize_levels(int64_t n, float* x, const float* lut16, int32_t depth_max, codon_stream_t stream);
 
+/* ---- hole-aware (mask-normalised) bicubic resampling: depth maps in which 0.0 / code 0 marks a hole ----------
+ * No reference counterpart (the reference ships neither a degradation nor an upsampler): DEFINITIONS, in
+ * codon_amd/csrc/resample_masked.hip, restated in numpy in tests/resample_masked_ref.py, required to agree bit for bit.
+ * With N the unmasked kernel's own arithmetic (holes entering as 0.0), D the same arithmetic over the validity (0.0f / 1.0f)
+ * and the count of invalid taps:  0 invalid -> N, valid;  otherwise D >= 0.5f -> N / D (correctly rounded), valid;  otherwise
+ * +0.0f, a hole.
+ *
+ * codon_bicubic_upsample_masked: codon_bicubic_upsample under that rule (the count over all 16 taps, a clamped border tap
+ * carrying its clamped pixel's validity).  valid: (B,1,h*scale,w*scale) u8, 1 where the result is valid, or NULL. */
+int codon_bicubic_upsample_masked(int32_t batch, int32_t lr_height, int32_t lr_width, int32_t scale, const float* lr,
+                                  const float* phase_weights, float* out, uint8_t* valid, codon_stream_t stream);
+/* codon_bicubic_downsample_masked: codon_bicubic_downsample under that rule (numerator and denominator through both passes,
+ * the count over the taps inside the image), then every valid value v is snapped as a sensor's file would hold it:
+ * out = lut[min(max((int)rintf(clamp(v, 0, 1) * (float)levels), 1), levels)] -- never code 0; a hole is +0.0f.  lut: levels + 1
+ * fp32 entries (levels 255 with the 256-entry table of codon_train_crops, or depth_max with lut16).  size <= 1024. */
+int codon_bicubic_downsample_masked(int32_t batch, int32_t size, int32_t scale, const float* hr, const float* weights,
+                                    const float* lut, int32_t levels, float* out, codon_stream_t stream);
+/* codon_lr_codes_to_input: a low-resolution code plane as the network's depth input, one launch:
+ *   codes (B,h,w) u8 (code_bits 8, depth_max 255, lut of 256 entries) or u16 (code_bits 16, lut16 of 65 536 entries)
+ *   -> lut -> codon_bicubic_upsample_masked's rule -> lut[(int)rintf(clamp(., 0, 1) * (float)depth_max)]
+ *   -> round to nearest even into dtype (a codon_dtype), written to out (B,1,h*scale,w*scale), 16-byte aligned.
+ * Bit for bit codon_bicubic_upsample_masked, then codon_quantize_u8 / codon_quantize_levels, then a cast. */
+int codon_lr_codes_to_input(int32_t batch, int32_t lr_height, int32_t lr_width, int32_t scale, const void* codes,
+                            int32_t code_bits, const float* lut, int32_t depth_max, const float* phase_weights, void* out,
+                            int32_t dtype, codon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
