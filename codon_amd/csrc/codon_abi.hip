@@ -132,6 +132,8 @@ int quantize_levels(long, float*, const float*, int, hipStream_t);
 int bicubic_upsample_masked(int, int, int, int, const float*, const float*, float*, unsigned char*, hipStream_t);
 int bicubic_downsample_masked(int, int, int, const float*, const float*, const float*, int, float*, hipStream_t);
 int lr_codes_to_input(int, int, int, int, const void*, int, const float*, int, const float*, void*, int, hipStream_t);
+int train_crops_lr(const codon_crop_desc*, const unsigned char*, int, int, const float*, int, const float*, const float*, float*,
+                   float*, float*, hipStream_t);
 size_t weight_checksum_workspace_bytes();
 int weight_checksum(const codon_wsum_desc*, void*, unsigned long long*, int, int*, int*, int, hipStream_t);
 
@@ -993,6 +995,40 @@ int codon_lr_codes_to_input(int32_t batch, int32_t lr_height, int32_t lr_width, 
                 "lr_codes_to_input: out must be 16-byte aligned and u16 codes 2-byte aligned");
   return lr_codes_to_input(batch, lr_height, lr_width, scale, codes, code_bits, lut, depth_max, phase_weights, out, dtype,
                            (hipStream_t)stream);
+}
+
+int codon_train_crops_lr(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, int32_t scale, int32_t code_bits,
+                         const float* lut, int32_t depth_max, const float* lut8, const float* phase_weights, float* x,
+                         float* guide, float* target, codon_stream_t stream) {
+  CODON_REQUIRE(desc && pool && lut && lut8 && phase_weights && x && guide && target, CODON_ERR_BAD_ARG,
+                "train_crops_lr: null pointer");
+  CODON_REQUIRE(desc->n >= 1 && desc->n <= CODON_TRAIN_MAX_BATCH, CODON_ERR_BAD_ARG, "train_crops_lr: batch %d (1..%d)", desc->n,
+                CODON_TRAIN_MAX_BATCH);
+  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "train_crops_lr: scale %d", scale);
+  CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "train_crops_lr: code_bits %d (8 or 16)", code_bits);
+  CODON_REQUIRE(code_bits == 16 ? (depth_max >= 1 && depth_max <= 65535) : depth_max == 255, CODON_ERR_BAD_ARG,
+                "train_crops_lr: depth_max %d (255 for 8-bit codes, 1..65535 for 16-bit codes)", depth_max);
+  CODON_REQUIRE(code_bits == 8 || ((uintptr_t)pool & 1) == 0, CODON_ERR_BAD_ARG, "train_crops_lr: the pool is not 2-byte aligned");
+  const int P = desc->crop;
+  CODON_REQUIRE(P >= 1 && P <= 2048, CODON_ERR_BAD_ARG, "train_crops_lr: crop %d (1..2048)", P);
+  for (int b = 0; b < desc->n; ++b) {
+    const codon_crop_sample& c = desc->s[b];
+    CODON_REQUIRE(c.height >= 1 && c.width >= 1 && c.height % scale == 0 && c.width % scale == 0, CODON_ERR_BAD_ARG,
+                  "train_crops_lr: sample %d: %dx%d is no multiple of the scale %d", b, c.height, c.width, scale);
+    CODON_REQUIRE(c.height >= P && c.width >= P && c.y0 >= 0 && c.x0 >= 0 && c.y0 <= c.height - P && c.x0 <= c.width - P &&
+                      c.op >= 0 && c.op <= 7,
+                  CODON_ERR_BAD_ARG, "train_crops_lr: sample %d: %dx%d crop at (%d, %d) op %d outside the image", b, c.height,
+                  c.width, c.y0, c.x0, c.op);
+    CODON_REQUIRE(c.offset >= 0 && (code_bits == 8 || c.offset % 2 == 0), CODON_ERR_BAD_ARG,
+                  "train_crops_lr: sample %d: offset %lld is negative, or odd (u16 planes start at even bytes)", b,
+                  (long long)c.offset);
+    const int64_t hw = (int64_t)c.height * c.width, lhw = hw / ((int64_t)scale * scale);
+    const int64_t record = code_bits == 16 ? 3 * hw + 2 * lhw : 2 * hw + lhw;
+    CODON_REQUIRE(c.offset <= pool_bytes - record, CODON_ERR_BAD_ARG,
+                  "train_crops_lr: sample %d: the record at offset %lld runs past the %lld-byte pool", b, (long long)c.offset,
+                  (long long)pool_bytes);
+  }
+  return train_crops_lr(desc, pool, scale, code_bits, lut, depth_max, lut8, phase_weights, x, guide, target, (hipStream_t)stream);
 }
 
 size_t codon_weight_checksum_workspace_bytes(void) { return weight_checksum_workspace_bytes(); }

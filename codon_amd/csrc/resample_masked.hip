@@ -1,7 +1,8 @@
 // Hole-aware (mask-normalised) bicubic resampling of depth maps in which 0.0 / code 0 marks a hole: the masked
-// twins of bicubic_kernel (upsample.hip) and bicubic_down_kernel (train_data.hip), and the fused inference kernel that turns a
-// sensor's low-resolution code plane into the network's depth input in one launch.  No reference counterpart (the reference
-// ships neither a degradation nor an upsampler): these are DEFINITIONS, restated in numpy in tests/resample_masked_ref.py, and
+// twins of bicubic_kernel (upsample.hip) and bicubic_down_kernel (train_data.hip), the fused inference kernel that turns a
+// sensor's low-resolution code plane into the network's depth input in one launch, and its training twin (train_crops_lr,
+// DESIGN 12.5).  No reference counterpart (the reference ships neither a degradation nor an upsampler): these are
+// DEFINITIONS, restated in numpy in tests/resample_masked_ref.py (the training twin in tests/train_lr_ref.py), and
 // the two agree BIT FOR BIT -- built with -ffp-contract=off, every multiply, add and divide rounded on its own (the fp32
 // divide is hipcc's correctly rounded default; nothing here relaxes it).
 //
@@ -20,6 +21,9 @@
 //             code = min(max((int)rintf(clamp(v, 0, 1) * levels), 1), levels), out = lut[code] -- never code 0.
 // fused:      codes (u8 / u16) -> lut -> upsample rule -> lut[(int)rintf(clamp(., 0, 1) * levels)] -> round to nearest even
 //             into fp32 / fp16 / bf16: bicubic_masked_kernel, quantize_u8_kernel / quantize_levels_kernel and a cast, fused.
+// paired:     a training batch from records that carry a sensor's low-resolution code plane: t and y are the crop
+//             kernels' look-ups, x is the fused kernel's fp32 value at the source pixel of the WHOLE plane -- the window, under
+//             the D4 op, of what inference builds from the file.  Restated in numpy in tests/train_lr_ref.py.
 
 #include <hip/hip_fp16.h>
 
@@ -237,6 +241,109 @@ __global__ __launch_bounds__(256) void lr_codes_to_input_kernel(const void* __re
       *reinterpret_cast<uint2*>(dst) = o2;
     }
   }
+}
+
+// ---- paired training: records with a low-resolution code plane -> x, y, t -------------------------------------
+// grid (ceil(P*P / 256), B), one thread per output pixel of one sample, window and D4 op as train_crops_kernel.  The record
+// at byte `offset` of the pool:   8-bit: depth H*W u8 | guidance H*W u8 | LR codes h*w u8
+//                                16-bit: depth H*W u16 | LR codes h*w u16 | guidance H*W u8       (h, w) = (H / S, W / S)
+// so the LR plane starts at byte 2*H*W of either record.  t and y are the crop kernels' table look-ups at the source pixel
+// (gy, gx); x is what lr_codes_to_input_kernel writes at (gy, gx) of the WHOLE plane in fp32: bicubic_masked_kernel's index
+// arithmetic with the border clamp at the image's edge (the window's real neighbours are read), lut[code] for the 16 taps, rows
+// then columns, the rule, back onto the code grid.  The denominator and the count only where one of the 16 taps is a hole.
+struct CropLrArgs {
+  codon_crop_sample s[CODON_TRAIN_MAX_BATCH];
+};
+static_assert(sizeof(CropLrArgs) + 96 <= CODON_KERNARG_LIMIT, "passed by value as a kernel argument");
+
+template <int S>
+__global__ __launch_bounds__(256) void train_crops_lr_kernel(const CropLrArgs a, const unsigned char* __restrict__ pool,
+                                                             int code16, const float* __restrict__ lut, float levels,
+                                                             const float* __restrict__ lut8, const float* __restrict__ wtab,
+                                                             float* __restrict__ x, float* __restrict__ guide,
+                                                             float* __restrict__ target, int P) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= P * P) return;
+  const codon_crop_sample d = a.s[blockIdx.y];
+  const int i = idx / P, j = idx - i * P;
+  int si = i, sj = j;
+  if (d.op & 4) sj = P - 1 - sj;
+  if (d.op & 2) si = P - 1 - si;
+  if (d.op & 1) { const int t = si; si = sj; sj = t; }
+  const int gy = d.y0 + si, gx = d.x0 + sj;
+  const int h = d.height / S, w = d.width / S;
+  const long hw = (long)d.height * d.width;
+  const long px = (long)gy * d.width + gx;
+  const unsigned char* rec = pool + d.offset;            // even for u16 records (ABI check)
+  const unsigned char* lr8 = rec + 2 * hw;
+  const unsigned short* lr16 = reinterpret_cast<const unsigned short*>(lr8);
+  const long o = (long)blockIdx.y * P * P + idx;
+  if (code16) {
+    target[o] = lut[reinterpret_cast<const unsigned short*>(rec)[px]];
+    guide[o] = lut8[rec[2 * hw + 2 * (long)h * w + px]];
+  } else {
+    target[o] = lut[rec[px]];
+    guide[o] = lut8[rec[hw + px]];
+  }
+  const int qx = gx / S, rx = gx - qx * S, qy = gy / S, ry = gy - qy * S;
+  const int ix0 = qx - ((2 * rx + 1 < S) ? 1 : 0), iy0 = qy - ((2 * ry + 1 < S) ? 1 : 0);
+  const float* wx = wtab + rx * 4;
+  const float* wy = wtab + ry * 4;
+  const float w0 = wx[0], w1 = wx[1], w2 = wx[2], w3 = wx[3];
+  int xs[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) xs[c] = min(max(ix0 - 1 + c, 0), w - 1);
+  float v[4][4];
+  bool anyhole = false;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const long row = (long)min(max(iy0 - 1 + k, 0), h - 1) * w;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int code = code16 ? (int)lr16[row + xs[c]] : (int)lr8[row + xs[c]];
+      v[k][c] = lut[code];
+      anyhole = anyhole || !(v[k][c] != 0.f);
+    }
+  }
+  float nrow[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) nrow[k] = dot4m_rn(w0, w1, w2, w3, v[k][0], v[k][1], v[k][2], v[k][3]);
+  float r = dot4m_rn(wy[0], wy[1], wy[2], wy[3], nrow[0], nrow[1], nrow[2], nrow[3]);
+  if (anyhole) {
+    float drow[4];
+    int invalid = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float m[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        m[c] = v[k][c] != 0.f ? 1.f : 0.f;
+        invalid += v[k][c] != 0.f ? 0 : 1;
+      }
+      drow[k] = dot4m_rn(w0, w1, w2, w3, m[0], m[1], m[2], m[3]);
+    }
+    const float D = dot4m_rn(wy[0], wy[1], wy[2], wy[3], drow[0], drow[1], drow[2], drow[3]);
+    bool ok;
+    r = masked_rule(r, D, invalid, &ok);
+  }
+  x[o] = lut[(int)rintf(fminf(fmaxf(r, 0.f), 1.f) * levels)];
+}
+
+int train_crops_lr(const codon_crop_desc* d, const unsigned char* pool, int s, int code_bits, const float* lut, int levels,
+                   const float* lut8, const float* wtab, float* x, float* guide, float* target, hipStream_t stream) {
+  CropLrArgs a;
+  for (int b = 0; b < d->n; ++b) a.s[b] = d->s[b];
+  for (int b = d->n; b < CODON_TRAIN_MAX_BATCH; ++b) a.s[b] = codon_crop_sample{};
+  const int P = d->crop, code16 = code_bits == 16 ? 1 : 0;
+  const dim3 grid((unsigned)((P * P + 255) / 256), (unsigned)d->n);
+#define CODON_LAUNCH_CROPS_LR(S_)                                                                                   \
+  hipLaunchKernelGGL((train_crops_lr_kernel<S_>), grid, dim3(256), 0, stream, a, pool, code16, lut, (float)levels, lut8, wtab, \
+                     x, guide, target, P)
+  if (s == 4) CODON_LAUNCH_CROPS_LR(4);
+  else if (s == 8) CODON_LAUNCH_CROPS_LR(8);
+  else CODON_LAUNCH_CROPS_LR(16);
+#undef CODON_LAUNCH_CROPS_LR
+  return check_launch("train_crops_lr_kernel");
 }
 
 int bicubic_upsample_masked(int B, int h, int w, int s, const float* lr, const float* wtab, float* out, unsigned char* valid,

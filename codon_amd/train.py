@@ -8,6 +8,9 @@ The degradation is a definition of this project, NOT pinned to the reference (it
 numpy in tests/train_data_ref.py and the two agree bit for bit.  --depth-bits 16: depth maps and labels are
 16-bit PNGs of codes 0 .. --depth-max (0 a hole, value = code / depth-max, guidance stays 8-bit); the crop reads u16 planes
 through a 65 536-entry table and the last step quantises onto the data set's own code grid (tests/train_data16_ref.py).
+--train-lr-depth DIR: REAL pairs -- a sensor's low-resolution map per pair, paired by file name; nothing is
+degraded, one launch (codon_train_crops_lr) builds x, y and t, and x is the crop of what `codon_amd.infer --lr-depth` builds from
+the whole low-resolution file, bit for bit (tests/train_lr_ref.py).
 
 One step: GradSync.zero_grad -> synthesize -> forward -> L1SSIMLoss(out.float(), t) (--mask-holes: MaskedL1SSIMLoss, which
 leaves the target's holes -- code 0 -- out of the loss; --train-label: targets from a third directory) -> GradSync.backward ->
@@ -46,6 +49,8 @@ RESUME_DEFAULTS = {"clip_norm": None, "skip_nonfinite": False, "ema": None, "lr_
 DEPTH_DEFAULTS = {"depth_bits": 8, "depth_max": 65535}
 # the same for --degrade-holes: a resume key with default False, written by a run that sets it ONLY
 DEGRADE_DEFAULTS = {"degrade_holes": False}
+# the same for --train-lr-depth: a resume key with default False, written by a run that sets it ONLY
+LR_DEFAULTS = {"train_lr_depth": False}
 MAX_REDRAWS = 64                                    # draw(min_valid=): per sample, before it gives up
 LR_SCHEDULES = ("constant", "cosine")
 
@@ -127,20 +132,37 @@ class TrainSet:
     depth_bits=16 (DESIGN 12.3): depth maps and labels are 16-bit PNGs of codes 0 .. depth_max (0 a hole, v = c / depth_max);
     the pool stays a BYTE pool and pair i's record at the even byte offset offsets[i] is the depth plane (H*W little-endian
     u16), the label plane if there is one (H*W u16), then the u8 guidance; a record of odd length is padded by one byte.  With
-    depth_bits=8 a 16-bit depth or label file is refused (it used to be clipped at 255), with 16 an 8-bit one."""
+    depth_bits=8 a 16-bit depth or label file is refused (it used to be clipped at 255), with 16 an 8-bit one.
+    `lr_dir` with `scale`: real pairs -- every pair has a namesake there, a LOW-RESOLUTION map of codes as a
+    sensor writes it (0 a hole), read through read_depth_plane under the set's bit depth.  Its (h, w) fixes the HR size
+    (h * scale, w * scale), to which depth map and guidance are cropped top-left (a smaller one is refused by name: the rule
+    of `infer --lr-depth`); `sizes` holds the HR sizes.  The depth map is the target and nothing is degraded, so lr_dir
+    excludes label_dir.  The record: 8-bit -- depth, guidance, LR codes (h * w u8); 16-bit -- depth (u16), LR codes (h * w
+    u16), guidance (u8), padded to an even length.  has_lr, lr_scale say so (False, None otherwise)."""
 
     def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None, label_dir: str = None, depth_bits: int = 8,
-                 depth_max: int = 65535):
+                 depth_max: int = 65535, lr_dir: str = None, scale: int = None):
         from .infer import list_pairs
         if depth_bits not in (8, 16):
             raise ValueError(f"TrainSet: depth_bits {depth_bits!r} (8 or 16)")
         check_depth_max(depth_max)
         self.depth_bits, self.depth_max = depth_bits, int(depth_max)
+        self.has_lr, self.lr_scale = lr_dir is not None, None
+        if self.has_lr:
+            if scale not in (4, 8, 16):
+                raise ValueError(f"TrainSet: lr_dir needs scale 4, 8 or 16 (got {scale!r})")
+            if label_dir is not None:
+                raise ValueError("TrainSet: lr_dir and label_dir exclude each other (with low-resolution maps the depth "
+                                 "directory is the target)")
+            self.lr_scale = int(scale)
         self.files = list_pairs(depth_dir, color_dir)
         if not self.files:
             raise ValueError(f"TrainSet: no file of {color_dir} has a namesake in {depth_dir}")
         self.has_label = label_dir is not None
         self.planes = 3 if self.has_label else 2
+        if self.has_lr:
+            self._init_lr(depth_dir, color_dir, device, crop, lr_dir)
+            return
         if depth_bits == 16:
             self._init16(depth_dir, color_dir, device, crop, label_dir)
             return
@@ -181,6 +203,39 @@ class TrainSet:
             sizes.append((h, w))
             off += (2 * len(deep) + 1) * h * w
             if off % 2:                                 # the next record's u16 planes start at an even byte
+                chunks.append(np.zeros(1, dtype=np.uint8))
+                off += 1
+        self.offsets = np.asarray(offsets, dtype=np.int64)
+        self.sizes = np.asarray(sizes, dtype=np.int64)
+        self.pool = torch.from_numpy(np.concatenate(chunks)).to(device)
+        self._integrals = None
+
+    def _init_lr(self, depth_dir, color_dir, device, crop, lr_dir):
+        s, deep = self.lr_scale, self.depth_bits == 16
+        chunks, offsets, sizes, off = [], [], [], 0
+        for f in self.files:
+            if not os.path.isfile(os.path.join(lr_dir, f)):
+                raise ValueError(f"TrainSet: {f} has no namesake in {lr_dir}")
+            lr = read_depth_plane(os.path.join(lr_dir, f), self.depth_bits, self.depth_max)
+            depth = read_depth_plane(os.path.join(depth_dir, f), self.depth_bits, self.depth_max)
+            guide = io.read_gray(os.path.join(color_dir, f))
+            h, w = lr.shape[0] * s, lr.shape[1] * s
+            for d, p in ((depth_dir, depth), (color_dir, guide)):
+                if p.shape[0] < h or p.shape[1] < w:
+                    raise ValueError(f"{os.path.join(d, f)}: {p.shape[0]}x{p.shape[1]}, smaller than the {h}x{w} that "
+                                     f"{os.path.join(lr_dir, f)} gives at x{s}")
+            if crop is not None and (h < crop or w < crop):
+                raise ValueError(f"TrainSet: {f} is {h}x{w}, smaller than the {crop}x{crop} crop")
+            flat = lambda p: np.ascontiguousarray(p).reshape(-1)                                     # noqa: E731
+            wide = lambda p: np.ascontiguousarray(p).astype("<u2").reshape(-1).view(np.uint8)        # noqa: E731
+            if deep:
+                chunks += [wide(depth[:h, :w]), wide(lr), flat(guide[:h, :w])]
+            else:
+                chunks += [flat(depth[:h, :w]), flat(guide[:h, :w]), flat(lr)]
+            offsets.append(off)
+            sizes.append((h, w))
+            off += (3 * h * w + 2 * lr.size) if deep else (2 * h * w + lr.size)
+            if deep and off % 2:                        # the next record's u16 planes start at an even byte
                 chunks.append(np.zeros(1, dtype=np.uint8))
                 off += 1
         self.offsets = np.asarray(offsets, dtype=np.int64)
@@ -270,7 +325,11 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
     codon_bicubic_downsample_masked (whose result is a low-resolution map on the code grid, holes 0.0, as a sensor's file holds
     it) and codon_bicubic_upsample_masked take the place of the down and up launches, the quantise launch follows unchanged:
     four launches still, no host synchronisation; x is bit for bit what infer.codes_to_input builds from that map's codes.
-    return_lr: (x, y, t, lr) with lr the (B,1,crop/scale,crop/scale) low-resolution map."""
+    return_lr: (x, y, t, lr) with lr the (B,1,crop/scale,crop/scale) low-resolution map.
+    A TrainSet with low-resolution maps (lr_dir): ONE launch, codon_train_crops_lr, and none of the others -- t and
+    y are the crop of the depth map and the guidance, x is the window, under the D4 op, of what infer.codes_to_input builds from
+    the WHOLE low-resolution file in fp32.  `scale` must be the set's lr_scale; degrade_holes and return_lr are refused (there
+    is no degradation to mask and no per-crop low-resolution map to return)."""
     lib = L.load()
     B = len(descs)
     if not 1 <= B <= L.TRAIN_MAX_BATCH:
@@ -279,6 +338,13 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
         raise ValueError(f"synthesize: crop {crop} must be a multiple of the scale {scale} and at least 4 * scale")
     if degrade_holes and crop > 1024:
         raise ValueError(f"synthesize: degrade_holes takes crops up to 1024 (crop {crop})")
+    has_lr = getattr(trainset, "has_lr", False)
+    if has_lr:
+        if scale != trainset.lr_scale:
+            raise ValueError(f"synthesize: scale {scale} with a TrainSet of x{trainset.lr_scale} low-resolution maps")
+        if degrade_holes or return_lr:
+            raise ValueError("synthesize: degrade_holes and return_lr do not go with a TrainSet of low-resolution maps "
+                             "(nothing is degraded, and there is no per-crop low-resolution map)")
     dev = trainset.pool.device
     d = L.CropDesc()
     d.n, d.crop = B, crop
@@ -286,11 +352,23 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
         s = d.s[b]
         s.offset, s.height, s.width, s.y0, s.x0, s.op = off, h, w, y0, x0, op
     lut = _on_device("lut", u8_lut, dev)
-    wdown = _on_device(("down", crop, scale), lambda: down_weights(crop, scale), dev)
     wup = _on_device(("up", scale), lambda: phase_weights(scale), dev)
-    p = crop // scale
     t = torch.empty((B, 1, crop, crop), dtype=torch.float32, device=dev)
     y = torch.empty_like(t)
+    if has_lr:
+        deep = trainset.depth_bits == 16
+        top = trainset.depth_max if deep else 255
+        tab = _on_device(("lut16", top), lambda: lut16(top), dev) if deep else lut
+        x = torch.empty_like(t)
+        P_ = C.c_void_p
+        with ops._on(dev):
+            L.check(lib.codon_train_crops_lr(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(), scale,
+                                             trainset.depth_bits, P_(tab.data_ptr()), top, P_(lut.data_ptr()),
+                                             P_(wup.data_ptr()), P_(x.data_ptr()), P_(y.data_ptr()), P_(t.data_ptr()),
+                                             ops._stream(dev)), "train_crops_lr")
+        return x, y, t
+    wdown = _on_device(("down", crop, scale), lambda: down_weights(crop, scale), dev)
+    p = crop // scale
     src = torch.empty_like(t) if trainset.has_label else t        # what the degradation reads
     lr = torch.empty((B, 1, p, p), dtype=torch.float32, device=dev)
     x = torch.empty_like(t)
@@ -374,13 +452,13 @@ def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, 
 
 def load_resume(path: str, args: dict) -> dict:
     """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype, or with
-    other options that change the trajectory (RESUME_KEYS, DEPTH_DEFAULTS' and DEGRADE_DEFAULTS' keys; a key the checkpoint's
-    args lack compares as its default)."""
+    other options that change the trajectory (RESUME_KEYS, DEPTH_DEFAULTS', DEGRADE_DEFAULTS' and LR_DEFAULTS' keys; a key the
+    checkpoint's args lack compares as its default)."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(ck, dict) or not all(k in ck for k in ("epoch", "model", "optimizer", "rng", "args")):
         raise ValueError(f"--resume {path}: not a codon_amd.train checkpoint (use --weights to start from other weights)")
-    absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS}
-    keys = RESUME_KEYS + tuple(DEPTH_DEFAULTS) + tuple(DEGRADE_DEFAULTS)
+    absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS, **LR_DEFAULTS}
+    keys = RESUME_KEYS + tuple(DEPTH_DEFAULTS) + tuple(DEGRADE_DEFAULTS) + tuple(LR_DEFAULTS)
     was, now = ({k: a.get(k, absent.get(k)) for k in keys} for a in (ck["args"], args))
     bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in keys if was[k] != now[k]]
     if bad:
@@ -409,6 +487,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
            valid fraction, computed on the host from the descriptors (no device read);
     min_valid: draw's threshold (needs mask_holes).
     degrade_holes: synthesize's hole-aware degradation; needs no other option.
+    A TrainSet with low-resolution maps (lr_dir) needs no argument here: synthesize reads the real maps, and the
+           checkpoint's args gain train_lr_depth=True.
     Returns {"losses": [(step, loss)], "gs", "opt", "rng", "step", ...}."""
     from .dist import FlatAdam, GradSync
     from .metrics import L1SSIMLoss, MaskedL1SSIMLoss
@@ -441,6 +521,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     args.update(mask_holes=bool(mask_holes), min_valid=float(min_valid), train_label=bool(trainset.has_label))
     if degrade_holes:                               # only then: a checkpoint of a run without it keeps the keys it always had
         args.update(degrade_holes=True)
+    if getattr(trainset, "has_lr", False):          # only then, likewise
+        args.update(train_lr_depth=True)
     if getattr(trainset, "depth_bits", 8) == 16:    # only then: an 8-bit checkpoint keeps the keys it always had
         args.update(depth_bits=16, depth_max=int(trainset.depth_max))
     stream = torch.cuda.current_stream(dev)
@@ -543,6 +625,10 @@ def parse_args(argv=None):
     ap.add_argument("--train-label", default=None,
                     help="targets, paired by file name: the depth maps are then only degraded into inputs (hole-filled depth "
                          "with holey labels, as the reference's data)")
+    ap.add_argument("--train-lr-depth", default=None,
+                    help="real low-resolution depth maps (codes, 0 a hole), paired by file name and --scale times smaller than "
+                         "the pairs they fix the size of: the inputs are built from them as `codon_amd.infer --lr-depth` "
+                         "builds its own, and --train-depth is the target (no synthetic degradation)")
     ap.add_argument("--mask-holes", action="store_true",
                     help="pixels whose target is 0 carry no loss and no gradient (the rule of the printed RMSE)")
     ap.add_argument("--min-valid", type=float, default=0.0,
@@ -597,6 +683,10 @@ def parse_args(argv=None):
         ap.error("--val-depth and --val-lr-depth exclude each other")
     if (a.val_depth is None and a.val_lr_depth is None) != (a.val_color is None):
         ap.error("--val-depth (or --val-lr-depth) and --val-color go together")
+    if a.train_lr_depth is not None and a.train_label is not None:
+        ap.error("--train-lr-depth and --train-label exclude each other (with low-resolution maps --train-depth is the target)")
+    if a.train_lr_depth is not None and a.degrade_holes:
+        ap.error("--train-lr-depth and --degrade-holes exclude each other (nothing is degraded)")
     if a.degrade_holes and a.crop > 1024:
         ap.error(f"--degrade-holes takes crops up to 1024 (--crop {a.crop})")
     if not 0.0 <= a.min_valid <= 1.0:
@@ -633,7 +723,8 @@ def run_args(a) -> dict:
             "clip_norm": a.clip_norm, "skip_nonfinite": a.skip_nonfinite, "ema": a.ema, "lr_schedule": a.lr_schedule,
             "warmup_steps": a.warmup_steps, "lr_min": a.lr_min, "lr_steps": a.lr_steps, "mask_holes": bool(a.mask_holes),
             "min_valid": float(a.min_valid), "train_label": a.train_label is not None,
-            **({"degrade_holes": True} if a.degrade_holes else {})}
+            **({"degrade_holes": True} if a.degrade_holes else {}),
+            **({"train_lr_depth": True} if a.train_lr_depth is not None else {})}
 
 
 def main(argv=None, emit=print) -> dict:
@@ -655,7 +746,7 @@ def main(argv=None, emit=print) -> dict:
     if a.batch // world > L.TRAIN_MAX_BATCH:
         raise SystemExit(f"--batch {a.batch}: at most {L.TRAIN_MAX_BATCH} images per rank")
     ts = TrainSet(a.train_depth, a.train_color, dev, crop=a.crop, label_dir=a.train_label, depth_bits=a.depth_bits,
-                  depth_max=a.depth_max)
+                  depth_max=a.depth_max, **({"lr_dir": a.train_lr_depth, "scale": a.scale} if a.train_lr_depth else {}))
     torch.manual_seed(a.seed)
     model = (CODONNet16 if a.scale == 16 else CODONNet)()
     rng = np.random.default_rng(a.seed)

@@ -694,6 +694,21 @@ int codon_bicubic_downsample_masked(int32_t batch, int32_t size, int32_t scale, 
 int codon_lr_codes_to_input(int32_t batch, int32_t lr_height, int32_t lr_width, int32_t scale, const void* codes,
                             int32_t code_bits, const float* lut, int32_t depth_max, const float* phase_weights, void* out,
                             int32_t dtype, codon_stream_t stream);
+/* codon_train_crops_lr: a whole training batch -- x, guide, target, (n,1,P,P) fp32 each -- from records that PAIR an HR depth
+ * map with a sensor's low-resolution code plane, one launch in place of the synthetic path's four.  Descriptor,
+ * window and D4 op are codon_train_crops'; height x width is the HR size (H, W), both multiples of scale (4 / 8 / 16), and the
+ * LR plane is (h, w) = (H / scale, W / scale).  The record at s[b].offset:
+ *   code_bits 8  (depth_max 255, lut = lut8 = the 256-entry table): depth H*W u8, guidance H*W u8, LR codes h*w u8;
+ *   code_bits 16 (lut = lut16 of depth_max, 65 536 entries):        depth H*W little-endian u16 at an EVEN offset, LR codes
+ *                h*w u16, guidance H*W u8; the pool 2-byte aligned.
+ * With (gy, gx) the source pixel of an output pixel under the window and the op:  target = lut[depth[gy][gx]],
+ * guide = lut8[guidance[gy][gx]], and x = the value codon_lr_codes_to_input (dtype fp32) gives at HR pixel (gy, gx) of the
+ * WHOLE LR plane -- the border clamp is at the image's edge, not the window's, and y0 / x0 need not be multiples of the scale:
+ * x is the window, under the D4 op, of what inference builds from the whole file.  Every window inside its image, every
+ * record inside the pool. */
+int codon_train_crops_lr(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, int32_t scale, int32_t code_bits,
+                         const float* lut, int32_t depth_max, const float* lut8, const float* phase_weights, float* x,
+                         float* guide, float* target, codon_stream_t stream);
 
 #ifdef __cplusplus
 }
