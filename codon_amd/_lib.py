@@ -167,6 +167,8 @@ SIGNATURES = {
     "codon_bicubic_downsample_masked": (C.c_int, [_I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "codon_lr_codes_to_input": (C.c_int, [_I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P]),
     "codon_train_crops_lr": (C.c_int, [C.POINTER(CropDesc), _P, C.c_int64, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "codon_d4_views": (C.c_int, [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "codon_d4_merge": (C.c_int, [_I, _I, _I, _P, _P, _I, _P, _P]),
     "codon_weight_checksum_workspace_bytes": (_S, []),
     "codon_weight_checksum": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P]),
     "codon_weight_checksum_clear": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P, _I, _P]),

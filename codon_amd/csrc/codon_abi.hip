@@ -134,6 +134,8 @@ int bicubic_downsample_masked(int, int, int, const float*, const float*, const f
 int lr_codes_to_input(int, int, int, int, const void*, int, const float*, int, const float*, void*, int, hipStream_t);
 int train_crops_lr(const codon_crop_desc*, const unsigned char*, int, int, const float*, int, const float*, const float*, float*,
                    float*, float*, hipStream_t);
+int d4_views(int, int, int, const void*, const void*, int, void*, void*, void*, void*, hipStream_t);
+int d4_merge(int, int, int, const void*, const void*, int, float*, hipStream_t);
 size_t weight_checksum_workspace_bytes();
 int weight_checksum(const codon_wsum_desc*, void*, unsigned long long*, int, int*, int*, int, hipStream_t);
 
@@ -1029,6 +1031,26 @@ int codon_train_crops_lr(const codon_crop_desc* desc, const uint8_t* pool, int64
                   (long long)pool_bytes);
   }
   return train_crops_lr(desc, pool, scale, code_bits, lut, depth_max, lut8, phase_weights, x, guide, target, (hipStream_t)stream);
+}
+
+int codon_d4_views(int32_t batch, int32_t height, int32_t width, const void* src0, const void* src1, int32_t dtype,
+                   void* upright0, void* transposed0, void* upright1, void* transposed1, codon_stream_t stream) {
+  CODON_REQUIRE(src0 && upright0 && transposed0, CODON_ERR_BAD_ARG, "d4_views: null pointer");
+  CODON_REQUIRE(src1 ? (upright1 && transposed1) : (!upright1 && !transposed1), CODON_ERR_BAD_ARG,
+                "d4_views: src1, upright1 and transposed1 go together (all three, or all three NULL)");
+  CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "d4_views: bad shape %dx%dx%d", batch, height, width);
+  CODON_REQUIRE(dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16, CODON_ERR_BAD_ARG, "d4_views: dtype %d", dtype);
+  CODON_REQUIRE(batch <= 32767, CODON_ERR_UNSUPPORTED, "d4_views: batch %d (at most 32767 images per launch)", batch);
+  return d4_views(batch, height, width, src0, src1, dtype, upright0, transposed0, upright1, transposed1, (hipStream_t)stream);
+}
+
+int codon_d4_merge(int32_t batch, int32_t height, int32_t width, const void* upright, const void* transposed, int32_t dtype,
+                   float* out_f32, codon_stream_t stream) {
+  CODON_REQUIRE(upright && transposed && out_f32, CODON_ERR_BAD_ARG, "d4_merge: null pointer");
+  CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "d4_merge: bad shape %dx%dx%d", batch, height, width);
+  CODON_REQUIRE(dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16, CODON_ERR_BAD_ARG, "d4_merge: dtype %d", dtype);
+  CODON_REQUIRE(batch <= 32767, CODON_ERR_UNSUPPORTED, "d4_merge: batch %d (at most 32767 images per launch)", batch);
+  return d4_merge(batch, height, width, upright, transposed, dtype, out_f32, (hipStream_t)stream);
 }
 
 size_t codon_weight_checksum_workspace_bytes(void) { return weight_checksum_workspace_bytes(); }

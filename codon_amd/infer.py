@@ -151,12 +151,14 @@ def _pinned_copy(t: torch.Tensor) -> torch.Tensor:
 
 
 def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None,
-             depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None):
+             depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None, self_ensemble=False):
     """The test loop over every image pair.  Returns {"n", "rmse_mean", "ssim_mean", "seconds", "images_per_s"}.
     depth_bits=16: 16-bit depth and label files with codes 0 .. depth_max, outputs through metrics.postprocess_u16 into 16-bit
     PNGs, RMSE (metrics.masked_rmse_u16) in codes times depth_unit, SSIM of label / depth_max against out / depth_max.
     lr_depth (with scale; instead of input_depth): a directory of LOW-RESOLUTION depth maps, code 0 a hole -- the
-    reader uploads the codes, and the main stream turns them into the depth input with codes_to_input ahead of the forward."""
+    reader uploads the codes, and the main stream turns them into the depth input with codes_to_input ahead of the forward.
+    self_ensemble: the forward of both loops becomes ensemble.self_ensemble(model, x, y) -- the mean over the eight
+    D4 views, fp32 whatever the model's dtype -- and post-processing takes that fp32 map."""
     if (lr_depth is None) == (input_depth is None):
         raise ValueError("run_loop: exactly one of input_depth and lr_depth")
     if lr_depth is not None and scale not in (4, 8, 16):
@@ -181,6 +183,11 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     else:
         load = lambda f: _load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max)             # noqa: E731
         to_x = lambda x: x                                                                                     # noqa: E731
+    if self_ensemble:
+        from .ensemble import self_ensemble as _ensemble
+        forward = lambda x, y: _ensemble(model, x, y)                                                          # noqa: E731
+    else:
+        forward = model
     t0 = time.perf_counter()
     rm_sum = ss_sum = 0.0
     n = 0
@@ -202,7 +209,7 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
         for f in files:
             x, y, lab, h, w = load(f)
             with torch.no_grad():
-                out = model(to_x(x.to(dev)), y.to(dev))
+                out = forward(to_x(x.to(dev)), y.to(dev))
             out_u8, line = finish(f, out, lab.to(dev) if lab is not None else None, h, w)
             if out_dir:
                 write(os.path.join(out_dir, f), out_u8.cpu().numpy())
@@ -279,7 +286,7 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                 for t in devs:
                     t.record_stream(main_s)                        # allocated on the upload stream, consumed on this one
                 with torch.no_grad():
-                    out = model(to_x(devs[0]), devs[1])
+                    out = forward(to_x(devs[0]), devs[1])
                 out_u8 = post(out[0, 0])
                 h_acc = h_ss = None
                 if len(devs) > 2:                                  # metrics stay on the device; read back one image later
@@ -335,6 +342,11 @@ def main(argv=None):
                     help="the reference script runs .half(); fp16 and bf16 carry 11 and 8 significant bits, so f32 is the "
                          "sensible choice for 16-bit data (--depth-bits 16)")
     ap.add_argument("--ema", action="store_true", help="load the EMA weights of a codon_amd.train --ema checkpoint")
+    ap.add_argument("--self-ensemble", action="store_true",
+                    help="geometric self-ensemble: run the network on the eight flips and rotations of every pair (two forwards of "
+                         "four views each), undo each on the output and average -- eight forwards' worth of convolution per "
+                         "image.  The mean is fp32 whatever --dtype is, so an f16 or bf16 run now post-processes an fp32 map "
+                         "(clip, scale and truncate in fp32) where it otherwise post-processes the 16-bit output itself")
     ap.add_argument("--serial", action="store_true", help="the reference's own serial loop (decode, upload, forward, download, "
                                                           "encode one after the other per image) instead of the pipeline")
     ap.add_argument("--depth-bits", type=int, default=8, choices=[8, 16],
@@ -366,6 +378,7 @@ def main(argv=None):
         os.makedirs(a.out, exist_ok=True)
     r = run_loop(model, dev, tdt, a.input_depth, a.input_color, a.label, a.out, pipelined=not a.serial,
                  depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit,
+                 **({"self_ensemble": True} if a.self_ensemble else {}),
                  **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}))
     print(r["n"])
     if a.label and r["n"]:

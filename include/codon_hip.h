@@ -710,6 +710,24 @@ int codon_train_crops_lr(const codon_crop_desc* desc, const uint8_t* pool, int64
                          const float* lut, int32_t depth_max, const float* lut8, const float* phase_weights, float* x,
                          float* guide, float* target, codon_stream_t stream);
 
+/* ---- D4 self-ensemble (codon_amd.ensemble.self_ensemble) ---------------------------------------------------
+ * No reference counterpart: DEFINITIONS, in codon_amd/csrc/d4.hip, restated in numpy in tests/d4_ref.py, equal bits required.
+ * The D4 code is codon_crop_sample.op's, on a whole (H, W) plane c:  op&1: c = c.T;  then op&2: c = c[::-1];  then op&4:
+ * c = c[:, ::-1].  Codes 0, 2, 4, 6 stay H x W ("upright"), codes 1, 3, 5, 7 are W x H ("transposed"); view k of image b is
+ * image 4*b + (k >> 1) of its batch.  dtype: a codon_dtype, the element type of every plane but out_f32.
+ *
+ * codon_d4_views: ONE launch copies the bits of src0 (batch,1,H,W) into upright0 (4*batch,1,H,W) and transposed0
+ * (4*batch,1,W,H), and the same from src1 into upright1 / transposed1; src1, upright1 and transposed1 may all three be NULL
+ * (one plane only).  No arithmetic: NaN payloads and -0.0 arrive as they left.
+ *
+ * codon_d4_merge: ONE launch, out_f32[b] = 0.125f * (((u0+u1)+(u2+u3)) + ((u4+u5)+(u6+u7))), u_k the inverse of view k (undo
+ * op&4, then op&2, then transpose if op&1) of the network's output on that view, upcast exactly to fp32, every add rounded
+ * on its own in this order -- eight equal values average to themselves.  out_f32: (batch,1,H,W), ALWAYS fp32.  No atomics. */
+int codon_d4_views(int32_t batch, int32_t height, int32_t width, const void* src0, const void* src1, int32_t dtype,
+                   void* upright0, void* transposed0, void* upright1, void* transposed1, codon_stream_t stream);
+int codon_d4_merge(int32_t batch, int32_t height, int32_t width, const void* upright, const void* transposed, int32_t dtype,
+                   float* out_f32, codon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
