@@ -6,6 +6,7 @@
 
 #include "codon_common.h"
 #include "pair.h"
+#include "train_record.h"
 
 namespace codon {
 
@@ -123,11 +124,9 @@ size_t grad_norm_workspace_bytes();
 int grad_norm(const float*, long, void*, hipStream_t);
 int adam_step_guarded(const codon_adam_desc*, const float*, float*, float*, float*, void*, float, float, float, float, float, int,
                       double, int, double, hipStream_t);
-int train_crops(const codon_crop_desc*, const unsigned char*, const float*, float*, float*, hipStream_t);
-int train_crops_labeled(const codon_crop_desc*, const unsigned char*, const float*, float*, float*, float*, hipStream_t);
+int train_crops(const codon_crop_desc*, const unsigned char*, int, const float*, const float*, float*, float*, float*,
+                hipStream_t);
 int bicubic_downsample(int, int, int, const float*, const float*, float*, hipStream_t);
-int quantize_u8(long, float*, const float*, hipStream_t);
-int train_crops_u16(const codon_crop_desc*, const unsigned char*, const float*, const float*, float*, float*, float*, hipStream_t);
 int quantize_levels(long, float*, const float*, int, hipStream_t);
 int bicubic_upsample_masked(int, int, int, int, const float*, const float*, float*, unsigned char*, hipStream_t);
 int bicubic_downsample_masked(int, int, int, const float*, const float*, const float*, int, float*, hipStream_t);
@@ -145,6 +144,34 @@ PairRecorder* pair_recorder() { return g_pair.active ? &g_pair : nullptr; }
 static bool slice_ok(const codon_tensor* t) { return t && t->data && t->coff >= 0 && t->coff + 64 <= t->ctotal; }
 
 static bool shape_ok(int b, int h, int w) { return b > 0 && h > 0 && w > 0 && (long)h * w < (1L << 31); }
+
+// The descriptor of a codon_train_crops* entry `name` against a pool of records of one layout (train_record.h): the batch,
+// the crop, and per sample the window inside its image and the whole record inside the pool.  lr_scale != 0: the image
+// sizes are multiples of it.  Nothing is launched before every sample has passed.
+static int check_crop_desc(const char* name, const codon_crop_desc* desc, int64_t pool_bytes, int bits, bool label,
+                           int lr_scale) {
+  CODON_REQUIRE(desc->n >= 1 && desc->n <= CODON_TRAIN_MAX_BATCH, CODON_ERR_BAD_ARG, "%s: batch %d (1..%d)", name, desc->n,
+                CODON_TRAIN_MAX_BATCH);
+  const int P = desc->crop;
+  CODON_REQUIRE(P >= 1 && P <= 2048, CODON_ERR_BAD_ARG, "%s: crop %d (1..2048)", name, P);
+  for (int b = 0; b < desc->n; ++b) {
+    const codon_crop_sample& c = desc->s[b];
+    CODON_REQUIRE(lr_scale == 0 || (c.height >= 1 && c.width >= 1 && c.height % lr_scale == 0 && c.width % lr_scale == 0),
+                  CODON_ERR_BAD_ARG, "%s: sample %d: %dx%d is no multiple of the scale %d", name, b, c.height, c.width,
+                  lr_scale);
+    CODON_REQUIRE(c.height >= P && c.width >= P && c.y0 >= 0 && c.x0 >= 0 && c.y0 <= c.height - P && c.x0 <= c.width - P &&
+                      c.op >= 0 && c.op <= 7,
+                  CODON_ERR_BAD_ARG, "%s: sample %d: %dx%d crop at (%d, %d) op %d outside the image", name, b, c.height,
+                  c.width, c.y0, c.x0, c.op);
+    CODON_REQUIRE(c.offset >= 0 && (bits == 8 || c.offset % 2 == 0), CODON_ERR_BAD_ARG,
+                  "%s: sample %d: offset %lld is negative, or odd (u16 planes start at even bytes)", name, b,
+                  (long long)c.offset);
+    CODON_REQUIRE(c.offset <= pool_bytes - record_layout(bits, label, lr_scale, c.height, c.width).size, CODON_ERR_BAD_ARG,
+                  "%s: sample %d: the record at offset %lld runs past the %lld-byte pool", name, b, (long long)c.offset,
+                  (long long)pool_bytes);
+  }
+  return CODON_OK;
+}
 
 }  // namespace codon
 
@@ -877,41 +904,15 @@ int codon_bicubic_upsample(int32_t batch, int32_t lr_height, int32_t lr_width, i
 int codon_train_crops(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, const float* lut, float* target,
                       float* guide, codon_stream_t stream) {
   CODON_REQUIRE(desc && pool && lut && target && guide, CODON_ERR_BAD_ARG, "train_crops: null pointer");
-  CODON_REQUIRE(desc->n >= 1 && desc->n <= CODON_TRAIN_MAX_BATCH, CODON_ERR_BAD_ARG, "train_crops: batch %d (1..%d)", desc->n,
-                CODON_TRAIN_MAX_BATCH);
-  const int P = desc->crop;
-  CODON_REQUIRE(P >= 1 && P <= 2048, CODON_ERR_BAD_ARG, "train_crops: crop %d (1..2048)", P);
-  for (int b = 0; b < desc->n; ++b) {
-    const codon_crop_sample& c = desc->s[b];
-    CODON_REQUIRE(c.height >= P && c.width >= P && c.y0 >= 0 && c.x0 >= 0 && c.y0 <= c.height - P && c.x0 <= c.width - P &&
-                      c.op >= 0 && c.op <= 7,
-                  CODON_ERR_BAD_ARG, "train_crops: sample %d: %dx%d crop at (%d, %d) op %d outside the image", b, c.height,
-                  c.width, c.y0, c.x0, c.op);
-    CODON_REQUIRE(c.offset >= 0 && c.offset <= pool_bytes - 2 * (int64_t)c.height * c.width, CODON_ERR_BAD_ARG,
-                  "train_crops: sample %d: images at offset %lld run past the %lld-byte pool", b, (long long)c.offset,
-                  (long long)pool_bytes);
-  }
-  return train_crops(desc, pool, lut, target, guide, (hipStream_t)stream);
+  if (const int st = check_crop_desc("train_crops", desc, pool_bytes, 8, false, 0)) return st;
+  return train_crops(desc, pool, 8, lut, lut, target, guide, nullptr, (hipStream_t)stream);
 }
 
 int codon_train_crops_labeled(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, const float* lut,
                               float* source, float* guide, float* target, codon_stream_t stream) {
   CODON_REQUIRE(desc && pool && lut && source && guide && target, CODON_ERR_BAD_ARG, "train_crops_labeled: null pointer");
-  CODON_REQUIRE(desc->n >= 1 && desc->n <= CODON_TRAIN_MAX_BATCH, CODON_ERR_BAD_ARG, "train_crops_labeled: batch %d (1..%d)",
-                desc->n, CODON_TRAIN_MAX_BATCH);
-  const int P = desc->crop;
-  CODON_REQUIRE(P >= 1 && P <= 2048, CODON_ERR_BAD_ARG, "train_crops_labeled: crop %d (1..2048)", P);
-  for (int b = 0; b < desc->n; ++b) {
-    const codon_crop_sample& c = desc->s[b];
-    CODON_REQUIRE(c.height >= P && c.width >= P && c.y0 >= 0 && c.x0 >= 0 && c.y0 <= c.height - P && c.x0 <= c.width - P &&
-                      c.op >= 0 && c.op <= 7,
-                  CODON_ERR_BAD_ARG, "train_crops_labeled: sample %d: %dx%d crop at (%d, %d) op %d outside the image", b,
-                  c.height, c.width, c.y0, c.x0, c.op);
-    CODON_REQUIRE(c.offset >= 0 && c.offset <= pool_bytes - 3 * (int64_t)c.height * c.width, CODON_ERR_BAD_ARG,
-                  "train_crops_labeled: sample %d: images at offset %lld run past the %lld-byte pool", b, (long long)c.offset,
-                  (long long)pool_bytes);
-  }
-  return train_crops_labeled(desc, pool, lut, source, guide, target, (hipStream_t)stream);
+  if (const int st = check_crop_desc("train_crops_labeled", desc, pool_bytes, 8, true, 0)) return st;
+  return train_crops(desc, pool, 8, lut, lut, source, guide, target, (hipStream_t)stream);
 }
 
 int codon_bicubic_downsample(int32_t batch, int32_t size, int32_t scale, const float* hr, const float* weights, float* out,
@@ -925,32 +926,15 @@ int codon_bicubic_downsample(int32_t batch, int32_t size, int32_t scale, const f
 
 int codon_quantize_u8(int64_t n, float* x, const float* lut, codon_stream_t stream) {
   CODON_REQUIRE(x && lut && n >= 1, CODON_ERR_BAD_ARG, "quantize_u8: null pointer or empty");
-  return quantize_u8((long)n, x, lut, (hipStream_t)stream);
+  return quantize_levels((long)n, x, lut, 255, (hipStream_t)stream);
 }
 
 int codon_train_crops_u16(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, const float* lut16,
                           const float* lut8, float* source, float* guide, float* target, codon_stream_t stream) {
   CODON_REQUIRE(desc && pool && lut16 && lut8 && source && guide, CODON_ERR_BAD_ARG, "train_crops_u16: null pointer");
   CODON_REQUIRE(((uintptr_t)pool & 1) == 0, CODON_ERR_BAD_ARG, "train_crops_u16: the pool is not 2-byte aligned");
-  CODON_REQUIRE(desc->n >= 1 && desc->n <= CODON_TRAIN_MAX_BATCH, CODON_ERR_BAD_ARG, "train_crops_u16: batch %d (1..%d)", desc->n,
-                CODON_TRAIN_MAX_BATCH);
-  const int P = desc->crop;
-  CODON_REQUIRE(P >= 1 && P <= 2048, CODON_ERR_BAD_ARG, "train_crops_u16: crop %d (1..2048)", P);
-  const int64_t per_pixel = target ? 5 : 3;              // u16 depth (+ u16 label) + u8 guidance
-  for (int b = 0; b < desc->n; ++b) {
-    const codon_crop_sample& c = desc->s[b];
-    CODON_REQUIRE(c.height >= P && c.width >= P && c.y0 >= 0 && c.x0 >= 0 && c.y0 <= c.height - P && c.x0 <= c.width - P &&
-                      c.op >= 0 && c.op <= 7,
-                  CODON_ERR_BAD_ARG, "train_crops_u16: sample %d: %dx%d crop at (%d, %d) op %d outside the image", b, c.height,
-                  c.width, c.y0, c.x0, c.op);
-    CODON_REQUIRE(c.offset >= 0 && c.offset % 2 == 0, CODON_ERR_BAD_ARG,
-                  "train_crops_u16: sample %d: offset %lld is odd or negative (u16 planes start at even bytes)", b,
-                  (long long)c.offset);
-    CODON_REQUIRE(c.offset <= pool_bytes - per_pixel * (int64_t)c.height * c.width, CODON_ERR_BAD_ARG,
-                  "train_crops_u16: sample %d: images at offset %lld run past the %lld-byte pool", b, (long long)c.offset,
-                  (long long)pool_bytes);
-  }
-  return train_crops_u16(desc, pool, lut16, lut8, source, guide, target, (hipStream_t)stream);
+  if (const int st = check_crop_desc("train_crops_u16", desc, pool_bytes, 16, target != nullptr, 0)) return st;
+  return train_crops(desc, pool, 16, lut16, lut8, source, guide, target, (hipStream_t)stream);
 }
 
 int codon_quantize_levels(int64_t n, float* x, const float* lut16, int32_t depth_max, codon_stream_t stream) {
@@ -1004,32 +988,12 @@ int codon_train_crops_lr(const codon_crop_desc* desc, const uint8_t* pool, int64
                          float* guide, float* target, codon_stream_t stream) {
   CODON_REQUIRE(desc && pool && lut && lut8 && phase_weights && x && guide && target, CODON_ERR_BAD_ARG,
                 "train_crops_lr: null pointer");
-  CODON_REQUIRE(desc->n >= 1 && desc->n <= CODON_TRAIN_MAX_BATCH, CODON_ERR_BAD_ARG, "train_crops_lr: batch %d (1..%d)", desc->n,
-                CODON_TRAIN_MAX_BATCH);
   CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "train_crops_lr: scale %d", scale);
   CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "train_crops_lr: code_bits %d (8 or 16)", code_bits);
   CODON_REQUIRE(code_bits == 16 ? (depth_max >= 1 && depth_max <= 65535) : depth_max == 255, CODON_ERR_BAD_ARG,
                 "train_crops_lr: depth_max %d (255 for 8-bit codes, 1..65535 for 16-bit codes)", depth_max);
   CODON_REQUIRE(code_bits == 8 || ((uintptr_t)pool & 1) == 0, CODON_ERR_BAD_ARG, "train_crops_lr: the pool is not 2-byte aligned");
-  const int P = desc->crop;
-  CODON_REQUIRE(P >= 1 && P <= 2048, CODON_ERR_BAD_ARG, "train_crops_lr: crop %d (1..2048)", P);
-  for (int b = 0; b < desc->n; ++b) {
-    const codon_crop_sample& c = desc->s[b];
-    CODON_REQUIRE(c.height >= 1 && c.width >= 1 && c.height % scale == 0 && c.width % scale == 0, CODON_ERR_BAD_ARG,
-                  "train_crops_lr: sample %d: %dx%d is no multiple of the scale %d", b, c.height, c.width, scale);
-    CODON_REQUIRE(c.height >= P && c.width >= P && c.y0 >= 0 && c.x0 >= 0 && c.y0 <= c.height - P && c.x0 <= c.width - P &&
-                      c.op >= 0 && c.op <= 7,
-                  CODON_ERR_BAD_ARG, "train_crops_lr: sample %d: %dx%d crop at (%d, %d) op %d outside the image", b, c.height,
-                  c.width, c.y0, c.x0, c.op);
-    CODON_REQUIRE(c.offset >= 0 && (code_bits == 8 || c.offset % 2 == 0), CODON_ERR_BAD_ARG,
-                  "train_crops_lr: sample %d: offset %lld is negative, or odd (u16 planes start at even bytes)", b,
-                  (long long)c.offset);
-    const int64_t hw = (int64_t)c.height * c.width, lhw = hw / ((int64_t)scale * scale);
-    const int64_t record = code_bits == 16 ? 3 * hw + 2 * lhw : 2 * hw + lhw;
-    CODON_REQUIRE(c.offset <= pool_bytes - record, CODON_ERR_BAD_ARG,
-                  "train_crops_lr: sample %d: the record at offset %lld runs past the %lld-byte pool", b, (long long)c.offset,
-                  (long long)pool_bytes);
-  }
+  if (const int st = check_crop_desc("train_crops_lr", desc, pool_bytes, code_bits, false, scale)) return st;
   return train_crops_lr(desc, pool, scale, code_bits, lut, depth_max, lut8, phase_weights, x, guide, target, (hipStream_t)stream);
 }
 

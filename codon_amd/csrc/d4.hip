@@ -4,7 +4,7 @@
 // the views only copy bits; the merge upcasts exactly to fp32 and adds in a fixed tree,
 //   out = 0.125f * (((u0+u1)+(u2+u3)) + ((u4+u5)+(u6+u7))),   u_k the inverse of view k of the network output,
 // every add rounded on its own (built with -ffp-contract=off, like upsample.hip), so that eight equal values average to
-// themselves exactly.  The D4 code is train_data.hip's; the index arithmetic and the layout of the two view batches are in
+// themselves exactly.  The D4 code is train_record.h's (crop_pixel); the index arithmetic and the layout of the two view batches are in
 // d4_tile.h, shared with the host-side sanitizer check.
 //
 // Both kernels are HBM-bound permutations.  One workgroup of 256 threads owns a 32 x 32 tile; the transposed half goes through

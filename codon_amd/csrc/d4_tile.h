@@ -4,7 +4,7 @@
 // kernel is two phases with a workgroup barrier between them, and the tile in LDS is what turns the transposed views' column
 // walk into row walks on both sides of the copy.
 //
-// The D4 code is train_data.hip's, on the whole plane c (H, W):  op&1: c = c.T; then op&2: c = c[::-1]; then op&4: c = c[:, ::-1].
+// The D4 code is train_record.h's (crop_pixel), on the whole plane c (H, W):  op&1: c = c.T; then op&2: c = c[::-1]; then op&4: c = c[:, ::-1].
 // Codes 0, 2, 4, 6 ("upright", H x W) sit at slot s = op >> 1 of the upright batch, codes 1, 3, 5, 7 ("transposed", W x H) at
 // slot s of the transposed batch; in both  fr = s & 1  flips rows and  fc = s & 2  flips columns:
 //   upright    view s:  v[i][j] = c[fr ? H-1-i : i][fc ? W-1-j : j]

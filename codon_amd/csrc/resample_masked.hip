@@ -20,28 +20,62 @@
 //             weight 0 and is not counted).  A valid value is snapped as a sensor's file would hold it:
 //             code = min(max((int)rintf(clamp(v, 0, 1) * levels), 1), levels), out = lut[code] -- never code 0.
 // fused:      codes (u8 / u16) -> lut -> upsample rule -> lut[(int)rintf(clamp(., 0, 1) * levels)] -> round to nearest even
-//             into fp32 / fp16 / bf16: bicubic_masked_kernel, quantize_u8_kernel / quantize_levels_kernel and a cast, fused.
+//             into fp32 / fp16 / bf16: bicubic_masked_kernel, quantize_levels_kernel and a cast, fused.
 // paired:     a training batch from records that carry a sensor's low-resolution code plane: t and y are the crop
 //             kernels' look-ups, x is the fused kernel's fp32 value at the source pixel of the WHOLE plane -- the window, under
 //             the D4 op, of what inference builds from the file.  Restated in numpy in tests/train_lr_ref.py.
 
 #include <hip/hip_fp16.h>
 
-#include "codon_common.h"
+#include "dot4_rn.h"
+#include "train_record.h"
 
 #pragma clang fp contract(off)
 
 namespace codon {
-
-__device__ __forceinline__ float dot4m_rn(float w0, float w1, float w2, float w3, float p0, float p1, float p2, float p3) {
-  return __fadd_rn(__fadd_rn(__fmul_rn(w0, p0), __fmul_rn(w1, p1)), __fadd_rn(__fmul_rn(w2, p2), __fmul_rn(w3, p3)));
-}
 
 __device__ __forceinline__ float masked_rule(float N, float D, int invalid, bool* ok) {
   if (invalid == 0) { *ok = true; return N; }
   if (D >= 0.5f) { *ok = true; return N / D; }
   *ok = false;
   return 0.f;
+}
+
+// The upsample rule for one output pixel whose taps are looked up already: v is a register window of 4 tap rows of which the
+// pixel reads columns o .. o + 3 (o a constant once the caller's loop is unrolled, so the window is indexed by constants only
+// and stays in registers), wx and wy the weight rows of its phases.  Rows then columns for the numerator; the denominator,
+// the count and the rule only where one of the 16 taps is a hole -- with none the rule gives the numerator's bits.
+template <int NW>
+__device__ __forceinline__ float bicubic4x4_masked(const float (&v)[4][NW], int o, const float* __restrict__ wx,
+                                                   const float* __restrict__ wy, bool* ok) {
+  const float w0 = wx[0], w1 = wx[1], w2 = wx[2], w3 = wx[3];
+  float nrow[4];
+  bool anyhole = false;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    nrow[k] = dot4_rn(w0, w1, w2, w3, v[k][o], v[k][o + 1], v[k][o + 2], v[k][o + 3]);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) anyhole = anyhole || !(v[k][o + c] != 0.f);
+  }
+  float r = dot4_rn(wy[0], wy[1], wy[2], wy[3], nrow[0], nrow[1], nrow[2], nrow[3]);
+  *ok = true;
+  if (anyhole) {
+    float drow[4];
+    int invalid = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float m[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        m[c] = v[k][o + c] != 0.f ? 1.f : 0.f;
+        invalid += v[k][o + c] != 0.f ? 0 : 1;
+      }
+      drow[k] = dot4_rn(w0, w1, w2, w3, m[0], m[1], m[2], m[3]);
+    }
+    const float D = dot4_rn(wy[0], wy[1], wy[2], wy[3], drow[0], drow[1], drow[2], drow[3]);
+    r = masked_rule(r, D, invalid, ok);
+  }
+  return r;
 }
 
 // one thread per output pixel, as bicubic_kernel
@@ -66,25 +100,15 @@ __global__ __launch_bounds__(256) void bicubic_masked_kernel(const float* __rest
     ys[k] = min(max(iy0 - 1 + k, 0), h - 1);
   }
   const float* p = lr + (long)b * h * w;
-  float nrow[4], drow[4];
-  int invalid = 0;
+  float v[4][4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float* r = p + (long)ys[k] * w;
-    float v[4], m[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      v[c] = r[xs[c]];
-      m[c] = v[c] != 0.f ? 1.f : 0.f;
-      invalid += v[c] != 0.f ? 0 : 1;
-    }
-    nrow[k] = dot4m_rn(wx[0], wx[1], wx[2], wx[3], v[0], v[1], v[2], v[3]);
-    drow[k] = dot4m_rn(wx[0], wx[1], wx[2], wx[3], m[0], m[1], m[2], m[3]);
+    for (int c = 0; c < 4; ++c) v[k][c] = r[xs[c]];
   }
-  const float N = dot4m_rn(wy[0], wy[1], wy[2], wy[3], nrow[0], nrow[1], nrow[2], nrow[3]);
-  const float D = dot4m_rn(wy[0], wy[1], wy[2], wy[3], drow[0], drow[1], drow[2], drow[3]);
   bool ok;
-  out[idx] = masked_rule(N, D, invalid, &ok);
+  out[idx] = bicubic4x4_masked(v, 0, wx, wy, &ok);
   if (valid != nullptr) valid[idx] = ok ? 1 : 0;
 }
 
@@ -179,7 +203,6 @@ __global__ __launch_bounds__(256) void lr_codes_to_input_kernel(const void* __re
   const float* wy = wtab + ry * 4;
   const long plane = (long)b * h * w;
   float v[4][NW];
-  bool anyhole = false;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const long row = plane + (long)min(max(iy0 - 1 + k, 0), h - 1) * w;
@@ -189,37 +212,13 @@ __global__ __launch_bounds__(256) void lr_codes_to_input_kernel(const void* __re
       const int code = code16 ? (int)static_cast<const unsigned short*>(codes)[at]
                               : (int)static_cast<const unsigned char*>(codes)[at];
       v[k][c] = lut[code];
-      anyhole = anyhole || !(v[k][c] != 0.f);
     }
   }
   float res[R];
 #pragma unroll
   for (int j = 0; j < R; ++j) {
-    const int o = Sh::off(j);                            // a constant once the loop is unrolled
-    const int rx = (gx0 + j) % S;
-    const float* wx = wtab + rx * 4;
-    const float w0 = wx[0], w1 = wx[1], w2 = wx[2], w3 = wx[3];
-    float nrow[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) nrow[k] = dot4m_rn(w0, w1, w2, w3, v[k][o], v[k][o + 1], v[k][o + 2], v[k][o + 3]);
-    float r = dot4m_rn(wy[0], wy[1], wy[2], wy[3], nrow[0], nrow[1], nrow[2], nrow[3]);
-    if (anyhole) {                                       // rare: the denominator and the count only where the window has a hole
-      float drow[4];
-      int invalid = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float m[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          m[c] = v[k][o + c] != 0.f ? 1.f : 0.f;
-          invalid += v[k][o + c] != 0.f ? 0 : 1;
-        }
-        drow[k] = dot4m_rn(w0, w1, w2, w3, m[0], m[1], m[2], m[3]);
-      }
-      const float D = dot4m_rn(wy[0], wy[1], wy[2], wy[3], drow[0], drow[1], drow[2], drow[3]);
-      bool ok;
-      r = masked_rule(r, D, invalid, &ok);
-    }
+    bool ok;
+    const float r = bicubic4x4_masked(v, Sh::off(j), wtab + (gx0 + j) % S * 4, wy, &ok);
     res[j] = lut[(int)rintf(fminf(fmaxf(r, 0.f), 1.f) * levels)];
   }
   const long at = run * R;
@@ -244,20 +243,13 @@ __global__ __launch_bounds__(256) void lr_codes_to_input_kernel(const void* __re
 }
 
 // ---- paired training: records with a low-resolution code plane -> x, y, t -------------------------------------
-// grid (ceil(P*P / 256), B), one thread per output pixel of one sample, window and D4 op as train_crops_kernel.  The record
-// at byte `offset` of the pool:   8-bit: depth H*W u8 | guidance H*W u8 | LR codes h*w u8
-//                                16-bit: depth H*W u16 | LR codes h*w u16 | guidance H*W u8       (h, w) = (H / S, W / S)
-// so the LR plane starts at byte 2*H*W of either record.  t and y are the crop kernels' table look-ups at the source pixel
+// grid (ceil(P*P / 256), B), one thread per output pixel of one sample; window, D4 op and record layout are train_record.h's
+// ((h, w) = (H / S, W / S) is the LR plane's size).  t and y are the crop kernels' table look-ups at the source pixel
 // (gy, gx); x is what lr_codes_to_input_kernel writes at (gy, gx) of the WHOLE plane in fp32: bicubic_masked_kernel's index
-// arithmetic with the border clamp at the image's edge (the window's real neighbours are read), lut[code] for the 16 taps, rows
-// then columns, the rule, back onto the code grid.  The denominator and the count only where one of the 16 taps is a hole.
-struct CropLrArgs {
-  codon_crop_sample s[CODON_TRAIN_MAX_BATCH];
-};
-static_assert(sizeof(CropLrArgs) + 96 <= CODON_KERNARG_LIMIT, "passed by value as a kernel argument");
-
+// arithmetic with the border clamp at the image's edge (the window's real neighbours are read), lut[code] for the 16 taps, the
+// rule, back onto the code grid.
 template <int S>
-__global__ __launch_bounds__(256) void train_crops_lr_kernel(const CropLrArgs a, const unsigned char* __restrict__ pool,
+__global__ __launch_bounds__(256) void train_crops_lr_kernel(const CropArgs a, const unsigned char* __restrict__ pool,
                                                              int code16, const float* __restrict__ lut, float levels,
                                                              const float* __restrict__ lut8, const float* __restrict__ wtab,
                                                              float* __restrict__ x, float* __restrict__ guide,
@@ -265,75 +257,35 @@ __global__ __launch_bounds__(256) void train_crops_lr_kernel(const CropLrArgs a,
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= P * P) return;
   const codon_crop_sample d = a.s[blockIdx.y];
-  const int i = idx / P, j = idx - i * P;
-  int si = i, sj = j;
-  if (d.op & 4) sj = P - 1 - sj;
-  if (d.op & 2) si = P - 1 - si;
-  if (d.op & 1) { const int t = si; si = sj; sj = t; }
-  const int gy = d.y0 + si, gx = d.x0 + sj;
+  const CropPixel cp = crop_pixel(idx, d, P);
+  const int gy = cp.gy, gx = cp.gx;
   const int h = d.height / S, w = d.width / S;
-  const long hw = (long)d.height * d.width;
-  const long px = (long)gy * d.width + gx;
+  const RecordLayout rl = record_layout(code16 ? 16 : 8, false, S, d.height, d.width);
   const unsigned char* rec = pool + d.offset;            // even for u16 records (ABI check)
-  const unsigned char* lr8 = rec + 2 * hw;
-  const unsigned short* lr16 = reinterpret_cast<const unsigned short*>(lr8);
-  const long o = (long)blockIdx.y * P * P + idx;
-  if (code16) {
-    target[o] = lut[reinterpret_cast<const unsigned short*>(rec)[px]];
-    guide[o] = lut8[rec[2 * hw + 2 * (long)h * w + px]];
-  } else {
-    target[o] = lut[rec[px]];
-    guide[o] = lut8[rec[hw + px]];
-  }
+  const unsigned char* lrp = rec + rl.lr;
+  const long px = (long)gy * d.width + gx;
+  target[cp.out] = lut[code16 ? record_code<16>(rec + rl.depth, px) : record_code<8>(rec + rl.depth, px)];
+  guide[cp.out] = lut8[rec[rl.guide + px]];
   const int qx = gx / S, rx = gx - qx * S, qy = gy / S, ry = gy - qy * S;
   const int ix0 = qx - ((2 * rx + 1 < S) ? 1 : 0), iy0 = qy - ((2 * ry + 1 < S) ? 1 : 0);
-  const float* wx = wtab + rx * 4;
-  const float* wy = wtab + ry * 4;
-  const float w0 = wx[0], w1 = wx[1], w2 = wx[2], w3 = wx[3];
   int xs[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) xs[c] = min(max(ix0 - 1 + c, 0), w - 1);
   float v[4][4];
-  bool anyhole = false;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const long row = (long)min(max(iy0 - 1 + k, 0), h - 1) * w;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int code = code16 ? (int)lr16[row + xs[c]] : (int)lr8[row + xs[c]];
-      v[k][c] = lut[code];
-      anyhole = anyhole || !(v[k][c] != 0.f);
-    }
+    for (int c = 0; c < 4; ++c) v[k][c] = lut[code16 ? record_code<16>(lrp, row + xs[c]) : record_code<8>(lrp, row + xs[c])];
   }
-  float nrow[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) nrow[k] = dot4m_rn(w0, w1, w2, w3, v[k][0], v[k][1], v[k][2], v[k][3]);
-  float r = dot4m_rn(wy[0], wy[1], wy[2], wy[3], nrow[0], nrow[1], nrow[2], nrow[3]);
-  if (anyhole) {
-    float drow[4];
-    int invalid = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float m[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        m[c] = v[k][c] != 0.f ? 1.f : 0.f;
-        invalid += v[k][c] != 0.f ? 0 : 1;
-      }
-      drow[k] = dot4m_rn(w0, w1, w2, w3, m[0], m[1], m[2], m[3]);
-    }
-    const float D = dot4m_rn(wy[0], wy[1], wy[2], wy[3], drow[0], drow[1], drow[2], drow[3]);
-    bool ok;
-    r = masked_rule(r, D, invalid, &ok);
-  }
-  x[o] = lut[(int)rintf(fminf(fmaxf(r, 0.f), 1.f) * levels)];
+  bool ok;
+  const float r = bicubic4x4_masked(v, 0, wtab + rx * 4, wtab + ry * 4, &ok);
+  x[cp.out] = lut[(int)rintf(fminf(fmaxf(r, 0.f), 1.f) * levels)];
 }
 
 int train_crops_lr(const codon_crop_desc* d, const unsigned char* pool, int s, int code_bits, const float* lut, int levels,
                    const float* lut8, const float* wtab, float* x, float* guide, float* target, hipStream_t stream) {
-  CropLrArgs a;
-  for (int b = 0; b < d->n; ++b) a.s[b] = d->s[b];
-  for (int b = d->n; b < CODON_TRAIN_MAX_BATCH; ++b) a.s[b] = codon_crop_sample{};
+  const CropArgs a = pack_crop_args(d);
   const int P = d->crop, code16 = code_bits == 16 ? 1 : 0;
   const dim3 grid((unsigned)((P * P + 255) / 256), (unsigned)d->n);
 #define CODON_LAUNCH_CROPS_LR(S_)                                                                                   \

@@ -12,17 +12,12 @@
 // every operation individually rounded (no FMA contraction) so that numpy reproduces it exactly.
 
 #include "codon_common.h"
+#include "dot4_rn.h"
 
-// HIP's __fmul_rn/__fadd_rn are plain * and + and would be contracted into v_fma under the default
-// -ffp-contract=fast; this file must round every operation separately.
+// this file must round every operation separately (dot4_rn.h)
 #pragma clang fp contract(off)
 
 namespace codon {
-
-__device__ __forceinline__ float dot4_rn(float w0, float w1, float w2, float w3, float p0, float p1, float p2,
-                                         float p3) {
-  return __fadd_rn(__fadd_rn(__fmul_rn(w0, p0), __fmul_rn(w1, p1)), __fadd_rn(__fmul_rn(w2, p2), __fmul_rn(w3, p3)));
-}
 
 __global__ __launch_bounds__(256) void bicubic_kernel(const float* __restrict__ lr, const float* __restrict__ wtab,
                                                       float* __restrict__ out, int h, int w, int s, long total) {

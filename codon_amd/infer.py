@@ -28,30 +28,32 @@ import numpy as np
 import torch
 
 from . import CODONNet, CODONNet16, io, metrics
-
-
-def list_pairs(input_depth: str, input_color: str):
-    return [f for f in sorted(os.listdir(input_color)) if os.path.exists(os.path.join(input_depth, f))]
+from .io import check_depth_max, list_pairs, read_depth_plane
+from .upsample import _on_device, code_table, phase_weights
 
 
 def _load_host(a_depth, a_color, a_label, f, tdt, depth_bits=8, depth_max=65535):
     """Host side of one image: decode, grey, /255 (float64 divide, then float32: test.py:116-123), crop both to the common
     size, cast to the model's dtype (the rounding `.cuda().half()` does on the device, done here on half the bytes).
-    depth_bits=16: depth and label are 16-bit codes (train.read_depth_plane: an 8-bit file or a code above
+    depth_bits=16: depth and label are 16-bit codes (io.read_depth_plane: an 8-bit file or a code above
     depth_max is refused), the depth input is float32(float64(c) / depth_max) before the same cast, the label is returned as
     an int16 view of its u16 bits; the guidance stays 8-bit.  depth_bits=8 refuses a 16-bit depth or label file."""
     # numpy only (single-threaded): torch's CPU ops fan a 170 k-element conversion out over every host core, which costs
     # milliseconds per call on a 128-core box; the values are io.to_input()'s -- float64 divide, float32, then the dtype's
     # round-to-nearest-even -- bit for bit
-    from .train import read_depth_plane
     px = read_depth_plane(os.path.join(a_depth, f), depth_bits, depth_max)
     py = io.read_gray(os.path.join(a_color, f))
     h, w = min(px.shape[0], py.shape[0]), min(px.shape[1], py.shape[1])
     lab = None
     if a_label:
-        lab = read_depth_plane(os.path.join(a_label, f), depth_bits, depth_max).copy()
-        lab = torch.from_numpy(lab.view(np.int16) if depth_bits == 16 else lab)
+        lab = _codes(read_depth_plane(os.path.join(a_label, f), depth_bits, depth_max))
     return _plane(px[:h, :w], depth_max if depth_bits == 16 else 255, tdt), _plane(py[:h, :w], 255, tdt), lab, h, w
+
+
+def _codes(a):
+    """A host tensor of a writable, contiguous copy of a code plane: uint8, or the bits of u16 codes as int16."""
+    a = np.array(a)
+    return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a)
 
 
 def _plane(p_, top, tdt):
@@ -68,10 +70,9 @@ def _plane(p_, top, tdt):
 
 def _load_host_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits=8, depth_max=65535):
     """Host side of one image under --lr-depth: the depth file is a LOW-RESOLUTION map of codes (0 a hole), read
-    through train.read_depth_plane and returned AS CODES -- (h,w) uint8, or the u16 bits as int16 -- for codes_to_input; the
+    through io.read_depth_plane and returned AS CODES -- (h,w) uint8, or the u16 bits as int16 -- for codes_to_input; the
     HR size is (h * scale, w * scale), and the guidance and the label are cropped top-left to it.  A smaller guidance or label
     raises ValueError naming the file."""
-    from .train import read_depth_plane
     px = read_depth_plane(os.path.join(a_lr, f), depth_bits, depth_max)
     py = io.read_gray(os.path.join(a_color, f))
     h, w = px.shape[0] * scale, px.shape[1] * scale
@@ -84,11 +85,8 @@ def _load_host_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits=8, depth_max
         if lab.shape[0] < h or lab.shape[1] < w:
             raise ValueError(f"{os.path.join(a_label, f)}: {lab.shape[0]}x{lab.shape[1]}, smaller than the {h}x{w} that "
                              f"{os.path.join(a_lr, f)} gives at x{scale}")
-        lab = np.array(lab[:h, :w])                # a writable, contiguous copy of the crop
-        lab = torch.from_numpy(lab.view(np.int16) if depth_bits == 16 else lab)
-    px = np.array(px)
-    codes = torch.from_numpy(px.view(np.int16) if depth_bits == 16 else px)
-    return codes, _plane(py[:h, :w], 255, tdt), lab, h, w
+        lab = _codes(lab[:h, :w])
+    return _codes(px), _plane(py[:h, :w], 255, tdt), lab, h, w
 
 
 def codes_to_input(codes: torch.Tensor, scale: int, tdt, depth_max: int = None) -> torch.Tensor:
@@ -99,8 +97,6 @@ def codes_to_input(codes: torch.Tensor, scale: int, tdt, depth_max: int = None) 
     low-resolution values."""
     from . import _lib as L
     from . import ops
-    from .train import _on_device, check_depth_max, lut16, u8_lut
-    from .upsample import phase_weights
     import ctypes as C
     if codes.dim() == 2:
         codes = codes[None]
@@ -116,17 +112,17 @@ def codes_to_input(codes: torch.Tensor, scale: int, tdt, depth_max: int = None) 
     if codes.dtype == torch.uint8:
         if depth_max not in (None, 255):
             raise ValueError(f"codes_to_input: depth_max {depth_max!r} with 8-bit codes")
-        bits, top, lut = 8, 255, _on_device("lut", u8_lut, dev)
+        bits = 8
     else:
-        top = 65535 if depth_max is None else depth_max
-        check_depth_max(top)
-        bits, lut = 16, _on_device(("lut16", int(top)), lambda: lut16(int(top)), dev)
+        bits, depth_max = 16, 65535 if depth_max is None else depth_max
+        check_depth_max(depth_max)
+    lut, top = code_table(bits, depth_max, dev)
     wt = _on_device(("up", scale), lambda: phase_weights(scale), dev)
     B, h, w = codes.shape
     out = torch.empty((B, 1, h * scale, w * scale), dtype=tdt, device=dev)
     P_ = C.c_void_p
     with ops._on(dev):
-        L.check(lib.codon_lr_codes_to_input(B, h, w, scale, P_(codes.data_ptr()), bits, P_(lut.data_ptr()), int(top),
+        L.check(lib.codon_lr_codes_to_input(B, h, w, scale, P_(codes.data_ptr()), bits, P_(lut.data_ptr()), top,
                                             P_(wt.data_ptr()), P_(out.data_ptr()), _ABI_DTYPE[tdt], ops._stream(dev)),
                 "lr_codes_to_input")
     return out
@@ -168,7 +164,6 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
         raise ValueError(f"run_loop: depth_bits {depth_bits!r} (8 or 16)")
     deep = depth_bits == 16
     if deep:
-        from .train import check_depth_max
         check_depth_max(depth_max)
         post = lambda o: metrics.postprocess_u16(o, depth_max)                                   # noqa: E731
         sqerr, write, top = metrics.masked_sqerr_u16_dev, io.write_depth16, float(depth_max)

@@ -48,6 +48,33 @@ def write_depth16(path: str, arr_u16: np.ndarray):
     Image.frombytes("I;16", (a.shape[1], a.shape[0]), a.astype("<u2").tobytes()).save(path)
 
 
+def check_depth_max(depth_max):
+    if not isinstance(depth_max, (int, np.integer)) or not 1 <= depth_max <= 65535:
+        raise ValueError(f"depth_max {depth_max!r} must be an integer in [1, 65535]")
+
+
+def read_depth_plane(path: str, depth_bits: int, depth_max: int = 65535) -> np.ndarray:
+    """One depth map or label under the data set's bit depth: 8 -> read_gray's uint8, and a 16-bit file is
+    REFUSED (convert("L") would clip it at 255 without a word); 16 -> uint16 codes, an 8-bit file refused (no mixing) and so
+    is a code above depth_max.  Every ValueError names the file."""
+    a = read_depth(path)
+    if depth_bits == 8:
+        if a.dtype != np.uint8:
+            raise ValueError(f"{path}: a 16-bit image (codes up to {int(a.max())}) in an 8-bit data set; it would be clipped at "
+                             "255 -- pass --depth-bits 16 (and --depth-max)")
+        return a
+    if a.dtype != np.uint16:
+        raise ValueError(f"{path}: an 8-bit image in a 16-bit data set (--depth-bits 16): depth maps and labels must all be "
+                         "16-bit")
+    if a.size and int(a.max()) > depth_max:
+        raise ValueError(f"{path}: code {int(a.max())} lies above depth_max {depth_max}")
+    return a
+
+
+def list_pairs(input_depth: str, input_color: str):
+    return [f for f in sorted(os.listdir(input_color)) if os.path.exists(os.path.join(input_depth, f))]
+
+
 def to_input(pic_u8: np.ndarray) -> torch.Tensor:
     """torch.from_numpy(pic / 255).float().unsqueeze(0).unsqueeze(0)   (float64 divide, then float32)."""
     return torch.from_numpy(np.asarray(pic_u8) / 255).float().unsqueeze(0).unsqueeze(0)

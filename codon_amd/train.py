@@ -25,7 +25,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import functools
 import math
 import os
 import time
@@ -36,7 +35,9 @@ import torch
 from . import CODONNet, CODONNet16, io
 from . import _lib as L
 from . import ops
-from .upsample import _keys, phase_weights
+from .infer import run_loop
+from .io import check_depth_max, list_pairs, read_depth_plane
+from .upsample import _on_device, code_table, down_weights, lut16, phase_weights, u8_lut      # noqa: F401 (lut16: for importers)
 
 DTYPES = {"bf16": torch.bfloat16, "f32": None}
 RESUME_KEYS = ("scale", "crop", "batch", "dtype", "clip_norm", "skip_nonfinite", "ema", "lr_schedule", "warmup_steps", "lr_min",
@@ -55,94 +56,38 @@ MAX_REDRAWS = 64                                    # draw(min_valid=): per samp
 LR_SCHEDULES = ("constant", "cosine")
 
 
-# ---- the degradation's host-side tables -------------------------------------------------------------------------------------
-
-def u8_lut() -> np.ndarray:
-    """256 fp32 values: io.to_input's conversion of every code (float64 divide by 255, then float32)."""
-    return (np.arange(256, dtype=np.float64) / 255).astype(np.float32)
-
-
-def lut16(depth_max: int = 65535) -> np.ndarray:
-    """65 536 fp32 values: code c of a 16-bit depth map as float32(float64(c) / depth_max) -- u8_lut's conversion on the data
-    set's own scale (lut16(65535)[257 * k] == u8_lut()[k] bit for bit).  Codes above depth_max are refused at load time; their
-    entries exist only so that no u16 indexes out of the table."""
-    check_depth_max(depth_max)
-    return (np.arange(65536, dtype=np.float64) / depth_max).astype(np.float32)
-
-
-def check_depth_max(depth_max):
-    if not isinstance(depth_max, (int, np.integer)) or not 1 <= depth_max <= 65535:
-        raise ValueError(f"depth_max {depth_max!r} must be an integer in [1, 65535]")
-
-
-def read_depth_plane(path: str, depth_bits: int, depth_max: int = 65535) -> np.ndarray:
-    """One depth map or label under the data set's bit depth: 8 -> io.read_gray's uint8, and a 16-bit file is
-    REFUSED (convert("L") would clip it at 255 without a word); 16 -> uint16 codes, an 8-bit file refused (no mixing) and so
-    is a code above depth_max.  Every ValueError names the file."""
-    a = io.read_depth(path)
-    if depth_bits == 8:
-        if a.dtype != np.uint8:
-            raise ValueError(f"{path}: a 16-bit image (codes up to {int(a.max())}) in an 8-bit data set; it would be clipped at "
-                             "255 -- pass --depth-bits 16 (and --depth-max)")
-        return a
-    if a.dtype != np.uint16:
-        raise ValueError(f"{path}: an 8-bit image in a 16-bit data set (--depth-bits 16): depth maps and labels must all be "
-                         "16-bit")
-    if a.size and int(a.max()) > depth_max:
-        raise ValueError(f"{path}: code {int(a.max())} lies above depth_max {depth_max}")
-    return a
-
-
-@functools.lru_cache(maxsize=None)
-def down_weights(size: int, scale: int) -> np.ndarray:
-    """(size/scale, 4*scale) fp32: row o weighs input taps i = o*scale - 3*scale/2 + k (PIL's BICUBIC reduce: Keys a = -0.5
-    stretched by scale, centre (o + 0.5) * scale, tap weight k((i + 0.5 - centre) / scale); taps outside [0, size) get 0 and
-    the rest are renormalised).  fp64, rounded once to fp32."""
-    p, taps = size // scale, 4 * scale
-    tab = np.zeros((p, taps), dtype=np.float64)
-    for o in range(p):
-        c = (o + 0.5) * scale
-        for k in range(taps):
-            i = o * scale - 3 * scale // 2 + k
-            if 0 <= i < size:
-                tab[o, k] = _keys((i + 0.5 - c) / scale, a=-0.5)
-        tab[o] /= tab[o].sum()
-    return tab.astype(np.float32)
-
-
-_dev_tabs: dict = {}
-
-
-def _on_device(key, make, dev):
-    k = (key, str(dev))
-    t = _dev_tabs.get(k)
-    if t is None:
-        t = _dev_tabs[k] = torch.from_numpy(np.ascontiguousarray(make())).to(dev)
-    return t
-
-
 # ---- the dataset --------------------------------------------------------------------------------------------------------------
 
+def record_layout(bits: int, label: bool, lr_scale: int, h: int, w: int) -> dict:
+    """Where the planes of one pool record sit, as byte offsets from its start, and the bytes they take ("size"): the mirror
+    of record_layout in csrc/train_record.h (the six layouts are tabled in DESIGN 12.3).  The depth plane (h*w codes of
+    `bits` bits) comes first; the label plane (h*w codes) or the low-resolution plane ((h/lr_scale)*(w/lr_scale) codes; 0: none)
+    -- never both -- starts at byte 2*h*w; the guidance is h*w u8, second in an 8-bit record and last in a 16-bit one.  u16
+    planes are little-endian and start at even bytes: the pool pads a 16-bit record of odd size by a byte "size" leaves out."""
+    hw = h * w
+    extra = (hw if label else 0) + ((h // lr_scale) * (w // lr_scale) if lr_scale else 0)
+    if bits == 16:
+        return {"depth": 0, "guide": 2 * hw + 2 * extra, "label": 2 * hw, "lr": 2 * hw, "size": 3 * hw + 2 * extra}
+    return {"depth": 0, "guide": hw, "label": 2 * hw, "lr": 2 * hw, "size": 2 * hw + extra}
+
+
 class TrainSet:
-    """Every (depth, guidance) pair of two directories, paired by file name (infer.list_pairs), read with io.read_gray and
-    cropped to their common size (as infer._load_host does), in ONE flat uint8 pool on `device`: pair i's depth map at
-    offsets[i], its guidance right behind it.  Uploaded once; a step reads nothing from the host.  `crop`: refuse images
-    smaller than it.  `label_dir`: a third plane per pair, the label (the target, which may carry holes coded 0 that the depth
-    map -- the degradation's source -- has filled in), behind the guidance; every pair needs a namesake there.
+    """Every (depth, guidance) pair of two directories, paired by file name (io.list_pairs), read with io.read_depth_plane and
+    io.read_gray and cropped to their common size (as infer._load_host does), in ONE flat uint8 pool on `device`: pair i's
+    record at offsets[i], its planes where record_layout says.  Uploaded once; a step reads nothing from the host.  `crop`:
+    refuse images smaller than it.  `label_dir`: a third plane per pair, the label (the target, which may carry holes coded 0
+    that the depth map -- the degradation's source -- has filled in); every pair needs a namesake there.
     depth_bits=16 (DESIGN 12.3): depth maps and labels are 16-bit PNGs of codes 0 .. depth_max (0 a hole, v = c / depth_max);
-    the pool stays a BYTE pool and pair i's record at the even byte offset offsets[i] is the depth plane (H*W little-endian
-    u16), the label plane if there is one (H*W u16), then the u8 guidance; a record of odd length is padded by one byte.  With
-    depth_bits=8 a 16-bit depth or label file is refused (it used to be clipped at 255), with 16 an 8-bit one.
+    the pool stays a BYTE pool of records at even offsets.  With depth_bits=8 a 16-bit depth or label file is refused (it used
+    to be clipped at 255), with 16 an 8-bit one.
     `lr_dir` with `scale`: real pairs -- every pair has a namesake there, a LOW-RESOLUTION map of codes as a
     sensor writes it (0 a hole), read through read_depth_plane under the set's bit depth.  Its (h, w) fixes the HR size
     (h * scale, w * scale), to which depth map and guidance are cropped top-left (a smaller one is refused by name: the rule
     of `infer --lr-depth`); `sizes` holds the HR sizes.  The depth map is the target and nothing is degraded, so lr_dir
-    excludes label_dir.  The record: 8-bit -- depth, guidance, LR codes (h * w u8); 16-bit -- depth (u16), LR codes (h * w
-    u16), guidance (u8), padded to an even length.  has_lr, lr_scale say so (False, None otherwise)."""
+    excludes label_dir.  has_lr, lr_scale say so (False, None otherwise)."""
 
     def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None, label_dir: str = None, depth_bits: int = 8,
                  depth_max: int = 65535, lr_dir: str = None, scale: int = None):
-        from .infer import list_pairs
         if depth_bits not in (8, 16):
             raise ValueError(f"TrainSet: depth_bits {depth_bits!r} (8 or 16)")
         check_depth_max(depth_max)
@@ -160,84 +105,40 @@ class TrainSet:
             raise ValueError(f"TrainSet: no file of {color_dir} has a namesake in {depth_dir}")
         self.has_label = label_dir is not None
         self.planes = 3 if self.has_label else 2
-        if self.has_lr:
-            self._init_lr(depth_dir, color_dir, device, crop, lr_dir)
-            return
-        if depth_bits == 16:
-            self._init16(depth_dir, color_dir, device, crop, label_dir)
-            return
+        deep = depth_bits == 16
         chunks, offsets, sizes, off = [], [], [], 0
         for f in self.files:
-            planes = [read_depth_plane(os.path.join(depth_dir, f), 8), io.read_gray(os.path.join(color_dir, f))]
-            if self.has_label:
-                if not os.path.isfile(os.path.join(label_dir, f)):
-                    raise ValueError(f"TrainSet: {f} has no namesake in {label_dir}")
-                planes.append(read_depth_plane(os.path.join(label_dir, f), 8))
-            h, w = min(p.shape[0] for p in planes), min(p.shape[1] for p in planes)
+            planes = {}
+            for name, d in (("lr", lr_dir), ("depth", depth_dir), ("label", label_dir)):
+                if d is None:
+                    continue
+                if name != "depth" and not os.path.isfile(os.path.join(d, f)):
+                    raise ValueError(f"TrainSet: {f} has no namesake in {d}")
+                planes[name] = read_depth_plane(os.path.join(d, f), depth_bits, self.depth_max)
+            planes["guide"] = io.read_gray(os.path.join(color_dir, f))
+            lr = planes.pop("lr", None)
+            if lr is None:
+                h, w = min(p.shape[0] for p in planes.values()), min(p.shape[1] for p in planes.values())
+            else:                                       # the low-resolution map fixes the size
+                h, w = lr.shape[0] * self.lr_scale, lr.shape[1] * self.lr_scale
+                for d, p in ((depth_dir, planes["depth"]), (color_dir, planes["guide"])):
+                    if p.shape[0] < h or p.shape[1] < w:
+                        raise ValueError(f"{os.path.join(d, f)}: {p.shape[0]}x{p.shape[1]}, smaller than the {h}x{w} that "
+                                         f"{os.path.join(lr_dir, f)} gives at x{self.lr_scale}")
             if crop is not None and (h < crop or w < crop):
                 raise ValueError(f"TrainSet: {f} is {h}x{w}, smaller than the {crop}x{crop} crop")
-            chunks += [np.ascontiguousarray(p[:h, :w]).reshape(-1) for p in planes]
+            planes = {name: p[:h, :w] for name, p in planes.items()}
+            if lr is not None:
+                planes["lr"] = lr
+            lay = record_layout(depth_bits, self.has_label, self.lr_scale or 0, h, w)
+            rec = np.zeros(lay["size"] + (lay["size"] % 2 if deep else 0), dtype=np.uint8)      # the next u16 record starts even
+            for name, p in planes.items():
+                raw = np.ascontiguousarray(p).astype("<u2" if deep and name != "guide" else np.uint8).reshape(-1).view(np.uint8)
+                rec[lay[name]:lay[name] + raw.size] = raw
+            chunks.append(rec)
             offsets.append(off)
             sizes.append((h, w))
-            off += self.planes * h * w
-        self.offsets = np.asarray(offsets, dtype=np.int64)
-        self.sizes = np.asarray(sizes, dtype=np.int64)
-        self.pool = torch.from_numpy(np.concatenate(chunks)).to(device)
-        self._integrals = None
-
-    def _init16(self, depth_dir, color_dir, device, crop, label_dir):
-        chunks, offsets, sizes, off = [], [], [], 0
-        for f in self.files:
-            deep = [read_depth_plane(os.path.join(depth_dir, f), 16, self.depth_max)]
-            if self.has_label:
-                if not os.path.isfile(os.path.join(label_dir, f)):
-                    raise ValueError(f"TrainSet: {f} has no namesake in {label_dir}")
-                deep.append(read_depth_plane(os.path.join(label_dir, f), 16, self.depth_max))
-            guide = io.read_gray(os.path.join(color_dir, f))
-            h, w = min(p.shape[0] for p in deep + [guide]), min(p.shape[1] for p in deep + [guide])
-            if crop is not None and (h < crop or w < crop):
-                raise ValueError(f"TrainSet: {f} is {h}x{w}, smaller than the {crop}x{crop} crop")
-            chunks += [np.ascontiguousarray(p[:h, :w]).astype("<u2").reshape(-1).view(np.uint8) for p in deep]
-            chunks.append(np.ascontiguousarray(guide[:h, :w]).reshape(-1))
-            offsets.append(off)
-            sizes.append((h, w))
-            off += (2 * len(deep) + 1) * h * w
-            if off % 2:                                 # the next record's u16 planes start at an even byte
-                chunks.append(np.zeros(1, dtype=np.uint8))
-                off += 1
-        self.offsets = np.asarray(offsets, dtype=np.int64)
-        self.sizes = np.asarray(sizes, dtype=np.int64)
-        self.pool = torch.from_numpy(np.concatenate(chunks)).to(device)
-        self._integrals = None
-
-    def _init_lr(self, depth_dir, color_dir, device, crop, lr_dir):
-        s, deep = self.lr_scale, self.depth_bits == 16
-        chunks, offsets, sizes, off = [], [], [], 0
-        for f in self.files:
-            if not os.path.isfile(os.path.join(lr_dir, f)):
-                raise ValueError(f"TrainSet: {f} has no namesake in {lr_dir}")
-            lr = read_depth_plane(os.path.join(lr_dir, f), self.depth_bits, self.depth_max)
-            depth = read_depth_plane(os.path.join(depth_dir, f), self.depth_bits, self.depth_max)
-            guide = io.read_gray(os.path.join(color_dir, f))
-            h, w = lr.shape[0] * s, lr.shape[1] * s
-            for d, p in ((depth_dir, depth), (color_dir, guide)):
-                if p.shape[0] < h or p.shape[1] < w:
-                    raise ValueError(f"{os.path.join(d, f)}: {p.shape[0]}x{p.shape[1]}, smaller than the {h}x{w} that "
-                                     f"{os.path.join(lr_dir, f)} gives at x{s}")
-            if crop is not None and (h < crop or w < crop):
-                raise ValueError(f"TrainSet: {f} is {h}x{w}, smaller than the {crop}x{crop} crop")
-            flat = lambda p: np.ascontiguousarray(p).reshape(-1)                                     # noqa: E731
-            wide = lambda p: np.ascontiguousarray(p).astype("<u2").reshape(-1).view(np.uint8)        # noqa: E731
-            if deep:
-                chunks += [wide(depth[:h, :w]), wide(lr), flat(guide[:h, :w])]
-            else:
-                chunks += [flat(depth[:h, :w]), flat(guide[:h, :w]), flat(lr)]
-            offsets.append(off)
-            sizes.append((h, w))
-            off += (3 * h * w + 2 * lr.size) if deep else (2 * h * w + lr.size)
-            if deep and off % 2:                        # the next record's u16 planes start at an even byte
-                chunks.append(np.zeros(1, dtype=np.uint8))
-                off += 1
+            off += rec.size
         self.offsets = np.asarray(offsets, dtype=np.int64)
         self.sizes = np.asarray(sizes, dtype=np.int64)
         self.pool = torch.from_numpy(np.concatenate(chunks)).to(device)
@@ -252,14 +153,11 @@ class TrainSet:
         valid count is then four lookups and no step reads the device for it."""
         if self._integrals is None:
             pool = self.pool.cpu().numpy()
-            plane = 2 if self.has_label else 0
+            wide = self.depth_bits // 8
             self._integrals = {}
             for off, (h, w) in zip(self.offsets.tolist(), self.sizes.tolist()):
-                if self.depth_bits == 16:               # the label follows the depth plane; both are u16
-                    lo = off + (2 * h * w if self.has_label else 0)
-                    v = pool[lo:lo + 2 * h * w].view("<u2").reshape(h, w) != 0
-                else:
-                    v = pool[off + plane * h * w:off + (plane + 1) * h * w].reshape(h, w) != 0
+                lo = off + record_layout(self.depth_bits, self.has_label, 0, h, w)["label" if self.has_label else "depth"]
+                v = pool[lo:lo + wide * h * w].view("<u2" if wide == 2 else np.uint8).reshape(h, w) != 0
                 ii = np.zeros((h + 1, w + 1), dtype=np.int32)
                 ii[1:, 1:] = v.cumsum(0, dtype=np.int32).cumsum(1, dtype=np.int32)
                 self._integrals[off] = ii
@@ -338,8 +236,7 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
         raise ValueError(f"synthesize: crop {crop} must be a multiple of the scale {scale} and at least 4 * scale")
     if degrade_holes and crop > 1024:
         raise ValueError(f"synthesize: degrade_holes takes crops up to 1024 (crop {crop})")
-    has_lr = getattr(trainset, "has_lr", False)
-    if has_lr:
+    if trainset.has_lr:
         if scale != trainset.lr_scale:
             raise ValueError(f"synthesize: scale {scale} with a TrainSet of x{trainset.lr_scale} low-resolution maps")
         if degrade_holes or return_lr:
@@ -351,48 +248,37 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
     for b, (off, h, w, y0, x0, op) in enumerate(np.asarray(descs, dtype=np.int64).tolist()):
         s = d.s[b]
         s.offset, s.height, s.width, s.y0, s.x0, s.op = off, h, w, y0, x0, op
-    lut = _on_device("lut", u8_lut, dev)
+    deep = trainset.depth_bits == 16
+    tab, top = code_table(trainset.depth_bits, trainset.depth_max, dev)      # the depth codes' table (the set's own grid)
+    lut = _on_device("lut", u8_lut, dev)                                     # the guidance's
     wup = _on_device(("up", scale), lambda: phase_weights(scale), dev)
-    t = torch.empty((B, 1, crop, crop), dtype=torch.float32, device=dev)
-    y = torch.empty_like(t)
-    if has_lr:
-        deep = trainset.depth_bits == 16
-        top = trainset.depth_max if deep else 255
-        tab = _on_device(("lut16", top), lambda: lut16(top), dev) if deep else lut
-        x = torch.empty_like(t)
-        P_ = C.c_void_p
-        with ops._on(dev):
-            L.check(lib.codon_train_crops_lr(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(), scale,
-                                             trainset.depth_bits, P_(tab.data_ptr()), top, P_(lut.data_ptr()),
-                                             P_(wup.data_ptr()), P_(x.data_ptr()), P_(y.data_ptr()), P_(t.data_ptr()),
-                                             ops._stream(dev)), "train_crops_lr")
-        return x, y, t
-    wdown = _on_device(("down", crop, scale), lambda: down_weights(crop, scale), dev)
-    p = crop // scale
-    src = torch.empty_like(t) if trainset.has_label else t        # what the degradation reads
-    lr = torch.empty((B, 1, p, p), dtype=torch.float32, device=dev)
-    x = torch.empty_like(t)
     P_ = C.c_void_p
-    deep = getattr(trainset, "depth_bits", 8) == 16
-    if deep:
-        lut_deep = _on_device(("lut16", trainset.depth_max), lambda: lut16(trainset.depth_max), dev)
+    pool = (C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel())
+    t = torch.empty((B, 1, crop, crop), dtype=torch.float32, device=dev)
+    y, x = torch.empty_like(t), torch.empty_like(t)
     with ops._on(dev):
         st = ops._stream(dev)
+        if trainset.has_lr:
+            L.check(lib.codon_train_crops_lr(*pool, scale, trainset.depth_bits, P_(tab.data_ptr()), top, P_(lut.data_ptr()),
+                                             P_(wup.data_ptr()), P_(x.data_ptr()), P_(y.data_ptr()), P_(t.data_ptr()), st),
+                    "train_crops_lr")
+            return x, y, t
+        wdown = _on_device(("down", crop, scale), lambda: down_weights(crop, scale), dev)
+        p = crop // scale
+        src = torch.empty_like(t) if trainset.has_label else t        # what the degradation reads
+        lr = torch.empty((B, 1, p, p), dtype=torch.float32, device=dev)
         if deep:
-            L.check(lib.codon_train_crops_u16(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(),
-                                              P_(lut_deep.data_ptr()), P_(lut.data_ptr()), P_(src.data_ptr()), P_(y.data_ptr()),
-                                              P_(t.data_ptr()) if trainset.has_label else None, st), "train_crops_u16")
+            L.check(lib.codon_train_crops_u16(*pool, P_(tab.data_ptr()), P_(lut.data_ptr()), P_(src.data_ptr()),
+                                              P_(y.data_ptr()), P_(t.data_ptr()) if trainset.has_label else None, st),
+                    "train_crops_u16")
         elif trainset.has_label:
-            L.check(lib.codon_train_crops_labeled(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(),
-                                                  P_(lut.data_ptr()), P_(src.data_ptr()), P_(y.data_ptr()), P_(t.data_ptr()), st),
-                    "train_crops_labeled")
+            L.check(lib.codon_train_crops_labeled(*pool, P_(lut.data_ptr()), P_(src.data_ptr()), P_(y.data_ptr()),
+                                                  P_(t.data_ptr()), st), "train_crops_labeled")
         else:
-            L.check(lib.codon_train_crops(C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel(), P_(lut.data_ptr()),
-                                          P_(t.data_ptr()), P_(y.data_ptr()), st), "train_crops")
+            L.check(lib.codon_train_crops(*pool, P_(lut.data_ptr()), P_(t.data_ptr()), P_(y.data_ptr()), st), "train_crops")
         if degrade_holes:
-            snap, levels = (lut_deep, trainset.depth_max) if deep else (lut, 255)
             L.check(lib.codon_bicubic_downsample_masked(B, crop, scale, P_(src.data_ptr()), P_(wdown.data_ptr()),
-                                                        P_(snap.data_ptr()), levels, P_(lr.data_ptr()), st),
+                                                        P_(tab.data_ptr()), top, P_(lr.data_ptr()), st),
                     "bicubic_downsample_masked")
             L.check(lib.codon_bicubic_upsample_masked(B, p, p, scale, P_(lr.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()),
                                                       None, st), "bicubic_upsample_masked")
@@ -402,10 +288,9 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
             L.check(lib.codon_bicubic_upsample(B, p, p, scale, P_(lr.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()), st),
                     "bicubic_upsample")
         if deep:
-            L.check(lib.codon_quantize_levels(x.numel(), P_(x.data_ptr()), P_(lut_deep.data_ptr()), trainset.depth_max, st),
-                    "quantize_levels")
+            L.check(lib.codon_quantize_levels(x.numel(), P_(x.data_ptr()), P_(tab.data_ptr()), top, st), "quantize_levels")
         else:
-            L.check(lib.codon_quantize_u8(x.numel(), P_(x.data_ptr()), P_(lut.data_ptr()), st), "quantize_u8")
+            L.check(lib.codon_quantize_u8(x.numel(), P_(x.data_ptr()), P_(tab.data_ptr()), st), "quantize_u8")
     return (x, y, t, lr) if return_lr else (x, y, t)
 
 
@@ -521,9 +406,9 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     args.update(mask_holes=bool(mask_holes), min_valid=float(min_valid), train_label=bool(trainset.has_label))
     if degrade_holes:                               # only then: a checkpoint of a run without it keeps the keys it always had
         args.update(degrade_holes=True)
-    if getattr(trainset, "has_lr", False):          # only then, likewise
+    if trainset.has_lr:                             # only then, likewise
         args.update(train_lr_depth=True)
-    if getattr(trainset, "depth_bits", 8) == 16:    # only then: an 8-bit checkpoint keeps the keys it always had
+    if trainset.depth_bits == 16:                   # only then: an 8-bit checkpoint keeps the keys it always had
         args.update(depth_bits=16, depth_max=int(trainset.depth_max))
     stream = torch.cuda.current_stream(dev)
     losses, val_log, ev = [], [], []
@@ -601,7 +486,6 @@ def validate(model, dev, val: dict, emit=print) -> dict:
     """infer.run_loop over the validation set in eval mode at the training compute dtype; prints the mean masked RMSE and
     SSIM (the numbers the reference's test.py prints), then returns the model to train().  val["depth_bits"] == 16: the set
     is read as 16-bit with val["depth_max"], and the RMSE is in codes."""
-    from .infer import run_loop
     model.eval()
     try:
         with torch.no_grad():

@@ -8,6 +8,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .io import check_depth_max
 
 
 def _keys(d, a=-0.75):
@@ -29,6 +30,58 @@ def phase_weights(scale: int) -> np.ndarray:
         t = num / (2.0 * scale)
         tab[r] = [_keys(1.0 + t), _keys(t), _keys(1.0 - t), _keys(2.0 - t)]
     return tab.astype(np.float32)
+
+
+# ---- the host-side tables of the degradation and of the code planes -------------------------------------------------------
+
+def u8_lut() -> np.ndarray:
+    """256 fp32 values: io.to_input's conversion of every code (float64 divide by 255, then float32)."""
+    return (np.arange(256, dtype=np.float64) / 255).astype(np.float32)
+
+
+def lut16(depth_max: int = 65535) -> np.ndarray:
+    """65 536 fp32 values: code c of a 16-bit depth map as float32(float64(c) / depth_max) -- u8_lut's conversion on the data
+    set's own scale (lut16(65535)[257 * k] == u8_lut()[k] bit for bit).  Codes above depth_max are refused at load time; their
+    entries exist only so that no u16 indexes out of the table."""
+    check_depth_max(depth_max)
+    return (np.arange(65536, dtype=np.float64) / depth_max).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def down_weights(size: int, scale: int) -> np.ndarray:
+    """(size/scale, 4*scale) fp32: row o weighs input taps i = o*scale - 3*scale/2 + k (PIL's BICUBIC reduce: Keys a = -0.5
+    stretched by scale, centre (o + 0.5) * scale, tap weight k((i + 0.5 - centre) / scale); taps outside [0, size) get 0 and
+    the rest are renormalised).  fp64, rounded once to fp32."""
+    p, taps = size // scale, 4 * scale
+    tab = np.zeros((p, taps), dtype=np.float64)
+    for o in range(p):
+        c = (o + 0.5) * scale
+        for k in range(taps):
+            i = o * scale - 3 * scale // 2 + k
+            if 0 <= i < size:
+                tab[o, k] = _keys((i + 0.5 - c) / scale, a=-0.5)
+        tab[o] /= tab[o].sum()
+    return tab.astype(np.float32)
+
+
+_dev_tabs: dict = {}
+
+
+def _on_device(key, make, dev):
+    k = (key, str(dev))
+    t = _dev_tabs.get(k)
+    if t is None:
+        t = _dev_tabs[k] = torch.from_numpy(np.ascontiguousarray(make())).to(dev)
+    return t
+
+
+def code_table(depth_bits: int, depth_max: int, dev):
+    """(table, top) on `dev` for codes of depth_bits bits: value = table[code], and top is the code of 1.0 -- u8_lut and 255,
+    or lut16(depth_max) and depth_max."""
+    if depth_bits == 16:
+        top = int(depth_max)
+        return _on_device(("lut16", top), lambda: lut16(top), dev), top
+    return _on_device("lut", u8_lut, dev), 255
 
 
 def bicubic_upsample(lr: torch.Tensor, scale: int) -> torch.Tensor:

@@ -190,6 +190,10 @@ def test_native_refusals_without_gpu():
     assert "odd" in crops([(-2, 40, 48, 0, 0, 0)])[1]
     assert "past the" in crops([ok], pool_bytes=5 * 40 * 48 - 1)[1]                  # labeled: 5 bytes per pixel
     assert "past the" in crops([ok], pool_bytes=3 * 40 * 48 - 1, target=None)[1]     # unlabeled: 3
+    assert crops([ok], pool_bytes=5 * 40 * 48 - 1)[0] == -1 and crops([ok], pool_bytes=3 * 40 * 48 - 1, target=None)[0] == -1
+    odd = (0, 33, 35, 0, 0, 0)                # records of odd size: the pad byte is not the record's, one byte short is refused
+    assert crops([odd], pool_bytes=5 * 33 * 35 - 1)[0] == -1 and "past the 5774-byte" in crops([odd], pool_bytes=5 * 33 * 35 - 1)[1]
+    assert crops([odd], pool_bytes=3 * 33 * 35 - 1, target=None)[0] == -1
     assert "past the" in crops([((1 << 33), 40, 48, 0, 0, 0)], pool_bytes=(1 << 33) + 5 * 40 * 48 - 2)[1]
     assert "batch 65" in crops([ok], n=L.TRAIN_MAX_BATCH + 1)[1]
     assert "batch 0" in crops([], n=0)[1]

@@ -158,6 +158,8 @@ def test_native_refusals_without_gpu():
     assert crops([(0, 40, 48, -1, 0, 0)])[0] == -1
     assert crops([(0, 40, 48, 0, 0, 8)])[0] == -1
     assert "past the" in crops([ok], pool_bytes=2 * 40 * 48 - 1)[1]
+    assert crops([ok], pool_bytes=2 * 40 * 48 - 1)[0] == -1                  # the record one byte short: CODON_ERR_BAD_ARG
+    assert crops([(0, 33, 35, 0, 0, 0)], pool_bytes=2 * 33 * 35 - 1)[0] == -1
     assert "past the" in crops([((1 << 33), 40, 48, 0, 0, 0)], pool_bytes=(1 << 33) + 2 * 40 * 48 - 1)[1]
     assert "batch 65" in crops([ok], n=L.TRAIN_MAX_BATCH + 1)[1]
     assert "batch 0" in crops([], n=0)[1]

@@ -174,6 +174,9 @@ def test_labeled_entry_refusals_without_gpu():
     assert crops([ok, (0, 40, 48, 9, 0, 0)])[1].startswith("train_crops_labeled: sample 1")
     assert crops([(0, 40, 48, 0, 0, 8)])[0] == -1
     assert "past the" in crops([ok], pool_bytes=3 * 40 * 48 - 1)[1]          # two planes fit, the label does not
+    assert crops([ok], pool_bytes=3 * 40 * 48 - 1)[0] == -1
+    assert crops([(0, 33, 35, 0, 0, 0)], pool_bytes=3 * 33 * 35 - 1) == (
+        -1, "train_crops_labeled: sample 0: the record at offset 0 runs past the 3464-byte pool")
     assert "batch 65" in crops([ok], n=L.TRAIN_MAX_BATCH + 1)[1]
     d = L.CropDesc()
     assert lib.codon_train_crops_labeled(C.byref(d), fake, 1 << 20, fake, fake, fake, None, None) == -1

@@ -169,6 +169,9 @@ def test_entry_point_refusals_without_gpu():
     assert call(nbytes=2 * 36 * 52) == -1 and call(d=_desc(offset=1)) == -1 and b"runs past the" in err()
     assert call(d=_desc(offset=-1)) == -1 and b"negative" in err()
     assert call(bits=16, dm=4096, nbytes=rec16 - 1) == -1 and b"runs past the" in err()
+    far = dict(height=36, width=44, offset=2)                       # another size, and not the pool's first record
+    for bits, dm, rec in ((8, 255, 2 * 36 * 44 + 9 * 11), (16, 4096, 3 * 36 * 44 + 2 * 9 * 11)):
+        assert call(bits=bits, dm=dm, nbytes=2 + rec - 1, d=_desc(**far)) == -1 and b"runs past the" in err(), bits
     # 16 bits: an even offset and a 2-byte-aligned pool
     assert call(bits=16, dm=4096, nbytes=rec16 + 2, d=_desc(offset=1)) == -1 and b"odd" in err()
     assert call(bits=16, dm=4096, nbytes=rec16, pool=C.c_void_p(4097)) == -1 and b"not 2-byte aligned" in err()
