@@ -38,16 +38,17 @@ __global__ __launch_bounds__(256) void postprocess_u8_f16_kernel(const _Float16*
   o[i] = (unsigned char)(int)(float)p;
 }
 
-// sum of squared integer differences and count of valid pixels: exact in 64-bit integers, so the result is
-// independent of summation order and equals the reference's float64 loop bit for bit.
-__global__ __launch_bounds__(256) void masked_sqerr_kernel(const unsigned char* __restrict__ label,
-                                                           const unsigned char* __restrict__ out, long n,
+// sum of squared integer differences and count of valid pixels over u8 or u16 codes: exact in 64-bit integers (|d| <= 65535,
+// d * d < 2^32, formed in 64 bits), so the result is independent of summation order and equals the reference's float64 loop
+// bit for bit.
+template <typename T>
+__global__ __launch_bounds__(256) void masked_sqerr_kernel(const T* __restrict__ label, const T* __restrict__ out, long n,
                                                            unsigned long long* __restrict__ acc /* [2] */) {
   unsigned long long s = 0, c = 0;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const int l = label[i];
     if (l != 0) {
-      const int d = l - (int)out[i];
+      const long long d = l - (int)out[i];
       s += (unsigned long long)(d * d);
       c += 1;
     }
@@ -82,30 +83,6 @@ __global__ __launch_bounds__(256) void postprocess_u16_kernel(const T* __restric
   o[i] = (unsigned short)(int)rintf(v);
 }
 
-// masked_sqerr_kernel over u16 codes: |d| <= 65535, d * d < 2^32, formed in 64 bits.
-__global__ __launch_bounds__(256) void masked_sqerr_u16_kernel(const unsigned short* __restrict__ label,
-                                                               const unsigned short* __restrict__ out, long n,
-                                                               unsigned long long* __restrict__ acc /* [2] */) {
-  unsigned long long s = 0, c = 0;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int l = label[i];
-    if (l != 0) {
-      const long long d = l - (int)out[i];
-      s += (unsigned long long)(d * d);
-      c += 1;
-    }
-  }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    s += __shfl_xor(s, m, 64);
-    c += __shfl_xor(c, m, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicAdd(&acc[0], s);
-    atomicAdd(&acc[1], c);
-  }
-}
-
 // ---- SSIM ----------------------------------------------------------------------------------------------
 constexpr int SS_R = 6, SS_T = 32, SS_P = SS_T + 2 * SS_R;  // radius, tile, padded tile
 
@@ -119,15 +96,35 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {  // scipy 'reflect': 
 
 struct GaussW { float w[2 * SS_R + 1]; };
 
-// One 32x32 output tile per workgroup.  Writes per-tile partial sums of the SSIM map and, if dmaps != null,
-// the three derivative maps d(sum ssim)/d{mu1, s11, s12} (s11 = G(x^2), s12 = G(x*t)) for the backward.
-__global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                       float* __restrict__ partial, float* __restrict__ dmaps,
-                                                       int H, int W, int tiles_x, int tiles_y, GaussW g, float C1,
-                                                       float C2) {
+// ---- the SSIM tile, unmasked and hole-aware -------------------------------------------------------------
+// Validity v: valid[idx] != 0, or (valid == null) t != 0 -- masked_rmse's rule.  Invalid pixels of BOTH images are loaded as 0
+// (a select, so that no value there -- NaN and Inf included -- reaches anything).  E = pixels whose whole 13x13 window, under
+// the same reflect indexing, is valid; there the SSIM value is the unmasked one.  The derivative maps are 0 outside E.
+__device__ __forceinline__ bool px_valid(const unsigned char* __restrict__ valid, const float* __restrict__ t, long i) {
+  return valid ? valid[i] != 0 : t[i] != 0.0f;
+}
+
+// what the masked instantiation alone keeps in LDS: validity; invalid pixels in the 13 horizontal taps; the integer partials
+template <bool MASKED> struct MaskTile {};
+template <> struct MaskTile<true> {
+  unsigned char tv[SS_P][SS_P + 4], hv[SS_P][SS_T + 4];
+  int redi[2][4];
+};
+
+// One 32x32 output tile per workgroup, written once for both losses.  Per tile: the sum of the SSIM map -> out[tile] and, if
+// dmaps != null, the three derivative maps d(sum ssim)/d{mu1, s11, s12} (s11 = G(x^2), s12 = G(x*t)) for the backward.
+// MASKED: the sum runs over E, and out is ws, 4 * ntiles words -- [0, nt) ssim sums, [nt, 2nt) sums of |a - b| over valid pixels
+// (float), [2nt, 3nt) valid counts, [3nt, 4nt) |E| (int32).  Unmasked, valid and ntiles are unused and nothing of the validity
+// planes, the invalid-tap counts, the L1 sum or the integer reductions is compiled in.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                        const unsigned char* __restrict__ valid, float* __restrict__ out,
+                                                        float* __restrict__ dmaps, int H, int W, int tiles_x, int tiles_y,
+                                                        int ntiles, GaussW g, float C1, float C2) {
   __shared__ float ta[SS_P][SS_P + 1], tb[SS_P][SS_P + 1];
   __shared__ float hz[5][SS_P][SS_T + 1];
-  __shared__ float red[4];
+  __shared__ float red[MASKED ? 2 : 1][4];
+  __shared__ MaskTile<MASKED> mk;
   const int tid = threadIdx.x;
   const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, img = blockIdx.x / (tiles_x * tiles_y);
   const int x0 = tx * SS_T, y0 = ty * SS_T;
@@ -136,43 +133,68 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
   for (int e = tid; e < SS_P * SS_P; e += 256) {
     const int r = e / SS_P, c = e % SS_P;
     const int yy = reflect_idx(y0 + r - SS_R, H), xx = reflect_idx(x0 + c - SS_R, W);
-    ta[r][c] = pa[(long)yy * W + xx];
-    tb[r][c] = pb[(long)yy * W + xx];
+    const long i = (long)yy * W + xx;
+    const float av = pa[i], bv = pb[i];
+    bool v = true;
+    if constexpr (MASKED) {
+      v = valid ? valid[(long)img * H * W + i] != 0 : bv != 0.0f;
+      mk.tv[r][c] = v ? 1 : 0;
+    }
+    ta[r][c] = v ? av : 0.f;
+    tb[r][c] = v ? bv : 0.f;
   }
   __syncthreads();
   // variances / covariance are shift invariant: take the moments of (a - ca), (b - cb) with ca, cb the tile's
   // centre pixels, so that E[x^2] - E[x]^2 does not cancel 4+ digits in fp32 on flat image regions
   const float ca = ta[SS_P / 2][SS_P / 2], cb = tb[SS_P / 2][SS_P / 2];
-  for (int e = tid; e < SS_P * SS_T; e += 256) {   // horizontal pass of the 5 moments
+  for (int e = tid; e < SS_P * SS_T; e += 256) {   // horizontal pass of the 5 moments (and of the invalid count)
     const int r = e / SS_T, c = e % SS_T;
     float s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
+    [[maybe_unused]] int bad = 0;
 #pragma unroll
     for (int k = 0; k <= 2 * SS_R; ++k) {
       const float u = ta[r][c + k] - ca, v = tb[r][c + k] - cb, w = g.w[k];
       s0 = fmaf(w, u, s0); s1 = fmaf(w, v, s1); s2 = fmaf(w, u * u, s2); s3 = fmaf(w, v * v, s3);
       s4 = fmaf(w, u * v, s4);
+      if constexpr (MASKED) bad += 1 - (int)mk.tv[r][c + k];
     }
     hz[0][r][c] = s0; hz[1][r][c] = s1; hz[2][r][c] = s2; hz[3][r][c] = s3; hz[4][r][c] = s4;
+    if constexpr (MASKED) mk.hv[r][c] = (unsigned char)bad;
   }
   __syncthreads();
-  float local = 0.f;
+  float lss = 0.f;
+  [[maybe_unused]] float ll1 = 0.f;
+  [[maybe_unused]] int nv = 0, ne = 0;
   for (int e = tid; e < SS_T * SS_T; e += 256) {
     const int r = e / SS_T, c = e % SS_T;
     const int gy = y0 + r, gx = x0 + c;
     float m[5] = {0, 0, 0, 0, 0};
+    [[maybe_unused]] int bad = 0;
 #pragma unroll
     for (int k = 0; k <= 2 * SS_R; ++k) {
       const float w = g.w[k];
 #pragma unroll
       for (int q = 0; q < 5; ++q) m[q] = fmaf(w, hz[q][r + k][c], m[q]);
+      if constexpr (MASKED) bad += mk.hv[r + k][c];
     }
     if (gy < H && gx < W) {
+      bool in_e = true;
+      if constexpr (MASKED) {
+        if (mk.tv[r + SS_R][c + SS_R]) {
+          ll1 += fabsf(ta[r + SS_R][c + SS_R] - tb[r + SS_R][c + SS_R]);
+          nv += 1;
+        }
+        in_e = bad == 0;
+      }
       const float mu1 = m[0] + ca, mu2 = m[1] + cb;
       const float s1 = m[2] - m[0] * m[0], s2 = m[3] - m[1] * m[1], s12 = m[4] - m[0] * m[1];
       const float A1 = 2.f * mu1 * mu2 + C1, A2 = 2.f * s12 + C2;
       const float B1 = mu1 * mu1 + mu2 * mu2 + C1, B2 = s1 + s2 + C2;
       const float ssim = (A1 * A2) / (B1 * B2);
-      local += ssim;
+      if (in_e) {
+        lss += ssim;
+        ne += 1;
+      }
       if (dmaps) {
         // S = A1*A2/(B1*B2) with s1 = s11 - mu1^2, s12 = s12raw - mu1*mu2
         const float inv = 1.f / (B1 * B2);
@@ -181,17 +203,38 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
         const float d_s12 = 2.f * dA2;                 // via A2
         const float d_mu1 = dA1 * 2.f * mu2 + dB1 * 2.f * mu1 + dA2 * (-2.f * mu2) + dB2 * (-2.f * mu1);
         const long o = (long)img * 3 * H * W + (long)gy * W + gx;
-        dmaps[o] = d_mu1;
-        dmaps[o + (long)H * W] = d_s11;
-        dmaps[o + 2L * H * W] = d_s12;
+        dmaps[o] = in_e ? d_mu1 : 0.f;
+        dmaps[o + (long)H * W] = in_e ? d_s11 : 0.f;
+        dmaps[o + 2L * H * W] = in_e ? d_s12 : 0.f;
       }
     }
   }
 #pragma unroll
-  for (int mm = 32; mm >= 1; mm >>= 1) local += __shfl_xor(local, mm, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = local;
+  for (int mm = 32; mm >= 1; mm >>= 1) {
+    lss += __shfl_xor(lss, mm, 64);
+    if constexpr (MASKED) {
+      ll1 += __shfl_xor(ll1, mm, 64);
+      nv += __shfl_xor(nv, mm, 64);
+      ne += __shfl_xor(ne, mm, 64);
+    }
+  }
+  if ((tid & 63) == 0) {
+    red[0][tid >> 6] = lss;
+    if constexpr (MASKED) {
+      red[1][tid >> 6] = ll1;
+      mk.redi[0][tid >> 6] = nv; mk.redi[1][tid >> 6] = ne;
+    }
+  }
   __syncthreads();
-  if (tid == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if (tid == 0) {
+    out[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    if constexpr (MASKED) {
+      out[ntiles + blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+      int* wi = (int*)out;
+      wi[2 * ntiles + blockIdx.x] = mk.redi[0][0] + mk.redi[0][1] + mk.redi[0][2] + mk.redi[0][3];
+      wi[3 * ntiles + blockIdx.x] = mk.redi[1][0] + mk.redi[1][1] + mk.redi[1][2] + mk.redi[1][3];
+    }
+  }
 }
 
 // adjoint of the reflect-boundary separable Gaussian applied to the three derivative maps, combined into
@@ -213,7 +256,7 @@ __device__ __forceinline__ float adj_axis(const float* __restrict__ d, int n, in
   return s;
 }
 
-// pass 1: rows (along W) of each derivative map -> tmp; pass 2: columns + combine.
+// pass 1: rows (along W) of each derivative map -> tmp; pass 2: columns + combine, written once for both losses.
 __global__ __launch_bounds__(256) void gauss_adj_rows_kernel(const float* __restrict__ d, float* __restrict__ tmp, int H,
                                                              int W, long total, GaussW g) {
   const long idx = blockIdx.x * 256L + threadIdx.x;  // over (plane, y, x)
@@ -222,17 +265,29 @@ __global__ __launch_bounds__(256) void gauss_adj_rows_kernel(const float* __rest
   const long row = idx / W;
   tmp[idx] = adj_axis(d + row * W, W, 1, x, g);
 }
-__global__ __launch_bounds__(256) void ssim_l1_bwd_kernel(const float* __restrict__ tmp, const float* __restrict__ a,
-                                                          const float* __restrict__ b, float* __restrict__ ga, int H,
-                                                          int W, long total, GaussW g, float ssim_scale,
-                                                          float l1_scale) {
+// MASKED: the two scales are read per image from the device (scales[2 * img], unmasked: the arguments), the upstream gradient is
+// applied here (gup[0]; unmasked: by the caller) and exactly +0.0f is SELECTED at every invalid pixel (a NaN there, or a
+// negative upstream gradient, cannot leave a mark).
+template <bool MASKED>
+__global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ tmp, const float* __restrict__ a,
+                                                       const float* __restrict__ b, const unsigned char* __restrict__ valid,
+                                                       const float* __restrict__ scales, const float* __restrict__ gup,
+                                                       float* __restrict__ ga, int H, int W, long total, GaussW g,
+                                                       float ssim_scale, float l1_scale) {
   const long idx = blockIdx.x * 256L + threadIdx.x;  // over (img, y, x)
   if (idx >= total) return;
+  if constexpr (MASKED) {
+    if (!px_valid(valid, b, idx)) {
+      ga[idx] = 0.f;
+      return;
+    }
+  }
   const int x = (int)(idx % W);
   const long t = idx / W;
   const int y = (int)(t % H);
   const long img = t / H;
   const long HW = (long)H * W;
+  if constexpr (MASKED) { ssim_scale = scales[2 * img]; l1_scale = scales[2 * img + 1]; }
   const float* base = tmp + img * 3 * HW + x;
   const float g_mu = adj_axis(base, H, W, y, g);
   const float g_s11 = adj_axis(base + HW, H, W, y, g);
@@ -241,6 +296,7 @@ __global__ __launch_bounds__(256) void ssim_l1_bwd_kernel(const float* __restric
   float r = ssim_scale * (g_mu + 2.f * av * g_s11 + bv * g_s12);
   const float df = av - bv;
   r += l1_scale * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f));
+  if constexpr (MASKED) r = r * gup[0];
   ga[idx] = r;
 }
 
@@ -293,13 +349,21 @@ int postprocess_u8_f16(const void* x, unsigned char* o, long n, hipStream_t stre
   return check_launch("postprocess_u8_f16_kernel");
 }
 
-int masked_sqerr(const unsigned char* label, const unsigned char* out, long n, unsigned long long* acc,
-                 hipStream_t stream) {
+template <typename T>
+static int masked_sqerr_launch(const char* what, const T* label, const T* out, long n, unsigned long long* acc,
+                               hipStream_t stream) {
   hipError_t e = hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), stream);
-  if (e != hipSuccess) { set_error("masked_rmse: memset: %s", hipGetErrorString(e)); return CODON_ERR_LAUNCH; }
+  if (e != hipSuccess) { set_error("%s: memset: %s", what, hipGetErrorString(e)); return CODON_ERR_LAUNCH; }
   const unsigned blocks = (unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256);
-  hipLaunchKernelGGL(masked_sqerr_kernel, dim3(blocks), dim3(256), 0, stream, label, out, n, acc);
+  hipLaunchKernelGGL(masked_sqerr_kernel<T>, dim3(blocks), dim3(256), 0, stream, label, out, n, acc);
   return check_launch("masked_sqerr_kernel");
+}
+int masked_sqerr(const unsigned char* label, const unsigned char* out, long n, unsigned long long* acc, hipStream_t stream) {
+  return masked_sqerr_launch("masked_rmse", label, out, n, acc, stream);
+}
+int masked_sqerr_u16(const unsigned short* label, const unsigned short* out, long n, unsigned long long* acc,
+                     hipStream_t stream) {
+  return masked_sqerr_launch("masked_sqerr_u16", label, out, n, acc, stream);
 }
 
 int postprocess_u16(const void* x, int dtype, int depth_max, unsigned short* o, long n, hipStream_t stream) {
@@ -314,27 +378,21 @@ int postprocess_u16(const void* x, int dtype, int depth_max, unsigned short* o, 
   return check_launch("postprocess_u16_kernel");
 }
 
-int masked_sqerr_u16(const unsigned short* label, const unsigned short* out, long n, unsigned long long* acc,
-                     hipStream_t stream) {
-  hipError_t e = hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), stream);
-  if (e != hipSuccess) { set_error("masked_sqerr_u16: memset: %s", hipGetErrorString(e)); return CODON_ERR_LAUNCH; }
-  const unsigned blocks = (unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256);
-  hipLaunchKernelGGL(masked_sqerr_u16_kernel, dim3(blocks), dim3(256), 0, stream, label, out, n, acc);
-  return check_launch("masked_sqerr_u16_kernel");
+struct SsimGrid { int tx, ty, nt; };
+static SsimGrid ssim_grid(int B, int H, int W) {
+  const int tx = (W + SS_T - 1) / SS_T, ty = (H + SS_T - 1) / SS_T;
+  return {tx, ty, B * tx * ty};
 }
-
-int ssim_tiles(int B, int H, int W) { return B * ((W + SS_T - 1) / SS_T) * ((H + SS_T - 1) / SS_T); }
+int ssim_tiles(int B, int H, int W) { return ssim_grid(B, H, W).nt; }
 
 int ssim_fwd(int B, int H, int W, const float* a, const float* b, float* partial, float* dmaps, double* value,
              hipStream_t stream) {
-  const int tx = (W + SS_T - 1) / SS_T, ty = (H + SS_T - 1) / SS_T;
-  const int nt = B * tx * ty;
-  const GaussW g = make_gauss(1.5);
-  hipLaunchKernelGGL(ssim_fwd_kernel, dim3(nt), dim3(256), 0, stream, a, b, partial, dmaps, H, W, tx, ty, g,
-                     0.01f * 0.01f, 0.03f * 0.03f);
-  int st = check_launch("ssim_fwd_kernel");
+  const SsimGrid t = ssim_grid(B, H, W);
+  hipLaunchKernelGGL(ssim_tile_kernel<false>, dim3(t.nt), dim3(256), 0, stream, a, b, (const unsigned char*)nullptr, partial,
+                     dmaps, H, W, t.tx, t.ty, t.nt, make_gauss(1.5), 0.01f * 0.01f, 0.03f * 0.03f);
+  int st = check_launch("ssim_tile_kernel<false>");
   if (st != CODON_OK) return st;
-  hipLaunchKernelGGL(sum_partials_f64_kernel, dim3(1), dim3(256), 0, stream, partial, nt, 1.0 / ((double)B * H * W),
+  hipLaunchKernelGGL(sum_partials_f64_kernel, dim3(1), dim3(256), 0, stream, partial, t.nt, 1.0 / ((double)B * H * W),
                      value);
   return check_launch("sum_partials_f64_kernel");
 }
@@ -347,134 +405,28 @@ int l1_fwd(long n, const float* a, const float* b, float* partial, int nparts, d
   return check_launch("sum_partials_f64_kernel");
 }
 
-int ssim_l1_bwd(int B, int H, int W, const float* a, const float* b, const float* dmaps, float* tmp, float* ga,
-                float ssim_scale, float l1_scale, hipStream_t stream) {
+// gauss_adj_rows_kernel, then loss_bwd_kernel<MASKED>
+template <bool MASKED>
+static int loss_bwd(int B, int H, int W, const float* a, const float* b, const unsigned char* valid, const float* dmaps,
+                    const float* scales, const float* gup, float* tmp, float* ga, float ssim_scale, float l1_scale,
+                    hipStream_t stream) {
   const GaussW g = make_gauss(1.5);
   const long t3 = (long)B * 3 * H * W, t1 = (long)B * H * W;
   hipLaunchKernelGGL(gauss_adj_rows_kernel, dim3((unsigned)((t3 + 255) / 256)), dim3(256), 0, stream, dmaps, tmp, H, W,
                      t3, g);
   int st = check_launch("gauss_adj_rows_kernel");
   if (st != CODON_OK) return st;
-  hipLaunchKernelGGL(ssim_l1_bwd_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, stream, tmp, a, b, ga, H, W,
-                     t1, g, ssim_scale, l1_scale);
-  return check_launch("ssim_l1_bwd_kernel");
+  hipLaunchKernelGGL(loss_bwd_kernel<MASKED>, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, stream, tmp, a, b, valid,
+                     scales, gup, ga, H, W, t1, g, ssim_scale, l1_scale);
+  return check_launch(MASKED ? "loss_bwd_kernel<true>" : "loss_bwd_kernel<false>");
 }
 
-// ---- hole-aware L1 + SSIM ------------------------------------------------------------------
-// Validity v: valid[idx] != 0, or (valid == null) t != 0 -- masked_rmse's rule.  Invalid pixels of BOTH images are loaded as 0
-// (a select, so that no value there -- NaN and Inf included -- reaches anything).  E = pixels whose whole 13x13 window, under
-// the same reflect indexing, is valid; there the SSIM value is ssim_fwd_kernel's.  Per tile: sum of ssim over E, sum of
-// |a - b| over valid pixels (floats) and the two counts (integers).  The derivative maps are 0 outside E.
-__device__ __forceinline__ bool px_valid(const unsigned char* __restrict__ valid, const float* __restrict__ t, long i) {
-  return valid ? valid[i] != 0 : t[i] != 0.0f;
+int ssim_l1_bwd(int B, int H, int W, const float* a, const float* b, const float* dmaps, float* tmp, float* ga,
+                float ssim_scale, float l1_scale, hipStream_t stream) {
+  return loss_bwd<false>(B, H, W, a, b, nullptr, dmaps, nullptr, nullptr, tmp, ga, ssim_scale, l1_scale, stream);
 }
 
-// ws: 4 * ntiles words -- [0, nt) ssim sums, [nt, 2nt) L1 sums (float), [2nt, 3nt) valid counts, [3nt, 4nt) |E| (int32)
-__global__ __launch_bounds__(256) void masked_ssim_l1_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                                 const unsigned char* __restrict__ valid,
-                                                                 float* __restrict__ ws, float* __restrict__ dmaps, int H,
-                                                                 int W, int tiles_x, int tiles_y, int ntiles, GaussW g,
-                                                                 float C1, float C2) {
-  __shared__ float ta[SS_P][SS_P + 1], tb[SS_P][SS_P + 1];
-  __shared__ float hz[5][SS_P][SS_T + 1];
-  __shared__ unsigned char tv[SS_P][SS_P + 4], hv[SS_P][SS_T + 4];   // validity; invalid pixels in the 13 horizontal taps
-  __shared__ float red[2][4];
-  __shared__ int redi[2][4];
-  const int tid = threadIdx.x;
-  const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, img = blockIdx.x / (tiles_x * tiles_y);
-  const int x0 = tx * SS_T, y0 = ty * SS_T;
-  const long ibase = (long)img * H * W;
-  for (int e = tid; e < SS_P * SS_P; e += 256) {
-    const int r = e / SS_P, c = e % SS_P;
-    const int yy = reflect_idx(y0 + r - SS_R, H), xx = reflect_idx(x0 + c - SS_R, W);
-    const long i = ibase + (long)yy * W + xx;
-    const float bv = b[i];
-    const bool v = valid ? valid[i] != 0 : bv != 0.0f;
-    const float av = a[i];
-    ta[r][c] = v ? av : 0.f;
-    tb[r][c] = v ? bv : 0.f;
-    tv[r][c] = v ? 1 : 0;
-  }
-  __syncthreads();
-  const float ca = ta[SS_P / 2][SS_P / 2], cb = tb[SS_P / 2][SS_P / 2];
-  for (int e = tid; e < SS_P * SS_T; e += 256) {   // horizontal pass of the 5 moments and of the invalid count
-    const int r = e / SS_T, c = e % SS_T;
-    float s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
-    int bad = 0;
-#pragma unroll
-    for (int k = 0; k <= 2 * SS_R; ++k) {
-      const float u = ta[r][c + k] - ca, v = tb[r][c + k] - cb, w = g.w[k];
-      s0 = fmaf(w, u, s0); s1 = fmaf(w, v, s1); s2 = fmaf(w, u * u, s2); s3 = fmaf(w, v * v, s3);
-      s4 = fmaf(w, u * v, s4);
-      bad += 1 - (int)tv[r][c + k];
-    }
-    hz[0][r][c] = s0; hz[1][r][c] = s1; hz[2][r][c] = s2; hz[3][r][c] = s3; hz[4][r][c] = s4;
-    hv[r][c] = (unsigned char)bad;
-  }
-  __syncthreads();
-  float lss = 0.f, ll1 = 0.f;
-  int nv = 0, ne = 0;
-  for (int e = tid; e < SS_T * SS_T; e += 256) {
-    const int r = e / SS_T, c = e % SS_T;
-    const int gy = y0 + r, gx = x0 + c;
-    float m[5] = {0, 0, 0, 0, 0};
-    int bad = 0;
-#pragma unroll
-    for (int k = 0; k <= 2 * SS_R; ++k) {
-      const float w = g.w[k];
-#pragma unroll
-      for (int q = 0; q < 5; ++q) m[q] = fmaf(w, hz[q][r + k][c], m[q]);
-      bad += hv[r + k][c];
-    }
-    if (gy < H && gx < W) {
-      if (tv[r + SS_R][c + SS_R]) {
-        ll1 += fabsf(ta[r + SS_R][c + SS_R] - tb[r + SS_R][c + SS_R]);
-        nv += 1;
-      }
-      const bool in_e = bad == 0;
-      const float mu1 = m[0] + ca, mu2 = m[1] + cb;
-      const float s1 = m[2] - m[0] * m[0], s2 = m[3] - m[1] * m[1], s12 = m[4] - m[0] * m[1];
-      const float A1 = 2.f * mu1 * mu2 + C1, A2 = 2.f * s12 + C2;
-      const float B1 = mu1 * mu1 + mu2 * mu2 + C1, B2 = s1 + s2 + C2;
-      const float ssim = (A1 * A2) / (B1 * B2);
-      if (in_e) {
-        lss += ssim;
-        ne += 1;
-      }
-      if (dmaps) {
-        const float inv = 1.f / (B1 * B2);
-        const float dA1 = A2 * inv, dA2 = A1 * inv, dB1 = -ssim / B1, dB2 = -ssim / B2;
-        const float d_s11 = dB2;
-        const float d_s12 = 2.f * dA2;
-        const float d_mu1 = dA1 * 2.f * mu2 + dB1 * 2.f * mu1 + dA2 * (-2.f * mu2) + dB2 * (-2.f * mu1);
-        const long o = (long)img * 3 * H * W + (long)gy * W + gx;
-        dmaps[o] = in_e ? d_mu1 : 0.f;
-        dmaps[o + (long)H * W] = in_e ? d_s11 : 0.f;
-        dmaps[o + 2L * H * W] = in_e ? d_s12 : 0.f;
-      }
-    }
-  }
-#pragma unroll
-  for (int mm = 32; mm >= 1; mm >>= 1) {
-    lss += __shfl_xor(lss, mm, 64);
-    ll1 += __shfl_xor(ll1, mm, 64);
-    nv += __shfl_xor(nv, mm, 64);
-    ne += __shfl_xor(ne, mm, 64);
-  }
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = lss; red[1][tid >> 6] = ll1;
-    redi[0][tid >> 6] = nv; redi[1][tid >> 6] = ne;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    ws[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    ws[ntiles + blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    int* wi = (int*)ws;
-    wi[2 * ntiles + blockIdx.x] = redi[0][0] + redi[0][1] + redi[0][2] + redi[0][3];
-    wi[3 * ntiles + blockIdx.x] = redi[1][0] + redi[1][1] + redi[1][2] + redi[1][3];
-  }
-}
-
+// ---- hole-aware L1 + SSIM: the finishing kernel and the two entries ---------------------------------------
 // One workgroup; image b is folded by wave b % 4: each lane sums a contiguous run of the image's tiles in index order, lane 0
 // then adds the runs in order -- float64 sums, integer counts, an order that depends on the image's size alone (an image's
 // partials are the same in any batch).  counts[b] = {n_b, e_b}; per_image[b] = {L1_b, SSIM_b} (SSIM_b = 1 when e_b = 0);
@@ -524,63 +476,22 @@ __global__ __launch_bounds__(256) void masked_loss_finish_kernel(const float* __
   }
 }
 
-// ssim_l1_bwd_kernel with the per-image scales read from the device, the upstream gradient applied here (gup[0]) and
-// exactly +0.0f SELECTED at every invalid pixel (a NaN there, or a negative upstream gradient, cannot leave a mark)
-__global__ __launch_bounds__(256) void masked_ssim_l1_bwd_kernel(const float* __restrict__ tmp, const float* __restrict__ a,
-                                                                 const float* __restrict__ b,
-                                                                 const unsigned char* __restrict__ valid,
-                                                                 const float* __restrict__ scales,
-                                                                 const float* __restrict__ gup, float* __restrict__ ga, int H,
-                                                                 int W, long total, GaussW g) {
-  const long idx = blockIdx.x * 256L + threadIdx.x;  // over (img, y, x)
-  if (idx >= total) return;
-  if (!px_valid(valid, b, idx)) {
-    ga[idx] = 0.f;
-    return;
-  }
-  const int x = (int)(idx % W);
-  const long t = idx / W;
-  const int y = (int)(t % H);
-  const long img = t / H;
-  const long HW = (long)H * W;
-  const float ssim_scale = scales[2 * img], l1_scale = scales[2 * img + 1];
-  const float* base = tmp + img * 3 * HW + x;
-  const float g_mu = adj_axis(base, H, W, y, g);
-  const float g_s11 = adj_axis(base + HW, H, W, y, g);
-  const float g_s12 = adj_axis(base + 2 * HW, H, W, y, g);
-  const float av = a[idx], bv = b[idx];
-  float r = ssim_scale * (g_mu + 2.f * av * g_s11 + bv * g_s12);
-  const float df = av - bv;
-  r += l1_scale * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f));
-  ga[idx] = r * gup[0];
-}
-
 int masked_l1_ssim_fwd(int B, int H, int W, const float* a, const float* b, const unsigned char* valid, float* ws,
                        float* dmaps, double w_l1, double w_ssim, long long* counts, double* per_image, float* scales,
                        double* value, hipStream_t stream) {
-  const int tx = (W + SS_T - 1) / SS_T, ty = (H + SS_T - 1) / SS_T;
-  const int nt = B * tx * ty;
-  const GaussW g = make_gauss(1.5);
-  hipLaunchKernelGGL(masked_ssim_l1_fwd_kernel, dim3(nt), dim3(256), 0, stream, a, b, valid, ws, dmaps, H, W, tx, ty, nt, g,
-                     0.01f * 0.01f, 0.03f * 0.03f);
-  int st = check_launch("masked_ssim_l1_fwd_kernel");
+  const SsimGrid t = ssim_grid(B, H, W);
+  hipLaunchKernelGGL(ssim_tile_kernel<true>, dim3(t.nt), dim3(256), 0, stream, a, b, valid, ws, dmaps, H, W, t.tx, t.ty, t.nt,
+                     make_gauss(1.5), 0.01f * 0.01f, 0.03f * 0.03f);
+  int st = check_launch("ssim_tile_kernel<true>");
   if (st != CODON_OK) return st;
-  hipLaunchKernelGGL(masked_loss_finish_kernel, dim3(1), dim3(256), 0, stream, ws, B, tx * ty, nt, w_l1, w_ssim, counts,
+  hipLaunchKernelGGL(masked_loss_finish_kernel, dim3(1), dim3(256), 0, stream, ws, B, t.tx * t.ty, t.nt, w_l1, w_ssim, counts,
                      per_image, scales, value);
   return check_launch("masked_loss_finish_kernel");
 }
 
 int masked_l1_ssim_bwd(int B, int H, int W, const float* a, const float* b, const unsigned char* valid, const float* dmaps,
                        const float* scales, const float* gup, float* tmp, float* ga, hipStream_t stream) {
-  const GaussW g = make_gauss(1.5);
-  const long t3 = (long)B * 3 * H * W, t1 = (long)B * H * W;
-  hipLaunchKernelGGL(gauss_adj_rows_kernel, dim3((unsigned)((t3 + 255) / 256)), dim3(256), 0, stream, dmaps, tmp, H, W,
-                     t3, g);
-  int st = check_launch("gauss_adj_rows_kernel");
-  if (st != CODON_OK) return st;
-  hipLaunchKernelGGL(masked_ssim_l1_bwd_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, stream, tmp, a, b, valid,
-                     scales, gup, ga, H, W, t1, g);
-  return check_launch("masked_ssim_l1_bwd_kernel");
+  return loss_bwd<true>(B, H, W, a, b, valid, dmaps, scales, gup, tmp, ga, 0.f, 0.f, stream);
 }
 
 }  // namespace codon

@@ -37,26 +37,41 @@ def postprocess_u8(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _sqerr_dev(label: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """int64[2] = { sum of squared errors, count over label != 0 } on the device, for u8 planes or (after _as_u16) u16 codes;
+    the label is cropped to the output's size."""
+    lib = L.load()
+    assert label.dtype == out.dtype and out.dtype in (torch.uint8, torch.uint16) and out.dim() == 2, (label.dtype, out.dtype)
+    wide = out.dtype == torch.uint16
+    if wide:
+        label = label.view(torch.int16)              # slicing and .contiguous() where an op lacks uint16: the same bits
+    label = label[:out.shape[0], :out.shape[1]].contiguous()
+    out = out.contiguous()
+    dev = ops._dev(label, out)
+    acc = torch.empty(2, dtype=torch.int64, device=dev)
+    fn, what = (lib.codon_masked_sqerr_u16, "masked_sqerr_u16") if wide else (lib.codon_masked_sqerr, "masked_sqerr")
+    with torch.cuda.device(dev):
+        L.check(fn(out.numel(), _p(label), _p(out), _p(acc), ops._stream(dev)), what)
+    return acc
+
+
+def _rmse(label: torch.Tensor, out: torch.Tensor) -> float:
+    s, c = (int(v) for v in _sqerr_dev(label, out).cpu())
+    return math.sqrt(s / c)
+
+
 def masked_sqerr_dev(label_u8: torch.Tensor, out_u8: torch.Tensor) -> torch.Tensor:
     """masked_rmse's two exact integer sums as a DEVICE tensor int64[2] = { sum of squared errors, count } -- no host
     synchronisation (codon_amd.infer reads them back one image later); rmse = sqrt(s / c)."""
-    lib = L.load()
-    assert label_u8.dtype == torch.uint8 and out_u8.dtype == torch.uint8 and out_u8.dim() == 2
-    label_u8 = label_u8[:out_u8.shape[0], :out_u8.shape[1]].contiguous()
-    out_u8 = out_u8.contiguous()
-    dev = ops._dev(label_u8, out_u8)
-    acc = torch.empty(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.codon_masked_sqerr(out_u8.numel(), _p(label_u8), _p(out_u8), _p(acc), ops._stream(dev)),
-                "masked_sqerr")
-    return acc
+    assert label_u8.dtype == torch.uint8 and out_u8.dtype == torch.uint8
+    return _sqerr_dev(label_u8, out_u8)
 
 
 def masked_rmse(label_u8: torch.Tensor, out_u8: torch.Tensor) -> float:
     """test.py::EvaluationResults: label is cropped to the output's size (:151); pixels with label == 0 are
     excluded from both the error and the count."""
-    s, c = (int(v) for v in masked_sqerr_dev(label_u8, out_u8).cpu())
-    return math.sqrt(s / c)
+    assert label_u8.dtype == torch.uint8 and out_u8.dtype == torch.uint8
+    return _rmse(label_u8, out_u8)
 
 
 def _as_u16(t: torch.Tensor) -> torch.Tensor:
@@ -90,23 +105,12 @@ def postprocess_u16(x: torch.Tensor, depth_max: int = 65535) -> torch.Tensor:
 
 def masked_sqerr_u16_dev(label_u16: torch.Tensor, out_u16: torch.Tensor) -> torch.Tensor:
     """masked_sqerr_dev over u16 codes: a DEVICE tensor int64[2] = { sum of squared errors, count over label != 0 }."""
-    lib = L.load()
-    label_u16, out_u16 = _as_u16(label_u16), _as_u16(out_u16)
-    assert out_u16.dim() == 2
-    label_u16 = label_u16.view(torch.int16)[:out_u16.shape[0], :out_u16.shape[1]].contiguous()
-    out_u16 = out_u16.contiguous()
-    dev = ops._dev(label_u16, out_u16)
-    acc = torch.empty(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.codon_masked_sqerr_u16(out_u16.numel(), _p(label_u16), _p(out_u16), _p(acc), ops._stream(dev)),
-                "masked_sqerr_u16")
-    return acc
+    return _sqerr_dev(_as_u16(label_u16), _as_u16(out_u16))
 
 
 def masked_rmse_u16(label_u16: torch.Tensor, out_u16: torch.Tensor) -> float:
     """masked_rmse in 16-bit codes: label cropped to the output's size, label == 0 excluded."""
-    s, c = (int(v) for v in masked_sqerr_u16_dev(label_u16, out_u16).cpu())
-    return math.sqrt(s / c)
+    return _rmse(_as_u16(label_u16), _as_u16(out_u16))
 
 
 def _ssim_forward(a, b, want_maps):
@@ -135,6 +139,11 @@ def ssim(a: torch.Tensor, b: torch.Tensor) -> float:
     return float(ssim_dev(a, b).item())
 
 
+def _bwd_buffers(p, dmaps):
+    """Both backwards' buffers: (tmp, the row pass of the three derivative maps; ga, the gradient)."""
+    return torch.empty_like(dmaps), torch.empty_like(p)
+
+
 class _L1SSIMFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, w_l1, w_ssim):
@@ -154,14 +163,10 @@ class _L1SSIMFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = L.load()
         p, t, dmaps = ctx.saved_tensors
         w_l1, w_ssim = ctx.w
-        dev = p.device
-        B, _, H, W = p.shape
-        n = p.numel()
-        tmp = torch.empty_like(dmaps)
-        ga = torch.empty_like(p)
+        lib, dev, (B, _, H, W), n = L.load(), p.device, p.shape, p.numel()
+        tmp, ga = _bwd_buffers(p, dmaps)
         # the kernel is linear in its two scales: run it for an upstream gradient of 1 and scale the 1-channel result by
         # g ON DEVICE -- float(g) here forced a host synchronisation in every training step
         with torch.cuda.device(dev):
@@ -232,13 +237,10 @@ class _MaskedL1SSIMFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = L.load()
         p, t, dmaps, scales, *v = ctx.saved_tensors
         v = v[0] if v else None
-        dev = p.device
-        B, _, H, W = p.shape
-        tmp = torch.empty_like(dmaps)
-        ga = torch.empty_like(p)
+        lib, dev, (B, _, H, W) = L.load(), p.device, p.shape
+        tmp, ga = _bwd_buffers(p, dmaps)
         up = g.to(torch.float32).reshape(1).contiguous()       # stays on the device: the kernel multiplies by it
         with torch.cuda.device(dev):
             L.check(lib.codon_masked_l1_ssim_bwd(B, H, W, _p(p), _p(t), _p(v), _p(dmaps), _p(scales), _p(up), _p(tmp), _p(ga),
