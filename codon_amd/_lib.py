@@ -70,6 +70,13 @@ class CropDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("crop", C.c_int32), ("s", CropSample * TRAIN_MAX_BATCH)]
 
 
+class SensorDesc(C.Structure):                      # codon_sensor_desc
+    _fields_ = [("batch", C.c_int32), ("size", C.c_int32), ("masked", C.c_int32), ("reserved", C.c_int32),
+                ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("step", C.c_int64), ("first_sample", C.c_int64),
+                ("sigma", C.c_float), ("quad", C.c_float), ("edge_thr", C.c_float), ("reserved_f", C.c_float),
+                ("p_drop", C.c_double), ("p_edge", C.c_double)]
+
+
 class CastDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("src", C.c_void_p * CAST_MAX), ("count", C.c_int64 * CAST_MAX),
                 ("dtype", C.c_int32 * CAST_MAX)]
@@ -167,6 +174,8 @@ SIGNATURES = {
     "codon_bicubic_downsample_masked": (C.c_int, [_I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "codon_lr_codes_to_input": (C.c_int, [_I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P]),
     "codon_train_crops_lr": (C.c_int, [C.POINTER(CropDesc), _P, C.c_int64, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "codon_philox4x32_10": (C.c_int, [C.POINTER(C.c_uint32)] * 3),
+    "codon_lr_sensor": (C.c_int, [C.POINTER(SensorDesc), _P, _P, _P, _I, _P, _P]),
     "codon_d4_views": (C.c_int, [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     "codon_d4_merge": (C.c_int, [_I, _I, _I, _P, _P, _I, _P, _P]),
     "codon_weight_checksum_workspace_bytes": (_S, []),

@@ -1,11 +1,13 @@
 // extern "C" surface of libcodon_hip.so (see include/codon_hip.h): argument validation, dtype
 // dispatch, error strings.  Never throws, never allocates device memory, never synchronises.
 
+#include <math.h>
 #include <stdarg.h>
 #include <string.h>
 
 #include "codon_common.h"
 #include "pair.h"
+#include "sensor_pixel.h"
 #include "train_record.h"
 
 namespace codon {
@@ -135,6 +137,7 @@ int train_crops_lr(const codon_crop_desc*, const unsigned char*, int, int, const
                    float*, float*, hipStream_t);
 int d4_views(int, int, int, const void*, const void*, int, void*, void*, void*, void*, hipStream_t);
 int d4_merge(int, int, int, const void*, const void*, int, float*, hipStream_t);
+int lr_sensor(const SensorArgs&, int, const float*, const float*, const float*, float*, hipStream_t);
 size_t weight_checksum_workspace_bytes();
 int weight_checksum(const codon_wsum_desc*, void*, unsigned long long*, int, int*, int*, int, hipStream_t);
 
@@ -1015,6 +1018,54 @@ int codon_d4_merge(int32_t batch, int32_t height, int32_t width, const void* upr
   CODON_REQUIRE(dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16, CODON_ERR_BAD_ARG, "d4_merge: dtype %d", dtype);
   CODON_REQUIRE(batch <= 32767, CODON_ERR_UNSUPPORTED, "d4_merge: batch %d (at most 32767 images per launch)", batch);
   return d4_merge(batch, height, width, upright, transposed, dtype, out_f32, (hipStream_t)stream);
+}
+
+int codon_philox4x32_10(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
+  CODON_REQUIRE(ctr && key && out, CODON_ERR_BAD_ARG, "philox4x32_10: null pointer");
+  const Philox4 r = philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1]);
+  for (int k = 0; k < 4; ++k) out[k] = r.w[k];
+  return CODON_OK;
+}
+
+int codon_lr_sensor(const codon_sensor_desc* desc, const float* lr, const float* gauss, const float* lut, int32_t levels,
+                    float* out, codon_stream_t stream) {
+  CODON_REQUIRE(desc && lr && gauss && lut && out, CODON_ERR_BAD_ARG, "lr_sensor: null pointer");
+  CODON_REQUIRE(lr != out, CODON_ERR_BAD_ARG, "lr_sensor: lr and out are the same buffer (the edge term reads lr's neighbours)");
+  CODON_REQUIRE(desc->batch >= 1 && desc->batch <= CODON_TRAIN_MAX_BATCH, CODON_ERR_BAD_ARG, "lr_sensor: batch %d (1..%d)",
+                desc->batch, CODON_TRAIN_MAX_BATCH);
+  CODON_REQUIRE(desc->size >= 4 && desc->size <= 512, CODON_ERR_BAD_ARG, "lr_sensor: size %d (4..512)", desc->size);
+  CODON_REQUIRE(levels >= 1 && levels <= 65535, CODON_ERR_BAD_ARG, "lr_sensor: levels %d (1..65535)", levels);
+  CODON_REQUIRE(desc->step >= 0 && desc->step <= 0xFFFFFFFFll, CODON_ERR_BAD_ARG, "lr_sensor: step %lld (0..2^32-1)",
+                (long long)desc->step);
+  CODON_REQUIRE(desc->first_sample >= 0 && desc->first_sample + desc->batch <= 0x100000000ll, CODON_ERR_BAD_ARG,
+                "lr_sensor: first_sample %lld (with the batch: 0..2^32)", (long long)desc->first_sample);
+  CODON_REQUIRE(isfinite(desc->sigma) && desc->sigma >= 0.f, CODON_ERR_BAD_ARG, "lr_sensor: sigma %g is negative or not finite",
+                (double)desc->sigma);
+  CODON_REQUIRE(isfinite(desc->quad) && desc->quad >= 0.f, CODON_ERR_BAD_ARG, "lr_sensor: quad %g is negative or not finite",
+                (double)desc->quad);
+  CODON_REQUIRE(isfinite(desc->edge_thr) && desc->edge_thr >= 0.f, CODON_ERR_BAD_ARG,
+                "lr_sensor: edge_thr %g is negative or not finite", (double)desc->edge_thr);
+  CODON_REQUIRE(desc->p_drop >= 0.0 && desc->p_drop <= 1.0, CODON_ERR_BAD_ARG, "lr_sensor: p_drop %g outside [0, 1]", desc->p_drop);
+  CODON_REQUIRE(desc->p_edge >= 0.0 && desc->p_edge <= 1.0, CODON_ERR_BAD_ARG, "lr_sensor: p_edge %g outside [0, 1]", desc->p_edge);
+  CODON_REQUIRE(desc->p_drop + desc->p_edge <= 1.0, CODON_ERR_BAD_ARG, "lr_sensor: p_drop + p_edge = %g exceeds 1",
+                desc->p_drop + desc->p_edge);
+  CODON_REQUIRE(desc->masked != 0 || (desc->p_drop == 0.0 && desc->p_edge == 0.0), CODON_ERR_BAD_ARG,
+                "lr_sensor: masked 0 with p_drop %g, p_edge %g (without the masked upsample a dropped pixel would ring)",
+                desc->p_drop, desc->p_edge);
+  SensorArgs a;
+  a.p = desc->size;
+  a.masked = desc->masked != 0 ? 1 : 0;
+  a.levels = levels;
+  a.k0 = desc->seed_lo;
+  a.k1 = desc->seed_hi;
+  a.step = (unsigned)desc->step;
+  a.first = (unsigned)desc->first_sample;
+  a.sigma = desc->sigma;
+  a.quad = desc->quad;
+  a.edge_thr = desc->edge_thr;
+  a.t_drop = (unsigned long long)floor(desc->p_drop * 4294967296.0);      // NaN fails the range checks above
+  a.t_edge = (unsigned long long)floor(desc->p_edge * 4294967296.0);
+  return lr_sensor(a, desc->batch, lr, gauss, lut, out, (hipStream_t)stream);
 }
 
 size_t codon_weight_checksum_workspace_bytes(void) { return weight_checksum_workspace_bytes(); }

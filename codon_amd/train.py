@@ -11,6 +11,9 @@ through a 65 536-entry table and the last step quantises onto the data set's own
 --train-lr-depth DIR: REAL pairs -- a sensor's low-resolution map per pair, paired by file name; nothing is
 degraded, one launch (codon_train_crops_lr) builds x, y and t, and x is the crop of what `codon_amd.infer --lr-depth` builds from
 the whole low-resolution file, bit for bit (tests/train_lr_ref.py).
+--sensor-noise / --sensor-noise-quad / --sensor-dropout / --sensor-edge-dropout: a sensor model on the synthetic
+low-resolution map -- range noise from a Gaussian table and per-pixel dropout, both driven by Philox4x32-10 of (pixel, sample
+of the global batch, step; --seed), so that any number of ranks and a resumed run see the same maps (tests/sensor_ref.py).
 
 One step: GradSync.zero_grad -> synthesize -> forward -> L1SSIMLoss(out.float(), t) (--mask-holes: MaskedL1SSIMLoss, which
 leaves the target's holes -- code 0 -- out of the loss; --train-label: targets from a third directory) -> GradSync.backward ->
@@ -25,6 +28,7 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
+import dataclasses
 import math
 import os
 import time
@@ -37,7 +41,8 @@ from . import _lib as L
 from . import ops
 from .infer import run_loop
 from .io import check_depth_max, list_pairs, read_depth_plane
-from .upsample import _on_device, code_table, down_weights, lut16, phase_weights, u8_lut      # noqa: F401 (lut16: for importers)
+from .upsample import (_on_device, code_table, down_weights, gauss_table, lut16,      # noqa: F401 (lut16: for importers)
+                       phase_weights, u8_lut)
 
 DTYPES = {"bf16": torch.bfloat16, "f32": None}
 RESUME_KEYS = ("scale", "crop", "batch", "dtype", "clip_norm", "skip_nonfinite", "ema", "lr_schedule", "warmup_steps", "lr_min",
@@ -52,6 +57,10 @@ DEPTH_DEFAULTS = {"depth_bits": 8, "depth_max": 65535}
 DEGRADE_DEFAULTS = {"degrade_holes": False}
 # the same for --train-lr-depth: a resume key with default False, written by a run that sets it ONLY
 LR_DEFAULTS = {"train_lr_depth": False}
+# the same for the sensor model: its fields, written by a run with a model ONLY; a checkpoint without them
+# compares as "no model"
+SENSOR_DEFAULTS = {"sensor_noise": None, "sensor_noise_quad": None, "sensor_dropout": None, "sensor_edge_dropout": None,
+                   "sensor_edge_threshold": None, "sensor_seed": None}
 MAX_REDRAWS = 64                                    # draw(min_valid=): per sample, before it gives up
 LR_SCHEDULES = ("constant", "cosine")
 
@@ -212,8 +221,57 @@ def draw(rng: np.random.Generator, trainset: TrainSet, batch: int, crop: int, ra
     return d[lo:hi]
 
 
+@dataclasses.dataclass(frozen=True)
+class SensorModel:
+    """The sensor model of the synthetic degradation, applied to the low-resolution map between the two bicubics.
+    noise, noise_quad, edge_threshold are in CODES of the data's own grid (255, or depth_max): the standard deviation of a
+    valid pixel of value v is noise + noise_quad * v^2 codes (noise_quad: sensors whose noise grows with the square of the
+    range; 0 for disparity-like data).  dropout is the probability that a valid pixel becomes a hole, edge_dropout the
+    probability added where a 4-neighbour differs by more than edge_threshold codes; both need degrade_holes (a hole must be
+    left out of the upsample, not smeared through it).  seed: 64 bits, the Philox key."""
+    noise: float = 0.0
+    noise_quad: float = 0.0
+    dropout: float = 0.0
+    edge_dropout: float = 0.0
+    edge_threshold: float = 0.0
+    seed: int = 0
+
+    def __post_init__(self):
+        for n in ("noise", "noise_quad", "edge_threshold"):
+            v = getattr(self, n)
+            if not (isinstance(v, (int, float)) and math.isfinite(v) and v >= 0):
+                raise ValueError(f"SensorModel: {n} {v!r} must be finite and not negative")
+        for n in ("dropout", "edge_dropout"):
+            v = getattr(self, n)
+            if not (isinstance(v, (int, float)) and 0.0 <= v <= 1.0):
+                raise ValueError(f"SensorModel: {n} {v!r} must lie in [0, 1]")
+        if self.dropout + self.edge_dropout > 1.0:
+            raise ValueError(f"SensorModel: dropout {self.dropout} + edge_dropout {self.edge_dropout} exceeds 1")
+        if not (isinstance(self.seed, int) and 0 <= self.seed < 1 << 64):
+            raise ValueError(f"SensorModel: seed {self.seed!r} must be an integer of 64 bits, not negative")
+
+    @property
+    def drops(self) -> bool:
+        return self.dropout > 0 or self.edge_dropout > 0
+
+    def args(self) -> dict:
+        """The checkpoint keys of SENSOR_DEFAULTS."""
+        return {"sensor_noise": float(self.noise), "sensor_noise_quad": float(self.noise_quad),
+                "sensor_dropout": float(self.dropout), "sensor_edge_dropout": float(self.edge_dropout),
+                "sensor_edge_threshold": float(self.edge_threshold), "sensor_seed": int(self.seed)}
+
+
+def check_sensor(who: str, trainset: TrainSet, sensor: SensorModel, degrade_holes: bool):
+    if trainset.has_lr:
+        raise ValueError(f"{who}: a sensor model does not go with a TrainSet of low-resolution maps (nothing is degraded: the "
+                         "maps carry their sensor's own noise and holes)")
+    if sensor.drops and not degrade_holes:
+        raise ValueError(f"{who}: sensor dropout needs degrade_holes (without the masked upsample a dropped pixel would ring "
+                         "instead of being left out)")
+
+
 def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, degrade_holes: bool = False,
-               return_lr: bool = False):
+               return_lr: bool = False, sensor: SensorModel = None, step: int = 0, first_sample: int = 0):
     """(x, y, t), each (B,1,crop,crop) fp32 on the pool's device: the network's depth input (crop -> bicubic down by `scale`
     -> bicubic up -> 8-bit), the guidance and the HR target.  Four launches on the caller's stream, no host synchronisation.
     A TrainSet with labels: x is degraded from the depth plane, t comes from the label plane (codon_train_crops_labeled).
@@ -227,7 +285,19 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
     A TrainSet with low-resolution maps (lr_dir): ONE launch, codon_train_crops_lr, and none of the others -- t and
     y are the crop of the depth map and the guidance, x is the window, under the D4 op, of what infer.codes_to_input builds from
     the WHOLE low-resolution file in fp32.  `scale` must be the set's lr_scale; degrade_holes and return_lr are refused (there
-    is no degradation to mask and no per-crop low-resolution map to return)."""
+    is no degradation to mask and no per-crop low-resolution map to return).
+    sensor: ONE more launch, codon_lr_sensor, between the down and the up launch of either path -- five launches,
+    still no host synchronisation.  Pixel (y, x) of sample b draws its noise and dropout from Philox4x32-10 of the counter
+    (y * p + x, first_sample + b, step, 0) under the model's seed: `step` is the training step and `first_sample` the index of
+    descs[0] in the GLOBAL batch (this rank's shard start).  The up launch reads the new map and return_lr returns it; on the
+    masked path the map stays on the code grid and x stays what infer.codes_to_input builds from its codes.  Dropout needs
+    degrade_holes, and a TrainSet with low-resolution maps refuses a model."""
+    if sensor is not None:
+        check_sensor("synthesize", trainset, sensor, degrade_holes)
+        if not 0 <= step < 1 << 32 or not 0 <= first_sample <= (1 << 32) - len(descs):
+            raise ValueError(f"synthesize: step {step} and first_sample {first_sample} must fit 32 bits")
+        if crop // scale > 512:
+            raise ValueError(f"synthesize: the sensor model takes low-resolution maps up to 512 (crop {crop} at x{scale})")
     lib = L.load()
     B = len(descs)
     if not 1 <= B <= L.TRAIN_MAX_BATCH:
@@ -280,18 +350,33 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
             L.check(lib.codon_bicubic_downsample_masked(B, crop, scale, P_(src.data_ptr()), P_(wdown.data_ptr()),
                                                         P_(tab.data_ptr()), top, P_(lr.data_ptr()), st),
                     "bicubic_downsample_masked")
-            L.check(lib.codon_bicubic_upsample_masked(B, p, p, scale, P_(lr.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()),
-                                                      None, st), "bicubic_upsample_masked")
         else:
             L.check(lib.codon_bicubic_downsample(B, crop, scale, P_(src.data_ptr()), P_(wdown.data_ptr()), P_(lr.data_ptr()),
                                                  st), "bicubic_downsample")
-            L.check(lib.codon_bicubic_upsample(B, p, p, scale, P_(lr.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()), st),
+        noisy = lr                                      # what the up launch reads
+        if sensor is not None:
+            noisy = torch.empty_like(lr)
+            sd = L.SensorDesc()
+            sd.batch, sd.size, sd.masked = B, p, 1 if degrade_holes else 0
+            sd.seed_lo, sd.seed_hi = sensor.seed & 0xFFFFFFFF, sensor.seed >> 32
+            sd.step, sd.first_sample = step, first_sample
+            sd.sigma, sd.quad, sd.edge_thr = (np.float32(np.float64(c) / top) for c in
+                                              (sensor.noise, sensor.noise_quad, sensor.edge_threshold))
+            sd.p_drop, sd.p_edge = sensor.dropout, sensor.edge_dropout
+            gauss = _on_device("gauss", gauss_table, dev)
+            L.check(lib.codon_lr_sensor(C.byref(sd), P_(lr.data_ptr()), P_(gauss.data_ptr()), P_(tab.data_ptr()), top,
+                                        P_(noisy.data_ptr()), st), "lr_sensor")
+        if degrade_holes:
+            L.check(lib.codon_bicubic_upsample_masked(B, p, p, scale, P_(noisy.data_ptr()), P_(wup.data_ptr()),
+                                                      P_(x.data_ptr()), None, st), "bicubic_upsample_masked")
+        else:
+            L.check(lib.codon_bicubic_upsample(B, p, p, scale, P_(noisy.data_ptr()), P_(wup.data_ptr()), P_(x.data_ptr()), st),
                     "bicubic_upsample")
         if deep:
             L.check(lib.codon_quantize_levels(x.numel(), P_(x.data_ptr()), P_(tab.data_ptr()), top, st), "quantize_levels")
         else:
             L.check(lib.codon_quantize_u8(x.numel(), P_(x.data_ptr()), P_(tab.data_ptr()), st), "quantize_u8")
-    return (x, y, t, lr) if return_lr else (x, y, t)
+    return (x, y, t, noisy) if return_lr else (x, y, t)
 
 
 # ---- training -----------------------------------------------------------------------------------------------------------------
@@ -337,13 +422,13 @@ def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, 
 
 def load_resume(path: str, args: dict) -> dict:
     """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype, or with
-    other options that change the trajectory (RESUME_KEYS, DEPTH_DEFAULTS', DEGRADE_DEFAULTS' and LR_DEFAULTS' keys; a key the
-    checkpoint's args lack compares as its default)."""
+    other options that change the trajectory (RESUME_KEYS, DEPTH_DEFAULTS', DEGRADE_DEFAULTS', LR_DEFAULTS' and
+    SENSOR_DEFAULTS' keys; a key the checkpoint's args lack compares as its default)."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(ck, dict) or not all(k in ck for k in ("epoch", "model", "optimizer", "rng", "args")):
         raise ValueError(f"--resume {path}: not a codon_amd.train checkpoint (use --weights to start from other weights)")
-    absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS, **LR_DEFAULTS}
-    keys = RESUME_KEYS + tuple(DEPTH_DEFAULTS) + tuple(DEGRADE_DEFAULTS) + tuple(LR_DEFAULTS)
+    absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS, **LR_DEFAULTS, **SENSOR_DEFAULTS}
+    keys = RESUME_KEYS + tuple(DEPTH_DEFAULTS) + tuple(DEGRADE_DEFAULTS) + tuple(LR_DEFAULTS) + tuple(SENSOR_DEFAULTS)
     was, now = ({k: a.get(k, absent.get(k)) for k in keys} for a in (ck["args"], args))
     bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in keys if was[k] != now[k]]
     if bad:
@@ -356,7 +441,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         val: dict = None, ckpt: dict = None, start_step: int = 0, opt_state: dict = None, fixed: np.ndarray = None,
         args: dict = None, time_synth: bool = False, emit=print, clip_norm: float = None, skip_nonfinite: bool = False,
         ema_decay: float = None, lr_schedule: str = "constant", warmup: int = 0, lr_min: float = 0.0, lr_steps: int = None,
-        grad_hook=None, mask_holes: bool = False, min_valid: float = 0.0, degrade_holes: bool = False) -> dict:
+        grad_hook=None, mask_holes: bool = False, min_valid: float = 0.0, degrade_holes: bool = False,
+        sensor: SensorModel = None) -> dict:
     """Train `model` (fp32 parameters on the pool's device) from step start_step + 1 to step `steps`.
     val:   {"depth", "color", "label", "every"} -- rank 0 runs infer.run_loop every `every` steps and prints the means;
     ckpt:  {"path", "every"} -- rank 0 saves every `every` steps and after the last one;
@@ -374,6 +460,9 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     degrade_holes: synthesize's hole-aware degradation; needs no other option.
     A TrainSet with low-resolution maps (lr_dir) needs no argument here: synthesize reads the real maps, and the
            checkpoint's args gain train_lr_depth=True.
+    sensor: synthesize's sensor model, given the step number and this rank's shard start -- also under `fixed`
+           descriptors, so N ranks see the global batch one process sees and a resumed run the maps the straight run saw; the
+           checkpoint's args gain the model's fields (SENSOR_DEFAULTS' keys).
     Returns {"losses": [(step, loss)], "gs", "opt", "rng", "step", ...}."""
     from .dist import FlatAdam, GradSync
     from .metrics import L1SSIMLoss, MaskedL1SSIMLoss
@@ -384,6 +473,11 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         raise ValueError(f"fit: a batch of {batch} does not split evenly over {world} ranks")
     if not 0.0 <= min_valid <= 1.0 or (min_valid > 0 and not mask_holes):
         raise ValueError(f"fit: min_valid {min_valid} must lie in [0, 1] and needs mask_holes")
+    synth_kw = {}
+    if sensor is not None:                          # refused before the first step; without a model synthesize is called as ever
+        from .dist import shard_batch
+        check_sensor("fit", trainset, sensor, degrade_holes)
+        synth_kw = {"sensor": sensor, "first_sample": shard_batch(batch, rank, world)[0]}
     rng = np.random.default_rng(seed) if rng is None else rng
     dev = trainset.pool.device
     model.set_compute_dtype(DTYPES[dtype])
@@ -408,6 +502,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         args.update(degrade_holes=True)
     if trainset.has_lr:                             # only then, likewise
         args.update(train_lr_depth=True)
+    if sensor is not None:                          # only then, likewise
+        args.update(sensor.args())
     if trainset.depth_bits == 16:                   # only then: an 8-bit checkpoint keeps the keys it always had
         args.update(depth_bits=16, depth_max=int(trainset.depth_max))
     stream = torch.cuda.current_stream(dev)
@@ -430,7 +526,9 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         gs.zero_grad()
         if time_synth:
             e[1].record(stream)
-        x, y, t = synthesize(trainset, descs, scale, crop, degrade_holes=degrade_holes)
+        if sensor is not None:
+            synth_kw["step"] = step
+        x, y, t = synthesize(trainset, descs, scale, crop, degrade_holes=degrade_holes, **synth_kw)
         if time_synth:
             e[2].record(stream)
         out = model(x, y)
@@ -536,6 +634,18 @@ def parse_args(argv=None):
     ap.add_argument("--degrade-holes", action="store_true",
                     help="holes (code 0) of the depth maps are left out of the degradation's two bicubics instead of being "
                          "smeared through them; the low-resolution map keeps them as holes, as a sensor's file does")
+    ap.add_argument("--sensor-noise", type=float, default=None, metavar="CODES",
+                    help="sensor model: Gaussian noise of this standard deviation, in codes of the data's grid (255, or "
+                         "--depth-max), on the synthetic low-resolution map; every --sensor option draws from --seed")
+    ap.add_argument("--sensor-noise-quad", type=float, default=None, metavar="CODES",
+                    help="sensor model: noise that grows with the square of the value v (0..1): CODES * v^2 more codes")
+    ap.add_argument("--sensor-dropout", type=float, default=None, metavar="P",
+                    help="sensor model: a valid low-resolution pixel becomes a hole with this probability (needs --degrade-holes)")
+    ap.add_argument("--sensor-edge-dropout", type=float, default=None, metavar="P",
+                    help="sensor model: this much more dropout where a 4-neighbour differs by more than "
+                         "--sensor-edge-threshold (needs --degrade-holes)")
+    ap.add_argument("--sensor-edge-threshold", type=float, default=None, metavar="CODES",
+                    help="with --sensor-edge-dropout: the difference to a neighbour, in codes, above which a pixel is on an edge")
     ap.add_argument("--val-depth", default=None)
     ap.add_argument("--val-lr-depth", default=None,
                     help="low-resolution validation depth maps, upsampled by --scale as `codon_amd.infer --lr-depth` does "
@@ -571,6 +681,28 @@ def parse_args(argv=None):
         ap.error("--train-lr-depth and --train-label exclude each other (with low-resolution maps --train-depth is the target)")
     if a.train_lr_depth is not None and a.degrade_holes:
         ap.error("--train-lr-depth and --degrade-holes exclude each other (nothing is degraded)")
+    given = {n: getattr(a, "sensor_" + n) for n in ("noise", "noise_quad", "dropout", "edge_dropout", "edge_threshold")}
+    given = {n: v for n, v in given.items() if v is not None}
+    if given:
+        opt = lambda n: "--sensor-" + n.replace("_", "-")                  # noqa: E731
+        if a.train_lr_depth is not None:
+            ap.error(f"{opt(next(iter(given)))} and --train-lr-depth exclude each other (nothing is degraded: real "
+                     "low-resolution maps carry their sensor's own noise and holes)")
+        for n in ("dropout", "edge_dropout"):
+            if n in given and not a.degrade_holes:
+                ap.error(f"{opt(n)} needs --degrade-holes (a dropped pixel must be left out of the upsample)")
+        if ("edge_dropout" in given) != ("edge_threshold" in given):
+            ap.error("--sensor-edge-dropout and --sensor-edge-threshold go together")
+        for n, v in given.items():
+            if not math.isfinite(v) or v < 0:
+                ap.error(f"{opt(n)} {v} must be finite and not negative")
+        if max(given.get("dropout", 0.0), given.get("edge_dropout", 0.0)) > 1 or \
+                given.get("dropout", 0.0) + given.get("edge_dropout", 0.0) > 1:
+            ap.error("--sensor-dropout and --sensor-edge-dropout are probabilities, together at most 1")
+        if a.crop // a.scale > 512:
+            ap.error(f"the sensor model takes low-resolution maps up to 512 (--crop {a.crop} at x{a.scale})")
+        if not 0 <= a.seed < 1 << 64:
+            ap.error(f"--seed {a.seed} must lie in [0, 2^64) with a sensor model")
     if a.degrade_holes and a.crop > 1024:
         ap.error(f"--degrade-holes takes crops up to 1024 (--crop {a.crop})")
     if not 0.0 <= a.min_valid <= 1.0:
@@ -601,14 +733,24 @@ def parse_args(argv=None):
     return a
 
 
+def sensor_of(a):
+    """The SensorModel the command line asks for, or None when it names no --sensor option."""
+    f = {n: getattr(a, "sensor_" + n) for n in ("noise", "noise_quad", "dropout", "edge_dropout", "edge_threshold")}
+    if all(v is None for v in f.values()):
+        return None
+    return SensorModel(seed=a.seed, **{n: 0.0 if v is None else v for n, v in f.items()})
+
+
 def run_args(a) -> dict:
+    sensor = sensor_of(a)
     deep = {"depth_bits": 16, "depth_max": a.depth_max} if a.depth_bits == 16 else {}
     return {**deep, "scale": a.scale, "crop": a.crop, "batch": a.batch, "dtype": a.dtype, "lr": a.lr, "seed": a.seed,
             "clip_norm": a.clip_norm, "skip_nonfinite": a.skip_nonfinite, "ema": a.ema, "lr_schedule": a.lr_schedule,
             "warmup_steps": a.warmup_steps, "lr_min": a.lr_min, "lr_steps": a.lr_steps, "mask_holes": bool(a.mask_holes),
             "min_valid": float(a.min_valid), "train_label": a.train_label is not None,
             **({"degrade_holes": True} if a.degrade_holes else {}),
-            **({"train_lr_depth": True} if a.train_lr_depth is not None else {})}
+            **({"train_lr_depth": True} if a.train_lr_depth is not None else {}),
+            **(sensor.args() if sensor is not None else {})}
 
 
 def main(argv=None, emit=print) -> dict:
@@ -654,11 +796,12 @@ def main(argv=None, emit=print) -> dict:
     if a.val_lr_depth:
         val.update(lr_depth=a.val_lr_depth, scale=a.scale)
     ckpt = {"path": a.save, "every": a.save_every} if a.save else None
+    kw = {"sensor": sensor_of(a)} if sensor_of(a) is not None else {}      # without a model fit is called as ever
     res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,
               log_every=a.log_every, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,
               args=args, emit=emit, clip_norm=a.clip_norm, skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema,
               lr_schedule=a.lr_schedule, warmup=a.warmup_steps, lr_min=a.lr_min, lr_steps=a.lr_steps,
-              mask_holes=a.mask_holes, min_valid=a.min_valid, degrade_holes=a.degrade_holes)
+              mask_holes=a.mask_holes, min_valid=a.min_valid, degrade_holes=a.degrade_holes, **kw)
     res["model"] = model
     return res
 

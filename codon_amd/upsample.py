@@ -2,6 +2,7 @@
 the per-phase Keys weights (fp64 -> fp32, once); the gather + arithmetic runs in upsample.hip."""
 import ctypes as C
 import functools
+import statistics
 
 import numpy as np
 import torch
@@ -45,6 +46,16 @@ def lut16(depth_max: int = 65535) -> np.ndarray:
     entries exist only so that no u16 indexes out of the table."""
     check_depth_max(depth_max)
     return (np.arange(65536, dtype=np.float64) / depth_max).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def gauss_table() -> np.ndarray:
+    """65 536 fp32 values: gauss[u] = float32(Phi^-1((u + 0.5) / 65536)), the quantile computed in float64 by the standard
+    library -- the Gaussian of the sensor model, indexed by the top 16 bits of a Philox word.  The kernel and the
+    numpy restatement read the same table: no logf or cosf can make them differ.  Exactly antisymmetric, strictly increasing,
+    +-4.3249 at the ends, mean 0, standard deviation 0.99998986."""
+    inv = statistics.NormalDist().inv_cdf
+    return np.array([inv((u + 0.5) / 65536) for u in range(65536)], dtype=np.float64).astype(np.float32)
 
 
 @functools.lru_cache(maxsize=None)

@@ -2,7 +2,8 @@
  *
  * The reference (619862306/CODON) is eager PyTorch with no native layer; what it calls for
  * this path are stock ATen ops from nn.Module.forward.  Each entry point below replaces the
- * ATen op sequence at the cited reference lines.  All pointers are DEVICE pointers; all work
+ * ATen op sequence at the cited reference lines.  All pointers are DEVICE pointers (descriptors and the three
+ * arguments of the host-only known-answer entry of the sensor model's generator excepted); all work
  * is enqueued on the caller's stream; nothing allocates, synchronises or throws.  Every
  * function returns CODON_OK (0) or a negative codon_status; codon_last_error_string() gives
  * the detail for the calling thread.
@@ -709,6 +710,43 @@ int codon_lr_codes_to_input(int32_t batch, int32_t lr_height, int32_t lr_width, 
 int codon_train_crops_lr(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, int32_t scale, int32_t code_bits,
                          const float* lut, int32_t depth_max, const float* lut8, const float* phase_weights, float* x,
                          float* guide, float* target, codon_stream_t stream);
+
+/* ---- the sensor model of the training degradation: range noise and dropout on the low-resolution map -------
+ * No reference counterpart (the reference ships no degradation): DEFINITIONS, in codon_amd/csrc/sensor.hip, sensor_pixel.h and
+ * sensor_rng.h, restated in numpy in tests/sensor_ref.py, required to agree bit for bit.
+ *
+ * codon_philox4x32_10: HOST ONLY, no GPU needed -- out[0..3] = Philox4x32-10 of the counter ctr[0..3] under the key key[0..1]
+ * (Salmon et al., SC'11), from the very function the kernel calls: the known-answer check of the generator.
+ *
+ * codon_lr_sensor: ONE launch over lr (batch,1,size,size) fp32 into out (same shape; NOT in place, the edge term reads lr's
+ * neighbours), one thread per pixel.  With v = lr[b][y][x] and (w0, w1, w2, w3) the Philox words of the counter
+ * (y * size + x, first_sample + b, step, 0) under the key (seed_lo, seed_hi):
+ *   masked != 0 and v == 0.0f: a hole stays a hole, +0.0f, and nothing below runs;
+ *   e = fabsf(v - n) > edge_thr for any 4-neighbour n of lr inside the map (masked: a neighbour n == 0.0f does not count);
+ *   masked != 0 and (uint64)w1 < T(p_drop) + (e ? T(p_edge) : 0), T(P) = (uint64)floor(P * 2^32) in float64: +0.0f (dropout);
+ *   v' = v + (sigma + quad * (v * v)) * gauss[w0 >> 16], every fp32 operation rounded on its own; sigma, quad, edge_thr in
+ *   VALUE units;
+ *   masked != 0: out = lut[min(max((int)rintf(clamp(v', 0, 1) * (float)levels), 1), levels)], the snap of
+ *   the masked downsample (never code 0);  masked == 0: out = v', unclamped.
+ * gauss: 65 536 fp32 entries, gauss[u] = float32(inverse normal CDF((u + 0.5) / 65536)); lut and levels: the masked
+ * downsample's (levels + 1 entries).  w2 and w3 are reserved.  Refused on the host, before any HIP call: null pointers, lr == out,
+ * batch outside 1 .. CODON_TRAIN_MAX_BATCH, size outside 4 .. 512, levels outside 1 .. 65535, step or first_sample (+ batch)
+ * outside 32 bits, a negative or non-finite sigma / quad / edge_thr, a probability outside [0, 1], p_drop + p_edge > 1, and
+ * a non-zero probability with masked == 0 (without the masked upsample a dropped pixel would ring, not be left out). */
+typedef struct codon_sensor_desc {
+  int32_t batch;         /* samples in this launch */
+  int32_t size;          /* p: each sample's map is size x size */
+  int32_t masked;        /* 0: plain path (noise only, unsnapped); else: 0.0f is a hole, dropout allowed, output snapped */
+  int32_t reserved;
+  uint32_t seed_lo, seed_hi; /* the key: the low and high 32 bits of the 64-bit sensor seed */
+  int64_t step;          /* c2: the training step, 0 .. 2^32 - 1 */
+  int64_t first_sample;  /* c1 of sample 0: its index in the GLOBAL batch (the shard start) */
+  float sigma, quad, edge_thr, reserved_f;
+  double p_drop, p_edge;
+} codon_sensor_desc;
+int codon_philox4x32_10(const uint32_t* ctr, const uint32_t* key, uint32_t* out);
+int codon_lr_sensor(const codon_sensor_desc* desc, const float* lr, const float* gauss, const float* lut, int32_t levels,
+                    float* out, codon_stream_t stream);
 
 /* ---- D4 self-ensemble (codon_amd.ensemble.self_ensemble) ---------------------------------------------------
  * No reference counterpart: DEFINITIONS, in codon_amd/csrc/d4.hip, restated in numpy in tests/d4_ref.py, equal bits required.
