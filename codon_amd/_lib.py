@@ -77,6 +77,13 @@ class SensorDesc(C.Structure):                      # codon_sensor_desc
                 ("p_drop", C.c_double), ("p_edge", C.c_double)]
 
 
+class DepthErrorsDesc(C.Structure):                 # codon_depth_errors_desc
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("bits", C.c_int32),
+                ("label_height", C.c_int32), ("label_width", C.c_int32), ("label_row_stride", C.c_int64),
+                ("label_image_stride", C.c_int64), ("n_thresholds", C.c_int32), ("thresholds", C.c_int32 * 4),
+                ("edge", C.c_int32), ("edge_threshold", C.c_int32), ("edge_radius", C.c_int32)]
+
+
 class CastDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("src", C.c_void_p * CAST_MAX), ("count", C.c_int64 * CAST_MAX),
                 ("dtype", C.c_int32 * CAST_MAX)]
@@ -178,6 +185,7 @@ SIGNATURES = {
     "codon_lr_sensor": (C.c_int, [C.POINTER(SensorDesc), _P, _P, _P, _I, _P, _P]),
     "codon_d4_views": (C.c_int, [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     "codon_d4_merge": (C.c_int, [_I, _I, _I, _P, _P, _I, _P, _P]),
+    "codon_depth_errors": (C.c_int, [C.POINTER(DepthErrorsDesc), _P, _P, _P, _P, _P, _P]),
     "codon_weight_checksum_workspace_bytes": (_S, []),
     "codon_weight_checksum": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P]),
     "codon_weight_checksum_clear": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P, _I, _P]),

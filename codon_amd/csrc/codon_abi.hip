@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "codon_common.h"
+#include "eval_tile.h"
 #include "pair.h"
 #include "sensor_pixel.h"
 #include "train_record.h"
@@ -138,6 +139,7 @@ int train_crops_lr(const codon_crop_desc*, const unsigned char*, int, int, const
 int d4_views(int, int, int, const void*, const void*, int, void*, void*, void*, void*, hipStream_t);
 int d4_merge(int, int, int, const void*, const void*, int, float*, hipStream_t);
 int lr_sensor(const SensorArgs&, int, const float*, const float*, const float*, float*, hipStream_t);
+int depth_errors(const EvalArgs&, int, int, const void*, const void*, void*, unsigned char*, unsigned long long*, hipStream_t);
 size_t weight_checksum_workspace_bytes();
 int weight_checksum(const codon_wsum_desc*, void*, unsigned long long*, int, int*, int*, int, hipStream_t);
 
@@ -1066,6 +1068,50 @@ int codon_lr_sensor(const codon_sensor_desc* desc, const float* lr, const float*
   a.t_drop = (unsigned long long)floor(desc->p_drop * 4294967296.0);      // NaN fails the range checks above
   a.t_edge = (unsigned long long)floor(desc->p_edge * 4294967296.0);
   return lr_sensor(a, desc->batch, lr, gauss, lut, out, (hipStream_t)stream);
+}
+
+// ---- depth evaluation suite ---------------------------------------------------------------------------------
+int codon_depth_errors(const codon_depth_errors_desc* desc, const void* label, const void* out, uint64_t* acc, void* error_map,
+                       uint8_t* region_map, codon_stream_t stream) {
+  CODON_REQUIRE(desc && label && out && acc, CODON_ERR_BAD_ARG, "depth_errors: null pointer");
+  CODON_REQUIRE(desc->bits == 8 || desc->bits == 16, CODON_ERR_BAD_ARG, "depth_errors: bits %d (8 or 16)", desc->bits);
+  CODON_REQUIRE(shape_ok(desc->batch, desc->height, desc->width), CODON_ERR_BAD_ARG, "depth_errors: bad shape %dx%dx%d",
+                desc->batch, desc->height, desc->width);
+  CODON_REQUIRE((int64_t)desc->height * desc->width <= ((int64_t)1 << 26), CODON_ERR_UNSUPPORTED,
+                "depth_errors: %lld pixels per image (at most 2^26)", (long long)desc->height * desc->width);
+  CODON_REQUIRE(desc->batch <= 65535 && (desc->height + EV_TILE - 1) / EV_TILE <= 65535, CODON_ERR_UNSUPPORTED,
+                "depth_errors: %d images of %d rows (at most 65535 images and 65535 tile rows per launch)", desc->batch,
+                desc->height);
+  CODON_REQUIRE(desc->label_height >= desc->height && desc->label_width >= desc->width, CODON_ERR_BAD_ARG,
+                "depth_errors: a %dx%d label is smaller than the %dx%d output", desc->label_height, desc->label_width,
+                desc->height, desc->width);
+  CODON_REQUIRE(desc->label_row_stride >= desc->label_width && desc->label_image_stride >= 0 &&
+                    (desc->batch == 1 || desc->label_image_stride >= desc->label_row_stride * (desc->label_height - 1) + desc->label_width),
+                CODON_ERR_BAD_ARG, "depth_errors: label strides %lld (row), %lld (image) for %dx%d planes",
+                (long long)desc->label_row_stride, (long long)desc->label_image_stride, desc->label_height, desc->label_width);
+  CODON_REQUIRE(desc->bits == 8 || (((uintptr_t)label | (uintptr_t)out | (uintptr_t)error_map) & 1) == 0, CODON_ERR_BAD_ARG,
+                "depth_errors: unaligned u16 plane");
+  CODON_REQUIRE(desc->n_thresholds >= 0 && desc->n_thresholds <= EV_MAX_THRESHOLDS, CODON_ERR_BAD_ARG,
+                "depth_errors: %d thresholds (at most %d)", desc->n_thresholds, EV_MAX_THRESHOLDS);
+  EvalArgs a;
+  for (int k = 0; k < EV_MAX_THRESHOLDS; ++k) {
+    a.thr[k] = k < desc->n_thresholds ? desc->thresholds[k] : 0;
+    CODON_REQUIRE(a.thr[k] >= 0, CODON_ERR_BAD_ARG, "depth_errors: threshold %d is negative (%d)", k, a.thr[k]);
+  }
+  CODON_REQUIRE(desc->edge == 0 || desc->edge_threshold >= 0, CODON_ERR_BAD_ARG, "depth_errors: edge_threshold %d is negative",
+                desc->edge_threshold);
+  CODON_REQUIRE(desc->edge == 0 || (desc->edge_radius >= 0 && desc->edge_radius <= EV_RMAX), CODON_ERR_BAD_ARG,
+                "depth_errors: edge_radius %d (0..%d)", desc->edge_radius, EV_RMAX);
+  a.H = desc->height;
+  a.W = desc->width;
+  a.label_row = (long)desc->label_row_stride;
+  a.label_image = (long)desc->label_image_stride;
+  a.nthr = desc->n_thresholds;
+  a.edge = desc->edge != 0 ? 1 : 0;
+  a.edge_thr = a.edge ? desc->edge_threshold : 0;
+  a.r = a.edge ? desc->edge_radius : 0;
+  return depth_errors(a, desc->batch, desc->bits, label, out, error_map, region_map, (unsigned long long*)acc,
+                      (hipStream_t)stream);
 }
 
 size_t codon_weight_checksum_workspace_bytes(void) { return weight_checksum_workspace_bytes(); }

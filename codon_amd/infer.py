@@ -147,14 +147,18 @@ def _pinned_copy(t: torch.Tensor) -> torch.Tensor:
 
 
 def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None,
-             depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None, self_ensemble=False):
+             depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None, self_ensemble=False, report=None):
     """The test loop over every image pair.  Returns {"n", "rmse_mean", "ssim_mean", "seconds", "images_per_s"}.
     depth_bits=16: 16-bit depth and label files with codes 0 .. depth_max, outputs through metrics.postprocess_u16 into 16-bit
     PNGs, RMSE (metrics.masked_rmse_u16) in codes times depth_unit, SSIM of label / depth_max against out / depth_max.
     lr_depth (with scale; instead of input_depth): a directory of LOW-RESOLUTION depth maps, code 0 a hole -- the
     reader uploads the codes, and the main stream turns them into the depth input with codes_to_input ahead of the forward.
     self_ensemble: the forward of both loops becomes ensemble.self_ensemble(model, x, y) -- the mean over the eight
-    D4 views, fp32 whatever the model's dtype -- and post-processing takes that fp32 map."""
+    D4 views, fp32 whatever the model's dtype -- and post-processing takes that fp32 map.
+    report (needs label): {"thresholds": up to four codes, "edge_threshold": codes or None, "edge_radius": r,
+    "error_maps": a directory or None} -- one more launch per image (metrics.depth_errors); every line gains the key=value
+    tokens of metrics.depth_report (mad, rmse and max in codes times depth_unit), the error maps are written under the images'
+    names, and the result gains "reports" (the per-image dicts, with "file") and "report_means" (metrics.report_means)."""
     if (lr_depth is None) == (input_depth is None):
         raise ValueError("run_loop: exactly one of input_depth and lr_depth")
     if lr_depth is not None and scale not in (4, 8, 16):
@@ -183,6 +187,23 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
         forward = lambda x, y: _ensemble(model, x, y)                                                          # noqa: E731
     else:
         forward = model
+    if report is not None:
+        if not label:
+            raise ValueError("run_loop: report needs label")
+        rp_kw = {"thresholds": tuple(report.get("thresholds", ())), "edge_threshold": report.get("edge_threshold"),
+                 "edge_radius": report.get("edge_radius", 1)}
+        err_dir = report.get("error_maps")
+        reports = []
+
+        def errors(lab, out_u8):
+            """-> (the image's sixteen words on the device, its error map or None)"""
+            r_ = metrics.depth_errors(lab, out_u8, error_map=bool(err_dir), **rp_kw)
+            return (r_[0][0], r_[1]) if err_dir else (r_[0], None)
+
+        def tokens(f, words):
+            rep = metrics.depth_report(words, unit=1.0 if scale_rm is None else scale_rm, thresholds=rp_kw["thresholds"])
+            reports.append({"file": f, **rep})
+            return " " + metrics.report_tokens(rep)
     t0 = time.perf_counter()
     rm_sum = ss_sum = 0.0
     n = 0
@@ -197,6 +218,11 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
             ss = metrics.ssim(unit(lab[:h, :w]), unit(out_u8))
             rm_sum += rm; ss_sum += ss
             line += f" {rm} {ss}"
+            if report is not None:
+                words, emap = errors(lab, out_u8)
+                line += tokens(f, words.cpu())
+                if err_dir:
+                    write(os.path.join(err_dir, f), emap.cpu().numpy())
         n += 1
         return out_u8, line
 
@@ -244,10 +270,12 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                     item = q_out.get()
                     if item is None:
                         return
-                    f, host_u8, ev = item
+                    f, host_u8, ev, *host_err = item
                     ev.synchronize()                               # the download of this image has landed
                     if out_dir:
                         write(os.path.join(out_dir, f), host_u8.numpy())
+                    if host_err:
+                        write(os.path.join(err_dir, f), host_err[0].numpy())
             except BaseException as e:      # noqa: BLE001
                 errs.append(e)
 
@@ -255,7 +283,7 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
             """Metrics of an image whose launches were enqueued one image ago: its three numbers have been downloaded behind
             its kernels; the same host arithmetic as metrics.masked_rmse / metrics.ssim."""
             nonlocal rm_sum, ss_sum, n
-            f, h_acc, h_ss, ev = pend
+            f, h_acc, h_ss, ev, *h_rep = pend
             line = f
             if h_acc is not None:
                 ev.synchronize()
@@ -263,6 +291,8 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                 rm, ss = math.sqrt(s_ / c_) if scale_rm is None else math.sqrt(s_ / c_) * scale_rm, float(h_ss.item())
                 rm_sum += rm; ss_sum += ss
                 line += f" {rm} {ss}"
+                if h_rep:
+                    line += tokens(f, h_rep[0])
             n += 1
             emit(line)
 
@@ -284,6 +314,7 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                     out = forward(to_x(devs[0]), devs[1])
                 out_u8 = post(out[0, 0])
                 h_acc = h_ss = None
+                h_rep, host_err = [], []
                 if len(devs) > 2:                                  # metrics stay on the device; read back one image later
                     lab = devs[2]
                     acc = sqerr(lab, out_u8)
@@ -292,14 +323,21 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                     h_ss = torch.empty(1, dtype=torch.float64, pin_memory=True)
                     h_acc.copy_(acc, non_blocking=True)
                     h_ss.copy_(ssv, non_blocking=True)
+                    if report is not None:                         # sixteen more words (and the error map) behind the same kernels
+                        words, emap = errors(lab, out_u8)
+                        h_rep = [torch.empty(metrics.EVAL_WORDS, dtype=torch.int64, pin_memory=True)]
+                        h_rep[0].copy_(words, non_blocking=True)
+                        if emap is not None:
+                            host_err = [torch.empty(emap.shape, dtype=emap.dtype, pin_memory=True)]
+                            host_err[0].copy_(emap, non_blocking=True)
                 host_u8 = torch.empty(out_u8.shape, dtype=out_u8.dtype, pin_memory=True)
                 host_u8.copy_(out_u8, non_blocking=True)
                 dv = torch.cuda.Event()
                 dv.record(main_s)
-                q_out.put((f, host_u8, dv))
+                q_out.put((f, host_u8, dv, *host_err))
                 if pending is not None:
                     settle(pending)                                # image i-1, while image i runs
-                pending = (f, h_acc, h_ss, dv)
+                pending = (f, h_acc, h_ss, dv, *h_rep)
             if pending is not None:
                 settle(pending)
         finally:
@@ -317,8 +355,53 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
             raise errs[0]
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
-    return {"n": n, "rmse_mean": rm_sum / n if (label and n) else None, "ssim_mean": ss_sum / n if (label and n) else None,
-            "seconds": dt, "images_per_s": n / dt if dt > 0 else 0.0}
+    res = {"n": n, "rmse_mean": rm_sum / n if (label and n) else None, "ssim_mean": ss_sum / n if (label and n) else None,
+           "seconds": dt, "images_per_s": n / dt if dt > 0 else 0.0}
+    if report is not None:
+        res.update(reports=reports, report_means=metrics.report_means(reports))
+    return res
+
+
+def write_report_json(path, reports, means):
+    """{"images": the per-image dicts, "means": {key: [mean, count]}} as STRICT JSON: a value over an empty set, nan in the
+    dicts (an image without a discontinuity, or no --edge-threshold), is written as null."""
+    import json
+    clean = lambda v: None if isinstance(v, float) and math.isnan(v) else v                        # noqa: E731
+    doc = {"images": [{k: clean(v) for k, v in r.items()} for r in reports],
+           "means": {k: [clean(v[0]), v[1]] for k, v in means.items()}}
+    with open(path, "w") as fh:
+        json.dump(doc, fh, indent=1, allow_nan=False)
+
+
+def add_report_args(ap, prefix=""):
+    """The parameter flags of the evaluation report, shared with codon_amd.train (prefix "val-")."""
+    ap.add_argument(f"--{prefix}bad-thresholds", default=None, metavar="A,B,...",
+                    help="report: up to four bad-pixel thresholds in codes; bad>T is the fraction of valid pixels off by more than T")
+    ap.add_argument(f"--{prefix}edge-threshold", type=int, default=None, metavar="CODES",
+                    help="report: split the error into an edge region and the rest; a valid label pixel with a valid 4-neighbour "
+                         "more than this many codes away is a discontinuity (the sensor model's rule)")
+    ap.add_argument(f"--{prefix}edge-radius", type=int, default=None, metavar="R",
+                    help="report: the edge region is every valid pixel within R pixels (Chebyshev, 0..8, default 1) of a discontinuity")
+
+
+def report_of(ap, a, prefix=""):
+    """The run_loop report dict of the parsed parameter flags (without "error_maps"); refusals through ap.error."""
+    key = prefix.replace("-", "_")
+    thr, edge, rad = (getattr(a, key + n) for n in ("bad_thresholds", "edge_threshold", "edge_radius"))
+    try:
+        thr = tuple(int(t) for t in thr.split(",")) if thr else ()
+    except ValueError:
+        ap.error(f"--{prefix}bad-thresholds {thr!r}: integers in codes, separated by commas")
+    if len(thr) > metrics.EVAL_MAX_THRESHOLDS or any(t < 0 for t in thr):
+        ap.error(f"--{prefix}bad-thresholds takes at most {metrics.EVAL_MAX_THRESHOLDS} thresholds, none negative")
+    if edge is not None and edge < 0:
+        ap.error(f"--{prefix}edge-threshold {edge} must not be negative")
+    if rad is not None and edge is None:
+        ap.error(f"--{prefix}edge-radius needs --{prefix}edge-threshold")
+    rad = 1 if rad is None else rad
+    if not 0 <= rad <= metrics.EVAL_MAX_RADIUS:
+        ap.error(f"--{prefix}edge-radius {rad} must lie in [0, {metrics.EVAL_MAX_RADIUS}]")
+    return {"thresholds": thr, "edge_threshold": edge, "edge_radius": rad}
 
 
 def main(argv=None):
@@ -349,7 +432,21 @@ def main(argv=None):
     ap.add_argument("--depth-max", type=int, default=None, help="with --depth-bits 16: the code of 1.0 (default 65535)")
     ap.add_argument("--depth-unit", type=float, default=1.0,
                     help="with --depth-bits 16: the printed RMSE is in codes times this (0.1: centimetres from millimetre codes)")
+    ap.add_argument("--report", action="store_true",
+                    help="with --label: append the evaluation suite's key=value tokens (MAD, RMSE, max, bad-pixel rates, delta "
+                         "accuracies, edge / flat split) to every image's line and print a last line of their means")
+    add_report_args(ap)
+    ap.add_argument("--report-json", default=None, metavar="FILE", help="report: write the per-image values and the means here (JSON; a value over an empty set is null)")
+    ap.add_argument("--error-maps", default=None, metavar="DIR",
+                    help="report: write every image's error map |label - output| (0 at holes) as a PNG of the data's depth")
     a = ap.parse_args(argv)
+    if a.report and not a.label:
+        ap.error("--report needs --label")
+    if not a.report:
+        for n in ("bad_thresholds", "edge_threshold", "edge_radius", "report_json", "error_maps"):
+            if getattr(a, n) is not None:
+                ap.error(f"--{n.replace('_', '-')} needs --report")
+    report = {**report_of(ap, a), "error_maps": a.error_maps} if a.report else None
     if (a.input_depth is None) == (a.lr_depth is None):
         ap.error("exactly one of --input-depth and --lr-depth is required")
     if a.ema and not a.weights:
@@ -371,13 +468,19 @@ def main(argv=None):
     model = model.to(dev).to(tdt).eval()
     if a.out:
         os.makedirs(a.out, exist_ok=True)
+    if a.error_maps:
+        os.makedirs(a.error_maps, exist_ok=True)
     r = run_loop(model, dev, tdt, a.input_depth, a.input_color, a.label, a.out, pipelined=not a.serial,
                  depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit,
-                 **({"self_ensemble": True} if a.self_ensemble else {}),
+                 **({"self_ensemble": True} if a.self_ensemble else {}), **({"report": report} if report else {}),
                  **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}))
     print(r["n"])
     if a.label and r["n"]:
         print(r["rmse_mean"], r["ssim_mean"])
+    if report and r["n"]:
+        print("mean " + metrics.report_tokens(r["report_means"]))
+    if a.report_json:
+        write_report_json(a.report_json, r.get("reports", []), r.get("report_means", {}))
     return 0
 
 

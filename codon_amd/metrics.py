@@ -2,6 +2,8 @@
   postprocess_u8  clip -> *255 -> truncating uint8          /root/reference/CODON_X4/test.py:127-132
   masked_rmse     RMSE over label != 0, exact integer sums   /root/reference/CODON_X4/test.py:148-164
   postprocess_u16, masked_rmse_u16   their 16-bit counterparts: definitions of this project, no reference
+  depth_errors, depth_report   the evaluation suite: MAD, RMSE, max, bad-pixel rates, delta accuracies and the
+                  edge / flat split from sixteen exact integer words per image, one launch; definitions of this project
   ssim            ssim_exact(img1, img2)                     /root/reference/CODON_X4/ssim_2.py:36-52
   L1SSIMLoss      w_l1 * mean|p - t| + w_ssim * (1 - SSIM(p, t)) with a HIP backward (the reference ships no
                   loss -- SURVEY D8 -- so the combination is this repo's; the SSIM value is pinned).
@@ -111,6 +113,105 @@ def masked_sqerr_u16_dev(label_u16: torch.Tensor, out_u16: torch.Tensor) -> torc
 def masked_rmse_u16(label_u16: torch.Tensor, out_u16: torch.Tensor) -> float:
     """masked_rmse in 16-bit codes: label cropped to the output's size, label == 0 excluded."""
     return _rmse(_as_u16(label_u16), _as_u16(out_u16))
+
+
+# ---- depth evaluation suite (DESIGN 12.8) ---------------------------------------------------------------------------------------
+
+EVAL_WORDS, EVAL_MAX_THRESHOLDS, EVAL_MAX_RADIUS = 16, 4, 8
+
+
+def depth_errors(label: torch.Tensor, out: torch.Tensor, *, thresholds=(), edge_threshold=None, edge_radius=1,
+                 error_map=False, region_map=False):
+    """The evaluation words of (H, W) or (B, H, W) code planes in ONE launch (codon_depth_errors), no host synchronisation:
+    a DEVICE int64 (B, 16) tensor per image -- 0 n, 1 sum e, 2 sum e^2, 3 max e, 4-7 #{e > thresholds[k]}, 8-10 the delta < 1.25 /
+    1.25^2 / 1.25^3 inliers, 11-13 n, sum e, sum e^2 over the edge region, 14-15 zero -- over the pixels with label != 0,
+    e = |label - out| in codes, exact integers (depth_report turns a row into MAD, RMSE, rates).  Both planes uint8, or both u16
+    codes held as uint16 or int16 bits.  The label is at least as large as the output and is read top-left through its own
+    strides (no cropped copy; only a layout whose rows or images overlap or whose pixels are not adjacent, such as a label
+    expanded over the batch, is copied first).  thresholds: up to four integers >= 0, codes.  edge_threshold None: no edge evaluation; else
+    the edge region is every valid pixel within Chebyshev distance edge_radius (0..8) of a valid pixel that has a valid
+    4-neighbour differing by more than edge_threshold codes (the sensor model's edge rule).
+    Returns the words alone, or (words, error map, region map) with the maps asked for: the error map has the codes' own dtype
+    (e where valid, else 0), the region map is uint8 (0 hole, 1 valid and flat, 2 valid and in the edge region)."""
+    lib = L.load()
+    if label.dtype != out.dtype and {label.dtype, out.dtype} == {torch.int16, torch.uint16}:
+        label = label.view(out.dtype)                 # the same bits
+    if label.dtype != out.dtype or out.dtype not in (torch.uint8, torch.uint16, torch.int16):
+        raise ValueError(f"depth_errors: label {label.dtype} and output {out.dtype} (both uint8, or both u16 codes as uint16 / int16)")
+    if label.dim() != out.dim() or out.dim() not in (2, 3):
+        raise ValueError(f"depth_errors: planes of shape {tuple(label.shape)} and {tuple(out.shape)} ((H, W) or (B, H, W))")
+    single = out.dim() == 2
+    if single:
+        label, out = label[None], out[None]
+    if label.shape[0] != out.shape[0]:
+        raise ValueError(f"depth_errors: {label.shape[0]} labels for {out.shape[0]} outputs")
+    thresholds = tuple(thresholds)
+    if any(int(t) != t for t in thresholds) or (edge_threshold is not None and int(edge_threshold) != edge_threshold) \
+            or int(edge_radius) != edge_radius:
+        raise ValueError("depth_errors: thresholds, edge_threshold and edge_radius are integers (codes, pixels)")
+    wide, carrier = out.dtype != torch.uint8, out.dtype
+    if wide:
+        label, out = label.view(torch.int16), out.view(torch.int16)     # the same bits, in a dtype every device op takes
+    Bl, Hl, Wl = label.shape
+    if label.stride(2) != 1 or label.stride(1) < Wl or (Bl > 1 and label.stride(0) < label.stride(1) * (Hl - 1) + Wl):
+        label = label.contiguous()                    # a layout the entry does not take (an expanded batch, a transposed plane)
+    out = out.contiguous()
+    dev = ops._dev(out)                               # the label goes by its strides: a window of a larger plane is welcome
+    if label.device != dev:
+        raise RuntimeError("codon_amd: tensors on different devices")
+    B, H, W = out.shape
+    d = L.DepthErrorsDesc(B, H, W, 16 if wide else 8, label.shape[1], label.shape[2], label.stride(1), label.stride(0),
+                          len(thresholds), (C.c_int32 * 4)(*(int(t) for t in thresholds[:EVAL_MAX_THRESHOLDS])),
+                          0 if edge_threshold is None else 1, 0 if edge_threshold is None else int(edge_threshold),
+                          int(edge_radius))
+    acc = torch.empty((B, EVAL_WORDS), dtype=torch.int64, device=dev)
+    err = torch.empty_like(out) if error_map else None
+    reg = torch.empty(out.shape, dtype=torch.uint8, device=dev) if region_map else None
+    with torch.cuda.device(dev):
+        L.check(lib.codon_depth_errors(C.byref(d), _p(label), _p(out), _p(acc), _p(err), _p(reg), ops._stream(dev)), "depth_errors")
+    err = err.view(carrier) if err is not None else None
+    maps = tuple(m[0] if single else m for m in (err, reg) if m is not None)
+    return (acc, *maps) if maps else acc
+
+
+def depth_report(acc_row, *, unit: float = 1.0, thresholds=()) -> dict:
+    """One image's sixteen words (a row of depth_errors, on the host) as numbers, in Python floats: n; mad, rmse and max in
+    codes times `unit`; "bad>t" for every threshold t (the fraction of valid pixels whose error exceeds t codes); delta1,
+    delta2, delta3 (the fractions with max(l/o, o/l) < 1.25, 1.25^2, 1.25^3); edge_fraction = n_E / n; edge_mad, edge_rmse
+    over the edge region and flat_mad, flat_rmse over the rest (words 0-2 minus words 11-13).  rmse is sqrt(word 2 / word 0):
+    with unit 1 it equals masked_rmse / masked_rmse_u16 of the same planes to the bit.  A value over an empty set is nan (an
+    image without a discontinuity is legitimate); n = 0 raises ZeroDivisionError, as the inference loop does."""
+    w = [int(v) for v in acc_row]
+    if len(w) != EVAL_WORDS:
+        raise ValueError(f"depth_report: {len(w)} words (one row of depth_errors has {EVAL_WORDS})")
+    thresholds = tuple(thresholds)
+    if len(thresholds) > EVAL_MAX_THRESHOLDS:
+        raise ValueError(f"depth_report: {len(thresholds)} thresholds (at most {EVAL_MAX_THRESHOLDS})")
+    unit = float(unit)
+    n, n_e = w[0], w[11]
+    mean = lambda s, c: s / c if c else math.nan                                                       # noqa: E731
+    r = {"n": n, "mad": w[1] / n * unit, "rmse": math.sqrt(w[2] / n) * unit, "max": w[3] * unit}
+    for k, t in enumerate(thresholds):
+        r[f"bad>{t}"] = w[4 + k] / n
+    r.update(delta1=w[8] / n, delta2=w[9] / n, delta3=w[10] / n, edge_fraction=n_e / n,
+             edge_mad=mean(w[12], n_e) * unit, edge_rmse=math.sqrt(mean(w[13], n_e)) * unit,
+             flat_mad=mean(w[1] - w[12], n - n_e) * unit, flat_rmse=math.sqrt(mean(w[2] - w[13], n - n_e)) * unit)
+    return r
+
+
+def report_means(reports) -> dict:
+    """Means of depth_report dicts over the images: {key: [mean over the images whose value is not nan, their count]}; the
+    mean of no image is nan.  Every float-valued key: n and whatever the caller added (a file name) are left out."""
+    out = {}
+    for k in (k for k, v in (reports[0] if reports else {}).items() if isinstance(v, float)):
+        vs = [r[k] for r in reports if not math.isnan(r[k])]
+        out[k] = [sum(vs) / len(vs) if vs else math.nan, len(vs)]
+    return out
+
+
+def report_tokens(r: dict) -> str:
+    """ key=value tokens of a depth_report dict, or of report_means (key=mean/count)."""
+    return " ".join(f"{k}={v[0]!r}/{v[1]}" if isinstance(v, list) else f"{k}={v!r}" for k, v in r.items())
 
 
 def _ssim_forward(a, b, want_maps):

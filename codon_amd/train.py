@@ -39,8 +39,9 @@ import torch
 from . import CODONNet, CODONNet16, io
 from . import _lib as L
 from . import ops
-from .infer import run_loop
+from .infer import add_report_args, report_of, run_loop
 from .io import check_depth_max, list_pairs, read_depth_plane
+from .metrics import report_tokens
 from .upsample import (_on_device, code_table, down_weights, gauss_table, lut16,      # noqa: F401 (lut16: for importers)
                        phase_weights, u8_lut)
 
@@ -590,10 +591,14 @@ def validate(model, dev, val: dict, emit=print) -> dict:
             deep = {"depth_bits": 16, "depth_max": val.get("depth_max", 65535)} if val.get("depth_bits", 8) == 16 else {}
             if val.get("lr_depth"):                 # low-resolution validation maps, upsampled as infer --lr-depth does
                 deep.update(lr_depth=val["lr_depth"], scale=val["scale"])
+            if val.get("report") is not None:       # the evaluation suite of infer --report
+                deep.update(report=val["report"])
             r = run_loop(model, dev, torch.float32, val.get("depth"), val["color"], val.get("label"), emit=lambda s: None, **deep)
     finally:
         model.train()
     emit(f"val {r['n']} images rmse {r['rmse_mean']} ssim {r['ssim_mean']}")
+    if val.get("report") is not None:
+        emit("val-report " + report_tokens(r["report_means"]))
     return r
 
 
@@ -653,6 +658,10 @@ def parse_args(argv=None):
     ap.add_argument("--val-color", default=None)
     ap.add_argument("--val-label", default=None)
     ap.add_argument("--val-every", type=int, default=1000)
+    ap.add_argument("--val-report", action="store_true",
+                    help="with --val-label: a second line per validation, `val-report ...`, with the means of the evaluation "
+                         "suite of `codon_amd.infer --report` over the validation set")
+    add_report_args(ap, "val-")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--clip-norm", type=float, default=None, help="clip the global gradient norm to this (on the device)")
     ap.add_argument("--skip-nonfinite", action="store_true",
@@ -677,6 +686,13 @@ def parse_args(argv=None):
         ap.error("--val-depth and --val-lr-depth exclude each other")
     if (a.val_depth is None and a.val_lr_depth is None) != (a.val_color is None):
         ap.error("--val-depth (or --val-lr-depth) and --val-color go together")
+    if a.val_report and a.val_label is None:
+        ap.error("--val-report needs --val-label")
+    if not a.val_report:
+        for n in ("val_bad_thresholds", "val_edge_threshold", "val_edge_radius"):
+            if getattr(a, n) is not None:
+                ap.error(f"--{n.replace('_', '-')} needs --val-report")
+    a.val_report_params = report_of(ap, a, "val-") if a.val_report else None
     if a.train_lr_depth is not None and a.train_label is not None:
         ap.error("--train-lr-depth and --train-label exclude each other (with low-resolution maps --train-depth is the target)")
     if a.train_lr_depth is not None and a.degrade_holes:
@@ -795,6 +811,8 @@ def main(argv=None, emit=print) -> dict:
             "depth_bits": a.depth_bits, "depth_max": a.depth_max} if a.val_depth or a.val_lr_depth else None)
     if a.val_lr_depth:
         val.update(lr_depth=a.val_lr_depth, scale=a.scale)
+    if val is not None and a.val_report_params is not None:
+        val.update(report=a.val_report_params)
     ckpt = {"path": a.save, "every": a.save_every} if a.save else None
     kw = {"sensor": sensor_of(a)} if sensor_of(a) is not None else {}      # without a model fit is called as ever
     res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,

@@ -766,6 +766,50 @@ int codon_d4_views(int32_t batch, int32_t height, int32_t width, const void* src
 int codon_d4_merge(int32_t batch, int32_t height, int32_t width, const void* upright, const void* transposed, int32_t dtype,
                    float* out_f32, codon_stream_t stream);
 
+/* ---- depth evaluation suite (codon_amd.metrics.depth_errors) ------------------------------------------------
+ * No reference counterpart (the reference prints one masked RMSE): DEFINITIONS, in codon_amd/csrc/eval.hip and eval_tile.h,
+ * restated in numpy in tests/eval_ref.py, equal bits required.  Integers only.
+ *
+ * codon_depth_errors: ONE launch over a batch of code planes, all u8 (bits 8) or all u16 (bits 16): the output out
+ * (batch, height, width), contiguous, and the label, image b at label + b * label_image_stride, its rows label_row_stride
+ * elements apart, label_height x label_width >= height x width and read top-left -- the window is the output's, and no label
+ * pixel beyond it is read, not even as a neighbour.  Per pixel: valid v = (L != 0), e = |L - O|.  acc: (batch, 16) uint64,
+ * zeroed by this entry on the stream, then per image
+ *   word 0      n = #v
+ *   word 1      sum_v e
+ *   word 2      sum_v e^2 (each square formed in 64 bits)
+ *   word 3      max_v e (0 when n = 0)
+ *   words 4-7   #{v, e > thresholds[k]}, k < n_thresholds (unused thresholds: 0)
+ *   words 8-10  delta inliers in integers: #{v, 4 max(L,O) < 5 min(L,O)}, then 16 max < 25 min, then 64 max < 125 min
+ *               (O = 0 is never an inlier)
+ *   word 11     n_E = #E
+ *   word 12     sum_E e
+ *   word 13     sum_E e^2
+ *   words 14-15 reserved, written as 0
+ * Edge region E (edge != 0): a pixel is a discontinuity when it is valid and some 4-neighbour inside the window is valid and
+ * differs from it by more than edge_threshold codes (codon_lr_sensor's rule); E = the valid pixels within Chebyshev distance
+ * edge_radius of a discontinuity.  edge == 0: words 11-13 are 0 and no neighbour is read.
+ * error_map (NULL, or (batch, height, width) of the codes' type): e where valid, 0 elsewhere.  region_map (NULL, or (batch,
+ * height, width) uint8): 0 hole, 1 valid outside E, 2 valid in E.
+ * Bound: e <= 65535, e^2 < 2^32, height * width <= 2^26, so no word exceeds 2^58.  Refused on the host, before any HIP call:
+ * null pointers, bits other than 8 or 16, an unaligned u16 plane, a bad shape, more than 2^26 pixels per image, more than 65535
+ * images or tile rows, a label smaller than the output or a row stride below label_width, n_thresholds outside 0..4, a
+ * negative threshold, a negative edge_threshold, edge_radius outside 0..8. */
+typedef struct codon_depth_errors_desc {
+  int32_t batch, height, width;        /* the output planes = the evaluation window */
+  int32_t bits;                        /* 8: uint8 codes, 16: uint16 codes (label, out and error_map alike) */
+  int32_t label_height, label_width;   /* the label planes, at least height x width */
+  int64_t label_row_stride;            /* elements between label rows (>= label_width) */
+  int64_t label_image_stride;          /* elements between label images */
+  int32_t n_thresholds;                /* 0..4 */
+  int32_t thresholds[4];               /* codes, >= 0 */
+  int32_t edge;                        /* 0: no edge evaluation */
+  int32_t edge_threshold;              /* T, codes, >= 0 */
+  int32_t edge_radius;                 /* r, 0..8 */
+} codon_depth_errors_desc;
+int codon_depth_errors(const codon_depth_errors_desc* desc, const void* label, const void* out, uint64_t* acc,
+                       void* error_map, uint8_t* region_map, codon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
