@@ -13,6 +13,9 @@ from tests.util import rel_rmse, rmse
 
 DT = [torch.bfloat16, torch.float16]
 SHAPES = [(2, 19, 45), (1, 1, 1), (1, 33, 70), (2, 64, 40), (1, 5, 3)]
+# beyond the smallest launch forms (tests/forms.py): mid-v4 = stem<4>, the 2048-pixel statistics form, a 33-tile backward;
+# mid-v1 = the same with two images, an odd width and an odd H W
+MID_SHAPES = [(1, 253, 260), (2, 127, 261)]
 
 
 def _dev():
@@ -49,7 +52,7 @@ def test_layout_round_trip_and_addressing():
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", SHAPES + MID_SHAPES)
 def test_stem_and_masked_flipped_stencil(shape, dtype):
     from codon_amd import ops
     from codon_amd.ops import Slice
@@ -95,7 +98,7 @@ def test_head_and_conv1ch_wgrad(shape, dtype):
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", SHAPES + MID_SHAPES)
 def test_cac_forward_passes(shape, dtype):
     from codon_amd import ops
     from codon_amd.ops import Slice
@@ -251,7 +254,7 @@ def test_ew_sum_mask(shape, dtype):
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("shape", [(2, 19, 45), (1, 1, 1), (1, 50, 70)])
+@pytest.mark.parametrize("shape", [(2, 19, 45), (1, 1, 1), (1, 50, 70)] + MID_SHAPES)
 @pytest.mark.parametrize("accumulate_in", [False, True])
 def test_cac_backward(shape, dtype, accumulate_in):
     """All four CAC backward launches on blocked tensors vs the fp32 kernels on the same 16-bit-representable values:
