@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "codon_common.h"
+#include "kernels.h"
 
 namespace codon {
 

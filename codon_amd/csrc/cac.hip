@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "codon_common.h"
+#include "kernels.h"
 #include "px8.h"
 
 namespace codon {
@@ -224,12 +225,6 @@ __global__ __launch_bounds__(256) void cac_apply_kernel(const ApplyStream<typena
   for (int i = 0; i < 8; ++i) v[i] = fmaf(v[i], gc * g[i], q[i]);
   P::store(s.out + b * s.out_img + c * HW, tile0, tid, HW, v);
 }
-
-// ew_c8.hip: the same passes over channel-blocked 16-bit tensors
-int cac_stats_fwd_c8(int, int, int, const codon_tensor*, const codon_tensor*, float*, float*, int, hipStream_t, const float*);
-int cac_apply_fwd_c8(int, int, int, const codon_tensor*, const codon_tensor*, const float*, const float*, const codon_tensor*,
-                     const codon_tensor*, const codon_tensor*, const codon_tensor*, int, hipStream_t);
-int ew_sq_scale_c8(int, int, int, const codon_tensor*, const float*, const codon_tensor*, int, hipStream_t);
 
 static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
   return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |

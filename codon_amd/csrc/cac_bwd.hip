@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "codon_common.h"
+#include "kernels.h"
 #include "px8.h"
 
 namespace codon {
@@ -409,15 +410,6 @@ __global__ __launch_bounds__(256) void ew_add_mask_kernel(typename P::T* __restr
 }
 
 // ---- host ------------------------------------------------------------------------------------------
-// ew_c8.hip: passes A and D and the elementwise helper over channel-blocked 16-bit tensors
-int cac_bwd_reduce_c8(int, int, int, const codon_tensor*, const codon_tensor*, const codon_tensor*, const codon_tensor*,
-                      const float*, const float*, const float*, float*, float*, int*, int, hipStream_t, const float*, int*,
-                      const codon_tensor*, const codon_tensor*, int);
-int cac_bwd_apply_c8(int, int, int, const codon_tensor*, const codon_tensor*, const codon_tensor*, const codon_tensor*,
-                     const float*, const float*, const float*, const float*, const float*, const int*, const codon_tensor*,
-                     const codon_tensor*, const codon_tensor*, const codon_tensor*, int, int, hipStream_t);
-int ew_add_mask_c8(int, int, int, int, const codon_tensor*, const codon_tensor*, const codon_tensor*, int, int, hipStream_t);
-int ew_sum_mask_c8(int, int, int, int, const codon_tensor*, int, const codon_tensor* const*, const codon_tensor*, int, hipStream_t);
 static bool al16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
   return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
            reinterpret_cast<uintptr_t>(d)) % 16) == 0;

@@ -7,6 +7,7 @@
 #include <hip/hip_fp16.h>
 
 #include "codon_common.h"
+#include "kernels.h"
 
 namespace codon {
 

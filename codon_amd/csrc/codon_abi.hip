@@ -7,6 +7,7 @@
 
 #include "codon_common.h"
 #include "eval_tile.h"
+#include "kernels.h"
 #include "pair.h"
 #include "sensor_pixel.h"
 #include "train_record.h"
@@ -30,118 +31,6 @@ int check_launch(const char* what) {
   }
   return CODON_OK;
 }
-
-// kernels (defined in the other translation units)
-int conv_ck(int ks);
-int conv2d_fwd_f32(const codon_conv_desc*, const float*, const float*, float*, const float*, hipStream_t);
-size_t conv_wgrad_workspace_bytes(const codon_conv_desc*);
-int conv2d_wgrad_f32(const codon_conv_desc*, const float*, const float*, float*, float*, size_t, int, hipStream_t);
-size_t conv_wgrad_bf16_workspace_bytes(const codon_conv_desc*);
-int conv2d_wgrad_bf16(const codon_conv_desc*, const void*, const void*, float*, float*, size_t, int, hipStream_t);
-int pack_weight_f32(const float*, float*, int, int, int, int, hipStream_t);
-int pack_chain1x1_f32(const float*, float*, hipStream_t);
-int conv2d_gated_fwd_f32(const codon_conv_desc*, const float*, const codon_tensor*, const float*, const float*, const float*,
-                         float*, const codon_tensor*, hipStream_t);
-int pack_chain1x1_16(const float*, void*, int, hipStream_t);
-int pack_chain1x1_f32x3(const float*, void*, hipStream_t);
-int conv_chain1x1_fwd_f32x3(const codon_conv_desc*, const float*, const void*, float*, const void*, const codon_tensor*,
-                            const codon_tensor*, hipStream_t);
-int conv_chain1x1_fwd_16(const codon_conv_desc*, const void*, const void*, void*, const void*, const codon_tensor*,
-                         const codon_tensor*, float*, float*, int, hipStream_t);
-int conv2d_gated_fwd_16(const codon_conv_desc*, const void*, const codon_tensor*, const float*, const float*, const void*,
-                        void*, const codon_tensor*, hipStream_t);
-struct Conv1x1GateBwd {
-  const float* ch; const float* sp; const float* g_pooled; const float* g_pools; const int* argpix; const int* argch;
-  int fbase;
-};
-int conv1x1_bwd_16(const codon_conv_desc*, const void*, const void*, const void*, const codon_tensor*, float*, float*, size_t,
-                   int, hipStream_t, const Conv1x1GateBwd*);
-int cac_bwd_reduce_acc(int, int, int, const codon_tensor*, const codon_tensor*, const codon_tensor*, const codon_tensor*,
-                       const float*, const float*, const float*, const float*, float*, float*, int*, int*, const codon_tensor*,
-                       const codon_tensor*, int, int, hipStream_t);
-int cac_fused_tiles(int, int);
-int cac_tail_fwd(int, int, int, int, const float*, const float*, const float*, const float*, float*, float*, int*, const float*,
-                 const float*, const float*, const float*, const float*, float*, float*, float*, hipStream_t);
-int cac_fused_finish(int, int, int, int, const float*, const float*, const float*, float*, float*, hipStream_t);
-int cac_gate_fwd_n(int, int, float, const float*, const float*, const float*, const float*, const float*, float*, float*,
-                   hipStream_t);
-int conv_tiling_f32(const codon_conv_desc*, int, int);
-int conv_form_c8(const codon_conv_desc*);
-int conv_chain1x1_fwd_f32(const codon_conv_desc*, const float*, const float*, float*, const float*, const codon_tensor*,
-                          const codon_tensor*, float*, float*, int, hipStream_t);
-bool conv_f32x3_supported(const codon_conv_desc*);
-int conv2d_fwd_f32x3(const codon_conv_desc*, const float*, const void*, float*, const float*, hipStream_t);
-int pack_weight_f32x3(const float*, void*, int, int, int, hipStream_t);
-int stem_fwd(int, int, int, const float*, const float*, void*, int, int, int, const void*, int, int, int, int*, int*, hipStream_t);
-int stem_pair_fwd(int, int, int, const float*, const float*, void*, int, int, const float*, const float*, void*, int, int, int,
-                  int*, int*, int*, hipStream_t);
-size_t conv1ch_wgrad_workspace_bytes(int, int, int);
-int conv1ch_wgrad(int, int, int, const void*, int, int, const float*, float*, int, float*, size_t, int, hipStream_t);
-int cac_bwd_tiles(int, int);
-int cac_bwd_spatial_blocks(int, int, int);
-int cac_bwd_reduce(int, int, int, const codon_tensor*, const codon_tensor*, const codon_tensor*, const codon_tensor*,
-                   const float*, const float*, const float*, float*, float*, int*, int, hipStream_t);
-int cac_bwd_gate(int, int, int, const float*, const int*, const float*, const float*, const float*, const float*,
-                 const float*, float*, int*, float*, float*, float*, float*, float*, hipStream_t);
-int cac_bwd_spatial(int, int, int, const float*, const float*, const float*, float*, float*, float*, hipStream_t);
-int cac_bwd_apply(int, int, int, const codon_tensor*, const codon_tensor*, const codon_tensor*, const codon_tensor*,
-                  const float*, const float*, const float*, const float*, const float*, const int*,
-                  const codon_tensor*, const codon_tensor*, const codon_tensor*, const codon_tensor*, int, int,
-                  hipStream_t);
-int ew_add_mask(int, int, int, int, const codon_tensor*, const codon_tensor*, const codon_tensor*, int, int,
-                hipStream_t);
-int ew_sum_mask(int, int, int, int, const codon_tensor*, int, const codon_tensor* const*, const codon_tensor*, int, hipStream_t);
-int head_fwd(int, int, int, const void*, int, int, const float*, const float*, void*, bool, int, const int*, hipStream_t);
-int cac_stats_tiles(int, int);
-int cac_stats_fwd(int, int, int, const codon_tensor*, const codon_tensor*, float*, float*, int, hipStream_t, const float*);
-int ew_sq_scale(int, int, int, const codon_tensor*, const float*, const codon_tensor*, int, hipStream_t);
-int conv2d_fwd_bf16(const codon_conv_desc*, const void*, const void*, void*, const void*, hipStream_t);
-int conv2d_sum_into_16(const codon_conv_desc*, const void*, const void*, void*, void*, hipStream_t);
-int pack_weight_bf16(const float*, void*, int, int, int, int, int, hipStream_t);
-int cac_gate_fwd(int, int, int, const float*, const float*, const float*, const float*, const float*, float*, float*,
-                 hipStream_t);
-int cac_spatial_fwd(int, int, int, const float*, const float*, float*, hipStream_t);
-int cac_apply_fwd(int, int, int, const codon_tensor*, const codon_tensor*, const float*, const float*,
-                  const codon_tensor*, const codon_tensor*, const codon_tensor*, const codon_tensor*, int, hipStream_t);
-
-int bicubic_upsample(int, int, int, int, const float*, const float*, float*, hipStream_t);
-
-int postprocess_u8(const float*, unsigned char*, long, hipStream_t);
-int postprocess_u8_f16(const void*, unsigned char*, long, hipStream_t);
-int masked_sqerr(const unsigned char*, const unsigned char*, long, unsigned long long*, hipStream_t);
-int postprocess_u16(const void*, int, int, unsigned short*, long, hipStream_t);
-int masked_sqerr_u16(const unsigned short*, const unsigned short*, long, unsigned long long*, hipStream_t);
-int ssim_tiles(int, int, int);
-int ssim_fwd(int, int, int, const float*, const float*, float*, float*, double*, hipStream_t);
-int l1_fwd(long, const float*, const float*, float*, int, double*, hipStream_t);
-int ssim_l1_bwd(int, int, int, const float*, const float*, const float*, float*, float*, float, float, hipStream_t);
-int masked_l1_ssim_fwd(int, int, int, const float*, const float*, const unsigned char*, float*, float*, double, double,
-                       long long*, double*, float*, double*, hipStream_t);
-int masked_l1_ssim_bwd(int, int, int, const float*, const float*, const unsigned char*, const float*, const float*, const float*,
-                       float*, float*, hipStream_t);
-
-int reduce_multi(const codon_reduce_item*, int, hipStream_t);
-int cast_multi(const codon_cast_desc*, float*, hipStream_t);
-int adam_step(const codon_adam_desc*, const float*, float*, float*, float, float, float, float, float, int, hipStream_t);
-size_t grad_norm_workspace_bytes();
-int grad_norm(const float*, long, void*, hipStream_t);
-int adam_step_guarded(const codon_adam_desc*, const float*, float*, float*, float*, void*, float, float, float, float, float, int,
-                      double, int, double, hipStream_t);
-int train_crops(const codon_crop_desc*, const unsigned char*, int, const float*, const float*, float*, float*, float*,
-                hipStream_t);
-int bicubic_downsample(int, int, int, const float*, const float*, float*, hipStream_t);
-int quantize_levels(long, float*, const float*, int, hipStream_t);
-int bicubic_upsample_masked(int, int, int, int, const float*, const float*, float*, unsigned char*, hipStream_t);
-int bicubic_downsample_masked(int, int, int, const float*, const float*, const float*, int, float*, hipStream_t);
-int lr_codes_to_input(int, int, int, int, const void*, int, const float*, int, const float*, void*, int, hipStream_t);
-int train_crops_lr(const codon_crop_desc*, const unsigned char*, int, int, const float*, int, const float*, const float*, float*,
-                   float*, float*, hipStream_t);
-int d4_views(int, int, int, const void*, const void*, int, void*, void*, void*, void*, hipStream_t);
-int d4_merge(int, int, int, const void*, const void*, int, float*, hipStream_t);
-int lr_sensor(const SensorArgs&, int, const float*, const float*, const float*, float*, hipStream_t);
-int depth_errors(const EvalArgs&, int, int, const void*, const void*, void*, unsigned char*, unsigned long long*, hipStream_t);
-size_t weight_checksum_workspace_bytes();
-int weight_checksum(const codon_wsum_desc*, void*, unsigned long long*, int, int*, int*, int, hipStream_t);
 
 static thread_local PairRecorder g_pair;
 PairRecorder* pair_recorder() { return g_pair.active ? &g_pair : nullptr; }

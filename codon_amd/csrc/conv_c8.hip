@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "c8.h"
+#include "kernels.h"
 #include "pair.h"
 
 namespace codon {

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "codon_common.h"
+#include "kernels.h"
 #include "pair.h"
 
 namespace codon {
@@ -696,17 +697,20 @@ int pack_chain1x1_f32(const float* w, float* out, hipStream_t stream) {
   return check_launch("pack_chain1x1_f32_kernel");
 }
 
+// THE TILING RULE of the fp32 convs, stated once: asked by launch_conv, launch_gated and conv_chain1x1_fwd_f32 (in_pair = a
+// pair bracket is open on this thread) and by conv_tiling_f32, the query behind codon_conv_tiling_f32, so that they cannot
+// drift apart.  Nothing else compares a block count with a threshold.
+//
 // SMALL-GRID MODE.  A launch whose 8 x 32 tiling gives fewer workgroups than ~1.5 per CU (single images: the reference
 // script's own use, test.py:125, and BASELINE configs[0]) is latency-bound on one workgroup's K loop; it takes 4 x 32
-// tiles instead (PSEG = 1: twice the workgroups, half the MFMAs each).  Per-pixel arithmetic and its order are the
-// same, so results stay bit-identical to the large-grid kernels (batch-independence tests compare the two).
-constexpr long SMALL_GRID = 384;
-constexpr long CSPLIT_MAX_BLOCKS = 192;     // 4 x 32 tiles: up to here a lone launch leaves a quarter of the SIMDs without a wave
-constexpr long CSPLIT_PAIR_MAX_BLOCKS = 128;   // ... and a PAIR of launches split this way is at most 512 workgroups: one round
-static bool small_grid(const codon_conv_desc* d) {
-  return (long)((d->width + 31) / 32) * ((d->height + 7) / 8) * d->batch < SMALL_GRID;
-}
-
+// tiles instead (PSEG = 1: twice the workgroups, half the MFMAs each), one workgroup per CU (solo_lds_pad below).  Up to
+// CSPLIT_MAX_BLOCKS such tiles alone on the chip (the trunk's conv10 + confuse_fuse at one image per call), or
+// CSPLIT_PAIR_MAX_BLOCKS in each launch of a pair (the two streams of a block), a conv that has the form takes 2 x 32 tiles
+// with the couts split over the waves: the chained conv and every plain or gated conv with cout % 64 == 0 and k != 1 (one
+// 128 x 128 image: conv7 alone is 128 tiles whose waves each run 1 152 MFMAs back to back; the gated 5x5 pairs 1 600 -- the
+// staging arithmetic is the workgroup's, the split only divides the MFMA chain).  The gated convs follow the plain rule of
+// their shape (chained = 0), and all three gated shapes are splittable.
+//
 // GRIDS OF A FEW ROUNDS (one image of a few hundred rows).  Two 4-wave workgroups share a CU, and a CU gives a lone workgroup
 // almost the throughput it gives two: 8 x 32 tiles of the chained conv take 0.72 ms as a pair and 0.36 ms alone.  So a launch
 // runs in rounds of 512 workgroups, and its last round costs a full pair time wherever the dispatcher happens to put two
@@ -717,18 +721,29 @@ static bool small_grid(const codon_conv_desc* d) {
 //   4 x 32 tiles, two per CU:   ceil(n4 / 512) rounds of 2
 //   4 x 32 tiles, one per CU:   ceil(n4 / 256) rounds of SOLO    (the LDS padding of solo_lds_pad; no pairing to be lucky with)
 // and the cheapest is taken.  8 x 32 wins by 1.4 % once the rounds are many (the headline batch: 75 rounds); the ratios
-// were measured on 15 image heights between 200 and 820 rows (tools/probes/grid_mode_sweep.sh).  Per-pixel arithmetic and
-// its order do not depend on the tiling: same bits.  3 x 3 and 1 x 1 convs (memory-bound, no such step pattern) keep 8 x 32.
-enum GridMode { GRID_8X32, GRID_4X32, GRID_4X32_SOLO };
+// were measured on 15 image heights between 200 and 820 rows (tools/probes/grid_mode_sweep.sh).  3 x 3 and 1 x 1 convs
+// (memory-bound, no such step pattern) keep 8 x 32.
+//
+// Per-pixel arithmetic and its order do not depend on the tiling: every tiling gives the same bits (the batch-independence
+// tests compare them).
+constexpr long SMALL_GRID = 384;
+constexpr long CSPLIT_MAX_BLOCKS = 192;     // 4 x 32 tiles: up to here a lone launch leaves a quarter of the SIMDs without a wave
+constexpr long CSPLIT_PAIR_MAX_BLOCKS = 128;   // ... and a PAIR of launches split this way is at most 512 workgroups: one round
 constexpr float GRID_SOLO_CHAIN = 1.093f, GRID_SOLO_CONV64 = 1.184f;
-static GridMode grid_mode(const codon_conv_desc* d, float solo) {
-  if (small_grid(d)) return GRID_4X32_SOLO;
+static int f32_tiling(const codon_conv_desc* d, bool chained, bool in_pair) {
   const long tx = (d->width + 31) / 32;
   const long n8 = tx * ((d->height + 7) / 8) * d->batch, n4 = tx * ((d->height + 3) / 4) * d->batch;
-  const float c8 = 3.945f * (float)((n8 + 511) / 512), c4 = 2.f * (float)((n4 + 511) / 512);
-  const float cs = solo * (float)((n4 + 255) / 256);
-  if (c8 <= c4 && c8 <= cs) return GRID_8X32;
-  return c4 <= cs ? GRID_4X32 : GRID_4X32_SOLO;
+  if (n8 >= SMALL_GRID) {
+    if (!chained && d->ksize != 5) return CODON_TILING_8X32;
+    const float solo = chained ? GRID_SOLO_CHAIN : GRID_SOLO_CONV64;
+    const float c8 = 3.945f * (float)((n8 + 511) / 512), c4 = 2.f * (float)((n4 + 511) / 512);
+    const float cs = solo * (float)((n4 + 255) / 256);
+    if (c8 <= c4 && c8 <= cs) return CODON_TILING_8X32;
+    if (c4 <= cs) return CODON_TILING_4X32;
+  }
+  const bool splittable = chained || (d->cout % 64 == 0 && d->ksize != 1);
+  if (splittable && n4 <= (in_pair ? CSPLIT_PAIR_MAX_BLOCKS : CSPLIT_MAX_BLOCKS)) return CODON_TILING_2X32_COUT_SPLIT;
+  return CODON_TILING_4X32_SOLO;
 }
 
 // Small grids leave CUs empty, and the host runs the two streams of a block on two HIP streams (model.py) -- but the
@@ -823,114 +838,76 @@ static int launch_or_hold_f32(const ConvParams& p, bool small, hipStream_t strea
   return launch_single_f32<KS, CIN, COUT, PSEG, FUSE, GATE, NW, false, false, ST>(&p, stream);
 }
 
-template <int KS, int CIN, int COUT, int PSEG, bool CSPLIT = false>
-static int launch_conv_p(const codon_conv_desc* d, const float* x, const float* w, float* y,
-                         const float* res, bool solo, hipStream_t stream) {
-  constexpr int TH = (CSPLIT ? 2 : 4) * PSEG;
-  ConvParams p;
-  p.x = x; p.w = w; p.y = y; p.res = res;
+// The one mapping from a tiling to the launcher's (PSEG, SOLO, CSPLIT).  The cout-split form exists for the chained conv and
+// for cout % 64 == 0, k != 1 only (the static_assert of the body), and f32_tiling names it for no other shape.
+template <int KS, int CIN, int COUT, bool FUSE, bool GATE, bool ST>
+static int launch_tiled_f32(int tiling, const ConvParams& p, hipStream_t stream) {
+  constexpr int NW = 4;      // waves per workgroup (one 8-wave workgroup per CU on a 16x32 tile measured slower: DESIGN.md 3.1)
+  switch (tiling) {
+    case CODON_TILING_8X32: return launch_or_hold_f32<KS, CIN, COUT, 2, FUSE, GATE, NW, ST>(p, false, stream);
+    case CODON_TILING_4X32: return launch_or_hold_f32<KS, CIN, COUT, 1, FUSE, GATE, NW, ST>(p, false, stream);
+    case CODON_TILING_4X32_SOLO: return launch_or_hold_f32<KS, CIN, COUT, 1, FUSE, GATE, NW, ST>(p, true, stream);
+    default:
+      if constexpr (FUSE || (COUT % 64 == 0 && KS != 1)) return launch_or_hold_csplit_f32<KS, CIN, COUT, FUSE, NW, ST, GATE>(p, stream);
+      set_error("conv_mfma_f32: no cout-split kernel for k=%d cout=%d", KS, COUT);
+      return CODON_ERR_UNSUPPORTED;
+  }
+}
+
+// The counterpart of c8_fill (conv_c8.hip): everything of the parameter block that every variant has, for the tile height
+// of `tiling`, and the two refusals, worded for the entry point `who`.  Whatever it does not set is zero; the callers add
+// what is theirs (the residual; the gate operands; the chained 1x1 and its statistics).
+static int f32_fill(ConvParams& p, const char* who, const codon_conv_desc* d, const float* x, const float* w, float* y,
+                    int tiling) {
+  const int th = tiling == CODON_TILING_8X32 ? 8 : tiling == CODON_TILING_2X32_COUT_SPLIT ? 2 : 4;
+  p = ConvParams{};
+  p.x = x; p.w = w; p.y = y;
   p.H = d->height; p.W = d->width;
   const long HW = (long)d->height * d->width;
-  p.x_img = d->x_ctotal * HW; p.y_img = d->y_ctotal * HW; p.r_img = d->r_ctotal * HW;
-  p.x_base = d->x_coff * HW; p.y_base = d->y_coff * HW; p.r_base = d->r_coff * HW;
+  p.x_img = d->x_ctotal * HW; p.y_img = d->y_ctotal * HW;
+  p.x_base = d->x_coff * HW; p.y_base = d->y_coff * HW;
   p.tiles_x = (d->width + 31) / 32;
-  p.tiles_y = (d->height + TH - 1) / TH;
+  p.tiles_y = (d->height + th - 1) / th;
   const long nblk = (long)p.tiles_x * p.tiles_y * d->batch;
-  CODON_REQUIRE(nblk < (1L << 31), CODON_ERR_UNSUPPORTED, "conv2d_fwd: grid too large (%ld blocks)", nblk);
+  CODON_REQUIRE(nblk < (1L << 31), CODON_ERR_UNSUPPORTED, "%s: grid too large (%ld blocks)", who, nblk);
   CODON_REQUIRE(HW * 4 * 32 < (long)BUF_OOB, CODON_ERR_UNSUPPORTED,
-                "conv2d_fwd: %dx%d image: 32 channel planes exceed the 4 GiB buffer-descriptor range", d->height, d->width);
+                "%s: %dx%d image: 32 channel planes exceed the 4 GiB buffer-descriptor range", who, d->height, d->width);
   p.nblk = (int)nblk;
   p.flags = d->flags;
 #ifdef CODON_TIMING
   p.dbg = codon_dbg_ptr();
 #endif
-  p.w2 = nullptr; p.y2 = nullptr; p.y2_img = p.y2_base = 0;
-  p.in2 = nullptr; p.ch = nullptr; p.sp = nullptr; p.in_img = p.in_base = 0;
-  p.gout = nullptr; p.go_img = p.go_base = 0;
-  p.st_pool = nullptr; p.st_part = nullptr; p.st_choff = 0;
-  if constexpr (CSPLIT)            // a small launch (see conv_chain1x1_fwd_f32): 2 x 32 tiles, couts split over the waves
-    return launch_or_hold_csplit_f32<KS, CIN, COUT, false, 4>(p, stream);
-  return launch_or_hold_f32<KS, CIN, COUT, PSEG, false, false, 4>(p, PSEG == 1 && solo, stream);
+  return CODON_OK;
 }
 
-template <int KS, int CIN, int COUT, int PSEG>
+template <int KS, int CIN, int COUT>
 static int launch_conv(const codon_conv_desc* d, const float* x, const float* w, float* y,
                        const float* res, hipStream_t stream) {
-  const GridMode mode = KS == 5 ? grid_mode(d, GRID_SOLO_CONV64) : small_grid(d) ? GRID_4X32_SOLO : GRID_8X32;
-  if (mode == GRID_4X32_SOLO) {
-    if constexpr (COUT % 64 == 0 && KS != 1) {
-      const long nblk4 = (long)((d->width + 31) / 32) * ((d->height + 3) / 4) * d->batch;
-      if (nblk4 <= (pair_recorder() ? CSPLIT_PAIR_MAX_BLOCKS : CSPLIT_MAX_BLOCKS))
-        return launch_conv_p<KS, CIN, COUT, 1, true>(d, x, w, y, res, true, stream);
-    }
-    return launch_conv_p<KS, CIN, COUT, 1>(d, x, w, y, res, true, stream);
-  }
-  if (mode == GRID_4X32) return launch_conv_p<KS, CIN, COUT, 1>(d, x, w, y, res, false, stream);
-  return launch_conv_p<KS, CIN, COUT, PSEG>(d, x, w, y, res, false, stream);
+  const int tiling = f32_tiling(d, false, pair_recorder() != nullptr);
+  ConvParams p;
+  if (const int st = f32_fill(p, "conv2d_fwd", d, x, w, y, tiling)) return st;
+  const long HW = (long)d->height * d->width;
+  p.res = res; p.r_img = d->r_ctotal * HW; p.r_base = d->r_coff * HW;
+  return launch_tiled_f32<KS, CIN, COUT, false, false, false>(tiling, p, stream);
 }
 
 int conv_ck(int ks) { return ks == 1 ? 16 : 8; }
 
-// codon_conv_tiling_f32 (include/codon_hip.h): the tiling the launchers above give a plain (chained = 0) / chained fp32 conv
-// of this shape outside / inside a pair bracket -- the same rule, restated without a launch (host code only)
-int conv_tiling_f32(const codon_conv_desc* d, int chained, int in_pair) {
-  const bool k5 = d->ksize == 5;
-  const GridMode mode = chained ? grid_mode(d, GRID_SOLO_CHAIN)
-                        : k5    ? grid_mode(d, GRID_SOLO_CONV64) : small_grid(d) ? GRID_4X32_SOLO : GRID_8X32;
-  if (mode == GRID_8X32) return CODON_TILING_8X32;
-  if (mode == GRID_4X32) return CODON_TILING_4X32;
-  const bool splittable = chained || (d->cout % 64 == 0 && d->ksize != 1);
-  const long nblk4 = (long)((d->width + 31) / 32) * ((d->height + 3) / 4) * d->batch;
-  if (splittable && nblk4 <= (in_pair ? CSPLIT_PAIR_MAX_BLOCKS : CSPLIT_MAX_BLOCKS)) return CODON_TILING_2X32_COUT_SPLIT;
-  return CODON_TILING_4X32_SOLO;
-}
-
-template <int KS, int CIN, int COUT, int PSEG, bool CSPLIT = false>
-static int launch_gated_p(const codon_conv_desc* d, const float* pre, const codon_tensor* in2, const float* ch,
-                          const float* sp, const float* w, float* y, const codon_tensor* gated_out, bool solo,
-                          hipStream_t stream) {
-  constexpr int TH = (CSPLIT ? 2 : 4) * PSEG;
-  ConvParams p;
-  p.x = pre; p.w = w; p.y = y; p.res = nullptr;
-  p.H = d->height; p.W = d->width;
-  const long HW = (long)d->height * d->width;
-  p.x_img = d->x_ctotal * HW; p.y_img = d->y_ctotal * HW; p.r_img = 0;
-  p.x_base = d->x_coff * HW; p.y_base = d->y_coff * HW; p.r_base = 0;
-  p.in2 = (const float*)in2->data; p.in_img = in2->ctotal * HW; p.in_base = in2->coff * HW;
-  p.ch = ch; p.sp = sp;
-  p.gout = gated_out ? (float*)gated_out->data : nullptr;
-  p.go_img = gated_out ? gated_out->ctotal * HW : 0; p.go_base = gated_out ? gated_out->coff * HW : 0;
-  p.w2 = nullptr; p.y2 = nullptr; p.y2_img = p.y2_base = 0;
-  p.st_pool = nullptr; p.st_part = nullptr; p.st_choff = 0;
-  p.tiles_x = (d->width + 31) / 32;
-  p.tiles_y = (d->height + TH - 1) / TH;
-  const long nblk = (long)p.tiles_x * p.tiles_y * d->batch;
-  CODON_REQUIRE(nblk < (1L << 31), CODON_ERR_UNSUPPORTED, "conv2d_gated_fwd: grid too large (%ld blocks)", nblk);
-  CODON_REQUIRE(HW * 4 * 32 < (long)BUF_OOB, CODON_ERR_UNSUPPORTED,
-                "conv2d_gated_fwd: %dx%d image: 32 channel planes exceed the 4 GiB buffer-descriptor range", d->height, d->width);
-  p.nblk = (int)nblk;
-  p.flags = d->flags;
-#ifdef CODON_TIMING
-  p.dbg = codon_dbg_ptr();
-#endif
-  if constexpr (CSPLIT) return launch_or_hold_csplit_f32<KS, CIN, COUT, false, 4, false, true>(p, stream);
-  return launch_or_hold_f32<KS, CIN, COUT, PSEG, false, true, 4>(p, PSEG == 1 && solo, stream);
-}
+// codon_conv_tiling_f32 (include/codon_hip.h): the tiling the launchers here give a plain (chained = 0) / chained fp32 conv
+// of this shape outside / inside a pair bracket -- f32_tiling itself, asked without a launch (host code only)
+int conv_tiling_f32(const codon_conv_desc* d, int chained, int in_pair) { return f32_tiling(d, chained != 0, in_pair != 0); }
 
 template <int KS, int CIN, int COUT>
 static int launch_gated(const codon_conv_desc* d, const float* pre, const codon_tensor* in2, const float* ch,
                         const float* sp, const float* w, float* y, const codon_tensor* gated_out, hipStream_t stream) {
-  const GridMode mode = KS == 5 ? grid_mode(d, GRID_SOLO_CONV64) : small_grid(d) ? GRID_4X32_SOLO : GRID_8X32;
-  if (mode == GRID_4X32_SOLO) {
-    // round 6: the gated convs of a small launch take the cout split too (one 128 x 128 image: conv7 alone is 128 tiles whose
-    // waves each run 1 152 MFMAs back to back; the gated 5x5 pairs 1 600) -- the staging arithmetic is the workgroup's, the split
-    // only divides the MFMA chain; same fma chain per output: same bits
-    const long nblk4 = (long)((d->width + 31) / 32) * ((d->height + 3) / 4) * d->batch;
-    if (nblk4 <= (pair_recorder() ? CSPLIT_PAIR_MAX_BLOCKS : CSPLIT_MAX_BLOCKS))
-      return launch_gated_p<KS, CIN, COUT, 1, true>(d, pre, in2, ch, sp, w, y, gated_out, true, stream);
-  }
-  if (mode != GRID_8X32) return launch_gated_p<KS, CIN, COUT, 1>(d, pre, in2, ch, sp, w, y, gated_out, mode == GRID_4X32_SOLO, stream);
-  return launch_gated_p<KS, CIN, COUT, 2>(d, pre, in2, ch, sp, w, y, gated_out, false, stream);
+  const int tiling = f32_tiling(d, false, pair_recorder() != nullptr);
+  ConvParams p;
+  if (const int st = f32_fill(p, "conv2d_gated_fwd", d, pre, w, y, tiling)) return st;
+  const long HW = (long)d->height * d->width;
+  p.in2 = (const float*)in2->data; p.in_img = in2->ctotal * HW; p.in_base = in2->coff * HW;
+  p.ch = ch; p.sp = sp;
+  if (gated_out) { p.gout = (float*)gated_out->data; p.go_img = gated_out->ctotal * HW; p.go_base = gated_out->coff * HW; }
+  return launch_tiled_f32<KS, CIN, COUT, false, true, false>(tiling, p, stream);
 }
 
 int conv2d_gated_fwd_f32(const codon_conv_desc* d, const float* pre, const codon_tensor* in2, const float* ch,
@@ -953,47 +930,17 @@ int conv_chain1x1_fwd_f32(const codon_conv_desc* d, const float* x, const float*
                           hipStream_t stream) {
   CODON_REQUIRE(d->ksize == 5 && d->cin == 128 && d->cout == 128, CODON_ERR_UNSUPPORTED,
                 "conv_chain1x1_fwd: f32 kernel is conv5x5 128->128 + 1x1 128->64 (got k=%d %d->%d)", d->ksize, d->cin, d->cout);
-  constexpr int NWC = 4;     // waves per workgroup (one 8-wave workgroup per CU on a 16x32 tile measured slower: DESIGN.md 3.1)
-  const GridMode mode = grid_mode(d, GRID_SOLO_CHAIN);
-  const bool small = mode == GRID_4X32_SOLO;
-  const int TH = (mode == GRID_8X32 ? 2 : 1) * NWC;
-  ConvParams p;
-  p.x = x; p.w = w; p.y = y; p.res = res ? (const float*)res->data : nullptr;
-  p.H = d->height; p.W = d->width;
-  const long HW = (long)d->height * d->width;
-  p.x_img = d->x_ctotal * HW; p.y_img = d->y_ctotal * HW; p.r_img = res ? res->ctotal * HW : 0;
-  p.x_base = d->x_coff * HW; p.y_base = d->y_coff * HW; p.r_base = res ? res->coff * HW : 0;
-  p.in2 = nullptr; p.ch = nullptr; p.sp = nullptr; p.in_img = p.in_base = 0;
-  p.gout = nullptr; p.go_img = p.go_base = 0;
-  p.w2 = w_chain; p.y2 = (float*)out->data; p.y2_img = out->ctotal * HW; p.y2_base = out->coff * HW;
-  p.st_pool = st_pool; p.st_part = st_part; p.st_choff = st_choff;
   const bool st = st_part != nullptr;
   CODON_REQUIRE(!st || (st_pool && !res), CODON_ERR_BAD_ARG, "conv_chain1x1_stats_fwd: statistics need both outputs and no residual");
-  p.tiles_x = (d->width + 31) / 32;
-  p.tiles_y = (d->height + TH - 1) / TH;
-  const long nblk = (long)p.tiles_x * p.tiles_y * d->batch;
-  CODON_REQUIRE(nblk < (1L << 31), CODON_ERR_UNSUPPORTED, "conv_chain1x1_fwd: grid too large (%ld blocks)", nblk);
-  CODON_REQUIRE(HW * 4 * 32 < (long)BUF_OOB, CODON_ERR_UNSUPPORTED,
-                "conv_chain1x1_fwd: %dx%d image: 32 channel planes exceed the 4 GiB buffer-descriptor range", d->height, d->width);
-  p.nblk = (int)nblk;
-  p.flags = d->flags;
-#ifdef CODON_TIMING
-  p.dbg = codon_dbg_ptr();
-#endif
-  if (small && nblk <= (pair_recorder() ? CSPLIT_PAIR_MAX_BLOCKS : CSPLIT_MAX_BLOCKS)) {
-    // at most 192 tiles of 4 x 32 alone on the chip (the trunk's conv10 + confuse_fuse at one image per call), or at most
-    // 128 in each launch of a pair (the two streams of a block): 2 x 32 tiles, couts split over the waves
-    p.tiles_y = (d->height + 1) / 2;
-    p.nblk = (int)((long)p.tiles_x * p.tiles_y * d->batch);
-    if (st) return launch_or_hold_csplit_f32<5, 128, 128, true, NWC, true>(p, stream);
-    return launch_or_hold_csplit_f32<5, 128, 128, true, NWC>(p, stream);
-  }
-  if (st) {
-    if (mode != GRID_8X32) return launch_or_hold_f32<5, 128, 128, 1, true, false, NWC, true>(p, small, stream);
-    return launch_or_hold_f32<5, 128, 128, 2, true, false, NWC, true>(p, false, stream);
-  }
-  if (mode != GRID_8X32) return launch_or_hold_f32<5, 128, 128, 1, true, false, NWC>(p, small, stream);
-  return launch_or_hold_f32<5, 128, 128, 2, true, false, NWC>(p, false, stream);
+  const int tiling = f32_tiling(d, true, pair_recorder() != nullptr);
+  ConvParams p;
+  if (const int e = f32_fill(p, "conv_chain1x1_fwd", d, x, w, y, tiling)) return e;
+  const long HW = (long)d->height * d->width;
+  if (res) { p.res = (const float*)res->data; p.r_img = res->ctotal * HW; p.r_base = res->coff * HW; }
+  p.w2 = w_chain; p.y2 = (float*)out->data; p.y2_img = out->ctotal * HW; p.y2_base = out->coff * HW;
+  p.st_pool = st_pool; p.st_part = st_part; p.st_choff = st_choff;
+  return st ? launch_tiled_f32<5, 128, 128, true, false, true>(tiling, p, stream)
+            : launch_tiled_f32<5, 128, 128, true, false, false>(tiling, p, stream);
 }
 
 // pixel rows per wave: 2 = 8 x 32 tile (4 operand fetches per 4 MFMAs) everywhere; the 16 x 32 tile (6 per 8) was measured on the
@@ -1002,13 +949,13 @@ int conv2d_fwd_f32(const codon_conv_desc* d, const float* x, const float* w, flo
                    hipStream_t stream) {
   const int key = d->ksize * 1000000 + d->cin * 1000 + d->cout;
   switch (key) {
-    case 5128128: return launch_conv<5, 128, 128, 2>(d, x, w, y, res, stream);
-    case 5064064: return launch_conv<5, 64, 64, 2>(d, x, w, y, res, stream);
-    case 3064064: return launch_conv<3, 64, 64, 2>(d, x, w, y, res, stream);
-    case 3128064: return launch_conv<3, 128, 64, 2>(d, x, w, y, res, stream);
-    case 3064128: return launch_conv<3, 64, 128, 2>(d, x, w, y, res, stream);  // dgrad of conv7
-    case 1128064: return launch_conv<1, 128, 64, 2>(d, x, w, y, res, stream);
-    case 1064128: return launch_conv<1, 64, 128, 2>(d, x, w, y, res, stream);  // dgrad of confuse*
+    case 5128128: return launch_conv<5, 128, 128>(d, x, w, y, res, stream);
+    case 5064064: return launch_conv<5, 64, 64>(d, x, w, y, res, stream);
+    case 3064064: return launch_conv<3, 64, 64>(d, x, w, y, res, stream);
+    case 3128064: return launch_conv<3, 128, 64>(d, x, w, y, res, stream);
+    case 3064128: return launch_conv<3, 64, 128>(d, x, w, y, res, stream);  // dgrad of conv7
+    case 1128064: return launch_conv<1, 128, 64>(d, x, w, y, res, stream);
+    case 1064128: return launch_conv<1, 64, 128>(d, x, w, y, res, stream);  // dgrad of confuse*
     default:
       set_error("conv2d_fwd: no f32 kernel for k=%d cin=%d cout=%d", d->ksize, d->cin, d->cout);
       return CODON_ERR_UNSUPPORTED;

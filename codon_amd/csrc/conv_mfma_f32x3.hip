@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "codon_common.h"
+#include "kernels.h"
 
 namespace codon {
 

@@ -22,6 +22,7 @@
 // summed through LDS.
 
 #include "c8.h"
+#include "kernels.h"
 
 namespace codon {
 
@@ -620,10 +621,6 @@ __global__ __launch_bounds__(Wc8Waves<KS>::value * 64, KS == 1 ? 2 : 3) void con
   }
 }
 
-// defined in conv_wgrad_f32.hip: dw[co][ci][tap] (+)= sum_s ws[s][tap][co][ci], fixed order
-int launch_wgrad_reduce(const float* ws, float* dw, int cout, int cin, int taps, int nsplit, int accumulate,
-                        hipStream_t stream);
-
 constexpr int WGRAD16_TARGET_BLOCKS = 256;   // workgroups per launch the band split aims for: one per CU
 
 struct Wgrad16Plan {
@@ -638,10 +635,7 @@ static bool wgrad16_plan(const codon_conv_desc* d, Wgrad16Plan* pl) {
   pl->nchan_blocks = (co / 64) * (ci / (k == 1 ? 32 * WC8_CIB1 : k == 3 ? 32 * Wc8Cit<3>::value : 32));
   const int th = k == 5 ? Wc8Th<5>::value : k == 3 ? Wc8Th<3>::value : WC8_TH;
   const int tiles_y = (d->height + th - 1) / th;
-  int want = (WGRAD16_TARGET_BLOCKS + pl->nchan_blocks * d->batch - 1) / (pl->nchan_blocks * d->batch);
-  if (want < 1) want = 1;
-  if (want > tiles_y) want = tiles_y;
-  pl->nbands = want;
+  pl->nbands = wgrad_band_count(WGRAD16_TARGET_BLOCKS, pl->nchan_blocks, d->batch, tiles_y);
   pl->nsplit = d->batch * pl->nbands;
   return true;
 }
@@ -652,30 +646,30 @@ size_t conv_wgrad_bf16_workspace_bytes(const codon_conv_desc* d) {
   return (size_t)pl.nsplit * d->cout * d->cin * d->ksize * d->ksize * sizeof(float);
 }
 
-int conv2d_wgrad_bf16(const codon_conv_desc* d, const void* x, const void* gy, float* dw, float* workspace,
-                      size_t ws_bytes, int accumulate, hipStream_t stream) {
-  Wgrad16Plan pl;
-  if (!wgrad16_plan(d, &pl)) {
-    set_error("conv2d_wgrad: no 16-bit kernel for k=%d cin=%d cout=%d", d->ksize, d->cin, d->cout);
+// What conv2d_wgrad_bf16 and conv1x1_bwd_16 (`who`, for the error texts) do before they pick a kernel: the plan, the slice,
+// workspace, split-count and descriptor-range checks, and the parameter block with its dg_* / gb_* fields null.
+static int wgrad16_prepare(const char* who, const codon_conv_desc* d, const void* x, const void* gy, float* workspace,
+                           size_t ws_bytes, Wgrad16Plan* pl, WgradC8Params* p) {
+  if (!wgrad16_plan(d, pl)) {
+    set_error("%s: no 16-bit kernel for k=%d cin=%d cout=%d", who, d->ksize, d->cin, d->cout);
     return CODON_ERR_UNSUPPORTED;
   }
   CODON_REQUIRE(c8_slice_ok(d->x_ctotal, d->x_coff, d->cin) && c8_slice_ok(d->y_ctotal, d->y_coff, d->cout),
-                CODON_ERR_BAD_ARG, "conv2d_wgrad: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
+                CODON_ERR_BAD_ARG, "%s: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8", who);
   CODON_REQUIRE(ws_bytes >= conv_wgrad_bf16_workspace_bytes(d), CODON_ERR_BAD_ARG,
-                "conv2d_wgrad: workspace %zu B < required %zu B", ws_bytes, conv_wgrad_bf16_workspace_bytes(d));
-  CODON_REQUIRE(pl.nsplit <= 65535, CODON_ERR_UNSUPPORTED, "conv2d_wgrad: %d splits > 65535", pl.nsplit);
-  const long HW = (long)d->height * d->width;
-  CODON_REQUIRE(HW * 2 * 128 < (long)C8_OOB, CODON_ERR_UNSUPPORTED,
-                "conv2d_wgrad: %dx%d image: 128 channels exceed the 4 GiB buffer-descriptor range", d->height, d->width);
+                "%s: workspace %zu B < required %zu B", who, ws_bytes, conv_wgrad_bf16_workspace_bytes(d));
+  CODON_REQUIRE(pl->nsplit <= 65535, CODON_ERR_UNSUPPORTED, "%s: %d splits > 65535", who, pl->nsplit);
+  CODON_REQUIRE((long)d->height * d->width * 2 * 128 < (long)C8_OOB, CODON_ERR_UNSUPPORTED,
+                "%s: %dx%d image: 128 channels exceed the 4 GiB buffer-descriptor range", who, d->height, d->width);
+  *p = wgrad_fill<WgradC8Params>(d, x, gy, workspace, 8, pl->nbands, pl->nsplit);
+  return CODON_OK;
+}
+
+int conv2d_wgrad_bf16(const codon_conv_desc* d, const void* x, const void* gy, float* dw, float* workspace,
+                      size_t ws_bytes, int accumulate, hipStream_t stream) {
+  Wgrad16Plan pl;
   WgradC8Params p;
-  p.x = (const uint4*)x; p.gy = (const uint4*)gy; p.ws = workspace;
-  p.H = d->height; p.W = d->width; p.cin = d->cin; p.cout = d->cout;
-  p.x_img = (d->x_ctotal / 8) * HW; p.g_img = (d->y_ctotal / 8) * HW;
-  p.x_base = (d->x_coff / 8) * HW; p.g_base = (d->y_coff / 8) * HW;
-  p.tiles_x = (d->width + 31) / 32;
-  p.nbands = pl.nbands; p.nsplit = pl.nsplit;
-  p.dg_w = nullptr; p.dg_y = nullptr; p.dy_img = p.dy_base = 0;
-  p.gb_ch = p.gb_sp = p.gb_gpooled = p.gb_gpools = nullptr; p.gb_argpix = p.gb_argch = nullptr; p.gb_fbase = 0; p.gb_inv_hw = 0.f;
+  if (const int st = wgrad16_prepare("conv2d_wgrad", d, x, gy, workspace, ws_bytes, &pl, &p)) return st;
   const dim3 grid(pl.nchan_blocks, pl.nsplit);
   const bool f16 = d->dtype == CODON_F16;
   if (d->ksize == 5) {
@@ -699,32 +693,17 @@ int conv2d_wgrad_bf16(const codon_conv_desc* d, const void* x, const void* gy, f
 
 // dL/dw AND dL/dx of a 1x1 conv 128 -> 64 whose input is a ReLU output (confuse / confuse_c / confuse_fuse,
 // CODON_x4.py:84,83,127), one pass: both are HBM-bound on the same two tensors (x = r2 128 ch, gy 64 ch)
-struct Conv1x1GateBwd {      // GB operands (see WgradC8Params); null = plain codon_conv1x1_bwd
-  const float* ch; const float* sp; const float* g_pooled; const float* g_pools; const int* argpix; const int* argch;
-  int fbase;
-};
 int conv1x1_bwd_16(const codon_conv_desc* d, const void* x, const void* gy, const void* w_dgrad, const codon_tensor* gx,
                    float* dw, float* workspace, size_t ws_bytes, int accumulate, hipStream_t stream,
                    const Conv1x1GateBwd* gb) {
-  Wgrad16Plan pl;
-  CODON_REQUIRE(d->ksize == 1 && d->cin == 128 && d->cout == 64 && wgrad16_plan(d, &pl), CODON_ERR_UNSUPPORTED,
+  CODON_REQUIRE(d->ksize == 1 && d->cin == 128 && d->cout == 64, CODON_ERR_UNSUPPORTED,
                 "conv1x1_bwd: k=%d cin=%d cout=%d (the fused pass exists for the 128 -> 64 1x1 convs)", d->ksize, d->cin, d->cout);
-  CODON_REQUIRE(c8_slice_ok(d->x_ctotal, d->x_coff, d->cin) && c8_slice_ok(d->y_ctotal, d->y_coff, d->cout) &&
-                    c8_slice_ok(gx->ctotal, gx->coff, d->cin),
-                CODON_ERR_BAD_ARG, "conv1x1_bwd: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
-  CODON_REQUIRE(ws_bytes >= conv_wgrad_bf16_workspace_bytes(d), CODON_ERR_BAD_ARG,
-                "conv1x1_bwd: workspace %zu B < required %zu B", ws_bytes, conv_wgrad_bf16_workspace_bytes(d));
-  CODON_REQUIRE(pl.nsplit <= 65535, CODON_ERR_UNSUPPORTED, "conv1x1_bwd: %d splits > 65535", pl.nsplit);
-  const long HW = (long)d->height * d->width;
-  CODON_REQUIRE(HW * 2 * 128 < (long)C8_OOB, CODON_ERR_UNSUPPORTED,
-                "conv1x1_bwd: %dx%d image: 128 channels exceed the 4 GiB buffer-descriptor range", d->height, d->width);
+  CODON_REQUIRE(c8_slice_ok(gx->ctotal, gx->coff, d->cin), CODON_ERR_BAD_ARG,
+                "conv1x1_bwd: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
+  Wgrad16Plan pl;
   WgradC8Params p;
-  p.x = (const uint4*)x; p.gy = (const uint4*)gy; p.ws = workspace;
-  p.H = d->height; p.W = d->width; p.cin = d->cin; p.cout = d->cout;
-  p.x_img = (d->x_ctotal / 8) * HW; p.g_img = (d->y_ctotal / 8) * HW;
-  p.x_base = (d->x_coff / 8) * HW; p.g_base = (d->y_coff / 8) * HW;
-  p.tiles_x = (d->width + 31) / 32;
-  p.nbands = pl.nbands; p.nsplit = pl.nsplit;
+  if (const int st = wgrad16_prepare("conv1x1_bwd", d, x, gy, workspace, ws_bytes, &pl, &p)) return st;
+  const long HW = (long)d->height * d->width;
   p.dg_w = (const uint4*)w_dgrad; p.dg_y = (uint4*)gx->data;
   p.dy_img = (gx->ctotal / 8) * HW; p.dy_base = (gx->coff / 8) * HW;
   const dim3 grid(pl.nchan_blocks, pl.nsplit);
@@ -737,7 +716,6 @@ int conv1x1_bwd_16(const codon_conv_desc* d, const void* x, const void* gy, cons
     else
       hipLaunchKernelGGL((conv_wgrad_c8_kernel<C8Bf16, 1, true, 0, 0, true>), grid, dim3(2 * WC8_TH * 64), 0, stream, p);
   } else {
-    p.gb_ch = p.gb_sp = p.gb_gpooled = p.gb_gpools = nullptr; p.gb_argpix = p.gb_argch = nullptr; p.gb_fbase = 0; p.gb_inv_hw = 0.f;
     if (d->dtype == CODON_F16) hipLaunchKernelGGL((conv_wgrad_c8_kernel<C8F16, 1, true>), grid, dim3(2 * WC8_TH * 64), 0, stream, p);
     else hipLaunchKernelGGL((conv_wgrad_c8_kernel<C8Bf16, 1, true>), grid, dim3(2 * WC8_TH * 64), 0, stream, p);
   }

@@ -19,6 +19,7 @@
 // (deterministic, no atomics) into OIHW, optionally accumulating (the 5x / 3x weight sharing).
 
 #include "codon_common.h"
+#include "kernels.h"
 
 namespace codon {
 
@@ -200,12 +201,6 @@ int launch_wgrad_reduce(const float* ws, float* dw, int cout, int cin, int taps,
   return check_launch("wgrad_reduce_kernel");
 }
 
-// conv_wgrad_f32_t16.hip: 16x16x4 tiles, 8 balanced waves, double-buffered (W % 4 == 0, 16-byte aligned slices, k in {3,5})
-bool conv_wgrad_f32_t16_shape(const codon_conv_desc* d);
-bool conv_wgrad_f32_t16_supported(const codon_conv_desc* d, const void* x, const void* gy);
-int launch_wgrad_f32_t16(const codon_conv_desc* d, const float* x, const float* gy, float* workspace, int nbands,
-                         int nsplit, hipStream_t stream);
-
 struct WgradPlan {
   int co_t, ci_t, nbands, band_tiles_y, nsplit, nchan_blocks;
   bool t16;
@@ -225,10 +220,7 @@ static bool wgrad_plan(const codon_conv_desc* d, WgradPlan* pl) {
   const int plan_blocks = pl->t16 ? (co / 64) * (ci / (k == 1 ? 128 : 32)) : pl->nchan_blocks;
   const int target = pl->t16 ? 256 : 1024;       // workgroups per launch: 1 per CU (A/B: 256 beats 512 / 768 by 2-4 % on the 64-channel convs) / 2 x 2 per CU
   const int tiles_y = (d->height + 3) / 4;
-  // enough workgroups to fill the chip, but bounded workspace: bands per image
-  int want = (target + plan_blocks * d->batch - 1) / (plan_blocks * d->batch);
-  if (want < 1) want = 1;
-  if (want > tiles_y) want = tiles_y;
+  const int want = wgrad_band_count(target, plan_blocks, d->batch, tiles_y);
   pl->band_tiles_y = (tiles_y + want - 1) / want;
   pl->nbands = (tiles_y + pl->band_tiles_y - 1) / pl->band_tiles_y;
   pl->nsplit = d->batch * pl->nbands;
@@ -256,20 +248,14 @@ int conv2d_wgrad_f32(const codon_conv_desc* d, const float* x, const float* gy, 
   CODON_REQUIRE(ws_bytes >= conv_wgrad_workspace_bytes(d), CODON_ERR_BAD_ARG,
                 "conv2d_wgrad: workspace %zu B < required %zu B", ws_bytes, conv_wgrad_workspace_bytes(d));
   CODON_REQUIRE(pl.nsplit <= 65535, CODON_ERR_UNSUPPORTED, "conv2d_wgrad: %d splits > 65535", pl.nsplit);
-  static const bool t16_env = getenv("CODON_WGRAD_T16") ? atoi(getenv("CODON_WGRAD_T16")) != 0 : true;   // 0: round-1 kernel (A/B)
-  if (pl.t16 && t16_env && conv_wgrad_f32_t16_supported(d, x, gy)) {
+  if (pl.t16 && conv_wgrad_f32_t16_supported(d, x, gy)) {
     const int st = launch_wgrad_f32_t16(d, x, gy, workspace, pl.nbands, pl.nsplit, stream);
     if (st != CODON_OK || accumulate == CODON_WGRAD_DEFER) return st;
     return launch_wgrad_reduce(workspace, dw, d->cout, d->cin, d->ksize * d->ksize, pl.nsplit, accumulate, stream);
   }
-  const long HW = (long)d->height * d->width;
-  WgradParams p;
-  p.x = x; p.gy = gy; p.ws = workspace;
-  p.H = d->height; p.W = d->width; p.cin = d->cin; p.cout = d->cout;
-  p.x_img = d->x_ctotal * HW; p.g_img = d->y_ctotal * HW;
-  p.x_base = d->x_coff * HW; p.g_base = d->y_coff * HW;
-  p.tiles_x = (d->width + 31) / 32;
-  p.band_tiles_y = pl.band_tiles_y; p.nbands = pl.nbands; p.nsplit = pl.nsplit;
+  // W % 4 != 0 or a misaligned slice: the round-1 kernel, on the same band split
+  WgradParams p = wgrad_fill<WgradParams>(d, x, gy, workspace, 1, pl.nbands, pl.nsplit);
+  p.band_tiles_y = pl.band_tiles_y;
   if (d->ksize == 5) launch_wgrad<5, 1, 1>(p, pl.nchan_blocks, stream);
   else if (d->ksize == 3) launch_wgrad<3, 2, 1>(p, pl.nchan_blocks, stream);
   else launch_wgrad<1, 2, 2>(p, pl.nchan_blocks, stream);

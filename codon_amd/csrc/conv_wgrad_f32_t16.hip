@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "codon_common.h"
+#include "kernels.h"
 
 namespace codon {
 
@@ -241,13 +242,7 @@ bool conv_wgrad_f32_t16_supported(const codon_conv_desc* d, const void* x, const
 
 int launch_wgrad_f32_t16(const codon_conv_desc* d, const float* x, const float* gy, float* workspace, int nbands,
                          int nsplit, hipStream_t stream) {
-  const long HW = (long)d->height * d->width;
-  WgradT16Params p;
-  p.x = x; p.gy = gy; p.ws = workspace;
-  p.H = d->height; p.W = d->width; p.cin = d->cin; p.cout = d->cout;
-  p.x_img = d->x_ctotal * HW; p.g_img = d->y_ctotal * HW;
-  p.x_base = d->x_coff * HW; p.g_base = d->y_coff * HW;
-  p.tiles_x = (d->width + 31) / 32; p.nbands = nbands; p.nsplit = nsplit;
+  const WgradT16Params p = wgrad_fill<WgradT16Params>(d, x, gy, workspace, 1, nbands, nsplit);
   const dim3 grid((d->cout / 64) * (d->cin / (d->ksize == 1 ? 128 : 32)), nsplit);
   if (d->ksize == 5) hipLaunchKernelGGL(conv_wgrad_f32_t16_kernel<5>, grid, dim3(512), 0, stream, p);
   else if (d->ksize == 3) hipLaunchKernelGGL(conv_wgrad_f32_t16_kernel<3>, grid, dim3(512), 0, stream, p);

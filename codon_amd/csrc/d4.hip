@@ -13,6 +13,7 @@
 
 #include "codon_common.h"
 #include "d4_tile.h"
+#include "kernels.h"
 
 #pragma clang fp contract(off)
 

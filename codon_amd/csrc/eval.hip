@@ -13,6 +13,7 @@
 
 #include "codon_common.h"
 #include "eval_tile.h"
+#include "kernels.h"
 
 namespace codon {
 

@@ -8,6 +8,7 @@
 #include <math.h>
 
 #include "c8.h"
+#include "kernels.h"
 
 namespace codon {
 
@@ -385,9 +386,6 @@ __global__ __launch_bounds__(512 / W1C8_PLANES) void conv1ch_wgrad_c8_kernel(C8S
       }
 }
 
-// defined in stencil.hip: dw[576] = fixed-order sum of the (nparts, 576) partials
-int conv1ch_wgrad_reduce(const float* part, float* dw, int nparts, int flip, hipStream_t stream);
-
 size_t conv1ch_wgrad_c8_workspace_bytes(int B, int H, int W) {
   return (size_t)B * ((H + W1C8_ROWS - 1) / W1C8_ROWS) * 576 * sizeof(float);
 }
@@ -492,7 +490,6 @@ __global__ __launch_bounds__(256) void cac_stats_c8_kernel(C8Slice pre_c, C8Slic
   }
 }
 
-int cac_stats_tiles(int H, int W);          // cac.hip
 int cac_stats_fwd_c8(int B, int H, int W, const codon_tensor* pc, const codon_tensor* pd, float* pooled, float* partials,
                      int dtype, hipStream_t stream, const float* chs) {
   const long HW = (long)H * W;

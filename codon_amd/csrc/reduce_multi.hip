@@ -15,6 +15,7 @@
 //           conv1ch_wgrad_reduce with nchunk = 16); f = identity, or the 3x3 tap flip of the head's weight gradient.
 
 #include "codon_common.h"
+#include "kernels.h"
 
 namespace codon {
 

@@ -28,6 +28,7 @@
 #include <hip/hip_fp16.h>
 
 #include "dot4_rn.h"
+#include "kernels.h"
 #include "train_record.h"
 
 #pragma clang fp contract(off)

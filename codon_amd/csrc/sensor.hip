@@ -11,6 +11,7 @@
 // pixel, one table gather, ten Philox rounds.  No atomics, no LDS.
 
 #include "codon_common.h"
+#include "kernels.h"
 #include "sensor_pixel.h"
 
 #pragma clang fp contract(off)

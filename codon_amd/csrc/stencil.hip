@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "codon_common.h"
+#include "kernels.h"
 
 namespace codon {
 
@@ -319,12 +320,6 @@ static int stem_launch(int B, int H, int W, const float* x, const float* w, T* y
   return check_launch("stem_kernel");
 }
 
-// ew_c8.hip: the same stencils over channel-blocked 16-bit tensors
-int stem_fwd_c8(int, int, int, const float*, const float*, void*, int, int, int, const void*, int, int, int, int*, int*, hipStream_t);
-int head_fwd_c8(int, int, int, const void*, int, int, const float*, const float*, void*, bool, int, const int*, hipStream_t);
-size_t conv1ch_wgrad_c8_workspace_bytes(int, int, int);
-int conv1ch_wgrad_c8(int, int, int, const void*, int, int, const float*, float*, int, float*, size_t, int, hipStream_t);
-
 int stem_fwd(int B, int H, int W, const float* x, const float* w, void* y, int y_ctotal, int y_coff, int flags,
              const void* mask, int m_ctotal, int m_coff, int dtype, int* bad, int* host, hipStream_t stream) {
   if (dtype != CODON_F32)
@@ -332,9 +327,6 @@ int stem_fwd(int B, int H, int W, const float* x, const float* w, void* y, int y
   return stem_launch<float>(B, H, W, x, w, (float*)y, y_ctotal, y_coff, flags, (const float*)mask, m_ctotal, m_coff,
                             bad, host, stream);
 }
-
-int stem_pair_fwd_c8(int, int, int, const float*, const float*, void*, int, int, const float*, const float*, void*, int, int,
-                     int, int*, int*, int*, hipStream_t);
 
 int stem_pair_fwd(int B, int H, int W, const float* xa, const float* wa, void* ya, int ya_ctotal, int ya_coff,
                   const float* xb, const float* wb, void* yb, int yb_ctotal, int yb_coff, int dtype, int* bad, int* host_a,

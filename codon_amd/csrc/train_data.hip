@@ -16,6 +16,7 @@
 // 16-bit depth: code c is lut16[c] = float32(float64(c) / depth_max), a 65 536-entry table, and the degraded
 // input goes back onto the data set's own grid: x = lut16[rint(clamp(x, 0, 1) * (float)depth_max)].
 
+#include "kernels.h"
 #include "train_record.h"
 
 #pragma clang fp contract(off)

@@ -13,6 +13,7 @@
 
 #include "codon_common.h"
 #include "dot4_rn.h"
+#include "kernels.h"
 
 // this file must round every operation separately (dot4_rn.h)
 #pragma clang fp contract(off)

@@ -9,6 +9,7 @@
 // index i.  Changing one word by d != 0 changes the sum by d * odd * odd != 0 mod 2^64: every single-word change is
 // detected, and the odd position factor makes swaps visible.
 #include "codon_common.h"
+#include "kernels.h"
 
 namespace codon {
 

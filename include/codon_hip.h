@@ -188,8 +188,8 @@ int codon_cac_tail_fwd(int32_t batch, int32_t height, int32_t width, int32_t nti
 int codon_conv_pair_begin(void);
 int codon_conv_pair_end(codon_stream_t stream);
 
-/* Which tiling the fp32 conv entry points give a launch of this shape -- a host-side restatement of the launch rule (no GPU
- * call, nothing is launched): diagnostics, and the CPU tests that pin the rule.  `chained`: codon_conv_chain1x1_fwd
+/* Which tiling the fp32 conv entry points give a launch of this shape -- the launch rule itself, the one function the
+ * launchers ask, called without a launch (host arithmetic, no GPU call): diagnostics, and the CPU tests that pin the rule.  `chained`: codon_conv_chain1x1_fwd
  * (conv5x5 128->128 + 1x1) instead of codon_conv2d_fwd; `in_pair`: as inside a codon_conv_pair_begin / _end bracket.
  * A launch of a few rounds of workgroups is priced by its rounds (256 CUs, two 4-wave workgroups per CU):
  * 8 x 32 pixel tiles two per CU, 4 x 32 two per CU, 4 x 32 one per CU, or (small launches) 2 x 32 with the couts split

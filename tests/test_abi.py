@@ -48,7 +48,8 @@ def test_host_arg_helpers_without_gpu():
 
 
 def test_fp32_launch_rule_without_gpu():
-    """codon_conv_tiling_f32 restates the fp32 launch rule on the host (csrc/conv_mfma_f32.hip grid_mode): a
+    """codon_conv_tiling_f32 is the fp32 launch rule, the function the launchers themselves ask (csrc/conv_mfma_f32.hip f32_tiling,
+    DESIGN.md 3.1 and 3.1.1), called on the host without a launch: a
     launch of a few rounds of workgroups is priced by its rounds -- 256 CUs, two 4-wave workgroups per CU, the last round at
     its full price -- and takes the cheapest of 8 x 32 two per CU, 4 x 32 two per CU, 4 x 32 one per CU; below 384 tiles of
     8 x 32 it is the small-grid mode (4 x 32 one per CU, or 2 x 32 cout-split up to 192 tiles alone / 128 per launch of a pair)."""
