@@ -16,6 +16,8 @@
 #pragma once
 #include <hip/hip_bf16.h>
 
+#include <initializer_list>
+
 #include "codon_common.h"
 
 namespace codon {
@@ -103,9 +105,45 @@ __device__ __forceinline__ void c8_st(const u32x4 q, const __amdgpu_buffer_rsrc_
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// host side: a C8 slice argument.  planes = 8-channel planes per image in the buffer, plane0 = first plane of the slice
+// ---- host side: the rules every 16-bit launcher follows, each stated once ----------------------------------
+
+// a C8 slice argument: whole 8-channel planes inside the buffer
 static inline bool c8_slice_ok(int ctotal, int coff, int c) {
   return ctotal % 8 == 0 && coff % 8 == 0 && c % 8 == 0 && coff >= 0 && coff + c <= ctotal;
+}
+
+// Element type: f(C8F16{}) or f(C8Bf16{}) -- the one place a dtype becomes a template argument, so that a launch names each of
+// its arguments once.  f launches (or forwards to a `template <class E> ..._launch`) and returns the status.
+template <class F>
+static inline auto c8_dispatch(int dtype, F&& f) {
+  return dtype == CODON_F16 ? f(C8F16{}) : f(C8Bf16{});
+}
+
+// The preamble of every 16-bit entry, under the caller's `name`: every slice is whole planes inside its buffer (BAD_ARG), and
+// an image of `channels` channels stays below the offset no buffer descriptor reaches (UNSUPPORTED).  c8_check makes both
+// refusals in that order; an entry with a check of its own between them calls the two halves.
+struct C8SliceArg {
+  int ctotal, coff, c;
+  bool given = true;      // an optional tensor that is absent passes
+};
+static inline C8SliceArg c8_arg(const codon_tensor* t, int c) {
+  return t ? C8SliceArg{t->ctotal, t->coff, c} : C8SliceArg{0, 0, 0, false};
+}
+static inline int c8_check_slices(const char* name, std::initializer_list<C8SliceArg> slices) {
+  for (const C8SliceArg& s : slices)
+    CODON_REQUIRE(!s.given || c8_slice_ok(s.ctotal, s.coff, s.c), CODON_ERR_BAD_ARG,
+                  "%s: 16-bit tensors are channel-blocked: coff %d / %d channels of ctotal %d must be whole 8-channel planes",
+                  name, s.coff, s.c, s.ctotal);
+  return CODON_OK;
+}
+static inline int c8_check_range(const char* name, int H, int W, int channels) {
+  CODON_REQUIRE((long)H * W * 2 * channels < (long)C8_OOB, CODON_ERR_UNSUPPORTED,
+                "%s: %dx%d image: %d channels exceed the 4 GiB buffer-descriptor range", name, H, W, channels);
+  return CODON_OK;
+}
+static inline int c8_check(const char* name, int H, int W, int channels, std::initializer_list<C8SliceArg> slices) {
+  if (const int st = c8_check_slices(name, slices)) return st;
+  return c8_check_range(name, H, W, channels);
 }
 
 }  // namespace codon

@@ -35,7 +35,17 @@ int check_launch(const char* what) {
 static thread_local PairRecorder g_pair;
 PairRecorder* pair_recorder() { return g_pair.active ? &g_pair : nullptr; }
 
-static bool slice_ok(const codon_tensor* t) { return t && t->data && t->coff >= 0 && t->coff + 64 <= t->ctotal; }
+// channels [coff, coff + c) lie inside a buffer of ctotal channels (whole 8-channel planes are the 16-bit launchers' rule, c8.h)
+static bool in_bounds(int coff, int c, int ctotal) { return coff >= 0 && coff + c <= ctotal; }
+static bool slice_ok(const codon_tensor* t, int c = 64) { return t && t->data && in_bounds(t->coff, c, t->ctotal); }
+// the slices of a conv descriptor: x always, y (cout channels of y_*) and the residual slot (cout channels of r_*) when used
+static bool conv_slices_ok(const codon_conv_desc* d, bool with_y, bool with_res) {
+  return in_bounds(d->x_coff, d->cin, d->x_ctotal) && (!with_y || in_bounds(d->y_coff, d->cout, d->y_ctotal)) &&
+         (!with_res || in_bounds(d->r_coff, d->cout, d->r_ctotal));
+}
+
+static bool is16(int dtype) { return dtype == CODON_BF16 || dtype == CODON_F16; }
+static bool dtype_known(int dtype) { return dtype == CODON_F32 || is16(dtype); }
 
 static bool shape_ok(int b, int h, int w) { return b > 0 && h > 0 && w > 0 && (long)h * w < (1L << 31); }
 
@@ -103,7 +113,7 @@ int codon_conv_pack_weight(const float* w_oihw, void* w_packed, int32_t cout, in
       CODON_REQUIRE(dtype == CODON_F32, CODON_ERR_UNSUPPORTED, "conv_pack_weight: CHAIN1X1_F16X3 is for fp32 tensors");
       return pack_chain1x1_f32x3(w_oihw, w_packed, (hipStream_t)stream);
     }
-    if (dtype == CODON_BF16 || dtype == CODON_F16) return pack_chain1x1_16(w_oihw, w_packed, dtype, (hipStream_t)stream);
+    if (is16(dtype)) return pack_chain1x1_16(w_oihw, w_packed, dtype, (hipStream_t)stream);
     CODON_REQUIRE(dtype == CODON_F32, CODON_ERR_UNSUPPORTED, "conv_pack_weight: CHAIN1X1 dtype %d", dtype);
     return pack_chain1x1_f32(w_oihw, (float*)w_packed, (hipStream_t)stream);
   }
@@ -111,9 +121,9 @@ int codon_conv_pack_weight(const float* w_oihw, void* w_packed, int32_t cout, in
   const int kin = mode == CODON_PACK_DGRAD ? cout : cin;
   CODON_REQUIRE(cout > 0 && cin > 0 && kin % conv_ck(ksize) == 0, CODON_ERR_UNSUPPORTED,
                 "conv_pack_weight: cin=%d cout=%d not a multiple of the channel chunk", cin, cout);
-  if (dtype == CODON_BF16 || dtype == CODON_F16) {
+  if (is16(dtype)) {
     CODON_REQUIRE(kin % 16 == 0, CODON_ERR_UNSUPPORTED, "conv_pack_weight: 16-bit packing needs cin %% 16 == 0");
-    return pack_weight_bf16(w_oihw, w_packed, cout, cin, ksize, mode, dtype, (hipStream_t)stream);
+    return pack_weight_16(w_oihw, w_packed, cout, cin, ksize, mode, dtype, (hipStream_t)stream);
   }
   CODON_REQUIRE(dtype == CODON_F32, CODON_ERR_UNSUPPORTED, "conv_pack_weight: dtype %d", dtype);
   return pack_weight_f32(w_oihw, (float*)w_packed, cout, cin, ksize, mode, (hipStream_t)stream);
@@ -124,9 +134,9 @@ int codon_conv2d_fwd(const codon_conv_desc* d, const void* x, const void* w_pack
   CODON_REQUIRE(d && x && w_packed && y, CODON_ERR_BAD_ARG, "conv2d_fwd: null pointer");
   CODON_REQUIRE(shape_ok(d->batch, d->height, d->width), CODON_ERR_BAD_ARG, "conv2d_fwd: bad shape %dx%dx%d",
                 d->batch, d->height, d->width);
-  CODON_REQUIRE(d->x_coff >= 0 && d->x_coff + d->cin <= d->x_ctotal, CODON_ERR_BAD_ARG,
+  CODON_REQUIRE(in_bounds(d->x_coff, d->cin, d->x_ctotal), CODON_ERR_BAD_ARG,
                 "conv2d_fwd: input slice [%d,%d) outside %d channels", d->x_coff, d->x_coff + d->cin, d->x_ctotal);
-  CODON_REQUIRE(d->y_coff >= 0 && d->y_coff + d->cout <= d->y_ctotal, CODON_ERR_BAD_ARG,
+  CODON_REQUIRE(in_bounds(d->y_coff, d->cout, d->y_ctotal), CODON_ERR_BAD_ARG,
                 "conv2d_fwd: output slice [%d,%d) outside %d channels", d->y_coff, d->y_coff + d->cout, d->y_ctotal);
   // only the public CODON_CONV_* bits: the kernels keep internal selector bits above them (conv_c8.hip: a read-write running
   // sum in the residual slot), which no caller of THIS entry point may reach -- `residual` is const here
@@ -137,15 +147,15 @@ int codon_conv2d_fwd(const codon_conv_desc* d, const void* x, const void* w_pack
                 "conv2d_fwd: ADD_RESIDUAL and MASK_RELU share the residual slot");
   if (d->flags & (CODON_CONV_ADD_RESIDUAL | CODON_CONV_MASK_RELU)) {
     CODON_REQUIRE(residual, CODON_ERR_BAD_ARG, "conv2d_fwd: ADD_RESIDUAL without a residual pointer");
-    CODON_REQUIRE(d->r_coff >= 0 && d->r_coff + d->cout <= d->r_ctotal, CODON_ERR_BAD_ARG,
+    CODON_REQUIRE(in_bounds(d->r_coff, d->cout, d->r_ctotal), CODON_ERR_BAD_ARG,
                   "conv2d_fwd: residual slice outside its buffer");
   }
   CODON_REQUIRE(!(d->flags & CODON_CONV_MASK_SUM) ||
                     ((d->flags & CODON_CONV_MASK_RELU) && (d->flags & CODON_CONV_ACCUM_OUT) && !(d->flags & (CODON_CONV_RELU | CODON_CONV_F16X3))),
                 CODON_ERR_BAD_ARG, "conv2d_fwd: MASK_SUM needs MASK_RELU | ACCUM_OUT (and neither RELU nor F16X3)");
   CODON_REQUIRE(((uintptr_t)w_packed % 16) == 0, CODON_ERR_BAD_ARG, "conv2d_fwd: packed weights not 16-byte aligned");
-  if (d->dtype == CODON_BF16 || d->dtype == CODON_F16)
-    return conv2d_fwd_bf16(d, x, w_packed, y, residual, (hipStream_t)stream);
+  if (is16(d->dtype))
+    return conv2d_fwd_16(d, x, w_packed, y, residual, (hipStream_t)stream);
   CODON_REQUIRE(d->dtype == CODON_F32, CODON_ERR_UNSUPPORTED, "conv2d_fwd: dtype %d", d->dtype);
   if (d->flags & CODON_CONV_F16X3) {
     CODON_REQUIRE(conv_f32x3_supported(d), CODON_ERR_UNSUPPORTED, "conv2d_fwd: no f16x3 kernel for k=%d cin=%d cout=%d",
@@ -161,12 +171,9 @@ int codon_conv2d_sum_into_fwd(const codon_conv_desc* d, const void* x, const voi
   CODON_REQUIRE(d && x && w_packed && y && sum, CODON_ERR_BAD_ARG, "conv2d_sum_into_fwd: null pointer");
   CODON_REQUIRE(shape_ok(d->batch, d->height, d->width), CODON_ERR_BAD_ARG, "conv2d_sum_into_fwd: bad shape %dx%dx%d",
                 d->batch, d->height, d->width);
-  CODON_REQUIRE(d->x_coff >= 0 && d->x_coff + d->cin <= d->x_ctotal && d->y_coff >= 0 && d->y_coff + d->cout <= d->y_ctotal &&
-                    d->r_coff >= 0 && d->r_coff + d->cout <= d->r_ctotal,
-                CODON_ERR_BAD_ARG, "conv2d_sum_into_fwd: channel slice outside its buffer");
+  CODON_REQUIRE(conv_slices_ok(d, true, true), CODON_ERR_BAD_ARG, "conv2d_sum_into_fwd: channel slice outside its buffer");
   CODON_REQUIRE(((uintptr_t)w_packed % 16) == 0, CODON_ERR_BAD_ARG, "conv2d_sum_into_fwd: packed weights not 16-byte aligned");
-  CODON_REQUIRE(d->dtype == CODON_BF16 || d->dtype == CODON_F16, CODON_ERR_UNSUPPORTED,
-                "conv2d_sum_into_fwd: 16-bit dtypes only (dtype %d)", d->dtype);
+  CODON_REQUIRE(is16(d->dtype), CODON_ERR_UNSUPPORTED, "conv2d_sum_into_fwd: 16-bit dtypes only (dtype %d)", d->dtype);
   // `sum` may be another channel slice of the buffer that holds y (or x), never an overlapping one
   auto disjoint = [](int a0, int an, int b0, int bn) { return a0 + an <= b0 || b0 + bn <= a0; };
   CODON_REQUIRE((sum != y || (d->r_ctotal == d->y_ctotal && disjoint(d->r_coff, d->cout, d->y_coff, d->cout))) &&
@@ -180,19 +187,17 @@ int codon_conv_chain1x1_fwd(const codon_conv_desc* d, const void* x, const void*
   CODON_REQUIRE(d && x && w_packed && w_chain && out && out->data, CODON_ERR_BAD_ARG, "conv_chain1x1_fwd: null pointer");
   CODON_REQUIRE(shape_ok(d->batch, d->height, d->width), CODON_ERR_BAD_ARG, "conv_chain1x1_fwd: bad shape %dx%dx%d",
                 d->batch, d->height, d->width);
-  CODON_REQUIRE(d->x_coff >= 0 && d->x_coff + d->cin <= d->x_ctotal, CODON_ERR_BAD_ARG,
+  CODON_REQUIRE(in_bounds(d->x_coff, d->cin, d->x_ctotal), CODON_ERR_BAD_ARG,
                 "conv_chain1x1_fwd: input slice outside its buffer");
-  CODON_REQUIRE(!y || (d->y_coff >= 0 && d->y_coff + d->cout <= d->y_ctotal), CODON_ERR_BAD_ARG,
+  CODON_REQUIRE(!y || in_bounds(d->y_coff, d->cout, d->y_ctotal), CODON_ERR_BAD_ARG,
                 "conv_chain1x1_fwd: intermediate slice outside its buffer");
-  CODON_REQUIRE(out->coff >= 0 && out->coff + 64 <= out->ctotal, CODON_ERR_BAD_ARG,
-                "conv_chain1x1_fwd: output slice outside its buffer");
-  CODON_REQUIRE(!residual || (residual->data && residual->coff >= 0 && residual->coff + 64 <= residual->ctotal),
-                CODON_ERR_BAD_ARG, "conv_chain1x1_fwd: residual slice outside its buffer");
+  CODON_REQUIRE(slice_ok(out), CODON_ERR_BAD_ARG, "conv_chain1x1_fwd: output slice outside its buffer");
+  CODON_REQUIRE(!residual || slice_ok(residual), CODON_ERR_BAD_ARG, "conv_chain1x1_fwd: residual slice outside its buffer");
   CODON_REQUIRE((d->flags & ~(CODON_CONV_RELU | CODON_CONV_F16X3)) == 0, CODON_ERR_BAD_ARG,
                 "conv_chain1x1_fwd: only RELU / F16X3 flags apply to the 5x5 stage");
   CODON_REQUIRE(((uintptr_t)w_packed % 16) == 0 && ((uintptr_t)w_chain % 16) == 0, CODON_ERR_BAD_ARG,
                 "conv_chain1x1_fwd: packed weights not 16-byte aligned");
-  if (d->dtype == CODON_BF16 || d->dtype == CODON_F16) {
+  if (is16(d->dtype)) {
     CODON_REQUIRE(!(d->flags & CODON_CONV_F16X3), CODON_ERR_BAD_ARG, "conv_chain1x1_fwd: F16X3 applies to fp32 tensors");
     return conv_chain1x1_fwd_16(d, x, w_packed, y, w_chain, out, residual, nullptr, nullptr, 0, (hipStream_t)stream);
   }
@@ -215,8 +220,7 @@ int codon_conv_chain1x1_stats_fwd(const codon_conv_desc* d, const void* x, const
   CODON_REQUIRE((d->flags & ~CODON_CONV_RELU) == 0, CODON_ERR_BAD_ARG, "conv_chain1x1_stats_fwd: only the RELU flag applies");
   CODON_REQUIRE(((uintptr_t)w_packed % 16) == 0 && ((uintptr_t)w_chain % 16) == 0 && ((uintptr_t)stats_partials % 8) == 0,
                 CODON_ERR_BAD_ARG, "conv_chain1x1_stats_fwd: misaligned buffer");
-  CODON_REQUIRE(d->x_coff >= 0 && d->x_coff + d->cin <= d->x_ctotal && (!y || (d->y_coff >= 0 && d->y_coff + d->cout <= d->y_ctotal)) &&
-                    out->coff >= 0 && out->coff + 64 <= out->ctotal, CODON_ERR_BAD_ARG,
+  CODON_REQUIRE(conv_slices_ok(d, y != nullptr, false) && slice_ok(out), CODON_ERR_BAD_ARG,
                 "conv_chain1x1_stats_fwd: slice outside its buffer");
   if (d->dtype == CODON_F32) {
     // fp32 (round 6): per-row-strip partials, codon_cac_fused_parts(height, width, CODON_F32) rows per image
@@ -224,7 +228,7 @@ int codon_conv_chain1x1_stats_fwd(const codon_conv_desc* d, const void* x, const
     return conv_chain1x1_fwd_f32(d, (const float*)x, (const float*)w_packed, (float*)y, (const float*)w_chain, out, nullptr,
                                  stats_pool, stats_partials, stats_choff, (hipStream_t)stream);
   }
-  CODON_REQUIRE(d->dtype == CODON_BF16 || d->dtype == CODON_F16, CODON_ERR_UNSUPPORTED, "conv_chain1x1_stats_fwd: dtype %d", d->dtype);
+  CODON_REQUIRE(is16(d->dtype), CODON_ERR_UNSUPPORTED, "conv_chain1x1_stats_fwd: dtype %d", d->dtype);
   return conv_chain1x1_fwd_16(d, x, w_packed, y, w_chain, out, residual, stats_pool, stats_partials, stats_choff,
                               (hipStream_t)stream);
 }
@@ -236,7 +240,7 @@ int32_t codon_cac_fused_tiles(int32_t height, int32_t width) {
 int32_t codon_cac_fused_parts(int32_t height, int32_t width, int32_t dtype) {
   if (height <= 0 || width <= 0) return 0;
   if (dtype == CODON_F32) return height * ((width + 31) / 32);         // one row strip of 32 pixels each
-  if (dtype == CODON_BF16 || dtype == CODON_F16) return cac_fused_tiles(height, width);
+  if (is16(dtype)) return cac_fused_tiles(height, width);
   return 0;
 }
 
@@ -279,19 +283,18 @@ static int gated_fwd(const codon_conv_desc* d, const void* pre, const codon_tens
                 "conv2d_gated_fwd: null pointer");
   CODON_REQUIRE(shape_ok(d->batch, d->height, d->width), CODON_ERR_BAD_ARG, "conv2d_gated_fwd: bad shape %dx%dx%d",
                 d->batch, d->height, d->width);
-  CODON_REQUIRE(d->x_coff >= 0 && d->x_coff + d->cin <= d->x_ctotal && d->x_coff % 64 == 0, CODON_ERR_BAD_ARG,
+  CODON_REQUIRE(in_bounds(d->x_coff, d->cin, d->x_ctotal) && d->x_coff % 64 == 0, CODON_ERR_BAD_ARG,
                 "conv2d_gated_fwd: input slice [%d,%d) of %d channels (must start at a multiple of 64)", d->x_coff,
                 d->x_coff + d->cin, d->x_ctotal);
-  CODON_REQUIRE(inputs->coff >= 0 && inputs->coff + d->cin <= inputs->ctotal, CODON_ERR_BAD_ARG,
-                "conv2d_gated_fwd: `inputs` slice outside its buffer");
-  CODON_REQUIRE(d->y_coff >= 0 && d->y_coff + d->cout <= d->y_ctotal, CODON_ERR_BAD_ARG,
+  CODON_REQUIRE(slice_ok(inputs, d->cin), CODON_ERR_BAD_ARG, "conv2d_gated_fwd: `inputs` slice outside its buffer");
+  CODON_REQUIRE(in_bounds(d->y_coff, d->cout, d->y_ctotal), CODON_ERR_BAD_ARG,
                 "conv2d_gated_fwd: output slice outside its buffer");
   CODON_REQUIRE((d->flags & ~CODON_CONV_RELU) == 0, CODON_ERR_BAD_ARG, "conv2d_gated_fwd: only the RELU flag applies");
   CODON_REQUIRE(((uintptr_t)w_packed % 16) == 0, CODON_ERR_BAD_ARG, "conv2d_gated_fwd: packed weights not 16-byte aligned");
-  if (d->dtype == CODON_BF16 || d->dtype == CODON_F16)
+  if (is16(d->dtype))
     return conv2d_gated_fwd_16(d, pre, inputs, ch, sp, w_packed, y, gated_out, (hipStream_t)stream);
   CODON_REQUIRE(d->dtype == CODON_F32, CODON_ERR_UNSUPPORTED, "conv2d_gated_fwd: dtype %d", d->dtype);
-  CODON_REQUIRE(!gated_out || (gated_out->coff >= 0 && gated_out->coff + d->cin <= gated_out->ctotal), CODON_ERR_BAD_ARG,
+  CODON_REQUIRE(!gated_out || slice_ok(gated_out, d->cin), CODON_ERR_BAD_ARG,
                 "conv2d_gated_emit_fwd: gated_out slice outside its buffer");
   return conv2d_gated_fwd_f32(d, (const float*)pre, inputs, ch, sp, (const float*)w_packed, (float*)y, gated_out, (hipStream_t)stream);
 }
@@ -310,7 +313,7 @@ int codon_conv2d_gated_emit_fwd(const codon_conv_desc* d, const void* pre, const
 
 size_t codon_conv_wgrad_workspace_bytes(const codon_conv_desc* d) {
   if (!d || !shape_ok(d->batch, d->height, d->width)) return 0;
-  if (d->dtype == CODON_BF16 || d->dtype == CODON_F16) return conv_wgrad_bf16_workspace_bytes(d);
+  if (is16(d->dtype)) return conv_wgrad_16_workspace_bytes(d);
   return conv_wgrad_workspace_bytes(d);
 }
 
@@ -319,11 +322,9 @@ int codon_conv2d_wgrad(const codon_conv_desc* d, const void* x, const void* gy, 
   CODON_REQUIRE(d && x && gy && (dw || accumulate == CODON_WGRAD_DEFER) && workspace, CODON_ERR_BAD_ARG, "conv2d_wgrad: null pointer");
   CODON_REQUIRE(accumulate >= 0 && accumulate <= CODON_WGRAD_DEFER, CODON_ERR_BAD_ARG, "conv2d_wgrad: accumulate %d", accumulate);
   CODON_REQUIRE(shape_ok(d->batch, d->height, d->width), CODON_ERR_BAD_ARG, "conv2d_wgrad: bad shape");
-  CODON_REQUIRE(d->x_coff >= 0 && d->x_coff + d->cin <= d->x_ctotal && d->y_coff >= 0 &&
-                    d->y_coff + d->cout <= d->y_ctotal,
-                CODON_ERR_BAD_ARG, "conv2d_wgrad: channel slice outside its buffer");
-  if (d->dtype == CODON_BF16 || d->dtype == CODON_F16)
-    return conv2d_wgrad_bf16(d, x, gy, dw, (float*)workspace, workspace_bytes, accumulate, (hipStream_t)stream);
+  CODON_REQUIRE(conv_slices_ok(d, true, false), CODON_ERR_BAD_ARG, "conv2d_wgrad: channel slice outside its buffer");
+  if (is16(d->dtype))
+    return conv2d_wgrad_16(d, x, gy, dw, (float*)workspace, workspace_bytes, accumulate, (hipStream_t)stream);
   CODON_REQUIRE(d->dtype == CODON_F32, CODON_ERR_UNSUPPORTED, "conv2d_wgrad: dtype %d", d->dtype);
   return conv2d_wgrad_f32(d, (const float*)x, (const float*)gy, dw, (float*)workspace, workspace_bytes, accumulate,
                           (hipStream_t)stream);
@@ -336,11 +337,10 @@ int codon_conv1x1_bwd(const codon_conv_desc* d, const void* x, const void* gy, c
                 CODON_ERR_BAD_ARG, "conv1x1_bwd: null pointer");
   CODON_REQUIRE(accumulate >= 0 && accumulate <= CODON_WGRAD_DEFER, CODON_ERR_BAD_ARG, "conv1x1_bwd: accumulate %d", accumulate);
   CODON_REQUIRE(shape_ok(d->batch, d->height, d->width), CODON_ERR_BAD_ARG, "conv1x1_bwd: bad shape");
-  CODON_REQUIRE(d->x_coff >= 0 && d->x_coff + d->cin <= d->x_ctotal && d->y_coff >= 0 &&
-                    d->y_coff + d->cout <= d->y_ctotal && gx->coff >= 0 && gx->coff + d->cin <= gx->ctotal,
-                CODON_ERR_BAD_ARG, "conv1x1_bwd: channel slice outside its buffer");
+  CODON_REQUIRE(conv_slices_ok(d, true, false) && slice_ok(gx, d->cin), CODON_ERR_BAD_ARG,
+                "conv1x1_bwd: channel slice outside its buffer");
   CODON_REQUIRE(((uintptr_t)w_packed_dgrad % 16) == 0, CODON_ERR_BAD_ARG, "conv1x1_bwd: packed weights not 16-byte aligned");
-  CODON_REQUIRE(d->dtype == CODON_BF16 || d->dtype == CODON_F16, CODON_ERR_UNSUPPORTED,
+  CODON_REQUIRE(is16(d->dtype), CODON_ERR_UNSUPPORTED,
                 "conv1x1_bwd: 16-bit dtypes only (dtype %d): call codon_conv2d_wgrad + codon_conv2d_fwd", d->dtype);
   return conv1x1_bwd_16(d, x, gy, w_packed_dgrad, gx, dw, (float*)workspace, workspace_bytes, accumulate, (hipStream_t)stream,
                         nullptr);
@@ -355,13 +355,11 @@ int codon_conv1x1_bwd_gated(const codon_conv_desc* d, const void* x, const void*
                 CODON_ERR_BAD_ARG, "conv1x1_bwd_gated: null pointer");
   CODON_REQUIRE(accumulate >= 0 && accumulate <= CODON_WGRAD_DEFER, CODON_ERR_BAD_ARG, "conv1x1_bwd_gated: accumulate %d", accumulate);
   CODON_REQUIRE(shape_ok(d->batch, d->height, d->width), CODON_ERR_BAD_ARG, "conv1x1_bwd_gated: bad shape");
-  CODON_REQUIRE(d->x_coff >= 0 && d->x_coff + d->cin <= d->x_ctotal && d->y_coff >= 0 &&
-                    d->y_coff + d->cout <= d->y_ctotal && gx->coff >= 0 && gx->coff + d->cin <= gx->ctotal,
-                CODON_ERR_BAD_ARG, "conv1x1_bwd_gated: channel slice outside its buffer");
+  CODON_REQUIRE(conv_slices_ok(d, true, false) && slice_ok(gx, d->cin), CODON_ERR_BAD_ARG,
+                "conv1x1_bwd_gated: channel slice outside its buffer");
   CODON_REQUIRE(fcat_base == 0 || fcat_base == 64, CODON_ERR_BAD_ARG, "conv1x1_bwd_gated: fcat_base %d (0 colour, 64 depth)", fcat_base);
   CODON_REQUIRE(((uintptr_t)w_packed_dgrad % 16) == 0, CODON_ERR_BAD_ARG, "conv1x1_bwd_gated: packed weights not 16-byte aligned");
-  CODON_REQUIRE(d->dtype == CODON_BF16 || d->dtype == CODON_F16, CODON_ERR_UNSUPPORTED,
-                "conv1x1_bwd_gated: 16-bit dtypes only (dtype %d)", d->dtype);
+  CODON_REQUIRE(is16(d->dtype), CODON_ERR_UNSUPPORTED, "conv1x1_bwd_gated: 16-bit dtypes only (dtype %d)", d->dtype);
   const Conv1x1GateBwd gb{ch, sp, g_pooled, g_pools, argpix, argch, fcat_base};
   return conv1x1_bwd_16(d, x, g_out, w_packed_dgrad, gx, dw, (float*)workspace, workspace_bytes, accumulate, (hipStream_t)stream,
                         &gb);
@@ -377,8 +375,8 @@ int codon_stem_fwd_guarded(int32_t batch, int32_t height, int32_t width, const f
                            codon_stream_t stream) {
   CODON_REQUIRE(x && w_oihw && y, CODON_ERR_BAD_ARG, "stem_fwd: null pointer");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "stem_fwd: bad shape");
-  CODON_REQUIRE(y_coff >= 0 && y_coff + 64 <= y_ctotal, CODON_ERR_BAD_ARG, "stem_fwd: output slice outside buffer");
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "stem_fwd: dtype %d", dtype);
+  CODON_REQUIRE(in_bounds(y_coff, 64, y_ctotal), CODON_ERR_BAD_ARG, "stem_fwd: output slice outside buffer");
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "stem_fwd: dtype %d", dtype);
   return stem_fwd(batch, height, width, x, w_oihw, y, y_ctotal, y_coff, 1, nullptr, 0, 0, dtype, bad, host_word,
                   (hipStream_t)stream);
 }
@@ -396,11 +394,11 @@ int codon_stem_pair_fwd_guarded(int32_t batch, int32_t height, int32_t width, co
                                 int32_t* host_word_b, codon_stream_t stream) {
   CODON_REQUIRE(xa && wa_oihw && ya && xb && wb_oihw && yb, CODON_ERR_BAD_ARG, "stem_pair_fwd: null pointer");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "stem_pair_fwd: bad shape");
-  CODON_REQUIRE(ya_coff >= 0 && ya_coff + 64 <= ya_ctotal && yb_coff >= 0 && yb_coff + 64 <= yb_ctotal, CODON_ERR_BAD_ARG,
+  CODON_REQUIRE(in_bounds(ya_coff, 64, ya_ctotal) && in_bounds(yb_coff, 64, yb_ctotal), CODON_ERR_BAD_ARG,
                 "stem_pair_fwd: output slice outside buffer");
   CODON_REQUIRE(ya != yb || ya_coff + 64 <= yb_coff || yb_coff + 64 <= ya_coff, CODON_ERR_BAD_ARG,
                 "stem_pair_fwd: the two output slices overlap");
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "stem_pair_fwd: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "stem_pair_fwd: dtype %d", dtype);
   return stem_pair_fwd(batch, height, width, xa, wa_oihw, ya, ya_ctotal, ya_coff, xb, wb_oihw, yb, yb_ctotal, yb_coff, dtype,
                        bad, host_word_a, host_word_b, (hipStream_t)stream);
 }
@@ -415,8 +413,8 @@ int codon_head_fwd_guarded(int32_t batch, int32_t height, int32_t width, const v
                            codon_stream_t stream) {
   CODON_REQUIRE(x && w_oihw && residual && y, CODON_ERR_BAD_ARG, "head_fwd: null pointer");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "head_fwd: bad shape");
-  CODON_REQUIRE(x_coff >= 0 && x_coff + 64 <= x_ctotal, CODON_ERR_BAD_ARG, "head_fwd: input slice outside buffer");
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "head_fwd: dtype %d", dtype);
+  CODON_REQUIRE(in_bounds(x_coff, 64, x_ctotal), CODON_ERR_BAD_ARG, "head_fwd: input slice outside buffer");
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "head_fwd: dtype %d", dtype);
   return head_fwd(batch, height, width, x, x_ctotal, x_coff, w_oihw, residual, y, false, dtype, bad, (hipStream_t)stream);
 }
 
@@ -430,8 +428,8 @@ int codon_head_fwd_y16_guarded(int32_t batch, int32_t height, int32_t width, con
                                codon_stream_t stream) {
   CODON_REQUIRE(x && w_oihw && residual && y16, CODON_ERR_BAD_ARG, "head_fwd_y16: null pointer");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "head_fwd_y16: bad shape");
-  CODON_REQUIRE(x_coff >= 0 && x_coff + 64 <= x_ctotal, CODON_ERR_BAD_ARG, "head_fwd_y16: input slice outside buffer");
-  CODON_REQUIRE((dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED,
+  CODON_REQUIRE(in_bounds(x_coff, 64, x_ctotal), CODON_ERR_BAD_ARG, "head_fwd_y16: input slice outside buffer");
+  CODON_REQUIRE(is16(dtype), CODON_ERR_UNSUPPORTED,
                 "head_fwd_y16: dtype %d (the 16-bit output exists for 16-bit activations)", dtype);
   CODON_REQUIRE(((uintptr_t)y16 % 2) == 0, CODON_ERR_BAD_ARG, "head_fwd_y16: output not 2-byte aligned");
   return head_fwd(batch, height, width, x, x_ctotal, x_coff, w_oihw, residual, y16, true, dtype, bad, (hipStream_t)stream);
@@ -449,7 +447,7 @@ int codon_cac_stats_fwd(int32_t batch, int32_t height, int32_t width, const codo
                 "cac_stats_fwd: null pointer or bad channel slice");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "cac_stats_fwd: bad shape");
   CODON_REQUIRE(((uintptr_t)partials % 8) == 0, CODON_ERR_BAD_ARG, "cac_stats_fwd: partials not 8-byte aligned");
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "cac_stats_fwd: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "cac_stats_fwd: dtype %d", dtype);
   return cac_stats_fwd(batch, height, width, pre_c, pre, pooled, partials, dtype, (hipStream_t)stream, nullptr);
 }
 
@@ -460,7 +458,7 @@ int codon_cac_stats_scaled_fwd(int32_t batch, int32_t height, int32_t width, con
                 "cac_stats_scaled_fwd: null pointer or bad channel slice");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "cac_stats_scaled_fwd: bad shape");
   CODON_REQUIRE(((uintptr_t)partials % 8) == 0, CODON_ERR_BAD_ARG, "cac_stats_scaled_fwd: partials not 8-byte aligned");
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "cac_stats_scaled_fwd: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "cac_stats_scaled_fwd: dtype %d", dtype);
   return cac_stats_fwd(batch, height, width, pre_c, pre, pooled, partials, dtype, (hipStream_t)stream, ch);
 }
 
@@ -468,7 +466,7 @@ int codon_ew_sq_scale(int32_t batch, int32_t height, int32_t width, const codon_
                       const codon_tensor* y, int32_t dtype, codon_stream_t stream) {
   CODON_REQUIRE(slice_ok(x) && slice_ok(y) && ch, CODON_ERR_BAD_ARG, "ew_sq_scale: null pointer or bad channel slice");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "ew_sq_scale: bad shape");
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "ew_sq_scale: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "ew_sq_scale: dtype %d", dtype);
   return ew_sq_scale(batch, height, width, x, ch, y, dtype, (hipStream_t)stream);
 }
 
@@ -495,7 +493,7 @@ int codon_cac_apply_fwd(int32_t batch, int32_t height, int32_t width, const codo
                     slice_ok(out) && slice_ok(out_c),
                 CODON_ERR_BAD_ARG, "cac_apply_fwd: null pointer or bad channel slice");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "cac_apply_fwd: bad shape");
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "cac_apply_fwd: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "cac_apply_fwd: dtype %d", dtype);
   return cac_apply_fwd(batch, height, width, pre, pre_c, ch, sp, inputs, inputs_c, out, out_c, dtype,
                        (hipStream_t)stream);
 }
@@ -506,7 +504,7 @@ int codon_stencil_1to64(int32_t batch, int32_t height, int32_t width, const floa
   CODON_REQUIRE(x && w_64x9 && slice_ok(y) && (!mask || slice_ok(mask)), CODON_ERR_BAD_ARG,
                 "stencil_1to64: null pointer or bad channel slice");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "stencil_1to64: bad shape");
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "stencil_1to64: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "stencil_1to64: dtype %d", dtype);
   return stem_fwd(batch, height, width, x, w_64x9, y->data, y->ctotal, y->coff, flags, mask ? mask->data : nullptr,
                   mask ? mask->ctotal : 0, mask ? mask->coff : 0, dtype, nullptr, nullptr, (hipStream_t)stream);
 }
@@ -519,7 +517,7 @@ size_t codon_conv1ch_wgrad_workspace_bytes(int32_t batch, int32_t height, int32_
 int codon_conv1ch_wgrad(int32_t batch, int32_t height, int32_t width, const codon_tensor* a, const float* s,
                         float* dw, int32_t flip, void* workspace, size_t workspace_bytes, int32_t dtype,
                         codon_stream_t stream) {
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "conv1ch_wgrad: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "conv1ch_wgrad: dtype %d", dtype);
   CODON_REQUIRE(slice_ok(a) && s && (dw || (flip & CODON_W1_DEFER)) && workspace, CODON_ERR_BAD_ARG,
                 "conv1ch_wgrad: null pointer or bad slice");
   CODON_REQUIRE((flip & ~(CODON_W1_FLIP | CODON_W1_ACCUMULATE | CODON_W1_DEFER)) == 0, CODON_ERR_BAD_ARG, "conv1ch_wgrad: flip 0x%x", (unsigned)flip);
@@ -573,8 +571,7 @@ int codon_conv_tiling_f32(const codon_conv_desc* d, int chained, int in_pair) {
 
 int codon_conv_form_c8(const codon_conv_desc* d) {
   CODON_REQUIRE(d && shape_ok(d->batch, d->height, d->width), CODON_ERR_BAD_ARG, "conv_form_c8: null descriptor or bad shape");
-  CODON_REQUIRE(d->dtype == CODON_BF16 || d->dtype == CODON_F16, CODON_ERR_UNSUPPORTED,
-                "conv_form_c8: dtype %d is not a 16-bit dtype", d->dtype);
+  CODON_REQUIRE(is16(d->dtype), CODON_ERR_UNSUPPORTED, "conv_form_c8: dtype %d is not a 16-bit dtype", d->dtype);
   return conv_form_c8(d);
 }
 
@@ -612,8 +609,8 @@ int codon_reduce_multi(const codon_reduce_item* items, int32_t n_items, codon_st
 int codon_ew_add_mask(int32_t batch, int32_t height, int32_t width, int32_t channels, const codon_tensor* dst,
                       const codon_tensor* src, const codon_tensor* mask, int32_t accumulate, int32_t dtype,
                       codon_stream_t stream) {
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "ew_add_mask: dtype %d", dtype);
-  auto ok = [&](const codon_tensor* t) { return t && t->data && t->coff >= 0 && t->coff + channels <= t->ctotal; };
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "ew_add_mask: dtype %d", dtype);
+  auto ok = [&](const codon_tensor* t) { return slice_ok(t, channels); };
   CODON_REQUIRE(channels > 0 && ok(dst) && (!src || ok(src)) && (!mask || ok(mask)), CODON_ERR_BAD_ARG,
                 "ew_add_mask: null pointer or bad channel slice");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "ew_add_mask: bad shape");
@@ -623,8 +620,8 @@ int codon_ew_add_mask(int32_t batch, int32_t height, int32_t width, int32_t chan
 int codon_ew_sum_mask(int32_t batch, int32_t height, int32_t width, int32_t channels, const codon_tensor* dst, int32_t nsrc,
                       const codon_tensor* src0, const codon_tensor* src1, const codon_tensor* src2, const codon_tensor* src3,
                       const codon_tensor* mask, int32_t dtype, codon_stream_t stream) {
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "ew_sum_mask: dtype %d", dtype);
-  auto ok = [&](const codon_tensor* t) { return t && t->data && t->coff >= 0 && t->coff + channels <= t->ctotal; };
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "ew_sum_mask: dtype %d", dtype);
+  auto ok = [&](const codon_tensor* t) { return slice_ok(t, channels); };
   const codon_tensor* srcs[4] = {src0, src1, src2, src3};
   CODON_REQUIRE(nsrc >= 1 && nsrc <= 4, CODON_ERR_BAD_ARG, "ew_sum_mask: %d sources (1..4)", nsrc);
   for (int i = 0; i < nsrc; ++i)
@@ -645,7 +642,7 @@ int codon_cac_bwd_reduce(int32_t batch, int32_t height, int32_t width, const cod
                          const codon_tensor* g_out_c, const codon_tensor* pre, const codon_tensor* pre_c,
                          const float* ch, const float* sp, const float* pools, float* g_z, float* part_gch,
                          int32_t* part_arg, int32_t dtype, codon_stream_t stream) {
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "cac_bwd_reduce: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "cac_bwd_reduce: dtype %d", dtype);
   CODON_REQUIRE(slice_ok(g_out) && slice_ok(g_out_c) && slice_ok(pre) && slice_ok(pre_c) && ch && sp && pools &&
                     g_z && part_gch && part_arg,
                 CODON_ERR_BAD_ARG, "cac_bwd_reduce: null pointer or bad channel slice");
@@ -659,7 +656,7 @@ int codon_cac_bwd_reduce_acc(int32_t batch, int32_t height, int32_t width, const
                              const float* ch, const float* sp, const float* pools, const float* pooled, float* g_z,
                              float* part_gch, int32_t* part_arg, int32_t* argch, const codon_tensor* g_in,
                              const codon_tensor* g_in_c, int32_t accumulate_in, int32_t dtype, codon_stream_t stream) {
-  CODON_REQUIRE(dtype == CODON_BF16 || dtype == CODON_F16, CODON_ERR_UNSUPPORTED,
+  CODON_REQUIRE(is16(dtype), CODON_ERR_UNSUPPORTED,
                 "cac_bwd_reduce_acc: 16-bit dtypes only (dtype %d): fp32 takes codon_cac_bwd_reduce + codon_cac_bwd_apply", dtype);
   CODON_REQUIRE(slice_ok(g_out) && slice_ok(g_out_c) && slice_ok(pre) && slice_ok(pre_c) && slice_ok(g_in) && slice_ok(g_in_c) &&
                     ch && sp && pools && pooled && g_z && part_gch && part_arg && argch,
@@ -696,7 +693,7 @@ int codon_cac_bwd_apply(int32_t batch, int32_t height, int32_t width, const codo
                         const float* g_pools, const int32_t* argpix, const codon_tensor* g_pre,
                         const codon_tensor* g_pre_c, const codon_tensor* g_in, const codon_tensor* g_in_c,
                         int32_t accumulate_in, int32_t dtype, codon_stream_t stream) {
-  CODON_REQUIRE((dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16), CODON_ERR_UNSUPPORTED, "cac_bwd_apply: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "cac_bwd_apply: dtype %d", dtype);
   CODON_REQUIRE(slice_ok(g_out) && slice_ok(g_out_c) && slice_ok(pre) && slice_ok(pre_c) && ch && sp && pooled &&
                     g_pooled && g_pools && argpix && slice_ok(g_pre) && slice_ok(g_pre_c) && slice_ok(g_in) &&
                     slice_ok(g_in_c),
@@ -726,8 +723,7 @@ int codon_masked_sqerr(int64_t n, const uint8_t* label, const uint8_t* out, uint
 
 int codon_postprocess_u16_dt(int64_t n, const void* x, int32_t dtype, int32_t depth_max, uint16_t* out, codon_stream_t stream) {
   CODON_REQUIRE(x && out && n > 0, CODON_ERR_BAD_ARG, "postprocess_u16_dt: null pointer or n <= 0");
-  CODON_REQUIRE(dtype == CODON_F32 || dtype == CODON_F16 || dtype == CODON_BF16, CODON_ERR_UNSUPPORTED,
-                "postprocess_u16_dt: dtype %d (fp32, fp16 or bf16)", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "postprocess_u16_dt: dtype %d (fp32, fp16 or bf16)", dtype);
   CODON_REQUIRE(depth_max >= 1 && depth_max <= 65535, CODON_ERR_BAD_ARG, "postprocess_u16_dt: depth_max %d (1..65535)",
                 depth_max);
   CODON_REQUIRE(((uintptr_t)out & 1) == 0, CODON_ERR_BAD_ARG, "postprocess_u16_dt: out is not 2-byte aligned");
@@ -863,8 +859,7 @@ int codon_lr_codes_to_input(int32_t batch, int32_t lr_height, int32_t lr_width, 
                             int32_t dtype, codon_stream_t stream) {
   CODON_REQUIRE(codes && lut && phase_weights && out, CODON_ERR_BAD_ARG, "lr_codes_to_input: null pointer");
   CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "lr_codes_to_input: scale %d", scale);
-  CODON_REQUIRE(dtype == CODON_F32 || dtype == CODON_F16 || dtype == CODON_BF16, CODON_ERR_UNSUPPORTED,
-                "lr_codes_to_input: dtype %d (fp32, fp16 or bf16)", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "lr_codes_to_input: dtype %d (fp32, fp16 or bf16)", dtype);
   CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "lr_codes_to_input: code_bits %d (8 or 16)", code_bits);
   CODON_REQUIRE(code_bits == 16 ? (depth_max >= 1 && depth_max <= 65535) : depth_max == 255, CODON_ERR_BAD_ARG,
                 "lr_codes_to_input: depth_max %d (255 for 8-bit codes, 1..65535 for 16-bit codes)", depth_max);
@@ -897,7 +892,7 @@ int codon_d4_views(int32_t batch, int32_t height, int32_t width, const void* src
   CODON_REQUIRE(src1 ? (upright1 && transposed1) : (!upright1 && !transposed1), CODON_ERR_BAD_ARG,
                 "d4_views: src1, upright1 and transposed1 go together (all three, or all three NULL)");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "d4_views: bad shape %dx%dx%d", batch, height, width);
-  CODON_REQUIRE(dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16, CODON_ERR_BAD_ARG, "d4_views: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_BAD_ARG, "d4_views: dtype %d", dtype);
   CODON_REQUIRE(batch <= 32767, CODON_ERR_UNSUPPORTED, "d4_views: batch %d (at most 32767 images per launch)", batch);
   return d4_views(batch, height, width, src0, src1, dtype, upright0, transposed0, upright1, transposed1, (hipStream_t)stream);
 }
@@ -906,7 +901,7 @@ int codon_d4_merge(int32_t batch, int32_t height, int32_t width, const void* upr
                    float* out_f32, codon_stream_t stream) {
   CODON_REQUIRE(upright && transposed && out_f32, CODON_ERR_BAD_ARG, "d4_merge: null pointer");
   CODON_REQUIRE(shape_ok(batch, height, width), CODON_ERR_BAD_ARG, "d4_merge: bad shape %dx%dx%d", batch, height, width);
-  CODON_REQUIRE(dtype == CODON_F32 || dtype == CODON_BF16 || dtype == CODON_F16, CODON_ERR_BAD_ARG, "d4_merge: dtype %d", dtype);
+  CODON_REQUIRE(dtype_known(dtype), CODON_ERR_BAD_ARG, "d4_merge: dtype %d", dtype);
   CODON_REQUIRE(batch <= 32767, CODON_ERR_UNSUPPORTED, "d4_merge: batch %d (at most 32767 images per launch)", batch);
   return d4_merge(batch, height, width, upright, transposed, dtype, out_f32, (hipStream_t)stream);
 }

@@ -78,7 +78,7 @@ constexpr int CONV_C8_SUM_INTO = 1 << 16;
 // pixel rows per wave: the 5x5 64-cout kernel takes 4 (16x32 tile) so that, like the 128-cout ones, a filter tap is
 // 8 MFMAs on 6 operand fetches.  (Measured and settled, profiles/HISTORY.md: 16x32 tiles for the 3x3 convs, 8-wave
 // workgroups for any of the shapes, staging through registers instead of LDS-DMA -- all slower; the switches are gone.)
-constexpr bool C8_DMA = true;     // x and weights go global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds); GATE kernels stage x through registers
+// x and weights go global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds); GATE kernels stage both through registers.
 template <int KS, int COUT> struct ConvC8Pseg { static constexpr int value = (COUT == 64 && KS == 5) ? 4 : 2; };
 // waves per workgroup of the staged kernels (the resident-filter conv3x3 runs 16)
 template <int KS, int COUT> struct ConvC8Nw { static constexpr int value = 4; };
@@ -103,7 +103,7 @@ template <int KS, int CIN, int COUT, int NW> constexpr int conv_c8_lds_vecs();
 template <class E, int KS, int CIN, int COUT, bool FUSE = false, int NW = 4, bool GATE = false, bool PERSIST = false,
           bool RESW = false, bool EXTLDS = false>
 __device__ __forceinline__ void conv_c8_body(const ConvC8Params& p, const int tile0, uint4* ext_lds = nullptr) {
-  static_assert(!PERSIST || (!FUSE && !GATE && C8_DMA), "the tile loop exists for the plain LDS-DMA convs");
+  static_assert(!PERSIST || (!FUSE && !GATE), "the tile loop exists for the plain LDS-DMA convs");
   static_assert(!RESW || PERSIST, "a resident filter pays only over many tiles");
   typedef typename E::vec8 vec8;
   typedef const volatile __attribute__((address_space(3))) u32x4* lds_rd;
@@ -219,16 +219,17 @@ __device__ __forceinline__ void conv_c8_body(const ConvC8Params& p, const int ti
 
   // the next chunk's halo tile is requested in two halves, during the last two filter rows of the current chunk
   constexpr int XE1 = XE / 2, XEH = XE - XE1;
-  constexpr bool DMA = C8_DMA && !GATE;      // the halo tile: by LDS-DMA, or -- GATE: the gate arithmetic needs the VALU -- through registers
+  // the halo tile and the weight rows: by LDS-DMA, or -- GATE: the gate arithmetic needs the VALU -- through registers
+  constexpr bool DMA = !GATE;
   // (the weight rows of a GATE kernel by LDS-DMA while x goes through registers: measured in round 5, 1.80 vs 1.74 ms gated,
   // 1.98 vs 1.91 gated + emitting -- the vmcnt(0) in front of the barrier then also waits for the emit stores;
-  // tools/probes/gate_weights_dma_experiment.patch)
-  constexpr bool DMAW = DMA;
+  // tools/probes/gate_weights_dma_experiment.patch -- a record of that experiment: it, and the other patches under tools/probes
+  // whose context names the C8_DMA / DMAW switches, were cut against the file as it was then and no longer apply to it)
   typedef __attribute__((address_space(3))) void lds_void;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   u32x4 xv[DMA ? 1 : XEH];
   u32x4 xg[GATE ? XEH : 1];
-  u32x4 wr[DMAW ? 1 : WE];
+  u32x4 wr[DMA ? 1 : WE];
 
 #define LOAD_XP(rs_, off_, chunk_, buf_, k0_, k1_)                                      \
   {                                                                                     \
@@ -272,7 +273,7 @@ __device__ __forceinline__ void conv_c8_body(const ConvC8Params& p, const int ti
   if constexpr (!RESW) {                                                                \
     const unsigned so_ = (unsigned)(stage_) * (unsigned)(WS * 16);                      \
     _Pragma("unroll") for (int k = 0; k < WE; ++k) {                                    \
-      if constexpr (DMAW) {                                                              \
+      if constexpr (DMA) {                                                             \
         if (WS % NT == 0 || k < WE - 1 || k * NT + wave_u * 64 < WS)                    \
           __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (lds_void*)(lds + 2 * XSP + (buf_) * WSP + k * NT + wave_u * 64), 16, \
                                                    k == WE - 1 ? wvo_last : wvo, so_ + k * (unsigned)(NT * 16), 0, 0); \
@@ -282,7 +283,7 @@ __device__ __forceinline__ void conv_c8_body(const ConvC8Params& p, const int ti
     }                                                                                   \
   }
 #define STORE_W(buf_)                                                                   \
-  if constexpr (!DMAW) {                                                                 \
+  if constexpr (!DMA) {                                                                \
     _Pragma("unroll") for (int k = 0; k < WE; ++k) ww[(buf_) * WSP + k * NT] = wr[k];   \
   }
 
@@ -307,7 +308,7 @@ __device__ __forceinline__ void conv_c8_body(const ConvC8Params& p, const int ti
   }
   STORE_X(0, 0, XE1, XE);
   STORE_W(0);
-  if constexpr (DMAW) __builtin_amdgcn_s_waitcnt(0x0070);    // vmcnt(0): this wave's pieces have landed
+  if constexpr (DMA) __builtin_amdgcn_s_waitcnt(0x0070);    // vmcnt(0): this wave's pieces have landed
   __syncthreads();
 
   static_assert(!PERSIST || (NST % 2 == 0), "the tile loop re-enters with stage parity 0");
@@ -418,7 +419,7 @@ __device__ __forceinline__ void conv_c8_body(const ConvC8Params& p, const int ti
       }
       // RESW: nothing changes hands inside a chunk -- one barrier per chunk, the one that publishes the next halo tile
       if constexpr (!RESW || dy == KS - 1) {
-        if constexpr (DMAW) __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) before the barrier: DMA pieces of the next stage are in LDS
+        if constexpr (DMA) __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) before the barrier: DMA pieces of the next stage are in LDS
         __syncthreads();
       }
     });
@@ -893,32 +894,51 @@ __global__ void pack_chain1x1_c8_kernel(const float* __restrict__ w, unsigned sh
 }
 
 int pack_chain1x1_16(const float* w, void* out, int dtype, hipStream_t stream) {
-  if (dtype == CODON_F16)
-    hipLaunchKernelGGL(pack_chain1x1_c8_kernel<C8F16>, dim3(32), dim3(256), 0, stream, w, (unsigned short*)out);
-  else
-    hipLaunchKernelGGL(pack_chain1x1_c8_kernel<C8Bf16>, dim3(32), dim3(256), 0, stream, w, (unsigned short*)out);
-  return check_launch("pack_chain1x1_c8_kernel");
+  return c8_dispatch(dtype, [&](auto e) {
+    hipLaunchKernelGGL(pack_chain1x1_c8_kernel<decltype(e)>, dim3(32), dim3(256), 0, stream, w, (unsigned short*)out);
+    return check_launch("pack_chain1x1_c8_kernel");
+  });
 }
 
-int pack_weight_bf16(const float* w, void* out, int cout, int cin, int ks, int mode, int dtype, hipStream_t stream) {
+int pack_weight_16(const float* w, void* out, int cout, int cin, int ks, int mode, int dtype, hipStream_t stream) {
   const long n = (long)cout * cin * ks * ks;
   const int blocks = (int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256);
   const int kout = mode == CODON_PACK_DGRAD ? cin : cout;
   CODON_REQUIRE(kout % 32 == 0, CODON_ERR_UNSUPPORTED, "conv_pack_weight: 16-bit packing needs 32-row output tiles (got %d)", kout);
-  if (dtype == CODON_F16)
-    hipLaunchKernelGGL(pack_weight_c8_kernel<C8F16>, dim3(blocks), dim3(256), 0, stream, w, (unsigned short*)out, cout,
+  return c8_dispatch(dtype, [&](auto e) {
+    hipLaunchKernelGGL(pack_weight_c8_kernel<decltype(e)>, dim3(blocks), dim3(256), 0, stream, w, (unsigned short*)out, cout,
                        cin, ks, mode == CODON_PACK_DGRAD ? 1 : 0);
-  else
-    hipLaunchKernelGGL(pack_weight_c8_kernel<C8Bf16>, dim3(blocks), dim3(256), 0, stream, w, (unsigned short*)out, cout,
-                       cin, ks, mode == CODON_PACK_DGRAD ? 1 : 0);
-  return check_launch("pack_weight_c8_kernel");
+    return check_launch("pack_weight_c8_kernel");
+  });
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------
-static bool c8_desc_ok(const codon_conv_desc* d, bool with_res) {
-  if (!c8_slice_ok(d->x_ctotal, d->x_coff, d->cin) || !c8_slice_ok(d->y_ctotal, d->y_coff, d->cout)) return false;
-  if (with_res && !c8_slice_ok(d->r_ctotal, d->r_coff, d->cout)) return false;
-  return true;
+// THE preamble of the conv entries (c8.h): the descriptor's x / y [/ residual] slices, and the descriptor range at 128 channels
+// -- the widest slice any conv kernel's descriptors span -- whatever cin and cout are (a 64 -> 64 conv of an image only a
+// 128-channel tensor would overflow is refused too; kept as it is).
+static int c8_conv_check(const char* name, const codon_conv_desc* d, bool with_res, std::initializer_list<C8SliceArg> more = {}) {
+  if (const int st = c8_check_slices(name, {{d->x_ctotal, d->x_coff, d->cin}, {d->y_ctotal, d->y_coff, d->cout},
+                                            {d->r_ctotal, d->r_coff, d->cout, with_res}}))
+    return st;
+  return c8_check(name, d->height, d->width, 128, more);
+}
+
+// THE tile grid of a 16-bit conv launch: tiles of 32 pixels by `th` rows over every image.  c8_tile_grid puts it into the
+// parameter block and refuses, under the caller's name, a grid the launch cannot index.
+struct C8Tiles {
+  int tiles_x, tiles_y;
+  long nblk;
+};
+static C8Tiles c8_tiles(int B, int H, int W, int th) {
+  const int tx = (W + 31) / 32, ty = (H + th - 1) / th;
+  return C8Tiles{tx, ty, (long)tx * ty * B};
+}
+template <int KS, int COUT> constexpr int c8_tile_rows() { return ConvC8Nw<KS, COUT>::value * ConvC8Pseg<KS, COUT>::value; }
+static int c8_tile_grid(const char* name, const codon_conv_desc* d, int th, ConvC8Params& p) {
+  const C8Tiles t = c8_tiles(d->batch, d->height, d->width, th);
+  CODON_REQUIRE(t.nblk < (1L << 31), CODON_ERR_UNSUPPORTED, "%s: grid too large (%ld blocks)", name, t.nblk);
+  p.tiles_x = t.tiles_x; p.tiles_y = t.tiles_y; p.nblk = (int)t.nblk;
+  return CODON_OK;
 }
 
 static void c8_fill(ConvC8Params& p, const codon_conv_desc* d, const void* x, const void* w, void* y, const void* res) {
@@ -976,13 +996,14 @@ static int c8_resident_blocks(K kernel, int threads) {
 constexpr int C8_RESIDENT_MIN_TILES = 8;
 constexpr int C8_NWR = 16;                                   // waves of the resident-filter workgroup: 32 x 32 tiles
 constexpr int C8_THR = C8_NWR * ConvC8Pseg<3, 64>::value;
+template <int KS, int CIN, int COUT> constexpr bool c8_has_resident() { return KS == 3 && CIN == 64 && COUT == 64; }
 // THE rule that sends a plain 16-bit conv3x3 64->64 of this shape to the resident-filter form, asked by launch_conv_c8 and by
 // codon_conv_form_c8 (include/codon_hip.h) so that the launch and the query cannot drift apart.  Returns the workgroups of the
 // resident generation, or 0 for the staged one-tile-per-workgroup form (also when the occupancy query fails: so does the launch).
 template <class E>
 static int c8_resident_grid(const codon_conv_desc* d) {
   const int res = c8_resident_blocks(conv_c8_kernel<E, 3, 64, 64, false, C8_NWR, false, true, true>, 64 * C8_NWR);
-  const long nblkr = (long)((d->width + 31) / 32) * ((d->height + C8_THR - 1) / C8_THR) * d->batch;
+  const long nblkr = c8_tiles(d->batch, d->height, d->width, C8_THR).nblk;
   return (res > 0 && nblkr >= (long)res * C8_RESIDENT_MIN_TILES) ? res : 0;
 }
 template <class E, int KS, int CIN, int COUT, bool FUSE, int NW, bool GATE>
@@ -1013,18 +1034,15 @@ static int launch_mix53_c8(const void* five, const void* three, hipStream_t stre
 template <class E, int KS, int CIN, int COUT, bool FUSE, bool GATE = false>
 static int launch_conv_c8(ConvC8Params& p, const codon_conv_desc* d, hipStream_t stream) {
   constexpr int NW = ConvC8Nw<KS, COUT>::value;
-  constexpr int TH = NW * ConvC8Pseg<KS, COUT>::value;
-  p.tiles_x = (d->width + 31) / 32;
-  p.tiles_y = (d->height + TH - 1) / TH;
-  const long nblk = (long)p.tiles_x * p.tiles_y * d->batch;
-  CODON_REQUIRE(nblk < (1L << 31), CODON_ERR_UNSUPPORTED, "conv2d_fwd: grid too large (%ld blocks)", nblk);
-  p.nblk = (int)nblk;
-  if constexpr (KS == 3 && CIN == 64 && COUT == 64 && !FUSE && !GATE && C8_DMA) {
+  // (under the plain conv's name for the chained and the gated entries too: kept as it is)
+  if (const int st = c8_tile_grid("conv2d_fwd", d, c8_tile_rows<KS, COUT>(), p)) return st;
+  if constexpr (c8_has_resident<KS, CIN, COUT>() && !FUSE && !GATE) {
     // resident-filter persistent form: 16 waves, 32 x 32 tiles, one workgroup per CU
     if (const int res = c8_resident_grid<E>(d)) {
       ConvC8Params pr = p;
-      pr.tiles_y = (d->height + C8_THR - 1) / C8_THR;
-      pr.nblk = (int)((long)p.tiles_x * pr.tiles_y * d->batch);
+      const C8Tiles tr = c8_tiles(d->batch, d->height, d->width, C8_THR);      // no more blocks than the grid just accepted
+      pr.tiles_y = tr.tiles_y;
+      pr.nblk = (int)tr.nblk;
       hipLaunchKernelGGL((conv_c8_kernel<E, KS, CIN, COUT, FUSE, C8_NWR, GATE, true, true>), dim3((unsigned)res),
                          dim3(64 * C8_NWR), 0, stream, pr);
       return check_launch("conv_c8_kernel<resident>");
@@ -1043,51 +1061,59 @@ static int launch_conv_c8(ConvC8Params& p, const codon_conv_desc* d, hipStream_t
   return launch_single_c8<E, KS, CIN, COUT, FUSE, NW, GATE>(&p, stream);
 }
 
-template <class E>
-static int conv2d_fwd_c8(const codon_conv_desc* d, const void* x, const void* w, void* y, const void* res,
-                         hipStream_t stream) {
-  ConvC8Params p;
-  c8_fill(p, d, x, w, y, res);
-  const int key = d->ksize * 1000000 + d->cin * 1000 + d->cout;
-  switch (key) {
-    case 5128128: return launch_conv_c8<E, 5, 128, 128, false>(p, d, stream);
-    case 5064064: return launch_conv_c8<E, 5, 64, 64, false>(p, d, stream);
-    case 3064064: return launch_conv_c8<E, 3, 64, 64, false>(p, d, stream);
-    case 3128064: return launch_conv_c8<E, 3, 128, 64, false>(p, d, stream);
-    case 3064128: return launch_conv_c8<E, 3, 64, 128, false>(p, d, stream);
-    case 1128064: return launch_conv1x1_c8<E, 128, 64>(d, x, w, y, res, stream);
-    case 1064128: return launch_conv1x1_c8<E, 64, 128>(d, x, w, y, res, stream);
-    default:
-      set_error("conv2d_fwd: no 16-bit kernel for k=%d cin=%d cout=%d", d->ksize, d->cin, d->cout);
-      return CODON_ERR_UNSUPPORTED;
+// THE set of (k, cin, cout) that have a 16-bit kernel, listed here and nowhere else: the plain conv, the gated conv (the
+// shapes marked GATED) and codon_conv_form_c8 all come through this visitor.  f(C8Shape<..>{}) for a shape of the set; any
+// other is refused under the caller's name.
+template <int KS, int CIN, int COUT, bool GATED = false>
+struct C8Shape {
+  static constexpr int ks = KS, cin = CIN, cout = COUT;
+  static constexpr bool gated = GATED;
+};
+static int c8_no_kernel(const char* name, const codon_conv_desc* d) {
+  set_error("%s: no 16-bit kernel for k=%d cin=%d cout=%d", name, d->ksize, d->cin, d->cout);
+  return CODON_ERR_UNSUPPORTED;
+}
+template <class F>
+static int c8_visit_shape(const char* name, const codon_conv_desc* d, F&& f) {
+  switch (d->ksize * 1000000 + d->cin * 1000 + d->cout) {
+    case 5128128: return f(C8Shape<5, 128, 128>{});
+    case 5064064: return f(C8Shape<5, 64, 64, true>{});
+    case 3064064: return f(C8Shape<3, 64, 64, true>{});
+    case 3128064: return f(C8Shape<3, 128, 64, true>{});
+    case 3064128: return f(C8Shape<3, 64, 128>{});
+    case 1128064: return f(C8Shape<1, 128, 64>{});
+    case 1064128: return f(C8Shape<1, 64, 128>{});
+    default: return c8_no_kernel(name, d);
   }
 }
 
-// codon_conv_form_c8 (include/codon_hip.h): the form conv2d_fwd_c8 gives a launch of this shape, without launching it
+// codon_conv_form_c8 (include/codon_hip.h): the form conv2d_fwd_16 gives a launch of this shape, without launching it
 int conv_form_c8(const codon_conv_desc* d) {
-  const int key = d->ksize * 1000000 + d->cin * 1000 + d->cout;
-  switch (key) {
-    case 3064064:
-      return (d->dtype == CODON_F16 ? c8_resident_grid<C8F16>(d) : c8_resident_grid<C8Bf16>(d)) ? CODON_C8_FORM_RESIDENT
-                                                                                                : CODON_C8_FORM_STAGED;
-    case 5128128: case 5064064: case 3128064: case 3064128: case 1128064: case 1064128:
-      return CODON_C8_FORM_STAGED;
-    default:
-      set_error("conv_form_c8: no 16-bit kernel for k=%d cin=%d cout=%d", d->ksize, d->cin, d->cout);
-      return CODON_ERR_UNSUPPORTED;
-  }
+  return c8_visit_shape("conv_form_c8", d, [&](auto s) {
+    typedef decltype(s) S;
+    if constexpr (c8_has_resident<S::ks, S::cin, S::cout>())
+      if (c8_dispatch(d->dtype, [&](auto e) { return c8_resident_grid<decltype(e)>(d); })) return CODON_C8_FORM_RESIDENT;
+    return CODON_C8_FORM_STAGED;
+  });
 }
 
-int conv2d_fwd_bf16(const codon_conv_desc* d, const void* x, const void* w, void* y, const void* res,
-                    hipStream_t stream) {
+int conv2d_fwd_16(const codon_conv_desc* d, const void* x, const void* w, void* y, const void* res, hipStream_t stream) {
   const bool with_res = res && (d->flags & (CODON_CONV_ADD_RESIDUAL | CODON_CONV_MASK_RELU));
-  CODON_REQUIRE(c8_desc_ok(d, with_res), CODON_ERR_BAD_ARG,
-                "conv2d_fwd: 16-bit tensors are channel-blocked: ctotal / coff / channels must be multiples of 8");
-  const long HW = (long)d->height * d->width;
-  CODON_REQUIRE(HW * 2 * 128 < (long)C8_OOB, CODON_ERR_UNSUPPORTED,
-                "conv2d_fwd: %dx%d image: 128 channels exceed the 4 GiB buffer-descriptor range", d->height, d->width);
-  return d->dtype == CODON_F16 ? conv2d_fwd_c8<C8F16>(d, x, w, y, with_res ? res : nullptr, stream)
-                               : conv2d_fwd_c8<C8Bf16>(d, x, w, y, with_res ? res : nullptr, stream);
+  if (const int st = c8_conv_check("conv2d_fwd", d, with_res)) return st;
+  if (!with_res) res = nullptr;
+  return c8_visit_shape("conv2d_fwd", d, [&](auto s) {
+    typedef decltype(s) S;
+    return c8_dispatch(d->dtype, [&](auto e) {
+      typedef decltype(e) E;
+      if constexpr (S::ks == 1) {
+        return launch_conv1x1_c8<E, S::cin, S::cout>(d, x, w, y, res, stream);
+      } else {
+        ConvC8Params p;
+        c8_fill(p, d, x, w, y, res);
+        return launch_conv_c8<E, S::ks, S::cin, S::cout, false>(p, d, stream);
+      }
+    });
+  });
 }
 
 // y (+)= conv5x5(x) (64 -> 64) and, in the same epilogue, sum += y
@@ -1095,26 +1121,16 @@ int conv2d_sum_into_16(const codon_conv_desc* d, const void* x, const void* w, v
   CODON_REQUIRE(d->ksize == 5 && d->cin == 64 && d->cout == 64, CODON_ERR_UNSUPPORTED,
                 "conv2d_sum_into_fwd: the 16-bit conv5x5 64->64 only (got k=%d %d->%d)", d->ksize, d->cin, d->cout);
   CODON_REQUIRE((d->flags & ~CODON_CONV_ACCUM_OUT) == 0, CODON_ERR_BAD_ARG, "conv2d_sum_into_fwd: only ACCUM_OUT applies");
-  CODON_REQUIRE(c8_desc_ok(d, true), CODON_ERR_BAD_ARG,
-                "conv2d_sum_into_fwd: 16-bit tensors are channel-blocked: ctotal / coff / channels must be multiples of 8");
-  const long HW = (long)d->height * d->width;
-  CODON_REQUIRE(HW * 2 * 128 < (long)C8_OOB, CODON_ERR_UNSUPPORTED,
-                "conv2d_sum_into_fwd: %dx%d image: 128 channels exceed the 4 GiB buffer-descriptor range", d->height, d->width);
+  if (const int st = c8_conv_check("conv2d_sum_into_fwd", d, true)) return st;
   ConvC8Params p;
   c8_fill(p, d, x, w, y, sum);
   p.flags |= CONV_C8_SUM_INTO;
-  // the plain one-tile-per-workgroup kernel (the variant is not compiled into the tile-loop forms)
-  constexpr int NW = ConvC8Nw<5, 64>::value, TH = NW * ConvC8Pseg<5, 64>::value;
-  p.tiles_x = (d->width + 31) / 32;
-  p.tiles_y = (d->height + TH - 1) / TH;
-  const long nblk = (long)p.tiles_x * p.tiles_y * d->batch;
-  CODON_REQUIRE(nblk < (1L << 31), CODON_ERR_UNSUPPORTED, "conv2d_sum_into_fwd: grid too large (%ld blocks)", nblk);
-  p.nblk = (int)nblk;
-  if (d->dtype == CODON_F16)
-    hipLaunchKernelGGL((conv_c8_kernel<C8F16, 5, 64, 64, false, NW, false>), dim3((unsigned)nblk), dim3(64 * NW), 0, stream, p);
-  else
-    hipLaunchKernelGGL((conv_c8_kernel<C8Bf16, 5, 64, 64, false, NW, false>), dim3((unsigned)nblk), dim3(64 * NW), 0, stream, p);
-  return check_launch("conv_c8_kernel<sum into>");
+  if (const int st = c8_tile_grid("conv2d_sum_into_fwd", d, c8_tile_rows<5, 64>(), p)) return st;
+  // the plain one-tile-per-workgroup kernel (the variant is not compiled into the tile-loop forms), launched at once: a call
+  // inside an open pair bracket is not held back (no pair_hold), so it never leaves as a pair or mix53 grid
+  return c8_dispatch(d->dtype, [&](auto e) {
+    return launch_single_c8<decltype(e), 5, 64, 64, false, ConvC8Nw<5, 64>::value, false>(&p, stream);
+  });
 }
 
 int conv_chain1x1_fwd_16(const codon_conv_desc* d, const void* x, const void* w, void* y, const void* w_chain,
@@ -1122,12 +1138,11 @@ int conv_chain1x1_fwd_16(const codon_conv_desc* d, const void* x, const void* w,
                          hipStream_t stream) {
   CODON_REQUIRE(d->ksize == 5 && d->cin == 128 && d->cout == 128, CODON_ERR_UNSUPPORTED,
                 "conv_chain1x1_fwd: 16-bit kernel is conv5x5 128->128 + 1x1 128->64 (got k=%d %d->%d)", d->ksize, d->cin, d->cout);
-  CODON_REQUIRE(c8_slice_ok(d->x_ctotal, d->x_coff, 128) && (!y || c8_slice_ok(d->y_ctotal, d->y_coff, 128)) &&
-                    c8_slice_ok(out->ctotal, out->coff, 64) && (!res || c8_slice_ok(res->ctotal, res->coff, 64)),
-                CODON_ERR_BAD_ARG, "conv_chain1x1_fwd: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
+  if (const int st = c8_check("conv_chain1x1_fwd", d->height, d->width, 128,
+                              {{d->x_ctotal, d->x_coff, 128}, {d->y_ctotal, d->y_coff, 128, y != nullptr}, c8_arg(out, 64),
+                               c8_arg(res, 64)}))
+    return st;
   const long HW = (long)d->height * d->width;
-  CODON_REQUIRE(HW * 2 * 128 < (long)C8_OOB, CODON_ERR_UNSUPPORTED,
-                "conv_chain1x1_fwd: %dx%d image: 128 channels exceed the 4 GiB buffer-descriptor range", d->height, d->width);
   ConvC8Params p;
   c8_fill(p, d, x, w, y, res ? res->data : nullptr);
   if (!y) { p.y_img = p.y_base = 0; }
@@ -1136,42 +1151,30 @@ int conv_chain1x1_fwd_16(const codon_conv_desc* d, const void* x, const void* w,
   p.w2 = (const uint4*)w_chain; p.y2 = (uint4*)out->data;
   p.y2_img = (out->ctotal / 8) * HW; p.y2_base = (out->coff / 8) * HW;
   p.st_pool = st_pool; p.st_part = st_part; p.st_choff = st_choff;
-  return d->dtype == CODON_F16 ? launch_conv_c8<C8F16, 5, 128, 128, true>(p, d, stream)
-                               : launch_conv_c8<C8Bf16, 5, 128, 128, true>(p, d, stream);
+  return c8_dispatch(d->dtype, [&](auto e) { return launch_conv_c8<decltype(e), 5, 128, 128, true>(p, d, stream); });
 }
 
 // y = conv(pre * (ch * sp) + inputs) [ReLU]: the gate-apply formed while the halo tile is staged (inference)
-template <class E>
-static int conv2d_gated_c8(ConvC8Params& p, const codon_conv_desc* d, hipStream_t stream) {
-  const int key = d->ksize * 1000000 + d->cin * 1000 + d->cout;
-  switch (key) {
-    case 5064064: return launch_conv_c8<E, 5, 64, 64, false, true>(p, d, stream);
-    case 3064064: return launch_conv_c8<E, 3, 64, 64, false, true>(p, d, stream);
-    case 3128064: return launch_conv_c8<E, 3, 128, 64, false, true>(p, d, stream);
-    default:
-      set_error("conv2d_gated_fwd: no 16-bit kernel for k=%d cin=%d cout=%d", d->ksize, d->cin, d->cout);
-      return CODON_ERR_UNSUPPORTED;
-  }
-}
-
 int conv2d_gated_fwd_16(const codon_conv_desc* d, const void* pre, const codon_tensor* inputs, const float* ch,
                         const float* sp, const void* w, void* y, const codon_tensor* gated_out, hipStream_t stream) {
-  CODON_REQUIRE(c8_desc_ok(d, false) && c8_slice_ok(inputs->ctotal, inputs->coff, d->cin), CODON_ERR_BAD_ARG,
-                "conv2d_gated_fwd: 16-bit tensors are channel-blocked: ctotal / coff / channels multiples of 8");
+  if (const int st = c8_conv_check("conv2d_gated_fwd", d, false, {c8_arg(inputs, d->cin)})) return st;
   const long HW = (long)d->height * d->width;
-  CODON_REQUIRE(HW * 2 * 128 < (long)C8_OOB, CODON_ERR_UNSUPPORTED,
-                "conv2d_gated_fwd: %dx%d image: 128 channels exceed the 4 GiB buffer-descriptor range", d->height, d->width);
   ConvC8Params p;
   c8_fill(p, d, pre, w, y, nullptr);
   p.gin = (const uint4*)inputs->data; p.g_img = (inputs->ctotal / 8) * HW; p.g_base = (inputs->coff / 8) * HW;
   p.gch = ch; p.gsp = sp;
   if (gated_out != nullptr) {
-    CODON_REQUIRE(gated_out->data != nullptr && c8_slice_ok(gated_out->ctotal, gated_out->coff, d->cin), CODON_ERR_BAD_ARG,
-                  "conv2d_gated_emit_fwd: gated_out slice [%d,%d) of %d channels", gated_out->coff,
-                  gated_out->coff + d->cin, gated_out->ctotal);
+    CODON_REQUIRE(gated_out->data != nullptr, CODON_ERR_BAD_ARG, "conv2d_gated_emit_fwd: null gated_out");
+    if (const int st = c8_check_slices("conv2d_gated_emit_fwd", {c8_arg(gated_out, d->cin)})) return st;
     p.gout = (uint4*)gated_out->data; p.go_img = (gated_out->ctotal / 8) * HW; p.go_base = (gated_out->coff / 8) * HW;
   }
-  return d->dtype == CODON_F16 ? conv2d_gated_c8<C8F16>(p, d, stream) : conv2d_gated_c8<C8Bf16>(p, d, stream);
+  return c8_visit_shape("conv2d_gated_fwd", d, [&](auto s) {
+    typedef decltype(s) S;
+    if constexpr (!S::gated) return c8_no_kernel("conv2d_gated_fwd", d);
+    else return c8_dispatch(d->dtype, [&](auto e) {
+      return launch_conv_c8<decltype(e), S::ks, S::cin, S::cout, false, true>(p, d, stream);
+    });
+  });
 }
 
 // tiles of the fused-statistics partials: the conv5x5 128->128 kernel's 8 x 32 (NW * PSEG rows) pixel tiles.
@@ -1182,8 +1185,7 @@ int conv2d_gated_fwd_16(const codon_conv_desc* d, const void* pre, const codon_t
 // per block).  Every 16-bit launch keeps the 8 x 32 tile at any batch, so per-tile partials are batch-invariant as they are.
 // tools/probes/c8_4x32_tiles_strip_statistics_experiment.patch, tools/probes/c8_tile_ab.py, profiles/HISTORY.md.)
 int cac_fused_tiles(int H, int W) {
-  constexpr int TH = ConvC8Nw<5, 128>::value * ConvC8Pseg<5, 128>::value;
-  return ((W + 31) / 32) * ((H + TH - 1) / TH);
+  return (int)c8_tiles(1, H, W, c8_tile_rows<5, 128>()).nblk;
 }
 
 }  // namespace codon

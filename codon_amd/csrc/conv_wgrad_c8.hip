@@ -640,13 +640,13 @@ static bool wgrad16_plan(const codon_conv_desc* d, Wgrad16Plan* pl) {
   return true;
 }
 
-size_t conv_wgrad_bf16_workspace_bytes(const codon_conv_desc* d) {
+size_t conv_wgrad_16_workspace_bytes(const codon_conv_desc* d) {
   Wgrad16Plan pl;
   if (!wgrad16_plan(d, &pl)) return 0;
   return (size_t)pl.nsplit * d->cout * d->cin * d->ksize * d->ksize * sizeof(float);
 }
 
-// What conv2d_wgrad_bf16 and conv1x1_bwd_16 (`who`, for the error texts) do before they pick a kernel: the plan, the slice,
+// What conv2d_wgrad_16 and conv1x1_bwd_16 (`who`, for the error texts) do before they pick a kernel: the plan, the slice,
 // workspace, split-count and descriptor-range checks, and the parameter block with its dg_* / gb_* fields null.
 static int wgrad16_prepare(const char* who, const codon_conv_desc* d, const void* x, const void* gy, float* workspace,
                            size_t ws_bytes, Wgrad16Plan* pl, WgradC8Params* p) {
@@ -654,23 +654,25 @@ static int wgrad16_prepare(const char* who, const codon_conv_desc* d, const void
     set_error("%s: no 16-bit kernel for k=%d cin=%d cout=%d", who, d->ksize, d->cin, d->cout);
     return CODON_ERR_UNSUPPORTED;
   }
-  CODON_REQUIRE(c8_slice_ok(d->x_ctotal, d->x_coff, d->cin) && c8_slice_ok(d->y_ctotal, d->y_coff, d->cout),
-                CODON_ERR_BAD_ARG, "%s: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8", who);
-  CODON_REQUIRE(ws_bytes >= conv_wgrad_bf16_workspace_bytes(d), CODON_ERR_BAD_ARG,
-                "%s: workspace %zu B < required %zu B", who, ws_bytes, conv_wgrad_bf16_workspace_bytes(d));
+  if (const int st = c8_check_slices(who, {{d->x_ctotal, d->x_coff, d->cin}, {d->y_ctotal, d->y_coff, d->cout}})) return st;
+  CODON_REQUIRE(ws_bytes >= conv_wgrad_16_workspace_bytes(d), CODON_ERR_BAD_ARG,
+                "%s: workspace %zu B < required %zu B", who, ws_bytes, conv_wgrad_16_workspace_bytes(d));
   CODON_REQUIRE(pl->nsplit <= 65535, CODON_ERR_UNSUPPORTED, "%s: %d splits > 65535", who, pl->nsplit);
-  CODON_REQUIRE((long)d->height * d->width * 2 * 128 < (long)C8_OOB, CODON_ERR_UNSUPPORTED,
-                "%s: %dx%d image: 128 channels exceed the 4 GiB buffer-descriptor range", who, d->height, d->width);
+  // (the two halves of c8_check with the workspace and split-count refusals between them, the order they always had; 128
+  // channels whatever cin is, as for the forward convs)
+  if (const int st = c8_check_range(who, d->height, d->width, 128)) return st;
   *p = wgrad_fill<WgradC8Params>(d, x, gy, workspace, 8, pl->nbands, pl->nsplit);
   return CODON_OK;
 }
 
-int conv2d_wgrad_bf16(const codon_conv_desc* d, const void* x, const void* gy, float* dw, float* workspace,
-                      size_t ws_bytes, int accumulate, hipStream_t stream) {
+int conv2d_wgrad_16(const codon_conv_desc* d, const void* x, const void* gy, float* dw, float* workspace,
+                    size_t ws_bytes, int accumulate, hipStream_t stream) {
   Wgrad16Plan pl;
   WgradC8Params p;
   if (const int st = wgrad16_prepare("conv2d_wgrad", d, x, gy, workspace, ws_bytes, &pl, &p)) return st;
   const dim3 grid(pl.nchan_blocks, pl.nsplit);
+  // (not through c8_dispatch: the bf16 5x5 launches instantiations tagged by shape that fp16 does not have; the 3x3 and 1x1
+  // arms could go through it, but as one-line pairs they are shorter than the lambdas would be, so they stay spelled out)
   const bool f16 = d->dtype == CODON_F16;
   if (d->ksize == 5) {
     const dim3 blk(Wc8Waves<5>::value * 64);
@@ -698,8 +700,7 @@ int conv1x1_bwd_16(const codon_conv_desc* d, const void* x, const void* gy, cons
                    const Conv1x1GateBwd* gb) {
   CODON_REQUIRE(d->ksize == 1 && d->cin == 128 && d->cout == 64, CODON_ERR_UNSUPPORTED,
                 "conv1x1_bwd: k=%d cin=%d cout=%d (the fused pass exists for the 128 -> 64 1x1 convs)", d->ksize, d->cin, d->cout);
-  CODON_REQUIRE(c8_slice_ok(gx->ctotal, gx->coff, d->cin), CODON_ERR_BAD_ARG,
-                "conv1x1_bwd: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
+  if (const int st = c8_check_slices("conv1x1_bwd", {c8_arg(gx, d->cin)})) return st;
   Wgrad16Plan pl;
   WgradC8Params p;
   if (const int st = wgrad16_prepare("conv1x1_bwd", d, x, gy, workspace, ws_bytes, &pl, &p)) return st;
@@ -711,15 +712,12 @@ int conv1x1_bwd_16(const codon_conv_desc* d, const void* x, const void* gy, cons
     p.gb_ch = gb->ch; p.gb_sp = gb->sp; p.gb_gpooled = gb->g_pooled; p.gb_gpools = gb->g_pools;
     p.gb_argpix = gb->argpix; p.gb_argch = gb->argch; p.gb_fbase = gb->fbase;
     p.gb_inv_hw = (float)(1.0 / (double)HW);                  // as cac_bwd_apply forms it
-    if (d->dtype == CODON_F16)
-      hipLaunchKernelGGL((conv_wgrad_c8_kernel<C8F16, 1, true, 0, 0, true>), grid, dim3(2 * WC8_TH * 64), 0, stream, p);
-    else
-      hipLaunchKernelGGL((conv_wgrad_c8_kernel<C8Bf16, 1, true, 0, 0, true>), grid, dim3(2 * WC8_TH * 64), 0, stream, p);
-  } else {
-    if (d->dtype == CODON_F16) hipLaunchKernelGGL((conv_wgrad_c8_kernel<C8F16, 1, true>), grid, dim3(2 * WC8_TH * 64), 0, stream, p);
-    else hipLaunchKernelGGL((conv_wgrad_c8_kernel<C8Bf16, 1, true>), grid, dim3(2 * WC8_TH * 64), 0, stream, p);
   }
-  const int st = check_launch("conv_wgrad_c8_kernel<1, dgrad>");
+  const int st = c8_dispatch(d->dtype, [&](auto e) {
+    const auto kernel = gb ? &conv_wgrad_c8_kernel<decltype(e), 1, true, 0, 0, true> : &conv_wgrad_c8_kernel<decltype(e), 1, true>;
+    hipLaunchKernelGGL(kernel, grid, dim3(2 * WC8_TH * 64), 0, stream, p);
+    return check_launch("conv_wgrad_c8_kernel<1, dgrad>");
+  });
   if (st != CODON_OK || accumulate == CODON_WGRAD_DEFER) return st;
   return launch_wgrad_reduce(workspace, dw, d->cout, d->cin, 1, pl.nsplit, accumulate, stream);
 }

@@ -166,13 +166,12 @@ static int stem_c8_pair_launch(int B, int H, int W, const float* xa, const float
 int stem_pair_fwd_c8(int B, int H, int W, const float* xa, const float* wa, void* ya, int ya_ctotal, int ya_coff,
                      const float* xb, const float* wb, void* yb, int yb_ctotal, int yb_coff, int dtype, int* bad, int* host_a,
                      int* host_b, hipStream_t stream) {
-  CODON_REQUIRE(c8_slice_ok(ya_ctotal, ya_coff, 64) && c8_slice_ok(yb_ctotal, yb_coff, 64), CODON_ERR_BAD_ARG,
-                "stem_pair: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
+  if (const int st = c8_check("stem_pair", H, W, 64, {{ya_ctotal, ya_coff, 64}, {yb_ctotal, yb_coff, 64}})) return st;
   const long HW = (long)H * W;
-  CODON_REQUIRE(HW * 2 * 64 < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "stem_pair: image too large for 32-bit buffer offsets");
   const C8Slice sa = c8_mk(ya, ya_ctotal, ya_coff, HW), sb = c8_mk(yb, yb_ctotal, yb_coff, HW);
-  return dtype == CODON_F16 ? stem_c8_pair_launch<C8F16>(B, H, W, xa, wa, sa, xb, wb, sb, bad, host_a, host_b, stream)
-                            : stem_c8_pair_launch<C8Bf16>(B, H, W, xa, wa, sa, xb, wb, sb, bad, host_a, host_b, stream);
+  return c8_dispatch(dtype, [&](auto e) {
+    return stem_c8_pair_launch<decltype(e)>(B, H, W, xa, wa, sa, xb, wb, sb, bad, host_a, host_b, stream);
+  });
 }
 
 template <class E>
@@ -190,14 +189,13 @@ static int stem_c8_launch(int B, int H, int W, const float* x, const float* w, C
 
 int stem_fwd_c8(int B, int H, int W, const float* x, const float* w, void* y, int y_ctotal, int y_coff, int flags,
                 const void* mask, int m_ctotal, int m_coff, int dtype, int* bad, int* host, hipStream_t stream) {
-  CODON_REQUIRE(c8_slice_ok(y_ctotal, y_coff, 64) && (!mask || c8_slice_ok(m_ctotal, m_coff, 64)), CODON_ERR_BAD_ARG,
-                "stem: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
+  if (const int st = c8_check("stem", H, W, 64, {{y_ctotal, y_coff, 64}, {m_ctotal, m_coff, 64, mask != nullptr}})) return st;
   const long HW = (long)H * W;
-  CODON_REQUIRE(HW * 2 * 64 < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "stem: image too large for 32-bit buffer offsets");
   const C8Slice ys = c8_mk(y, y_ctotal, y_coff, HW);
   const C8Slice ms = mask ? c8_mk(mask, m_ctotal, m_coff, HW) : ys;
-  return dtype == CODON_F16 ? stem_c8_launch<C8F16>(B, H, W, x, w, ys, ms, mask ? 1 : 0, flags, bad, host, stream)
-                            : stem_c8_launch<C8Bf16>(B, H, W, x, w, ys, ms, mask ? 1 : 0, flags, bad, host, stream);
+  return c8_dispatch(dtype, [&](auto e) {
+    return stem_c8_launch<decltype(e)>(B, H, W, x, w, ys, ms, mask ? 1 : 0, flags, bad, host, stream);
+  });
 }
 
 // ---- head: y = conv3x3_{64->1}(x) + res -------------------------------------------------------------------------------
@@ -306,15 +304,13 @@ static int head_c8_launch(int B, int H, int W, C8Slice x, const float* w, const 
 
 int head_fwd_c8(int B, int H, int W, const void* x, int x_ctotal, int x_coff, const float* w, const float* res, void* y,
                 bool y16, int dtype, const int* bad, hipStream_t stream) {
-  CODON_REQUIRE(c8_slice_ok(x_ctotal, x_coff, 64), CODON_ERR_BAD_ARG,
-                "head_fwd: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
-  const long HW = (long)H * W;
-  CODON_REQUIRE(HW * 2 * 64 < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "head_fwd: image too large for 32-bit buffer offsets");
-  const C8Slice xs = c8_mk(x, x_ctotal, x_coff, HW);
-  const bool big = (long)B * H * W >= (1L << 22);
-  if (dtype == CODON_F16)
-    return big ? head_c8_launch<C8F16, 8>(B, H, W, xs, w, res, y, y16, bad, stream) : head_c8_launch<C8F16, 4>(B, H, W, xs, w, res, y, y16, bad, stream);
-  return big ? head_c8_launch<C8Bf16, 8>(B, H, W, xs, w, res, y, y16, bad, stream) : head_c8_launch<C8Bf16, 4>(B, H, W, xs, w, res, y, y16, bad, stream);
+  if (const int st = c8_check("head_fwd", H, W, 64, {{x_ctotal, x_coff, 64}})) return st;
+  const C8Slice xs = c8_mk(x, x_ctotal, x_coff, (long)H * W);
+  const bool big = (long)B * H * W >= (1L << 22);       // bands of 8 rows instead of 4
+  return c8_dispatch(dtype, [&](auto e) {
+    const auto launch = big ? &head_c8_launch<decltype(e), 8> : &head_c8_launch<decltype(e), 4>;
+    return launch(B, H, W, xs, w, res, y, y16, bad, stream);
+  });
 }
 
 // ---- weight gradient of the 1->64 / 64->1 3x3 convs ------------------------------------------------------------------
@@ -392,19 +388,17 @@ size_t conv1ch_wgrad_c8_workspace_bytes(int B, int H, int W) {
 
 int conv1ch_wgrad_c8(int B, int H, int W, const void* a, int a_ctotal, int a_coff, const float* s, float* dw, int flip,
                      float* ws, size_t ws_bytes, int dtype, hipStream_t stream) {
-  CODON_REQUIRE(c8_slice_ok(a_ctotal, a_coff, 64), CODON_ERR_BAD_ARG,
-                "conv1ch_wgrad: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
+  // (no descriptor-range refusal here: the fp32 entry has none either, and adding one is a change of behaviour)
+  if (const int st = c8_check_slices("conv1ch_wgrad", {{a_ctotal, a_coff, 64}})) return st;
   CODON_REQUIRE(ws_bytes >= conv1ch_wgrad_c8_workspace_bytes(B, H, W), CODON_ERR_BAD_ARG, "conv1ch_wgrad: workspace too small");
   const long HW = (long)H * W;
   const int nrowblk = (H + W1C8_ROWS - 1) / W1C8_ROWS;
   const C8Slice as = c8_mk(a, a_ctotal, a_coff, HW);
-  if (dtype == CODON_F16)
-    hipLaunchKernelGGL(conv1ch_wgrad_c8_kernel<C8F16>, dim3(B * nrowblk), dim3(512 / W1C8_PLANES), 0, stream, as, s, ws, H,
+  const int st = c8_dispatch(dtype, [&](auto e) {
+    hipLaunchKernelGGL(conv1ch_wgrad_c8_kernel<decltype(e)>, dim3(B * nrowblk), dim3(512 / W1C8_PLANES), 0, stream, as, s, ws, H,
                        W, nrowblk);
-  else
-    hipLaunchKernelGGL(conv1ch_wgrad_c8_kernel<C8Bf16>, dim3(B * nrowblk), dim3(512 / W1C8_PLANES), 0, stream, as, s, ws, H,
-                       W, nrowblk);
-  const int st = check_launch("conv1ch_wgrad_c8_kernel");
+    return check_launch("conv1ch_wgrad_c8_kernel");
+  });
   if (st != CODON_OK) return st;
   return conv1ch_wgrad_reduce(ws, dw, B * nrowblk, flip, stream);
 }
@@ -495,25 +489,13 @@ int cac_stats_fwd_c8(int B, int H, int W, const codon_tensor* pc, const codon_te
   const long HW = (long)H * W;
   const int nt = cac_stats_tiles(H, W);
   CODON_REQUIRE(B <= 65535, CODON_ERR_UNSUPPORTED, "cac_stats_fwd: batch %d > 65535", B);
-  CODON_REQUIRE(c8_slice_ok(pc->ctotal, pc->coff, 64) && c8_slice_ok(pd->ctotal, pd->coff, 64), CODON_ERR_BAD_ARG,
-                "cac_stats_fwd: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
-  CODON_REQUIRE(HW * 2 * 64 < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "cac_stats_fwd: image too large for 32-bit buffer offsets");
-  if (nt != (int)((HW + EW_TILE - 1) / EW_TILE)) {          // small image: 256-pixel tiles (cac.hip)
-    if (dtype == CODON_F16)
-      hipLaunchKernelGGL((cac_stats_c8_kernel<C8F16, 1>), dim3(nt, B), dim3(256), 0, stream, c8_mk(pc, HW), c8_mk(pd, HW), pooled,
-                         partials, HW, nt, chs);
-    else
-      hipLaunchKernelGGL((cac_stats_c8_kernel<C8Bf16, 1>), dim3(nt, B), dim3(256), 0, stream, c8_mk(pc, HW), c8_mk(pd, HW), pooled,
-                         partials, HW, nt, chs);
-    return check_launch("cac_stats_c8_kernel<small>");
-  }
-  if (dtype == CODON_F16)
-    hipLaunchKernelGGL(cac_stats_c8_kernel<C8F16>, dim3(nt, B), dim3(256), 0, stream, c8_mk(pc, HW), c8_mk(pd, HW), pooled,
-                       partials, HW, nt, chs);
-  else
-    hipLaunchKernelGGL(cac_stats_c8_kernel<C8Bf16>, dim3(nt, B), dim3(256), 0, stream, c8_mk(pc, HW), c8_mk(pd, HW), pooled,
-                       partials, HW, nt, chs);
-  return check_launch("cac_stats_c8_kernel");
+  if (const int st = c8_check("cac_stats_fwd", H, W, 64, {c8_arg(pc, 64), c8_arg(pd, 64)})) return st;
+  const bool small = nt != (int)((HW + EW_TILE - 1) / EW_TILE);          // small image: 256-pixel tiles (cac.hip)
+  return c8_dispatch(dtype, [&](auto e) {
+    const auto kernel = small ? &cac_stats_c8_kernel<decltype(e), 1> : &cac_stats_c8_kernel<decltype(e), EW_NP>;
+    hipLaunchKernelGGL(kernel, dim3(nt, B), dim3(256), 0, stream, c8_mk(pc, HW), c8_mk(pd, HW), pooled, partials, HW, nt, chs);
+    return check_launch(small ? "cac_stats_c8_kernel<small>" : "cac_stats_c8_kernel");
+  });
 }
 
 // ---- gate apply: out = pre * (ch * sp) + inputs, both streams ---------------------------------------------------------
@@ -568,17 +550,15 @@ int cac_apply_fwd_c8(int B, int H, int W, const codon_tensor* pre, const codon_t
                      const codon_tensor* out_c, int dtype, hipStream_t stream) {
   const long HW = (long)H * W;
   CODON_REQUIRE(B <= 65535, CODON_ERR_UNSUPPORTED, "cac_apply_fwd: batch %d too large", B);
-  for (const codon_tensor* t : {pre, pre_c, in, in_c, out, out_c})
-    CODON_REQUIRE(c8_slice_ok(t->ctotal, t->coff, 64), CODON_ERR_BAD_ARG,
-                  "cac_apply_fwd: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
-  CODON_REQUIRE(HW * 2 * 64 < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "cac_apply_fwd: image too large for 32-bit buffer offsets");
+  if (const int st = c8_check("cac_apply_fwd", H, W, 64, {c8_arg(pre, 64), c8_arg(pre_c, 64), c8_arg(in, 64), c8_arg(in_c, 64),
+                                                          c8_arg(out, 64), c8_arg(out_c, 64)}))
+    return st;
   const ApplyC8 sd{c8_mk(pre, HW), c8_mk(in, HW), c8_mk(out, HW)}, sc{c8_mk(pre_c, HW), c8_mk(in_c, HW), c8_mk(out_c, HW)};
   const unsigned nt = (unsigned)((HW + 1023) / 1024);
-  if (dtype == CODON_F16)
-    hipLaunchKernelGGL(cac_apply_c8_kernel<C8F16>, dim3(nt, B), dim3(256), 0, stream, sd, sc, ch, sp, HW);
-  else
-    hipLaunchKernelGGL(cac_apply_c8_kernel<C8Bf16>, dim3(nt, B), dim3(256), 0, stream, sd, sc, ch, sp, HW);
-  return check_launch("cac_apply_c8_kernel");
+  return c8_dispatch(dtype, [&](auto e) {
+    hipLaunchKernelGGL(cac_apply_c8_kernel<decltype(e)>, dim3(nt, B), dim3(256), 0, stream, sd, sc, ch, sp, HW);
+    return check_launch("cac_apply_c8_kernel");
+  });
 }
 
 // ---- elementwise helpers ------------------------------------------------------------------------------------------------
@@ -604,14 +584,13 @@ int ew_sq_scale_c8(int B, int H, int W, const codon_tensor* x, const float* ch, 
                    hipStream_t stream) {
   const long HW = (long)H * W;
   CODON_REQUIRE(B <= 65535, CODON_ERR_UNSUPPORTED, "ew_sq_scale: batch %d too large", B);
-  CODON_REQUIRE(c8_slice_ok(x->ctotal, x->coff, 64) && c8_slice_ok(y->ctotal, y->coff, 64), CODON_ERR_BAD_ARG,
-                "ew_sq_scale: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
+  // (no descriptor-range refusal here today; adding one is a change of behaviour)
+  if (const int st = c8_check_slices("ew_sq_scale", {c8_arg(x, 64), c8_arg(y, 64)})) return st;
   const unsigned nt = (unsigned)((HW + 255) / 256);
-  if (dtype == CODON_F16)
-    hipLaunchKernelGGL(ew_sq_scale_c8_kernel<C8F16>, dim3(nt, B), dim3(256), 0, stream, c8_mk(x, HW), ch, c8_mk(y, HW), HW);
-  else
-    hipLaunchKernelGGL(ew_sq_scale_c8_kernel<C8Bf16>, dim3(nt, B), dim3(256), 0, stream, c8_mk(x, HW), ch, c8_mk(y, HW), HW);
-  return check_launch("ew_sq_scale_c8_kernel");
+  return c8_dispatch(dtype, [&](auto e) {
+    hipLaunchKernelGGL(ew_sq_scale_c8_kernel<decltype(e)>, dim3(nt, B), dim3(256), 0, stream, c8_mk(x, HW), ch, c8_mk(y, HW), HW);
+    return check_launch("ew_sq_scale_c8_kernel");
+  });
 }
 
 // dst = [dst +] src, then dst = mask > 0 ? dst : 0; grid = (pixel blocks, planes, B)
@@ -647,19 +626,14 @@ int ew_add_mask_c8(int B, int H, int W, int C, const codon_tensor* dst, const co
                    int accumulate, int dtype, hipStream_t stream) {
   const long HW = (long)H * W;
   CODON_REQUIRE(B <= 65535 && C % 8 == 0, CODON_ERR_UNSUPPORTED, "ew_add_mask: batch %d / channels %d", B, C);
-  CODON_REQUIRE(c8_slice_ok(dst->ctotal, dst->coff, C) && (!src || c8_slice_ok(src->ctotal, src->coff, C)) &&
-                    (!mask || c8_slice_ok(mask->ctotal, mask->coff, C)),
-                CODON_ERR_BAD_ARG, "ew_add_mask: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
-  CODON_REQUIRE(HW * 2 * C < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "ew_add_mask: image too large for 32-bit buffer offsets");
+  if (const int st = c8_check("ew_add_mask", H, W, C, {c8_arg(dst, C), c8_arg(src, C), c8_arg(mask, C)})) return st;
   const C8Slice d = c8_mk(dst, HW), s = src ? c8_mk(src, HW) : d, m = mask ? c8_mk(mask, HW) : d;
   const dim3 grid((unsigned)((HW + 255) / 256), C / 8, B);
-  if (dtype == CODON_F16)
-    hipLaunchKernelGGL(ew_add_mask_c8_kernel<C8F16>, grid, dim3(256), 0, stream, d, s, src ? 1 : 0, m, mask ? 1 : 0, C / 8, HW,
-                       accumulate);
-  else
-    hipLaunchKernelGGL(ew_add_mask_c8_kernel<C8Bf16>, grid, dim3(256), 0, stream, d, s, src ? 1 : 0, m, mask ? 1 : 0, C / 8, HW,
-                       accumulate);
-  return check_launch("ew_add_mask_c8_kernel");
+  return c8_dispatch(dtype, [&](auto e) {
+    hipLaunchKernelGGL(ew_add_mask_c8_kernel<decltype(e)>, grid, dim3(256), 0, stream, d, s, src ? 1 : 0, m, mask ? 1 : 0, C / 8,
+                       HW, accumulate);
+    return check_launch("ew_add_mask_c8_kernel");
+  });
 }
 
 // dst = mask > 0 ? s0 + s1 [+ s2 [+ s3]] : 0, summed in fp32 in that order, rounded once (round 4: dL/d(fuse) of the
@@ -704,9 +678,7 @@ int ew_sum_mask_c8(int B, int H, int W, int C, const codon_tensor* dst, int nsrc
   const long HW = (long)H * W;
   CODON_REQUIRE(B <= 65535 && C % 8 == 0 && nsrc >= 1 && nsrc <= 4, CODON_ERR_UNSUPPORTED,
                 "ew_sum_mask: batch %d / channels %d / %d sources (1..4)", B, C, nsrc);
-  CODON_REQUIRE(c8_slice_ok(dst->ctotal, dst->coff, C) && (!mask || c8_slice_ok(mask->ctotal, mask->coff, C)), CODON_ERR_BAD_ARG,
-                "ew_sum_mask: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
-  CODON_REQUIRE(HW * 2 * C < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "ew_sum_mask: image too large for 32-bit buffer offsets");
+  if (const int st = c8_check("ew_sum_mask", H, W, C, {c8_arg(dst, C), c8_arg(mask, C)})) return st;
   const C8Slice d = c8_mk(dst, HW), m = mask ? c8_mk(mask, HW) : d;
   EwSum4 s4;
   for (int i = 0; i < 4; ++i) {
@@ -715,11 +687,10 @@ int ew_sum_mask_c8(int B, int H, int W, int C, const codon_tensor* dst, int nsrc
     s4.s[i] = c8_mk(t, HW);
   }
   const dim3 grid((unsigned)((HW + 255) / 256), C / 8, B);
-  if (dtype == CODON_F16)
-    hipLaunchKernelGGL(ew_sum_mask_c8_kernel<C8F16>, grid, dim3(256), 0, stream, d, s4, nsrc, m, mask ? 1 : 0, C / 8, HW);
-  else
-    hipLaunchKernelGGL(ew_sum_mask_c8_kernel<C8Bf16>, grid, dim3(256), 0, stream, d, s4, nsrc, m, mask ? 1 : 0, C / 8, HW);
-  return check_launch("ew_sum_mask_c8_kernel");
+  return c8_dispatch(dtype, [&](auto e) {
+    hipLaunchKernelGGL(ew_sum_mask_c8_kernel<decltype(e)>, grid, dim3(256), 0, stream, d, s4, nsrc, m, mask ? 1 : 0, C / 8, HW);
+    return check_launch("ew_sum_mask_c8_kernel");
+  });
 }
 
 // ---- CAC backward, the two passes over the 64-channel tensors (math: cac_bwd.hip) --------------------------------------
@@ -935,31 +906,23 @@ int cac_bwd_reduce_c8(int B, int H, int W, const codon_tensor* g_out, const codo
                       const codon_tensor* g_in, const codon_tensor* g_in_c, int accumulate_in) {
   const long HW = (long)H * W;
   const int nt = (int)((HW + EW_TILE - 1) / EW_TILE);
-  for (const codon_tensor* t : {g_out, g_outc, pre, pre_c})
-    CODON_REQUIRE(c8_slice_ok(t->ctotal, t->coff, 64), CODON_ERR_BAD_ARG,
-                  "cac_bwd_reduce: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
-  CODON_REQUIRE(HW * 2 * 64 < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "cac_bwd_reduce: image too large for 32-bit buffer offsets");
+  if (const int st = c8_check("cac_bwd_reduce", H, W, 64, {c8_arg(g_out, 64), c8_arg(g_outc, 64), c8_arg(pre, 64), c8_arg(pre_c, 64)}))
+    return st;
   if (argch != nullptr) {
-    CODON_REQUIRE(pooled && g_in && g_in_c && c8_slice_ok(g_in->ctotal, g_in->coff, 64) &&
-                      c8_slice_ok(g_in_c->ctotal, g_in_c->coff, 64),
-                  CODON_ERR_BAD_ARG, "cac_bwd_reduce_acc: pooled / g_in / g_in_c");
-    if (dtype == CODON_F16)
-      hipLaunchKernelGGL(cac_bwd_reduce_acc_c8_kernel<C8F16>, dim3(nt, B), dim3(256), 0, stream, c8_mk(g_out, HW),
+    CODON_REQUIRE(pooled && g_in && g_in_c, CODON_ERR_BAD_ARG, "cac_bwd_reduce_acc: pooled / g_in / g_in_c");
+    if (const int st = c8_check_slices("cac_bwd_reduce_acc", {c8_arg(g_in, 64), c8_arg(g_in_c, 64)})) return st;
+    return c8_dispatch(dtype, [&](auto e) {
+      hipLaunchKernelGGL(cac_bwd_reduce_acc_c8_kernel<decltype(e)>, dim3(nt, B), dim3(256), 0, stream, c8_mk(g_out, HW),
                          c8_mk(g_outc, HW), c8_mk(pre, HW), c8_mk(pre_c, HW), c8_mk(g_in, HW), c8_mk(g_in_c, HW), ch, sp, pools,
                          pooled, g_z, part_gch, part_arg, argch, HW, nt, accumulate_in);
-    else
-      hipLaunchKernelGGL(cac_bwd_reduce_acc_c8_kernel<C8Bf16>, dim3(nt, B), dim3(256), 0, stream, c8_mk(g_out, HW),
-                         c8_mk(g_outc, HW), c8_mk(pre, HW), c8_mk(pre_c, HW), c8_mk(g_in, HW), c8_mk(g_in_c, HW), ch, sp, pools,
-                         pooled, g_z, part_gch, part_arg, argch, HW, nt, accumulate_in);
-    return check_launch("cac_bwd_reduce_acc_c8_kernel");
+      return check_launch("cac_bwd_reduce_acc_c8_kernel");
+    });
   }
-  if (dtype == CODON_F16)
-    hipLaunchKernelGGL(cac_bwd_reduce_c8_kernel<C8F16>, dim3(nt, B), dim3(256), 0, stream, c8_mk(g_out, HW), c8_mk(g_outc, HW),
-                       c8_mk(pre, HW), c8_mk(pre_c, HW), ch, sp, pools, g_z, part_gch, part_arg, HW, nt);
-  else
-    hipLaunchKernelGGL(cac_bwd_reduce_c8_kernel<C8Bf16>, dim3(nt, B), dim3(256), 0, stream, c8_mk(g_out, HW), c8_mk(g_outc, HW),
-                       c8_mk(pre, HW), c8_mk(pre_c, HW), ch, sp, pools, g_z, part_gch, part_arg, HW, nt);
-  return check_launch("cac_bwd_reduce_c8_kernel");
+  return c8_dispatch(dtype, [&](auto e) {
+    hipLaunchKernelGGL(cac_bwd_reduce_c8_kernel<decltype(e)>, dim3(nt, B), dim3(256), 0, stream, c8_mk(g_out, HW),
+                       c8_mk(g_outc, HW), c8_mk(pre, HW), c8_mk(pre_c, HW), ch, sp, pools, g_z, part_gch, part_arg, HW, nt);
+    return check_launch("cac_bwd_reduce_c8_kernel");
+  });
 }
 
 // D: g_pre / g_pre_c (direct term + avg-pool broadcast + max-pool routing + channel-mean broadcast + channel-max
@@ -1052,21 +1015,18 @@ int cac_bwd_apply_c8(int B, int H, int W, const codon_tensor* g_out, const codon
                      const float* g_pools, const int* argpix, const codon_tensor* g_pre, const codon_tensor* g_pre_c,
                      const codon_tensor* g_in, const codon_tensor* g_in_c, int accumulate_in, int dtype, hipStream_t stream) {
   const long HW = (long)H * W;
-  for (const codon_tensor* t : {g_out, g_outc, pre, pre_c, g_pre, g_pre_c, g_in, g_in_c})
-    CODON_REQUIRE(c8_slice_ok(t->ctotal, t->coff, 64), CODON_ERR_BAD_ARG,
-                  "cac_bwd_apply: 16-bit tensors are channel-blocked: ctotal / coff multiples of 8");
-  CODON_REQUIRE(HW * 2 * 64 < (long)C8_OOB, CODON_ERR_UNSUPPORTED, "cac_bwd_apply: image too large for 32-bit buffer offsets");
+  if (const int st = c8_check("cac_bwd_apply", H, W, 64, {c8_arg(g_out, 64), c8_arg(g_outc, 64), c8_arg(pre, 64), c8_arg(pre_c, 64),
+                                                          c8_arg(g_pre, 64), c8_arg(g_pre_c, 64), c8_arg(g_in, 64), c8_arg(g_in_c, 64)}))
+    return st;
   const float inv = (float)(1.0 / (double)HW);
   const BwdApplyC8 sd{c8_mk(g_out, HW), c8_mk(pre, HW), c8_mk(g_pre, HW), c8_mk(g_in, HW)};
   const BwdApplyC8 sc{c8_mk(g_outc, HW), c8_mk(pre_c, HW), c8_mk(g_pre_c, HW), c8_mk(g_in_c, HW)};
   const dim3 grid((unsigned)((HW + 511) / 512), B);
-  if (dtype == CODON_F16)
-    hipLaunchKernelGGL(cac_bwd_apply_c8_kernel<C8F16>, grid, dim3(256), 0, stream, sd, sc, ch, sp, pooled, g_pooled, g_pools,
+  return c8_dispatch(dtype, [&](auto e) {
+    hipLaunchKernelGGL(cac_bwd_apply_c8_kernel<decltype(e)>, grid, dim3(256), 0, stream, sd, sc, ch, sp, pooled, g_pooled, g_pools,
                        argpix, accumulate_in, HW, inv);
-  else
-    hipLaunchKernelGGL(cac_bwd_apply_c8_kernel<C8Bf16>, grid, dim3(256), 0, stream, sd, sc, ch, sp, pooled, g_pooled, g_pools,
-                       argpix, accumulate_in, HW, inv);
-  return check_launch("cac_bwd_apply_c8_kernel");
+    return check_launch("cac_bwd_apply_c8_kernel");
+  });
 }
 
 }  // namespace codon

@@ -98,10 +98,9 @@ int cast_multi(const codon_cast_desc* d, float* dst, hipStream_t stream);
 
 // conv_c8.hip
 int pack_chain1x1_16(const float* w, void* out, int dtype, hipStream_t stream);
-int pack_weight_bf16(const float* w, void* out, int cout, int cin, int ks, int mode, int dtype, hipStream_t stream);
+int pack_weight_16(const float* w, void* out, int cout, int cin, int ks, int mode, int dtype, hipStream_t stream);
 int conv_form_c8(const codon_conv_desc* d);
-int conv2d_fwd_bf16(const codon_conv_desc* d, const void* x, const void* w, void* y, const void* res,
-                    hipStream_t stream);
+int conv2d_fwd_16(const codon_conv_desc* d, const void* x, const void* w, void* y, const void* res, hipStream_t stream);
 int conv2d_sum_into_16(const codon_conv_desc* d, const void* x, const void* w, void* y, void* sum, hipStream_t stream);
 int conv_chain1x1_fwd_16(const codon_conv_desc* d, const void* x, const void* w, void* y, const void* w_chain,
                          const codon_tensor* out, const codon_tensor* res, float* st_pool, float* st_part, int st_choff,
@@ -133,9 +132,9 @@ int conv2d_fwd_f32x3(const codon_conv_desc* d, const float* x, const void* w, fl
 int pack_weight_f32x3(const float* w, void* out, int cout, int cin, int ks, hipStream_t stream);
 
 // conv_wgrad_c8.hip
-size_t conv_wgrad_bf16_workspace_bytes(const codon_conv_desc* d);
-int conv2d_wgrad_bf16(const codon_conv_desc* d, const void* x, const void* gy, float* dw, float* workspace,
-                      size_t ws_bytes, int accumulate, hipStream_t stream);
+size_t conv_wgrad_16_workspace_bytes(const codon_conv_desc* d);
+int conv2d_wgrad_16(const codon_conv_desc* d, const void* x, const void* gy, float* dw, float* workspace,
+                    size_t ws_bytes, int accumulate, hipStream_t stream);
 int conv1x1_bwd_16(const codon_conv_desc* d, const void* x, const void* gy, const void* w_dgrad, const codon_tensor* gx,
                    float* dw, float* workspace, size_t ws_bytes, int accumulate, hipStream_t stream,
                    const Conv1x1GateBwd* gb);

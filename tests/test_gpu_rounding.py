@@ -34,7 +34,7 @@ pytestmark = pytest.mark.gpu
 from codon_amd import _lib as L
 from tests.bounds import assert_rounded, conv_ref, tau_of
 
-# every (k, cin, cout) conv2d_fwd_c8 dispatches; the set is closed under cin <-> cout, so each also runs as a dgrad launch
+# every (k, cin, cout) c8_visit_shape (csrc/conv_c8.hip) lists; the set is closed under cin <-> cout, so each also runs as a dgrad launch
 FORMS = [(5, 128, 128), (5, 64, 64), (3, 64, 64), (3, 128, 64), (3, 64, 128), (1, 128, 64), (1, 64, 128)]
 # around the c8 tile (32 px wide, 8 rows; 16 rows for 5x5 64->64): one pixel, one row and one column past a tile on both
 # axes with two images, exact tiles, and a ragged shape of three images
