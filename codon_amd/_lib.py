@@ -23,6 +23,7 @@ PACK_FWD, PACK_DGRAD, PACK_FWD_F16X3, PACK_CHAIN1X1, PACK_CHAIN1X1_F16X3 = 0, 1,
 TILING_8X32, TILING_4X32, TILING_4X32_SOLO, TILING_2X32_COUT_SPLIT = 0, 1, 2, 3      # codon_conv_tiling_f32
 C8_FORM_STAGED, C8_FORM_RESIDENT = 0, 1                                             # codon_conv_form_c8
 CAC_FOLDS = 16   # CODON_CAC_FOLDS
+FILL_U8, FILL_U16, FILL_F32 = 0, 1, 2                                               # CODON_FILL_*
 
 
 class ConvDesc(C.Structure):
@@ -186,6 +187,8 @@ SIGNATURES = {
     "codon_d4_views": (C.c_int, [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     "codon_d4_merge": (C.c_int, [_I, _I, _I, _P, _P, _I, _P, _P]),
     "codon_depth_errors": (C.c_int, [C.POINTER(DepthErrorsDesc), _P, _P, _P, _P, _P, _P]),
+    "codon_fill_holes_workspace_bytes": (_S, [_I, _I]),
+    "codon_fill_holes": (C.c_int, [_I, _I, _I, _P, _I, _P, _I, _P, _P, _S, _P]),
     "codon_weight_checksum_workspace_bytes": (_S, []),
     "codon_weight_checksum": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P]),
     "codon_weight_checksum_clear": (C.c_int, [C.POINTER(WsumDesc), _P, _P, _I, _P, _P, _I, _P]),

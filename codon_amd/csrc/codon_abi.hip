@@ -7,6 +7,7 @@
 
 #include "codon_common.h"
 #include "eval_tile.h"
+#include "fill_tile.h"
 #include "kernels.h"
 #include "pair.h"
 #include "sensor_pixel.h"
@@ -996,6 +997,29 @@ int codon_depth_errors(const codon_depth_errors_desc* desc, const void* label, c
   a.r = a.edge ? desc->edge_radius : 0;
   return depth_errors(a, desc->batch, desc->bits, label, out, error_map, region_map, (unsigned long long*)acc,
                       (hipStream_t)stream);
+}
+
+// ---- pull-push hole filling -----------------------------------------------------------------------------------
+size_t codon_fill_holes_workspace_bytes(int32_t height, int32_t width) { return fill_holes_workspace_bytes(height, width); }
+
+int codon_fill_holes(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, const float* tab, int32_t top,
+                     void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
+  CODON_REQUIRE(in && out && workspace, CODON_ERR_BAD_ARG, "fill_holes: null pointer");
+  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16 || fmt == FL_F32, CODON_ERR_BAD_ARG,
+                "fill_holes: fmt %d (0: u8 codes, 1: u16 codes, 2: fp32 on the code grid)", fmt);
+  CODON_REQUIRE(fmt != FL_F32 || tab, CODON_ERR_BAD_ARG, "fill_holes: null pointer (the fp32 format needs tab)");
+  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "fill_holes: batch %d (1..65535)", batch);
+  CODON_REQUIRE(height >= 1 && height <= FL_MAX_SIDE && width >= 1 && width <= FL_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "fill_holes: a %dx%d plane (1..%d each way)", height, width, FL_MAX_SIDE);
+  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
+                "fill_holes: top %d (255 for u8 codes, 1..65535 otherwise)", top);
+  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "fill_holes: in and out are the same buffer");
+  CODON_REQUIRE((((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0 && ((uintptr_t)workspace & 1) == 0,
+                CODON_ERR_BAD_ARG, "fill_holes: unaligned plane or workspace");
+  const size_t need = (size_t)batch * fill_holes_workspace_bytes(height, width);
+  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "fill_holes: a workspace of %zu bytes is too small (%zu needed)",
+                workspace_bytes, need);
+  return fill_holes(batch, height, width, in, fmt, tab, top, out, workspace, (hipStream_t)stream);
 }
 
 size_t codon_weight_checksum_workspace_bytes(void) { return weight_checksum_workspace_bytes(); }

@@ -162,6 +162,11 @@ int d4_merge(int B, int H, int W, const void* upright, const void* transposed, i
 int depth_errors(const EvalArgs& a, int B, int bits, const void* label, const void* out, void* err, unsigned char* region,
                  unsigned long long* acc, hipStream_t stream);
 
+// fill_holes.hip
+size_t fill_holes_workspace_bytes(int h, int w);
+int fill_holes(int B, int h, int w, const void* in, int fmt, const float* tab, int top, void* out, void* workspace,
+               hipStream_t stream);
+
 // ew_c8.hip: the stencils, CAC passes and elementwise helpers of stencil.hip, cac.hip and cac_bwd.hip over channel-blocked 16-bit tensors
 int stem_pair_fwd_c8(int B, int H, int W, const float* xa, const float* wa, void* ya, int ya_ctotal, int ya_coff,
                      const float* xb, const float* wb, void* yb, int yb_ctotal, int yb_coff, int dtype, int* bad, int* host_a,

@@ -30,6 +30,7 @@ import torch
 from . import CODONNet, CODONNet16, io, metrics
 from .io import check_depth_max, list_pairs, read_depth_plane
 from .upsample import _on_device, code_table, phase_weights
+from .upsample import fill_holes as _fill_holes
 
 
 def _load_host(a_depth, a_color, a_label, f, tdt, depth_bits=8, depth_max=65535):
@@ -147,7 +148,7 @@ def _pinned_copy(t: torch.Tensor) -> torch.Tensor:
 
 
 def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None,
-             depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None, self_ensemble=False, report=None):
+             depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None, self_ensemble=False, report=None, fill_holes=False):
     """The test loop over every image pair.  Returns {"n", "rmse_mean", "ssim_mean", "seconds", "images_per_s"}.
     depth_bits=16: 16-bit depth and label files with codes 0 .. depth_max, outputs through metrics.postprocess_u16 into 16-bit
     PNGs, RMSE (metrics.masked_rmse_u16) in codes times depth_unit, SSIM of label / depth_max against out / depth_max.
@@ -158,9 +159,13 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     report (needs label): {"thresholds": up to four codes, "edge_threshold": codes or None, "edge_radius": r,
     "error_maps": a directory or None} -- one more launch per image (metrics.depth_errors); every line gains the key=value
     tokens of metrics.depth_report (mad, rmse and max in codes times depth_unit), the error maps are written under the images'
-    names, and the result gains "reports" (the per-image dicts, with "file") and "report_means" (metrics.report_means)."""
+    names, and the result gains "reports" (the per-image dicts, with "file") and "report_means" (metrics.report_means).
+    fill_holes (needs lr_depth): the main stream fills the holes of the uploaded codes by pull-push
+    (upsample.fill_holes) ahead of codes_to_input, in both loops -- the network sees a dense input."""
     if (lr_depth is None) == (input_depth is None):
         raise ValueError("run_loop: exactly one of input_depth and lr_depth")
+    if fill_holes and lr_depth is None:
+        raise ValueError("run_loop: fill_holes needs lr_depth (only low-resolution code planes are filled)")
     if lr_depth is not None and scale not in (4, 8, 16):
         raise ValueError(f"run_loop: lr_depth needs scale 4, 8 or 16 (got {scale!r})")
     files = list_pairs(lr_depth or input_depth, input_color) if files is None else files
@@ -178,7 +183,11 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     scale_rm = float(depth_unit) if deep else None
     if lr_depth is not None:
         load = lambda f: _load_host_lr(lr_depth, input_color, label, f, tdt, scale, depth_bits, depth_max)      # noqa: E731
-        to_x = lambda c: codes_to_input(c, scale, tdt, depth_max if deep else None)                            # noqa: E731
+        if fill_holes:
+            to_x = lambda c: codes_to_input(_fill_holes(c, depth_max if deep else None), scale, tdt,           # noqa: E731
+                                            depth_max if deep else None)
+        else:
+            to_x = lambda c: codes_to_input(c, scale, tdt, depth_max if deep else None)                        # noqa: E731
     else:
         load = lambda f: _load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max)             # noqa: E731
         to_x = lambda x: x                                                                                     # noqa: E731
@@ -412,6 +421,10 @@ def main(argv=None):
                     help="LOW-RESOLUTION depth maps as a sensor writes them, code 0 a hole: upsampled by --scale on the device "
                          "with the training degradation's own hole-aware bicubic; guidance and label are cropped to "
                          "(h * scale, w * scale)")
+    ap.add_argument("--fill-holes", action="store_true",
+                    help="with --lr-depth: fill the holes of every low-resolution map on the device by pull-push (the mean of "
+                         "the valid pixels up a pyramid, a 9/3/3/1 mix back down; integers, bit-exact) before it is upsampled, "
+                         "so that the network sees a dense input; valid pixels are untouched")
     ap.add_argument("--input-color", required=True)
     ap.add_argument("--label", default=None)
     ap.add_argument("--out", default=None)
@@ -449,6 +462,8 @@ def main(argv=None):
     report = {**report_of(ap, a), "error_maps": a.error_maps} if a.report else None
     if (a.input_depth is None) == (a.lr_depth is None):
         ap.error("exactly one of --input-depth and --lr-depth is required")
+    if a.fill_holes and a.lr_depth is None:
+        ap.error("--fill-holes needs --lr-depth")
     if a.ema and not a.weights:
         ap.error("--ema needs --weights")
     if a.depth_bits != 16 and (a.depth_max is not None or a.depth_unit != 1.0):
@@ -473,7 +488,8 @@ def main(argv=None):
     r = run_loop(model, dev, tdt, a.input_depth, a.input_color, a.label, a.out, pipelined=not a.serial,
                  depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit,
                  **({"self_ensemble": True} if a.self_ensemble else {}), **({"report": report} if report else {}),
-                 **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}))
+                 **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}),
+                 **({"fill_holes": True} if a.fill_holes else {}))
     print(r["n"])
     if a.label and r["n"]:
         print(r["rmse_mean"], r["ssim_mean"])

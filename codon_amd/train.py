@@ -8,6 +8,8 @@ The degradation is a definition of this project, NOT pinned to the reference (it
 numpy in tests/train_data_ref.py and the two agree bit for bit.  --depth-bits 16: depth maps and labels are
 16-bit PNGs of codes 0 .. --depth-max (0 a hole, value = code / depth-max, guidance stays 8-bit); the crop reads u16 planes
 through a 65 536-entry table and the last step quantises onto the data set's own code grid (tests/train_data16_ref.py).
+--fill-holes: the holes of the low-resolution maps -- real ones, or the synthetic ones of --degrade-holes -- are
+filled on the device by pull-push before they are upsampled, exactly as `codon_amd.infer --lr-depth --fill-holes` fills them.
 --train-lr-depth DIR: REAL pairs -- a sensor's low-resolution map per pair, paired by file name; nothing is
 degraded, one launch (codon_train_crops_lr) builds x, y and t, and x is the crop of what `codon_amd.infer --lr-depth` builds from
 the whole low-resolution file, bit for bit (tests/train_lr_ref.py).
@@ -42,8 +44,9 @@ from . import ops
 from .infer import add_report_args, report_of, run_loop
 from .io import check_depth_max, list_pairs, read_depth_plane
 from .metrics import report_tokens
-from .upsample import (_on_device, code_table, down_weights, gauss_table, lut16,      # noqa: F401 (lut16: for importers)
-                       phase_weights, u8_lut)
+from .upsample import (_fill_launch, _on_device, code_table, down_weights, gauss_table, lut16,      # noqa: F401 (lut16: for
+                       phase_weights, u8_lut)                                                      # importers)
+from .upsample import fill_holes as _fill_holes
 
 DTYPES = {"bf16": torch.bfloat16, "f32": None}
 RESUME_KEYS = ("scale", "crop", "batch", "dtype", "clip_norm", "skip_nonfinite", "ema", "lr_schedule", "warmup_steps", "lr_min",
@@ -62,6 +65,8 @@ LR_DEFAULTS = {"train_lr_depth": False}
 # compares as "no model"
 SENSOR_DEFAULTS = {"sensor_noise": None, "sensor_noise_quad": None, "sensor_dropout": None, "sensor_edge_dropout": None,
                    "sensor_edge_threshold": None, "sensor_seed": None}
+# the same for --fill-holes: a resume key with default False, written by a run that sets it ONLY
+FILL_DEFAULTS = {"fill_holes": False}
 MAX_REDRAWS = 64                                    # draw(min_valid=): per sample, before it gives up
 LR_SCHEDULES = ("constant", "cosine")
 
@@ -94,15 +99,21 @@ class TrainSet:
     sensor writes it (0 a hole), read through read_depth_plane under the set's bit depth.  Its (h, w) fixes the HR size
     (h * scale, w * scale), to which depth map and guidance are cropped top-left (a smaller one is refused by name: the rule
     of `infer --lr-depth`); `sizes` holds the HR sizes.  The depth map is the target and nothing is degraded, so lr_dir
-    excludes label_dir.  has_lr, lr_scale say so (False, None otherwise)."""
+    excludes label_dir.  has_lr, lr_scale say so (False, None otherwise).
+    `fill_holes` (needs lr_dir): once the pool is on the device, the low-resolution plane of every record is
+    filled by pull-push from the WHOLE file (upsample.fill_holes, one call per record), so that a step costs nothing extra and x
+    stays the crop of what `infer --lr-depth --fill-holes` builds from that file; the target plane is untouched."""
 
     def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None, label_dir: str = None, depth_bits: int = 8,
-                 depth_max: int = 65535, lr_dir: str = None, scale: int = None):
+                 depth_max: int = 65535, lr_dir: str = None, scale: int = None, fill_holes: bool = False):
         if depth_bits not in (8, 16):
             raise ValueError(f"TrainSet: depth_bits {depth_bits!r} (8 or 16)")
         check_depth_max(depth_max)
         self.depth_bits, self.depth_max = depth_bits, int(depth_max)
         self.has_lr, self.lr_scale = lr_dir is not None, None
+        if fill_holes and lr_dir is None:
+            raise ValueError("TrainSet: fill_holes needs lr_dir (only low-resolution code planes are filled)")
+        self.fill_holes = bool(fill_holes)
         if self.has_lr:
             if scale not in (4, 8, 16):
                 raise ValueError(f"TrainSet: lr_dir needs scale 4, 8 or 16 (got {scale!r})")
@@ -153,6 +164,14 @@ class TrainSet:
         self.sizes = np.asarray(sizes, dtype=np.int64)
         self.pool = torch.from_numpy(np.concatenate(chunks)).to(device)
         self._integrals = None
+        if self.fill_holes:
+            wide = depth_bits // 8
+            for off, (h, w) in zip(self.offsets.tolist(), self.sizes.tolist()):
+                lo = off + record_layout(depth_bits, False, self.lr_scale, h, w)["lr"]
+                lh, lw = h // self.lr_scale, w // self.lr_scale
+                plane = self.pool[lo:lo + wide * lh * lw]
+                plane = (plane.view(torch.int16) if deep else plane).view(lh, lw)
+                plane.copy_(_fill_holes(plane, self.depth_max if deep else None))
 
     def __len__(self):
         return len(self.files)
@@ -272,7 +291,8 @@ def check_sensor(who: str, trainset: TrainSet, sensor: SensorModel, degrade_hole
 
 
 def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, degrade_holes: bool = False,
-               return_lr: bool = False, sensor: SensorModel = None, step: int = 0, first_sample: int = 0):
+               return_lr: bool = False, sensor: SensorModel = None, step: int = 0, first_sample: int = 0,
+               fill_holes: bool = False):
     """(x, y, t), each (B,1,crop,crop) fp32 on the pool's device: the network's depth input (crop -> bicubic down by `scale`
     -> bicubic up -> 8-bit), the guidance and the HR target.  Four launches on the caller's stream, no host synchronisation.
     A TrainSet with labels: x is degraded from the depth plane, t comes from the label plane (codon_train_crops_labeled).
@@ -292,7 +312,15 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
     (y * p + x, first_sample + b, step, 0) under the model's seed: `step` is the training step and `first_sample` the index of
     descs[0] in the GLOBAL batch (this rank's shard start).  The up launch reads the new map and return_lr returns it; on the
     masked path the map stays on the code grid and x stays what infer.codes_to_input builds from its codes.  Dropout needs
-    degrade_holes, and a TrainSet with low-resolution maps refuses a model."""
+    degrade_holes, and a TrainSet with low-resolution maps refuses a model.
+    fill_holes: with degrade_holes ONE more launch, codon_fill_holes in its fp32-on-the-grid format, between the
+    sensor launch (or the down launch) and the masked up launch: the low-resolution map's holes are filled by pull-push, the up
+    and the quantise launch stay as they are, return_lr returns the filled map, and x is what infer.codes_to_input builds from
+    upsample.fill_holes of that map's codes.  With a TrainSet of low-resolution maps built with fill_holes it changes nothing
+    (the pool is already filled).  Anything else is refused: the unmasked degradation has no holes."""
+    if fill_holes and not (degrade_holes or (trainset.has_lr and trainset.fill_holes)):
+        raise ValueError("synthesize: fill_holes needs degrade_holes, or a TrainSet of low-resolution maps built with fill_holes "
+                         "(the unmasked degradation has no holes to fill)")
     if sensor is not None:
         check_sensor("synthesize", trainset, sensor, degrade_holes)
         if not 0 <= step < 1 << 32 or not 0 <= first_sample <= (1 << 32) - len(descs):
@@ -367,6 +395,10 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
             gauss = _on_device("gauss", gauss_table, dev)
             L.check(lib.codon_lr_sensor(C.byref(sd), P_(lr.data_ptr()), P_(gauss.data_ptr()), P_(tab.data_ptr()), top,
                                         P_(noisy.data_ptr()), st), "lr_sensor")
+        if fill_holes:                                  # degrade_holes: refused otherwise
+            filled = torch.empty_like(noisy)
+            _fill_launch(dev, B, p, p, noisy.data_ptr(), L.FILL_F32, tab, top, filled.data_ptr())
+            noisy = filled
         if degrade_holes:
             L.check(lib.codon_bicubic_upsample_masked(B, p, p, scale, P_(noisy.data_ptr()), P_(wup.data_ptr()),
                                                       P_(x.data_ptr()), None, st), "bicubic_upsample_masked")
@@ -424,12 +456,13 @@ def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, 
 def load_resume(path: str, args: dict) -> dict:
     """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype, or with
     other options that change the trajectory (RESUME_KEYS, DEPTH_DEFAULTS', DEGRADE_DEFAULTS', LR_DEFAULTS' and
-    SENSOR_DEFAULTS' keys; a key the checkpoint's args lack compares as its default)."""
+    SENSOR_DEFAULTS' and FILL_DEFAULTS' keys; a key the checkpoint's args lack compares as its default)."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(ck, dict) or not all(k in ck for k in ("epoch", "model", "optimizer", "rng", "args")):
         raise ValueError(f"--resume {path}: not a codon_amd.train checkpoint (use --weights to start from other weights)")
-    absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS, **LR_DEFAULTS, **SENSOR_DEFAULTS}
-    keys = RESUME_KEYS + tuple(DEPTH_DEFAULTS) + tuple(DEGRADE_DEFAULTS) + tuple(LR_DEFAULTS) + tuple(SENSOR_DEFAULTS)
+    absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS, **LR_DEFAULTS, **SENSOR_DEFAULTS, **FILL_DEFAULTS}
+    keys = (RESUME_KEYS + tuple(DEPTH_DEFAULTS) + tuple(DEGRADE_DEFAULTS) + tuple(LR_DEFAULTS) + tuple(SENSOR_DEFAULTS) +
+            tuple(FILL_DEFAULTS))
     was, now = ({k: a.get(k, absent.get(k)) for k in keys} for a in (ck["args"], args))
     bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in keys if was[k] != now[k]]
     if bad:
@@ -443,7 +476,7 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         args: dict = None, time_synth: bool = False, emit=print, clip_norm: float = None, skip_nonfinite: bool = False,
         ema_decay: float = None, lr_schedule: str = "constant", warmup: int = 0, lr_min: float = 0.0, lr_steps: int = None,
         grad_hook=None, mask_holes: bool = False, min_valid: float = 0.0, degrade_holes: bool = False,
-        sensor: SensorModel = None) -> dict:
+        sensor: SensorModel = None, fill_holes: bool = False) -> dict:
     """Train `model` (fp32 parameters on the pool's device) from step start_step + 1 to step `steps`.
     val:   {"depth", "color", "label", "every"} -- rank 0 runs infer.run_loop every `every` steps and prints the means;
     ckpt:  {"path", "every"} -- rank 0 saves every `every` steps and after the last one;
@@ -464,6 +497,9 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     sensor: synthesize's sensor model, given the step number and this rank's shard start -- also under `fixed`
            descriptors, so N ranks see the global batch one process sees and a resumed run the maps the straight run saw; the
            checkpoint's args gain the model's fields (SENSOR_DEFAULTS' keys).
+    fill_holes: synthesize's hole filling; needs degrade_holes, or a TrainSet of low-resolution maps built with
+           fill_holes (one built without refuses it, and one built with it refuses a fit without); the checkpoint's args gain
+           fill_holes=True.  A `val` dict with "lr_depth" and "fill_holes" validates on filled maps.
     Returns {"losses": [(step, loss)], "gs", "opt", "rng", "step", ...}."""
     from .dist import FlatAdam, GradSync
     from .metrics import L1SSIMLoss, MaskedL1SSIMLoss
@@ -474,11 +510,14 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         raise ValueError(f"fit: a batch of {batch} does not split evenly over {world} ranks")
     if not 0.0 <= min_valid <= 1.0 or (min_valid > 0 and not mask_holes):
         raise ValueError(f"fit: min_valid {min_valid} must lie in [0, 1] and needs mask_holes")
-    synth_kw = {}
+    if bool(fill_holes) != trainset.fill_holes if trainset.has_lr else (fill_holes and not degrade_holes):
+        raise ValueError("fit: fill_holes needs degrade_holes, or a TrainSet of low-resolution maps -- and that TrainSet must "
+                         "have been built with the same fill_holes (its pool is filled once, when it is built)")
+    synth_kw = {"fill_holes": True} if fill_holes else {}      # without it synthesize is called as ever
     if sensor is not None:                          # refused before the first step; without a model synthesize is called as ever
         from .dist import shard_batch
         check_sensor("fit", trainset, sensor, degrade_holes)
-        synth_kw = {"sensor": sensor, "first_sample": shard_batch(batch, rank, world)[0]}
+        synth_kw.update(sensor=sensor, first_sample=shard_batch(batch, rank, world)[0])
     rng = np.random.default_rng(seed) if rng is None else rng
     dev = trainset.pool.device
     model.set_compute_dtype(DTYPES[dtype])
@@ -505,6 +544,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         args.update(train_lr_depth=True)
     if sensor is not None:                          # only then, likewise
         args.update(sensor.args())
+    if fill_holes:                                  # only then, likewise
+        args.update(fill_holes=True)
     if trainset.depth_bits == 16:                   # only then: an 8-bit checkpoint keeps the keys it always had
         args.update(depth_bits=16, depth_max=int(trainset.depth_max))
     stream = torch.cuda.current_stream(dev)
@@ -591,6 +632,8 @@ def validate(model, dev, val: dict, emit=print) -> dict:
             deep = {"depth_bits": 16, "depth_max": val.get("depth_max", 65535)} if val.get("depth_bits", 8) == 16 else {}
             if val.get("lr_depth"):                 # low-resolution validation maps, upsampled as infer --lr-depth does
                 deep.update(lr_depth=val["lr_depth"], scale=val["scale"])
+                if val.get("fill_holes"):           # filled as infer --lr-depth --fill-holes fills them
+                    deep.update(fill_holes=True)
             if val.get("report") is not None:       # the evaluation suite of infer --report
                 deep.update(report=val["report"])
             r = run_loop(model, dev, torch.float32, val.get("depth"), val["color"], val.get("label"), emit=lambda s: None, **deep)
@@ -639,6 +682,10 @@ def parse_args(argv=None):
     ap.add_argument("--degrade-holes", action="store_true",
                     help="holes (code 0) of the depth maps are left out of the degradation's two bicubics instead of being "
                          "smeared through them; the low-resolution map keeps them as holes, as a sensor's file does")
+    ap.add_argument("--fill-holes", action="store_true",
+                    help="fill the holes of the low-resolution maps on the device by pull-push before they are upsampled, as "
+                         "`codon_amd.infer --lr-depth --fill-holes` does: the maps of --train-lr-depth (once, when they are "
+                         "loaded) or the synthetic ones of --degrade-holes (every step), and those of --val-lr-depth")
     ap.add_argument("--sensor-noise", type=float, default=None, metavar="CODES",
                     help="sensor model: Gaussian noise of this standard deviation, in codes of the data's grid (255, or "
                          "--depth-max), on the synthetic low-resolution map; every --sensor option draws from --seed")
@@ -697,6 +744,8 @@ def parse_args(argv=None):
         ap.error("--train-lr-depth and --train-label exclude each other (with low-resolution maps --train-depth is the target)")
     if a.train_lr_depth is not None and a.degrade_holes:
         ap.error("--train-lr-depth and --degrade-holes exclude each other (nothing is degraded)")
+    if a.fill_holes and a.train_lr_depth is None and not a.degrade_holes:
+        ap.error("--fill-holes needs --train-lr-depth or --degrade-holes (the unmasked degradation has no holes to fill)")
     given = {n: getattr(a, "sensor_" + n) for n in ("noise", "noise_quad", "dropout", "edge_dropout", "edge_threshold")}
     given = {n: v for n, v in given.items() if v is not None}
     if given:
@@ -766,7 +815,8 @@ def run_args(a) -> dict:
             "min_valid": float(a.min_valid), "train_label": a.train_label is not None,
             **({"degrade_holes": True} if a.degrade_holes else {}),
             **({"train_lr_depth": True} if a.train_lr_depth is not None else {}),
-            **(sensor.args() if sensor is not None else {})}
+            **(sensor.args() if sensor is not None else {}),
+            **({"fill_holes": True} if a.fill_holes else {})}
 
 
 def main(argv=None, emit=print) -> dict:
@@ -788,7 +838,8 @@ def main(argv=None, emit=print) -> dict:
     if a.batch // world > L.TRAIN_MAX_BATCH:
         raise SystemExit(f"--batch {a.batch}: at most {L.TRAIN_MAX_BATCH} images per rank")
     ts = TrainSet(a.train_depth, a.train_color, dev, crop=a.crop, label_dir=a.train_label, depth_bits=a.depth_bits,
-                  depth_max=a.depth_max, **({"lr_dir": a.train_lr_depth, "scale": a.scale} if a.train_lr_depth else {}))
+                  depth_max=a.depth_max, **({"lr_dir": a.train_lr_depth, "scale": a.scale} if a.train_lr_depth else {}),
+                  **({"fill_holes": True} if a.fill_holes and a.train_lr_depth else {}))
     torch.manual_seed(a.seed)
     model = (CODONNet16 if a.scale == 16 else CODONNet)()
     rng = np.random.default_rng(a.seed)
@@ -810,11 +861,13 @@ def main(argv=None, emit=print) -> dict:
     val = ({"depth": a.val_depth, "color": a.val_color, "label": a.val_label, "every": a.val_every,
             "depth_bits": a.depth_bits, "depth_max": a.depth_max} if a.val_depth or a.val_lr_depth else None)
     if a.val_lr_depth:
-        val.update(lr_depth=a.val_lr_depth, scale=a.scale)
+        val.update(lr_depth=a.val_lr_depth, scale=a.scale, **({"fill_holes": True} if a.fill_holes else {}))
     if val is not None and a.val_report_params is not None:
         val.update(report=a.val_report_params)
     ckpt = {"path": a.save, "every": a.save_every} if a.save else None
     kw = {"sensor": sensor_of(a)} if sensor_of(a) is not None else {}      # without a model fit is called as ever
+    if a.fill_holes:
+        kw["fill_holes"] = True
     res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,
               log_every=a.log_every, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,
               args=args, emit=emit, clip_norm=a.clip_norm, skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema,

@@ -127,3 +127,62 @@ def bicubic_upsample_masked(lr: torch.Tensor, scale: int):
                                                   C.c_void_p(out.data_ptr()), C.c_void_p(valid.data_ptr()), ops._stream(dev)),
                 "bicubic_upsample_masked")
     return out, valid
+
+
+# ---- pull-push hole filling of low-resolution maps --------------------------------------------------------------
+
+_fill_ws = None             # guards.PerStream -> uint8 workspace of the (device, stream, thread)
+_fill_held: list = []       # workspaces made under a hipGraph capture
+
+
+def _fill_launch(dev, B: int, h: int, w: int, src_ptr: int, fmt: int, tab, top: int, out_ptr: int):
+    """codon_fill_holes on dev's current stream, with the per-stream workspace (capture-safe: guards.PerStream)."""
+    global _fill_ws
+    from .guards import PerStream
+    lib = L.load()
+    need = B * lib.codon_fill_holes_workspace_bytes(h, w)
+    if need == 0:
+        raise ValueError(f"fill_holes: a {h}x{w} plane (1..4096 each way)")
+    if _fill_ws is None:
+        _fill_ws = PerStream()
+    with torch.cuda.device(dev):
+        ws = _fill_ws.get(dev, lambda capturing: torch.empty(need, dtype=torch.uint8, device=dev), need=need, hold=_fill_held)
+        L.check(lib.codon_fill_holes(B, h, w, C.c_void_p(src_ptr), fmt, C.c_void_p(tab.data_ptr()) if tab is not None else None,
+                                     top, C.c_void_p(out_ptr), C.c_void_p(ws.data_ptr()), ws.numel(), ops._stream(dev)),
+                "fill_holes")
+
+
+def fill_holes(codes: torch.Tensor, depth_max: int = None) -> torch.Tensor:
+    """A low-resolution map with its holes filled by pull-push, a new tensor of the same shape and dtype; the
+    argument is not modified.  codes: (h,w) or (B,h,w) uint8 codes, or the bits of u16 codes as int16 / uint16, code 0 a hole
+    (depth_max: 255 for uint8, default 65535 otherwise) -- or a (B,1,h,w) float32 map on the code grid of depth_max (default 255:
+    code_table's 8-bit table; else the 16-bit table of depth_max), 0.0 a hole, as train.synthesize(degrade_holes=True) holds it
+    between its two bicubics.  Valid pixels come back bit for bit, a map without a valid pixel comes back unchanged, and a hole
+    never takes a value above the largest valid code.  Integer arithmetic, bit-exact: tests/fill_ref.py.  One launch up to
+    64 x 64, three beyond; no host synchronisation."""
+    on_grid = codes.dtype == torch.float32
+    if on_grid:
+        if codes.dim() != 4 or codes.shape[1] != 1:
+            raise RuntimeError("fill_holes expects (h,w) / (B,h,w) uint8, int16 or uint16 codes, or a (B,1,h,w) float32 map")
+        bits, top = (8, 255) if depth_max is None else (16, depth_max)
+    elif codes.dim() in (2, 3) and codes.dtype in (torch.uint8, torch.int16, torch.uint16):
+        if codes.dtype == torch.uint8:
+            if depth_max not in (None, 255):
+                raise ValueError(f"fill_holes: depth_max {depth_max!r} with 8-bit codes")
+            bits, top = 8, 255
+        else:
+            bits, top = 16, 65535 if depth_max is None else depth_max
+    else:
+        raise RuntimeError("fill_holes expects (h,w) / (B,h,w) uint8, int16 or uint16 codes, or a (B,1,h,w) float32 map")
+    check_depth_max(top)
+    src = codes.contiguous()
+    dev = ops._dev(src)
+    h, w = src.shape[-2:]
+    B = src.numel() // (h * w) if h * w else 0
+    if B < 1:
+        raise ValueError(f"fill_holes: an empty map {tuple(codes.shape)}")
+    tab = code_table(bits, top, dev)[0] if on_grid else None
+    out = torch.empty_like(src)
+    _fill_launch(dev, B, h, w, src.data_ptr(), L.FILL_F32 if on_grid else L.FILL_U8 if bits == 8 else L.FILL_U16, tab, int(top),
+                 out.data_ptr())
+    return out

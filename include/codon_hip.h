@@ -810,6 +810,37 @@ typedef struct codon_depth_errors_desc {
 int codon_depth_errors(const codon_depth_errors_desc* desc, const void* label, const void* out, uint64_t* acc,
                        void* error_map, uint8_t* region_map, codon_stream_t stream);
 
+/* ---- pull-push hole filling of low-resolution code planes (codon_amd.upsample.fill_holes) -------------------
+ * No reference counterpart (its depth inputs were hole-filled offline by a tool it does not ship): a DEFINITION, in
+ * codon_amd/csrc/fill_holes.hip and fill_tile.h, restated in numpy in tests/fill_ref.py, equal bits required.  Integers only.
+ *
+ * A plane of codes, 0 a hole.  Level 0 is the plane; level k+1 has ceil(h_k / 2) x ceil(w_k / 2) cells; the top level K is the
+ * first of 1 x 1.  Pull: cell (i, j) of level k+1 is (2 S + n) / (2 n) in integer division over its n valid children
+ * (2i+a, 2j+b) inside level k, S their sum -- the mean, half rounded up -- or a hole when n = 0; only values valid at level k
+ * enter.  Push, from the top down: a valid cell keeps its value; a hole at (y, x) of level k takes
+ *   (9 F(py, px) + 3 F(py, qx) + 3 F(qy, px) + F(qy, qx) + 8) >> 4  of the filled level k+1, py = y >> 1,
+ *   qy = clamp(py + (y odd ? +1 : -1), 0, h_{k+1} - 1), px and qx likewise from x.
+ * Valid codes come back as they were, a plane without holes or without a valid code comes back unchanged, and with one valid
+ * code no output is 0 or above the largest valid code.
+ *
+ * fmt: CODON_FILL_U8 (u8 codes, top 255), CODON_FILL_U16 (u16 codes, 2-byte aligned) or CODON_FILL_F32 (fp32 on the code grid
+ * of `top`, as the masked downsample and the sensor launch write it: v loads as code (int)rintf(v * (float)top), anything not
+ * positive is a hole, code c stores as tab[c] and a hole as +0.0f; tab: top + 1 fp32 entries).  tab is read by the fp32 format
+ * only and may be NULL otherwise.  in, out: (batch, height, width), contiguous; out must not be in.
+ *
+ * codon_fill_holes_workspace_bytes: HOST ONLY, no GPU needed -- the bytes ONE image takes, at least 2 bytes per cell of the
+ * levels 1 .. K; 0 for a height or width outside 1 .. 4096.  workspace: batch times that, 2-byte aligned, private to the stream.
+ * Planes up to 64 x 64: one launch; larger: three.  The launches depend on (batch, height, width) alone; no atomics, no host
+ * synchronisation.  Refused on the host, before any HIP call: null pointers, an unknown fmt, batch outside 1 .. 65535, height
+ * or width outside 1 .. 4096, top outside 1 .. 65535 or not 255 for u8 codes, out == in, an unaligned plane or workspace, a
+ * workspace that is too small. */
+#define CODON_FILL_U8 0
+#define CODON_FILL_U16 1
+#define CODON_FILL_F32 2
+size_t codon_fill_holes_workspace_bytes(int32_t height, int32_t width);
+int codon_fill_holes(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, const float* tab, int32_t top,
+                     void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
