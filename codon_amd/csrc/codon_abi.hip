@@ -11,6 +11,7 @@
 #include "kernels.h"
 #include "pair.h"
 #include "sensor_pixel.h"
+#include "stretch_tile.h"
 #include "train_record.h"
 
 namespace codon {
@@ -1020,6 +1021,43 @@ int codon_fill_holes(int32_t batch, int32_t height, int32_t width, const void* i
   CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "fill_holes: a workspace of %zu bytes is too small (%zu needed)",
                 workspace_bytes, need);
   return fill_holes(batch, height, width, in, fmt, tab, top, out, workspace, (hipStream_t)stream);
+}
+
+// ---- per-image range normalisation of depth codes ---------------------------------------------------------------
+int codon_code_range(int32_t batch, int32_t height, int32_t width, const void* codes, int32_t code_bits, int32_t* lo_hi,
+                     codon_stream_t stream) {
+  CODON_REQUIRE(codes && lo_hi, CODON_ERR_BAD_ARG, "code_range: null pointer");
+  CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "code_range: code_bits %d (8 or 16)", code_bits);
+  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "code_range: batch %d (1..65535)", batch);
+  CODON_REQUIRE(height >= 1 && height <= ST_MAX_SIDE && width >= 1 && width <= ST_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "code_range: a %dx%d plane (1..%d each way)", height, width, ST_MAX_SIDE);
+  CODON_REQUIRE(((uintptr_t)codes & (uintptr_t)(code_bits / 8 - 1)) == 0 && ((uintptr_t)lo_hi & 3) == 0, CODON_ERR_BAD_ARG,
+                "code_range: unaligned plane or range");
+  return code_range(batch, (long)height * width, codes, code_bits == 8 ? ST_U8 : ST_U16, lo_hi, (hipStream_t)stream);
+}
+
+static int map_codes_checked(const char* who, int dir, int32_t batch, int32_t height, int32_t width, const void* in,
+                             int32_t code_bits, int32_t top, const int32_t* lo_hi, void* out, codon_stream_t stream) {
+  CODON_REQUIRE(in && lo_hi && out, CODON_ERR_BAD_ARG, "%s: null pointer", who);
+  CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "%s: code_bits %d (8 or 16)", who, code_bits);
+  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "%s: batch %d (1..65535)", who, batch);
+  CODON_REQUIRE(height >= 1 && height <= ST_MAX_SIDE && width >= 1 && width <= ST_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "%s: a %dx%d plane (1..%d each way)", who, height, width, ST_MAX_SIDE);
+  CODON_REQUIRE(code_bits == 16 ? (top >= 2 && top <= 65535) : top == 255, CODON_ERR_BAD_ARG,
+                "%s: top %d (255 for 8-bit codes, 2..65535 for 16-bit codes)", who, top);
+  CODON_REQUIRE((((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(code_bits / 8 - 1)) == 0 && ((uintptr_t)lo_hi & 3) == 0,
+                CODON_ERR_BAD_ARG, "%s: unaligned plane or range", who);
+  return map_codes(dir, batch, (long)height * width, in, code_bits == 8 ? ST_U8 : ST_U16, top, lo_hi, out, (hipStream_t)stream);
+}
+
+int codon_stretch_codes(int32_t batch, int32_t height, int32_t width, const void* in, int32_t code_bits, int32_t top,
+                        const int32_t* lo_hi, void* out, codon_stream_t stream) {
+  return map_codes_checked("stretch_codes", ST_STRETCH, batch, height, width, in, code_bits, top, lo_hi, out, stream);
+}
+
+int codon_unstretch_codes(int32_t batch, int32_t height, int32_t width, const void* in, int32_t code_bits, int32_t top,
+                          const int32_t* lo_hi, void* out, codon_stream_t stream) {
+  return map_codes_checked("unstretch_codes", ST_UNSTRETCH, batch, height, width, in, code_bits, top, lo_hi, out, stream);
 }
 
 size_t codon_weight_checksum_workspace_bytes(void) { return weight_checksum_workspace_bytes(); }

@@ -167,6 +167,10 @@ size_t fill_holes_workspace_bytes(int h, int w);
 int fill_holes(int B, int h, int w, const void* in, int fmt, const float* tab, int top, void* out, void* workspace,
                hipStream_t stream);
 
+// stretch.hip; fmt: ST_U8 / ST_U16, dir: ST_STRETCH / ST_UNSTRETCH (stretch_tile.h); n: codes per image
+int code_range(int B, long n, const void* codes, int fmt, int* lo_hi, hipStream_t stream);
+int map_codes(int dir, int B, long n, const void* in, int fmt, int top, const int* lo_hi, void* out, hipStream_t stream);
+
 // ew_c8.hip: the stencils, CAC passes and elementwise helpers of stencil.hip, cac.hip and cac_bwd.hip over channel-blocked 16-bit tensors
 int stem_pair_fwd_c8(int B, int H, int W, const float* xa, const float* wa, void* ya, int ya_ctotal, int ya_coff,
                      const float* xb, const float* wb, void* yb, int yb_ctotal, int yb_coff, int dtype, int* bad, int* host_a,

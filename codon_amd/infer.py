@@ -31,6 +31,7 @@ from . import CODONNet, CODONNet16, io, metrics
 from .io import check_depth_max, list_pairs, read_depth_plane
 from .upsample import _on_device, code_table, phase_weights
 from .upsample import fill_holes as _fill_holes
+from .upsample import check_stretch_top, stretch_codes, unstretch_codes
 
 
 def _load_host(a_depth, a_color, a_label, f, tdt, depth_bits=8, depth_max=65535):
@@ -148,7 +149,8 @@ def _pinned_copy(t: torch.Tensor) -> torch.Tensor:
 
 
 def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None,
-             depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None, self_ensemble=False, report=None, fill_holes=False):
+             depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None, self_ensemble=False, report=None, fill_holes=False,
+             normalize=False):
     """The test loop over every image pair.  Returns {"n", "rmse_mean", "ssim_mean", "seconds", "images_per_s"}.
     depth_bits=16: 16-bit depth and label files with codes 0 .. depth_max, outputs through metrics.postprocess_u16 into 16-bit
     PNGs, RMSE (metrics.masked_rmse_u16) in codes times depth_unit, SSIM of label / depth_max against out / depth_max.
@@ -161,11 +163,19 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     tokens of metrics.depth_report (mad, rmse and max in codes times depth_unit), the error maps are written under the images'
     names, and the result gains "reports" (the per-image dicts, with "file") and "report_means" (metrics.report_means).
     fill_holes (needs lr_depth): the main stream fills the holes of the uploaded codes by pull-push
-    (upsample.fill_holes) ahead of codes_to_input, in both loops -- the network sees a dense input."""
+    (upsample.fill_holes) ahead of codes_to_input, in both loops -- the network sees a dense input.
+    normalize (needs lr_depth): per-image range normalisation on the code grid.  The main stream stretches the
+    (filled) codes' own range [lo, hi] onto [1, top] (upsample.stretch_codes: two launches, the range stays on the device)
+    ahead of codes_to_input and maps the post-processed output codes back (upsample.unstretch_codes) before anything else sees
+    them, in both loops: the metrics, the report, the error maps and the written files are in the files' own codes, and the
+    label is never remapped."""
     if (lr_depth is None) == (input_depth is None):
         raise ValueError("run_loop: exactly one of input_depth and lr_depth")
     if fill_holes and lr_depth is None:
         raise ValueError("run_loop: fill_holes needs lr_depth (only low-resolution code planes are filled)")
+    if normalize and lr_depth is None:
+        raise ValueError("run_loop: normalize needs lr_depth (input_depth maps are not code planes: only low-resolution codes "
+                         "are normalised)")
     if lr_depth is not None and scale not in (4, 8, 16):
         raise ValueError(f"run_loop: lr_depth needs scale 4, 8 or 16 (got {scale!r})")
     files = list_pairs(lr_depth or input_depth, input_color) if files is None else files
@@ -181,6 +191,9 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
         post, sqerr, write = metrics.postprocess_u8, metrics.masked_sqerr_dev, io.write_gray
         unit = lambda t: t.float() / 255                                                         # noqa: E731
     scale_rm = float(depth_unit) if deep else None
+    lo_hi = None                                        # normalize: the range of the image in flight, on the device
+    if normalize:
+        check_stretch_top("run_loop: normalize", depth_max if deep else 255)
     if lr_depth is not None:
         load = lambda f: _load_host_lr(lr_depth, input_color, label, f, tdt, scale, depth_bits, depth_max)      # noqa: E731
         if fill_holes:
@@ -188,6 +201,17 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                                             depth_max if deep else None)
         else:
             to_x = lambda c: codes_to_input(c, scale, tdt, depth_max if deep else None)                        # noqa: E731
+        if normalize:                                   # [fill_holes ->] stretch -> codes_to_input; the range rides to `post`
+            dm = depth_max if deep else None
+            fill = (lambda c: _fill_holes(c, dm)) if fill_holes else (lambda c: c)                             # noqa: E731
+            post_codes = post
+
+            def to_x(c):                                # noqa: F811
+                nonlocal lo_hi
+                c, lo_hi = stretch_codes(fill(c), dm)
+                return codes_to_input(c, scale, tdt, dm)
+
+            post = lambda o: unstretch_codes(post_codes(o), lo_hi, dm)                                         # noqa: E731
     else:
         load = lambda f: _load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max)             # noqa: E731
         to_x = lambda x: x                                                                                     # noqa: E731
@@ -425,6 +449,11 @@ def main(argv=None):
                     help="with --lr-depth: fill the holes of every low-resolution map on the device by pull-push (the mean of "
                          "the valid pixels up a pyramid, a 9/3/3/1 mix back down; integers, bit-exact) before it is upsampled, "
                          "so that the network sees a dense input; valid pixels are untouched")
+    ap.add_argument("--normalize", action="store_true",
+                    help="with --lr-depth: per-image range normalisation -- the valid codes [lo, hi] of every low-resolution "
+                         "map (after --fill-holes) are stretched onto [1, top] of the code grid on the device, holes stay "
+                         "holes, and the output codes are mapped back before they are measured and written (integers, "
+                         "bit-exact; DESIGN 12.10)")
     ap.add_argument("--input-color", required=True)
     ap.add_argument("--label", default=None)
     ap.add_argument("--out", default=None)
@@ -464,6 +493,8 @@ def main(argv=None):
         ap.error("exactly one of --input-depth and --lr-depth is required")
     if a.fill_holes and a.lr_depth is None:
         ap.error("--fill-holes needs --lr-depth")
+    if a.normalize and a.lr_depth is None:
+        ap.error("--normalize needs --lr-depth (it is refused with --input-depth: only low-resolution code planes are normalised)")
     if a.ema and not a.weights:
         ap.error("--ema needs --weights")
     if a.depth_bits != 16 and (a.depth_max is not None or a.depth_unit != 1.0):
@@ -489,7 +520,7 @@ def main(argv=None):
                  depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit,
                  **({"self_ensemble": True} if a.self_ensemble else {}), **({"report": report} if report else {}),
                  **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}),
-                 **({"fill_holes": True} if a.fill_holes else {}))
+                 **({"fill_holes": True} if a.fill_holes else {}), **({"normalize": True} if a.normalize else {}))
     print(r["n"])
     if a.label and r["n"]:
         print(r["rmse_mean"], r["ssim_mean"])

@@ -10,6 +10,8 @@ numpy in tests/train_data_ref.py and the two agree bit for bit.  --depth-bits 16
 through a 65 536-entry table and the last step quantises onto the data set's own code grid (tests/train_data16_ref.py).
 --fill-holes: the holes of the low-resolution maps -- real ones, or the synthetic ones of --degrade-holes -- are
 filled on the device by pull-push before they are upsampled, exactly as `codon_amd.infer --lr-depth --fill-holes` fills them.
+--normalize: per-image range normalisation -- once the pool is on the device every record's codes are stretched in
+place from their own valid range onto the whole code grid, exactly as `codon_amd.infer --lr-depth --normalize` stretches them.
 --train-lr-depth DIR: REAL pairs -- a sensor's low-resolution map per pair, paired by file name; nothing is
 degraded, one launch (codon_train_crops_lr) builds x, y and t, and x is the crop of what `codon_amd.infer --lr-depth` builds from
 the whole low-resolution file, bit for bit (tests/train_lr_ref.py).
@@ -47,6 +49,7 @@ from .metrics import report_tokens
 from .upsample import (_fill_launch, _on_device, code_table, down_weights, gauss_table, lut16,      # noqa: F401 (lut16: for
                        phase_weights, u8_lut)                                                      # importers)
 from .upsample import fill_holes as _fill_holes
+from .upsample import check_stretch_top, code_range, stretch_codes
 
 DTYPES = {"bf16": torch.bfloat16, "f32": None}
 RESUME_KEYS = ("scale", "crop", "batch", "dtype", "clip_norm", "skip_nonfinite", "ema", "lr_schedule", "warmup_steps", "lr_min",
@@ -67,6 +70,8 @@ SENSOR_DEFAULTS = {"sensor_noise": None, "sensor_noise_quad": None, "sensor_drop
                    "sensor_edge_threshold": None, "sensor_seed": None}
 # the same for --fill-holes: a resume key with default False, written by a run that sets it ONLY
 FILL_DEFAULTS = {"fill_holes": False}
+# the same for --normalize: a resume key with default False, written by a run that sets it ONLY
+NORM_DEFAULTS = {"normalize": False}
 MAX_REDRAWS = 64                                    # draw(min_valid=): per sample, before it gives up
 LR_SCHEDULES = ("constant", "cosine")
 
@@ -102,10 +107,15 @@ class TrainSet:
     excludes label_dir.  has_lr, lr_scale say so (False, None otherwise).
     `fill_holes` (needs lr_dir): once the pool is on the device, the low-resolution plane of every record is
     filled by pull-push from the WHOLE file (upsample.fill_holes, one call per record), so that a step costs nothing extra and x
-    stays the crop of what `infer --lr-depth --fill-holes` builds from that file; the target plane is untouched."""
+    stays the crop of what `infer --lr-depth --fill-holes` builds from that file; the target plane is untouched.
+    `normalize` (excludes label_dir): once the pool is on the device, and after the filling, every record's code
+    planes are stretched IN PLACE (upsample.stretch_codes) so that a step costs nothing extra.  With lr_dir the range is that of
+    the (filled) low-resolution plane of the WHOLE file, as `infer --lr-depth --normalize` takes it; it stretches that plane
+    and, clamped, the HR target plane.  Without lr_dir the depth plane is stretched by its own range."""
 
     def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None, label_dir: str = None, depth_bits: int = 8,
-                 depth_max: int = 65535, lr_dir: str = None, scale: int = None, fill_holes: bool = False):
+                 depth_max: int = 65535, lr_dir: str = None, scale: int = None, fill_holes: bool = False,
+                 normalize: bool = False):
         if depth_bits not in (8, 16):
             raise ValueError(f"TrainSet: depth_bits {depth_bits!r} (8 or 16)")
         check_depth_max(depth_max)
@@ -114,6 +124,12 @@ class TrainSet:
         if fill_holes and lr_dir is None:
             raise ValueError("TrainSet: fill_holes needs lr_dir (only low-resolution code planes are filled)")
         self.fill_holes = bool(fill_holes)
+        if normalize:
+            if label_dir is not None:
+                raise ValueError("TrainSet: normalize and label_dir exclude each other (a label plane has no range of its own "
+                                 "to be stretched by)")
+            check_stretch_top("TrainSet: normalize", self.depth_max if depth_bits == 16 else 255)
+        self.normalize = bool(normalize)
         if self.has_lr:
             if scale not in (4, 8, 16):
                 raise ValueError(f"TrainSet: lr_dir needs scale 4, 8 or 16 (got {scale!r})")
@@ -172,6 +188,18 @@ class TrainSet:
                 plane = self.pool[lo:lo + wide * lh * lw]
                 plane = (plane.view(torch.int16) if deep else plane).view(lh, lw)
                 plane.copy_(_fill_holes(plane, self.depth_max if deep else None))
+        if self.normalize:
+            wide, dm = depth_bits // 8, self.depth_max if deep else None
+            for off, (h, w) in zip(self.offsets.tolist(), self.sizes.tolist()):
+                lay = record_layout(depth_bits, False, self.lr_scale or 0, h, w)
+                shapes = [("depth", h, w)] + ([("lr", h // self.lr_scale, w // self.lr_scale)] if self.has_lr else [])
+                planes = {}
+                for name, ph, pw in shapes:
+                    p = self.pool[off + lay[name]:off + lay[name] + wide * ph * pw]
+                    planes[name] = (p.view(torch.int16) if deep else p).view(ph, pw)
+                lo_hi = code_range(planes["lr" if self.has_lr else "depth"])
+                for p in planes.values():               # the target plane of real pairs is clamped into the map's range
+                    stretch_codes(p, dm, lo_hi, out=p)
 
     def __len__(self):
         return len(self.files)
@@ -456,13 +484,14 @@ def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, 
 def load_resume(path: str, args: dict) -> dict:
     """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype, or with
     other options that change the trajectory (RESUME_KEYS, DEPTH_DEFAULTS', DEGRADE_DEFAULTS', LR_DEFAULTS' and
-    SENSOR_DEFAULTS' and FILL_DEFAULTS' keys; a key the checkpoint's args lack compares as its default)."""
+    SENSOR_DEFAULTS', FILL_DEFAULTS' and NORM_DEFAULTS' keys; a key the checkpoint's args lack compares as its default)."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(ck, dict) or not all(k in ck for k in ("epoch", "model", "optimizer", "rng", "args")):
         raise ValueError(f"--resume {path}: not a codon_amd.train checkpoint (use --weights to start from other weights)")
-    absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS, **LR_DEFAULTS, **SENSOR_DEFAULTS, **FILL_DEFAULTS}
+    absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS, **LR_DEFAULTS, **SENSOR_DEFAULTS, **FILL_DEFAULTS,
+              **NORM_DEFAULTS}
     keys = (RESUME_KEYS + tuple(DEPTH_DEFAULTS) + tuple(DEGRADE_DEFAULTS) + tuple(LR_DEFAULTS) + tuple(SENSOR_DEFAULTS) +
-            tuple(FILL_DEFAULTS))
+            tuple(FILL_DEFAULTS) + tuple(NORM_DEFAULTS))
     was, now = ({k: a.get(k, absent.get(k)) for k in keys} for a in (ck["args"], args))
     bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in keys if was[k] != now[k]]
     if bad:
@@ -476,7 +505,7 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         args: dict = None, time_synth: bool = False, emit=print, clip_norm: float = None, skip_nonfinite: bool = False,
         ema_decay: float = None, lr_schedule: str = "constant", warmup: int = 0, lr_min: float = 0.0, lr_steps: int = None,
         grad_hook=None, mask_holes: bool = False, min_valid: float = 0.0, degrade_holes: bool = False,
-        sensor: SensorModel = None, fill_holes: bool = False) -> dict:
+        sensor: SensorModel = None, fill_holes: bool = False, normalize: bool = False) -> dict:
     """Train `model` (fp32 parameters on the pool's device) from step start_step + 1 to step `steps`.
     val:   {"depth", "color", "label", "every"} -- rank 0 runs infer.run_loop every `every` steps and prints the means;
     ckpt:  {"path", "every"} -- rank 0 saves every `every` steps and after the last one;
@@ -500,6 +529,9 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     fill_holes: synthesize's hole filling; needs degrade_holes, or a TrainSet of low-resolution maps built with
            fill_holes (one built without refuses it, and one built with it refuses a fit without); the checkpoint's args gain
            fill_holes=True.  A `val` dict with "lr_depth" and "fill_holes" validates on filled maps.
+    normalize: per-image range normalisation is a property of the TrainSet, whose pool is stretched once, when it
+           is built: fit and the TrainSet must agree on it (either way round is refused); the checkpoint's args gain
+           normalize=True.  A `val` dict with "lr_depth" and "normalize" validates as `infer --lr-depth --normalize` does.
     Returns {"losses": [(step, loss)], "gs", "opt", "rng", "step", ...}."""
     from .dist import FlatAdam, GradSync
     from .metrics import L1SSIMLoss, MaskedL1SSIMLoss
@@ -513,6 +545,9 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     if bool(fill_holes) != trainset.fill_holes if trainset.has_lr else (fill_holes and not degrade_holes):
         raise ValueError("fit: fill_holes needs degrade_holes, or a TrainSet of low-resolution maps -- and that TrainSet must "
                          "have been built with the same fill_holes (its pool is filled once, when it is built)")
+    if bool(normalize) != trainset.normalize:
+        raise ValueError(f"fit: normalize {bool(normalize)!r} with a TrainSet built with normalize {trainset.normalize!r} (its "
+                         "pool is stretched once, when it is built)")
     synth_kw = {"fill_holes": True} if fill_holes else {}      # without it synthesize is called as ever
     if sensor is not None:                          # refused before the first step; without a model synthesize is called as ever
         from .dist import shard_batch
@@ -546,6 +581,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         args.update(sensor.args())
     if fill_holes:                                  # only then, likewise
         args.update(fill_holes=True)
+    if normalize:                                   # only then, likewise
+        args.update(normalize=True)
     if trainset.depth_bits == 16:                   # only then: an 8-bit checkpoint keeps the keys it always had
         args.update(depth_bits=16, depth_max=int(trainset.depth_max))
     stream = torch.cuda.current_stream(dev)
@@ -634,6 +671,8 @@ def validate(model, dev, val: dict, emit=print) -> dict:
                 deep.update(lr_depth=val["lr_depth"], scale=val["scale"])
                 if val.get("fill_holes"):           # filled as infer --lr-depth --fill-holes fills them
                     deep.update(fill_holes=True)
+                if val.get("normalize"):            # stretched and mapped back as infer --lr-depth --normalize does
+                    deep.update(normalize=True)
             if val.get("report") is not None:       # the evaluation suite of infer --report
                 deep.update(report=val["report"])
             r = run_loop(model, dev, torch.float32, val.get("depth"), val["color"], val.get("label"), emit=lambda s: None, **deep)
@@ -686,6 +725,12 @@ def parse_args(argv=None):
                     help="fill the holes of the low-resolution maps on the device by pull-push before they are upsampled, as "
                          "`codon_amd.infer --lr-depth --fill-holes` does: the maps of --train-lr-depth (once, when they are "
                          "loaded) or the synthetic ones of --degrade-holes (every step), and those of --val-lr-depth")
+    ap.add_argument("--normalize", action="store_true",
+                    help="per-image range normalisation, as `codon_amd.infer --lr-depth --normalize` does it: when the data is "
+                         "loaded, the valid codes [lo, hi] of every map are stretched onto [1, top] of the code grid on the "
+                         "device, holes staying holes -- the low-resolution map of --train-lr-depth by its own range (after "
+                         "--fill-holes) and its HR target by the same range, else the depth map by its own; also applies to "
+                         "--val-lr-depth; refused with --train-label")
     ap.add_argument("--sensor-noise", type=float, default=None, metavar="CODES",
                     help="sensor model: Gaussian noise of this standard deviation, in codes of the data's grid (255, or "
                          "--depth-max), on the synthetic low-resolution map; every --sensor option draws from --seed")
@@ -746,6 +791,8 @@ def parse_args(argv=None):
         ap.error("--train-lr-depth and --degrade-holes exclude each other (nothing is degraded)")
     if a.fill_holes and a.train_lr_depth is None and not a.degrade_holes:
         ap.error("--fill-holes needs --train-lr-depth or --degrade-holes (the unmasked degradation has no holes to fill)")
+    if a.normalize and a.train_label is not None:
+        ap.error("--normalize and --train-label exclude each other (a label plane has no range of its own to be stretched by)")
     given = {n: getattr(a, "sensor_" + n) for n in ("noise", "noise_quad", "dropout", "edge_dropout", "edge_threshold")}
     given = {n: v for n, v in given.items() if v is not None}
     if given:
@@ -816,7 +863,8 @@ def run_args(a) -> dict:
             **({"degrade_holes": True} if a.degrade_holes else {}),
             **({"train_lr_depth": True} if a.train_lr_depth is not None else {}),
             **(sensor.args() if sensor is not None else {}),
-            **({"fill_holes": True} if a.fill_holes else {})}
+            **({"fill_holes": True} if a.fill_holes else {}),
+            **({"normalize": True} if a.normalize else {})}
 
 
 def main(argv=None, emit=print) -> dict:
@@ -839,7 +887,8 @@ def main(argv=None, emit=print) -> dict:
         raise SystemExit(f"--batch {a.batch}: at most {L.TRAIN_MAX_BATCH} images per rank")
     ts = TrainSet(a.train_depth, a.train_color, dev, crop=a.crop, label_dir=a.train_label, depth_bits=a.depth_bits,
                   depth_max=a.depth_max, **({"lr_dir": a.train_lr_depth, "scale": a.scale} if a.train_lr_depth else {}),
-                  **({"fill_holes": True} if a.fill_holes and a.train_lr_depth else {}))
+                  **({"fill_holes": True} if a.fill_holes and a.train_lr_depth else {}),
+                  **({"normalize": True} if a.normalize else {}))
     torch.manual_seed(a.seed)
     model = (CODONNet16 if a.scale == 16 else CODONNet)()
     rng = np.random.default_rng(a.seed)
@@ -861,13 +910,16 @@ def main(argv=None, emit=print) -> dict:
     val = ({"depth": a.val_depth, "color": a.val_color, "label": a.val_label, "every": a.val_every,
             "depth_bits": a.depth_bits, "depth_max": a.depth_max} if a.val_depth or a.val_lr_depth else None)
     if a.val_lr_depth:
-        val.update(lr_depth=a.val_lr_depth, scale=a.scale, **({"fill_holes": True} if a.fill_holes else {}))
+        val.update(lr_depth=a.val_lr_depth, scale=a.scale, **({"fill_holes": True} if a.fill_holes else {}),
+                   **({"normalize": True} if a.normalize else {}))
     if val is not None and a.val_report_params is not None:
         val.update(report=a.val_report_params)
     ckpt = {"path": a.save, "every": a.save_every} if a.save else None
     kw = {"sensor": sensor_of(a)} if sensor_of(a) is not None else {}      # without a model fit is called as ever
     if a.fill_holes:
         kw["fill_holes"] = True
+    if a.normalize:
+        kw["normalize"] = True
     res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,
               log_every=a.log_every, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,
               args=args, emit=emit, clip_norm=a.clip_norm, skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema,

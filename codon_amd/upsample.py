@@ -186,3 +186,84 @@ def fill_holes(codes: torch.Tensor, depth_max: int = None) -> torch.Tensor:
     _fill_launch(dev, B, h, w, src.data_ptr(), L.FILL_F32 if on_grid else L.FILL_U8 if bits == 8 else L.FILL_U16, tab, int(top),
                  out.data_ptr())
     return out
+
+
+# ---- per-image range normalisation of depth codes --------------------------------------------------------------
+
+def _code_planes(who: str, codes: torch.Tensor, depth_max):
+    """-> (contiguous codes, B, h, w, code_bits, top) of (h,w) / (B,h,w) uint8, int16 or uint16 codes; refusals by name"""
+    if codes.dim() not in (2, 3) or codes.dtype not in (torch.uint8, torch.int16, torch.uint16):
+        raise RuntimeError(f"{who} expects (h,w) or (B,h,w) uint8 codes, or u16 codes as int16 / uint16")
+    if codes.dtype == torch.uint8:
+        if depth_max not in (None, 255):
+            raise ValueError(f"{who}: depth_max {depth_max!r} with 8-bit codes")
+        bits, top = 8, 255
+    else:
+        bits, top = 16, 65535 if depth_max is None else depth_max
+    check_depth_max(top)
+    check_stretch_top(who, top)
+    src = codes.contiguous()
+    h, w = src.shape[-2:]
+    B = src.numel() // (h * w) if h * w else 0
+    if B < 1:
+        raise ValueError(f"{who}: an empty map {tuple(codes.shape)}")
+    return src, B, h, w, bits, int(top)
+
+
+def check_stretch_top(who: str, depth_max: int):
+    """The stretch maps onto [1, depth_max] with depth_max - 1 steps: a grid of fewer than two codes is refused by name."""
+    if depth_max < 2:
+        raise ValueError(f"{who}: depth_max {depth_max!r} leaves per-image normalisation no grid to stretch onto (at least 2)")
+
+
+def code_range(codes: torch.Tensor) -> torch.Tensor:
+    """(B, 2) int32 on the codes' device: per image (lo, hi), the smallest non-zero and the largest code of the plane, (0, 0)
+    for a plane without a valid code.  codes: (h,w) or (B,h,w) uint8 codes, or the bits of u16 codes as
+    int16 / uint16, code 0 a hole.  One launch, one workgroup per image; nothing is read back."""
+    src, B, h, w, bits, _ = _code_planes("code_range", codes, None)
+    dev = ops._dev(src)
+    lo_hi = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    with ops._on(dev):
+        L.check(L.load().codon_code_range(B, h, w, C.c_void_p(src.data_ptr()), bits, C.c_void_p(lo_hi.data_ptr()),
+                                          ops._stream(dev)), "code_range")
+    return lo_hi
+
+
+def _map_codes(who: str, entry: str, codes, lo_hi, depth_max, out):
+    src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
+    dev = ops._dev(src)
+    if lo_hi is None:
+        lo_hi = code_range(src)
+    else:
+        lo_hi = torch.as_tensor(lo_hi, dtype=torch.int32, device=dev).reshape(-1, 2).contiguous()
+        if lo_hi.shape[0] != B:
+            raise ValueError(f"{who}: {lo_hi.shape[0]} ranges for {B} images")
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.shape != codes.shape or out.dtype != codes.dtype or out.device != src.device or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous tensor of the codes' shape, dtype and device")
+    with ops._on(dev):
+        L.check(getattr(L.load(), entry)(B, h, w, C.c_void_p(src.data_ptr()), bits, top, C.c_void_p(lo_hi.data_ptr()),
+                                         C.c_void_p(out.data_ptr()), ops._stream(dev)), who)
+    return out, lo_hi
+
+
+def stretch_codes(codes: torch.Tensor, depth_max: int = None, lo_hi: torch.Tensor = None, out: torch.Tensor = None):
+    """(codes', lo_hi): every image's valid codes [lo, hi] stretched onto [1, top] of the data's own grid -- top 255 for uint8
+    codes, depth_max (default 65535) for u16 codes held as int16 / uint16 -- code 0, a hole, staying 0:
+    c' = 1 + (2 (clamp(c, lo, hi) - lo) (top - 1) + n) // (2 n) with n = hi - lo, top when n == 0, in integers, bit-exact
+    (tests/stretch_ref.py).  codes: (h,w) or (B,h,w); a new tensor of the same shape and dtype comes back and the argument is
+    not modified, unless `out` names the result's tensor, which may be `codes` itself.  lo_hi: (B, 2) int32 on the device --
+    code_range(codes) when None (one more launch); another plane's range clamps the codes into it.  A plane without a valid
+    code, range (0, 0), comes back as it is.  No host synchronisation."""
+    return _map_codes("stretch_codes", "codon_stretch_codes", codes, lo_hi, depth_max, out)
+
+
+def unstretch_codes(codes: torch.Tensor, lo_hi: torch.Tensor, depth_max: int = None, out: torch.Tensor = None) -> torch.Tensor:
+    """stretch_codes undone on codes of the stretched grid (the network's output after post-processing):
+    o = lo + (2 (max(o', 1) - 1) n + top - 1) // (2 (top - 1)), a value in [lo, hi]; unstretch_codes(*stretch_codes(c)) == c
+    bit for bit on valid codes.  lo_hi: the (B, 2) int32 device tensor stretch_codes returned.  One launch, no host
+    synchronisation."""
+    if lo_hi is None:
+        raise ValueError("unstretch_codes: lo_hi is needed (the range stretch_codes returned)")
+    return _map_codes("unstretch_codes", "codon_unstretch_codes", codes, lo_hi, depth_max, out)[0]

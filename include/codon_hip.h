@@ -841,6 +841,32 @@ size_t codon_fill_holes_workspace_bytes(int32_t height, int32_t width);
 int codon_fill_holes(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, const float* tab, int32_t top,
                      void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream);
 
+/* ---- per-image range normalisation of depth codes (codon_amd.upsample.code_range / stretch_codes /
+ * unstretch_codes) ---------------------------------------------------------------------------------------------------------
+ * No reference counterpart (its data was normalised offline, if at all): a DEFINITION, in codon_amd/csrc/stretch.hip and
+ * stretch_tile.h, restated in numpy in tests/stretch_ref.py, equal bits required.  Integers only.
+ *
+ * A plane of codes on the grid 0 .. top, 0 a hole; T = top - 1.  The range of a plane is (lo, hi), its smallest non-zero and
+ * its largest code, (0, 0) without a valid code.  With n = hi - lo, in 64-bit integer division:
+ *   stretch:    0 -> 0;  c -> 1 + (2 k T + n) / (2 n),  k = clamp(c, lo, hi) - lo;  n == 0: c -> top
+ *   unstretch:  o -> lo + (2 (clamp(o, 1, top) - 1) n + T) / (2 T)
+ * A range that is not 1 <= lo <= hi <= top, (0, 0) above all, makes both the identity.  unstretch(stretch(c)) == c for every
+ * c in [lo, hi]; a valid code never becomes 0; the range (1, top) makes stretch the identity.
+ *
+ * codes, in, out: (batch, height, width), contiguous, u8 codes (code_bits 8, top 255) or u16 codes (code_bits 16, 2-byte
+ * aligned, top 2 .. 65535); no other alignment is asked of a plane.  lo_hi: (batch, 2) int32 ON THE DEVICE, written by
+ * codon_code_range and read by the other two, never by the host; image b is mapped with its own pair.  out may be in.
+ * codon_code_range: one launch, one workgroup per image, no atomics, lo_hi needs no initialisation.  codon_stretch_codes,
+ * codon_unstretch_codes: one launch each.  The launches depend on (batch, height, width) alone; no host synchronisation.
+ * Refused on the host, before any HIP call: null pointers, code_bits other than 8 or 16, batch outside 1 .. 65535, height or
+ * width outside 1 .. 16384, top not 255 for u8 codes or outside 2 .. 65535 for u16 codes, an unaligned plane or range. */
+int codon_code_range(int32_t batch, int32_t height, int32_t width, const void* codes, int32_t code_bits, int32_t* lo_hi,
+                     codon_stream_t stream);
+int codon_stretch_codes(int32_t batch, int32_t height, int32_t width, const void* in, int32_t code_bits, int32_t top,
+                        const int32_t* lo_hi, void* out, codon_stream_t stream);
+int codon_unstretch_codes(int32_t batch, int32_t height, int32_t width, const void* in, int32_t code_bits, int32_t top,
+                          const int32_t* lo_hi, void* out, codon_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
