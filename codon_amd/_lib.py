@@ -189,6 +189,8 @@ SIGNATURES = {
     "codon_depth_errors": (C.c_int, [C.POINTER(DepthErrorsDesc), _P, _P, _P, _P, _P, _P]),
     "codon_fill_holes_workspace_bytes": (_S, [_I, _I]),
     "codon_fill_holes": (C.c_int, [_I, _I, _I, _P, _I, _P, _I, _P, _P, _S, _P]),
+    "codon_fill_guided_workspace_bytes": (_S, [_I, _I]),
+    "codon_fill_holes_guided": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, C.c_int64, C.c_int64, _I, _P, _P, _P, _S, _P]),
     "codon_code_range": (C.c_int, [_I, _I, _I, _P, _I, _P, _P]),
     "codon_stretch_codes": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _P, _P]),
     "codon_unstretch_codes": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _P, _P]),

@@ -1023,6 +1023,37 @@ int codon_fill_holes(int32_t batch, int32_t height, int32_t width, const void* i
   return fill_holes(batch, height, width, in, fmt, tab, top, out, workspace, (hipStream_t)stream);
 }
 
+// ---- guidance-aware pull-push hole filling ---------------------------------------------------------------------
+size_t codon_fill_guided_workspace_bytes(int32_t height, int32_t width) { return fill_guided_workspace_bytes(height, width); }
+
+int codon_fill_holes_guided(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top,
+                            const uint8_t* guide, int64_t guide_row_bytes, int64_t guide_image_bytes, int32_t scale,
+                            const uint16_t* range_tab, void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
+  CODON_REQUIRE(in && out && workspace && guide && range_tab, CODON_ERR_BAD_ARG, "fill_holes_guided: null pointer");
+  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "fill_holes_guided: fmt %d (0: u8 codes, 1: u16 codes)", fmt);
+  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "fill_holes_guided: batch %d (1..65535)", batch);
+  CODON_REQUIRE(height >= 1 && height <= FL_MAX_SIDE && width >= 1 && width <= FL_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "fill_holes_guided: a %dx%d plane (1..%d each way)", height, width, FL_MAX_SIDE);
+  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
+                "fill_holes_guided: top %d (255 for u8 codes, 1..65535 otherwise)", top);
+  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_BAD_ARG, "fill_holes_guided: scale %d (4, 8 or 16)", scale);
+  CODON_REQUIRE(guide_row_bytes >= (int64_t)width * scale, CODON_ERR_BAD_ARG,
+                "fill_holes_guided: guide rows of %lld bytes (at least %lld: width times scale)", (long long)guide_row_bytes,
+                (long long)width * scale);
+  CODON_REQUIRE(batch == 1 || guide_image_bytes >= (int64_t)height * scale * guide_row_bytes, CODON_ERR_BAD_ARG,
+                "fill_holes_guided: guide images %lld bytes apart (at least %lld: height times scale rows)",
+                (long long)guide_image_bytes, (long long)height * scale * guide_row_bytes);
+  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "fill_holes_guided: in and out are the same buffer");
+  const bool planes_ok = (((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;      // u16 codes: 2 bytes
+  const bool tab_ok = ((uintptr_t)range_tab & 1) == 0, ws_ok = ((uintptr_t)workspace & 15) == 0;             // u16 entries; 16 bytes
+  CODON_REQUIRE(planes_ok && tab_ok && ws_ok, CODON_ERR_BAD_ARG, "fill_holes_guided: unaligned plane, table or workspace");
+  const size_t need = (size_t)batch * fill_guided_workspace_bytes(height, width);
+  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "fill_holes_guided: a workspace of %zu bytes is too small (%zu needed)",
+                workspace_bytes, need);
+  return fill_holes_guided(batch, height, width, in, fmt, top, guide, (long)guide_row_bytes,
+                           batch == 1 ? 0L : (long)guide_image_bytes, scale, range_tab, out, workspace, (hipStream_t)stream);
+}
+
 // ---- per-image range normalisation of depth codes ---------------------------------------------------------------
 int codon_code_range(int32_t batch, int32_t height, int32_t width, const void* codes, int32_t code_bits, int32_t* lo_hi,
                      codon_stream_t stream) {

@@ -167,6 +167,11 @@ size_t fill_holes_workspace_bytes(int h, int w);
 int fill_holes(int B, int h, int w, const void* in, int fmt, const float* tab, int top, void* out, void* workspace,
                hipStream_t stream);
 
+// fill_guided.hip; guide: u8 rows row_bytes apart, images image_bytes apart; range_tab: 256 u16
+size_t fill_guided_workspace_bytes(int h, int w);
+int fill_holes_guided(int B, int h, int w, const void* in, int fmt, int top, const void* guide, long row_bytes, long image_bytes,
+                      int scale, const void* range_tab, void* out, void* workspace, hipStream_t stream);
+
 // stretch.hip; fmt: ST_U8 / ST_U16, dir: ST_STRETCH / ST_UNSTRETCH (stretch_tile.h); n: codes per image
 int code_range(int B, long n, const void* codes, int fmt, int* lo_hi, hipStream_t stream);
 int map_codes(int dir, int B, long n, const void* in, int fmt, int top, const int* lo_hi, void* out, hipStream_t stream);

@@ -31,6 +31,8 @@ from . import CODONNet, CODONNet16, io, metrics
 from .io import check_depth_max, list_pairs, read_depth_plane
 from .upsample import _on_device, code_table, phase_weights
 from .upsample import fill_holes as _fill_holes
+from .upsample import fill_holes_guided as _fill_guided
+from .upsample import FILL_SIGMA, check_fill_sigma
 from .upsample import check_stretch_top, stretch_codes, unstretch_codes
 
 
@@ -75,6 +77,12 @@ def _load_host_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits=8, depth_max
     through io.read_depth_plane and returned AS CODES -- (h,w) uint8, or the u16 bits as int16 -- for codes_to_input; the
     HR size is (h * scale, w * scale), and the guidance and the label are cropped top-left to it.  A smaller guidance or label
     raises ValueError naming the file."""
+    return _load_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits, depth_max)[:5]
+
+
+def _load_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits=8, depth_max=65535, with_guide=False):
+    """_load_host_lr's five items and a sixth, always there: with_guide the cropped guidance AS CODES, (H, W)
+    uint8, for the guided hole filler, else None."""
     px = read_depth_plane(os.path.join(a_lr, f), depth_bits, depth_max)
     py = io.read_gray(os.path.join(a_color, f))
     h, w = px.shape[0] * scale, px.shape[1] * scale
@@ -88,7 +96,8 @@ def _load_host_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits=8, depth_max
             raise ValueError(f"{os.path.join(a_label, f)}: {lab.shape[0]}x{lab.shape[1]}, smaller than the {h}x{w} that "
                              f"{os.path.join(a_lr, f)} gives at x{scale}")
         lab = _codes(lab[:h, :w])
-    return _codes(px), _plane(py[:h, :w], 255, tdt), lab, h, w
+    guide = torch.from_numpy(np.array(py[:h, :w])) if with_guide else None
+    return _codes(px), _plane(py[:h, :w], 255, tdt), lab, h, w, guide
 
 
 def codes_to_input(codes: torch.Tensor, scale: int, tdt, depth_max: int = None) -> torch.Tensor:
@@ -150,7 +159,7 @@ def _pinned_copy(t: torch.Tensor) -> torch.Tensor:
 
 def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None,
              depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None, self_ensemble=False, report=None, fill_holes=False,
-             normalize=False):
+             normalize=False, fill_guided=False, fill_sigma=FILL_SIGMA):
     """The test loop over every image pair.  Returns {"n", "rmse_mean", "ssim_mean", "seconds", "images_per_s"}.
     depth_bits=16: 16-bit depth and label files with codes 0 .. depth_max, outputs through metrics.postprocess_u16 into 16-bit
     PNGs, RMSE (metrics.masked_rmse_u16) in codes times depth_unit, SSIM of label / depth_max against out / depth_max.
@@ -168,11 +177,18 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     (filled) codes' own range [lo, hi] onto [1, top] (upsample.stretch_codes: two launches, the range stays on the device)
     ahead of codes_to_input and maps the post-processed output codes back (upsample.unstretch_codes) before anything else sees
     them, in both loops: the metrics, the report, the error maps and the written files are in the files' own codes, and the
-    label is never remapped."""
+    label is never remapped.
+    fill_guided (needs fill_holes): the filling is upsample.fill_holes_guided instead -- the loader also hands
+    over the guidance as uint8 codes cropped to (h * scale, w * scale), one more upload of that many bytes, and the main stream
+    runs guided fill -> [stretch ->] codes_to_input in both loops.  fill_sigma: the range table's sigma, in guidance codes."""
     if (lr_depth is None) == (input_depth is None):
         raise ValueError("run_loop: exactly one of input_depth and lr_depth")
     if fill_holes and lr_depth is None:
         raise ValueError("run_loop: fill_holes needs lr_depth (only low-resolution code planes are filled)")
+    if fill_guided and not fill_holes:
+        raise ValueError("run_loop: fill_guided needs fill_holes (it chooses how the holes are filled)")
+    if fill_guided:
+        fill_sigma = check_fill_sigma("run_loop", fill_sigma)
     if normalize and lr_depth is None:
         raise ValueError("run_loop: normalize needs lr_depth (input_depth maps are not code planes: only low-resolution codes "
                          "are normalised)")
@@ -195,26 +211,29 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     if normalize:
         check_stretch_top("run_loop: normalize", depth_max if deep else 255)
     if lr_depth is not None:
-        load = lambda f: _load_host_lr(lr_depth, input_color, label, f, tdt, scale, depth_bits, depth_max)      # noqa: E731
-        if fill_holes:
-            to_x = lambda c: codes_to_input(_fill_holes(c, depth_max if deep else None), scale, tdt,           # noqa: E731
-                                            depth_max if deep else None)
+        # every load gives (x, y, label or None, h, w, guidance codes or None); to_x(codes, guide) -- guide is None without fill_guided
+        load = lambda f: _load_lr(lr_depth, input_color, label, f, tdt, scale, depth_bits, depth_max,            # noqa: E731
+                                  with_guide=fill_guided)
+        dm = depth_max if deep else None
+        if fill_guided:
+            fill = lambda c, g: _fill_guided(c, g, scale, fill_sigma, dm)                                      # noqa: E731
+        elif fill_holes:
+            fill = lambda c, g: _fill_holes(c, dm)                                                             # noqa: E731
         else:
-            to_x = lambda c: codes_to_input(c, scale, tdt, depth_max if deep else None)                        # noqa: E731
-        if normalize:                                   # [fill_holes ->] stretch -> codes_to_input; the range rides to `post`
-            dm = depth_max if deep else None
-            fill = (lambda c: _fill_holes(c, dm)) if fill_holes else (lambda c: c)                             # noqa: E731
+            fill = lambda c, g: c                                                                              # noqa: E731
+        to_x = lambda c, g: codes_to_input(fill(c, g), scale, tdt, dm)                                         # noqa: E731
+        if normalize:                                   # [fill ->] stretch -> codes_to_input; the range rides to `post`
             post_codes = post
 
-            def to_x(c):                                # noqa: F811
+            def to_x(c, g):                             # noqa: F811
                 nonlocal lo_hi
-                c, lo_hi = stretch_codes(fill(c), dm)
+                c, lo_hi = stretch_codes(fill(c, g), dm)
                 return codes_to_input(c, scale, tdt, dm)
 
             post = lambda o: unstretch_codes(post_codes(o), lo_hi, dm)                                         # noqa: E731
     else:
-        load = lambda f: _load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max)             # noqa: E731
-        to_x = lambda x: x                                                                                     # noqa: E731
+        load = lambda f: (*_load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max), None)    # noqa: E731
+        to_x = lambda x, g: x                                                                                  # noqa: E731
     if self_ensemble:
         from .ensemble import self_ensemble as _ensemble
         forward = lambda x, y: _ensemble(model, x, y)                                                          # noqa: E731
@@ -261,9 +280,9 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
 
     if not pipelined:
         for f in files:
-            x, y, lab, h, w = load(f)
+            x, y, lab, h, w, g = load(f)
             with torch.no_grad():
-                out = forward(to_x(x.to(dev)), y.to(dev))
+                out = forward(to_x(x.to(dev), g.to(dev) if g is not None else None), y.to(dev))
             out_u8, line = finish(f, out, lab.to(dev) if lab is not None else None, h, w)
             if out_dir:
                 write(os.path.join(out_dir, f), out_u8.cpu().numpy())
@@ -285,10 +304,10 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                 for f in files[k::READERS]:
                     if stop.is_set():
                         break
-                    x, y, lab, h, w = load(f)
-                    host = [_pinned_copy(t) for t in ((x, y) if lab is None else (x, y, lab))]
-                    with torch.cuda.stream(up_s):
-                        devs = [t.to(dev, non_blocking=True) for t in host]
+                    x, y, lab, h, w, g = load(f)
+                    host = [_pinned_copy(t) if t is not None else None for t in (x, y, lab, g)]
+                    with torch.cuda.stream(up_s):             # devs: (x, y, label or None, guidance codes or None)
+                        devs = [t.to(dev, non_blocking=True) if t is not None else None for t in host]
                         ev = torch.cuda.Event()
                         ev.record(up_s)
                     q_in.put((f, devs, host, ev, h, w))          # `host` rides along: pinned sources stay alive until consumed
@@ -342,13 +361,14 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                 f, devs, _host, ev, h, w = item
                 main_s.wait_event(ev)
                 for t in devs:
-                    t.record_stream(main_s)                        # allocated on the upload stream, consumed on this one
+                    if t is not None:
+                        t.record_stream(main_s)                    # allocated on the upload stream, consumed on this one
                 with torch.no_grad():
-                    out = forward(to_x(devs[0]), devs[1])
+                    out = forward(to_x(devs[0], devs[3]), devs[1])
                 out_u8 = post(out[0, 0])
                 h_acc = h_ss = None
                 h_rep, host_err = [], []
-                if len(devs) > 2:                                  # metrics stay on the device; read back one image later
+                if devs[2] is not None:                            # metrics stay on the device; read back one image later
                     lab = devs[2]
                     acc = sqerr(lab, out_u8)
                     ssv = metrics.ssim_dev(unit(lab[:h, :w]), unit(out_u8))
@@ -449,6 +469,13 @@ def main(argv=None):
                     help="with --lr-depth: fill the holes of every low-resolution map on the device by pull-push (the mean of "
                          "the valid pixels up a pyramid, a 9/3/3/1 mix back down; integers, bit-exact) before it is upsampled, "
                          "so that the network sees a dense input; valid pixels are untouched")
+    ap.add_argument("--fill-guided", action="store_true",
+                    help="with --fill-holes: guidance-aware filling -- a hole weighs the pixels it is filled from by how close "
+                         "their guidance (the --input-color image, box-averaged over the pixel) is to its own, so a hole beside "
+                         "an occlusion edge takes its own side's depth instead of a ramp across the edge (integers, bit-exact; "
+                         "DESIGN 12.11)")
+    ap.add_argument("--fill-sigma", type=float, default=None, metavar="CODES",
+                    help=f"with --fill-guided: the sigma of the range weight in guidance codes (default {FILL_SIGMA}, untuned)")
     ap.add_argument("--normalize", action="store_true",
                     help="with --lr-depth: per-image range normalisation -- the valid codes [lo, hi] of every low-resolution "
                          "map (after --fill-holes) are stretched onto [1, top] of the code grid on the device, holes stay "
@@ -493,6 +520,12 @@ def main(argv=None):
         ap.error("exactly one of --input-depth and --lr-depth is required")
     if a.fill_holes and a.lr_depth is None:
         ap.error("--fill-holes needs --lr-depth")
+    if a.fill_guided and not a.fill_holes:
+        ap.error("--fill-guided needs --fill-holes (and with it --lr-depth)")
+    if a.fill_sigma is not None and not a.fill_guided:
+        ap.error("--fill-sigma needs --fill-guided")
+    if a.fill_sigma is not None and not (0.0 < a.fill_sigma < float("inf")):
+        ap.error(f"--fill-sigma {a.fill_sigma} must be positive")
     if a.normalize and a.lr_depth is None:
         ap.error("--normalize needs --lr-depth (it is refused with --input-depth: only low-resolution code planes are normalised)")
     if a.ema and not a.weights:
@@ -520,7 +553,9 @@ def main(argv=None):
                  depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit,
                  **({"self_ensemble": True} if a.self_ensemble else {}), **({"report": report} if report else {}),
                  **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}),
-                 **({"fill_holes": True} if a.fill_holes else {}), **({"normalize": True} if a.normalize else {}))
+                 **({"fill_holes": True} if a.fill_holes else {}), **({"normalize": True} if a.normalize else {}),
+                 **({"fill_guided": True, "fill_sigma": FILL_SIGMA if a.fill_sigma is None else a.fill_sigma}
+                    if a.fill_guided else {}))
     print(r["n"])
     if a.label and r["n"]:
         print(r["rmse_mean"], r["ssim_mean"])

@@ -49,6 +49,8 @@ from .metrics import report_tokens
 from .upsample import (_fill_launch, _on_device, code_table, down_weights, gauss_table, lut16,      # noqa: F401 (lut16: for
                        phase_weights, u8_lut)                                                      # importers)
 from .upsample import fill_holes as _fill_holes
+from .upsample import fill_holes_guided as _fill_guided
+from .upsample import FILL_SIGMA, check_fill_sigma
 from .upsample import check_stretch_top, code_range, stretch_codes
 
 DTYPES = {"bf16": torch.bfloat16, "f32": None}
@@ -70,6 +72,8 @@ SENSOR_DEFAULTS = {"sensor_noise": None, "sensor_noise_quad": None, "sensor_drop
                    "sensor_edge_threshold": None, "sensor_seed": None}
 # the same for --fill-holes: a resume key with default False, written by a run that sets it ONLY
 FILL_DEFAULTS = {"fill_holes": False}
+# the same for --fill-guided and --fill-sigma: resume keys with these defaults, written by a run with --fill-guided ONLY
+GUIDED_DEFAULTS = {"fill_guided": False, "fill_sigma": 10.0}
 # the same for --normalize: a resume key with default False, written by a run that sets it ONLY
 NORM_DEFAULTS = {"normalize": False}
 MAX_REDRAWS = 64                                    # draw(min_valid=): per sample, before it gives up
@@ -108,6 +112,8 @@ class TrainSet:
     `fill_holes` (needs lr_dir): once the pool is on the device, the low-resolution plane of every record is
     filled by pull-push from the WHOLE file (upsample.fill_holes, one call per record), so that a step costs nothing extra and x
     stays the crop of what `infer --lr-depth --fill-holes` builds from that file; the target plane is untouched.
+    `fill_guided` (needs fill_holes): that filling is upsample.fill_holes_guided with the record's own guide plane,
+    read in place (row stride W), and the range table of `fill_sigma` -- as `infer --lr-depth --fill-holes --fill-guided` does it.
     `normalize` (excludes label_dir): once the pool is on the device, and after the filling, every record's code
     planes are stretched IN PLACE (upsample.stretch_codes) so that a step costs nothing extra.  With lr_dir the range is that of
     the (filled) low-resolution plane of the WHOLE file, as `infer --lr-depth --normalize` takes it; it stretches that plane
@@ -115,7 +121,7 @@ class TrainSet:
 
     def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None, label_dir: str = None, depth_bits: int = 8,
                  depth_max: int = 65535, lr_dir: str = None, scale: int = None, fill_holes: bool = False,
-                 normalize: bool = False):
+                 normalize: bool = False, fill_guided: bool = False, fill_sigma: float = FILL_SIGMA):
         if depth_bits not in (8, 16):
             raise ValueError(f"TrainSet: depth_bits {depth_bits!r} (8 or 16)")
         check_depth_max(depth_max)
@@ -124,6 +130,10 @@ class TrainSet:
         if fill_holes and lr_dir is None:
             raise ValueError("TrainSet: fill_holes needs lr_dir (only low-resolution code planes are filled)")
         self.fill_holes = bool(fill_holes)
+        if fill_guided and not fill_holes:
+            raise ValueError("TrainSet: fill_guided needs fill_holes (it chooses how the holes are filled)")
+        self.fill_guided = bool(fill_guided)
+        self.fill_sigma = check_fill_sigma("TrainSet", fill_sigma) if fill_guided else FILL_SIGMA
         if normalize:
             if label_dir is not None:
                 raise ValueError("TrainSet: normalize and label_dir exclude each other (a label plane has no range of its own "
@@ -183,11 +193,16 @@ class TrainSet:
         if self.fill_holes:
             wide = depth_bits // 8
             for off, (h, w) in zip(self.offsets.tolist(), self.sizes.tolist()):
-                lo = off + record_layout(depth_bits, False, self.lr_scale, h, w)["lr"]
+                lay = record_layout(depth_bits, False, self.lr_scale, h, w)
+                lo = off + lay["lr"]
                 lh, lw = h // self.lr_scale, w // self.lr_scale
                 plane = self.pool[lo:lo + wide * lh * lw]
                 plane = (plane.view(torch.int16) if deep else plane).view(lh, lw)
-                plane.copy_(_fill_holes(plane, self.depth_max if deep else None))
+                if self.fill_guided:                    # the record's own guide plane, in place
+                    guide = self.pool[off + lay["guide"]:off + lay["guide"] + h * w].view(h, w)
+                    plane.copy_(_fill_guided(plane, guide, self.lr_scale, self.fill_sigma, self.depth_max if deep else None))
+                else:
+                    plane.copy_(_fill_holes(plane, self.depth_max if deep else None))
         if self.normalize:
             wide, dm = depth_bits // 8, self.depth_max if deep else None
             for off, (h, w) in zip(self.offsets.tolist(), self.sizes.tolist()):
@@ -484,14 +499,14 @@ def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, 
 def load_resume(path: str, args: dict) -> dict:
     """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype, or with
     other options that change the trajectory (RESUME_KEYS, DEPTH_DEFAULTS', DEGRADE_DEFAULTS', LR_DEFAULTS' and
-    SENSOR_DEFAULTS', FILL_DEFAULTS' and NORM_DEFAULTS' keys; a key the checkpoint's args lack compares as its default)."""
+    SENSOR_DEFAULTS', FILL_DEFAULTS', GUIDED_DEFAULTS' and NORM_DEFAULTS' keys; a key the checkpoint's args lack compares as its default)."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(ck, dict) or not all(k in ck for k in ("epoch", "model", "optimizer", "rng", "args")):
         raise ValueError(f"--resume {path}: not a codon_amd.train checkpoint (use --weights to start from other weights)")
     absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS, **LR_DEFAULTS, **SENSOR_DEFAULTS, **FILL_DEFAULTS,
-              **NORM_DEFAULTS}
+              **GUIDED_DEFAULTS, **NORM_DEFAULTS}
     keys = (RESUME_KEYS + tuple(DEPTH_DEFAULTS) + tuple(DEGRADE_DEFAULTS) + tuple(LR_DEFAULTS) + tuple(SENSOR_DEFAULTS) +
-            tuple(FILL_DEFAULTS) + tuple(NORM_DEFAULTS))
+            tuple(FILL_DEFAULTS) + tuple(GUIDED_DEFAULTS) + tuple(NORM_DEFAULTS))
     was, now = ({k: a.get(k, absent.get(k)) for k in keys} for a in (ck["args"], args))
     bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in keys if was[k] != now[k]]
     if bad:
@@ -505,7 +520,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         args: dict = None, time_synth: bool = False, emit=print, clip_norm: float = None, skip_nonfinite: bool = False,
         ema_decay: float = None, lr_schedule: str = "constant", warmup: int = 0, lr_min: float = 0.0, lr_steps: int = None,
         grad_hook=None, mask_holes: bool = False, min_valid: float = 0.0, degrade_holes: bool = False,
-        sensor: SensorModel = None, fill_holes: bool = False, normalize: bool = False) -> dict:
+        sensor: SensorModel = None, fill_holes: bool = False, normalize: bool = False, fill_guided: bool = False,
+        fill_sigma: float = FILL_SIGMA) -> dict:
     """Train `model` (fp32 parameters on the pool's device) from step start_step + 1 to step `steps`.
     val:   {"depth", "color", "label", "every"} -- rank 0 runs infer.run_loop every `every` steps and prints the means;
     ckpt:  {"path", "every"} -- rank 0 saves every `every` steps and after the last one;
@@ -529,6 +545,10 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     fill_holes: synthesize's hole filling; needs degrade_holes, or a TrainSet of low-resolution maps built with
            fill_holes (one built without refuses it, and one built with it refuses a fit without); the checkpoint's args gain
            fill_holes=True.  A `val` dict with "lr_depth" and "fill_holes" validates on filled maps.
+    fill_guided, fill_sigma: guidance-aware filling is a property of a TrainSet of low-resolution maps, filled
+           once, when it is built: fit and the TrainSet must agree on both (either way round is refused); the checkpoint's args
+           gain fill_guided=True and fill_sigma.  A `val` dict with "lr_depth", "fill_holes" and "fill_guided" (and
+           "fill_sigma") validates as `infer --lr-depth --fill-holes --fill-guided` does.
     normalize: per-image range normalisation is a property of the TrainSet, whose pool is stretched once, when it
            is built: fit and the TrainSet must agree on it (either way round is refused); the checkpoint's args gain
            normalize=True.  A `val` dict with "lr_depth" and "normalize" validates as `infer --lr-depth --normalize` does.
@@ -545,6 +565,13 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     if bool(fill_holes) != trainset.fill_holes if trainset.has_lr else (fill_holes and not degrade_holes):
         raise ValueError("fit: fill_holes needs degrade_holes, or a TrainSet of low-resolution maps -- and that TrainSet must "
                          "have been built with the same fill_holes (its pool is filled once, when it is built)")
+    if fill_guided:
+        fill_sigma = check_fill_sigma("fit", fill_sigma)
+    if bool(fill_guided) != trainset.fill_guided or (fill_guided and fill_sigma != trainset.fill_sigma):
+        raise ValueError(f"fit: fill_guided {bool(fill_guided)!r}" + (f" (fill_sigma {fill_sigma!r})" if fill_guided else "") +
+                         f" with a TrainSet built with fill_guided {trainset.fill_guided!r}" +
+                         (f" (fill_sigma {trainset.fill_sigma!r})" if trainset.fill_guided else "") +
+                         " -- only a TrainSet of low-resolution maps is filled with guidance, once, when it is built")
     if bool(normalize) != trainset.normalize:
         raise ValueError(f"fit: normalize {bool(normalize)!r} with a TrainSet built with normalize {trainset.normalize!r} (its "
                          "pool is stretched once, when it is built)")
@@ -581,6 +608,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         args.update(sensor.args())
     if fill_holes:                                  # only then, likewise
         args.update(fill_holes=True)
+    if fill_guided:                                 # only then, likewise
+        args.update(fill_guided=True, fill_sigma=float(fill_sigma))
     if normalize:                                   # only then, likewise
         args.update(normalize=True)
     if trainset.depth_bits == 16:                   # only then: an 8-bit checkpoint keeps the keys it always had
@@ -671,6 +700,8 @@ def validate(model, dev, val: dict, emit=print) -> dict:
                 deep.update(lr_depth=val["lr_depth"], scale=val["scale"])
                 if val.get("fill_holes"):           # filled as infer --lr-depth --fill-holes fills them
                     deep.update(fill_holes=True)
+                if val.get("fill_guided"):          # with the guidance's say
+                    deep.update(fill_guided=True, fill_sigma=val.get("fill_sigma", FILL_SIGMA))
                 if val.get("normalize"):            # stretched and mapped back as infer --lr-depth --normalize does
                     deep.update(normalize=True)
             if val.get("report") is not None:       # the evaluation suite of infer --report
@@ -725,6 +756,13 @@ def parse_args(argv=None):
                     help="fill the holes of the low-resolution maps on the device by pull-push before they are upsampled, as "
                          "`codon_amd.infer --lr-depth --fill-holes` does: the maps of --train-lr-depth (once, when they are "
                          "loaded) or the synthetic ones of --degrade-holes (every step), and those of --val-lr-depth")
+    ap.add_argument("--fill-guided", action="store_true",
+                    help="with --train-lr-depth --fill-holes: guidance-aware filling, as `codon_amd.infer --lr-depth --fill-holes "
+                         "--fill-guided` does it -- every record's low-resolution map is filled once, when the data is loaded, "
+                         "with the record's own guidance plane deciding which side of an edge a hole is filled from (DESIGN "
+                         "12.11); also applies to --val-lr-depth.  Refused with --degrade-holes")
+    ap.add_argument("--fill-sigma", type=float, default=None, metavar="CODES",
+                    help=f"with --fill-guided: the sigma of the range weight in guidance codes (default {FILL_SIGMA}, untuned)")
     ap.add_argument("--normalize", action="store_true",
                     help="per-image range normalisation, as `codon_amd.infer --lr-depth --normalize` does it: when the data is "
                          "loaded, the valid codes [lo, hi] of every map are stretched onto [1, top] of the code grid on the "
@@ -791,6 +829,16 @@ def parse_args(argv=None):
         ap.error("--train-lr-depth and --degrade-holes exclude each other (nothing is degraded)")
     if a.fill_holes and a.train_lr_depth is None and not a.degrade_holes:
         ap.error("--fill-holes needs --train-lr-depth or --degrade-holes (the unmasked degradation has no holes to fill)")
+    if a.fill_guided and a.degrade_holes:
+        ap.error("--fill-guided is refused with --degrade-holes: the synthetic path holds its guidance as fp32 D4 crops, not as "
+                 "the codes of a whole image (only the real maps of --train-lr-depth and --val-lr-depth are filled with guidance)")
+    if a.fill_guided and not (a.fill_holes and a.train_lr_depth is not None):
+        ap.error("--fill-guided needs --train-lr-depth --fill-holes")
+    if a.fill_sigma is not None and not a.fill_guided:
+        ap.error("--fill-sigma needs --fill-guided")
+    if a.fill_sigma is not None and not (0.0 < a.fill_sigma < float("inf")):
+        ap.error(f"--fill-sigma {a.fill_sigma} must be positive")
+    a.fill_sigma = FILL_SIGMA if a.fill_sigma is None else float(a.fill_sigma)
     if a.normalize and a.train_label is not None:
         ap.error("--normalize and --train-label exclude each other (a label plane has no range of its own to be stretched by)")
     given = {n: getattr(a, "sensor_" + n) for n in ("noise", "noise_quad", "dropout", "edge_dropout", "edge_threshold")}
@@ -864,6 +912,7 @@ def run_args(a) -> dict:
             **({"train_lr_depth": True} if a.train_lr_depth is not None else {}),
             **(sensor.args() if sensor is not None else {}),
             **({"fill_holes": True} if a.fill_holes else {}),
+            **({"fill_guided": True, "fill_sigma": a.fill_sigma} if a.fill_guided else {}),
             **({"normalize": True} if a.normalize else {})}
 
 
@@ -888,6 +937,7 @@ def main(argv=None, emit=print) -> dict:
     ts = TrainSet(a.train_depth, a.train_color, dev, crop=a.crop, label_dir=a.train_label, depth_bits=a.depth_bits,
                   depth_max=a.depth_max, **({"lr_dir": a.train_lr_depth, "scale": a.scale} if a.train_lr_depth else {}),
                   **({"fill_holes": True} if a.fill_holes and a.train_lr_depth else {}),
+                  **({"fill_guided": True, "fill_sigma": a.fill_sigma} if a.fill_guided else {}),
                   **({"normalize": True} if a.normalize else {}))
     torch.manual_seed(a.seed)
     model = (CODONNet16 if a.scale == 16 else CODONNet)()
@@ -911,6 +961,7 @@ def main(argv=None, emit=print) -> dict:
             "depth_bits": a.depth_bits, "depth_max": a.depth_max} if a.val_depth or a.val_lr_depth else None)
     if a.val_lr_depth:
         val.update(lr_depth=a.val_lr_depth, scale=a.scale, **({"fill_holes": True} if a.fill_holes else {}),
+                   **({"fill_guided": True, "fill_sigma": a.fill_sigma} if a.fill_guided else {}),
                    **({"normalize": True} if a.normalize else {}))
     if val is not None and a.val_report_params is not None:
         val.update(report=a.val_report_params)
@@ -918,6 +969,8 @@ def main(argv=None, emit=print) -> dict:
     kw = {"sensor": sensor_of(a)} if sensor_of(a) is not None else {}      # without a model fit is called as ever
     if a.fill_holes:
         kw["fill_holes"] = True
+    if a.fill_guided:
+        kw.update(fill_guided=True, fill_sigma=a.fill_sigma)
     if a.normalize:
         kw["normalize"] = True
     res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,

@@ -188,6 +188,112 @@ def fill_holes(codes: torch.Tensor, depth_max: int = None) -> torch.Tensor:
     return out
 
 
+# ---- guidance-aware pull-push hole filling ---------------------------------------------------------------------
+
+FILL_SIGMA = 10.0           # the default range sigma in guidance codes: the prototype's value, untuned
+
+_guided_ws = None           # guards.PerStream -> uint8 workspace of the (device, stream, thread)
+_guided_held: list = []     # workspaces made under a hipGraph capture
+
+
+def check_fill_sigma(who: str, sigma) -> float:
+    """sigma as a float; anything but a finite positive number is refused by name"""
+    try:
+        s = float(sigma)
+    except (TypeError, ValueError):
+        s = float("nan")
+    if not (s > 0.0 and s != float("inf")):
+        raise ValueError(f"{who}: fill_sigma {sigma!r} (a positive number of guidance codes)")
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def _range_table(sigma: float) -> np.ndarray:
+    d = np.arange(256, dtype=np.float64)
+    t = np.maximum(1.0, np.rint(256.0 * np.exp(-d * d / (2.0 * sigma * sigma)))).astype(np.uint16)
+    t.setflags(write=False)
+    return t
+
+
+def range_table(sigma: float = FILL_SIGMA, device=None):
+    """The range table of the guided hole filler: T[d] = max(1, rint(256 exp(-d^2 / (2 sigma^2)))) for the
+    guidance differences d = 0 .. 255, float64 on the host -- a (256,) read-only numpy uint16 array, T[0] = 256, never rising,
+    never below 1.  With `device` the cached copy on that device instead (the u16 bits as a (256,) int16 tensor)."""
+    s = check_fill_sigma("range_table", sigma)
+    if device is None:
+        return _range_table(s)
+    return _on_device(("range", s), lambda: _range_table(s).view(np.int16).copy(), torch.device(device))
+
+
+def fill_holes_guided(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigma: float = FILL_SIGMA, depth_max: int = None,
+                      _table: torch.Tensor = None) -> torch.Tensor:
+    """fill_holes with the guidance image's say: a hole weighs each of the plain filler's four parents by the
+    range table of the difference between its own guidance and the guidance attached to the parent, so that a hole beside an
+    occlusion edge is filled from its own side.  A new tensor of the codes' shape and dtype; no argument is modified.
+    codes: (h,w) or (B,h,w) uint8 codes, or the bits of u16 codes as int16 / uint16, code 0 a hole (depth_max: 255 for uint8,
+    default 65535 otherwise).  guide: (H,W) or (B,H,W) uint8 on the same device with H >= h * scale, W >= w * scale and unit
+    stride along a row; its top-left (h * scale, w * scale) is read IN PLACE through its row and image strides (a plane of a
+    training-pool record, the corner of a larger image).  scale: 4, 8 or 16.  sigma: of range_table, in guidance codes.
+    A constant guide gives fill_holes' bits.  _table is for the tests alone (a constant table, which also gives fill_holes'
+    bits): a (256,) int16 / uint16 device tensor used instead of range_table(sigma); its entries are NOT checked -- nothing
+    reads the device here -- and an entry outside 1 .. 256 makes the output undefined (a 0 can zero a sum of weights, which
+    the kernels divide by).  Valid pixels come back bit for bit, a map without a valid pixel comes back unchanged, and
+    a hole never takes a value above the largest valid code.  Integer arithmetic, bit-exact: tests/guided_fill_ref.py.  One
+    launch up to 64 x 64, three beyond; no host synchronisation."""
+    global _guided_ws
+    from .guards import PerStream
+    who = "fill_holes_guided"
+    if codes.dim() not in (2, 3) or codes.dtype not in (torch.uint8, torch.int16, torch.uint16):
+        raise RuntimeError(f"{who} expects (h,w) or (B,h,w) uint8 codes, or u16 codes as int16 / uint16")
+    if codes.dtype == torch.uint8:
+        if depth_max not in (None, 255):
+            raise ValueError(f"{who}: depth_max {depth_max!r} with 8-bit codes")
+        fmt, top = L.FILL_U8, 255
+    else:
+        fmt, top = L.FILL_U16, 65535 if depth_max is None else depth_max
+    check_depth_max(top)
+    if scale not in (4, 8, 16):
+        raise ValueError(f"{who}: scale {scale!r} (4, 8 or 16)")
+    src = codes.contiguous()
+    dev = ops._dev(src)
+    h, w = src.shape[-2:]
+    B = src.numel() // (h * w) if h * w else 0
+    if B < 1:
+        raise ValueError(f"{who}: an empty map {tuple(codes.shape)}")
+    if guide.dtype != torch.uint8 or guide.dim() != codes.dim() or guide.device != src.device:
+        raise RuntimeError(f"{who} expects a uint8 guide on the codes' device, (H,W) for (h,w) codes and (B,H,W) for (B,h,w) codes")
+    if guide.dim() == 3 and guide.shape[0] != B:
+        raise ValueError(f"{who}: {guide.shape[0]} guidance images for {B} maps")
+    if guide.shape[-2] < h * scale or guide.shape[-1] < w * scale:
+        raise ValueError(f"{who}: a {guide.shape[-2]}x{guide.shape[-1]} guide, smaller than the {h * scale}x{w * scale} that a "
+                         f"{h}x{w} map gives at x{scale}")
+    if guide.stride(-1) != 1 and guide.shape[-1] > 1:
+        raise ValueError(f"{who}: the guide needs unit stride along a row (stride {guide.stride(-1)})")
+    row_bytes = guide.stride(-2) if guide.shape[-2] > 1 else max(guide.shape[-1], guide.stride(-2))
+    image_bytes = guide.stride(0) if guide.dim() == 3 and B > 1 else 0
+    if _table is None:
+        table = range_table(sigma, dev)
+    elif (not isinstance(_table, torch.Tensor) or _table.shape != (256,) or _table.dtype not in (torch.int16, torch.uint16)
+          or _table.device != src.device or not _table.is_contiguous()):
+        raise RuntimeError(f"{who}: _table must be a contiguous (256,) int16 / uint16 tensor on the codes' device")
+    else:
+        table = _table
+    lib = L.load()
+    need = B * lib.codon_fill_guided_workspace_bytes(h, w)
+    if need == 0:
+        raise ValueError(f"{who}: a {h}x{w} plane (1..4096 each way)")
+    out = torch.empty_like(src)
+    if _guided_ws is None:
+        _guided_ws = PerStream()
+    P_ = C.c_void_p
+    with torch.cuda.device(dev):
+        ws = _guided_ws.get(dev, lambda capturing: torch.empty(need, dtype=torch.uint8, device=dev), need=need, hold=_guided_held)
+        L.check(lib.codon_fill_holes_guided(B, h, w, P_(src.data_ptr()), fmt, int(top), P_(guide.data_ptr()), row_bytes,
+                                            image_bytes, scale, P_(table.data_ptr()), P_(out.data_ptr()), P_(ws.data_ptr()),
+                                            ws.numel(), ops._stream(dev)), who)
+    return out
+
+
 # ---- per-image range normalisation of depth codes (DESIGN 12.10) --------------------------------------------------------------
 
 def _code_planes(who: str, codes: torch.Tensor, depth_max):

@@ -841,6 +841,34 @@ size_t codon_fill_holes_workspace_bytes(int32_t height, int32_t width);
 int codon_fill_holes(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, const float* tab, int32_t top,
                      void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream);
 
+/* ---- guidance-aware (joint) pull-push hole filling (codon_amd.upsample.fill_holes_guided) -------------------
+ * No reference counterpart: a DEFINITION on top of codon_fill_holes', in codon_amd/csrc/fill_guided.hip and
+ * fill_guided_tile.h, restated in numpy in tests/guided_fill_ref.py, equal bits required.  Integers only.
+ *
+ * The levels, the pull of the codes (V) and the four parents of a hole with their base weights B = 9, 3, 3, 1 are
+ * codon_fill_holes'.  guide: u8, image b at guide + b * guide_image_bytes, row r at + r * guide_row_bytes; its top-left
+ * (height * scale) x (width * scale) is used.  Guidance pyramid: G_0 the scale x scale box mean (2 S + s^2) / (2 s^2),
+ * G_{k+1} = (2 S + n) / (2 n) over the n children inside level k.  Attached guidance: A_0 = G_0 at valid pixels,
+ * A_{k+1} = (2 S_A + n) / (2 n) over the n valid children that entered V_{k+1}.  Push: a hole at (y, x) of level k weighs
+ * parent p by w_p = B_p * range_tab[|G_k(y, x) - A^(p)|], A^(p) = A_{k+1}(p) where V_{k+1}(p) is valid, else G_{k+1}(p), and
+ * takes (2 sum w_p F_{k+1}(p) + sum w_p) / (2 sum w_p).  range_tab: 256 u16 ON THE DEVICE, each 1 .. 256 (the caller's
+ * duty: 16 <= sum w_p <= 4096 keeps everything inside 32 bits); a constant table, or a constant guide, gives
+ * codon_fill_holes' bits.  Valid codes come back as they were and no filled value exceeds the largest valid code.
+ *
+ * fmt: CODON_FILL_U8 or CODON_FILL_U16.  in, out: (batch, height, width), contiguous; out must not be in.
+ * codon_fill_guided_workspace_bytes: HOST ONLY -- the bytes ONE image takes (V, A and G of levels 1 .. K and G_0), a
+ * multiple of 16; 0 for a height or width outside 1 .. 4096.  workspace: batch times that, 16-byte aligned, private to the
+ * stream.  Planes up to 64 x 64: one launch; larger: three.  The launches depend on (batch, height, width, scale) alone; no
+ * atomics, no host synchronisation.  Refused on the host, before any HIP call: null pointers, an fmt other than the two,
+ * batch outside 1 .. 65535, height or width outside 1 .. 4096, top outside 1 .. 65535 or not 255 for u8 codes, a scale other
+ * than 4, 8, 16, guide_row_bytes < width * scale, guide_image_bytes < height * scale * guide_row_bytes with batch > 1,
+ * out == in, a u16 plane or a table that is not 2-byte aligned, a workspace that is not 16-byte aligned, a workspace that is
+ * too small. */
+size_t codon_fill_guided_workspace_bytes(int32_t height, int32_t width);
+int codon_fill_holes_guided(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top,
+                            const uint8_t* guide, int64_t guide_row_bytes, int64_t guide_image_bytes, int32_t scale,
+                            const uint16_t* range_tab, void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream);
+
 /* ---- per-image range normalisation of depth codes (codon_amd.upsample.code_range / stretch_codes /
  * unstretch_codes) ---------------------------------------------------------------------------------------------------------
  * No reference counterpart (its data was normalised offline, if at all): a DEFINITION, in codon_amd/csrc/stretch.hip and
