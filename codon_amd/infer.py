@@ -29,11 +29,8 @@ import torch
 
 from . import CODONNet, CODONNet16, io, metrics
 from .io import check_depth_max, list_pairs, read_depth_plane
-from .upsample import _on_device, code_table, phase_weights
-from .upsample import fill_holes as _fill_holes
-from .upsample import fill_holes_guided as _fill_guided
-from .upsample import FILL_SIGMA, check_fill_sigma
-from .upsample import check_stretch_top, stretch_codes, unstretch_codes
+from .prep import LrPrep, add_prep_args, prep_of
+from .upsample import FILL_SIGMA, _code_planes, _on_device, code_table, phase_weights, unstretch_codes
 
 
 def _load_host(a_depth, a_color, a_label, f, tdt, depth_bits=8, depth_max=65535):
@@ -109,32 +106,19 @@ def codes_to_input(codes: torch.Tensor, scale: int, tdt, depth_max: int = None) 
     from . import _lib as L
     from . import ops
     import ctypes as C
-    if codes.dim() == 2:
-        codes = codes[None]
-    if codes.dim() != 3 or codes.dtype not in (torch.uint8, torch.int16, torch.uint16):
-        raise RuntimeError("codes_to_input expects (h,w) or (B,h,w) uint8 codes, or u16 codes as int16 / uint16")
+    codes, B, h, w, bits, top = _code_planes("codes_to_input", codes, depth_max)
     if scale not in (4, 8, 16):
         raise ValueError(f"codes_to_input: scale {scale!r} (4, 8 or 16)")
     if tdt not in _ABI_DTYPE:
         raise ValueError(f"codes_to_input: dtype {tdt!r} (float32, float16 or bfloat16)")
-    lib = L.load()
-    codes = codes.contiguous()
     dev = ops._dev(codes)
-    if codes.dtype == torch.uint8:
-        if depth_max not in (None, 255):
-            raise ValueError(f"codes_to_input: depth_max {depth_max!r} with 8-bit codes")
-        bits = 8
-    else:
-        bits, depth_max = 16, 65535 if depth_max is None else depth_max
-        check_depth_max(depth_max)
-    lut, top = code_table(bits, depth_max, dev)
+    lut, top = code_table(bits, top, dev)
     wt = _on_device(("up", scale), lambda: phase_weights(scale), dev)
-    B, h, w = codes.shape
     out = torch.empty((B, 1, h * scale, w * scale), dtype=tdt, device=dev)
     P_ = C.c_void_p
     with ops._on(dev):
-        L.check(lib.codon_lr_codes_to_input(B, h, w, scale, P_(codes.data_ptr()), bits, P_(lut.data_ptr()), top,
-                                            P_(wt.data_ptr()), P_(out.data_ptr()), _ABI_DTYPE[tdt], ops._stream(dev)),
+        L.check(L.load().codon_lr_codes_to_input(B, h, w, scale, P_(codes.data_ptr()), bits, P_(lut.data_ptr()), top,
+                                                 P_(wt.data_ptr()), P_(out.data_ptr()), _ABI_DTYPE[tdt], ops._stream(dev)),
                 "lr_codes_to_input")
     return out
 
@@ -171,69 +155,52 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     "error_maps": a directory or None} -- one more launch per image (metrics.depth_errors); every line gains the key=value
     tokens of metrics.depth_report (mad, rmse and max in codes times depth_unit), the error maps are written under the images'
     names, and the result gains "reports" (the per-image dicts, with "file") and "report_means" (metrics.report_means).
-    fill_holes (needs lr_depth): the main stream fills the holes of the uploaded codes by pull-push
-    (upsample.fill_holes) ahead of codes_to_input, in both loops -- the network sees a dense input.
-    normalize (needs lr_depth): per-image range normalisation on the code grid.  The main stream stretches the
-    (filled) codes' own range [lo, hi] onto [1, top] (upsample.stretch_codes: two launches, the range stays on the device)
-    ahead of codes_to_input and maps the post-processed output codes back (upsample.unstretch_codes) before anything else sees
-    them, in both loops: the metrics, the report, the error maps and the written files are in the files' own codes, and the
-    label is never remapped.
-    fill_guided (needs fill_holes): the filling is upsample.fill_holes_guided instead -- the loader also hands
-    over the guidance as uint8 codes cropped to (h * scale, w * scale), one more upload of that many bytes, and the main stream
-    runs guided fill -> [stretch ->] codes_to_input in both loops.  fill_sigma: the range table's sigma, in guidance codes."""
+    fill_holes, fill_guided, fill_sigma, normalize (need lr_depth): the preparation of the uploaded codes ahead of
+    codes_to_input, prep.LrPrep's fields, run on the main stream in both loops.  fill_holes: the holes
+    are filled by pull-push -- the network sees a dense input; fill_guided: by upsample.fill_holes_guided under
+    fill_sigma, for which the loader also hands over the guidance as uint8 codes cropped to (h * scale, w * scale), one more
+    upload of that many bytes.  normalize: the (filled) codes' own range [lo, hi] is stretched onto [1, top], the
+    range stays on the device, and the post-processed output codes are mapped back (upsample.unstretch_codes) before anything
+    else sees them: the metrics, the report, the error maps and the written files are in the files' own codes, and the label
+    is never remapped."""
     if (lr_depth is None) == (input_depth is None):
         raise ValueError("run_loop: exactly one of input_depth and lr_depth")
-    if fill_holes and lr_depth is None:
-        raise ValueError("run_loop: fill_holes needs lr_depth (only low-resolution code planes are filled)")
-    if fill_guided and not fill_holes:
-        raise ValueError("run_loop: fill_guided needs fill_holes (it chooses how the holes are filled)")
-    if fill_guided:
-        fill_sigma = check_fill_sigma("run_loop", fill_sigma)
-    if normalize and lr_depth is None:
-        raise ValueError("run_loop: normalize needs lr_depth (input_depth maps are not code planes: only low-resolution codes "
-                         "are normalised)")
-    if lr_depth is not None and scale not in (4, 8, 16):
-        raise ValueError(f"run_loop: lr_depth needs scale 4, 8 or 16 (got {scale!r})")
-    files = list_pairs(lr_depth or input_depth, input_color) if files is None else files
     if depth_bits not in (8, 16):
         raise ValueError(f"run_loop: depth_bits {depth_bits!r} (8 or 16)")
     deep = depth_bits == 16
     if deep:
         check_depth_max(depth_max)
-        post = lambda o: metrics.postprocess_u16(o, depth_max)                                   # noqa: E731
+    prep = LrPrep.checked("run_loop", fill_holes, fill_guided, fill_sigma, normalize, lr=("lr_depth", lr_depth is not None),
+                          top=depth_max if deep else 255)
+    if lr_depth is not None and scale not in (4, 8, 16):
+        raise ValueError(f"run_loop: lr_depth needs scale 4, 8 or 16 (got {scale!r})")
+    files = list_pairs(lr_depth or input_depth, input_color) if files is None else files
+    if deep:
+        post_codes = lambda o: metrics.postprocess_u16(o, depth_max)                             # noqa: E731
         sqerr, write, top = metrics.masked_sqerr_u16_dev, io.write_depth16, float(depth_max)
         unit = lambda t: metrics.codes_to_float(t) / top                                         # noqa: E731
     else:
-        post, sqerr, write = metrics.postprocess_u8, metrics.masked_sqerr_dev, io.write_gray
+        post_codes, sqerr, write = metrics.postprocess_u8, metrics.masked_sqerr_dev, io.write_gray
         unit = lambda t: t.float() / 255                                                         # noqa: E731
     scale_rm = float(depth_unit) if deep else None
-    lo_hi = None                                        # normalize: the range of the image in flight, on the device
-    if normalize:
-        check_stretch_top("run_loop: normalize", depth_max if deep else 255)
+    dm = depth_max if deep else None                    # as the upsample functions take it
+    # every load gives (x, y, label or None, h, w, guidance codes or None), guidance codes with fill_guided only; to_x(x or codes,
+    # guidance codes) gives (the depth input, the range it was stretched by or None), and that range rides to post
     if lr_depth is not None:
-        # every load gives (x, y, label or None, h, w, guidance codes or None); to_x(codes, guide) -- guide is None without fill_guided
         load = lambda f: _load_lr(lr_depth, input_color, label, f, tdt, scale, depth_bits, depth_max,            # noqa: E731
-                                  with_guide=fill_guided)
-        dm = depth_max if deep else None
-        if fill_guided:
-            fill = lambda c, g: _fill_guided(c, g, scale, fill_sigma, dm)                                      # noqa: E731
-        elif fill_holes:
-            fill = lambda c, g: _fill_holes(c, dm)                                                             # noqa: E731
-        else:
-            fill = lambda c, g: c                                                                              # noqa: E731
-        to_x = lambda c, g: codes_to_input(fill(c, g), scale, tdt, dm)                                         # noqa: E731
-        if normalize:                                   # [fill ->] stretch -> codes_to_input; the range rides to `post`
-            post_codes = post
+                                  with_guide=prep.fill_guided)
 
-            def to_x(c, g):                             # noqa: F811
-                nonlocal lo_hi
-                c, lo_hi = stretch_codes(fill(c, g), dm)
-                return codes_to_input(c, scale, tdt, dm)
-
-            post = lambda o: unstretch_codes(post_codes(o), lo_hi, dm)                                         # noqa: E731
+        def to_x(c, g):                                 # [fill ->] [stretch ->] codes_to_input
+            c, lo_hi = prep.apply(c, g, scale, dm)
+            return codes_to_input(c, scale, tdt, dm), lo_hi
     else:
         load = lambda f: (*_load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max), None)    # noqa: E731
-        to_x = lambda x, g: x                                                                                  # noqa: E731
+        to_x = lambda x, g: (x, None)                                                                          # noqa: E731
+
+    def post(o, lo_hi):
+        o = post_codes(o)
+        return o if lo_hi is None else unstretch_codes(o, lo_hi, dm)
+
     if self_ensemble:
         from .ensemble import self_ensemble as _ensemble
         forward = lambda x, y: _ensemble(model, x, y)                                                          # noqa: E731
@@ -260,9 +227,9 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     rm_sum = ss_sum = 0.0
     n = 0
 
-    def finish(f, out, lab, h, w):
+    def finish(f, out, lo_hi, lab, h, w):
         nonlocal rm_sum, ss_sum, n
-        out_u8 = post(out[0, 0])
+        out_u8 = post(out[0, 0], lo_hi)
         line = f
         if lab is not None:
             s_, c_ = (int(v) for v in sqerr(lab, out_u8).cpu())
@@ -282,8 +249,9 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
         for f in files:
             x, y, lab, h, w, g = load(f)
             with torch.no_grad():
-                out = forward(to_x(x.to(dev), g.to(dev) if g is not None else None), y.to(dev))
-            out_u8, line = finish(f, out, lab.to(dev) if lab is not None else None, h, w)
+                x, lo_hi = to_x(x.to(dev), g.to(dev) if g is not None else None)
+                out = forward(x, y.to(dev))
+            out_u8, line = finish(f, out, lo_hi, lab.to(dev) if lab is not None else None, h, w)
             if out_dir:
                 write(os.path.join(out_dir, f), out_u8.cpu().numpy())
             emit(line)
@@ -364,8 +332,9 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                     if t is not None:
                         t.record_stream(main_s)                    # allocated on the upload stream, consumed on this one
                 with torch.no_grad():
-                    out = forward(to_x(devs[0], devs[3]), devs[1])
-                out_u8 = post(out[0, 0])
+                    x, lo_hi = to_x(devs[0], devs[3])
+                    out = forward(x, devs[1])
+                out_u8 = post(out[0, 0], lo_hi)
                 h_acc = h_ss = None
                 h_rep, host_err = [], []
                 if devs[2] is not None:                            # metrics stay on the device; read back one image later
@@ -465,22 +434,18 @@ def main(argv=None):
                     help="LOW-RESOLUTION depth maps as a sensor writes them, code 0 a hole: upsampled by --scale on the device "
                          "with the training degradation's own hole-aware bicubic; guidance and label are cropped to "
                          "(h * scale, w * scale)")
-    ap.add_argument("--fill-holes", action="store_true",
-                    help="with --lr-depth: fill the holes of every low-resolution map on the device by pull-push (the mean of "
-                         "the valid pixels up a pyramid, a 9/3/3/1 mix back down; integers, bit-exact) before it is upsampled, "
-                         "so that the network sees a dense input; valid pixels are untouched")
-    ap.add_argument("--fill-guided", action="store_true",
-                    help="with --fill-holes: guidance-aware filling -- a hole weighs the pixels it is filled from by how close "
-                         "their guidance (the --input-color image, box-averaged over the pixel) is to its own, so a hole beside "
-                         "an occlusion edge takes its own side's depth instead of a ramp across the edge (integers, bit-exact; "
-                         "DESIGN 12.11)")
-    ap.add_argument("--fill-sigma", type=float, default=None, metavar="CODES",
-                    help=f"with --fill-guided: the sigma of the range weight in guidance codes (default {FILL_SIGMA}, untuned)")
-    ap.add_argument("--normalize", action="store_true",
-                    help="with --lr-depth: per-image range normalisation -- the valid codes [lo, hi] of every low-resolution "
-                         "map (after --fill-holes) are stretched onto [1, top] of the code grid on the device, holes stay "
-                         "holes, and the output codes are mapped back before they are measured and written (integers, "
-                         "bit-exact; DESIGN 12.10)")
+    add_prep_args(ap, {
+        "fill_holes": "with --lr-depth: fill the holes of every low-resolution map on the device by pull-push (the mean of "
+                      "the valid pixels up a pyramid, a 9/3/3/1 mix back down; integers, bit-exact) before it is upsampled, "
+                      "so that the network sees a dense input; valid pixels are untouched",
+        "fill_guided": "with --fill-holes: guidance-aware filling -- a hole weighs the pixels it is filled from by how close "
+                       "their guidance (the --input-color image, box-averaged over the pixel) is to its own, so a hole beside "
+                       "an occlusion edge takes its own side's depth instead of a ramp across the edge (integers, bit-exact; "
+                       "DESIGN 12.11)",
+        "normalize": "with --lr-depth: per-image range normalisation -- the valid codes [lo, hi] of every low-resolution "
+                     "map (after --fill-holes) are stretched onto [1, top] of the code grid on the device, holes stay "
+                     "holes, and the output codes are mapped back before they are measured and written (integers, "
+                     "bit-exact; DESIGN 12.10)"})
     ap.add_argument("--input-color", required=True)
     ap.add_argument("--label", default=None)
     ap.add_argument("--out", default=None)
@@ -520,12 +485,7 @@ def main(argv=None):
         ap.error("exactly one of --input-depth and --lr-depth is required")
     if a.fill_holes and a.lr_depth is None:
         ap.error("--fill-holes needs --lr-depth")
-    if a.fill_guided and not a.fill_holes:
-        ap.error("--fill-guided needs --fill-holes (and with it --lr-depth)")
-    if a.fill_sigma is not None and not a.fill_guided:
-        ap.error("--fill-sigma needs --fill-guided")
-    if a.fill_sigma is not None and not (0.0 < a.fill_sigma < float("inf")):
-        ap.error(f"--fill-sigma {a.fill_sigma} must be positive")
+    prep = prep_of(ap, a, a.fill_holes, "--fill-holes (and with it --lr-depth)")
     if a.normalize and a.lr_depth is None:
         ap.error("--normalize needs --lr-depth (it is refused with --input-depth: only low-resolution code planes are normalised)")
     if a.ema and not a.weights:
@@ -552,10 +512,7 @@ def main(argv=None):
     r = run_loop(model, dev, tdt, a.input_depth, a.input_color, a.label, a.out, pipelined=not a.serial,
                  depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit,
                  **({"self_ensemble": True} if a.self_ensemble else {}), **({"report": report} if report else {}),
-                 **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}),
-                 **({"fill_holes": True} if a.fill_holes else {}), **({"normalize": True} if a.normalize else {}),
-                 **({"fill_guided": True, "fill_sigma": FILL_SIGMA if a.fill_sigma is None else a.fill_sigma}
-                    if a.fill_guided else {}))
+                 **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}), **prep.set_options())
     print(r["n"])
     if a.label and r["n"]:
         print(r["rmse_mean"], r["ssim_mean"])

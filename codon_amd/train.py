@@ -48,10 +48,8 @@ from .io import check_depth_max, list_pairs, read_depth_plane
 from .metrics import report_tokens
 from .upsample import (_fill_launch, _on_device, code_table, down_weights, gauss_table, lut16,      # noqa: F401 (lut16: for
                        phase_weights, u8_lut)                                                      # importers)
-from .upsample import fill_holes as _fill_holes
-from .upsample import fill_holes_guided as _fill_guided
-from .upsample import FILL_SIGMA, check_fill_sigma
-from .upsample import check_stretch_top, code_range, stretch_codes
+from .prep import LrPrep, add_prep_args, prep_of
+from .upsample import FILL_SIGMA, code_range, stretch_codes
 
 DTYPES = {"bf16": torch.bfloat16, "f32": None}
 RESUME_KEYS = ("scale", "crop", "batch", "dtype", "clip_norm", "skip_nonfinite", "ema", "lr_schedule", "warmup_steps", "lr_min",
@@ -70,12 +68,15 @@ LR_DEFAULTS = {"train_lr_depth": False}
 # compares as "no model"
 SENSOR_DEFAULTS = {"sensor_noise": None, "sensor_noise_quad": None, "sensor_dropout": None, "sensor_edge_dropout": None,
                    "sensor_edge_threshold": None, "sensor_seed": None}
-# the same for --fill-holes: a resume key with default False, written by a run that sets it ONLY
-FILL_DEFAULTS = {"fill_holes": False}
-# the same for --fill-guided and --fill-sigma: resume keys with these defaults, written by a run with --fill-guided ONLY
-GUIDED_DEFAULTS = {"fill_guided": False, "fill_sigma": 10.0}
-# the same for --normalize: a resume key with default False, written by a run that sets it ONLY
-NORM_DEFAULTS = {"normalize": False}
+# the same for the preparation of low-resolution maps: prep.LrPrep's fields with their defaults, written as
+# LrPrep.set_options() gives them -- by a run that sets the option ONLY
+FILL_DEFAULTS = LrPrep.defaults("fill_holes")
+GUIDED_DEFAULTS = LrPrep.defaults("fill_guided", "fill_sigma")
+NORM_DEFAULTS = LrPrep.defaults("normalize")
+# what load_resume compares: every key above, and what each compares as when a checkpoint's args lack it
+_LATER_DEFAULTS = (DEPTH_DEFAULTS, DEGRADE_DEFAULTS, LR_DEFAULTS, SENSOR_DEFAULTS, FILL_DEFAULTS, GUIDED_DEFAULTS, NORM_DEFAULTS)
+RESUME_ALL_KEYS = RESUME_KEYS + tuple(k for d in _LATER_DEFAULTS for k in d)
+RESUME_ALL_DEFAULTS = {k: v for d in (RESUME_DEFAULTS,) + _LATER_DEFAULTS for k, v in d.items()}
 MAX_REDRAWS = 64                                    # draw(min_valid=): per sample, before it gives up
 LR_SCHEDULES = ("constant", "cosine")
 
@@ -109,15 +110,14 @@ class TrainSet:
     (h * scale, w * scale), to which depth map and guidance are cropped top-left (a smaller one is refused by name: the rule
     of `infer --lr-depth`); `sizes` holds the HR sizes.  The depth map is the target and nothing is degraded, so lr_dir
     excludes label_dir.  has_lr, lr_scale say so (False, None otherwise).
-    `fill_holes` (needs lr_dir): once the pool is on the device, the low-resolution plane of every record is
-    filled by pull-push from the WHOLE file (upsample.fill_holes, one call per record), so that a step costs nothing extra and x
-    stays the crop of what `infer --lr-depth --fill-holes` builds from that file; the target plane is untouched.
-    `fill_guided` (needs fill_holes): that filling is upsample.fill_holes_guided with the record's own guide plane,
-    read in place (row stride W), and the range table of `fill_sigma` -- as `infer --lr-depth --fill-holes --fill-guided` does it.
-    `normalize` (excludes label_dir): once the pool is on the device, and after the filling, every record's code
-    planes are stretched IN PLACE (upsample.stretch_codes) so that a step costs nothing extra.  With lr_dir the range is that of
-    the (filled) low-resolution plane of the WHOLE file, as `infer --lr-depth --normalize` takes it; it stretches that plane
-    and, clamped, the HR target plane.  Without lr_dir the depth plane is stretched by its own range."""
+    `fill_holes`, `fill_guided`, `fill_sigma`, `normalize`: the preparation (prep.LrPrep's fields; kept as `prep`
+    and readable under their names), done ONCE, when the pool is on the device, so that a step costs nothing extra.
+    fill_holes (needs lr_dir): the low-resolution plane of every record is filled by pull-push from the WHOLE file, so
+    that x stays the crop of what `infer --lr-depth --fill-holes` builds from that file; the target plane is untouched.
+    fill_guided: by upsample.fill_holes_guided under fill_sigma, with the record's own guide plane read in place.
+    normalize (excludes label_dir): after the filling, every record's code planes are stretched IN PLACE.  With
+    lr_dir the range is that of the (filled) low-resolution plane of the WHOLE file, as `infer --lr-depth --normalize` takes it;
+    it stretches that plane and, clamped, the HR target plane.  Without lr_dir the depth plane is stretched by its own range."""
 
     def __init__(self, depth_dir: str, color_dir: str, device, crop: int = None, label_dir: str = None, depth_bits: int = 8,
                  depth_max: int = 65535, lr_dir: str = None, scale: int = None, fill_holes: bool = False,
@@ -127,19 +127,11 @@ class TrainSet:
         check_depth_max(depth_max)
         self.depth_bits, self.depth_max = depth_bits, int(depth_max)
         self.has_lr, self.lr_scale = lr_dir is not None, None
-        if fill_holes and lr_dir is None:
-            raise ValueError("TrainSet: fill_holes needs lr_dir (only low-resolution code planes are filled)")
-        self.fill_holes = bool(fill_holes)
-        if fill_guided and not fill_holes:
-            raise ValueError("TrainSet: fill_guided needs fill_holes (it chooses how the holes are filled)")
-        self.fill_guided = bool(fill_guided)
-        self.fill_sigma = check_fill_sigma("TrainSet", fill_sigma) if fill_guided else FILL_SIGMA
-        if normalize:
-            if label_dir is not None:
-                raise ValueError("TrainSet: normalize and label_dir exclude each other (a label plane has no range of its own "
-                                 "to be stretched by)")
-            check_stretch_top("TrainSet: normalize", self.depth_max if depth_bits == 16 else 255)
-        self.normalize = bool(normalize)
+        if normalize and label_dir is not None:
+            raise ValueError("TrainSet: normalize and label_dir exclude each other (a label plane has no range of its own "
+                             "to be stretched by)")
+        self.prep = LrPrep.checked("TrainSet", fill_holes, fill_guided, fill_sigma, normalize, lr=("lr_dir", self.has_lr),
+                                   top=self.depth_max if depth_bits == 16 else 255, normalize_needs_lr=False)
         if self.has_lr:
             if scale not in (4, 8, 16):
                 raise ValueError(f"TrainSet: lr_dir needs scale 4, 8 or 16 (got {scale!r})")
@@ -190,31 +182,34 @@ class TrainSet:
         self.sizes = np.asarray(sizes, dtype=np.int64)
         self.pool = torch.from_numpy(np.concatenate(chunks)).to(device)
         self._integrals = None
-        if self.fill_holes:
-            wide = depth_bits // 8
-            for off, (h, w) in zip(self.offsets.tolist(), self.sizes.tolist()):
-                lay = record_layout(depth_bits, False, self.lr_scale, h, w)
-                lo = off + lay["lr"]
-                lh, lw = h // self.lr_scale, w // self.lr_scale
-                plane = self.pool[lo:lo + wide * lh * lw]
-                plane = (plane.view(torch.int16) if deep else plane).view(lh, lw)
-                if self.fill_guided:                    # the record's own guide plane, in place
-                    guide = self.pool[off + lay["guide"]:off + lay["guide"] + h * w].view(h, w)
-                    plane.copy_(_fill_guided(plane, guide, self.lr_scale, self.fill_sigma, self.depth_max if deep else None))
-                else:
-                    plane.copy_(_fill_holes(plane, self.depth_max if deep else None))
-        if self.normalize:
-            wide, dm = depth_bits // 8, self.depth_max if deep else None
-            for off, (h, w) in zip(self.offsets.tolist(), self.sizes.tolist()):
-                lay = record_layout(depth_bits, False, self.lr_scale or 0, h, w)
-                shapes = [("depth", h, w)] + ([("lr", h // self.lr_scale, w // self.lr_scale)] if self.has_lr else [])
-                planes = {}
-                for name, ph, pw in shapes:
-                    p = self.pool[off + lay[name]:off + lay[name] + wide * ph * pw]
-                    planes[name] = (p.view(torch.int16) if deep else p).view(ph, pw)
-                lo_hi = code_range(planes["lr" if self.has_lr else "depth"])
-                for p in planes.values():               # the target plane of real pairs is clamped into the map's range
+        dm = self.depth_max if deep else None
+        records = list(zip(self.offsets.tolist(), self.sizes.tolist()))
+        if self.prep.fill_holes:                        # every record filled, then every record stretched
+            for off, (h, w) in records:
+                lr = self.plane(off, "lr", h, w)
+                lr.copy_(self.prep.fill(lr, self.plane(off, "guide", h, w), self.lr_scale, dm))
+        if self.prep.normalize:
+            for off, (h, w) in records:
+                planes = [self.plane(off, name, h, w) for name in (("depth", "lr") if self.has_lr else ("depth",))]
+                lo_hi = code_range(planes[-1])
+                for p in planes:                        # the target plane of real pairs is clamped into the map's range
                     stretch_codes(p, dm, lo_hi, out=p)
+
+    fill_holes, fill_guided, fill_sigma, normalize = (property(lambda self, n=n: getattr(self.prep, n)) for n in
+                                                      ("fill_holes", "fill_guided", "fill_sigma", "normalize"))
+
+    def plane_offset(self, off: int, name: str, h: int, w: int) -> int:
+        """Where plane `name` ("depth", "guide", "label", "lr") of the (h, w) record at pool offset `off` starts, in bytes"""
+        return off + record_layout(self.depth_bits, self.has_label, self.lr_scale or 0, h, w)[name]
+
+    def plane(self, off: int, name: str, h: int, w: int) -> torch.Tensor:
+        """The device view of that plane in the pool: (h, w) -- the low-resolution plane (h / lr_scale, w / lr_scale) -- uint8, or
+        the u16 bits of a code plane of a 16-bit set as int16"""
+        ph, pw = (h // self.lr_scale, w // self.lr_scale) if name == "lr" else (h, w)
+        lo = self.plane_offset(off, name, h, w)
+        if self.depth_bits == 8 or name == "guide":
+            return self.pool[lo:lo + ph * pw].view(ph, pw)
+        return self.pool[lo:lo + 2 * ph * pw].view(torch.int16).view(ph, pw)
 
     def __len__(self):
         return len(self.files)
@@ -228,7 +223,7 @@ class TrainSet:
             wide = self.depth_bits // 8
             self._integrals = {}
             for off, (h, w) in zip(self.offsets.tolist(), self.sizes.tolist()):
-                lo = off + record_layout(self.depth_bits, self.has_label, 0, h, w)["label" if self.has_label else "depth"]
+                lo = self.plane_offset(off, "label" if self.has_label else "depth", h, w)
                 v = pool[lo:lo + wide * h * w].view("<u2" if wide == 2 else np.uint8).reshape(h, w) != 0
                 ii = np.zeros((h + 1, w + 1), dtype=np.int32)
                 ii[1:, 1:] = v.cumsum(0, dtype=np.int32).cumsum(1, dtype=np.int32)
@@ -498,17 +493,13 @@ def save_checkpoint(path: str, step: int, model, opt, rng: np.random.Generator, 
 
 def load_resume(path: str, args: dict) -> dict:
     """A checkpoint written by save_checkpoint, refused if it was trained with another scale, crop, batch or dtype, or with
-    other options that change the trajectory (RESUME_KEYS, DEPTH_DEFAULTS', DEGRADE_DEFAULTS', LR_DEFAULTS' and
-    SENSOR_DEFAULTS', FILL_DEFAULTS', GUIDED_DEFAULTS' and NORM_DEFAULTS' keys; a key the checkpoint's args lack compares as its default)."""
+    other options that change the trajectory (RESUME_ALL_KEYS; a key the checkpoint's args lack compares as its default in
+    RESUME_ALL_DEFAULTS)."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(ck, dict) or not all(k in ck for k in ("epoch", "model", "optimizer", "rng", "args")):
         raise ValueError(f"--resume {path}: not a codon_amd.train checkpoint (use --weights to start from other weights)")
-    absent = {**RESUME_DEFAULTS, **DEPTH_DEFAULTS, **DEGRADE_DEFAULTS, **LR_DEFAULTS, **SENSOR_DEFAULTS, **FILL_DEFAULTS,
-              **GUIDED_DEFAULTS, **NORM_DEFAULTS}
-    keys = (RESUME_KEYS + tuple(DEPTH_DEFAULTS) + tuple(DEGRADE_DEFAULTS) + tuple(LR_DEFAULTS) + tuple(SENSOR_DEFAULTS) +
-            tuple(FILL_DEFAULTS) + tuple(GUIDED_DEFAULTS) + tuple(NORM_DEFAULTS))
-    was, now = ({k: a.get(k, absent.get(k)) for k in keys} for a in (ck["args"], args))
-    bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in keys if was[k] != now[k]]
+    was, now = ({k: a.get(k, RESUME_ALL_DEFAULTS.get(k)) for k in RESUME_ALL_KEYS} for a in (ck["args"], args))
+    bad = [f"{k} {was[k]!r} != {now[k]!r}" for k in RESUME_ALL_KEYS if was[k] != now[k]]
     if bad:
         raise ValueError(f"--resume {path}: the checkpoint was trained with other arguments: {', '.join(bad)}")
     return ck
@@ -542,16 +533,11 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     sensor: synthesize's sensor model, given the step number and this rank's shard start -- also under `fixed`
            descriptors, so N ranks see the global batch one process sees and a resumed run the maps the straight run saw; the
            checkpoint's args gain the model's fields (SENSOR_DEFAULTS' keys).
-    fill_holes: synthesize's hole filling; needs degrade_holes, or a TrainSet of low-resolution maps built with
-           fill_holes (one built without refuses it, and one built with it refuses a fit without); the checkpoint's args gain
-           fill_holes=True.  A `val` dict with "lr_depth" and "fill_holes" validates on filled maps.
-    fill_guided, fill_sigma: guidance-aware filling is a property of a TrainSet of low-resolution maps, filled
-           once, when it is built: fit and the TrainSet must agree on both (either way round is refused); the checkpoint's args
-           gain fill_guided=True and fill_sigma.  A `val` dict with "lr_depth", "fill_holes" and "fill_guided" (and
-           "fill_sigma") validates as `infer --lr-depth --fill-holes --fill-guided` does.
-    normalize: per-image range normalisation is a property of the TrainSet, whose pool is stretched once, when it
-           is built: fit and the TrainSet must agree on it (either way round is refused); the checkpoint's args gain
-           normalize=True.  A `val` dict with "lr_depth" and "normalize" validates as `infer --lr-depth --normalize` does.
+    fill_holes, fill_guided, fill_sigma, normalize: the preparation of the low-resolution maps (prep.LrPrep's fields, DESIGN
+           12.12).  A TrainSet of low-resolution maps is prepared once, when it is built, so fit and the TrainSet must agree on
+           every one of them (either way round is refused); fill_holes alone also goes with degrade_holes on the synthetic path
+           (synthesize's hole filling).  The checkpoint's args gain the options that are set, and a `val` dict with
+           "lr_depth" and the same keys validates as `infer --lr-depth` with the same flags does.
     Returns {"losses": [(step, loss)], "gs", "opt", "rng", "step", ...}."""
     from .dist import FlatAdam, GradSync
     from .metrics import L1SSIMLoss, MaskedL1SSIMLoss
@@ -562,20 +548,18 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         raise ValueError(f"fit: a batch of {batch} does not split evenly over {world} ranks")
     if not 0.0 <= min_valid <= 1.0 or (min_valid > 0 and not mask_holes):
         raise ValueError(f"fit: min_valid {min_valid} must lie in [0, 1] and needs mask_holes")
-    if bool(fill_holes) != trainset.fill_holes if trainset.has_lr else (fill_holes and not degrade_holes):
+    prep, built = LrPrep.checked("fit", fill_holes, fill_guided, fill_sigma, normalize), trainset.prep
+    if prep.fill_holes != built.fill_holes if trainset.has_lr else (prep.fill_holes and not degrade_holes):
         raise ValueError("fit: fill_holes needs degrade_holes, or a TrainSet of low-resolution maps -- and that TrainSet must "
                          "have been built with the same fill_holes (its pool is filled once, when it is built)")
-    if fill_guided:
-        fill_sigma = check_fill_sigma("fit", fill_sigma)
-    if bool(fill_guided) != trainset.fill_guided or (fill_guided and fill_sigma != trainset.fill_sigma):
-        raise ValueError(f"fit: fill_guided {bool(fill_guided)!r}" + (f" (fill_sigma {fill_sigma!r})" if fill_guided else "") +
-                         f" with a TrainSet built with fill_guided {trainset.fill_guided!r}" +
-                         (f" (fill_sigma {trainset.fill_sigma!r})" if trainset.fill_guided else "") +
+    if (prep.fill_guided, prep.fill_sigma) != (built.fill_guided, built.fill_sigma):
+        say = lambda p: f"fill_guided {p.fill_guided!r}" + (f" (fill_sigma {p.fill_sigma!r})" if p.fill_guided else "")   # noqa: E731
+        raise ValueError(f"fit: {say(prep)} with a TrainSet built with {say(built)}"
                          " -- only a TrainSet of low-resolution maps is filled with guidance, once, when it is built")
-    if bool(normalize) != trainset.normalize:
-        raise ValueError(f"fit: normalize {bool(normalize)!r} with a TrainSet built with normalize {trainset.normalize!r} (its "
+    if prep.normalize != built.normalize:
+        raise ValueError(f"fit: normalize {prep.normalize!r} with a TrainSet built with normalize {built.normalize!r} (its "
                          "pool is stretched once, when it is built)")
-    synth_kw = {"fill_holes": True} if fill_holes else {}      # without it synthesize is called as ever
+    synth_kw = {"fill_holes": True} if prep.fill_holes else {}      # without it synthesize is called as ever
     if sensor is not None:                          # refused before the first step; without a model synthesize is called as ever
         from .dist import shard_batch
         check_sensor("fit", trainset, sensor, degrade_holes)
@@ -606,12 +590,7 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         args.update(train_lr_depth=True)
     if sensor is not None:                          # only then, likewise
         args.update(sensor.args())
-    if fill_holes:                                  # only then, likewise
-        args.update(fill_holes=True)
-    if fill_guided:                                 # only then, likewise
-        args.update(fill_guided=True, fill_sigma=float(fill_sigma))
-    if normalize:                                   # only then, likewise
-        args.update(normalize=True)
+    args.update(prep.set_options())                 # the options that are set only, likewise
     if trainset.depth_bits == 16:                   # only then: an 8-bit checkpoint keeps the keys it always had
         args.update(depth_bits=16, depth_max=int(trainset.depth_max))
     stream = torch.cuda.current_stream(dev)
@@ -698,12 +677,7 @@ def validate(model, dev, val: dict, emit=print) -> dict:
             deep = {"depth_bits": 16, "depth_max": val.get("depth_max", 65535)} if val.get("depth_bits", 8) == 16 else {}
             if val.get("lr_depth"):                 # low-resolution validation maps, upsampled as infer --lr-depth does
                 deep.update(lr_depth=val["lr_depth"], scale=val["scale"])
-                if val.get("fill_holes"):           # filled as infer --lr-depth --fill-holes fills them
-                    deep.update(fill_holes=True)
-                if val.get("fill_guided"):          # with the guidance's say
-                    deep.update(fill_guided=True, fill_sigma=val.get("fill_sigma", FILL_SIGMA))
-                if val.get("normalize"):            # stretched and mapped back as infer --lr-depth --normalize does
-                    deep.update(normalize=True)
+                deep.update(LrPrep.from_mapping(val).set_options())       # prepared as infer --lr-depth prepares them
             if val.get("report") is not None:       # the evaluation suite of infer --report
                 deep.update(report=val["report"])
             r = run_loop(model, dev, torch.float32, val.get("depth"), val["color"], val.get("label"), emit=lambda s: None, **deep)
@@ -752,23 +726,19 @@ def parse_args(argv=None):
     ap.add_argument("--degrade-holes", action="store_true",
                     help="holes (code 0) of the depth maps are left out of the degradation's two bicubics instead of being "
                          "smeared through them; the low-resolution map keeps them as holes, as a sensor's file does")
-    ap.add_argument("--fill-holes", action="store_true",
-                    help="fill the holes of the low-resolution maps on the device by pull-push before they are upsampled, as "
-                         "`codon_amd.infer --lr-depth --fill-holes` does: the maps of --train-lr-depth (once, when they are "
-                         "loaded) or the synthetic ones of --degrade-holes (every step), and those of --val-lr-depth")
-    ap.add_argument("--fill-guided", action="store_true",
-                    help="with --train-lr-depth --fill-holes: guidance-aware filling, as `codon_amd.infer --lr-depth --fill-holes "
-                         "--fill-guided` does it -- every record's low-resolution map is filled once, when the data is loaded, "
-                         "with the record's own guidance plane deciding which side of an edge a hole is filled from (DESIGN "
-                         "12.11); also applies to --val-lr-depth.  Refused with --degrade-holes")
-    ap.add_argument("--fill-sigma", type=float, default=None, metavar="CODES",
-                    help=f"with --fill-guided: the sigma of the range weight in guidance codes (default {FILL_SIGMA}, untuned)")
-    ap.add_argument("--normalize", action="store_true",
-                    help="per-image range normalisation, as `codon_amd.infer --lr-depth --normalize` does it: when the data is "
-                         "loaded, the valid codes [lo, hi] of every map are stretched onto [1, top] of the code grid on the "
-                         "device, holes staying holes -- the low-resolution map of --train-lr-depth by its own range (after "
-                         "--fill-holes) and its HR target by the same range, else the depth map by its own; also applies to "
-                         "--val-lr-depth; refused with --train-label")
+    add_prep_args(ap, {
+        "fill_holes": "fill the holes of the low-resolution maps on the device by pull-push before they are upsampled, as "
+                      "`codon_amd.infer --lr-depth --fill-holes` does: the maps of --train-lr-depth (once, when they are "
+                      "loaded) or the synthetic ones of --degrade-holes (every step), and those of --val-lr-depth",
+        "fill_guided": "with --train-lr-depth --fill-holes: guidance-aware filling, as `codon_amd.infer --lr-depth --fill-holes "
+                       "--fill-guided` does it -- every record's low-resolution map is filled once, when the data is loaded, "
+                       "with the record's own guidance plane deciding which side of an edge a hole is filled from (DESIGN "
+                       "12.11); also applies to --val-lr-depth.  Refused with --degrade-holes",
+        "normalize": "per-image range normalisation, as `codon_amd.infer --lr-depth --normalize` does it: when the data is "
+                     "loaded, the valid codes [lo, hi] of every map are stretched onto [1, top] of the code grid on the "
+                     "device, holes staying holes -- the low-resolution map of --train-lr-depth by its own range (after "
+                     "--fill-holes) and its HR target by the same range, else the depth map by its own; also applies to "
+                     "--val-lr-depth; refused with --train-label"})
     ap.add_argument("--sensor-noise", type=float, default=None, metavar="CODES",
                     help="sensor model: Gaussian noise of this standard deviation, in codes of the data's grid (255, or "
                          "--depth-max), on the synthetic low-resolution map; every --sensor option draws from --seed")
@@ -832,13 +802,7 @@ def parse_args(argv=None):
     if a.fill_guided and a.degrade_holes:
         ap.error("--fill-guided is refused with --degrade-holes: the synthetic path holds its guidance as fp32 D4 crops, not as "
                  "the codes of a whole image (only the real maps of --train-lr-depth and --val-lr-depth are filled with guidance)")
-    if a.fill_guided and not (a.fill_holes and a.train_lr_depth is not None):
-        ap.error("--fill-guided needs --train-lr-depth --fill-holes")
-    if a.fill_sigma is not None and not a.fill_guided:
-        ap.error("--fill-sigma needs --fill-guided")
-    if a.fill_sigma is not None and not (0.0 < a.fill_sigma < float("inf")):
-        ap.error(f"--fill-sigma {a.fill_sigma} must be positive")
-    a.fill_sigma = FILL_SIGMA if a.fill_sigma is None else float(a.fill_sigma)
+    a.prep = prep_of(ap, a, a.fill_holes and a.train_lr_depth is not None, "--train-lr-depth --fill-holes")
     if a.normalize and a.train_label is not None:
         ap.error("--normalize and --train-label exclude each other (a label plane has no range of its own to be stretched by)")
     given = {n: getattr(a, "sensor_" + n) for n in ("noise", "noise_quad", "dropout", "edge_dropout", "edge_threshold")}
@@ -910,14 +874,12 @@ def run_args(a) -> dict:
             "min_valid": float(a.min_valid), "train_label": a.train_label is not None,
             **({"degrade_holes": True} if a.degrade_holes else {}),
             **({"train_lr_depth": True} if a.train_lr_depth is not None else {}),
-            **(sensor.args() if sensor is not None else {}),
-            **({"fill_holes": True} if a.fill_holes else {}),
-            **({"fill_guided": True, "fill_sigma": a.fill_sigma} if a.fill_guided else {}),
-            **({"normalize": True} if a.normalize else {})}
+            **(sensor.args() if sensor is not None else {}), **a.prep.set_options()}
 
 
 def main(argv=None, emit=print) -> dict:
     a = parse_args(argv)
+    prep = a.prep
     args = run_args(a)
     resume = load_resume(a.resume, args) if a.resume else None     # refused before any GPU work
     import torch.distributed as dist
@@ -936,9 +898,8 @@ def main(argv=None, emit=print) -> dict:
         raise SystemExit(f"--batch {a.batch}: at most {L.TRAIN_MAX_BATCH} images per rank")
     ts = TrainSet(a.train_depth, a.train_color, dev, crop=a.crop, label_dir=a.train_label, depth_bits=a.depth_bits,
                   depth_max=a.depth_max, **({"lr_dir": a.train_lr_depth, "scale": a.scale} if a.train_lr_depth else {}),
-                  **({"fill_holes": True} if a.fill_holes and a.train_lr_depth else {}),
-                  **({"fill_guided": True, "fill_sigma": a.fill_sigma} if a.fill_guided else {}),
-                  **({"normalize": True} if a.normalize else {}))
+                  # the synthetic maps of --degrade-holes are filled every step, by synthesize: only real ones in the pool
+                  **(prep if a.train_lr_depth else dataclasses.replace(prep, fill_holes=False)).set_options())
     torch.manual_seed(a.seed)
     model = (CODONNet16 if a.scale == 16 else CODONNet)()
     rng = np.random.default_rng(a.seed)
@@ -960,19 +921,12 @@ def main(argv=None, emit=print) -> dict:
     val = ({"depth": a.val_depth, "color": a.val_color, "label": a.val_label, "every": a.val_every,
             "depth_bits": a.depth_bits, "depth_max": a.depth_max} if a.val_depth or a.val_lr_depth else None)
     if a.val_lr_depth:
-        val.update(lr_depth=a.val_lr_depth, scale=a.scale, **({"fill_holes": True} if a.fill_holes else {}),
-                   **({"fill_guided": True, "fill_sigma": a.fill_sigma} if a.fill_guided else {}),
-                   **({"normalize": True} if a.normalize else {}))
+        val.update(lr_depth=a.val_lr_depth, scale=a.scale, **prep.set_options())
     if val is not None and a.val_report_params is not None:
         val.update(report=a.val_report_params)
     ckpt = {"path": a.save, "every": a.save_every} if a.save else None
     kw = {"sensor": sensor_of(a)} if sensor_of(a) is not None else {}      # without a model fit is called as ever
-    if a.fill_holes:
-        kw["fill_holes"] = True
-    if a.fill_guided:
-        kw.update(fill_guided=True, fill_sigma=a.fill_sigma)
-    if a.normalize:
-        kw["normalize"] = True
+    kw.update(prep.set_options())
     res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,
               log_every=a.log_every, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,
               args=args, emit=emit, clip_norm=a.clip_norm, skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema,

@@ -129,26 +129,52 @@ def bicubic_upsample_masked(lr: torch.Tensor, scale: int):
     return out, valid
 
 
+# ---- code planes: the one checker of the argument, the fillers' workspaces ---------------------------------------------------------
+
+CODES = "(h,w) or (B,h,w) uint8 codes, or u16 codes as int16 / uint16"
+
+
+def _code_planes(who: str, codes: torch.Tensor, depth_max, expects: str = CODES):
+    """-> (contiguous codes, B, h, w, code_bits, top) of (h,w) / (B,h,w) uint8, int16 or uint16 codes; refusals by name"""
+    if codes.dim() not in (2, 3) or codes.dtype not in (torch.uint8, torch.int16, torch.uint16):
+        raise RuntimeError(f"{who} expects {expects}")
+    if codes.dtype == torch.uint8:
+        if depth_max not in (None, 255):
+            raise ValueError(f"{who}: depth_max {depth_max!r} with 8-bit codes")
+        bits, top = 8, 255
+    else:
+        bits, top = 16, 65535 if depth_max is None else depth_max
+    check_depth_max(top)
+    src = codes.contiguous()
+    h, w = src.shape[-2:]
+    B = src.numel() // (h * w) if h * w else 0
+    if B < 1:
+        raise ValueError(f"{who}: an empty map {tuple(codes.shape)}")
+    return src, B, h, w, bits, int(top)
+
+
+_ws: dict = {}              # filler -> (guards.PerStream -> uint8 workspace of the (device, stream, thread), those made under a capture)
+
+
+def _workspace(who: str, query: str, dev, B: int, h: int, w: int):
+    """Filler `who`'s workspace for B planes of h x w on dev's current stream, sized by the library's `query` (capture-safe:
+    guards.PerStream); the two fillers never share one.  Call it with `dev` current."""
+    from .guards import PerStream
+    need = B * getattr(L.load(), query)(h, w)
+    if need == 0:
+        raise ValueError(f"{who}: a {h}x{w} plane (1..4096 each way)")
+    per_stream, held = _ws.setdefault(who, (PerStream(), []))
+    return per_stream.get(dev, lambda capturing: torch.empty(need, dtype=torch.uint8, device=dev), need=need, hold=held)
+
+
 # ---- pull-push hole filling of low-resolution maps (DESIGN 12.9) --------------------------------------------------------------
 
-_fill_ws = None             # guards.PerStream -> uint8 workspace of the (device, stream, thread)
-_fill_held: list = []       # workspaces made under a hipGraph capture
-
-
 def _fill_launch(dev, B: int, h: int, w: int, src_ptr: int, fmt: int, tab, top: int, out_ptr: int):
-    """codon_fill_holes on dev's current stream, with the per-stream workspace (capture-safe: guards.PerStream)."""
-    global _fill_ws
-    from .guards import PerStream
-    lib = L.load()
-    need = B * lib.codon_fill_holes_workspace_bytes(h, w)
-    if need == 0:
-        raise ValueError(f"fill_holes: a {h}x{w} plane (1..4096 each way)")
-    if _fill_ws is None:
-        _fill_ws = PerStream()
+    """codon_fill_holes on dev's current stream, with the per-stream workspace"""
     with torch.cuda.device(dev):
-        ws = _fill_ws.get(dev, lambda capturing: torch.empty(need, dtype=torch.uint8, device=dev), need=need, hold=_fill_held)
-        L.check(lib.codon_fill_holes(B, h, w, C.c_void_p(src_ptr), fmt, C.c_void_p(tab.data_ptr()) if tab is not None else None,
-                                     top, C.c_void_p(out_ptr), C.c_void_p(ws.data_ptr()), ws.numel(), ops._stream(dev)),
+        ws = _workspace("fill_holes", "codon_fill_holes_workspace_bytes", dev, B, h, w)
+        L.check(L.load().codon_fill_holes(B, h, w, C.c_void_p(src_ptr), fmt, C.c_void_p(tab.data_ptr()) if tab is not None else None,
+                                          top, C.c_void_p(out_ptr), C.c_void_p(ws.data_ptr()), ws.numel(), ops._stream(dev)),
                 "fill_holes")
 
 
@@ -160,40 +186,28 @@ def fill_holes(codes: torch.Tensor, depth_max: int = None) -> torch.Tensor:
     between its two bicubics.  Valid pixels come back bit for bit, a map without a valid pixel comes back unchanged, and a hole
     never takes a value above the largest valid code.  Integer arithmetic, bit-exact: tests/fill_ref.py.  One launch up to
     64 x 64, three beyond; no host synchronisation."""
-    on_grid = codes.dtype == torch.float32
-    if on_grid:
+    expects = "(h,w) / (B,h,w) uint8, int16 or uint16 codes, or a (B,1,h,w) float32 map"
+    if codes.dtype == torch.float32:                # on the grid
         if codes.dim() != 4 or codes.shape[1] != 1:
-            raise RuntimeError("fill_holes expects (h,w) / (B,h,w) uint8, int16 or uint16 codes, or a (B,1,h,w) float32 map")
+            raise RuntimeError(f"fill_holes expects {expects}")
         bits, top = (8, 255) if depth_max is None else (16, depth_max)
-    elif codes.dim() in (2, 3) and codes.dtype in (torch.uint8, torch.int16, torch.uint16):
-        if codes.dtype == torch.uint8:
-            if depth_max not in (None, 255):
-                raise ValueError(f"fill_holes: depth_max {depth_max!r} with 8-bit codes")
-            bits, top = 8, 255
-        else:
-            bits, top = 16, 65535 if depth_max is None else depth_max
+        check_depth_max(top)
+        src = codes.contiguous()
+        B, _, h, w = src.shape
+        if B * h * w == 0:
+            raise ValueError(f"fill_holes: an empty map {tuple(codes.shape)}")
+        fmt, tab = L.FILL_F32, code_table(bits, top, ops._dev(src))[0]
     else:
-        raise RuntimeError("fill_holes expects (h,w) / (B,h,w) uint8, int16 or uint16 codes, or a (B,1,h,w) float32 map")
-    check_depth_max(top)
-    src = codes.contiguous()
-    dev = ops._dev(src)
-    h, w = src.shape[-2:]
-    B = src.numel() // (h * w) if h * w else 0
-    if B < 1:
-        raise ValueError(f"fill_holes: an empty map {tuple(codes.shape)}")
-    tab = code_table(bits, top, dev)[0] if on_grid else None
+        src, B, h, w, bits, top = _code_planes("fill_holes", codes, depth_max, expects)
+        fmt, tab = L.FILL_U8 if bits == 8 else L.FILL_U16, None
     out = torch.empty_like(src)
-    _fill_launch(dev, B, h, w, src.data_ptr(), L.FILL_F32 if on_grid else L.FILL_U8 if bits == 8 else L.FILL_U16, tab, int(top),
-                 out.data_ptr())
+    _fill_launch(ops._dev(src), B, h, w, src.data_ptr(), fmt, tab, int(top), out.data_ptr())
     return out
 
 
 # ---- guidance-aware pull-push hole filling (DESIGN 12.11) ---------------------------------------------------------------------
 
 FILL_SIGMA = 10.0           # the default range sigma in guidance codes: the prototype's value, untuned
-
-_guided_ws = None           # guards.PerStream -> uint8 workspace of the (device, stream, thread)
-_guided_held: list = []     # workspaces made under a hipGraph capture
 
 
 def check_fill_sigma(who: str, sigma) -> float:
@@ -240,26 +254,11 @@ def fill_holes_guided(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigm
     the kernels divide by).  Valid pixels come back bit for bit, a map without a valid pixel comes back unchanged, and
     a hole never takes a value above the largest valid code.  Integer arithmetic, bit-exact: tests/guided_fill_ref.py.  One
     launch up to 64 x 64, three beyond; no host synchronisation."""
-    global _guided_ws
-    from .guards import PerStream
     who = "fill_holes_guided"
-    if codes.dim() not in (2, 3) or codes.dtype not in (torch.uint8, torch.int16, torch.uint16):
-        raise RuntimeError(f"{who} expects (h,w) or (B,h,w) uint8 codes, or u16 codes as int16 / uint16")
-    if codes.dtype == torch.uint8:
-        if depth_max not in (None, 255):
-            raise ValueError(f"{who}: depth_max {depth_max!r} with 8-bit codes")
-        fmt, top = L.FILL_U8, 255
-    else:
-        fmt, top = L.FILL_U16, 65535 if depth_max is None else depth_max
-    check_depth_max(top)
+    src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
     if scale not in (4, 8, 16):
         raise ValueError(f"{who}: scale {scale!r} (4, 8 or 16)")
-    src = codes.contiguous()
     dev = ops._dev(src)
-    h, w = src.shape[-2:]
-    B = src.numel() // (h * w) if h * w else 0
-    if B < 1:
-        raise ValueError(f"{who}: an empty map {tuple(codes.shape)}")
     if guide.dtype != torch.uint8 or guide.dim() != codes.dim() or guide.device != src.device:
         raise RuntimeError(f"{who} expects a uint8 guide on the codes' device, (H,W) for (h,w) codes and (B,H,W) for (B,h,w) codes")
     if guide.dim() == 3 and guide.shape[0] != B:
@@ -278,43 +277,17 @@ def fill_holes_guided(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigm
         raise RuntimeError(f"{who}: _table must be a contiguous (256,) int16 / uint16 tensor on the codes' device")
     else:
         table = _table
-    lib = L.load()
-    need = B * lib.codon_fill_guided_workspace_bytes(h, w)
-    if need == 0:
-        raise ValueError(f"{who}: a {h}x{w} plane (1..4096 each way)")
     out = torch.empty_like(src)
-    if _guided_ws is None:
-        _guided_ws = PerStream()
     P_ = C.c_void_p
     with torch.cuda.device(dev):
-        ws = _guided_ws.get(dev, lambda capturing: torch.empty(need, dtype=torch.uint8, device=dev), need=need, hold=_guided_held)
-        L.check(lib.codon_fill_holes_guided(B, h, w, P_(src.data_ptr()), fmt, int(top), P_(guide.data_ptr()), row_bytes,
-                                            image_bytes, scale, P_(table.data_ptr()), P_(out.data_ptr()), P_(ws.data_ptr()),
-                                            ws.numel(), ops._stream(dev)), who)
+        ws = _workspace(who, "codon_fill_guided_workspace_bytes", dev, B, h, w)
+        L.check(L.load().codon_fill_holes_guided(B, h, w, P_(src.data_ptr()), L.FILL_U8 if bits == 8 else L.FILL_U16, top,
+                                                 P_(guide.data_ptr()), row_bytes, image_bytes, scale, P_(table.data_ptr()),
+                                                 P_(out.data_ptr()), P_(ws.data_ptr()), ws.numel(), ops._stream(dev)), who)
     return out
 
 
 # ---- per-image range normalisation of depth codes --------------------------------------------------------------
-
-def _code_planes(who: str, codes: torch.Tensor, depth_max):
-    """-> (contiguous codes, B, h, w, code_bits, top) of (h,w) / (B,h,w) uint8, int16 or uint16 codes; refusals by name"""
-    if codes.dim() not in (2, 3) or codes.dtype not in (torch.uint8, torch.int16, torch.uint16):
-        raise RuntimeError(f"{who} expects (h,w) or (B,h,w) uint8 codes, or u16 codes as int16 / uint16")
-    if codes.dtype == torch.uint8:
-        if depth_max not in (None, 255):
-            raise ValueError(f"{who}: depth_max {depth_max!r} with 8-bit codes")
-        bits, top = 8, 255
-    else:
-        bits, top = 16, 65535 if depth_max is None else depth_max
-    check_depth_max(top)
-    check_stretch_top(who, top)
-    src = codes.contiguous()
-    h, w = src.shape[-2:]
-    B = src.numel() // (h * w) if h * w else 0
-    if B < 1:
-        raise ValueError(f"{who}: an empty map {tuple(codes.shape)}")
-    return src, B, h, w, bits, int(top)
-
 
 def check_stretch_top(who: str, depth_max: int):
     """The stretch maps onto [1, depth_max] with depth_max - 1 steps: a grid of fewer than two codes is refused by name."""
@@ -337,6 +310,7 @@ def code_range(codes: torch.Tensor) -> torch.Tensor:
 
 def _map_codes(who: str, entry: str, codes, lo_hi, depth_max, out):
     src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
+    check_stretch_top(who, top)
     dev = ops._dev(src)
     if lo_hi is None:
         lo_hi = code_range(src)

@@ -5,6 +5,7 @@ guided fill must at least halve the plain fill's error over the holes; the host-
 entry; the range table; the command lines' refusals and defaults; and a resume of a checkpoint written before the option
 existed."""
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
@@ -211,7 +212,7 @@ def test_python_refusals(tmp_path):
     ts = train.TrainSet(dd, cd, "cpu")
     with pytest.raises(ValueError, match="fit: fill_guided True .* with a TrainSet built with fill_guided False"):
         train.fit(None, ts, 1, scale=4, crop=32, batch=1, degrade_holes=True, fill_holes=True, fill_guided=True)
-    tl.fill_holes = tl.fill_guided = True                                 # as if it had been built with both, at sigma 10
+    tl.prep = dataclasses.replace(tl.prep, fill_holes=True, fill_guided=True)         # as if it had been built with both, at sigma 10
     with pytest.raises(ValueError, match="fit: fill_guided False with a TrainSet built with fill_guided True"):
         train.fit(None, tl, 1, scale=4, crop=32, batch=1, fill_holes=True)
     with pytest.raises(ValueError, match=r"fit: fill_guided True \(fill_sigma 3.0\) with a TrainSet built with fill_guided True "

@@ -3,6 +3,7 @@
 random ranges and the extremes n = 0, n = 1, n = T; the shared cases; the refusals of the three C entries, of the Python
 functions and of the command lines; and a resume of a checkpoint written before the option existed."""
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
@@ -162,7 +163,7 @@ def test_python_refusals(tmp_path):
     assert ts.normalize is False
     with pytest.raises(ValueError, match="fit: normalize True with a TrainSet built with normalize False"):
         train.fit(None, ts, 1, scale=4, crop=32, batch=1, normalize=True)
-    ts.normalize = True                                                   # as one built with the option says
+    ts.prep = dataclasses.replace(ts.prep, normalize=True)                # as one built with the option says
     with pytest.raises(ValueError, match="fit: normalize False with a TrainSet built with normalize True"):
         train.fit(None, ts, 1, scale=4, crop=32, batch=1)
     from codon_amd.upsample import code_range, stretch_codes, unstretch_codes
