@@ -4,8 +4,8 @@
 // the views only copy bits; the merge upcasts exactly to fp32 and adds in a fixed tree,
 //   out = 0.125f * (((u0+u1)+(u2+u3)) + ((u4+u5)+(u6+u7))),   u_k the inverse of view k of the network output,
 // every add rounded on its own (built with -ffp-contract=off, like upsample.hip), so that eight equal values average to
-// themselves exactly.  The D4 code is train_record.h's (crop_pixel); the index arithmetic and the layout of the two view batches are in
-// d4_tile.h, shared with the host-side sanitizer check.
+// themselves exactly.  The D4 code is train_record.h's (crop_pixel); the workgroup bodies, the index arithmetic and the layout of the two
+// view batches are in d4_tile.h, and the host-side sanitizer check calls the same bodies.
 //
 // Both kernels are HBM-bound permutations.  One workgroup of 256 threads owns a 32 x 32 tile; the transposed half goes through
 // a padded LDS tile, so that every global read and write of every view runs along that view's contiguous axis; the flipped
@@ -19,39 +19,24 @@
 
 namespace codon {
 
-// grid (ceil(W/32), ceil(H/32), B * planes): plane p of image b = blockIdx.z
+// grid (d4_tiles(W), d4_tiles(H), B * planes)
 template <typename T>
 __global__ __launch_bounds__(D4_THREADS) void d4_views_kernel(const T* __restrict__ src0, const T* __restrict__ src1,
                                                               T* __restrict__ up0, T* __restrict__ tp0, T* __restrict__ up1,
                                                               T* __restrict__ tp1, int H, int W, int planes) {
   __shared__ T tile[D4_TILE][D4Stride<T>::value];
-  const int b = blockIdx.z / planes, p = blockIdx.z - b * planes;      // uniform
-  const long hw = (long)H * W;
-  const T* src = (p ? src1 : src0) + b * hw;
-  T* up = (p ? up1 : up0) + 4 * b * hw;
-  T* tp = (p ? tp1 : tp0) + 4 * b * hw;
-  const int i0 = blockIdx.y * D4_TILE, j0 = blockIdx.x * D4_TILE;
-  d4_views_phase1<T>(threadIdx.x, i0, j0, H, W, src, up, tile);
-  __syncthreads();
-  d4_views_phase2<T>(threadIdx.x, i0, j0, H, W, tp, tile);
+  wg_d4_views<T>(WgDevice(), blockIdx.x, blockIdx.y, blockIdx.z, src0, src1, up0, tp0, up1, tp1, H, W, planes, tile);
 }
 
-// grid (ceil(W/32), ceil(H/32), B)
+// grid (d4_tiles(W), d4_tiles(H), B)
 template <int DT>
 __global__ __launch_bounds__(D4_THREADS) void d4_merge_kernel(const void* __restrict__ upright, const void* __restrict__ transposed,
                                                               float* __restrict__ out, int H, int W) {
   __shared__ float lds[4][D4_TILE][D4_TILE + 1];
-  const long hw = (long)H * W;
-  const long base = 4 * (long)blockIdx.z * hw;
-  const int i0 = blockIdx.y * D4_TILE, j0 = blockIdx.x * D4_TILE;
-  d4_merge_phase1<DT>(threadIdx.x, i0, j0, H, W, transposed, base, lds);
-  __syncthreads();
-  d4_merge_phase2<DT>(threadIdx.x, i0, j0, H, W, upright, base, lds, out + (long)blockIdx.z * hw);
+  wg_d4_merge<DT>(WgDevice(), blockIdx.x, blockIdx.y, blockIdx.z, upright, transposed, out, H, W, lds);
 }
 
-static dim3 d4_grid(int z, int H, int W) {
-  return dim3((unsigned)((W + D4_TILE - 1) / D4_TILE), (unsigned)((H + D4_TILE - 1) / D4_TILE), (unsigned)z);
-}
+static dim3 d4_grid(int z, int H, int W) { return dim3((unsigned)d4_tiles(W), (unsigned)d4_tiles(H), (unsigned)z); }
 
 int d4_views(int B, int H, int W, const void* src0, const void* src1, int dtype, void* up0, void* tp0, void* up1, void* tp1,
              hipStream_t stream) {

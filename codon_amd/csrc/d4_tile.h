@@ -1,8 +1,8 @@
-// The per-thread bodies of the two D4 self-ensemble kernels (d4.hip), written so that the SAME text compiles for
-// the device and for a plain host compiler: tools/d4_host_check.cpp drives them thread by thread under the address and
-// undefined-behaviour sanitizers.  A workgroup of D4_THREADS threads owns one D4_TILE x D4_TILE tile of the (H, W) plane; each
-// kernel is two phases with a workgroup barrier between them, and the tile in LDS is what turns the transposed views' column
-// walk into row walks on both sides of the copy.
+// The two workgroup bodies of the D4 self-ensemble kernels (d4.hip; wg_d4_*, over wg.h's group type: DESIGN 12.13)
+// and the per-thread phases they run, written so that the SAME text compiles for the device and for a plain host compiler: the
+// kernels and tools/d4_host_check.cpp, under the address and undefined-behaviour sanitizers, call the same bodies.  A workgroup
+// of D4_THREADS threads owns one D4_TILE x D4_TILE tile of the (H, W) plane; each kernel is two phases with a workgroup barrier
+// between them, and the tile in LDS is what turns the transposed views' column walk into row walks on both sides of the copy.
 //
 // The D4 code is train_record.h's (crop_pixel), on the whole plane c (H, W):  op&1: c = c.T; then op&2: c = c[::-1]; then op&4: c = c[:, ::-1].
 // Codes 0, 2, 4, 6 ("upright", H x W) sit at slot s = op >> 1 of the upright batch, codes 1, 3, 5, 7 ("transposed", W x H) at
@@ -13,6 +13,8 @@
 //   upright    : u[i][j] = o[fr ? H-1-i : i][fc ? W-1-j : j]
 //   transposed : u[i][j] = o[fr ? W-1-j : j][fc ? H-1-i : i]
 #pragma once
+
+#include "wg.h"
 
 #if defined(__HIPCC__)
 #define CODON_D4_HD __host__ __device__ __forceinline__
@@ -25,6 +27,8 @@ namespace codon {
 constexpr int D4_TILE = 32;
 constexpr int D4_THREADS = 256;
 constexpr int D4_ROWS = D4_THREADS / D4_TILE;       // tile rows per pass of the workgroup
+
+CODON_D4_HD int d4_tiles(int n) { return (n + D4_TILE - 1) / D4_TILE; }      // both grids are (d4_tiles(W), d4_tiles(H), .)
 
 // LDS row stride in elements: an ODD number of dwords (33 for 4-byte, 17 for 2-byte elements), so that the 32 lanes that
 // read one tile COLUMN land on 32 different banks
@@ -129,6 +133,35 @@ CODON_D4_HD void d4_merge_phase2(int tid, int i0, int j0, int H, int W, const vo
       out[(long)i * W + j] = 0.125f * (a + b);
     }
   }
+}
+
+// ---- the workgroup bodies -----------------------------------------------------------------------------------------------------
+
+// workgroup (bx, by, bz) of grid (d4_tiles(W), d4_tiles(H), B * planes): plane p of image b = bz.  LDS: tile
+template <typename T, class G>
+CODON_D4_HD void wg_d4_views(G wg, int bx, int by, unsigned bz, const T* src0, const T* src1, T* up0, T* tp0, T* up1, T* tp1, int H,
+                             int W, int planes, T (*tile)[D4Stride<T>::value]) {
+  const int b = bz / planes, p = bz - b * planes;                      // uniform (bz is unsigned: no signed division)
+  const long hw = (long)H * W;
+  const T* src = (p ? src1 : src0) + b * hw;
+  T* up = (p ? up1 : up0) + 4 * b * hw;
+  T* tp = (p ? tp1 : tp0) + 4 * b * hw;
+  const int i0 = by * D4_TILE, j0 = bx * D4_TILE;
+  WG_EACH(wg, tid) d4_views_phase1<T>(tid, i0, j0, H, W, src, up, tile);
+  wg.sync();
+  WG_EACH(wg, tid) d4_views_phase2<T>(tid, i0, j0, H, W, tp, tile);
+}
+
+// workgroup (bx, by, bz) of grid (d4_tiles(W), d4_tiles(H), B): image bz.  LDS: lds
+template <int DT, class G>
+CODON_D4_HD void wg_d4_merge(G wg, int bx, int by, unsigned bz, const void* upright, const void* transposed, float* out, int H, int W,
+                             float (*lds)[D4_TILE][D4_TILE + 1]) {
+  const long hw = (long)H * W;
+  const long base = 4 * (long)bz * hw;
+  const int i0 = by * D4_TILE, j0 = bx * D4_TILE;
+  WG_EACH(wg, tid) d4_merge_phase1<DT>(tid, i0, j0, H, W, transposed, base, lds);
+  wg.sync();
+  WG_EACH(wg, tid) d4_merge_phase2<DT>(tid, i0, j0, H, W, upright, base, lds, out + (long)bz * hw);
 }
 
 }  // namespace codon

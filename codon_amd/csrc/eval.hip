@@ -5,10 +5,11 @@
 // held to its bits: integers only (no floating point anywhere), so the words do not depend on the order of summation.
 //
 // One workgroup of 256 threads owns a 32 x 32 tile of one image.  The label tile plus a halo of r + 1 goes to LDS (50 x 50
-// codes at r = 8); the discontinuity flags over tile + r are dilated separably there (a row OR, then a column OR); the index
-// arithmetic of all four phases is in eval_tile.h, shared with the host-side sanitizer check.  Each thread accumulates its
-// pixels in registers; the wave reduces by __shfl_xor over 64 lanes, the four waves through LDS, and the workgroup issues one
-// u64 atomicAdd / atomicMax per accumulator it touched.  The label is read through its own row stride, top-left: no cropped copy.
+// codes at r = 8); the discontinuity flags over tile + r are dilated separably there (a row OR, then a column OR); the workgroup
+// body and its four phases are in eval_tile.h, and the host-side sanitizer check calls the same body.  Each
+// thread accumulates its pixels in registers; the wave reduces by __shfl_xor over 64 lanes, the four waves through LDS, and the
+// workgroup issues one u64 atomicAdd / atomicMax per accumulator it touched.  The label is read through its own row stride,
+// top-left: no cropped copy.
 // Bounds: |e| <= 65535, e^2 < 2^32, at most 2^26 pixels per image, so every sum stays below 2^58.
 
 #include "codon_common.h"
@@ -17,7 +18,7 @@
 
 namespace codon {
 
-// grid (ceil(W/32), ceil(H/32), B)
+// grid (ev_tiles(W), ev_tiles(H), B)
 template <typename T>
 __global__ __launch_bounds__(EV_THREADS) void depth_errors_kernel(EvalArgs a, const T* __restrict__ label,
                                                                   const T* __restrict__ out, T* __restrict__ err,
@@ -28,20 +29,9 @@ __global__ __launch_bounds__(EV_THREADS) void depth_errors_kernel(EvalArgs a, co
   __shared__ unsigned char rowor[EV_FSIDE][EV_TILE];
   __shared__ unsigned long long red[EV_THREADS / 64][EV_WORDS];
   const int b = blockIdx.z, tid = threadIdx.x;
-  const int i0 = blockIdx.y * EV_TILE, j0 = blockIdx.x * EV_TILE;
-  const long hw = (long)a.H * a.W;
-  ev_load<T>(a, tid, i0, j0, label + b * a.label_image, lab);
-  __syncthreads();
-  if (a.edge) {                                                    // uniform
-    ev_flags<T>(a, tid, lab, flag);
-    __syncthreads();
-    ev_row_or(a, tid, flag, rowor);
-    __syncthreads();
-  }
-  unsigned long long w[EV_WORDS];
-#pragma unroll
-  for (int k = 0; k < EV_WORDS; ++k) w[k] = 0;
-  ev_pixels<T>(a, tid, i0, j0, lab, rowor, out + b * hw, err ? err + b * hw : nullptr, region ? region + b * hw : nullptr, w);
+  WgDevice::Regs<unsigned long long, EV_WORDS> regs{WgDevice()};
+  wg_eval_tile<T>(WgDevice(), blockIdx.x, blockIdx.y, b, a, label, out, err, region, lab, flag, rowor, regs);
+  unsigned long long* w = regs[tid];                               // the reduction: the device's own
 #pragma unroll
   for (int k = 0; k < 14; ++k) {
 #pragma unroll
@@ -69,7 +59,7 @@ int depth_errors(const EvalArgs& a, int B, int bits, const void* label, const vo
                  unsigned long long* acc, hipStream_t stream) {
   hipError_t e = hipMemsetAsync(acc, 0, (size_t)B * EV_WORDS * sizeof(unsigned long long), stream);
   if (e != hipSuccess) { set_error("depth_errors: memset: %s", hipGetErrorString(e)); return CODON_ERR_LAUNCH; }
-  const dim3 grid((unsigned)((a.W + EV_TILE - 1) / EV_TILE), (unsigned)((a.H + EV_TILE - 1) / EV_TILE), (unsigned)B);
+  const dim3 grid((unsigned)ev_tiles(a.W), (unsigned)ev_tiles(a.H), (unsigned)B);
   if (bits == 16) {
     typedef unsigned short T;
     hipLaunchKernelGGL(depth_errors_kernel<T>, grid, dim3(EV_THREADS), 0, stream, a, (const T*)label, (const T*)out, (T*)err,

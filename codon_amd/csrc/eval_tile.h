@@ -1,7 +1,8 @@
-// The per-thread bodies of the depth evaluation kernel (eval.hip), written so that the SAME text compiles for the
-// device and for a plain host compiler: tools/eval_host_check.cpp drives them thread by thread under the address and
-// undefined-behaviour sanitizers.  Integers only.  A workgroup of EV_THREADS threads owns one EV_TILE x EV_TILE tile of one
-// image's (H, W) output window and runs four phases with a workgroup barrier between them:
+// The workgroup body of the depth evaluation kernel (eval.hip; wg_eval_tile, over wg.h's group type: DESIGN 12.13)
+// and the per-thread phases it runs, written so that the SAME text compiles for the device and for a plain host compiler: the
+// kernel and tools/eval_host_check.cpp, under the address and undefined-behaviour sanitizers, call the same body.  Integers
+// only.  A workgroup of EV_THREADS threads owns one EV_TILE x EV_TILE tile of one image's (H, W) output window and runs four
+// phases with a workgroup barrier between them:
 //   1 load    the label tile plus a halo of h = r + 1 codes (edge evaluation off: h = 0, no neighbour is read) into `lab`;
 //             a position outside the H x W window is stored as code 0 -- a hole is never a neighbour and never a discontinuity,
 //             which is exactly the rule "a valid 4-neighbour INSIDE the window" -- and the label beyond the window is not read
@@ -12,6 +13,8 @@
 // LDS coordinates: lab[ly][lx] is window position (i0 - h + ly, j0 - h + lx); flag[fy][fx] is (i0 - r + fy, j0 - r + fx),
 // i.e. lab[fy + 1][fx + 1]; rowor[fy][x] is (i0 - r + fy, j0 + x).
 #pragma once
+
+#include "wg.h"
 
 #if defined(__HIPCC__)
 #define CODON_EV_HD __host__ __device__ __forceinline__
@@ -40,6 +43,7 @@ struct EvalArgs {
 };
 
 CODON_EV_HD int ev_halo(const EvalArgs& a) { return a.edge ? a.r + 1 : 0; }
+CODON_EV_HD int ev_tiles(int n) { return (n + EV_TILE - 1) / EV_TILE; }      // the grid is (ev_tiles(W), ev_tiles(H), B)
 
 // phase 1
 template <typename T>
@@ -132,6 +136,31 @@ CODON_EV_HD void ev_pixels(const EvalArgs& a, int tid, int i0, int j0, const T (
     }
     if (err) err[at] = (T)e;
     if (region) region[at] = (unsigned char)reg;
+  }
+}
+
+// workgroup (bx, by, b) of grid (ev_tiles(W), ev_tiles(H), B): one tile of image b.  label / out / err / region: the batches; err
+// and region may be null.  LDS: lab, flag, rowor.  w: the threads' sixteen words of this tile, for the caller to fold
+template <typename T, class G>
+CODON_EV_HD void wg_eval_tile(G wg, int bx, int by, int b, const EvalArgs& a, const T* label, const T* out, T* err,
+                              unsigned char* region, T (*lab)[EV_SIDE], unsigned char (*flag)[EV_FSIDE],
+                              unsigned char (*rowor)[EV_TILE], typename G::template Regs<unsigned long long, EV_WORDS>& w) {
+  const int i0 = by * EV_TILE, j0 = bx * EV_TILE;
+  const long hw = (long)a.H * a.W;
+  WG_EACH(wg, tid) ev_load<T>(a, tid, i0, j0, label + b * a.label_image, lab);
+  wg.sync();
+  if (a.edge) {                                                    // uniform
+    WG_EACH(wg, tid) ev_flags<T>(a, tid, lab, flag);
+    wg.sync();
+    WG_EACH(wg, tid) ev_row_or(a, tid, flag, rowor);
+    wg.sync();
+  }
+  WG_EACH(wg, tid) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < EV_WORDS; ++k) w[tid][k] = 0;
+    ev_pixels<T>(a, tid, i0, j0, lab, rowor, out + b * hw, err ? err + b * hw : nullptr, region ? region + b * hw : nullptr, w[tid]);
   }
 }
 

@@ -1,6 +1,7 @@
-// The per-thread bodies of the guidance-aware (joint) pull-push hole filler (fill_guided.hip), written like
-// fill_tile.h so that the SAME text compiles for the device and for a plain host compiler: tools/guided_fill_host_check.cpp drives
-// them workgroup by workgroup, thread by thread, under the address and undefined-behaviour sanitizers.  Integers only.
+// The guidance-aware (joint) pull-push hole filler (fill_guided.hip): its launch plan (fg_plan), its three
+// workgroup bodies (wg_fillg_*, over wg.h's group type: DESIGN 12.13) and the per-thread phases they run, written like fill_tile.h
+// so that the SAME text compiles for the device and for a plain host compiler: the kernels and tools/guided_fill_host_check.cpp,
+// under the address and undefined-behaviour sanitizers, call the same bodies.  Integers only.
 //
 // Three pyramids ride together, all with fill_tile.h's geometry (tile pyramid: level k at fl_pyr_off(k), row stride FL_TILE >> k;
 // halo pyramid: level k at fl_halo_off(k), side (FL_TILE >> k) + 2):
@@ -18,12 +19,12 @@
 //   fg_plane_load8  A^ and G of a plane that is its own tile from two u8 planes (level 6 of a larger plane, from the workspace)
 //   fg_pull         level k -> k + 1 of v, a and g, and (ws != null) the in-plane cells out to the workspace
 //   fg_push         level k's holes from level k + 1 (a plane that is its own tile)
-//   fg_halo_load8   a u8 halo pyramid from the workspace in one sweep (fl_halo_load's, for A^ and G)
+//   fl_halo_load    (fill_tile.h's, over u8 cells) the halo pyramids of A^ and G from the workspace, one sweep each
 //   fg_halo_g0      the thread's level-0 G of the tile from the workspace into registers
 //   fg_halo_push    the holes of halo level k from halo level k + 1, in place
 //   fg_halo_out     F at level 0 over the tile's cells, to the output plane
 // Workspace of one image, fg_workspace_bytes(h, w) bytes with C = fl_workspace_cells(h, w): V of levels 1 .. K (u16) at 0, A^ at
-// 2 C, G at 3 C (u8, the same level offsets in cells), G_0 (h x w, u8) at 4 C.
+// fg_a_at(C), G at fg_g_at(C) (u8, the same level offsets in cells), G_0 (h x w, u8) at fg_g0_at(C).
 #pragma once
 
 #include <stdint.h>
@@ -35,7 +36,34 @@ namespace codon {
 
 constexpr int FG_TAB = 256;
 
-CODON_FL_HD long fg_workspace_bytes(int h, int w) { return 4 * fl_workspace_cells(h, w) + (long)h * w; }
+// byte offsets of the planes in one image's workspace of C = fl_workspace_cells(h, w) cells per pyramid
+CODON_FL_HD long fg_a_at(long cells) { return 2 * cells; }
+CODON_FL_HD long fg_g_at(long cells) { return 3 * cells; }
+CODON_FL_HD long fg_g0_at(long cells) { return 4 * cells; }
+CODON_FL_HD long fg_workspace_bytes(int h, int w) { return fg_g0_at(fl_workspace_cells(h, w)) + (long)h * w; }
+
+// The launches of an h x w plane: the plain filler's (FlPlan), with the workspace in bytes.  Level 6 of each image: V (u16) at
+// byte v6, A^ and G (u8) at bytes a6 and g6
+struct FgPlan {
+  int single, gx, gy, h6, w6;
+  long v6, a6, g6;
+  long stride;                    // workspace bytes per image: never 0, and images 16 bytes apart
+};
+CODON_FL_HD FgPlan fg_plan(int h, int w) {
+  const FlPlan f = fl_plan(h, w);
+  const long cells = fl_workspace_cells(h, w);
+  FgPlan p;
+  p.single = f.single;
+  p.gx = f.gx;
+  p.gy = f.gy;
+  p.h6 = f.h6;
+  p.w6 = f.w6;
+  p.v6 = 2 * f.l6;
+  p.a6 = fg_a_at(cells) + f.l6;
+  p.g6 = fg_g_at(cells) + f.l6;
+  p.stride = (fg_workspace_bytes(h, w) + 15) / 16 * 16;
+  return p;
+}
 CODON_FL_HD int fg_log2(int s) { return s == 4 ? 2 : s == 8 ? 3 : 4; }
 
 CODON_FL_HD void fg_tab_load(int tid, const unsigned short* tab, unsigned short* t) {
@@ -251,40 +279,6 @@ CODON_FL_HD void fg_push(int tid, int k, int h, int w, unsigned short* v, const 
 
 // ---- the push of one tile of a larger plane -----------------------------------------------------------------------------------
 
-// fl_halo_load for a u8 pyramid: `img` is this image's level 1 of A^ or of G in the workspace
-CODON_FL_HD void fg_halo_load8(int tid, int h, int w, int ty, int tx, const unsigned char* img, unsigned char* hp) {
-  constexpr int PER = (FL_HALO_CELLS + FL_THREADS - 1) / FL_THREADS;                       // 7
-  long base[FL_LOG + 1];
-  base[0] = 0;
-  base[1] = 0;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-  for (int k = 1; k < FL_LOG; ++k) base[k + 1] = base[k] + (long)fl_size(h, k) * fl_size(w, k);
-  unsigned char v[PER];
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-  for (int q = 0; q < PER; ++q) {
-    const int at = tid + q * FL_THREADS, idx = at < FL_HALO_CELLS ? at : FL_HALO_CELLS - 1;
-    const int k = idx < 9 ? 6 : idx < 25 ? 5 : idx < 61 ? 4 : idx < 161 ? 3 : idx < 485 ? 2 : 1;
-    const long lb = k == 6 ? base[6] : k == 5 ? base[5] : k == 4 ? base[4] : k == 3 ? base[3] : k == 2 ? base[2] : base[1];
-    const int n = FL_TILE >> k, s = n + 2, r = idx - fl_halo_off(k);
-    const int i = r / s, j = r - i * s;
-    const int gy = ty * n - 1 + i, gx = tx * n - 1 + j;
-    const int hk = fl_size(h, k), wk = fl_size(w, k);
-    const int cy = gy < 0 ? 0 : gy < hk ? gy : hk - 1, cx = gx < 0 ? 0 : gx < wk ? gx : wk - 1;
-    v[q] = img[lb + (long)cy * wk + cx];                         // no branch around the load: the loads go out together
-  }
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-  for (int q = 0; q < PER; ++q) {
-    const int idx = tid + q * FL_THREADS;
-    if (idx < FL_HALO_CELLS) hp[idx] = v[q];
-  }
-}
-
 // the thread's level-0 guidance of the tile from the workspace's G_0 plane (h x w); unused outside the plane
 CODON_FL_HD void fg_halo_g0(int tid, int h, int w, int ty, int tx, const unsigned char* ws_g0, int* g0) {
 #if defined(__HIPCC__)
@@ -347,6 +341,98 @@ CODON_FL_HD void fg_halo_out(int tid, int h, int w, int ty, int tx, const int* v
     const int gy = ty * FL_TILE + (idx >> FL_LOG), gx = tx * FL_TILE + (idx & (FL_TILE - 1));
     if (gy < h && gx < w) fl_store<FMT>(out, (long)gy * w + gx, f[q], nullptr);
   }
+}
+
+// ---- the workgroup bodies -------------------------------------------------------------------------------------------------------
+// LDS: v (u16), a and g (u8) are FL_PYR_CELLS cells each; hv (u16), ha and hg (u8) FL_HALO_CELLS cells each; t is FG_TAB u16.
+
+// one phase: G_0 (and A_0) of the tile at (y0, x0) from the guidance image, by the scale
+template <class G>
+CODON_FL_HD void wg_fillg_g0(G wg, int scale, const unsigned char* gimg, long row_bytes, int h, int w, int y0, int x0,
+                             unsigned char* g, unsigned char* a, unsigned char* ws_g0) {
+  if (scale == 4) {
+    WG_EACH(wg, tid) fg_g0_tile<4>(tid, gimg, row_bytes, h, w, y0, x0, g, a, ws_g0);
+  } else if (scale == 8) {
+    WG_EACH(wg, tid) fg_g0_tile<8>(tid, gimg, row_bytes, h, w, y0, x0, g, a, ws_g0);
+  } else {
+    WG_EACH(wg, tid) fg_g0_tile<16>(tid, gimg, row_bytes, h, w, y0, x0, g, a, ws_g0);
+  }
+}
+
+// workgroup b of grid (B): the h x w plane that is its own tile.  in / out: image b at + b * stride elements; they may be the
+// same buffer (level 6 of the workspace).  guide != null: G_0 from image b of the guidance; else A^ and G of the plane from
+// a0 / g0 (image b at + b * ag_stride bytes)
+template <int FMT, class G>
+CODON_FL_HD void wg_fillg_plane(G wg, long b, const void* in, long in_stride, void* out, long out_stride, int h, int w, int top,
+                                const unsigned char* guide, long row_bytes, long image_bytes, int scale, const unsigned char* a0,
+                                const unsigned char* g0, long ag_stride, const unsigned short* tab, unsigned short* v,
+                                unsigned char* a, unsigned char* g, unsigned short* t) {
+  const int K = fl_top_level(h, w);                                // uniform, <= FL_LOG
+  WG_EACH(wg, tid) {
+    fg_tab_load(tid, tab, t);
+    fl_tile_load<FMT>(tid, (const char*)in + b * in_stride * fl_elem_bytes(FMT), h, w, 0, 0, top, v);
+  }
+  if (guide) {
+    wg_fillg_g0(wg, scale, guide + b * image_bytes, row_bytes, h, w, 0, 0, g, a, nullptr);
+  } else {
+    WG_EACH(wg, tid) fg_plane_load8(tid, a0 + b * ag_stride, g0 + b * ag_stride, h, w, a, g);
+  }
+  wg.sync();
+  for (int k = 0; k < K; ++k) {
+    WG_EACH(wg, tid) fg_pull(tid, k, v, a, g, h, w, 0, 0, nullptr, nullptr, nullptr);
+    wg.sync();
+  }
+  for (int k = K - 1; k >= 0; --k) {
+    WG_EACH(wg, tid) fg_push(tid, k, h, w, v, a, g, t);
+    wg.sync();
+  }
+  WG_EACH(wg, tid) fl_tile_store<FMT>(tid, (char*)out + b * out_stride * fl_elem_bytes(FMT), h, w, nullptr, v);
+}
+
+// workgroup (tx, ty, b) of grid (gx, gy, B): V_0 and G_0 of one tile (G_0 also to the workspace), then levels 1 .. 6 of the
+// three pyramids to the workspace.  ws: image b at + b * ws_stride bytes
+template <int FMT, class G>
+CODON_FL_HD void wg_fillg_pull(G wg, int tx, int ty, long b, const void* in, int h, int w, int top, const unsigned char* guide,
+                               long row_bytes, long image_bytes, int scale, unsigned char* ws, long ws_stride, unsigned short* v,
+                               unsigned char* a, unsigned char* g) {
+  const long cells = fl_workspace_cells(h, w);
+  unsigned char* img = ws + b * ws_stride;
+  WG_EACH(wg, tid)
+    fl_tile_load<FMT>(tid, (const char*)in + b * h * w * fl_elem_bytes(FMT), h, w, ty * FL_TILE, tx * FL_TILE, top, v);
+  wg_fillg_g0(wg, scale, guide + b * image_bytes, row_bytes, h, w, ty * FL_TILE, tx * FL_TILE, g, a, img + fg_g0_at(cells));
+  wg.sync();
+  long at = 0;                                                      // level k + 1 of this image, in cells
+  for (int k = 0; k < FL_LOG; ++k) {
+    WG_EACH(wg, tid)
+      fg_pull(tid, k, v, a, g, h, w, ty, tx, (unsigned short*)img + at, img + fg_a_at(cells) + at, img + fg_g_at(cells) + at);
+    at += (long)fl_size(h, k + 1) * fl_size(w, k + 1);
+    wg.sync();
+  }
+}
+
+// workgroup (tx, ty, b) of grid (gx, gy, B): one tile's holes from the workspace's filled level 6 down, to the output
+template <int FMT, class G>
+CODON_FL_HD void wg_fillg_push(G wg, int tx, int ty, long b, const void* in, void* out, int h, int w, int top,
+                               const unsigned short* tab, const unsigned char* ws, long ws_stride, unsigned short* hv,
+                               unsigned char* ha, unsigned char* hg, unsigned short* t) {
+  const long at = b * h * w * fl_elem_bytes(FMT);
+  const long cells = fl_workspace_cells(h, w);
+  const unsigned char* img = ws + b * ws_stride;
+  typename G::template Regs<int, FL_PER_THREAD> v0(wg), g0(wg);
+  WG_EACH(wg, tid) {
+    fg_tab_load(tid, tab, t);
+    fl_halo_load<true>(tid, h, w, ty, tx, (const unsigned short*)img, hv);
+    fl_halo_load<false>(tid, h, w, ty, tx, img + fg_a_at(cells), ha);
+    fl_halo_load<false>(tid, h, w, ty, tx, img + fg_g_at(cells), hg);
+    fl_halo_in<FMT>(tid, h, w, ty, tx, (const char*)in + at, top, v0[tid]);
+    fg_halo_g0(tid, h, w, ty, tx, img + fg_g0_at(cells), g0[tid]);
+  }
+  wg.sync();
+  for (int k = FL_LOG - 1; k >= 1; --k) {
+    WG_EACH(wg, tid) fg_halo_push(tid, k, h, w, ty, tx, hv, ha, hg, t);
+    wg.sync();
+  }
+  WG_EACH(wg, tid) fg_halo_out<FMT>(tid, h, w, ty, tx, v0[tid], g0[tid], hv, ha, t, (char*)out + at);
 }
 
 }  // namespace codon

@@ -1,8 +1,8 @@
 // Pull-push hole filling of low-resolution code planes (codon_amd.upsample.fill_holes): code 0 is a hole, the
 // plane is pulled up a pyramid of means over the valid children and pushed back down, a hole taking the 9/3/3/1 mix of the
 // filled level above.  A DEFINITION of this project, in integers, restated in numpy in tests/fill_ref.py; the kernels are held
-// to its bits.  u8 codes, u16 codes and fp32 on the code grid share the one integer core; the per-thread bodies are in
-// fill_tile.h, shared with the host-side sanitizer check.
+// to its bits.  u8 codes, u16 codes and fp32 on the code grid share the one integer core; the launch plan, the workgroup bodies and
+// their phases are in fill_tile.h, and the host-side sanitizer check calls the same bodies.
 //
 // The launches depend on (B, h, w) alone, never on the hole pattern; no atomics, no flag, no wait on another workgroup: levels
 // pass between workgroups only across kernel boundaries.
@@ -23,99 +23,65 @@
 
 namespace codon {
 
-// grid (B).  in / out: image b at + b * stride elements; they may be the same buffer (level 6 of the workspace)
+// grid (B)
 template <int FMT>
 __global__ __launch_bounds__(FL_THREADS) void fill_plane_kernel(const void* in, long in_stride, void* out, long out_stride, int h,
                                                                 int w, const float* __restrict__ tab, int top) {
   __shared__ unsigned short pyr[FL_PYR_CELLS];
-  const int tid = threadIdx.x;
-  const long b = blockIdx.x;
-  const int K = fl_top_level(h, w);                                // uniform, <= FL_LOG
-  fl_tile_load<FMT>(tid, (const char*)in + b * in_stride * fl_elem_bytes(FMT), h, w, 0, 0, top, pyr);
-  __syncthreads();
-  for (int k = 0; k < K; ++k) {
-    fl_tile_pull(tid, k, pyr, nullptr, h, w, 0, 0);
-    __syncthreads();
-  }
-  for (int k = K - 1; k >= 0; --k) {
-    fl_tile_push(tid, k, h, w, pyr);
-    __syncthreads();
-  }
-  fl_tile_store<FMT>(tid, (char*)out + b * out_stride * fl_elem_bytes(FMT), h, w, tab, pyr);
+  wg_fill_plane<FMT>(WgDevice(), blockIdx.x, in, in_stride, out, out_stride, h, w, tab, top, pyr);
 }
 
-// grid (ceil(w/64), ceil(h/64), B)
+// grid (gx, gy, B) of fl_plan
 template <int FMT>
 __global__ __launch_bounds__(FL_THREADS) void fill_pull_kernel(const void* __restrict__ in, int h, int w, int top,
                                                                unsigned short* __restrict__ ws, long ws_stride) {
   __shared__ unsigned short pyr[FL_PYR_CELLS];
-  const int tid = threadIdx.x, tx = blockIdx.x, ty = blockIdx.y;
-  const long b = blockIdx.z;
-  fl_tile_load<FMT>(tid, (const char*)in + b * h * w * fl_elem_bytes(FMT), h, w, ty * FL_TILE, tx * FL_TILE, top, pyr);
-  __syncthreads();
-  unsigned short* lvl = ws + b * ws_stride;                         // level k + 1 of this image
-  for (int k = 0; k < FL_LOG; ++k) {
-    fl_tile_pull(tid, k, pyr, lvl, h, w, ty, tx);
-    lvl += (long)fl_size(h, k + 1) * fl_size(w, k + 1);
-    __syncthreads();
-  }
+  wg_fill_pull<FMT>(WgDevice(), blockIdx.x, blockIdx.y, blockIdx.z, in, h, w, top, ws, ws_stride, pyr);
 }
 
-// grid (ceil(w/64), ceil(h/64), B)
+// grid (gx, gy, B) of fl_plan
 template <int FMT>
 __global__ __launch_bounds__(FL_THREADS) void fill_push_kernel(const void* __restrict__ in, void* __restrict__ out, int h, int w,
                                                                const float* __restrict__ tab, int top,
                                                                const unsigned short* __restrict__ ws, long ws_stride) {
   __shared__ unsigned short hp[FL_HALO_CELLS];
-  const int tid = threadIdx.x, tx = blockIdx.x, ty = blockIdx.y;
-  const long b = blockIdx.z;
-  const long at = b * h * w * fl_elem_bytes(FMT);
-  int v0[FL_PER_THREAD];
-  fl_halo_load(tid, h, w, ty, tx, ws + b * ws_stride, hp);
-  fl_halo_in<FMT>(tid, h, w, ty, tx, (const char*)in + at, top, v0);
-  __syncthreads();
-  for (int k = FL_LOG - 1; k >= 1; --k) {
-    fl_halo_push(tid, k, h, w, ty, tx, hp);
-    __syncthreads();
-  }
-  fl_halo_out<FMT>(tid, h, w, ty, tx, v0, hp, (char*)out + at, tab);
+  wg_fill_push<FMT>(WgDevice(), blockIdx.x, blockIdx.y, blockIdx.z, in, out, h, w, tab, top, ws, ws_stride, hp);
 }
 
 template <int FMT>
 static int fill_launch(int B, int h, int w, const void* in, const float* tab, int top, void* out, unsigned short* ws,
-                       long ws_stride, hipStream_t stream) {
-  if (h <= FL_TILE && w <= FL_TILE) {
+                       hipStream_t stream) {
+  const FlPlan p = fl_plan(h, w);
+  if (p.single) {
     hipLaunchKernelGGL(fill_plane_kernel<FMT>, dim3((unsigned)B), dim3(FL_THREADS), 0, stream, in, (long)h * w, out, (long)h * w,
                        h, w, tab, top);
     return check_launch("fill_plane_kernel");
   }
-  const dim3 grid((unsigned)((w + FL_TILE - 1) / FL_TILE), (unsigned)((h + FL_TILE - 1) / FL_TILE), (unsigned)B);
-  hipLaunchKernelGGL(fill_pull_kernel<FMT>, grid, dim3(FL_THREADS), 0, stream, in, h, w, top, ws, ws_stride);
+  const dim3 grid((unsigned)p.gx, (unsigned)p.gy, (unsigned)B);
+  hipLaunchKernelGGL(fill_pull_kernel<FMT>, grid, dim3(FL_THREADS), 0, stream, in, h, w, top, ws, p.stride);
   int st = check_launch("fill_pull_kernel");
   if (st != CODON_OK) return st;
-  unsigned short* l6 = ws + fl_level_offset(h, w, FL_LOG);
-  hipLaunchKernelGGL(fill_plane_kernel<FL_U16>, dim3((unsigned)B), dim3(FL_THREADS), 0, stream, (const void*)l6, ws_stride,
-                     (void*)l6, ws_stride, fl_size(h, FL_LOG), fl_size(w, FL_LOG), (const float*)nullptr, 65535);
+  unsigned short* l6 = ws + p.l6;
+  hipLaunchKernelGGL(fill_plane_kernel<FL_U16>, dim3((unsigned)B), dim3(FL_THREADS), 0, stream, (const void*)l6, p.stride,
+                     (void*)l6, p.stride, p.h6, p.w6, (const float*)nullptr, 65535);
   st = check_launch("fill_plane_kernel");
   if (st != CODON_OK) return st;
   hipLaunchKernelGGL(fill_push_kernel<FMT>, grid, dim3(FL_THREADS), 0, stream, in, out, h, w, tab, top,
-                     (const unsigned short*)ws, ws_stride);
+                     (const unsigned short*)ws, p.stride);
   return check_launch("fill_push_kernel");
 }
 
 size_t fill_holes_workspace_bytes(int h, int w) {
   if (h < 1 || h > FL_MAX_SIDE || w < 1 || w > FL_MAX_SIDE) return 0;
-  const size_t bytes = 2 * (size_t)fl_workspace_cells(h, w);
-  return bytes < 16 ? 16 : (bytes + 15) / 16 * 16;                 // never 0 for a shape that is taken; images 16 bytes apart
+  return sizeof(unsigned short) * (size_t)fl_plan(h, w).stride;
 }
 
 int fill_holes(int B, int h, int w, const void* in, int fmt, const float* tab, int top, void* out, void* workspace,
                hipStream_t stream) {
-  const long ws_stride = (long)(fill_holes_workspace_bytes(h, w) / 2);
   unsigned short* ws = (unsigned short*)workspace;
-  if (fmt == FL_U8) return fill_launch<FL_U8>(B, h, w, in, tab, top, out, ws, ws_stride, stream);
-  if (fmt == FL_U16) return fill_launch<FL_U16>(B, h, w, in, tab, top, out, ws, ws_stride, stream);
-  return fill_launch<FL_F32>(B, h, w, in, tab, top, out, ws, ws_stride, stream);
+  if (fmt == FL_U8) return fill_launch<FL_U8>(B, h, w, in, tab, top, out, ws, stream);
+  if (fmt == FL_U16) return fill_launch<FL_U16>(B, h, w, in, tab, top, out, ws, stream);
+  return fill_launch<FL_F32>(B, h, w, in, tab, top, out, ws, stream);
 }
 
 }  // namespace codon

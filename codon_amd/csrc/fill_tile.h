@@ -1,8 +1,9 @@
-// The per-thread bodies of the pull-push hole filler (fill_holes.hip), written so that the SAME text compiles for
-// the device and for a plain host compiler: tools/fill_host_check.cpp drives them workgroup by workgroup, thread by thread,
-// under the address and undefined-behaviour sanitizers.  Integers only past the load: a plane of codes (0 a hole) is pulled
-// up a pyramid of means over the valid children, level k+1 of size ceil(h_k / 2) x ceil(w_k / 2) up to 1 x 1, and pushed back
-// down, a hole taking the 9/3/3/1 mix of the filled level above.  Levels are u16 cells, 0 a hole.
+// The pull-push hole filler (fill_holes.hip): its launch plan (fl_plan), its three workgroup bodies (wg_fill_*,
+// over wg.h's group type: DESIGN 12.13) and the per-thread phases they run, written so that the SAME text compiles for the
+// device and for a plain host compiler: the kernels and tools/fill_host_check.cpp, under the address and undefined-behaviour
+// sanitizers, call the same bodies.  Integers only past the load: a plane of codes (0 a hole) is pulled up a pyramid of means
+// over the valid children, level k+1 of size ceil(h_k / 2) x ceil(w_k / 2) up to 1 x 1, and pushed back down, a hole taking the
+// 9/3/3/1 mix of the filled level above.  Levels are u16 cells, 0 a hole.
 //
 // A workgroup of FL_THREADS threads works on an aligned FL_TILE x FL_TILE tile of level 0 (a plane up to FL_TILE x FL_TILE is
 // its own tile) and runs phases with a workgroup barrier between them.
@@ -25,6 +26,8 @@
 #pragma once
 
 #include <math.h>
+
+#include "wg.h"
 
 #if defined(__HIPCC__)
 #define CODON_FL_HD __host__ __device__ __forceinline__
@@ -56,6 +59,27 @@ CODON_FL_HD long fl_level_offset(int h, int w, int k) {                         
 CODON_FL_HD long fl_workspace_cells(int h, int w) { return fl_level_offset(h, w, fl_top_level(h, w) + 1); }
 CODON_FL_HD int fl_pyr_off(int k) { return (16384 - (16384 >> (2 * k))) / 3; }             // 0, 4096, 5120, 5376, ...
 CODON_FL_HD int fl_elem_bytes(int fmt) { return fmt == FL_U8 ? 1 : fmt == FL_U16 ? 2 : 4; }
+
+// The launches of an h x w plane, a function of the shape alone.  single: one launch of the plane body, one workgroup per
+// image.  Else three: the pull body over gx x gy tiles per image, the plane body on level 6 of the workspace (h6 x w6 u16 cells
+// at cell l6 of each image, in place), the push body over the same tiles.
+struct FlPlan {
+  int single, gx, gy, h6, w6;
+  long l6;
+  long stride;                    // workspace cells (u16) per image: never 0, and images 16 bytes apart
+};
+CODON_FL_HD FlPlan fl_plan(int h, int w) {
+  FlPlan p;
+  p.single = h <= FL_TILE && w <= FL_TILE;
+  p.gx = fl_size(w, FL_LOG);
+  p.gy = fl_size(h, FL_LOG);
+  p.h6 = p.gy;                    // a level-6 cell is a tile
+  p.w6 = p.gx;
+  p.l6 = fl_level_offset(h, w, FL_LOG);
+  const long cells = fl_workspace_cells(h, w);
+  p.stride = cells < 8 ? 8 : (cells + 7) / 8 * 8;
+  return p;
+}
 
 // the code of element i.  fp32 on the code grid: rintf(v * top) is exact for v = tab[c]; a value off the grid is rounded
 // onto it and clamped to top, and anything that is not positive (0.0f, a negative, a NaN) is a hole
@@ -163,8 +187,10 @@ CODON_FL_HD int fl_halo_off(int k) {                                            
 
 // phase 1: the whole halo pyramid from this image's workspace `img` in ONE sweep -- F at level FL_LOG (already filled), V at
 // levels FL_LOG - 1 .. 1.  Every thread first issues all of its loads, then stores them: one trip to memory, not one per level.
-// A cell outside the plane is stored as 0 and never read.
-CODON_FL_HD void fl_halo_load(int tid, int h, int w, int ty, int tx, const unsigned short* img, unsigned short* hp) {
+// `img` is this image's level 1 of one pyramid in the workspace.  HOLES: the cells are codes, 0 a hole (V, u16), and a cell
+// outside the plane is stored as 0; else (the guided filler's A^ and G, u8) as its nearest cell inside.  Never read, either way.
+template <bool HOLES, typename T>
+CODON_FL_HD void fl_halo_load(int tid, int h, int w, int ty, int tx, const T* img, T* hp) {
   constexpr int PER = (FL_HALO_CELLS + FL_THREADS - 1) / FL_THREADS;                       // 7
   long base[FL_LOG + 1];
   base[0] = 0;
@@ -173,7 +199,7 @@ CODON_FL_HD void fl_halo_load(int tid, int h, int w, int ty, int tx, const unsig
 #pragma unroll
 #endif
   for (int k = 1; k < FL_LOG; ++k) base[k + 1] = base[k] + (long)fl_size(h, k) * fl_size(w, k);
-  unsigned short v[PER];
+  T v[PER];
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
@@ -186,8 +212,8 @@ CODON_FL_HD void fl_halo_load(int tid, int h, int w, int ty, int tx, const unsig
     const int gy = ty * n - 1 + i, gx = tx * n - 1 + j;
     const int hk = fl_size(h, k), wk = fl_size(w, k);
     const int cy = gy < 0 ? 0 : gy < hk ? gy : hk - 1, cx = gx < 0 ? 0 : gx < wk ? gx : wk - 1;
-    const unsigned short c = img[lb + (long)cy * wk + cx];       // no branch around the load: the loads go out together
-    v[q] = (cy == gy && cx == gx) ? c : (unsigned short)0;
+    const T c = img[lb + (long)cy * wk + cx];                    // no branch around the load: the loads go out together
+    v[q] = (!HOLES || (cy == gy && cx == gx)) ? c : (T)0;
   }
 #if defined(__HIPCC__)
 #pragma unroll
@@ -254,6 +280,61 @@ CODON_FL_HD void fl_halo_out(int tid, int h, int w, int ty, int tx, const int* v
     if (v == 0) v = fl_halo_mix(gy, gx, hu, wu, up, su, uy0, ux0);
     fl_store<FMT>(out, (long)gy * w + gx, v, tab);
   }
+}
+
+// ---- the workgroup bodies -------------------------------------------------------------------------------------------------------
+// LDS: pyr is FL_PYR_CELLS cells, hp is FL_HALO_CELLS cells.
+
+// workgroup b of grid (B): the h x w plane that is its own tile.  in / out: image b at + b * stride elements; they may be the
+// same buffer (level 6 of the workspace): the whole plane is in LDS before any of it is written
+template <int FMT, class G>
+CODON_FL_HD void wg_fill_plane(G wg, long b, const void* in, long in_stride, void* out, long out_stride, int h, int w,
+                               const float* tab, int top, unsigned short* pyr) {
+  const int K = fl_top_level(h, w);                                // uniform, <= FL_LOG
+  WG_EACH(wg, tid) fl_tile_load<FMT>(tid, (const char*)in + b * in_stride * fl_elem_bytes(FMT), h, w, 0, 0, top, pyr);
+  wg.sync();
+  for (int k = 0; k < K; ++k) {
+    WG_EACH(wg, tid) fl_tile_pull(tid, k, pyr, nullptr, h, w, 0, 0);
+    wg.sync();
+  }
+  for (int k = K - 1; k >= 0; --k) {
+    WG_EACH(wg, tid) fl_tile_push(tid, k, h, w, pyr);
+    wg.sync();
+  }
+  WG_EACH(wg, tid) fl_tile_store<FMT>(tid, (char*)out + b * out_stride * fl_elem_bytes(FMT), h, w, tab, pyr);
+}
+
+// workgroup (tx, ty, b) of grid (gx, gy, B): levels 1 .. 6 of one tile, to the workspace
+template <int FMT, class G>
+CODON_FL_HD void wg_fill_pull(G wg, int tx, int ty, long b, const void* in, int h, int w, int top, unsigned short* ws,
+                              long ws_stride, unsigned short* pyr) {
+  WG_EACH(wg, tid)
+    fl_tile_load<FMT>(tid, (const char*)in + b * h * w * fl_elem_bytes(FMT), h, w, ty * FL_TILE, tx * FL_TILE, top, pyr);
+  wg.sync();
+  unsigned short* lvl = ws + b * ws_stride;                         // level k + 1 of this image
+  for (int k = 0; k < FL_LOG; ++k) {
+    WG_EACH(wg, tid) fl_tile_pull(tid, k, pyr, lvl, h, w, ty, tx);
+    lvl += (long)fl_size(h, k + 1) * fl_size(w, k + 1);
+    wg.sync();
+  }
+}
+
+// workgroup (tx, ty, b) of grid (gx, gy, B): one tile's holes from the workspace's filled level 6 down, to the output
+template <int FMT, class G>
+CODON_FL_HD void wg_fill_push(G wg, int tx, int ty, long b, const void* in, void* out, int h, int w, const float* tab, int top,
+                              const unsigned short* ws, long ws_stride, unsigned short* hp) {
+  const long at = b * h * w * fl_elem_bytes(FMT);
+  typename G::template Regs<int, FL_PER_THREAD> v0(wg);
+  WG_EACH(wg, tid) {
+    fl_halo_load<true>(tid, h, w, ty, tx, ws + b * ws_stride, hp);
+    fl_halo_in<FMT>(tid, h, w, ty, tx, (const char*)in + at, top, v0[tid]);
+  }
+  wg.sync();
+  for (int k = FL_LOG - 1; k >= 1; --k) {
+    WG_EACH(wg, tid) fl_halo_push(tid, k, h, w, ty, tx, hp);
+    wg.sync();
+  }
+  WG_EACH(wg, tid) fl_halo_out<FMT>(tid, h, w, ty, tx, v0[tid], hp, (char*)out + at, tab);
 }
 
 }  // namespace codon

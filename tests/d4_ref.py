@@ -80,7 +80,7 @@ def self_ensemble(model, x, y, dt):
     return merge(upcast(model(ux, uy), dt), upcast(model(tx, ty), dt))
 
 
-# ---- test inputs (shared by tests/test_gpu_d4.py and tools/d4_host_check.py) -------------------------------------------------
+# ---- test inputs (shared by tests/test_gpu_d4.py and tools/host_check.py) -------------------------------------------------
 
 SHAPES = ((1, 5, 7), (1, 32, 32), (1, 33, 70), (3, 37, 53))       # B x H x W: below one 32 x 32 tile, exactly one, ragged, a batch
 BITS = {"f32": np.uint32, "f16": np.uint16, "bf16": np.uint16}

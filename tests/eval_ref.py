@@ -100,7 +100,7 @@ def depth_report(words, unit=1.0, thresholds=()):
     return r
 
 
-# ---- test inputs (shared by tests/test_eval_cpu.py, tests/test_gpu_eval.py and tools/eval_host_check.py) ---------------------
+# ---- test inputs (shared by tests/test_eval_cpu.py, tests/test_gpu_eval.py and tools/host_check.py) ---------------------
 
 SHAPES = ((1, 5, 7), (1, 32, 32), (1, 33, 70), (3, 37, 53))       # B x H x W: below one halo, exactly one tile, ragged, a batch
 RADII = (0, 1, 3, 8)

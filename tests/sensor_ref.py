@@ -96,7 +96,7 @@ def sensor(lr, masked, key, step, first, sigma, quad, edge_thr, p_drop, p_edge, 
     return (out, hole, dropped, e, g) if with_parts else out
 
 
-# ---- test inputs (shared by tests/test_gpu_sensor.py and tools/sensor_host_check.py) ------------------------------------------
+# ---- test inputs (shared by tests/test_gpu_sensor.py and tools/host_check.py) ------------------------------------------
 
 SIZES = (4, 7, 33)                 # the upsampler's minimum, a row shorter than a wavefront, no multiple of the block
 BATCHES = (1, 5, 64)

@@ -1,5 +1,5 @@
 """The sensor model of the training degradation on the MI355X.  The yardstick is the numpy restatement in
-tests/sensor_ref.py (pinned on the CPU by tests/test_sensor_cpu.py and, through tools/sensor_host_check.py, equal byte for byte
+tests/sensor_ref.py (pinned on the CPU by tests/test_sensor_cpu.py and, through tools/host_check.py, equal byte for byte
 to the kernel's own text compiled for the host); the bar is EQUAL BITS: codon_lr_sensor over every size, batch, level count,
 mode, parameter set and hole pattern of sensor_ref.cases, its hole and snap properties, shards against one launch, the whole of
 synthesize(sensor=...) against the composition of the existing restatements, and training that resumes bit for bit."""

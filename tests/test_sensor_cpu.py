@@ -1,7 +1,7 @@
 """The sensor model of the training degradation, what needs no GPU: Philox4x32-10 in the library and in the numpy
 restatement against the published known-answer vectors, the Gaussian table, the statistics of the definition (on the
 restatement alone), every host-side refusal of codon_lr_sensor, of synthesize, of fit and of the command line, the
-checkpoint keys.  (The host-side sanitizer check of the kernel's own text: tests/test_tools_sensor.py.)"""
+checkpoint keys.  (The host-side sanitizer check of the kernel's own text: tests/test_tools_host_checks.py.)"""
 import ctypes as C
 import math
 import os

@@ -1,92 +1,69 @@
-// Host-side check of the depth evaluation kernel's tile, halo and dilation arithmetic: the four per-thread phase
-// bodies of csrc/eval_tile.h -- the very text the device kernel of csrc/eval.hip calls -- compiled for the host and driven block
-// by block, thread by thread, phase by phase over exactly-sized heap buffers, so that the address and undefined-behaviour
-// sanitizers see every access.  Only the wave / workgroup reduction is the device's own; here the threads' words are added up
-// (word 3: the maximum) in plain C++.  No GPU, no HIP, nothing loaded into Python.  tools/eval_host_check.py builds this with
-//   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all
-// runs it over the GPU tests' cases and compares what it writes with tests/eval_ref.py, bit for bit.
+// Host-side check of the depth evaluation kernel: the workgroup body of csrc/eval_tile.h -- the very text the
+// device kernel of csrc/eval.hip calls -- compiled for the host and run workgroup by workgroup over exactly-sized heap buffers
+// (the LDS arrays too), so that the address and undefined-behaviour sanitizers see every access.  Only the wave / workgroup
+// reduction after the body is the device's own; here the threads' words are added up (word 3: the maximum) in plain C++.  Every
+// case runs with the threads of a workgroup forwards and backwards, and the two outputs must agree.  No GPU, no HIP, nothing
+// loaded into Python.  `python tools/host_check.py eval` builds this, runs it over the GPU tests' cases and compares what it
+// writes with tests/eval_ref.py, bit for bit.
 //
 //   eval_host_check <bits 8|16> B H W Hl Wl <nthr> t0 t1 t2 t3 <edge 0|1> T r label.bin out.bin out_prefix
 //     label.bin: (B, Hl, Wl) codes, out.bin: (B, H, W) codes  ->  out_prefix.{acc (B,16) u64, err (B,H,W) codes, reg (B,H,W) u8}
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
+#include "host_check.h"
 
 #include "../codon_amd/csrc/eval_tile.h"
 
 using namespace codon;
 
-static void* slurp(const char* path, size_t bytes) {
-  void* p = malloc(bytes);                      // exactly `bytes`: one element past either end is a sanitizer report
-  FILE* f = fopen(path, "rb");
-  if (!p || !f || fread(p, 1, bytes, f) != bytes || fgetc(f) != EOF) {
-    fprintf(stderr, "eval_host_check: %s does not hold exactly %zu bytes\n", path, bytes);
-    exit(2);
-  }
-  fclose(f);
-  return p;
-}
-
-static void dump(const std::string& path, const void* p, size_t bytes) {
-  FILE* f = fopen(path.c_str(), "wb");
-  if (!f || fwrite(p, 1, bytes, f) != bytes || fclose(f) != 0) {
-    fprintf(stderr, "eval_host_check: cannot write %s\n", path.c_str());
-    exit(2);
-  }
-}
-
-// the launch of depth_errors_kernel<T>: grid (ceil(W/32), ceil(H/32), B)
 template <typename T>
 static int run(const EvalArgs& a, int B, int Hl, const char* fl, const char* fo, const std::string& prefix) {
-  const size_t n = (size_t)B * a.H * a.W;
-  T* label = (T*)slurp(fl, (size_t)B * Hl * a.label_row * sizeof(T));
-  T* out = (T*)slurp(fo, n * sizeof(T));
-  T* err = (T*)malloc(n * sizeof(T));
-  unsigned char* reg = (unsigned char*)malloc(n);
-  unsigned long long* acc = (unsigned long long*)calloc((size_t)B * EV_WORDS, sizeof(unsigned long long));   // the entry's memset
-  memset(err, 0xEE, n * sizeof(T));             // an element no thread writes stays this
-  memset(reg, 0xEE, n);
-  const long hw = (long)a.H * a.W;
-  for (int b = 0; b < B; ++b)
-    for (int by = 0; by < (a.H + EV_TILE - 1) / EV_TILE; ++by)
-      for (int bx = 0; bx < (a.W + EV_TILE - 1) / EV_TILE; ++bx) {
-        T lab[EV_SIDE][EV_SIDE];
-        unsigned char flag[EV_FSIDE][EV_FSIDE], rowor[EV_FSIDE][EV_TILE];
-        memset(lab, 0xCD, sizeof(lab));         // what a phase reads without an earlier phase having written it shows as this
-        memset(flag, 0xCD, sizeof(flag));
-        memset(rowor, 0xCD, sizeof(rowor));
-        const int i0 = by * EV_TILE, j0 = bx * EV_TILE;
-        for (int t = 0; t < EV_THREADS; ++t) ev_load<T>(a, t, i0, j0, label + b * a.label_image, lab);
-        if (a.edge) {
-          for (int t = 0; t < EV_THREADS; ++t) ev_flags<T>(a, t, lab, flag);
-          for (int t = 0; t < EV_THREADS; ++t) ev_row_or(a, t, flag, rowor);
+  const size_t n = (size_t)B * a.H * a.W, words = (size_t)B * EV_WORDS * sizeof(unsigned long long);
+  T* label = hc_read<T>(fl, (size_t)B * Hl * a.label_row * sizeof(T));
+  T* out = hc_read<T>(fo, n * sizeof(T));
+  T* err[2];
+  unsigned char* reg[2];
+  unsigned long long* acc[2];
+  for (int rev = 0; rev < 2; ++rev) {
+    const WgHost wg{EV_THREADS, rev != 0};
+    err[rev] = hc_alloc<T>(n * sizeof(T), 0xEE);
+    reg[rev] = hc_alloc<unsigned char>(n, 0xEE);
+    acc[rev] = hc_alloc<unsigned long long>(words, 0);              // the entry's memset
+    for (int b = 0; b < B; ++b)                                     // the launch of depth_errors_kernel<T>
+      for (int by = 0; by < ev_tiles(a.H); ++by)
+        for (int bx = 0; bx < ev_tiles(a.W); ++bx) {
+          typedef T LabRow[EV_SIDE];
+          typedef unsigned char FlagRow[EV_FSIDE];
+          typedef unsigned char OrRow[EV_TILE];
+          LabRow* lab = hc_alloc<LabRow>(sizeof(LabRow) * EV_SIDE, 0xCD);
+          FlagRow* flag = hc_alloc<FlagRow>(sizeof(FlagRow) * EV_FSIDE, 0xCD);
+          OrRow* rowor = hc_alloc<OrRow>(sizeof(OrRow) * EV_FSIDE, 0xCD);
+          WgHost::Regs<unsigned long long, EV_WORDS> w(wg);
+          wg_eval_tile<T>(wg, bx, by, b, a, label, out, err[rev], reg[rev], lab, flag, rowor, w);
+          for (int t = 0; t < EV_THREADS; ++t)
+            for (int k = 0; k < EV_WORDS; ++k) {
+              unsigned long long& d = acc[rev][(size_t)b * EV_WORDS + k];
+              d = k == 3 ? (w[t][k] > d ? w[t][k] : d) : d + w[t][k];
+            }
+          free(lab);
+          free(flag);
+          free(rowor);
         }
-        for (int t = 0; t < EV_THREADS; ++t) {
-          unsigned long long w[EV_WORDS] = {0};
-          ev_pixels<T>(a, t, i0, j0, lab, rowor, out + b * hw, err + b * hw, reg + b * hw, w);
-          for (int k = 0; k < EV_WORDS; ++k) {
-            unsigned long long& d = acc[(size_t)b * EV_WORDS + k];
-            d = k == 3 ? (w[k] > d ? w[k] : d) : d + w[k];
-          }
-        }
-      }
-  dump(prefix + ".acc", acc, (size_t)B * EV_WORDS * sizeof(unsigned long long));
-  dump(prefix + ".err", err, n * sizeof(T));
-  dump(prefix + ".reg", reg, n);
+  }
+  const char* order = "the output depends on the order of the threads within a phase";
+  hc_same(acc[0], acc[1], words, order);
+  hc_same(err[0], err[1], n * sizeof(T), order);
+  hc_same(reg[0], reg[1], n, order);
+  hc_write(prefix + ".acc", acc[0], words);
+  hc_write(prefix + ".err", err[0], n * sizeof(T));
+  hc_write(prefix + ".reg", reg[0], n);
   free(label);
   free(out);
-  free(err);
-  free(reg);
-  free(acc);
+  for (int rev = 0; rev < 2; ++rev) free(err[rev]), free(reg[rev]), free(acc[rev]);
   return 0;
 }
 
 int main(int argc, char** argv) {
-  if (argc != 18) {
-    fprintf(stderr, "usage: eval_host_check <8|16> B H W Hl Wl nthr t0 t1 t2 t3 edge T r label.bin out.bin out_prefix\n");
-    return 2;
-  }
+  hc_name = "eval_host_check";
+  if (argc != 18) hc_die("usage: eval_host_check <8|16> B H W Hl Wl nthr t0 t1 t2 t3 edge T r label.bin out.bin out_prefix");
   int v[14];
   for (int k = 0; k < 14; ++k) v[k] = atoi(argv[1 + k]);
   const int bits = v[0], B = v[1], Hl = v[4], Wl = v[5];

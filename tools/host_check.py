@@ -1,0 +1,224 @@
+"""Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
+into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
+guided_fill) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
+restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
+
+    python tools/host_check.py NAME|all [--cxx /opt/rocm/llvm/bin/clang++]
+"""
+import argparse
+import os
+import shutil
+import struct
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from tests import d4_ref as D  # noqa: E402
+from tests import eval_ref as E  # noqa: E402
+from tests import fill_ref as F  # noqa: E402
+from tests import guided_fill_ref as R  # noqa: E402
+from tests import resample_masked_ref as M  # noqa: E402
+from tests import sensor_ref as S  # noqa: E402
+from tests import stretch_ref as T  # noqa: E402
+
+FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+
+def default_cxx():
+    """$CXX, a clang++ on the PATH, or the one ROCm ships next to hipcc."""
+    rocm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
+    return os.environ.get("CXX") or shutil.which("clang++") or (rocm if os.path.exists(rocm) else "clang++")
+
+
+# A check is a function (run, p) -> (count, "what was covered: no report, what equals what"): run(*args) runs the program, which
+# must exit 0; p(name) is a path in the temporary directory.
+
+def d4(run, p):
+    code = {"f32": 0, "bf16": 1, "f16": 2}                                                        # codon_dtype
+    runs = 0
+    for shape in D.SHAPES:
+        B, H, W = shape
+        for dt in ("f32", "f16", "bf16"):
+            x, y = D.random_bits(shape, dt, 1), D.random_bits(shape, dt, 2)
+            x.tofile(p("x")), y.tofile(p("y"))
+            for two in (True, False):
+                run("views", x.itemsize, B, H, W, p("x"), p("y") if two else "-", p("v"))
+                for src, names in ((x, ("v.up0", "v.tp0")),) + (((y, ("v.up1", "v.tp1")),) if two else ()):
+                    for ref, n in zip(D.views(src), names):
+                        got = np.fromfile(p(n), dtype=src.dtype).reshape(ref.shape)
+                        assert np.array_equal(got, ref), ("views", shape, dt, two, n)
+                        os.remove(p(n))
+                runs += 1
+            up, tr = D.merge_values(4 * B, H, W, dt, 3), D.merge_values(4 * B, W, H, dt, 4)
+            up.tofile(p("u")), tr.tofile(p("t"))
+            run("merge", code[dt], B, H, W, p("u"), p("t"), p("o"))
+            ref = D.merge(D.upcast(up, dt), D.upcast(tr, dt))
+            got = np.fromfile(p("o"), dtype=np.float32).reshape(ref.shape)
+            assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), ("merge", shape, dt)
+            runs += 1
+    return runs, f"over {len(D.SHAPES)} shapes x 3 dtypes: no report, every byte equals tests/d4_ref.py"
+
+
+def sensor(run, p):
+    S.gauss_table().tofile(p("gauss.bin"))
+    for levels in S.LEVELS:
+        np.ascontiguousarray(M.tables(8 if levels == 255 else 16, levels)[1][:levels + 1]).tofile(p(f"lut{levels}.bin"))
+    total = 0
+    for B in S.BATCHES:
+        for size in S.SIZES:
+            want = []
+            with open(p("cases.bin"), "wb") as f:
+                for c in S.cases(B, size):
+                    lr = S.input_map(B, size, c["kind"], c["levels"], c["masked"], c["seed"])
+                    f.write(struct.pack("<4i4I3fI2Q", B, size, c["masked"], c["levels"], S.KEY[0], S.KEY[1], c["step"], c["first"],
+                                        c["sigma"], c["quad"], c["edge_thr"], 0, S.threshold(c["p_drop"]), S.threshold(c["p_edge"])))
+                    f.write(lr.tobytes())
+                    want.append((c["name"], S.run_case(c, lr)))
+            run(os.path.dirname(p("")))
+            got = np.fromfile(p("out.bin"), dtype=np.uint32)
+            assert got.size == len(want) * B * size * size, (B, size, got.size)
+            for k, (name, ref) in enumerate(want):
+                assert np.array_equal(got[k * ref.size:(k + 1) * ref.size].reshape(ref.shape), ref.view(np.uint32)), name
+            total += len(want)
+    return total, f"over {len(S.BATCHES)} batches x {len(S.SIZES)} sizes: no report, every byte equals tests/sensor_ref.py"
+
+
+def eval_(run, p):
+    cases = 0
+    for shape in E.SHAPES:
+        B, H, W = shape
+        for bits in (8, 16):
+            label, out = E.case(shape, bits)
+            label.tofile(p("l")), out.tofile(p("o"))
+            full = E.PARAMS[bits]
+            forms = [dict(full, edge_radius=r) for r in E.RADII] + [{"thresholds": full["thresholds"][:2], "edge_threshold": None}]
+            for kw in forms:
+                thr, thr_e = kw["thresholds"], kw["edge_threshold"]
+                run(bits, B, H, W, label.shape[1], label.shape[2], len(thr), *(list(thr) + [0] * 4)[:4],
+                    0 if thr_e is None else 1, 0 if thr_e is None else thr_e, kw.get("edge_radius", 0), p("l"), p("o"), p("r"))
+                words, err, reg = E.depth_errors_batch(label, out, **kw)
+                assert np.array_equal(np.fromfile(p("r.acc"), dtype=np.uint64).reshape(B, E.WORDS), words), ("words", shape, bits, kw)
+                assert np.array_equal(np.fromfile(p("r.err"), dtype=out.dtype).reshape(out.shape), err), ("error map", shape, bits, kw)
+                assert np.array_equal(np.fromfile(p("r.reg"), dtype=np.uint8).reshape(out.shape), reg), ("region map", shape, bits, kw)
+                cases += 1
+    return cases, f"over {len(E.SHAPES)} shapes x 2 code widths: no report, every word and map equals tests/eval_ref.py"
+
+
+def fill(run, p):
+    cases = 0
+    for shape in F.SHAPES:
+        B, h, w = shape
+        for name, dtype, top, on_grid in F.FORMATS:
+            tab = "-"
+            if on_grid:
+                F.table(top)[:top + 1].tofile(p("t"))
+                tab = p("t")
+            for pattern in F.PATTERNS:
+                codes, want = F.case(shape, pattern, top), F.want(shape, pattern, top)
+                src = F.to_grid(codes, top) if on_grid else codes
+                src.tofile(p("i"))
+                run(2 if on_grid else 0 if dtype == np.uint8 else 1, B, h, w, top, p("i"), tab, p("o"))
+                got = np.fromfile(p("o"), dtype=src.dtype).reshape(shape)
+                ref = F.to_grid(want, top) if on_grid else want
+                assert got.tobytes() == ref.tobytes(), (shape, name, pattern)
+                cases += 1
+    return cases, (f"over {len(F.SHAPES)} shapes x {len(F.FORMATS)} formats x {len(F.PATTERNS)} patterns: no report, "
+                   "every output equals tests/fill_ref.py")
+
+
+def stretch(run, p):
+    skews = (0, 1)      # the planes on a vector boundary and one element off it
+    cases = 0
+    for shape in T.SHAPES:
+        B, h, w = shape
+        for name, dtype, top in T.FORMATS:
+            for pattern in T.PATTERNS:
+                codes = T.case(shape, pattern, top)
+                want, rng = T.want(shape, pattern, top)
+                back = T.unstretch_batch(want, rng, top)
+                codes.tofile(p("i"))
+                for skew in skews:
+                    run(0 if dtype == np.uint8 else 1, B, h * w, top, skew, p("i"), p("r"), p("s"), p("b"))
+                    what = (shape, name, pattern, skew)
+                    assert np.fromfile(p("r"), dtype=np.int32).tobytes() == rng.tobytes(), what
+                    assert np.fromfile(p("s"), dtype=dtype).tobytes() == want.tobytes(), what
+                    assert np.fromfile(p("b"), dtype=dtype).tobytes() == back.tobytes(), what
+                    cases += 1
+    return cases, (f"over {len(T.SHAPES)} shapes x {len(T.FORMATS)} formats x {len(T.PATTERNS)} patterns x {len(skews)} "
+                   "alignments: no report, every output equals tests/stretch_ref.py")
+
+
+def guided_layouts(row):
+    """(name, skew, pad) for guidance rows of `row` = w * scale bytes (a multiple of 4): the row stride is row + pad, the image
+    starts skew bytes into a 16-byte aligned buffer.
+      dense   as the file holds it: 16-byte segments when row % 16 == 0, else 4-byte words
+      wide16  a 16-byte aligned stride wider than the row: 16-byte segments, and when row % 16 != 0 a partial last segment of
+              4-byte words in the same row
+      words   a stride that is a multiple of 4 but not of 16: 4-byte words throughout
+      bytes   an odd start and an odd stride: bytes throughout"""
+    return (("dense", 0, 0), ("wide16", 0, (-row) % 16 + 16), ("words", 0, 4 if (row + 4) % 16 else 8), ("bytes", 1, 3))
+
+
+def guided_fill(run, p):
+    """Every load path of the guidance reduction; the kind of guidance and the range table follow from pattern and layout."""
+    formats, tables = [("u8", 0, 255), ("u16", 1, 65535)], (10.0, 3.0, "c37")
+    cases = 0
+    for shape in F.SHAPES:
+        B, h, w = shape
+        s = R.SHAPE_SCALE[shape]
+        for name, fmt, top in formats:
+            for pi, pattern in enumerate(F.PATTERNS):
+                codes = F.case(shape, pattern, top)
+                codes.tofile(p("i"))
+                for li, (layout, skew, pad) in enumerate(guided_layouts(w * s)):
+                    kind, table = R.GUIDES[(pi + li) % 3], tables[(pi // 3 + li) % 3]
+                    want = R.want(shape, pattern, top, s, kind, table)
+                    R.guide_case(shape, s, kind).tofile(p("g"))
+                    R.table_of(table).tofile(p("t"))
+                    run(fmt, B, h, w, top, s, skew, pad, p("i"), p("g"), p("t"), p("o"))
+                    got = np.fromfile(p("o"), dtype=codes.dtype).reshape(shape)
+                    assert got.tobytes() == want.tobytes(), (shape, name, pattern, layout, kind, table)
+                    cases += 1
+    return cases, (f"over {len(F.SHAPES)} shapes x {len(formats)} formats x {len(F.PATTERNS)} patterns x 4 layouts of the guidance: "
+                   "no report, every output equals tests/guided_fill_ref.py")
+
+
+# name -> (check, extra compile flags, what the count counts)
+CHECKS = {
+    "d4": (d4, ["-ffp-contract=off"], "runs"),
+    "sensor": (sensor, ["-ffp-contract=off"], "cases"),
+    "eval": (eval_, [], "cases"),
+    "fill": (fill, [], "cases"),
+    "stretch": (stretch, [], "cases"),
+    "guided_fill": (guided_fill, [], "cases"),
+}
+
+
+def check(name, cxx):
+    fn, extra, noun = CHECKS[name]
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, f"{name}_host_check")
+        subprocess.run([cxx, *FLAGS, *extra, os.path.join(ROOT, "tools", f"{name}_host_check.cpp"), "-o", exe], check=True)
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+        count, tail = fn(lambda *args: subprocess.run([exe, *map(str, args)], check=True, env=env, stdout=subprocess.DEVNULL),
+                         lambda n: os.path.join(tmp, n))
+    print(f"{name}_host_check: {count} {noun} under -fsanitize=address,undefined {tail}", flush=True)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("name", choices=[*CHECKS, "all"])
+    ap.add_argument("--cxx", default=default_cxx(), help="a clang++ with the sanitizer runtimes")
+    a = ap.parse_args(argv)
+    for name in (CHECKS if a.name == "all" else [a.name]):
+        check(name, a.cxx)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

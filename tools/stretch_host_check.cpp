@@ -3,34 +3,18 @@
 // launch, workgroup by workgroup, thread by thread over exactly-sized heap buffers, so that the address and
 // undefined-behaviour sanitizers see every access (a vector access off its alignment is an undefined-behaviour report).  The
 // launch plans below are code_range's and map_launch's.  No GPU, no HIP, nothing loaded into Python.
-// tools/stretch_host_check.py builds this with
-//   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all
-// runs it over the GPU tests' shapes, patterns and formats and compares what it writes with tests/stretch_ref.py, bit for bit.
+// `python tools/host_check.py stretch` builds this, runs it over the GPU tests' shapes, patterns and formats and compares what it
+// writes with tests/stretch_ref.py, bit for bit.
 //
 //   stretch_host_check <fmt 0|1> B n top skew in.bin range.bin stretched.bin back.bin
 //     in.bin: (B, n) codes of the format; skew: the planes start that many ELEMENTS into a 16-byte aligned buffer (0: the first
 //     image takes the vector path; 1: none does)  ->  range.bin: (B, 2) int32; stretched.bin, back.bin: (B, n) codes -- every
 //     image stretched by its own range, and that unstretched again.  The stretch is also run in place and must agree.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
+#include "host_check.h"
 
 #include "../codon_amd/csrc/stretch_tile.h"
 
 using namespace codon;
-
-static void spill(const char* path, const void* p, size_t bytes) {
-  FILE* f = fopen(path, "wb");
-  if (!f || fwrite(p, 1, bytes, f) != bytes || fclose(f) != 0) {
-    fprintf(stderr, "stretch_host_check: cannot write %s\n", path);
-    exit(2);
-  }
-}
-
-static char* buf(size_t bytes) {                   // 16-byte aligned, as a device allocation is at least
-  void* p = nullptr;
-  return posix_memalign(&p, 16, bytes) == 0 ? (char*)p : nullptr;
-}
 
 // code_range_kernel<FMT>, workgroup b: the threads' partial ranges, folded as the shuffles and the LDS pass fold them
 template <int FMT>
@@ -65,29 +49,21 @@ template <int FMT>
 static int run(int B, long n, int top, int skew, char** path) {
   const size_t eb = (size_t)st_elem_bytes(FMT), bytes = (size_t)B * n * eb, lead = (size_t)skew * eb;
   // exactly lead + bytes each: one element past the end is a sanitizer report
-  char *in = buf(lead + bytes), *out = buf(lead + bytes), *back = buf(lead + bytes), *place = buf(lead + bytes);
-  int* lo_hi = (int*)malloc(sizeof(int) * 2 * B);
-  FILE* f = fopen(path[0], "rb");
-  if (!in || !out || !back || !place || !lo_hi || !f || fread(in + lead, 1, bytes, f) != bytes || fgetc(f) != EOF) {
-    fprintf(stderr, "stretch_host_check: %s does not hold exactly %zu bytes\n", path[0], bytes);
-    return 2;
-  }
-  fclose(f);
+  char *in = hc_aligned(lead + bytes), *out = hc_aligned(lead + bytes), *back = hc_aligned(lead + bytes);
+  char* place = hc_aligned(lead + bytes);
+  int* lo_hi = hc_alloc<int>(sizeof(int) * 2 * B, 0xEE);        // code_range needs no initialisation
+  hc_read(path[0], bytes, lead, in);
   memset(out, 0xEE, lead + bytes);                 // an element no thread writes stays this
   memset(back, 0xEE, lead + bytes);
-  memset(lo_hi, 0xEE, sizeof(int) * 2 * B);        // code_range needs no initialisation
   memcpy(place, in, lead + bytes);
   for (long b = 0; b < B; ++b) range_block<FMT>(b, in + lead, n, lo_hi);
   map_grid<FMT, ST_STRETCH>(B, in + lead, out + lead, n, top, lo_hi);
   map_grid<FMT, ST_STRETCH>(B, place + lead, place + lead, n, top, lo_hi);
-  if (memcmp(place + lead, out + lead, bytes) != 0) {
-    fprintf(stderr, "stretch_host_check: the stretch in place differs from the stretch into another buffer\n");
-    return 3;
-  }
+  hc_same(place + lead, out + lead, bytes, "the stretch in place differs from the stretch into another buffer");
   map_grid<FMT, ST_UNSTRETCH>(B, out + lead, back + lead, n, top, lo_hi);
-  spill(path[1], lo_hi, sizeof(int) * 2 * B);
-  spill(path[2], out + lead, bytes);
-  spill(path[3], back + lead, bytes);
+  hc_write(path[1], lo_hi, sizeof(int) * 2 * B);
+  hc_write(path[2], out + lead, bytes);
+  hc_write(path[3], back + lead, bytes);
   free(in);
   free(out);
   free(back);
@@ -97,10 +73,8 @@ static int run(int B, long n, int top, int skew, char** path) {
 }
 
 int main(int argc, char** argv) {
-  if (argc != 10) {
-    fprintf(stderr, "usage: stretch_host_check <fmt 0|1> B n top skew in.bin range.bin stretched.bin back.bin\n");
-    return 2;
-  }
+  hc_name = "stretch_host_check";
+  if (argc != 10) hc_die("usage: stretch_host_check <fmt 0|1> B n top skew in.bin range.bin stretched.bin back.bin");
   const int fmt = atoi(argv[1]), B = atoi(argv[2]), top = atoi(argv[4]), skew = atoi(argv[5]);
   const long n = atol(argv[3]);
   if (B < 1 || n < 1 || n > (long)ST_MAX_SIDE * ST_MAX_SIDE || top < 2 || top > 65535 || skew < 0 || skew > 15) return 2;
