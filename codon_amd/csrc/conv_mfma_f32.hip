@@ -724,8 +724,9 @@ int pack_chain1x1_f32(const float* w, float* out, hipStream_t stream) {
 // were measured on 15 image heights between 200 and 820 rows (tools/probes/grid_mode_sweep.sh).  3 x 3 and 1 x 1 convs
 // (memory-bound, no such step pattern) keep 8 x 32.
 //
-// Per-pixel arithmetic and its order do not depend on the tiling: every tiling gives the same bits (the batch-independence
-// tests compare them).
+// Per-pixel arithmetic and its order do not depend on the tiling: every tiling gives the same bits.  tests/test_gpu_f32_tilings.py
+// compares them: every image of a batch that runs in T8, T4 or SOLO, single and as a pair grid, against the cout-split launch of
+// that image alone, and each tiling on its own against float64 element by element.
 constexpr long SMALL_GRID = 384;
 constexpr long CSPLIT_MAX_BLOCKS = 192;     // 4 x 32 tiles: up to here a lone launch leaves a quarter of the SIMDs without a wave
 constexpr long CSPLIT_PAIR_MAX_BLOCKS = 128;   // ... and a PAIR of launches split this way is at most 512 workgroups: one round

@@ -87,13 +87,14 @@ def _np(t) -> np.ndarray:
     return t.detach().cpu().double().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
 
 
-def assert_rounded(got, ref, tau, dtype, what: str, epi=None, S=None, show: int = 6) -> dict:
+def assert_rounded(got, ref, tau, dtype, what: str, epi=None, S=None, show: int = 6, where=None) -> dict:
     """Check every element of the kernel output `got` (B, C, H, W) against the float64 accumulator reference `ref` (the
     same shape) within `tau` (a tensor of that shape, see tau_of), with the epilogue `epi` (a monotone elementwise map of
     float64 tensors, identity when None) applied to ref -+ tau before the store rounding of `dtype`.  A NaN in `got`
     fails (outputs are NaN-prefilled: an element never written shows up).  Prints one summary line -- max |got - E(ref)| / S
     (S defaults to tau / 2^-20) and, for 16-bit, the share of elements whose interval holds ONE value, which must be at
-    least 50 %: a check that allows several values for most elements says nothing.  Returns the summary numbers."""
+    least 50 %: a check that allows several values for most elements says nothing.  `where` (optional): index tuple -> text
+    appended to that element's line of a failure message (the tile it lies in).  Returns the summary numbers."""
     epi = epi or (lambda a: a)
     ref, tau = ref.detach().cpu().double(), tau.detach().cpu().double()
     g = _np(got)
@@ -116,7 +117,8 @@ def assert_rounded(got, ref, tau, dtype, what: str, epi=None, S=None, show: int 
         u = ulp(e_ref, dtype)
         at = lambda a, i: float(a[tuple(i)])
         lines = [f"  (b,c,h,w)={tuple(int(v) for v in i)}: got {at(g, i)!r} ref {at(e_ref, i)!r} allowed "
-                 f"[{at(lo, i)!r}, {at(hi, i)!r}] error {(at(g, i) - at(e_ref, i)) / at(u, i):+.2f} ulp" for i in idx]
+                 f"[{at(lo, i)!r}, {at(hi, i)!r}] error {(at(g, i) - at(e_ref, i)) / at(u, i):+.2f} ulp"
+                 + (f": {where(tuple(int(v) for v in i))}" if where else "") for i in idx]
         raise AssertionError(f"{what}: {nbad} of {g.size} elements outside the correctly rounded interval "
                              f"(tau = 2^-20 (S + |additive|)); first {len(idx)}:\n" + "\n".join(lines))
     if share is not None:

@@ -4,7 +4,8 @@ for them (tests/test_gpu_conv_bits.py), plus the table of codon_co
 ops names are called, so the module runs unchanged on an older tree -- which is how tests/golden/conv_bits.json and
 tests/golden/f32_tiling.json are recorded (python -m tests.conv_bits bits OUT.json / tiling OUT.json, on the commit BEFORE a
 change to the host code that launches these kernels).  Every group of cases first asserts, through codon_conv_tiling_f32 or
-tests.bounds.wgrad_bands, the tiling or band plan its shape is there for."""
+tests.bounds.wgrad_bands, the tiling or band plan its shape is there for.  Also here: the batches of one small image that
+select each fp32 tiling, the exact power-of-two batch construction and the bit comparison of tests/test_gpu_f32_tilings.py."""
 import ctypes as C
 import hashlib
 import json
@@ -36,6 +37,104 @@ def tiling_table():
     return {f"k{k}_{ci}_{co}_chained{ch}_pair{p}":
             "".join(str(tiling(B, H, W, k, ci, co, ch, p)) for B in TILING_BATCH for H, W in TILING_HW)
             for k, ci, co, ch in TILING_FORMS for p in (0, 1)}
+
+
+# ---- one small image, the batch selects the tiling (tests/test_gpu_f32_tilings.py; premises: tests/test_conv_tiling_table.py) ----
+TILING_NAME = {T8: "T8", T4: "T4", SOLO: "SOLO", SPLIT: "SPLIT"}
+TILE_ROWS = {T8: 8, T4: 4, SOLO: 4, SPLIT: 2}          # f32_fill: pixel rows of a tile; every tile is 32 pixels wide
+TILE_COLS = 32
+# A: ragged -- 3 tile columns, the last 6 pixels wide; last tile rows of 5 of 8, 1 of 4 and 1 of 2 rows; no block count below is
+# a multiple of 8.  B: exact tiles, W % 4 == 0, every row starts on 16 bytes.
+GEOMETRY = {"A": (13, 70), "B": (16, 64)}
+# (geometry, batch) -> what the case is there for: the tiling of (the chained conv, a plain 5x5, a plain 3x3, a 1x1) outside a
+# pair bracket, and inside one.  What the library answers is asked, never computed here: tiling_premise.
+BATCH_TILING = {("A", 1): ((SPLIT, SPLIT, SPLIT, SOLO),) * 2,
+                ("A", 5): ((SPLIT, SPLIT, SPLIT, SOLO),) * 2,          # a cout-split pair of 210 workgroups: <= 256, padded
+                ("A", 8): ((SPLIT, SPLIT, SPLIT, SOLO),) * 2,          # ... of 336: two to a CU, no padding
+                ("A", 12): ((SPLIT, SPLIT, SPLIT, SOLO), (SOLO,) * 4),  # 144 tiles of 4 x 32: <= 192 alone, > 128 in a pair
+                ("A", 17): ((SOLO,) * 4,) * 2,                         # 204 > 192
+                ("A", 65): ((T8,) * 4,) * 2,                           # 390 tiles of 8 x 32 >= 384, one round
+                ("A", 107): ((T4, T4, T8, T8),) * 2,                   # 642 tiles of 8 x 32: two rounds, three of 4 x 32
+                ("B", 1): ((SPLIT, SPLIT, SPLIT, SOLO),) * 2,
+                ("B", 25): ((SOLO,) * 4,) * 2,                         # 200 > 192
+                ("B", 97): ((T8,) * 4,) * 2,                           # 388 >= 384
+                ("B", 161): ((T4, T4, T8, T8),) * 2}                   # 644
+PAIR_GRID_LIMIT = 256                                  # launch_pair_f32: a cout-split pair of at most this many workgroups is padded
+
+
+def tiling_premise(geo, B, k, cin, cout, chained=0, in_pair=0):
+    """The tiling codon_conv_tiling_f32 gives the launch (cin -> cout as its descriptor has them), asserted to be the one the
+    case (geo, B) is there for."""
+    H, W = GEOMETRY[geo]
+    want = BATCH_TILING[geo, B][in_pair][0 if chained else {5: 1, 3: 2, 1: 3}[k]]
+    got = tiling(B, H, W, k, cin, cout, chained, in_pair)
+    assert got == want, (f"premise: {B}x{H}x{W} k={k} {cin}->{cout} chained={chained} in_pair={in_pair} runs "
+                         f"{TILING_NAME[got]}, the case is there for {TILING_NAME[want]}")
+    return got
+
+
+def assert_batch_tiling(geo, B):
+    for p in (0, 1):
+        for k, ci, co, ch in TILING_FORMS:
+            tiling_premise(geo, B, k, ci, co, ch, p)
+
+
+def batch_exponents(B):
+    """(base image, exponent) of every image of a batch of B: image b is base[b % 3] * 2^(b // 3 - E), E half the largest b // 3."""
+    b = np.arange(B)
+    return b % 3, b // 3 - ((B - 1) // 3) // 2
+
+
+def expand(base, B, imgs=None, scaled=True):
+    """base (3, ...) -> the images `imgs` (default: all) of the batch of B built from it; on base's device, in its dtype.
+    A power-of-two scale: exact unless something under- or overflows (|exponent| <= 27 here)."""
+    idx, e = batch_exponents(B)
+    if imgs is not None:
+        idx, e = idx[list(imgs)], e[list(imgs)]
+    out = base[torch.from_numpy(idx).to(base.device)]
+    if scaled:
+        s = torch.from_numpy(2.0 ** e.astype(np.float64)).to(device=base.device, dtype=base.dtype)
+        out = out * s.reshape((-1,) + (1,) * (base.dim() - 1))
+    return out
+
+
+def probe_images(B):
+    """The first, a middle and the last image of a batch, the middle one on another base image where there is one."""
+    if B < 3:
+        return list(range(B))
+    mid = B // 2
+    while mid % 3 in (0, (B - 1) % 3) and mid + 1 < B - 1:
+        mid += 1
+    return [0, mid, B - 1]
+
+
+def tile_where(t, H, W, h, w):
+    """'T8: band j of n (rows a..b), segment s of m (columns c..d)' of pixel (h, w) under tiling t (tests.forms.where), and
+    the wave and row segment that own the row."""
+    from tests import forms
+    th = TILE_ROWS[t]
+    form = {"bands": forms._spans(H, th), "segs": forms._spans(W, TILE_COLS)}
+    own = (f"wave {h % th // 2}, row segment {h % 2} of 2" if t == T8 else
+           f"waves {h % th} and {h % th + 2} (halves of the couts)" if t == SPLIT else f"wave {h % th}")
+    return f"{TILING_NAME[t]}: {forms.where(form, h, w)}, {own}"
+
+
+def bits_mismatch(got, base, B, t, H, W, what, show=6, col_step=1):
+    """None when image b of `got` (B, C, h, w) equals base[b % 3] * 2^(b // 3 - E) bit for bit -- base (3, C, h, w): the results
+    for the three base images run alone -- else a message naming the first differing elements: image, channel, pixel, its
+    tile under tiling t, both values.  Compared on got's device.  col_step: pixels per element along the last axis (32 for
+    the row-strip statistics, whose last axis counts tile columns)."""
+    exp = expand(base, B)
+    assert got.shape == exp.shape, (what, tuple(got.shape), tuple(exp.shape))
+    if torch.equal(got, exp):
+        return None
+    bad = ~(got == exp)                                                # a NaN on either side differs
+    idx = bad.nonzero()[:show].cpu().tolist()
+    _, e = batch_exponents(B)
+    lines = [f"  image {b} (base image {b % 3} x 2^{int(e[b])}) channel {c} pixel ({h}, {w * col_step}): got {float(got[b, c, h, w])!r} "
+             f"expected {float(exp[b, c, h, w])!r}; {tile_where(t, H, W, h, w * col_step)}" for b, c, h, w in idx]
+    return (f"{what}: {int(bad.sum())} of {got.numel()} elements differ from the single-image result scaled by a power of two; "
+            f"first {len(lines)}:\n" + "\n".join(lines))
 
 
 # ---- inputs ----

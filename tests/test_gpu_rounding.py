@@ -18,6 +18,10 @@ The chained out is checked against the float64 1x1 of the kernel's OWN mid, so o
 into the next check.  Every operand is read from, and every result written to, a channel slice at coff = 64 of a wider
 buffer whose other channels must stay untouched.
 
+The shapes here are chosen around the 16-bit tile: at every one of them the fp32 kernels run in the cout-split form only (the
+4 x 32 one-per-CU form for 1x1).  tests/test_gpu_f32_tilings.py holds the fp32 kernels to the same bound in each of their four
+tilings, single and as pair grids, and compares the tilings with each other bit for bit.
+
 Covered transitively, bit for bit, by other tests and not repeated here: the pair and mix53 launches
 (test_conv_pair_is_one_launch_and_bit_identical, test_mix53_conv5x5_and_conv3x3_as_one_grid), codon_conv2d_gated_fwd /
 _emit_fwd == codon_cac_apply_fwd then codon_conv2d_fwd (test_gated_conv_equals_apply_then_conv), codon_conv2d_sum_into_fwd
