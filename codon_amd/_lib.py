@@ -22,6 +22,7 @@ CONV_RELU, CONV_ADD_RESIDUAL, CONV_ACCUM_OUT, CONV_MASK_RELU, CONV_F16X3, CONV_M
 PACK_FWD, PACK_DGRAD, PACK_FWD_F16X3, PACK_CHAIN1X1, PACK_CHAIN1X1_F16X3 = 0, 1, 2, 3, 4
 TILING_8X32, TILING_4X32, TILING_4X32_SOLO, TILING_2X32_COUT_SPLIT = 0, 1, 2, 3      # codon_conv_tiling_f32
 C8_FORM_STAGED, C8_FORM_RESIDENT = 0, 1                                             # codon_conv_form_c8
+FORM_STEM, FORM_HEAD, FORM_CAC_STATS, FORM_CAC_BWD_GATE, FORM_CAC_SPATIAL_FWD, FORM_CAC_SPATIAL_BWD, FORM_CONV1CH_WGRAD = range(7)  # codon_launch_form
 CAC_FOLDS = 16   # CODON_CAC_FOLDS
 FILL_U8, FILL_U16, FILL_F32 = 0, 1, 2                                               # CODON_FILL_*
 
@@ -30,6 +31,10 @@ class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "batch", "height", "width", "cin", "cout", "ksize", "x_ctotal", "x_coff", "y_ctotal", "y_coff",
         "r_ctotal", "r_coff", "flags", "dtype")]
+
+
+class Form(C.Structure):                            # codon_form
+    _fields_ = [(n, C.c_int32) for n in ("vec", "rows", "depth", "cols", "tile", "tiles", "slices", "per", "vector")]
 
 
 class Tensor(C.Structure):
@@ -165,6 +170,7 @@ SIGNATURES = {
     "codon_conv_pair_end": (C.c_int, [_P]),
     "codon_conv_tiling_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int]),
     "codon_conv_form_c8": (C.c_int, [C.POINTER(ConvDesc)]),
+    "codon_launch_form": (C.c_int, [_I, _I, _I, _I, _I, _I, C.POINTER(Form)]),
     "codon_cast_multi": (C.c_int, [C.POINTER(CastDesc), _P, _P]),
     "codon_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),
     "codon_grad_norm_workspace_bytes": (_S, []),

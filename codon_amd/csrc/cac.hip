@@ -12,11 +12,10 @@
 
 #include "codon_common.h"
 #include "kernels.h"
+#include "launch_rules.h"
 #include "px8.h"
 
 namespace codon {
-
-constexpr int STATS_TILE = PX_TILE;  // pixels per workgroup (8 per thread)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -144,7 +143,7 @@ __global__ __launch_bounds__(128) void cac_gate_kernel(const float* __restrict__
 // rows of one column and reads each plane's 8 x 5 window once; the 50 weights come by scalar loads.  Taps in the order
 // (plane, dy, dx) of the previous one-load-per-tap kernel: same sums bit for bit (a padded tap adds w * 0).
 // (Round 2: three aligned float4 loads per (plane, row) and 4 pixels, 0.13 ms for a 40 MB map; now 0.04.)
-constexpr int SPF_T = 32, SPF_HALO = SPF_T + 4, SPF_PITCH = SPF_HALO + 1;
+constexpr int SPF_HALO = SPF_T + 4, SPF_PITCH = SPF_HALO + 1;     // SPF_T: launch_rules.h
 __global__ __launch_bounds__(256) void cac_spatial_kernel(const float* __restrict__ pooled, const float* __restrict__ w,
                                                           float* __restrict__ sp, int H, int W, int tiles_x, int tiles_y) {
   __shared__ float tl[2][SPF_HALO][SPF_PITCH];
@@ -231,16 +230,10 @@ static bool aligned16(const void* a, const void* b = nullptr, const void* c = nu
            reinterpret_cast<uintptr_t>(d)) % 16) == 0;
 }
 
-// SMALL IMAGES (one 128 x 128 pair per call, BASELINE configs[0]): 2048-pixel tiles make 8 workgroups that walk 128 planes in
-// 16 dependent trips -- 57 us of a 2.9 ms forward on a chip with 256 CUs (profiles/r05_b1_fp32_128x128_timeline.txt).  Up to
-// STATS_SMALL_HW pixels a tile is 256 pixels (one per thread, 64 workgroups for 128 x 128) and a trip holds 32 planes.  The
-// choice depends on H * W only, never on the batch: an image's statistics do not depend on what else is in the batch.
-constexpr long STATS_SMALL_HW = 32768;
-constexpr int STATS_SMALL_TILE = 256;
-static bool stats_small(long HW) { return HW <= STATS_SMALL_HW; }
+// small images take 256-pixel tiles and cac_stats_small_kernel: stats_small / stats_tile, launch_rules.h
 int cac_stats_tiles(int H, int W) {
   const long HW = (long)H * W;
-  return stats_small(HW) ? (int)((HW + STATS_SMALL_TILE - 1) / STATS_SMALL_TILE) : (int)((HW + STATS_TILE - 1) / STATS_TILE);
+  return (int)((HW + stats_tile(HW) - 1) / stats_tile(HW));
 }
 
 // grid = (ntiles, B), 256 threads, thread = pixel.  Same outputs as cac_stats_kernel (per-pixel channel max / mean, per-tile
@@ -567,7 +560,7 @@ int cac_apply_fwd(int B, int H, int W, const codon_tensor* pre, const codon_tens
   const size_t es = 4;
   auto base = [&](const codon_tensor* t) { return (char*)t->data + t->coff * HW * es; };
   const bool al = aligned16(base(pre), base(in), base(out), sp) && aligned16(base(pre_c), base(in_c), base(out_c));
-  const unsigned nt = (unsigned)((HW + PX_TILE - 1) / PX_TILE);
+  const unsigned nt = px_tiles(HW);
   px_dispatch(dtype, HW, al, [&](auto pol) {
     using P = decltype(pol);
     using T = typename P::T;
@@ -610,7 +603,7 @@ int ew_sq_scale(int B, int H, int W, const codon_tensor* x, const float* ch, con
   const size_t es = 4;
   const char* xp = (const char*)x->data + x->coff * HW * es;
   char* yp = (char*)y->data + y->coff * HW * es;
-  const int nt = (int)((HW + PX_TILE - 1) / PX_TILE);
+  const int nt = px_tiles(HW);
   px_dispatch(dtype, HW, aligned16(xp, yp, yp), [&](auto pol) {
     using P = decltype(pol);
     using T = typename P::T;

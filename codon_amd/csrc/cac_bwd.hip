@@ -23,6 +23,7 @@
 
 #include "codon_common.h"
 #include "kernels.h"
+#include "launch_rules.h"
 #include "px8.h"
 
 namespace codon {
@@ -125,8 +126,7 @@ constexpr int GATE_NPARAM = 8 * 128 + 8 + 64 * 8 + 64;
 // 1024 threads = 128 channels x 8 slices of the tile range (round 5): the two walks over the per-tile partials -- the arg-max
 // pixel of every channel, the 64 gate-gradient sums -- were ONE thread per channel stepping through 1200 tiles (480 x 640):
 // 97 us per launch, latency.  Each slice walks its contiguous share, the eight results meet in LDS in slice order (fixed
-// order: deterministic; min is exact, the sums are re-associated once).
-constexpr int GATE_SLICES = 8;
+// order: deterministic; min is exact, the sums are re-associated once).  GATE_SLICES, gate_slice_tiles: launch_rules.h
 __global__ __launch_bounds__(128 * GATE_SLICES) void cac_bwd_gate_kernel(const float* __restrict__ part_gch,
                                                            const int* __restrict__ part_arg,
                                                            const float* __restrict__ ch,
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(128 * GATE_SLICES) void cac_bwd_gate_kernel(const f
   __shared__ float s_gs[GATE_SLICES][64];
   const int t = threadIdx.x & 127, sl = threadIdx.x >> 7, b = blockIdx.x;
   {
-    const int per = (ntiles + GATE_SLICES - 1) / GATE_SLICES;
+    const int per = gate_slice_tiles(ntiles);
     const int k0 = sl * per, k1 = min(k0 + per, ntiles);
     int am = INT_MAX;
     for (int k = k0; k < k1; ++k) am = min(am, part_arg[((long)b * ntiles + k) * 128 + t]);
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(64) void partial_chunk_sum_kernel(float* __restrict
 // (one global load per pixel and tap cost 0.67 - 1.07 ms for a 40 MB map in rounds 2 - 3; the three planes are 0.12 GB).
 // A thread owns 4 consecutive pixels of one column and keeps the 50 weight-gradient partials in registers;
 // they are reduced over the workgroup once per tile (fixed order: deterministic).
-constexpr int SPB_T = 32, SPB_HALO = SPB_T + 4, SPB_PITCH = SPB_HALO + 1;
+constexpr int SPB_HALO = SPB_T + 4, SPB_PITCH = SPB_HALO + 1;     // SPB_T: launch_rules.h
 __global__ __launch_bounds__(256) void cac_bwd_spatial_kernel(const float* __restrict__ g_z,
                                                               const float* __restrict__ pooled,
                                                               const float* __restrict__ w,
@@ -422,7 +422,7 @@ static const char* basep(const codon_tensor* t, long HW, int dtype) {
   return (const char*)t->data + t->coff * HW * 4;
 }
 
-int cac_bwd_tiles(int H, int W) { return (int)(((long)H * W + BWD_TILE - 1) / BWD_TILE); }
+int cac_bwd_tiles(int H, int W) { return px_tiles((long)H * W); }
 int cac_bwd_spatial_blocks(int B, int H, int W) { return B * ((H + SPB_T - 1) / SPB_T) * ((W + SPB_T - 1) / SPB_T); }
 
 int cac_bwd_reduce(int B, int H, int W, const codon_tensor* g_out, const codon_tensor* g_outc,
@@ -532,7 +532,7 @@ int ew_add_mask(int B, int H, int W, int C, const codon_tensor* dst, const codon
   const char* s = src ? basep(src, HW, dtype) : nullptr;
   const char* m = mask ? basep(mask, HW, dtype) : nullptr;
   const long s_img = src ? src->ctotal * HW : 0, m_img = mask ? mask->ctotal * HW : 0;
-  const unsigned nt = (unsigned)((HW + PX_TILE - 1) / PX_TILE);
+  const unsigned nt = px_tiles(HW);
   px_dispatch(dtype, HW, al16(d, s, m), [&](auto pol) {
     using P = decltype(pol);
     using T = typename P::T;

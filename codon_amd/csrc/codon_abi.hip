@@ -9,6 +9,7 @@
 #include "eval_tile.h"
 #include "fill_tile.h"
 #include "kernels.h"
+#include "launch_rules.h"
 #include "pair.h"
 #include "sensor_pixel.h"
 #include "stretch_tile.h"
@@ -575,6 +576,42 @@ int codon_conv_form_c8(const codon_conv_desc* d) {
   CODON_REQUIRE(d && shape_ok(d->batch, d->height, d->width), CODON_ERR_BAD_ARG, "conv_form_c8: null descriptor or bad shape");
   CODON_REQUIRE(is16(d->dtype), CODON_ERR_UNSUPPORTED, "conv_form_c8: dtype %d is not a 16-bit dtype", d->dtype);
   return conv_form_c8(d);
+}
+
+// codon_launch_form (include/codon_hip.h): the rules of launch_rules.h / px8.h as the launchers ask them, without a launch
+int codon_launch_form(int32_t op, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t aligned, codon_form* out) {
+  CODON_REQUIRE(out && op >= CODON_FORM_STEM && op <= CODON_FORM_CONV1CH_WGRAD && dtype_known(dtype) && shape_ok(B, H, W),
+                CODON_ERR_BAD_ARG, "launch_form: null out, unknown op %d or dtype %d, or bad shape", op, dtype);
+  const long HW = (long)H * W;
+  codon_form f{};
+  switch (op) {
+    case CODON_FORM_STEM:
+      f.vec = is16(dtype) ? STEM_C8_VEC : stem_vec_f32(B * HW, W, aligned != 0);
+      f.cols = is16(dtype) ? 64 * STEM_C8_VEC : 0;
+      break;
+    case CODON_FORM_HEAD:
+      if (is16(dtype)) {
+        f.rows = head_rows_c8(B * HW); f.cols = HEAD_C8_COLS;
+      } else {
+        head_form_f32(B * HW, W, aligned != 0, [&](auto s) {
+          f.vec = s.vec; f.rows = s.rows; f.depth = s.depth; f.cols = 64 * s.vec;
+          return 0;
+        });
+      }
+      break;
+    case CODON_FORM_CAC_STATS:
+      f.tile = stats_tile(HW); f.tiles = cac_stats_tiles(H, W);
+      f.vector = !is16(dtype) && !stats_small(HW) && px_vector(HW, aligned != 0);
+      break;
+    case CODON_FORM_CAC_BWD_GATE:
+      f.tile = PX_TILE; f.tiles = cac_bwd_tiles(H, W); f.slices = GATE_SLICES; f.per = gate_slice_tiles(f.tiles);
+      break;
+    case CODON_FORM_CAC_SPATIAL_FWD: f.tile = SPF_T; break;
+    case CODON_FORM_CAC_SPATIAL_BWD: f.tile = SPB_T; break;
+    default: f.rows = W1_ROWS; f.cols = W1_CHUNK; break;      // CODON_FORM_CONV1CH_WGRAD
+  }
+  *out = f;
+  return CODON_OK;
 }
 
 int codon_cast_multi(const codon_cast_desc* desc, float* dst, codon_stream_t stream) {

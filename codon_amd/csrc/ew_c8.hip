@@ -9,6 +9,7 @@
 
 #include "c8.h"
 #include "kernels.h"
+#include "launch_rules.h"
 
 namespace codon {
 
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(256) void stem_c8_pair_kernel(const float* __restri
 template <class E>
 static int stem_c8_pair_launch(int B, int H, int W, const float* xa, const float* wa, C8Slice ya, const float* xb,
                                const float* wb, C8Slice yb, int* bad, int* host_a, int* host_b, hipStream_t stream) {
-  constexpr int VEC = 2;
+  constexpr int VEC = STEM_C8_VEC;
   const int nseg = (W + 64 * VEC - 1) / (64 * VEC);
   const long nwave = (long)B * H * nseg;
   const long blocks = (nwave + 3) / 4;
@@ -177,7 +178,7 @@ int stem_pair_fwd_c8(int B, int H, int W, const float* xa, const float* wa, void
 template <class E>
 static int stem_c8_launch(int B, int H, int W, const float* x, const float* w, C8Slice y, C8Slice mask, int has_mask,
                           int flags, int* bad, int* host, hipStream_t stream) {
-  constexpr int VEC = 2;
+  constexpr int VEC = STEM_C8_VEC;
   const int nseg = (W + 64 * VEC - 1) / (64 * VEC);
   const long nwave = (long)B * H * nseg;
   const long blocks = (nwave + 3) / 4;
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(256) void head_c8_kernel(C8Slice x, const float* __
   const int seg = (int)(wid % nseg);
   const long t_ = wid / nseg;
   const int band = (int)(t_ % nband), b = (int)(t_ / nband);
-  const int col = seg * 62 - 1 + lane;                  // this lane's input column
+  const int col = seg * HEAD_C8_COLS - 1 + lane;        // this lane's input column
   const int gy0 = band * R;
   const long HW = (long)H * W;
   const unsigned HW16 = 16u * (unsigned)HW;
@@ -289,7 +290,7 @@ template <class E, int R>
 static int head_c8_launch(int B, int H, int W, C8Slice x, const float* w, const float* res, void* y, bool y16, const int* bad,
                           hipStream_t stream) {
   const int nband = (H + R - 1) / R;
-  const int nseg = (W + 61) / 62;
+  const int nseg = (W + HEAD_C8_COLS - 1) / HEAD_C8_COLS;
   const long nwave = (long)B * nband * nseg;
   const long blocks = (nwave + 3) / 4;
   CODON_REQUIRE(blocks < (1L << 31), CODON_ERR_UNSUPPORTED, "head_fwd: grid too large");
@@ -306,19 +307,18 @@ int head_fwd_c8(int B, int H, int W, const void* x, int x_ctotal, int x_coff, co
                 bool y16, int dtype, const int* bad, hipStream_t stream) {
   if (const int st = c8_check("head_fwd", H, W, 64, {{x_ctotal, x_coff, 64}})) return st;
   const C8Slice xs = c8_mk(x, x_ctotal, x_coff, (long)H * W);
-  const bool big = (long)B * H * W >= (1L << 22);       // bands of 8 rows instead of 4
+  const bool r8 = head_rows_c8((long)B * H * W) == 8;
   return c8_dispatch(dtype, [&](auto e) {
-    const auto launch = big ? &head_c8_launch<decltype(e), 8> : &head_c8_launch<decltype(e), 4>;
+    const auto launch = r8 ? &head_c8_launch<decltype(e), 8> : &head_c8_launch<decltype(e), 4>;
     return launch(B, H, W, xs, w, res, y, y16, bad, stream);
   });
 }
 
 // ---- weight gradient of the 1->64 / 64->1 3x3 convs ------------------------------------------------------------------
 //   R[c][t] = sum_{b,q} A[b,c,q] * s[b, q + (t/3 - 1, t%3 - 1)]        c < 64, t < 9        (see stencil.hip)
-// Workgroup = (image, band of rows); wave w owns planes 2w, 2w+1 (16 channels) and keeps their 16 x 9 partial sums in
-// registers over the whole band: lanes walk the row, a load is one 16-byte vector = the 8 channels of a plane.
-constexpr int W1C8_ROWS = 8;
-
+// Workgroup = (image, band of W1_ROWS rows: launch_rules.h); wave w owns planes 2w, 2w+1 (16 channels) and keeps their
+// 16 x 9 partial sums in registers over the whole band: lanes walk the row, a load is one 16-byte vector = the 8 channels
+// of a plane.
 // One wave per 8-channel plane (8 waves): 72 accumulators per lane instead of 144 -- 4 instead of 2 waves per SIMD keep
 // twice the loads in flight (the kernel waits on memory: 61 % of its wave cycles parked, 2.7 TB/s with two planes per
 // wave).  Every accumulator still sees its pixels in the same order: bit-identical to the two-plane form.
@@ -342,9 +342,9 @@ __global__ __launch_bounds__(512 / W1C8_PLANES) void conv1ch_wgrad_c8_kernel(C8S
     for (int c = 0; c < 8; ++c)
 #pragma unroll
       for (int t = 0; t < 9; ++t) acc[g][c][t] = 0.f;
-  const int y0 = rb * W1C8_ROWS, y1 = min(y0 + W1C8_ROWS, H);
+  const int y0 = rb * W1_ROWS, y1 = min(y0 + W1_ROWS, H);
   for (int y = y0; y < y1; ++y) {
-    for (int x0 = 0; x0 < W; x0 += 64) {
+    for (int x0 = 0; x0 < W; x0 += W1_CHUNK) {
       const int x = x0 + lane;
       const bool xin = x < W;
       const unsigned vo = xin ? 16u * (unsigned)(y * W + x) : C8_OOB;
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(512 / W1C8_PLANES) void conv1ch_wgrad_c8_kernel(C8S
 }
 
 size_t conv1ch_wgrad_c8_workspace_bytes(int B, int H, int W) {
-  return (size_t)B * ((H + W1C8_ROWS - 1) / W1C8_ROWS) * 576 * sizeof(float);
+  return (size_t)B * w1_bands(H) * 576 * sizeof(float);
 }
 
 int conv1ch_wgrad_c8(int B, int H, int W, const void* a, int a_ctotal, int a_coff, const float* s, float* dw, int flip,
@@ -392,7 +392,7 @@ int conv1ch_wgrad_c8(int B, int H, int W, const void* a, int a_ctotal, int a_cof
   if (const int st = c8_check_slices("conv1ch_wgrad", {{a_ctotal, a_coff, 64}})) return st;
   CODON_REQUIRE(ws_bytes >= conv1ch_wgrad_c8_workspace_bytes(B, H, W), CODON_ERR_BAD_ARG, "conv1ch_wgrad: workspace too small");
   const long HW = (long)H * W;
-  const int nrowblk = (H + W1C8_ROWS - 1) / W1C8_ROWS;
+  const int nrowblk = w1_bands(H);
   const C8Slice as = c8_mk(a, a_ctotal, a_coff, HW);
   const int st = c8_dispatch(dtype, [&](auto e) {
     hipLaunchKernelGGL(conv1ch_wgrad_c8_kernel<decltype(e)>, dim3(B * nrowblk), dim3(512 / W1C8_PLANES), 0, stream, as, s, ws, H,
@@ -408,7 +408,7 @@ int conv1ch_wgrad_c8(int B, int H, int W, const void* a, int a_ctotal, int a_cof
 // first): the per-pixel channel max / sum stay in two registers per pixel, the per-channel tile sums / maxima are
 // reduced in registers over the thread's pixels, then over the wave (shuffles), then over the 4 waves (LDS).
 // NP = pixels per thread: NP (2048-pixel tiles), or 1 for small images (256-pixel tiles, all 16 planes' loads in flight:
-// cac.hip, STATS_SMALL_HW -- the tile rule is the fp32 pass's, so that codon_cac_stats_tiles holds for every dtype)
+// launch_rules.h, STATS_SMALL_HW -- the tile rule is the fp32 pass's, so that codon_cac_stats_tiles holds for every dtype)
 template <class E, int NP = EW_NP>
 __global__ __launch_bounds__(256) void cac_stats_c8_kernel(C8Slice pre_c, C8Slice pre, float* __restrict__ pooled,
                                                            float* __restrict__ partials, long HW, int ntiles,

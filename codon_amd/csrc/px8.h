@@ -54,11 +54,17 @@ struct PxF32S {
   }
 };
 
-// Host-side dispatch: calls fn(Policy{}) with the widest policy the shapes/pointers allow.
+// tiles of PX_TILE pixels in a plane of HW pixels
+inline int px_tiles(long HW) { return (int)((HW + PX_TILE - 1) / PX_TILE); }
+
+// the widest policy the shapes / pointers allow: PxF32V or (false) PxF32S
+inline bool px_vector(long HW, bool aligned16) { return HW % 4 == 0 && aligned16; }
+
+// Host-side dispatch: calls fn(Policy{}) with that policy.
 template <typename F>
 static inline void px_dispatch(int dtype, long HW, bool aligned16, F&& fn) {
   (void)dtype;   // fp32 only: 16-bit tensors are channel-blocked and take the kernels of ew_c8.hip
-  if (HW % 4 == 0 && aligned16) fn(PxF32V{});
+  if (px_vector(HW, aligned16)) fn(PxF32V{});
   else fn(PxF32S{});
 }
 

@@ -10,6 +10,7 @@
 
 #include "codon_common.h"
 #include "kernels.h"
+#include "launch_rules.h"
 
 namespace codon {
 
@@ -302,12 +303,8 @@ template <typename T>
 static int stem_launch(int B, int H, int W, const float* x, const float* w, T* y, int y_ctotal, int y_coff, int flags,
                        const T* mask, int m_ctotal, int m_coff, int* bad, int* host, hipStream_t stream) {
   const long HW = (long)H * W;
-  // images of a few thousand pixels (one 128 x 128 pair per call, BASELINE configs[0]): the four-pixel form is 16 workgroups
-  // on 256 CUs, each thread 64 dependent row stores long -- the one-pixel form has four times the threads.  Same fma chain
-  // per output either way: same bits.
-  const bool tiny = (long)B * H * W <= 65536;
-  const bool v4 = !tiny && (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) |
-                                             reinterpret_cast<uintptr_t>(mask)) % 16 == 0);
+  const bool v4 = stem_vec_f32(B * HW, W, (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) |
+                                           reinterpret_cast<uintptr_t>(mask)) % 16 == 0) == 4;
   const long total = (long)B * H * (v4 ? W / 4 : W);
   const long blocks = (total + 255) / 256;
   CODON_REQUIRE(blocks < (1L << 31), CODON_ERR_UNSUPPORTED, "stem_fwd: grid too large");
@@ -335,9 +332,9 @@ int stem_pair_fwd(int B, int H, int W, const float* xa, const float* wa, void* y
     return stem_pair_fwd_c8(B, H, W, xa, wa, ya, ya_ctotal, ya_coff, xb, wb, yb, yb_ctotal, yb_coff, dtype, bad, host_a, host_b,
                             stream);
   const long HW = (long)H * W;
-  const bool tiny = (long)B * H * W <= 65536;                    // as stem_launch: same form, same bits as the lone launches
-  const bool v4 = !tiny && (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(xa) | reinterpret_cast<uintptr_t>(ya) |
-                                             reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(yb)) % 16 == 0);
+  // the form of the lone launches (stem_launch asks the same rule): same bits
+  const bool v4 = stem_vec_f32(B * HW, W, (reinterpret_cast<uintptr_t>(xa) | reinterpret_cast<uintptr_t>(ya) |
+                                           reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(yb)) % 16 == 0) == 4;
   const long total = (long)B * H * (v4 ? W / 4 : W);
   const long blocks = (total + 255) / 256;
   CODON_REQUIRE(2 * blocks < (1L << 31), CODON_ERR_UNSUPPORTED, "stem_pair_fwd: grid too large");
@@ -374,9 +371,9 @@ static int head_launch(int B, int H, int W, const T* x, int x_ctotal, int x_coff
                 "head_fwd: %dx%d image: 64 channel planes exceed the 4 GiB buffer-descriptor range", H, W);
   // 16-byte (fp32) / 8-byte (16-bit) row accesses need every plane row start aligned to them
   const uintptr_t al = sizeof(T) == 4 ? 16 : 8;
-  const bool v4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % al == 0) &&
-                  ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res)) % 16 == 0) &&
-                  ((x_ctotal * HW * sizeof(T)) % al == 0) && ((x_coff * HW * sizeof(T)) % al == 0);
+  const bool aligned = (reinterpret_cast<uintptr_t>(x) % al == 0) &&
+                       ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res)) % 16 == 0) &&
+                       ((x_ctotal * HW * sizeof(T)) % al == 0) && ((x_coff * HW * sizeof(T)) % al == 0);
 #ifdef CODON_TUNE
   if (const char* e = getenv("CODON_HEAD_BAND")) {
     const int r = atoi(e);
@@ -386,18 +383,10 @@ static int head_launch(int B, int H, int W, const T* x, int x_ctotal, int x_coff
 #undef HV
   }
 #endif
-  // band height R: an input row is fetched (R + 2) / R times.  Measured at 32 x 64 x 480 x 640 (tools/time_head.py, one box):
-  // fp32 R = 4 / 8 / 16: 0.531 / 0.468 / 0.462 ms; bf16: 0.429 / 0.393 / 0.345 ms (round 1: 1.11 / 1.30 ms).  Small
-  // images keep R = 4 (more waves).
-  const bool big = (long)B * H * W >= (1L << 22);
-  // a few thousand pixels (one 128 x 128 image: 32 waves of the 4-pixel form, each 16 memory round trips long): one row and
-  // 64 pixels per wave, 16 channels' rows in flight -- 256 waves, 4 round trips.  Same accumulation order: same bits.
-  if ((long)B * H * W <= 65536) return head_launch_v<1, 1, T, 16>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream);
-  if (v4)
-    return big ? head_launch_v<4, 16, T>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream)
-               : head_launch_v<4, 4, T, 4>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream);
-  return big ? head_launch_v<1, 4, T>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream)
-             : head_launch_v<1, 4, T, 8>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream);
+  return head_form_f32(B * HW, W, aligned, [&](auto f) {
+    using F = decltype(f);
+    return head_launch_v<F::vec, F::rows, T, F::depth>(B, H, W, x, x_ctotal, x_coff, w, res, y, bad, stream);
+  });
 }
 
 // y16 (16-bit activations only): y is stored in the activations' type instead of fp32
@@ -413,11 +402,9 @@ int head_fwd(int B, int H, int W, const void* x, int x_ctotal, int x_coff, const
 //   head: A = t11 (the head's input),         s = dL/dy  -> output.weight.grad[0][c][t] = R[c][8-t]
 // HBM-bound (one read of the 64-channel tensor A): lanes walk x so every A load is a coalesced row segment;
 // the 3x3 window of the 1-channel map s is loaded once per (row, 64-pixel chunk) and reused by all channels.
-// Workgroup = (image, band of W1_ROWS rows); wave w owns channels 16w .. 16w+15 and keeps their 16 x 9 partial
-// sums in registers over the whole band; one wave reduction per sum at the end, per-block partials, fixed-order
+// Workgroup = (image, band of W1_ROWS rows: launch_rules.h); wave w owns channels 16w .. 16w+15 and keeps their 16 x 9
+// partial sums in registers over the whole band; one wave reduction per sum at the end, per-block partials, fixed-order
 // final sum (deterministic).
-constexpr int W1_ROWS = 8;
-
 template <typename T>
 __global__ __launch_bounds__(256) void conv1ch_wgrad_kernel(const T* __restrict__ a, long a_img, long a_base,
                                                             const float* __restrict__ s, float* __restrict__ part,
@@ -434,7 +421,7 @@ __global__ __launch_bounds__(256) void conv1ch_wgrad_kernel(const T* __restrict_
     for (int t = 0; t < 9; ++t) acc[c][t] = 0.f;
   const int y0 = rb * W1_ROWS, y1 = min(y0 + W1_ROWS, H);
   for (int y = y0; y < y1; ++y) {
-    for (int x0 = 0; x0 < W; x0 += 64) {
+    for (int x0 = 0; x0 < W; x0 += W1_CHUNK) {
       const int x = x0 + lane;
       const bool xin = x < W;
       float sv[9];
@@ -500,8 +487,7 @@ int conv1ch_wgrad_reduce(const float* part, float* dw, int nparts, int flip, hip
 }
 
 size_t conv1ch_wgrad_workspace_bytes(int B, int H, int W) {
-  const int nrowblk = (H + W1_ROWS - 1) / W1_ROWS;
-  return (size_t)B * nrowblk * 576 * sizeof(float);
+  return (size_t)B * w1_bands(H) * 576 * sizeof(float);
 }
 
 int conv1ch_wgrad(int B, int H, int W, const void* a, int a_ctotal, int a_coff, const float* s, float* dw, int flip,
@@ -511,7 +497,7 @@ int conv1ch_wgrad(int B, int H, int W, const void* a, int a_ctotal, int a_coff, 
   CODON_REQUIRE(ws_bytes >= conv1ch_wgrad_workspace_bytes(B, H, W), CODON_ERR_BAD_ARG,
                 "conv1ch_wgrad: workspace too small");
   const long HW = (long)H * W;
-  const int nrowblk = (H + W1_ROWS - 1) / W1_ROWS;
+  const int nrowblk = w1_bands(H);
   hipLaunchKernelGGL(conv1ch_wgrad_kernel<float>, dim3(B * nrowblk), dim3(256), 0, stream, (const float*)a,
                      a_ctotal * HW, a_coff * HW, s, ws, H, W, nrowblk);
   const int st = check_launch("conv1ch_wgrad_kernel");

@@ -215,6 +215,36 @@ int codon_conv_tiling_f32(const codon_conv_desc* desc, int chained, int in_pair)
 #define CODON_C8_FORM_RESIDENT 1
 int codon_conv_form_c8(const codon_conv_desc* desc);
 
+/* Which form the stem / head stencils, the one-channel weight gradient and the CAC gate passes give a launch of this size:
+ * the host rules the launchers themselves switch on (csrc/launch_rules.h, px8.h, cac_stats_tiles), called without a launch
+ * (host arithmetic, no GPU call): diagnostics, and the tests that place their probes on a form's seams (tests/forms.py).
+ * `aligned`: every pointer and slice of the launch starts on 16 bytes (the launcher finds that out from its own arguments).
+ * Fields an op does not have are 0.
+ *   CODON_FORM_STEM          fp32: vec (pixels per thread, 1 or 4), cols 0 (a thread index walks the flattened rows: no
+ *                            segments); 16-bit: vec 2, cols 128 (columns of one row per wave)
+ *   CODON_FORM_HEAD          fp32: vec, rows, depth = VEC, R, DEPTH of the kernel, cols = 64 vec (output columns per wave);
+ *                            16-bit: rows (4 or 8), cols 62
+ *   CODON_FORM_CAC_STATS     tile (pixels per tile: 256 for small images, else 2048), tiles (per image, codon_cac_stats_tiles),
+ *                            vector (fp32, 2048-pixel form: 1 = 16-byte accesses, 0 = scalar)
+ *   CODON_FORM_CAC_BWD_GATE  tile (2048), tiles (per image, codon_cac_bwd_tiles), slices (of the tile range the gate kernel
+ *                            walks), per (tiles per slice)
+ *   CODON_FORM_CAC_SPATIAL_FWD / _BWD   tile (edge of the square pixel tile of the forward / the backward kernel)
+ *   CODON_FORM_CONV1CH_WGRAD rows (per band), cols (pixels per chunk)
+ * The CODON_TUNE lab override of the head's band height is not reported.  CODON_ERR_BAD_ARG for a NULL out, an unknown op
+ * or dtype or a non-positive size.  Replaces nothing in the reference (eager PyTorch leaves the kernel choice to cuDNN,
+ * CODON_x4.py:68-131). */
+#define CODON_FORM_STEM 0
+#define CODON_FORM_HEAD 1
+#define CODON_FORM_CAC_STATS 2
+#define CODON_FORM_CAC_BWD_GATE 3
+#define CODON_FORM_CAC_SPATIAL_FWD 4
+#define CODON_FORM_CAC_SPATIAL_BWD 5
+#define CODON_FORM_CONV1CH_WGRAD 6
+typedef struct codon_form {
+  int32_t vec, rows, depth, cols, tile, tiles, slices, per, vector;
+} codon_form;
+int codon_launch_form(int32_t op, int32_t dtype, int32_t batch, int32_t height, int32_t width, int32_t aligned, codon_form* out);
+
 /* A conv whose input is the CAC gate-apply of the producing block, formed while the input tile is staged instead of
  * being written to HBM and read back (inference):   x = pre * (ch * sp) + inputs ,  y = conv(x) [ReLU]
  *   out*ad_CAC + inputs  /  out_c*ad_CAC + inputs_c  feeding conv1, conv2 / conv4, conv5 / conv7

@@ -1,31 +1,47 @@
-"""The launch forms of the stem / head stencils and the CAC gate passes, restated (test infrastructure, CPU only).
+"""The launch forms of the stem / head stencils and the CAC gate passes, as the library states them (test infrastructure, CPU only).
 
 The launchers pick a kernel instantiation from the problem size.  A test states WHICH form it runs as a premise
 (`assert head_form(...)["name"] == "head<4,4,4>"`) and places its windows and impulses on that form's seams; no result depends
-on anything here.  A mirror kept in step by hand, as tests/bounds.py::wgrad_bands is:
+on anything here.  Every rule is ASKED of the library: codon_launch_form (include/codon_hip.h) is the host functions the
+launchers themselves switch on (codon_amd/csrc/launch_rules.h, px8.h), called without a launch.  Nothing of
+a rule is restated here: a threshold that moves in csrc/ moves these answers, and the premises fail.  What remains is
+geometry: spans, seams and probes built from the answers.
 
-  head_form    codon_amd/csrc/stencil.hip head_launch (the B H W <= 65536 / v4 / `big` lines) and head_launch_v (nband, nseg);
-               codon_amd/csrc/ew_c8.hip head_fwd_c8 (`big`) and head_c8_launch (nseg: 62 output columns per wave)
-  stem_form    stencil.hip stem_launch / stem_pair_fwd (`tiny`, `v4`); ew_c8.hip stem_c8_launch (VEC = 2, 128 columns per wave)
-  stats_form   codon_amd/csrc/cac.hip STATS_SMALL_HW, STATS_SMALL_TILE, cac_stats_tiles; px8.h PX_TILE and px_dispatch
-  bwd_gate_walk  codon_amd/csrc/cac_bwd.hip cac_bwd_tiles and the k0 / k1 lines of cac_bwd_gate_kernel (GATE_SLICES)
-  spatial_tiles  cac.hip SPF_T / cac_bwd.hip SPB_T: 32 x 32 pixel tiles
-  wgrad1_plan  stencil.hip W1_ROWS and the 64-pixel chunk loop of conv1ch_wgrad_kernel (ew_c8.hip W1C8_ROWS: the same 8)"""
+  head_form    CODON_FORM_HEAD: VEC, R, DEPTH of head_kernel (fp32) or R of head_c8_kernel, output columns per wave
+  stem_form    CODON_FORM_STEM: pixels per thread; 16-bit: columns of one row per wave
+  stats_form   CODON_FORM_CAC_STATS: pixels per tile, tiles per image, vector or scalar accesses
+  bwd_gate_walk  CODON_FORM_CAC_BWD_GATE: tiles per image, slices, tiles per slice
+  spatial_tiles  CODON_FORM_CAC_SPATIAL_FWD / _BWD: the tile edge of each kernel
+  wgrad1_plan  CODON_FORM_CONV1CH_WGRAD: rows per band, pixels per chunk
+  PX_TILE      the backward's pixels per tile (a module attribute, read from the library)"""
 from __future__ import annotations
+
+import ctypes as C
 
 import torch
 
-HEAD_TINY_PIXELS = 65536          # stencil.hip: B H W <= 65536 -> one row and 64 pixels per wave
-HEAD_BIG_PIXELS = 1 << 22         # stencil.hip / ew_c8.hip: `big`
-STATS_SMALL_HW = 32768            # cac.hip
-STATS_SMALL_TILE = 256            # cac.hip
-PX_TILE = 2048                    # px8.h
-GATE_SLICES = 8                   # cac_bwd.hip
-SPATIAL_TILE = 32                 # cac.hip SPF_T, cac_bwd.hip SPB_T
-W1_ROWS = 8                       # stencil.hip, ew_c8.hip
-W1_CHUNK = 64
+from codon_amd import _lib as L
 
 _cdiv = lambda a, b: (a + b - 1) // b
+_DT = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}
+
+
+def ask(op: int, dtype, B: int, H: int, W: int, aligned: bool = True) -> L.Form:
+    """codon_launch_form's answer for one launch."""
+    f = L.Form()
+    L.check(L.load().codon_launch_form(op, _DT[dtype], B, H, W, int(aligned), C.byref(f)), "codon_launch_form")
+    return f
+
+
+def _px_tile() -> int:
+    """Pixels per tile of the 8-pixels-per-thread passes (px8.h)."""
+    return ask(L.FORM_CAC_BWD_GATE, torch.float32, 1, 1, 1).tile
+
+
+def __getattr__(name):
+    if name == "PX_TILE":
+        return _px_tile()
+    raise AttributeError(name)
 
 
 def _is16(dtype) -> bool:
@@ -39,33 +55,22 @@ def _spans(n: int, step: int) -> list:
 def head_form(dtype, B: int, H: int, W: int, aligned: bool = True) -> dict:
     """name, rows (R: rows per band), seg_cols (output columns per wave), bands = [(first row, one past the last)],
     segs = [(first column, one past the last)].  aligned: x, y and res start on 16 bytes (torch allocations do)."""
-    px = B * H * W
-    big = px >= HEAD_BIG_PIXELS
-    if _is16(dtype):
-        R, cols = (8 if big else 4), 62
-        name = f"head_c8<{R}>"
-    elif px <= HEAD_TINY_PIXELS:
-        R, cols, name = 1, 64, "head<1,1,16>"
-    elif W % 4 == 0 and aligned:
-        R, cols = (16 if big else 4), 256
-        name = "head<4,16>" if big else "head<4,4,4>"
-    else:
-        R, cols = 4, 64
-        name = "head<1,4>" if big else "head<1,4,8>"
-    return {"name": name, "rows": R, "seg_cols": cols, "bands": _spans(H, R), "segs": _spans(W, cols), "H": H, "W": W}
+    f = ask(L.FORM_HEAD, dtype, B, H, W, aligned)
+    args = (f.rows,) if _is16(dtype) else (f.vec, f.rows) + ((f.depth,) if f.depth != 1 else ())
+    name = ("head_c8<%s>" if _is16(dtype) else "head<%s>") % ",".join(map(str, args))
+    return {"name": name, "rows": f.rows, "seg_cols": f.cols, "bands": _spans(H, f.rows), "segs": _spans(W, f.cols), "H": H, "W": W}
 
 
 def stem_form(dtype, B: int, H: int, W: int, aligned: bool = True) -> dict:
     """name, vec, segs and starts.  The fp32 kernels give a thread VEC consecutive pixels of one row and a workgroup 256
     consecutive threads of the flattened (b, y, x / VEC) index: no column segments; `starts` are the pixels (b, y, x) at
-    which the second, a middle and the last workgroup begin.  The 16-bit kernel gives a wave 128 columns of one row."""
-    if _is16(dtype):
-        return {"name": "stem_c8<2>", "vec": 2, "segs": _spans(W, 128), "starts": [], "H": H, "W": W}
-    v4 = B * H * W > HEAD_TINY_PIXELS and W % 4 == 0 and aligned
-    vec = 4 if v4 else 1
+    which the second, a middle and the last workgroup begin.  The 16-bit kernel gives a wave a segment of columns of one row."""
+    f = ask(L.FORM_STEM, dtype, B, H, W, aligned)
+    vec, starts = f.vec, []
+    if f.cols:
+        return {"name": f"stem_c8<{vec}>", "vec": vec, "segs": _spans(W, f.cols), "starts": starts, "H": H, "W": W}
     wv = W // vec
     nblk = _cdiv(B * H * wv, 256)
-    starts = []
     for m in sorted({1, nblk // 2, nblk - 1} - {0}):
         if m < nblk:
             idx = 256 * m
@@ -75,29 +80,27 @@ def stem_form(dtype, B: int, H: int, W: int, aligned: bool = True) -> dict:
 
 def stats_form(H: int, W: int, aligned: bool = True) -> dict:
     """name, tile (pixels of the flattened plane per workgroup), ntiles, last (pixels in the last tile)."""
-    HW = H * W
-    if HW <= STATS_SMALL_HW:
-        name, tile = "stats_small<256>", STATS_SMALL_TILE
-    else:
-        name, tile = ("stats<2048,v4>" if HW % 4 == 0 and aligned else "stats<2048,v1>"), PX_TILE
-    nt = _cdiv(HW, tile)
-    return {"name": name, "tile": tile, "ntiles": nt, "last": HW - (nt - 1) * tile}
+    f = ask(L.FORM_CAC_STATS, torch.float32, 1, H, W, aligned)
+    name = f"stats<{f.tile},v{4 if f.vector else 1}>" if f.tile == _px_tile() else f"stats_small<{f.tile}>"
+    return {"name": name, "tile": f.tile, "ntiles": f.tiles, "last": H * W - (f.tiles - 1) * f.tile}
 
 
 def bwd_gate_walk(H: int, W: int) -> dict:
-    """ntiles (2048-pixel tiles of the backward), per, and the tile range [k0, k1) each of the 8 slices walks."""
-    nt = _cdiv(H * W, PX_TILE)
-    per = _cdiv(nt, GATE_SLICES)
-    sl = [(min(s * per, nt), min(s * per + per, nt)) for s in range(GATE_SLICES)]
-    return {"ntiles": nt, "per": per, "slices": sl, "last": H * W - (nt - 1) * PX_TILE}
+    """ntiles (the backward's tiles per image), per, and the tile range [k0, k1) each slice of the gate kernel walks."""
+    f = ask(L.FORM_CAC_BWD_GATE, torch.float32, 1, H, W)
+    nt, per = f.tiles, f.per
+    sl = [(min(s * per, nt), min(s * per + per, nt)) for s in range(f.slices)]
+    return {"ntiles": nt, "per": per, "slices": sl, "last": H * W - (nt - 1) * f.tile}
 
 
-def spatial_tiles(H: int, W: int) -> dict:
-    return {"rows": _spans(H, SPATIAL_TILE), "cols": _spans(W, SPATIAL_TILE)}
+def spatial_tiles(H: int, W: int, backward: bool = False) -> dict:
+    t = ask(L.FORM_CAC_SPATIAL_BWD if backward else L.FORM_CAC_SPATIAL_FWD, torch.float32, 1, H, W).tile
+    return {"rows": _spans(H, t), "cols": _spans(W, t)}
 
 
 def wgrad1_plan(H: int, W: int) -> dict:
-    return {"bands": _spans(H, W1_ROWS), "chunks": _spans(W, W1_CHUNK)}
+    f = ask(L.FORM_CONV1CH_WGRAD, torch.float32, 1, H, W)
+    return {"bands": _spans(H, f.rows), "chunks": _spans(W, f.cols)}
 
 
 def seam_lines(spans: list, n: int, reach: int = 0) -> list:

@@ -91,6 +91,23 @@ def test_16bit_form_query_refusals_without_gpu():
     assert lib.codon_conv_form_c8(d(k=5, ci=64, co=128, dt=L.F16)) == -2 and b"no 16-bit kernel" in lib.codon_last_error_string()
 
 
+def test_launch_form_query_without_gpu():
+    """codon_launch_form answers from the host rules the stencil and gate launchers switch on (csrc/launch_rules.h, DESIGN
+    3.1.3) and launches nothing; a NULL out, an unknown op or dtype and a non-positive size are BAD_ARG under its name."""
+    import ctypes as C
+    from codon_amd import _lib as L
+    lib = L.load()
+    f = L.Form()
+    q = lambda op=L.FORM_HEAD, dt=L.F32, B=1, H=8, W=8, out=C.byref(f): lib.codon_launch_form(op, dt, B, H, W, 1, out)
+    assert q() == 0 and (f.vec, f.rows, f.depth, f.cols) == (1, 1, 16, 64)
+    assert q(B=32, H=480, W=640) == 0 and (f.vec, f.rows, f.depth, f.cols) == (4, 16, 1, 256)
+    assert q(L.FORM_CAC_STATS, H=480, W=640) == 0 and (f.tile, f.tiles, f.vector) == (2048, lib.codon_cac_stats_tiles(480, 640), 1)
+    assert q(L.FORM_CAC_BWD_GATE, H=480, W=640) == 0 and (f.tiles, f.slices, f.per) == (lib.codon_cac_bwd_tiles(480, 640), 8, 19)
+    for bad in (dict(out=None), dict(op=-1), dict(op=L.FORM_CONV1CH_WGRAD + 1), dict(dt=7), dict(dt=-1), dict(B=0), dict(H=0),
+                dict(W=-3)):
+        assert q(**bad) == -1 and b"launch_form" in lib.codon_last_error_string(), bad
+
+
 def test_module_surface_matches_reference_contract(golden_dir):
     from codon_amd import CODONNet, CODONNet16
     ref = {}

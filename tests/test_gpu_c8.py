@@ -1379,8 +1379,14 @@ def test_stem_pair_equals_two_stem_launches(shape, dtype):
     pixels, four-pixel rows, channel-blocked 16-bit)."""
     from codon_amd import ops
     from codon_amd.ops import Slice
+    from tests import forms
     dev = _dev()
     B, H, W = shape
+    # premise: the forms the shapes are there for, asked of the rule both launchers ask (DESIGN 3.1.3)
+    want = {(3, 300, 256): "stem<4>", (1, 370, 463): "stem<1>", (1, 128, 128): "stem<1>"}
+    if dtype == torch.float32 and shape in want:
+        assert forms.stem_form(dtype, B, H, W)["name"] == want[shape]
+        assert (forms.head_form(dtype, B, H, W)["name"] == "head<1,1,16>") == (shape == (1, 128, 128))      # tiny, or beyond it
     xa, xb = _rand((B, 1, H, W), 1).to(dev), _rand((B, 1, H, W), 2).to(dev)
     wa, wb = _rand((64, 1, 3, 3), 3, 0.3).to(dev), _rand((64, 1, 3, 3), 4, 0.3).to(dev)
     new = (lambda: torch.full((B, 128, H, W), float("nan"), device=dev)) if dtype == torch.float32 else \

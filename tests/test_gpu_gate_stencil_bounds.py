@@ -1,5 +1,6 @@
 """The fp32 stem / head stencils, the CAC gate forward and backward and their 16-bit twins, held to float64 element by element
-in EVERY launch form (tests/forms.py restates the launchers' rules; each test asserts the form it runs as its premise).
+in EVERY launch form (tests/forms.py asks the library for the launchers' own rules, codon_launch_form; each test asserts the
+form it runs as its premise, so a threshold that moves in csrc/ fails the premise instead of moving the seams unseen).
 
 Bound: the project's tau = 2^-20 (S + |additive operands|) of tests/bounds.py, S the same expression over absolute values
 (tests/cac_ref.py for the gate); 16-bit outputs are held to the correctly rounded interval (one rounding).  Outputs are
