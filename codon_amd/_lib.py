@@ -187,6 +187,7 @@ SIGNATURES = {
     "codon_bicubic_upsample_masked": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "codon_bicubic_downsample_masked": (C.c_int, [_I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "codon_lr_codes_to_input": (C.c_int, [_I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P]),
+    "codon_lr_codes_upsample": (C.c_int, [_I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
     "codon_train_crops_lr": (C.c_int, [C.POINTER(CropDesc), _P, C.c_int64, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "codon_philox4x32_10": (C.c_int, [C.POINTER(C.c_uint32)] * 3),
     "codon_lr_sensor": (C.c_int, [C.POINTER(SensorDesc), _P, _P, _P, _I, _P, _P]),
@@ -197,6 +198,8 @@ SIGNATURES = {
     "codon_fill_holes": (C.c_int, [_I, _I, _I, _P, _I, _P, _I, _P, _P, _S, _P]),
     "codon_fill_guided_workspace_bytes": (_S, [_I, _I]),
     "codon_fill_holes_guided": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, C.c_int64, C.c_int64, _I, _P, _P, _P, _S, _P]),
+    "codon_jbu_workspace_bytes": (_S, [_I, _I]),
+    "codon_jbu_upsample": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, C.c_int64, C.c_int64, _I, _P, _P, _P, _P, _S, _P]),
     "codon_code_range": (C.c_int, [_I, _I, _I, _P, _I, _P, _P]),
     "codon_stretch_codes": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _P, _P]),
     "codon_unstretch_codes": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _P, _P]),

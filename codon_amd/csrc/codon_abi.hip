@@ -911,6 +911,24 @@ int codon_lr_codes_to_input(int32_t batch, int32_t lr_height, int32_t lr_width, 
                            (hipStream_t)stream);
 }
 
+int codon_lr_codes_upsample(int32_t batch, int32_t lr_height, int32_t lr_width, int32_t scale, const void* codes,
+                            int32_t code_bits, const float* lut, int32_t depth_max, const float* phase_weights, void* out,
+                            codon_stream_t stream) {
+  CODON_REQUIRE(codes && lut && phase_weights && out, CODON_ERR_BAD_ARG, "lr_codes_upsample: null pointer");
+  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "lr_codes_upsample: scale %d", scale);
+  CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "lr_codes_upsample: code_bits %d (8 or 16)", code_bits);
+  CODON_REQUIRE(code_bits == 16 ? (depth_max >= 1 && depth_max <= 65535) : depth_max == 255, CODON_ERR_BAD_ARG,
+                "lr_codes_upsample: depth_max %d (255 for 8-bit codes, 1..65535 for 16-bit codes)", depth_max);
+  CODON_REQUIRE(lr_height >= 1 && lr_width >= 1 && lr_height <= 65536 && lr_width <= 65536 &&
+                    shape_ok(batch, lr_height * scale, lr_width * scale),
+                CODON_ERR_BAD_ARG, "lr_codes_upsample: bad shape");
+  CODON_REQUIRE(((uintptr_t)out & 15) == 0 && (code_bits == 8 || ((uintptr_t)codes & 1) == 0), CODON_ERR_BAD_ARG,
+                "lr_codes_upsample: out must be 16-byte aligned and u16 codes 2-byte aligned");
+  CODON_REQUIRE(codes != out, CODON_ERR_BAD_ARG, "lr_codes_upsample: codes and out are the same buffer");
+  return lr_codes_upsample(batch, lr_height, lr_width, scale, codes, code_bits, lut, depth_max, phase_weights, out,
+                           (hipStream_t)stream);
+}
+
 int codon_train_crops_lr(const codon_crop_desc* desc, const uint8_t* pool, int64_t pool_bytes, int32_t scale, int32_t code_bits,
                          const float* lut, int32_t depth_max, const float* lut8, const float* phase_weights, float* x,
                          float* guide, float* target, codon_stream_t stream) {
@@ -1089,6 +1107,37 @@ int codon_fill_holes_guided(int32_t batch, int32_t height, int32_t width, const 
                 workspace_bytes, need);
   return fill_holes_guided(batch, height, width, in, fmt, top, guide, (long)guide_row_bytes,
                            batch == 1 ? 0L : (long)guide_image_bytes, scale, range_tab, out, workspace, (hipStream_t)stream);
+}
+
+// ---- joint bilateral upsampling ----------------------------------------------------------------------------------
+size_t codon_jbu_workspace_bytes(int32_t height, int32_t width) { return jbu_workspace_bytes(height, width); }
+
+int codon_jbu_upsample(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top, const uint8_t* guide,
+                       int64_t guide_row_bytes, int64_t guide_image_bytes, int32_t scale, const uint16_t* range_tab,
+                       const uint16_t* spatial_tab, void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
+  CODON_REQUIRE(in && out && workspace && guide && range_tab && spatial_tab, CODON_ERR_BAD_ARG, "jbu_upsample: null pointer");
+  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "jbu_upsample: fmt %d (0: u8 codes, 1: u16 codes)", fmt);
+  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "jbu_upsample: batch %d (1..65535)", batch);
+  CODON_REQUIRE(height >= 1 && height <= FL_MAX_SIDE && width >= 1 && width <= FL_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "jbu_upsample: a %dx%d plane (1..%d each way)", height, width, FL_MAX_SIDE);
+  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
+                "jbu_upsample: top %d (255 for u8 codes, 1..65535 otherwise)", top);
+  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_BAD_ARG, "jbu_upsample: scale %d (4, 8 or 16)", scale);
+  CODON_REQUIRE(guide_row_bytes >= (int64_t)width * scale, CODON_ERR_BAD_ARG,
+                "jbu_upsample: guide rows of %lld bytes (at least %lld: width times scale)", (long long)guide_row_bytes,
+                (long long)width * scale);
+  CODON_REQUIRE(batch == 1 || guide_image_bytes >= (int64_t)height * scale * guide_row_bytes, CODON_ERR_BAD_ARG,
+                "jbu_upsample: guide images %lld bytes apart (at least %lld: height times scale rows)",
+                (long long)guide_image_bytes, (long long)height * scale * guide_row_bytes);
+  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "jbu_upsample: in and out are the same buffer");
+  const bool planes_ok = ((uintptr_t)in & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0 && ((uintptr_t)out & 15) == 0;
+  const bool tab_ok = (((uintptr_t)range_tab | (uintptr_t)spatial_tab) & 1) == 0, ws_ok = ((uintptr_t)workspace & 15) == 0;
+  CODON_REQUIRE(planes_ok && tab_ok && ws_ok, CODON_ERR_BAD_ARG, "jbu_upsample: unaligned plane, table or workspace");
+  const size_t need = (size_t)batch * jbu_workspace_bytes(height, width);
+  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "jbu_upsample: a workspace of %zu bytes is too small (%zu needed)",
+                workspace_bytes, need);
+  return jbu_upsample(batch, height, width, in, fmt, guide, (long)guide_row_bytes, batch == 1 ? 0L : (long)guide_image_bytes, scale,
+                      range_tab, spatial_tab, out, workspace, (hipStream_t)stream);
 }
 
 // ---- per-image range normalisation of depth codes ---------------------------------------------------------------

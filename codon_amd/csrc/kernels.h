@@ -172,6 +172,11 @@ size_t fill_guided_workspace_bytes(int h, int w);
 int fill_holes_guided(int B, int h, int w, const void* in, int fmt, int top, const void* guide, long row_bytes, long image_bytes,
                       int scale, const void* range_tab, void* out, void* workspace, hipStream_t stream);
 
+// jbu.hip; guide as fill_guided.hip's; range_tab: 256 u16, spatial_tab: scale x 4 u16; out: (B, h * scale, w * scale) codes
+size_t jbu_workspace_bytes(int h, int w);
+int jbu_upsample(int B, int h, int w, const void* in, int fmt, const void* guide, long row_bytes, long image_bytes, int scale,
+                 const void* range_tab, const void* spatial_tab, void* out, void* workspace, hipStream_t stream);
+
 // stretch.hip; fmt: ST_U8 / ST_U16, dir: ST_STRETCH / ST_UNSTRETCH (stretch_tile.h); n: codes per image
 int code_range(int B, long n, const void* codes, int fmt, int* lo_hi, hipStream_t stream);
 int map_codes(int dir, int B, long n, const void* in, int fmt, int top, const int* lo_hi, void* out, hipStream_t stream);
@@ -238,6 +243,8 @@ int bicubic_downsample_masked(int B, int P, int s, const float* hr, const float*
                               hipStream_t stream);
 int lr_codes_to_input(int B, int h, int w, int s, const void* codes, int code_bits, const float* lut, int levels,
                       const float* wtab, void* out, int dtype, hipStream_t stream);
+int lr_codes_upsample(int B, int h, int w, int s, const void* codes, int code_bits, const float* lut, int levels,
+                      const float* wtab, void* out, hipStream_t stream);
 
 // sensor.hip
 int lr_sensor(const SensorArgs& a, int B, const float* lr, const float* gauss, const float* lut, float* out,

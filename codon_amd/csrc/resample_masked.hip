@@ -184,7 +184,9 @@ __device__ __forceinline__ unsigned short to_bits16(float v, int dtype) {
   return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
 }
 
-template <int S, int R>
+// CODES: the run is written as the INTEGERS the look-up takes, (int)rintf(clamp(., 0, 1) * levels), in the codes' own width (a
+// hole stays 0) -- codon_lr_codes_upsample, the bicubic baseline; R = 4: 4 or 8 bytes per lane
+template <int S, int R, bool CODES>
 __global__ __launch_bounds__(256) void lr_codes_to_input_kernel(const void* __restrict__ codes, int code16,
                                                                 const float* __restrict__ lut, float levels,
                                                                 const float* __restrict__ wtab, void* __restrict__ out,
@@ -216,14 +218,24 @@ __global__ __launch_bounds__(256) void lr_codes_to_input_kernel(const void* __re
     }
   }
   float res[R];
+  int code[R];
 #pragma unroll
   for (int j = 0; j < R; ++j) {
     bool ok;
     const float r = bicubic4x4_masked(v, Sh::off(j), wtab + (gx0 + j) % S * 4, wy, &ok);
-    res[j] = lut[(int)rintf(fminf(fmaxf(r, 0.f), 1.f) * levels)];
+    code[j] = (int)rintf(fminf(fmaxf(r, 0.f), 1.f) * levels);
+    if constexpr (!CODES) res[j] = lut[code[j]];
   }
   const long at = run * R;
-  if (dtype == CODON_F32) {                              // R == 4 (host rule)
+  if constexpr (CODES) {                                 // R == 4 (host rule)
+    if (code16) {
+      uint2 o2 = make_uint2((unsigned)code[0] | ((unsigned)code[1] << 16), (unsigned)code[2] | ((unsigned)code[3] << 16));
+      *reinterpret_cast<uint2*>(static_cast<unsigned short*>(out) + at) = o2;
+    } else {
+      *reinterpret_cast<unsigned*>(static_cast<unsigned char*>(out) + at) =
+          (unsigned)code[0] | ((unsigned)code[1] << 8) | ((unsigned)code[2] << 16) | ((unsigned)code[3] << 24);
+    }
+  } else if (dtype == CODON_F32) {                              // R == 4 (host rule)
     f32x4 o4;
     o4[0] = res[0]; o4[1] = res[1]; o4[2] = res[2]; o4[3] = res[3];
     *reinterpret_cast<f32x4*>(static_cast<float*>(out) + at) = o4;
@@ -316,13 +328,13 @@ int bicubic_downsample_masked(int B, int P, int s, const float* hr, const float*
   return check_launch("bicubic_down_masked_kernel");
 }
 
-template <int S, int R>
+template <int S, int R, bool CODES = false>
 static int launch_codes(int B, int h, int w, const void* codes, int code16, const float* lut, int levels, const float* wtab,
                         void* out, int dtype, hipStream_t stream) {
   const long runs = (long)B * h * S * w * S / R;
   const long blocks = (runs + 255) / 256;
   CODON_REQUIRE(blocks < (1L << 31), CODON_ERR_UNSUPPORTED, "lr_codes_to_input: grid too large");
-  hipLaunchKernelGGL((lr_codes_to_input_kernel<S, R>), dim3((unsigned)blocks), dim3(256), 0, stream, codes, code16, lut,
+  hipLaunchKernelGGL((lr_codes_to_input_kernel<S, R, CODES>), dim3((unsigned)blocks), dim3(256), 0, stream, codes, code16, lut,
                      (float)levels, wtab, out, dtype, h, w, runs);
   return check_launch("lr_codes_to_input_kernel");
 }
@@ -338,6 +350,15 @@ int lr_codes_to_input(int B, int h, int w, int s, const void* codes, int code_bi
   if (s == 8) { CODON_LAUNCH_CODES(8); }
   CODON_LAUNCH_CODES(16);
 #undef CODON_LAUNCH_CODES
+}
+
+// out: codes of the input's width; dtype is not looked at
+int lr_codes_upsample(int B, int h, int w, int s, const void* codes, int code_bits, const float* lut, int levels,
+                      const float* wtab, void* out, hipStream_t stream) {
+  const int code16 = code_bits == 16 ? 1 : 0;
+  if (s == 4) return launch_codes<4, 4, true>(B, h, w, codes, code16, lut, levels, wtab, out, CODON_F32, stream);
+  if (s == 8) return launch_codes<8, 4, true>(B, h, w, codes, code16, lut, levels, wtab, out, CODON_F32, stream);
+  return launch_codes<16, 4, true>(B, h, w, codes, code16, lut, levels, wtab, out, CODON_F32, stream);
 }
 
 }  // namespace codon

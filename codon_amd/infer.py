@@ -30,7 +30,10 @@ import torch
 from . import CODONNet, CODONNet16, io, metrics
 from .io import check_depth_max, list_pairs, read_depth_plane
 from .prep import LrPrep, add_prep_args, prep_of
-from .upsample import FILL_SIGMA, _code_planes, _on_device, code_table, phase_weights, unstretch_codes
+from .upsample import (FILL_SIGMA, JBU_SIGMA_S, _code_planes, _on_device, bicubic_upsample_codes, check_fill_sigma,
+                       check_jbu_sigma_s, code_table, joint_bilateral_upsample, phase_weights, unstretch_codes)
+
+BASELINES = ("bicubic", "jbu")
 
 
 def _load_host(a_depth, a_color, a_label, f, tdt, depth_bits=8, depth_max=65535):
@@ -143,7 +146,7 @@ def _pinned_copy(t: torch.Tensor) -> torch.Tensor:
 
 def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None,
              depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None, self_ensemble=False, report=None, fill_holes=False,
-             normalize=False, fill_guided=False, fill_sigma=FILL_SIGMA):
+             normalize=False, fill_guided=False, fill_sigma=FILL_SIGMA, baseline=None, jbu_sigma_s=JBU_SIGMA_S, jbu_sigma_r=FILL_SIGMA):
     """The test loop over every image pair.  Returns {"n", "rmse_mean", "ssim_mean", "seconds", "images_per_s"}.
     depth_bits=16: 16-bit depth and label files with codes 0 .. depth_max, outputs through metrics.postprocess_u16 into 16-bit
     PNGs, RMSE (metrics.masked_rmse_u16) in codes times depth_unit, SSIM of label / depth_max against out / depth_max.
@@ -162,7 +165,12 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     upload of that many bytes.  normalize: the (filled) codes' own range [lo, hi] is stretched onto [1, top], the
     range stays on the device, and the post-processed output codes are mapped back (upsample.unstretch_codes) before anything
     else sees them: the metrics, the report, the error maps and the written files are in the files' own codes, and the label
-    is never remapped."""
+    is never remapped.
+    baseline (needs lr_depth, and model may be None): "bicubic" or "jbu" -- a classical upsampler in the network's
+    place.  The prepared codes (fill -> stretch, unchanged) go through upsample.bicubic_upsample_codes, or through
+    upsample.joint_bilateral_upsample under jbu_sigma_s (low-resolution pixels) and jbu_sigma_r (guidance codes), for which the
+    loader hands over the guidance codes as for fill_guided; what comes out already is codes, so post-processing is skipped, and
+    unstretching, metrics, report, error maps and files are the network path's.  tdt then only types the guidance nothing reads."""
     if (lr_depth is None) == (input_depth is None):
         raise ValueError("run_loop: exactly one of input_depth and lr_depth")
     if depth_bits not in (8, 16):
@@ -172,8 +180,19 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
         check_depth_max(depth_max)
     prep = LrPrep.checked("run_loop", fill_holes, fill_guided, fill_sigma, normalize, lr=("lr_depth", lr_depth is not None),
                           top=depth_max if deep else 255)
+    if baseline is not None:
+        if baseline not in BASELINES:
+            raise ValueError(f"run_loop: baseline {baseline!r} ({' or '.join(BASELINES)})")
+        if lr_depth is None:
+            raise ValueError("run_loop: baseline needs lr_depth (a baseline upsamples low-resolution code planes)")
+        if self_ensemble:
+            raise ValueError("run_loop: baseline with self_ensemble (there is no network to ensemble)")
+        if baseline == "jbu":
+            jbu_sigma_s, jbu_sigma_r = check_jbu_sigma_s("run_loop", jbu_sigma_s), check_fill_sigma("run_loop", jbu_sigma_r)
     if lr_depth is not None and scale not in (4, 8, 16):
         raise ValueError(f"run_loop: lr_depth needs scale 4, 8 or 16 (got {scale!r})")
+    if model is None and baseline is None:
+        raise ValueError("run_loop: model is None without a baseline")
     files = list_pairs(lr_depth or input_depth, input_color) if files is None else files
     if deep:
         post_codes = lambda o: metrics.postprocess_u16(o, depth_max)                             # noqa: E731
@@ -188,20 +207,26 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     # guidance codes) gives (the depth input, the range it was stretched by or None), and that range rides to post
     if lr_depth is not None:
         load = lambda f: _load_lr(lr_depth, input_color, label, f, tdt, scale, depth_bits, depth_max,            # noqa: E731
-                                  with_guide=prep.fill_guided)
+                                  with_guide=prep.fill_guided or baseline == "jbu")
 
-        def to_x(c, g):                                 # [fill ->] [stretch ->] codes_to_input
+        def to_x(c, g):                                 # [fill ->] [stretch ->] codes_to_input, or the baseline's codes
             c, lo_hi = prep.apply(c, g, scale, dm)
-            return codes_to_input(c, scale, tdt, dm), lo_hi
+            if baseline is None:
+                return codes_to_input(c, scale, tdt, dm), lo_hi
+            up = (bicubic_upsample_codes(c, scale, dm) if baseline == "bicubic" else
+                  joint_bilateral_upsample(c, g, scale, jbu_sigma_s, jbu_sigma_r, dm))
+            return (up.view(torch.uint16) if deep else up), lo_hi
     else:
         load = lambda f: (*_load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max), None)    # noqa: E731
         to_x = lambda x, g: (x, None)                                                                          # noqa: E731
 
     def post(o, lo_hi):
-        o = post_codes(o)
+        o = post_codes(o) if baseline is None else o    # a baseline's output already is codes
         return o if lo_hi is None else unstretch_codes(o, lo_hi, dm)
 
-    if self_ensemble:
+    if baseline is not None:
+        forward = lambda x, y: x[None, None]                                                                   # noqa: E731
+    elif self_ensemble:
         from .ensemble import self_ensemble as _ensemble
         forward = lambda x, y: _ensemble(model, x, y)                                                          # noqa: E731
     else:
@@ -459,6 +484,16 @@ def main(argv=None):
                          "four views each), undo each on the output and average -- eight forwards' worth of convolution per "
                          "image.  The mean is fp32 whatever --dtype is, so an f16 or bf16 run now post-processes an fp32 map "
                          "(clip, scale and truncate in fp32) where it otherwise post-processes the 16-bit output itself")
+    ap.add_argument("--baseline", default=None, choices=list(BASELINES),
+                    help="with --lr-depth: run a classical upsampler in the network's place (DESIGN 12.14) -- bicubic: the "
+                         "hole-aware bicubic that builds the network's input, as codes; jbu: joint bilateral upsampling (Kopf et "
+                         "al. 2007) under the --input-color image.  No model is built and --dtype is not looked at; "
+                         "--fill-holes, --fill-guided and --normalize prepare the map as they do for the network, and the "
+                         "metrics, the report and the files are the network path's (integers, bit-exact)")
+    ap.add_argument("--jbu-sigma-s", type=float, default=None, metavar="F",
+                    help=f"with --baseline jbu: the spatial sigma in low-resolution pixels (default {JBU_SIGMA_S}, untuned)")
+    ap.add_argument("--jbu-sigma-r", type=float, default=None, metavar="CODES",
+                    help=f"with --baseline jbu: the range sigma in guidance codes (default {FILL_SIGMA}, untuned)")
     ap.add_argument("--serial", action="store_true", help="the reference's own serial loop (decode, upload, forward, download, "
                                                           "encode one after the other per image) instead of the pipeline")
     ap.add_argument("--depth-bits", type=int, default=8, choices=[8, 16],
@@ -488,8 +523,19 @@ def main(argv=None):
     prep = prep_of(ap, a, a.fill_holes, "--fill-holes (and with it --lr-depth)")
     if a.normalize and a.lr_depth is None:
         ap.error("--normalize needs --lr-depth (it is refused with --input-depth: only low-resolution code planes are normalised)")
+    if a.baseline is not None:
+        if a.input_depth is not None or a.lr_depth is None:
+            ap.error("--baseline needs --lr-depth (it is refused with --input-depth: a baseline upsamples low-resolution code planes)")
+        for flag, given in (("--weights", a.weights is not None), ("--ema", a.ema), ("--self-ensemble", a.self_ensemble)):
+            if given:
+                ap.error(f"--baseline is refused with {flag} (no network runs)")
     if a.ema and not a.weights:
         ap.error("--ema needs --weights")
+    for flag, v in (("--jbu-sigma-s", a.jbu_sigma_s), ("--jbu-sigma-r", a.jbu_sigma_r)):
+        if v is not None and a.baseline != "jbu":
+            ap.error(f"{flag} needs --baseline jbu")
+        if v is not None and not (0.0 < v < float("inf")):
+            ap.error(f"{flag} {v} must be positive")
     if a.depth_bits != 16 and (a.depth_max is not None or a.depth_unit != 1.0):
         ap.error("--depth-max and --depth-unit belong to --depth-bits 16")
     a.depth_max = 65535 if a.depth_max is None else a.depth_max
@@ -498,13 +544,20 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("No GPU found, codon_amd has no CPU path")          # test.py:37-38
     dev = torch.device("cuda:0")
-    model = (CODONNet16 if a.scale == 16 else CODONNet)()
-    if a.weights:
-        print("loaded epoch", io.load_checkpoint(a.weights, model, ema=a.ema))
+    if a.baseline is not None:                          # no network: nothing is constructed, --dtype is not looked at
+        model, tdt = None, torch.float32
+        extra = {"baseline": a.baseline,
+                 **({"jbu_sigma_s": JBU_SIGMA_S if a.jbu_sigma_s is None else a.jbu_sigma_s,
+                     "jbu_sigma_r": FILL_SIGMA if a.jbu_sigma_r is None else a.jbu_sigma_r} if a.baseline == "jbu" else {})}
     else:
-        print("WARNING: no --weights given (the reference's X*.pth are not shipped): random init")
-    tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[a.dtype]
-    model = model.to(dev).to(tdt).eval()
+        model = (CODONNet16 if a.scale == 16 else CODONNet)()
+        if a.weights:
+            print("loaded epoch", io.load_checkpoint(a.weights, model, ema=a.ema))
+        else:
+            print("WARNING: no --weights given (the reference's X*.pth are not shipped): random init")
+        tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[a.dtype]
+        model = model.to(dev).to(tdt).eval()
+        extra = {}
     if a.out:
         os.makedirs(a.out, exist_ok=True)
     if a.error_maps:
@@ -512,7 +565,7 @@ def main(argv=None):
     r = run_loop(model, dev, tdt, a.input_depth, a.input_color, a.label, a.out, pipelined=not a.serial,
                  depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit,
                  **({"self_ensemble": True} if a.self_ensemble else {}), **({"report": report} if report else {}),
-                 **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}), **prep.set_options())
+                 **({"lr_depth": a.lr_depth, "scale": a.scale} if a.lr_depth else {}), **prep.set_options(), **extra)
     print(r["n"])
     if a.label and r["n"]:
         print(r["rmse_mean"], r["ssim_mean"])

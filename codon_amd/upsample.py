@@ -239,22 +239,9 @@ def range_table(sigma: float = FILL_SIGMA, device=None):
     return _on_device(("range", s), lambda: _range_table(s).view(np.int16).copy(), torch.device(device))
 
 
-def fill_holes_guided(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigma: float = FILL_SIGMA, depth_max: int = None,
-                      _table: torch.Tensor = None) -> torch.Tensor:
-    """fill_holes with the guidance image's say (DESIGN 12.11): a hole weighs each of the plain filler's four parents by the
-    range table of the difference between its own guidance and the guidance attached to the parent, so that a hole beside an
-    occlusion edge is filled from its own side.  A new tensor of the codes' shape and dtype; no argument is modified.
-    codes: (h,w) or (B,h,w) uint8 codes, or the bits of u16 codes as int16 / uint16, code 0 a hole (depth_max: 255 for uint8,
-    default 65535 otherwise).  guide: (H,W) or (B,H,W) uint8 on the same device with H >= h * scale, W >= w * scale and unit
-    stride along a row; its top-left (h * scale, w * scale) is read IN PLACE through its row and image strides (a plane of a
-    training-pool record, the corner of a larger image).  scale: 4, 8 or 16.  sigma: of range_table, in guidance codes.
-    A constant guide gives fill_holes' bits.  _table is for the tests alone (a constant table, which also gives fill_holes'
-    bits): a (256,) int16 / uint16 device tensor used instead of range_table(sigma); its entries are NOT checked -- nothing
-    reads the device here -- and an entry outside 1 .. 256 makes the output undefined (a 0 can zero a sum of weights, which
-    the kernels divide by).  Valid pixels come back bit for bit, a map without a valid pixel comes back unchanged, and
-    a hole never takes a value above the largest valid code.  Integer arithmetic, bit-exact: tests/guided_fill_ref.py.  One
-    launch up to 64 x 64, three beyond; no host synchronisation."""
-    who = "fill_holes_guided"
+def _guided_args(who: str, codes, guide, scale, sigma, depth_max, _table):
+    """The argument checks and the strided-guide rules the guided filler and the joint bilateral upsampler share ->
+    (contiguous codes, B, h, w, code_bits, top, device, guide row bytes, guide image bytes, range table on the device)"""
     src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
     if scale not in (4, 8, 16):
         raise ValueError(f"{who}: scale {scale!r} (4, 8 or 16)")
@@ -277,6 +264,26 @@ def fill_holes_guided(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigm
         raise RuntimeError(f"{who}: _table must be a contiguous (256,) int16 / uint16 tensor on the codes' device")
     else:
         table = _table
+    return src, B, h, w, bits, top, dev, row_bytes, image_bytes, table
+
+
+def fill_holes_guided(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigma: float = FILL_SIGMA, depth_max: int = None,
+                      _table: torch.Tensor = None) -> torch.Tensor:
+    """fill_holes with the guidance image's say (DESIGN 12.11): a hole weighs each of the plain filler's four parents by the
+    range table of the difference between its own guidance and the guidance attached to the parent, so that a hole beside an
+    occlusion edge is filled from its own side.  A new tensor of the codes' shape and dtype; no argument is modified.
+    codes: (h,w) or (B,h,w) uint8 codes, or the bits of u16 codes as int16 / uint16, code 0 a hole (depth_max: 255 for uint8,
+    default 65535 otherwise).  guide: (H,W) or (B,H,W) uint8 on the same device with H >= h * scale, W >= w * scale and unit
+    stride along a row; its top-left (h * scale, w * scale) is read IN PLACE through its row and image strides (a plane of a
+    training-pool record, the corner of a larger image).  scale: 4, 8 or 16.  sigma: of range_table, in guidance codes.
+    A constant guide gives fill_holes' bits.  _table is for the tests alone (a constant table, which also gives fill_holes'
+    bits): a (256,) int16 / uint16 device tensor used instead of range_table(sigma); its entries are NOT checked -- nothing
+    reads the device here -- and an entry outside 1 .. 256 makes the output undefined (a 0 can zero a sum of weights, which
+    the kernels divide by).  Valid pixels come back bit for bit, a map without a valid pixel comes back unchanged, and
+    a hole never takes a value above the largest valid code.  Integer arithmetic, bit-exact: tests/guided_fill_ref.py.  One
+    launch up to 64 x 64, three beyond; no host synchronisation."""
+    who = "fill_holes_guided"
+    src, B, h, w, bits, top, dev, row_bytes, image_bytes, table = _guided_args(who, codes, guide, scale, sigma, depth_max, _table)
     out = torch.empty_like(src)
     P_ = C.c_void_p
     with torch.cuda.device(dev):
@@ -284,6 +291,91 @@ def fill_holes_guided(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigm
         L.check(L.load().codon_fill_holes_guided(B, h, w, P_(src.data_ptr()), L.FILL_U8 if bits == 8 else L.FILL_U16, top,
                                                  P_(guide.data_ptr()), row_bytes, image_bytes, scale, P_(table.data_ptr()),
                                                  P_(out.data_ptr()), P_(ws.data_ptr()), ws.numel(), ops._stream(dev)), who)
+    return out
+
+
+# ---- the classical baselines: joint bilateral and bicubic upsampling of code planes ---------------------------------
+
+JBU_SIGMA_S = 1.0           # the default spatial sigma of the joint bilateral upsampler in LOW-RESOLUTION pixels: untuned
+
+
+def check_jbu_sigma_s(who: str, sigma_s) -> float:
+    """sigma_s as a float; anything but a finite positive number is refused by name"""
+    try:
+        s = float(sigma_s)
+    except (TypeError, ValueError):
+        s = float("nan")
+    if not (s > 0.0 and s != float("inf")):
+        raise ValueError(f"{who}: sigma_s {sigma_s!r} (a positive number of low-resolution pixels)")
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def _spatial_table(scale: int, sigma_s: float) -> np.ndarray:
+    t = np.zeros((scale, 4), dtype=np.uint16)
+    for ph in range(scale):
+        num = (2 * ph + 1 - scale) % (2 * scale)          # phase_weights' fraction, over 2 * scale
+        for k in range(4):
+            d = abs(num - 2 * scale * (k - 1)) / (2.0 * scale)
+            t[ph, k] = max(1.0, np.rint(256.0 * np.exp(-d * d / (2.0 * sigma_s * sigma_s))))
+    t.setflags(write=False)
+    return t
+
+
+def spatial_table(scale: int, sigma_s: float = JBU_SIGMA_S, device=None):
+    """The spatial table of the joint bilateral upsampler: S[ph][k] = max(1, rint(256 exp(-d^2 / (2 sigma_s^2))))
+    for the output phase ph = 0 .. scale - 1 and the taps k = 0 .. 3 of the bicubic's footprint, d the tap's distance from the
+    pixel in low-resolution pixels, float64 on the host -- a (scale, 4) read-only numpy uint16 array, every entry 1 .. 256.
+    With `device` the cached copy on that device instead (the u16 bits as a (scale, 4) int16 tensor)."""
+    if scale not in (4, 8, 16):
+        raise ValueError(f"spatial_table: scale {scale!r} (4, 8 or 16)")
+    s = check_jbu_sigma_s("spatial_table", sigma_s)
+    if device is None:
+        return _spatial_table(scale, s)
+    return _on_device(("spatial", scale, s), lambda: _spatial_table(scale, s).view(np.int16).copy(), torch.device(device))
+
+
+def joint_bilateral_upsample(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigma_s: float = JBU_SIGMA_S,
+                             sigma_r: float = FILL_SIGMA, depth_max: int = None, _table: torch.Tensor = None) -> torch.Tensor:
+    """Joint bilateral upsampling (Kopf et al. 2007), the classical guided baseline in the network's place: codes of
+    shape (..., h * scale, w * scale) and the input's dtype, no argument modified.  A high-resolution pixel takes the weighted
+    mean of the valid codes in the bicubic's own 4 x 4 footprint, a tap weighing spatial_table(scale, sigma_s) of its distance
+    times range_table(sigma_r) of the difference between the pixel's guidance and the tap's (the box mean of the guidance over
+    the low-resolution pixel); a hole (code 0) weighs nothing, and the output is a hole exactly where the footprint holds no
+    valid code.  codes, guide, scale, depth_max and _table (for the tests alone: the range table, unchecked) as
+    fill_holes_guided takes them, the guide read IN PLACE through its strides.  sigma_s: in low-resolution pixels; sigma_r: in
+    guidance codes.  Integer arithmetic, bit-exact: tests/jbu_ref.py.  Two launches; no host synchronisation."""
+    who = "joint_bilateral_upsample"
+    src, B, h, w, bits, top, dev, row_bytes, image_bytes, table = _guided_args(who, codes, guide, scale, sigma_r, depth_max, _table)
+    stab = spatial_table(scale, check_jbu_sigma_s(who, sigma_s), dev)
+    out = torch.empty((*src.shape[:-2], h * scale, w * scale), dtype=src.dtype, device=dev)
+    P_ = C.c_void_p
+    with torch.cuda.device(dev):
+        ws = _workspace(who, "codon_jbu_workspace_bytes", dev, B, h, w)
+        L.check(L.load().codon_jbu_upsample(B, h, w, P_(src.data_ptr()), L.FILL_U8 if bits == 8 else L.FILL_U16, top,
+                                            P_(guide.data_ptr()), row_bytes, image_bytes, scale, P_(table.data_ptr()),
+                                            P_(stab.data_ptr()), P_(out.data_ptr()), P_(ws.data_ptr()), ws.numel(),
+                                            ops._stream(dev)), who)
+    return out
+
+
+def bicubic_upsample_codes(codes: torch.Tensor, scale: int, depth_max: int = None) -> torch.Tensor:
+    """The bicubic baseline: the hole-aware bicubic of infer.codes_to_input, written as the INTEGER that function
+    looks up before its cast, rint(clamp(up) * top) -- codes of shape (..., h * scale, w * scale) and the input's dtype, a hole
+    of the rule staying 0.  (Not the float input truncated back: float32(k / 255) * 255 truncates to k - 1 for some k.)  codes:
+    (h,w) or (B,h,w) uint8 codes, or the bits of u16 codes as int16 / uint16 (depth_max: default 65535).  One launch."""
+    who = "bicubic_upsample_codes"
+    src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
+    if scale not in (4, 8, 16):
+        raise ValueError(f"{who}: scale {scale!r} (4, 8 or 16)")
+    dev = ops._dev(src)
+    lut, top = code_table(bits, top, dev)
+    wt = _on_device(("up", scale), lambda: phase_weights(scale), dev)
+    out = torch.empty((*src.shape[:-2], h * scale, w * scale), dtype=src.dtype, device=dev)
+    P_ = C.c_void_p
+    with ops._on(dev):
+        L.check(L.load().codon_lr_codes_upsample(B, h, w, scale, P_(src.data_ptr()), bits, P_(lut.data_ptr()), top, P_(wt.data_ptr()),
+                                                 P_(out.data_ptr()), ops._stream(dev)), who)
     return out
 
 

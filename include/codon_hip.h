@@ -725,6 +725,14 @@ int codon_bicubic_downsample_masked(int32_t batch, int32_t size, int32_t scale, 
 int codon_lr_codes_to_input(int32_t batch, int32_t lr_height, int32_t lr_width, int32_t scale, const void* codes,
                             int32_t code_bits, const float* lut, int32_t depth_max, const float* phase_weights, void* out,
                             int32_t dtype, codon_stream_t stream);
+/* codon_lr_codes_upsample: codon_lr_codes_to_input's sibling, the BICUBIC BASELINE: the same per-pixel
+ * arithmetic, but what is written is the INTEGER the look-up takes before the cast, (int)rintf(clamp(., 0, 1) * (float)depth_max),
+ * as codes of the input's own width: out (B,h*scale,w*scale) u8 or u16, 16-byte aligned, not codes itself.  A hole of the
+ * rule stays code 0.  (A baseline cannot go through the float input and back: float32(k / 255) * 255 truncates to k - 1 for
+ * some k.)  One launch. */
+int codon_lr_codes_upsample(int32_t batch, int32_t lr_height, int32_t lr_width, int32_t scale, const void* codes,
+                            int32_t code_bits, const float* lut, int32_t depth_max, const float* phase_weights, void* out,
+                            codon_stream_t stream);
 /* codon_train_crops_lr: a whole training batch -- x, guide, target, (n,1,P,P) fp32 each -- from records that PAIR an HR depth
  * map with a sensor's low-resolution code plane, one launch in place of the synthetic path's four.  Descriptor,
  * window and D4 op are codon_train_crops'; height x width is the HR size (H, W), both multiples of scale (4 / 8 / 16), and the
@@ -898,6 +906,27 @@ size_t codon_fill_guided_workspace_bytes(int32_t height, int32_t width);
 int codon_fill_holes_guided(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top,
                             const uint8_t* guide, int64_t guide_row_bytes, int64_t guide_image_bytes, int32_t scale,
                             const uint16_t* range_tab, void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream);
+
+/* ---- joint bilateral upsampling (codon_amd.upsample.joint_bilateral_upsample) ----------------------------------
+ * The classical guided baseline (Kopf et al. 2007) in the network's place.  No reference counterpart: a DEFINITION, in
+ * codon_amd/csrc/jbu.hip and jbu_tile.h, restated in numpy in tests/jbu_ref.py, equal bits required.  Integers only.
+ *
+ * in: (batch, height, width) codes, 0 a hole; guide as codon_fill_holes_guided's, with its box means G_0.  The pixel (Y, X) of
+ * out, (batch, height * scale, width * scale) codes of the input's width, reads the bicubic's 4 x 4 footprint: rows
+ * y0 - 1 .. y0 + 2, y0 = floor((2 Y + 1 - scale) / (2 scale)), columns likewise.  Tap q = (row ky, column kx) weighs
+ *   w_q = max(1, (spatial_tab[Y % scale][ky] * spatial_tab[X % scale][kx] + 128) >> 8) * range_tab[|guide(Y, X) - G_0(q)|],
+ * 0 where q lies outside the plane or in(q) is 0, and out = (2 sum w_q in(q) + sum w_q) / (2 sum w_q), 0 (a hole) exactly
+ * where no tap is valid.  range_tab: 256 u16, spatial_tab: scale x 4 u16, both ON THE DEVICE and each entry 1 .. 256 (the
+ * caller's duty: sum w_q <= 2^20; the sums are 32-bit for u8 codes and 64-bit for u16 codes).  top is checked, not used.
+ *
+ * codon_jbu_workspace_bytes: HOST ONLY -- the bytes ONE image takes (G_0), a multiple of 16; 0 for a height or width outside
+ * 1 .. 4096.  workspace: batch times that, 16-byte aligned, private to the stream.  Two launches, which depend on (batch,
+ * height, width, scale) alone; no atomics, no host synchronisation.  Refused on the host, before any HIP call:
+ * codon_fill_holes_guided's list, a null spatial_tab, and an out that is not 16-byte aligned. */
+size_t codon_jbu_workspace_bytes(int32_t height, int32_t width);
+int codon_jbu_upsample(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top, const uint8_t* guide,
+                       int64_t guide_row_bytes, int64_t guide_image_bytes, int32_t scale, const uint16_t* range_tab,
+                       const uint16_t* spatial_tab, void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream);
 
 /* ---- per-image range normalisation of depth codes (codon_amd.upsample.code_range / stretch_codes /
  * unstretch_codes) ---------------------------------------------------------------------------------------------------------

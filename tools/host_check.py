@@ -1,6 +1,6 @@
 """Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
 into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
-guided_fill) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+guided_fill, jbu) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
 address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
 restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
 
@@ -22,6 +22,7 @@ from tests import d4_ref as D  # noqa: E402
 from tests import eval_ref as E  # noqa: E402
 from tests import fill_ref as F  # noqa: E402
 from tests import guided_fill_ref as R  # noqa: E402
+from tests import jbu_ref as J  # noqa: E402
 from tests import resample_masked_ref as M  # noqa: E402
 from tests import sensor_ref as S  # noqa: E402
 from tests import stretch_ref as T  # noqa: E402
@@ -188,6 +189,28 @@ def guided_fill(run, p):
                    "no report, every output equals tests/guided_fill_ref.py")
 
 
+def jbu(run, p):
+    """The GPU test's cases (jbu_ref.cases), each with the layout of the guidance its row names: both load paths of a run."""
+    cases = 0
+    for shape in F.SHAPES:
+        B, h, w = shape
+        s = R.SHAPE_SCALE[shape]
+        for name, top, pattern, kind, sigma_s, li in J.cases(shape):
+            layout, skew, pad = guided_layouts(w * s)[li]
+            codes = F.case(shape, pattern, top)
+            codes.tofile(p("i"))
+            R.guide_case(shape, s, kind).tofile(p("g"))
+            R.table_of(10.0).tofile(p("t"))
+            J.spatial_table(s, sigma_s).tofile(p("s"))
+            run(0 if top == 255 else 1, B, h, w, s, skew, pad, p("i"), p("g"), p("t"), p("s"), p("o"))
+            want = J.want(shape, pattern, top, s, kind, 10.0, sigma_s)
+            got = np.fromfile(p("o"), dtype=codes.dtype).reshape(want.shape)
+            assert got.tobytes() == want.tobytes(), (shape, name, pattern, layout, kind, sigma_s)
+            cases += 1
+    return cases, (f"over {len(F.SHAPES)} shapes x {len(J.FORMATS)} formats x {len(F.PATTERNS)} patterns, the guides, sigmas and "
+                   "layouts of the guidance in turn: no report, every output equals tests/jbu_ref.py")
+
+
 # name -> (check, extra compile flags, what the count counts)
 CHECKS = {
     "d4": (d4, ["-ffp-contract=off"], "runs"),
@@ -196,6 +219,7 @@ CHECKS = {
     "fill": (fill, [], "cases"),
     "stretch": (stretch, [], "cases"),
     "guided_fill": (guided_fill, [], "cases"),
+    "jbu": (jbu, [], "cases"),
 }
 
 
