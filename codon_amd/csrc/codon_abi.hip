@@ -11,6 +11,7 @@
 #include "kernels.h"
 #include "launch_rules.h"
 #include "pair.h"
+#include "register_tile.h"
 #include "sensor_pixel.h"
 #include "stretch_tile.h"
 #include "train_record.h"
@@ -1138,6 +1139,39 @@ int codon_jbu_upsample(int32_t batch, int32_t height, int32_t width, const void*
                 workspace_bytes, need);
   return jbu_upsample(batch, height, width, in, fmt, guide, (long)guide_row_bytes, batch == 1 ? 0L : (long)guide_image_bytes, scale,
                       range_tab, spatial_tab, out, workspace, (hipStream_t)stream);
+}
+
+// ---- registration of depth maps to the colour camera ---------------------------------------------------------------
+size_t codon_register_workspace_bytes(int32_t out_height, int32_t out_width) { return register_workspace_bytes(out_height, out_width); }
+
+int codon_register_depth(int32_t batch, int32_t src_height, int32_t src_width, const void* in, int32_t fmt, int32_t top,
+                         const int32_t* rays, const int64_t* trans, const int32_t* proj, int32_t out_height, int32_t out_width,
+                         void* out, uint32_t* stats, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
+  CODON_REQUIRE(in && out && workspace && rays && trans && proj, CODON_ERR_BAD_ARG, "register_depth: null pointer");
+  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "register_depth: fmt %d (0: u8 codes, 1: u16 codes)", fmt);
+  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "register_depth: batch %d (1..65535)", batch);
+  CODON_REQUIRE(src_height >= 1 && src_height <= RG_MAX_SIDE && src_width >= 1 && src_width <= RG_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "register_depth: a %dx%d source (1..%d each way)", src_height, src_width, RG_MAX_SIDE);
+  CODON_REQUIRE(out_height >= 1 && out_height <= RG_MAX_SIDE && out_width >= 1 && out_width <= RG_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "register_depth: a %dx%d target (1..%d each way)", out_height, out_width, RG_MAX_SIDE);
+  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
+                "register_depth: top %d (255 for u8 codes, 1..65535 otherwise)", top);
+  for (int q = 0; q < 3; ++q)
+    CODON_REQUIRE(trans[q] > -RG_T_LIMIT && trans[q] < RG_T_LIMIT, CODON_ERR_BAD_ARG,
+                  "register_depth: translation %d is %lld (Q20 codes, below 2^38 in magnitude)", q, (long long)trans[q]);
+  CODON_REQUIRE(proj[0] >= 1 && proj[0] < RG_F_LIMIT && proj[1] >= 1 && proj[1] < RG_F_LIMIT, CODON_ERR_BAD_ARG,
+                "register_depth: projection FX %d, FY %d (Q8 pixels, 1 .. 2^20 - 1)", proj[0], proj[1]);
+  CODON_REQUIRE(proj[2] > -RG_C_LIMIT && proj[2] < RG_C_LIMIT && proj[3] > -RG_C_LIMIT && proj[3] < RG_C_LIMIT, CODON_ERR_BAD_ARG,
+                "register_depth: projection CX %d, CY %d (Q8 pixels, below 2^21 in magnitude)", proj[2], proj[3]);
+  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "register_depth: in and out are the same buffer");
+  const bool planes_ok = (((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
+  const bool words_ok = (((uintptr_t)rays | (uintptr_t)stats) & 3) == 0 && ((uintptr_t)workspace & 15) == 0;
+  CODON_REQUIRE(planes_ok && words_ok, CODON_ERR_BAD_ARG, "register_depth: unaligned plane, table, statistics or workspace");
+  const size_t need = (size_t)batch * register_workspace_bytes(out_height, out_width);
+  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "register_depth: a workspace of %zu bytes is too small (%zu needed)",
+                workspace_bytes, need);
+  return register_depth(batch, src_height, src_width, in, fmt, top, rays, (const long long*)trans, proj, out_height, out_width, out,
+                        stats, workspace, (hipStream_t)stream);
 }
 
 // ---- per-image range normalisation of depth codes ---------------------------------------------------------------

@@ -177,6 +177,12 @@ size_t jbu_workspace_bytes(int h, int w);
 int jbu_upsample(int B, int h, int w, const void* in, int fmt, const void* guide, long row_bytes, long image_bytes, int scale,
                  const void* range_tab, const void* spatial_tab, void* out, void* workspace, hipStream_t stream);
 
+// register.hip; rays: (hs + 1, ws + 1, 3) int32 on the device; trans (3) and proj (4) on the host; stats: (B, 4) u32 or null;
+// workspace: B u32 planes of ho x wo
+size_t register_workspace_bytes(int ho, int wo);
+int register_depth(int B, int hs, int ws, const void* in, int fmt, int top, const void* rays, const long long* trans, const int* proj,
+                   int ho, int wo, void* out, void* stats, void* workspace, hipStream_t stream);
+
 // stretch.hip; fmt: ST_U8 / ST_U16, dir: ST_STRETCH / ST_UNSTRETCH (stretch_tile.h); n: codes per image
 int code_range(int B, long n, const void* codes, int fmt, int* lo_hi, hipStream_t stream);
 int map_codes(int dir, int B, long n, const void* in, int fmt, int top, const int* lo_hi, void* out, hipStream_t stream);

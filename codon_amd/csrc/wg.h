@@ -9,10 +9,12 @@
 //   WgDevice  WG_EACH is one trip with tid = threadIdx.x, spelled as an `if` with an initialiser and not as a one-trip `for`:
 //             with a `for` around them the compiler schedules the phases' unrolled loads differently (fill_push_kernel: 54 -> 70
 //             VGPRs), with the `if` the code is the hand-strung kernel's; sync() is __syncthreads(); Regs<T, N> is a plain local
-//             array.  Hence: WG_EACH takes one statement or a braced block, and never stands before an `else`
+//             array.  Hence: WG_EACH takes one statement or a braced block, and never stands before an `else`;
+//             atomic_min / atomic_add are the device's atomics on global memory, results not returned
 //   WgHost    WG_EACH runs tid over all threads, forwards or (reverse) backwards, so that a phase that reads what another thread
 //             of the SAME phase writes gives different bytes in the two orders; sync() does nothing; Regs<T, N> is one
-//             separately allocated row of exactly N elements per thread: a thread that writes past its registers is a report
+//             separately allocated row of exactly N elements per thread: a thread that writes past its registers is a report;
+//             atomic_min / atomic_add are a plain minimum and a plain add (one thread runs at a time)
 #pragma once
 
 #if defined(__HIPCC__)
@@ -30,6 +32,8 @@ struct WgDevice {
   };
   __device__ __forceinline__ int first() const { return threadIdx.x; }
   __device__ __forceinline__ void sync() const { __syncthreads(); }
+  __device__ __forceinline__ void atomic_min(unsigned* p, unsigned v) const { atomicMin(p, v); }
+  __device__ __forceinline__ void atomic_add(unsigned* p, unsigned v) const { atomicAdd(p, v); }
 };
 
 }  // namespace codon
@@ -64,6 +68,8 @@ struct WgHost {
   int count() const { return threads; }
   int step() const { return reverse ? -1 : 1; }
   void sync() const {}
+  void atomic_min(unsigned* p, unsigned v) const { *p = v < *p ? v : *p; }
+  void atomic_add(unsigned* p, unsigned v) const { *p += v; }
 };
 
 }  // namespace codon

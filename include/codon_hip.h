@@ -928,6 +928,37 @@ int codon_jbu_upsample(int32_t batch, int32_t height, int32_t width, const void*
                        int64_t guide_row_bytes, int64_t guide_image_bytes, int32_t scale, const uint16_t* range_tab,
                        const uint16_t* spatial_tab, void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream);
 
+/* ---- registration of depth maps to the colour camera (codon_amd.register) ---------------------------------------
+ * Nothing in the reference: its inputs were registered and upsampled offline.  A DEFINITION, in codon_amd/csrc/register.hip and
+ * register_tile.h, restated in numpy in tests/register_ref.py, equal bits required.  Integers only.
+ *
+ * A depth sensor's map, in its own camera, is projected forwards onto the colour camera's grid under a z-test.  in: (batch,
+ * src_height, src_width) codes, 0 a hole.  rays: int32 (src_height + 1, src_width + 1, 3) ON THE DEVICE, shared by the batch:
+ * rays[i][j] = rint(2^20 R r) with r the undistorted normalised ray of the source image point (j - 0.5, i - 0.5), the top-left
+ * corner of pixel (i, j), and R the depth -> colour rotation; every entry below 2^22 in magnitude (the caller's duty: nothing
+ * reads the device here).  trans: int64[3] ON THE HOST, rint(2^20 t / unit) in Q20 codes.  proj: int32[4] ON THE HOST, FX, FY,
+ * CX, CY in Q8 pixels of the output grid.  A valid pixel (i, j) with code k has the corners a = (i, j), b = (i + 1, j + 1),
+ * c = (i, j + 1), d = (i + 1, j); P_q = k rays[q] + trans.  Any P_q.z < 2^20: dropped.  z' = (((P_a.z + P_b.z + 1) >> 1) + 2^19)
+ * >> 20; not 1 <= z' <= top: dropped.  U_q = floor((FX P_q.x + CX P_q.z) / P_q.z), V_q likewise with FY, CY and P_q.y.  The
+ * footprint is x0 = (min U + 255) >> 8 .. x1 = ((max U + 255) >> 8) - 1 and y likewise: wider or taller than 8 pixels: dropped;
+ * empty: nothing is written; wholly outside the out_height x out_width plane: counted as outside; else clipped to the plane, and
+ * every pixel of it takes the minimum of what it holds and z'.  out: (batch, out_height, out_width) codes of the input's width,
+ * the minimum where one was written, 0 elsewhere.  stats: NULL, or (batch, 4) uint32 ON THE DEVICE: valid source pixels,
+ * outside, dropped, filled target pixels; it needs no initialisation.
+ *
+ * codon_register_workspace_bytes: HOST ONLY -- the bytes ONE image takes (a u32 per target pixel), a multiple of 16; 0 for a
+ * height or width outside 1 .. 4096.  workspace: batch times that, 16-byte aligned, private to the stream; initialised by the
+ * call itself, on the stream.  Three launches, which depend on the sizes alone; 32-bit atomic minima and adds on global memory,
+ * whose result does not depend on their order; no host synchronisation.  Refused on the host, before any HIP call: null
+ * pointers (stats may be NULL), an fmt other than CODON_FILL_U8 / _U16, batch outside 1 .. 65535, a source or target height or
+ * width outside 1 .. 4096, top outside 1 .. 65535 or not 255 for u8 codes, |trans| >= 2^38, FX or FY outside 1 .. 2^20 - 1,
+ * |CX| or |CY| >= 2^21, out == in, a u16 plane that is not 2-byte aligned, rays or stats not 4-byte aligned, a workspace that
+ * is not 16-byte aligned or too small. */
+size_t codon_register_workspace_bytes(int32_t out_height, int32_t out_width);
+int codon_register_depth(int32_t batch, int32_t src_height, int32_t src_width, const void* in, int32_t fmt, int32_t top,
+                         const int32_t* rays, const int64_t* trans, const int32_t* proj, int32_t out_height, int32_t out_width,
+                         void* out, uint32_t* stats, void* workspace, size_t workspace_bytes, codon_stream_t stream);
+
 /* ---- per-image range normalisation of depth codes (codon_amd.upsample.code_range / stretch_codes /
  * unstretch_codes) ---------------------------------------------------------------------------------------------------------
  * No reference counterpart (its data was normalised offline, if at all): a DEFINITION, in codon_amd/csrc/stretch.hip and

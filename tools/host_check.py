@@ -1,6 +1,6 @@
 """Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
 into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
-guided_fill, jbu) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+guided_fill, jbu, register) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
 address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
 restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
 
@@ -23,6 +23,7 @@ from tests import eval_ref as E  # noqa: E402
 from tests import fill_ref as F  # noqa: E402
 from tests import guided_fill_ref as R  # noqa: E402
 from tests import jbu_ref as J  # noqa: E402
+from tests import register_ref as G  # noqa: E402
 from tests import resample_masked_ref as M  # noqa: E402
 from tests import sensor_ref as S  # noqa: E402
 from tests import stretch_ref as T  # noqa: E402
@@ -211,6 +212,26 @@ def jbu(run, p):
                    "layouts of the guidance in turn: no report, every output equals tests/jbu_ref.py")
 
 
+def register(run, p):
+    """The GPU test's cases (register_ref.cases): every shape under every pattern and calibration, the formats in turn."""
+    cases = 0
+    for shape in G.SHAPES:
+        B, hs, ws, ho, wo = shape[:5]
+        for name, top, pattern, calib in G.cases(shape):
+            A, T, P = G.tables(shape, calib, top)
+            codes = G.plane(shape, pattern, top)
+            codes.tofile(p("i")), A.tofile(p("a"))
+            np.concatenate([T, P.astype(np.int64)]).tofile(p("p"))
+            run(0 if top == 255 else 1, B, hs, ws, top, ho, wo, p("i"), p("a"), p("p"), p("o"), p("s"))
+            want, stats = G.want(shape, pattern, top, calib)
+            got = np.fromfile(p("o"), dtype=codes.dtype).reshape(want.shape)
+            assert got.tobytes() == want.tobytes(), (shape, name, pattern, calib)
+            assert np.fromfile(p("s"), dtype=np.uint32).tobytes() == stats.tobytes(), (shape, name, pattern, calib, "statistics")
+            cases += 1
+    return cases, (f"over {len(G.SHAPES)} shapes x {len(G.PATTERNS)} patterns x {len(G.CALIBS)} calibrations, the {len(G.FORMATS)} formats "
+                   "in turn: no report, every output equals tests/register_ref.py")
+
+
 # name -> (check, extra compile flags, what the count counts)
 CHECKS = {
     "d4": (d4, ["-ffp-contract=off"], "runs"),
@@ -220,6 +241,7 @@ CHECKS = {
     "stretch": (stretch, [], "cases"),
     "guided_fill": (guided_fill, [], "cases"),
     "jbu": (jbu, [], "cases"),
+    "register": (register, [], "cases"),
 }
 
 
