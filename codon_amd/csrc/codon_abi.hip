@@ -15,6 +15,7 @@
 #include "sensor_pixel.h"
 #include "stretch_tile.h"
 #include "train_record.h"
+#include "undistort_tile.h"
 
 namespace codon {
 
@@ -1172,6 +1173,41 @@ int codon_register_depth(int32_t batch, int32_t src_height, int32_t src_width, c
                 workspace_bytes, need);
   return register_depth(batch, src_height, src_width, in, fmt, top, rays, (const long long*)trans, proj, out_height, out_width, out,
                         stats, workspace, (hipStream_t)stream);
+}
+
+// ---- undistortion of colour images ---------------------------------------------------------------------------------
+size_t codon_undistort_tiles_bytes(int32_t out_height, int32_t out_width) { return undistort_tiles_bytes(out_height, out_width); }
+
+int codon_undistort_plan(int32_t src_height, int32_t src_width, int32_t out_height, int32_t out_width, const int32_t* map_host,
+                         int32_t* tiles_host, uint32_t* counts_host) {
+  CODON_REQUIRE(map_host && tiles_host && counts_host, CODON_ERR_BAD_ARG, "undistort_plan: null pointer");
+  CODON_REQUIRE(src_height >= 1 && src_height <= UD_MAX_SIDE && src_width >= 1 && src_width <= UD_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "undistort_plan: a %dx%d source (1..%d each way)", src_height, src_width, UD_MAX_SIDE);
+  CODON_REQUIRE(out_height >= 1 && out_height <= UD_MAX_SIDE && out_width >= 1 && out_width <= UD_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "undistort_plan: a %dx%d target (1..%d each way)", out_height, out_width, UD_MAX_SIDE);
+  const long bad = undistort_plan(src_height, src_width, out_height, out_width, map_host, tiles_host, counts_host);
+  CODON_REQUIRE(bad < 0, CODON_ERR_BAD_ARG,
+                "undistort_plan: map entry (%ld, %ld) is (%d, %d): neither the outside pair nor a Q5 position in the %dx%d source "
+                "(-16 <= U < 32 width - 16, V likewise)", bad / out_width, bad % out_width, map_host[2 * bad], map_host[2 * bad + 1],
+                src_height, src_width);
+  return CODON_OK;
+}
+
+int codon_undistort(int32_t batch, int32_t src_height, int32_t src_width, int32_t channels, const uint8_t* in, int32_t out_height,
+                    int32_t out_width, const int32_t* map, const int32_t* tiles, const int16_t* weights, uint8_t* out,
+                    codon_stream_t stream) {
+  CODON_REQUIRE(in && out && map && tiles && weights, CODON_ERR_BAD_ARG, "undistort: null pointer");
+  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "undistort: batch %d (1..65535)", batch);
+  CODON_REQUIRE(src_height >= 1 && src_height <= UD_MAX_SIDE && src_width >= 1 && src_width <= UD_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "undistort: a %dx%d source (1..%d each way)", src_height, src_width, UD_MAX_SIDE);
+  CODON_REQUIRE(out_height >= 1 && out_height <= UD_MAX_SIDE && out_width >= 1 && out_width <= UD_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "undistort: a %dx%d target (1..%d each way)", out_height, out_width, UD_MAX_SIDE);
+  CODON_REQUIRE(channels == 1 || channels == 3, CODON_ERR_BAD_ARG, "undistort: channels %d (1: grey, 3: RGB)", channels);
+  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "undistort: in and out are the same buffer");
+  CODON_REQUIRE(((uintptr_t)map & 7) == 0 && ((uintptr_t)tiles & 15) == 0 && ((uintptr_t)weights & 1) == 0, CODON_ERR_BAD_ARG,
+                "undistort: unaligned table (map: 8 bytes, tiles: 16, weights: 2)");
+  return undistort(batch, src_height, src_width, channels, in, out_height, out_width, map, tiles, weights, out,
+                   (hipStream_t)stream);
 }
 
 // ---- per-image range normalisation of depth codes ---------------------------------------------------------------

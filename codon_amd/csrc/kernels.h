@@ -183,6 +183,14 @@ size_t register_workspace_bytes(int ho, int wo);
 int register_depth(int B, int hs, int ws, const void* in, int fmt, int top, const void* rays, const long long* trans, const int* proj,
                    int ho, int wo, void* out, void* stats, void* workspace, hipStream_t stream);
 
+// undistort.hip; in: (B, hs, ws, channels) u8, out: (B, ho, wo, channels) u8; map (ho, wo, 2) int32, tiles (the words of
+// undistort_tiles_bytes) and weights (32, 4) int16 on the device.  undistort_plan: HOST -- the tile table and the four counts of a
+// host copy of the map; -1, or the index of the first entry it refuses
+size_t undistort_tiles_bytes(int ho, int wo);
+long undistort_plan(int hs, int ws, int ho, int wo, const int* map, int* tiles, unsigned* counts);
+int undistort(int B, int hs, int ws, int channels, const void* in, int ho, int wo, const void* map, const void* tiles,
+              const void* weights, void* out, hipStream_t stream);
+
 // stretch.hip; fmt: ST_U8 / ST_U16, dir: ST_STRETCH / ST_UNSTRETCH (stretch_tile.h); n: codes per image
 int code_range(int B, long n, const void* codes, int fmt, int* lo_hi, hipStream_t stream);
 int map_codes(int dir, int B, long n, const void* in, int fmt, int top, const int* lo_hi, void* out, hipStream_t stream);

@@ -9,7 +9,8 @@ out as code 0, which `--fill-holes --fill-guided` was built for.
 A z-buffered forward projection in integers (tests/register_ref.py; csrc/register.hip): every valid source pixel's four corners
 are projected, the box of them takes the pixel's z in the colour camera's frame under a minimum.  Only the tables -- the corner
 rays with the lens distortion removed and the rotation applied, the translation, the projection -- are floating point, float64
-on the host, once.  Not handled: distortion of the COLOUR lens (undistort the colour images first), a rolling shutter, and the
+on the host, once.  Not handled here: distortion of the COLOUR lens (undistort the colour images first, with
+`python -m codon_amd.undistort`, whose --calib-out is the calibration to pass here: DESIGN 12.16), a rolling shutter, and the
 growth of a foreground silhouette by up to one target pixel (the box is conservative)."""
 from __future__ import annotations
 
@@ -110,7 +111,8 @@ class Calibration:
             raise ValueError(f"{who}: translation must be three numbers (metres)")
         t = _finite(who, "translation", t)
         if any(self.color.dist):
-            raise ValueError(f"{who}: color.dist {self.color.dist!r} is not zero: undistort the colour images first")
+            raise ValueError(f"{who}: color.dist {self.color.dist!r} is not zero: undistort the colour images first "
+                             "(python -m codon_amd.undistort --calib-out ...)")
         object.__setattr__(self, "rotation", tuple(tuple(float(v) for v in r) for r in R))
         object.__setattr__(self, "translation", tuple(t))
 

@@ -959,6 +959,40 @@ int codon_register_depth(int32_t batch, int32_t src_height, int32_t src_width, c
                          const int32_t* rays, const int64_t* trans, const int32_t* proj, int32_t out_height, int32_t out_width,
                          void* out, uint32_t* stats, void* workspace, size_t workspace_bytes, codon_stream_t stream);
 
+/* ---- undistortion of colour images (codon_amd.undistort) ---------------------------------------------------------
+ * Nothing in the reference: its colour images were rectified offline.  A DEFINITION, in codon_amd/csrc/undistort.hip and
+ * undistort_tile.h, restated in numpy in tests/undistort_ref.py, equal bits required.  Integers only.
+ *
+ * The image of a camera with Brown distortion is resampled to a pinhole camera, the grid codon_register_depth projects onto.
+ * in: (batch, src_height, src_width, channels) u8, interleaved, channels 1 (grey) or 3 (RGB); out: (batch, out_height,
+ * out_width, channels) u8.  Neither needs any alignment.  map: int32 (out_height, out_width, 2) ON THE DEVICE, shared by the
+ * batch: the source position (U, V) of a target pixel in Q5 source pixels, -16 <= U < 32 src_width - 16 and V likewise, or
+ * the outside pair (-2^20, -2^20).  weights: int16 (32, 4) ON THE DEVICE: the taps -1, 0, 1, 2 of a cubic at the 32 phases,
+ * Q11, sum |weights[p]| <= 2560 (the caller's duty: nothing reads the device here; then every intermediate fits 32 bits).  A
+ * pixel that is not outside: xi = U >> 5, px = U & 31, yi and py likewise; tap (r, c) = in[clamp(yi - 1 + r)][clamp(xi - 1 +
+ * c)]; row_r = sum_c weights[px][c] tap, acc = sum_r weights[py][r] row_r, out = clamp((acc + 2^21) >> 22, 0, 255) per
+ * channel.  An outside pixel is 0 in every channel.
+ *
+ * tiles: int32 (ceil(out_height / 8), ceil(out_width / 32), 4) ON THE DEVICE = kind, x0, y0, 0 per 32 x 8 tile of target
+ * pixels, as codon_undistort_plan wrote it: 0 EMPTY (no pixel inside: zeros), 1 STAGED (the box of every tap of the tile's
+ * inside pixels fits the 48 x 24 window from (y0, x0), which the workgroup stages in LDS), 2 DIRECT (taps from global memory).
+ * The kind changes how a tile is computed, never what.
+ *
+ * codon_undistort_tiles_bytes: HOST ONLY -- the bytes of the tile table; 0 for a height or width outside 1 .. 4096.
+ * codon_undistort_plan: HOST ONLY, every pointer ON THE HOST -- writes the tile table of a map and counts_host[4]: staged,
+ * direct and empty tiles, outside pixels.  Refused: null pointers, a height or width outside 1 .. 4096, and a map entry that is
+ * neither the outside pair nor inside the bounds above: a table that passes cannot make a tile read past its window.
+ * codon_undistort: one launch, which depends on (batch, out_height, out_width, channels) alone; no workspace, no atomics, no
+ * host synchronisation.  Refused on the host, before any HIP call: null pointers, batch outside 1 .. 65535, a source or target
+ * height or width outside 1 .. 4096, channels other than 1 or 3, out == in, a map that is not 8-byte aligned, tiles not
+ * 16-byte aligned, weights not 2-byte aligned. */
+size_t codon_undistort_tiles_bytes(int32_t out_height, int32_t out_width);
+int codon_undistort_plan(int32_t src_height, int32_t src_width, int32_t out_height, int32_t out_width, const int32_t* map_host,
+                         int32_t* tiles_host, uint32_t* counts_host);
+int codon_undistort(int32_t batch, int32_t src_height, int32_t src_width, int32_t channels, const uint8_t* in, int32_t out_height,
+                    int32_t out_width, const int32_t* map, const int32_t* tiles, const int16_t* weights, uint8_t* out,
+                    codon_stream_t stream);
+
 /* ---- per-image range normalisation of depth codes (codon_amd.upsample.code_range / stretch_codes /
  * unstretch_codes) ---------------------------------------------------------------------------------------------------------
  * No reference counterpart (its data was normalised offline, if at all): a DEFINITION, in codon_amd/csrc/stretch.hip and

@@ -1,6 +1,6 @@
 """Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
 into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
-guided_fill, jbu, register) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+guided_fill, jbu, register, undistort) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
 address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
 restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
 
@@ -27,6 +27,7 @@ from tests import register_ref as G  # noqa: E402
 from tests import resample_masked_ref as M  # noqa: E402
 from tests import sensor_ref as S  # noqa: E402
 from tests import stretch_ref as T  # noqa: E402
+from tests import undistort_ref as U  # noqa: E402
 
 FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 
@@ -232,6 +233,25 @@ def register(run, p):
                    "in turn: no report, every output equals tests/register_ref.py")
 
 
+def undistort(run, p):
+    """The GPU test's cases (undistort_ref.cases): every shape under every rig and pattern, the images on a 16-byte boundary and
+    one byte off it in turn; the tile table and the counts the program made with ud_tiles beside the output"""
+    U.weight_table().tofile(p("k"))
+    cases = 0
+    for shape in U.SHAPES:
+        B, H, W, C, ho, wo = shape
+        for rig, pattern in U.cases(shape):
+            M, tiles, counts = U.tables(shape, rig)
+            M.tofile(p("m")), U.image(shape, pattern).tofile(p("i"))
+            run(C, B, H, W, ho, wo, cases % 2, p("i"), p("m"), p("k"), p("o"), p("t"), p("c"))
+            assert np.fromfile(p("o"), dtype=np.uint8).tobytes() == U.want(shape, rig, pattern).tobytes(), (shape, rig, pattern)
+            assert np.fromfile(p("t"), dtype=np.int32).tobytes() == tiles.tobytes(), (shape, rig, "tile table")
+            assert np.fromfile(p("c"), dtype=np.uint32).tobytes() == counts.tobytes(), (shape, rig, "counts")
+            cases += 1
+    return cases, (f"over {len(U.SHAPES)} shapes x {len(U.RIGS)} rigs x {len(U.PATTERNS)} patterns: no report, every output, tile "
+                   "table and count equals tests/undistort_ref.py")
+
+
 # name -> (check, extra compile flags, what the count counts)
 CHECKS = {
     "d4": (d4, ["-ffp-contract=off"], "runs"),
@@ -242,6 +262,7 @@ CHECKS = {
     "guided_fill": (guided_fill, [], "cases"),
     "jbu": (jbu, [], "cases"),
     "register": (register, [], "cases"),
+    "undistort": (undistort, [], "cases"),
 }
 
 
