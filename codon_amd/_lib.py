@@ -202,6 +202,8 @@ SIGNATURES = {
     "codon_jbu_upsample": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, C.c_int64, C.c_int64, _I, _P, _P, _P, _P, _S, _P]),
     "codon_register_workspace_bytes": (_S, [_I, _I]),
     "codon_register_depth": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _S, _P]),
+    "codon_clean_workspace_bytes": (_S, [_I, _I, _I]),
+    "codon_clean_depth": (C.c_int, [_I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _S, _P]),
     "codon_undistort_tiles_bytes": (_S, [_I, _I]),
     "codon_undistort_plan": (C.c_int, [_I, _I, _I, _I, _P, _P, _P]),
     "codon_undistort": (C.c_int, [_I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),

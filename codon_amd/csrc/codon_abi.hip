@@ -12,6 +12,7 @@
 #include "launch_rules.h"
 #include "pair.h"
 #include "register_tile.h"
+#include "clean_tile.h"
 #include "sensor_pixel.h"
 #include "stretch_tile.h"
 #include "train_record.h"
@@ -1173,6 +1174,37 @@ int codon_register_depth(int32_t batch, int32_t src_height, int32_t src_width, c
                 workspace_bytes, need);
   return register_depth(batch, src_height, src_width, in, fmt, top, rays, (const long long*)trans, proj, out_height, out_width, out,
                         stats, workspace, (hipStream_t)stream);
+}
+
+// ---- outlier rejection of sensor depth maps -------------------------------------------------------------------------
+size_t codon_clean_workspace_bytes(int32_t batch, int32_t height, int32_t width) { return clean_workspace_bytes(batch, height, width); }
+
+int codon_clean_depth(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top, int32_t tol_abs,
+                      int32_t tol_rel_q16, int32_t min_support, int32_t min_region, void* out, uint32_t* counts, void* workspace,
+                      size_t workspace_bytes, codon_stream_t stream) {
+  CODON_REQUIRE(in && out && workspace, CODON_ERR_BAD_ARG, "clean_depth: null pointer");
+  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "clean_depth: fmt %d (0: u8 codes, 1: u16 codes)", fmt);
+  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "clean_depth: batch %d (1..65535)", batch);
+  CODON_REQUIRE(height >= 1 && height <= CL_MAX_SIDE && width >= 1 && width <= CL_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "clean_depth: a %dx%d plane (1..%d each way)", height, width, CL_MAX_SIDE);
+  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
+                "clean_depth: top %d (255 for u8 codes, 1..65535 otherwise)", top);
+  CODON_REQUIRE(tol_abs >= 0 && tol_abs <= top, CODON_ERR_BAD_ARG, "clean_depth: tolerance %d (codes, 0..top = %d)", tol_abs, top);
+  CODON_REQUIRE(tol_rel_q16 >= 0 && tol_rel_q16 <= CL_MAX_REL, CODON_ERR_BAD_ARG,
+                "clean_depth: tolerance_rel %d (Q16, 0..%d)", tol_rel_q16, CL_MAX_REL);
+  CODON_REQUIRE(min_support >= 0 && min_support <= CL_MAX_SUPPORT, CODON_ERR_BAD_ARG, "clean_depth: min_support %d (0..%d)",
+                min_support, CL_MAX_SUPPORT);
+  CODON_REQUIRE(min_region >= 0 && min_region <= CL_MAX_REGION, CODON_ERR_BAD_ARG, "clean_depth: min_region %d (0..%d)", min_region,
+                CL_MAX_REGION);
+  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "clean_depth: in and out are the same buffer");
+  const bool planes_ok = (((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
+  const bool words_ok = ((uintptr_t)counts & 3) == 0 && ((uintptr_t)workspace & 15) == 0;
+  CODON_REQUIRE(planes_ok && words_ok, CODON_ERR_BAD_ARG, "clean_depth: unaligned plane, statistics or workspace");
+  const size_t need = clean_workspace_bytes(batch, height, width);
+  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "clean_depth: a workspace of %zu bytes is too small (%zu needed)",
+                workspace_bytes, need);
+  return clean_depth(batch, height, width, in, fmt, tol_abs, tol_rel_q16, min_support, min_region, out, counts, workspace,
+                     (hipStream_t)stream);
 }
 
 // ---- undistortion of colour images ---------------------------------------------------------------------------------

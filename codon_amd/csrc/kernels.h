@@ -183,6 +183,11 @@ size_t register_workspace_bytes(int ho, int wo);
 int register_depth(int B, int hs, int ws, const void* in, int fmt, int top, const void* rays, const long long* trans, const int* proj,
                    int ho, int wo, void* out, void* stats, void* workspace, hipStream_t stream);
 
+// clean.hip; stats: (B, 4) u32 or null; workspace: a u32 label plane and a u32 size plane of B images
+size_t clean_workspace_bytes(int B, int h, int w);
+int clean_depth(int B, int h, int w, const void* in, int fmt, int tol_abs, int tol_rel_q16, int min_support, int min_region, void* out,
+                void* stats, void* workspace, hipStream_t stream);
+
 // undistort.hip; in: (B, hs, ws, channels) u8, out: (B, ho, wo, channels) u8; map (ho, wo, 2) int32, tiles (the words of
 // undistort_tiles_bytes) and weights (32, 4) int16 on the device.  undistort_plan: HOST -- the tile table and the four counts of a
 // host copy of the map; -1, or the index of the first entry it refuses

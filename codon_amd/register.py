@@ -4,14 +4,17 @@ colour / scale, which is what `infer --lr-depth`, `train --train-lr-depth` and `
 out as code 0, which `--fill-holes --fill-guided` was built for.
 
     python -m codon_amd.register --depth DIR --calib FILE --out DIR [--scale {1,4,8,16}] [--depth-bits {8,16}] [--depth-max N]
-                                 [--depth-unit M] [--radial] [--stats]
+                                 [--depth-unit M] [--radial] [--stats] [--clean [--clean-tolerance CODES]
+                                 [--clean-tolerance-rel F] [--clean-min-support K] [--clean-min-region N]]
 
 A z-buffered forward projection in integers (tests/register_ref.py; csrc/register.hip): every valid source pixel's four corners
 are projected, the box of them takes the pixel's z in the colour camera's frame under a minimum.  Only the tables -- the corner
 rays with the lens distortion removed and the rotation applied, the translation, the projection -- are floating point, float64
 on the host, once.  Not handled here: distortion of the COLOUR lens (undistort the colour images first, with
 `python -m codon_amd.undistort`, whose --calib-out is the calibration to pass here: DESIGN 12.16), a rolling shutter, and the
-growth of a foreground silhouette by up to one target pixel (the box is conservative)."""
+growth of a foreground silhouette by up to one target pixel (the box is conservative).  --clean removes the sensor's flying
+pixels and speckles first, in the sensor's frame (codon_amd.clean): the same bytes as `python -m codon_amd.clean`
+followed by this, on one upload."""
 from __future__ import annotations
 
 import argparse
@@ -25,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import clean as cleaning
 from . import io, ops
 from .upsample import _code_planes, _workspace
 
@@ -274,6 +278,9 @@ def parse_args(argv=None):
     ap.add_argument("--depth-unit", type=float, default=0.001, metavar="M", help="metres per code (default 0.001)")
     ap.add_argument("--radial", action="store_true", help="the files hold ranges along the ray, not z")
     ap.add_argument("--stats", action="store_true", help="print valid=, outside=, dropped= and filled= per file")
+    ap.add_argument("--clean", action="store_true", help="remove flying pixels and speckles first (python -m codon_amd.clean); "
+                    "--stats then also prints valid=, flying=, speckle= and regions= of the cleaning")
+    cleaning.add_arguments(ap, "clean-")
     a = ap.parse_args(argv)
     if a.depth_max is not None and a.depth_bits != 16:
         ap.error("--depth-max needs --depth-bits 16")
@@ -283,6 +290,16 @@ def parse_args(argv=None):
         ap.error(f"--depth-unit {a.depth_unit} must be positive")
     if os.path.abspath(a.out) == os.path.abspath(a.depth):
         ap.error("--out is --depth: the registered maps would overwrite the sensor's")
+    a.cleaner = None
+    if a.clean:
+        a.cleaner = cleaning.cleaner_of(a, ap, "clean-")
+        top = 255 if a.depth_bits == 8 else 65535 if a.depth_max is None else a.depth_max
+        if a.cleaner.tolerance > top:
+            ap.error(f"--clean-tolerance {a.cleaner.tolerance} is above the largest code {top}")
+    else:
+        for name, default in cleaning.DEFAULTS.items():
+            if getattr(a, "clean_" + name) != default:
+                ap.error(f"--clean-{name.replace('_', '-')} needs --clean")
     return a, ap
 
 
@@ -302,6 +319,10 @@ def main(argv=None, emit=print):
     for name in sorted(os.listdir(a.depth)):
         plane = io.read_depth_plane(os.path.join(a.depth, name), a.depth_bits, depth_max)
         codes = torch.from_numpy((plane.view(np.int16) if plane.dtype == np.uint16 else plane).copy()).to(reg.device)
+        cleaned = None
+        if a.cleaner is not None:
+            codes = a.cleaner(codes, depth_max if a.depth_bits == 16 else None, stats=a.stats)
+            codes, cleaned = codes if a.stats else (codes, None)
         got = reg(codes, depth_max if a.depth_bits == 16 else None, stats=a.stats)
         out, counts = got if a.stats else (got, None)
         if a.depth_bits == 16:
@@ -310,7 +331,8 @@ def main(argv=None, emit=print):
             io.write_gray(os.path.join(a.out, name), out.cpu().numpy())
         if a.stats:
             c = counts.cpu().numpy().view(np.uint32)[0]
-            emit(f"{name} " + " ".join(f"{k}={int(v)}" for k, v in zip(STATS, c)))
+            tail = "" if cleaned is None else " cleaned: " + cleaning.stats_line(cleaned.cpu().numpy()[0])
+            emit(f"{name} " + " ".join(f"{k}={int(v)}" for k, v in zip(STATS, c)) + tail)
         else:
             emit(name)
     return 0

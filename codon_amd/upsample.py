@@ -156,11 +156,12 @@ def _code_planes(who: str, codes: torch.Tensor, depth_max, expects: str = CODES)
 _ws: dict = {}              # filler -> (guards.PerStream -> uint8 workspace of the (device, stream, thread), those made under a capture)
 
 
-def _workspace(who: str, query: str, dev, B: int, h: int, w: int):
+def _workspace(who: str, query: str, dev, B: int, h: int, w: int, batched: bool = False):
     """Filler `who`'s workspace for B planes of h x w on dev's current stream, sized by the library's `query` (capture-safe:
-    guards.PerStream); the two fillers never share one.  Call it with `dev` current."""
+    guards.PerStream); the two fillers never share one.  `query` answers for one plane, or (batched) for all B.  Call it with
+    `dev` current."""
     from .guards import PerStream
-    need = B * getattr(L.load(), query)(h, w)
+    need = getattr(L.load(), query)(B, h, w) if batched else B * getattr(L.load(), query)(h, w)
     if need == 0:
         raise ValueError(f"{who}: a {h}x{w} plane (1..4096 each way)")
     per_stream, held = _ws.setdefault(who, (PerStream(), []))

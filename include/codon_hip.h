@@ -959,6 +959,33 @@ int codon_register_depth(int32_t batch, int32_t src_height, int32_t src_width, c
                          const int32_t* rays, const int64_t* trans, const int32_t* proj, int32_t out_height, int32_t out_width,
                          void* out, uint32_t* stats, void* workspace, size_t workspace_bytes, codon_stream_t stream);
 
+/* ---- outlier rejection of sensor depth maps (codon_amd.clean) ----------------------------------------------------
+ * Nothing in the reference: its inputs were cleaned offline, if at all.  A DEFINITION, in codon_amd/csrc/clean.hip and
+ * clean_tile.h, restated in numpy in tests/clean_ref.py, equal bits required.  Integers only.
+ *
+ * in, out: (batch, height, width) codes, u8 or u16, 0 a hole; every output code is the input code or 0.  tau(v) = tol_abs +
+ * ((tol_rel_q16 * v) >> 16), the product in unsigned 32 bits; two pixels are LINKED iff both are non-zero and their codes differ
+ * by at most tau of the smaller.  Rule 1, flying pixels: a valid pixel with fewer than min_support of its 8 neighbours inside
+ * the plane linked to it becomes 0; min_support 0 switches it off; it reads `in`, a single pass, not idempotent.  Rule 2,
+ * speckles: the connected components of what rule 1 left, under 4-connectivity, two 4-neighbours in one component iff linked; a
+ * component of fewer than min_region pixels becomes 0; min_region <= 1 switches it off.  counts: NULL, or (batch, 4) uint32 ON
+ * THE DEVICE: valid inputs, pixels removed by rule 1, pixels removed by rule 2, components removed by rule 2; it needs no
+ * initialisation.
+ *
+ * codon_clean_workspace_bytes: HOST ONLY -- the bytes the batch takes (a u32 label and a u32 size per pixel, each image rounded
+ * up to 16 bytes), 0 for a batch outside 1 .. 65535 or a height or width outside 1 .. 4096.  workspace: 16-byte aligned, private
+ * to the stream; initialised by the call itself, on the stream.  Two launches with rule 2 off, four with it on: they depend on
+ * (batch, height, width) and on that alone; the components are labelled by a lock-free union-find, 32-bit atomic minima on
+ * global memory, every loop of it with a trip limit; no host synchronisation.  Refused on the host, before any HIP call: null
+ * pointers (counts may be NULL), an fmt other than CODON_FILL_U8 / _U16, batch outside 1 .. 65535, a height or width outside
+ * 1 .. 4096, top outside 1 .. 65535 or not 255 for u8 codes, tol_abs outside 0 .. top, tol_rel_q16 outside 0 .. 65535,
+ * min_support outside 0 .. 8, min_region outside 0 .. 2^24, out == in, a u16 plane that is not 2-byte aligned, counts not 4-byte
+ * aligned, a workspace that is not 16-byte aligned or too small. */
+size_t codon_clean_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int codon_clean_depth(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top, int32_t tol_abs,
+                      int32_t tol_rel_q16, int32_t min_support, int32_t min_region, void* out, uint32_t* counts, void* workspace,
+                      size_t workspace_bytes, codon_stream_t stream);
+
 /* ---- undistortion of colour images (codon_amd.undistort) ---------------------------------------------------------
  * Nothing in the reference: its colour images were rectified offline.  A DEFINITION, in codon_amd/csrc/undistort.hip and
  * undistort_tile.h, restated in numpy in tests/undistort_ref.py, equal bits required.  Integers only.

@@ -1,6 +1,6 @@
 """Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
 into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
-guided_fill, jbu, register, undistort) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+guided_fill, jbu, register, clean, undistort) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
 address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
 restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
 
@@ -18,6 +18,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tests import clean_ref as K  # noqa: E402
 from tests import d4_ref as D  # noqa: E402
 from tests import eval_ref as E  # noqa: E402
 from tests import fill_ref as F  # noqa: E402
@@ -233,6 +234,25 @@ def register(run, p):
                    "in turn: no report, every output equals tests/register_ref.py")
 
 
+def clean(run, p):
+    """The GPU test's cases (clean_ref.cases): every shape under every pattern and parameter form, the formats in turn; the program
+    runs each in both thread orders, with and without statistics"""
+    cases = 0
+    for shape in K.SHAPES:
+        B, h, w = shape
+        for name, top, pattern, form in K.cases(shape):
+            codes = K.plane(shape, pattern, top)
+            codes.tofile(p("i"))
+            run(0 if top == 255 else 1, B, h, w, *K.params(shape, form, top, pattern), p("i"), p("o"), p("s"))
+            want, stats = K.want(shape, pattern, top, form)
+            got = np.fromfile(p("o"), dtype=codes.dtype).reshape(want.shape)
+            assert got.tobytes() == want.tobytes(), (shape, name, pattern, form)
+            assert np.fromfile(p("s"), dtype=np.uint32).tobytes() == stats.tobytes(), (shape, name, pattern, form, "statistics")
+            cases += 1
+    return cases, (f"over {len(K.SHAPES)} shapes x {len(K.PATTERNS)} patterns x {len(K.FORMS)} parameter forms, the {len(K.FORMATS)} "
+                   "formats in turn: no report, every output and count equals tests/clean_ref.py")
+
+
 def undistort(run, p):
     """The GPU test's cases (undistort_ref.cases): every shape under every rig and pattern, the images on a 16-byte boundary and
     one byte off it in turn; the tile table and the counts the program made with ud_tiles beside the output"""
@@ -262,6 +282,7 @@ CHECKS = {
     "guided_fill": (guided_fill, [], "cases"),
     "jbu": (jbu, [], "cases"),
     "register": (register, [], "cases"),
+    "clean": (clean, [], "cases"),
     "undistort": (undistort, [], "cases"),
 }
 
