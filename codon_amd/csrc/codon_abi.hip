@@ -13,6 +13,7 @@
 #include "pair.h"
 #include "register_tile.h"
 #include "clean_tile.h"
+#include "cloud_tile.h"
 #include "sensor_pixel.h"
 #include "stretch_tile.h"
 #include "train_record.h"
@@ -1205,6 +1206,42 @@ int codon_clean_depth(int32_t batch, int32_t height, int32_t width, const void* 
                 workspace_bytes, need);
   return clean_depth(batch, height, width, in, fmt, tol_abs, tol_rel_q16, min_support, min_region, out, counts, workspace,
                      (hipStream_t)stream);
+}
+
+// ---- depth maps as point clouds with normals -----------------------------------------------------------------------
+size_t codon_cloud_workspace_bytes(int32_t batch, int32_t height, int32_t width) { return cloud_workspace_bytes(batch, height, width); }
+
+int codon_cloud_points(int32_t batch, int32_t height, int32_t width, const void* codes, int32_t fmt, int32_t top, const int32_t* rx,
+                       const int32_t* ry, const int32_t* ray_span, double m, int32_t normals, int32_t radius, int32_t tol_abs,
+                       int32_t tol_rel_q16, const uint8_t* color, int32_t color_channels, uint8_t* body, uint32_t* counts,
+                       uint8_t* normal_map, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
+  CODON_REQUIRE(codes && rx && ry && ray_span && body && counts && workspace, CODON_ERR_BAD_ARG, "cloud_points: null pointer");
+  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "cloud_points: fmt %d (0: u8 codes, 1: u16 codes)", fmt);
+  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "cloud_points: batch %d (1..65535)", batch);
+  CODON_REQUIRE(height >= 1 && height <= CD_MAX_SIDE && width >= 1 && width <= CD_MAX_SIDE, CODON_ERR_BAD_ARG,
+                "cloud_points: a %dx%d plane (1..%d each way)", height, width, CD_MAX_SIDE);
+  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
+                "cloud_points: top %d (255 for u8 codes, 1..65535 otherwise)", top);
+  CODON_REQUIRE(normals == 0 || normals == 1, CODON_ERR_BAD_ARG, "cloud_points: normals %d (0 or 1)", normals);
+  CODON_REQUIRE(radius >= 1 && radius <= CD_MAX_RADIUS, CODON_ERR_BAD_ARG, "cloud_points: radius %d (1..%d)", radius, CD_MAX_RADIUS);
+  CODON_REQUIRE(tol_abs >= 0 && tol_abs <= top, CODON_ERR_BAD_ARG, "cloud_points: tolerance %d (codes, 0..top = %d)", tol_abs, top);
+  CODON_REQUIRE(tol_rel_q16 >= 0 && tol_rel_q16 <= CD_MAX_REL, CODON_ERR_BAD_ARG, "cloud_points: tolerance_rel %d (Q16, 0..%d)",
+                tol_rel_q16, CD_MAX_REL);
+  for (int q = 0; q < 4; ++q)
+    CODON_REQUIRE(ray_span[q] > -CD_RAY_LIMIT && ray_span[q] < CD_RAY_LIMIT, CODON_ERR_BAD_ARG,
+                  "cloud_points: ray %d of the span is %d (Q20, below 2^22 in magnitude)", q, ray_span[q]);
+  CODON_REQUIRE(m > 0.0 && isfinite(m), CODON_ERR_BAD_ARG, "cloud_points: m %g (metres per Q20 code: positive and finite)", m);
+  CODON_REQUIRE(color ? color_channels == 1 || color_channels == 3 : color_channels == 0, CODON_ERR_BAD_ARG,
+                "cloud_points: color_channels %d (1: grey, 3: RGB; 0 without colour)", color_channels);
+  CODON_REQUIRE(!normal_map || normals, CODON_ERR_BAD_ARG, "cloud_points: a normal map without normals");
+  const bool planes_ok = ((uintptr_t)codes & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
+  const bool words_ok = (((uintptr_t)rx | (uintptr_t)ry | (uintptr_t)counts) & 3) == 0 && ((uintptr_t)workspace & 15) == 0;
+  CODON_REQUIRE(planes_ok && words_ok, CODON_ERR_BAD_ARG, "cloud_points: unaligned plane, table, counts or workspace");
+  const size_t need = cloud_workspace_bytes(batch, height, width);
+  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "cloud_points: a workspace of %zu bytes is too small (%zu needed)",
+                workspace_bytes, need);
+  return cloud_points(batch, height, width, codes, fmt, rx, ry, m, normals ? radius : 0, tol_abs, tol_rel_q16, color, color_channels,
+                      body, counts, normal_map, workspace, (hipStream_t)stream);
 }
 
 // ---- undistortion of colour images ---------------------------------------------------------------------------------

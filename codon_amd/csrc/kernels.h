@@ -188,6 +188,13 @@ size_t clean_workspace_bytes(int B, int h, int w);
 int clean_depth(int B, int h, int w, const void* in, int fmt, int tol_abs, int tol_rel_q16, int min_support, int min_region, void* out,
                 void* stats, void* workspace, hipStream_t stream);
 
+// cloud.hip; rx (w), ry (h): int32 on the device; radius 0: records without normals; color: null, or (B, h, w, channels) u8; body:
+// (B, h w rec) bytes; counts: (B, 2) u32; nmap: null or (B, h, w, 3) u8; workspace: a u32 per 1024 pixels of every image
+size_t cloud_workspace_bytes(int B, int h, int w);
+int cloud_points(int B, int h, int w, const void* in, int fmt, const int* rx, const int* ry, double m, int radius, int tol_abs,
+                 int tol_rel_q16, const void* color, int channels, void* body, void* counts, void* nmap, void* workspace,
+                 hipStream_t stream);
+
 // undistort.hip; in: (B, hs, ws, channels) u8, out: (B, ho, wo, channels) u8; map (ho, wo, 2) int32, tiles (the words of
 // undistort_tiles_bytes) and weights (32, 4) int16 on the device.  undistort_plan: HOST -- the tile table and the four counts of a
 // host copy of the map; -1, or the index of the first entry it refuses

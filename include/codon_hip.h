@@ -986,6 +986,38 @@ int codon_clean_depth(int32_t batch, int32_t height, int32_t width, const void* 
                       int32_t tol_rel_q16, int32_t min_support, int32_t min_region, void* out, uint32_t* counts, void* workspace,
                       size_t workspace_bytes, codon_stream_t stream);
 
+/* ---- depth maps as point clouds with normals (codon_amd.cloud) ---------------------------------------------------
+ * Nothing in the reference: it stops at the depth map.  A DEFINITION, in codon_amd/csrc/cloud.hip and cloud_tile.h, restated in
+ * numpy in tests/cloud_ref.py, equal bytes required.
+ *
+ * codes: (batch, height, width) codes, u8 or u16, 0 a hole.  rx (width), ry (height): int32 ON THE DEVICE, the Q20 rays
+ * rint(2^20 (j - cx) / fx) and rint(2^20 (i - cy) / fy) of a pinhole camera without distortion; ray_span: ON THE HOST, their four
+ * ends rx[0], rx[width - 1], ry[0], ry[height - 1] -- the tables are monotone, so the ends bound them, and the device tables are
+ * trusted to be the ones the span describes.  A valid pixel (i, j) with code k has P = (k rx[j], k ry[i], k << 20); its record
+ * holds float32(float64(P_c) m) for c = x, y, z (x right, y down, z forward; m = metres per code / 2^20); with normals three more
+ * floats N_c 2^-14 of the integer normal of cloud_tile.h (tangents between the pixels `radius` steps away that are linked to k
+ * under tol_abs radius + ((tol_rel_q16 min) >> 16), facing the camera, three zeros where there is none); with colour (color:
+ * (batch, height, width) u8 for color_channels 1, (batch, height, width, 3) for 3) three more bytes r g b.  Records are 12, 24, 15
+ * or 27 bytes, packed, in row-major order of the pixels: image b's start at byte b height width rec of body, which needs no
+ * alignment.  counts: (batch, 2) uint32 ON THE DEVICE: records, records with a normal; it needs no initialisation.  normal_map:
+ * NULL, or (batch, height, width, 3) u8: 128 + ((127 N_c + 8192) >> 14), and 0 0 0 for a hole or no normal.
+ *
+ * codon_cloud_workspace_bytes: HOST ONLY -- the bytes the batch takes (a u32 per 1024 pixels, each image rounded up to 16 bytes),
+ * 0 for a batch outside 1 .. 65535 or a height or width outside 1 .. 4096.  workspace: 16-byte aligned, private to the stream;
+ * initialised by the call itself, on the stream.  Three launches (count, scan, emit), which depend on (batch, height, width) and
+ * the record form alone; no atomic decides a position, no workgroup waits for another; no host synchronisation.  Refused on the
+ * host, before any HIP call: null pointers (color and normal_map may be NULL), an fmt other than CODON_FILL_U8 / _U16, batch
+ * outside 1 .. 65535, a height or width outside 1 .. 4096, top outside 1 .. 65535 or not 255 for u8 codes, normals other than 0
+ * or 1, radius outside 1 .. 8, tol_abs outside 0 .. top, tol_rel_q16 outside 0 .. 65535, a ray of the span of 2^22 or more in
+ * magnitude, m not positive or not finite, color_channels other than 1 or 3 with colour or 0 without, a normal map without
+ * normals, a u16 plane that is not 2-byte aligned, tables or counts not 4-byte aligned, a workspace that is not 16-byte aligned
+ * or too small. */
+size_t codon_cloud_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int codon_cloud_points(int32_t batch, int32_t height, int32_t width, const void* codes, int32_t fmt, int32_t top, const int32_t* rx,
+                       const int32_t* ry, const int32_t* ray_span, double m, int32_t normals, int32_t radius, int32_t tol_abs,
+                       int32_t tol_rel_q16, const uint8_t* color, int32_t color_channels, uint8_t* body, uint32_t* counts,
+                       uint8_t* normal_map, void* workspace, size_t workspace_bytes, codon_stream_t stream);
+
 /* ---- undistortion of colour images (codon_amd.undistort) ---------------------------------------------------------
  * Nothing in the reference: its colour images were rectified offline.  A DEFINITION, in codon_amd/csrc/undistort.hip and
  * undistort_tile.h, restated in numpy in tests/undistort_ref.py, equal bits required.  Integers only.

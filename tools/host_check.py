@@ -1,6 +1,6 @@
 """Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
 into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
-guided_fill, jbu, register, clean, undistort) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+guided_fill, jbu, register, clean, undistort, cloud) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
 address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
 restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
 
@@ -19,6 +19,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tests import clean_ref as K  # noqa: E402
+from tests import cloud_ref as Q  # noqa: E402
 from tests import d4_ref as D  # noqa: E402
 from tests import eval_ref as E  # noqa: E402
 from tests import fill_ref as F  # noqa: E402
@@ -272,6 +273,36 @@ def undistort(run, p):
                    "table and count equals tests/undistort_ref.py")
 
 
+def cloud(run, p):
+    """The GPU test's cases (cloud_ref.cases): every shape under every pattern and record form; the program runs each in both
+    thread orders, with the body and the normal map one byte into their buffers"""
+    cases = 0
+    for shape in Q.SHAPES:
+        B, h, w = shape
+        rx, ry = Q.tables(shape)
+        rx.tofile(p("x")), ry.tofile(p("y"))
+        for pattern, form in Q.cases(shape):
+            top = Q.top_of(pattern)
+            normals, channels, radius, A, Rq, nmap = Q.params(form, top)
+            codes = Q.plane(shape, pattern)
+            codes.tofile(p("i"))
+            if channels:
+                Q.tint(shape, channels).tofile(p("c"))
+            run(0 if top == 255 else 1, B, h, w, int(normals), channels, radius, A, Rq, repr(Q.DEFAULTS["depth_unit"] / (1 << 20)),
+                int(nmap), p("i"), p("x"), p("y"), p("c"), p("b"), p("n"), p("m"))
+            bodies, counts, maps, rec = Q.want(shape, pattern, form)
+            got = np.fromfile(p("b"), dtype=np.uint8).reshape(B, h * w * rec)
+            for b, body in enumerate(bodies):
+                assert got[b, :len(body)].tobytes() == body, (shape, pattern, form, b)
+                assert (got[b, len(body):] == 0xEE).all(), (shape, pattern, form, b, "bytes behind the records")
+            assert np.fromfile(p("n"), dtype=np.uint32).tobytes() == counts.tobytes(), (shape, pattern, form, "counts")
+            if nmap:
+                assert np.fromfile(p("m"), dtype=np.uint8).tobytes() == maps.tobytes(), (shape, pattern, form, "normal map")
+            cases += 1
+    return cases, (f"over {len(Q.SHAPES)} shapes, {len(Q.PATTERNS)} patterns x {len(Q.FORMS)} record forms ({len(Q.BIG_CASES)} of them on "
+                   "the largest): no report, every byte and count equals tests/cloud_ref.py")
+
+
 # name -> (check, extra compile flags, what the count counts)
 CHECKS = {
     "d4": (d4, ["-ffp-contract=off"], "runs"),
@@ -284,6 +315,7 @@ CHECKS = {
     "register": (register, [], "cases"),
     "clean": (clean, [], "cases"),
     "undistort": (undistort, [], "cases"),
+    "cloud": (cloud, [], "cases"),
 }
 
 
