@@ -18,37 +18,19 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import math
 import os
 
 import numpy as np
 import torch
 
 from . import _lib as L
-from . import io, ops
-from .upsample import _code_planes, _workspace
+from . import codes as K
+from . import ops
+from .codes import integer, rel_q16
 
 MAX_SUPPORT, MAX_REGION, MAX_REL_Q16 = 8, 1 << 24, 65535
 STATS = ("valid", "flying", "speckle", "regions")
 DEFAULTS = dict(tolerance=2, tolerance_rel=0.02, min_support=3, min_region=16)
-
-
-def _integer(who: str, name: str, v, lo: int, hi: int, what: str) -> int:
-    if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not lo <= v <= hi:
-        raise ValueError(f"{who}: {name} {v!r} ({what})")
-    return int(v)
-
-
-def rel_q16(who: str, rel) -> int:
-    """Rq = rint(65536 rel) of a relative tolerance in [0, 1), at most 65535"""
-    try:
-        r = float(rel)
-    except (TypeError, ValueError):
-        r = float("nan")
-    q = int(np.rint(65536.0 * r)) if math.isfinite(r) else -1
-    if isinstance(rel, bool) or not (0.0 <= r < 1.0) or q > MAX_REL_Q16:
-        raise ValueError(f"{who}: tolerance_rel {rel!r} (a number in [0, 1), at most 65535 / 65536)")
-    return q
 
 
 class Cleaner:
@@ -57,11 +39,11 @@ class Cleaner:
 
     def __init__(self, tolerance: int = 2, tolerance_rel: float = 0.02, min_support: int = 3, min_region: int = 16):
         who = "Cleaner"
-        self.tolerance = _integer(who, "tolerance", tolerance, 0, 65535, "an integer number of codes, 0 .. the largest code")
+        self.tolerance = integer(who, "tolerance", tolerance, 0, 65535, "an integer number of codes, 0 .. the largest code")
         self.tolerance_rel = tolerance_rel
         self.tolerance_rel_q16 = rel_q16(who, tolerance_rel)
-        self.min_support = _integer(who, "min_support", min_support, 0, MAX_SUPPORT, f"an integer in 0..{MAX_SUPPORT}")
-        self.min_region = _integer(who, "min_region", min_region, 0, MAX_REGION, f"an integer in 0..{MAX_REGION}")
+        self.min_support = integer(who, "min_support", min_support, 0, MAX_SUPPORT, f"an integer in 0..{MAX_SUPPORT}")
+        self.min_region = integer(who, "min_region", min_region, 0, MAX_REGION, f"an integer in 0..{MAX_REGION}")
 
     def __call__(self, codes: torch.Tensor, depth_max: int = None, stats: bool = False):
         """codes: (h, w) or (B, h, w) uint8 codes, or u16 codes as int16 / uint16 (read as unsigned), 0 a hole, on a GPU -> codes
@@ -69,16 +51,15 @@ class Cleaner:
         int32 (B, 4) on the device: valid inputs, pixels removed by rule 1, pixels removed by rule 2, components removed by
         rule 2).  Two launches with rule 2 off, four with it on; no host synchronisation."""
         who = "clean_depth"
-        src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
-        if self.tolerance > top:
-            raise ValueError(f"{who}: tolerance {self.tolerance} above the largest code {top}")
-        dev = ops._dev(src)
-        out = torch.empty_like(src)
-        counts = torch.empty((B, 4), dtype=torch.int32, device=dev) if stats else None
+        p = K.code_planes(who, codes, depth_max)
+        if self.tolerance > p.top:
+            raise ValueError(f"{who}: tolerance {self.tolerance} above the largest code {p.top}")
+        dev, out = p.dev, p.out()
+        counts = torch.empty((p.B, 4), dtype=torch.int32, device=dev) if stats else None
         P_ = C.c_void_p
-        with torch.cuda.device(dev):
-            ws = _workspace(who, "codon_clean_workspace_bytes", dev, B, h, w, batched=True)
-            L.check(L.load().codon_clean_depth(B, h, w, P_(src.data_ptr()), L.FILL_U8 if bits == 8 else L.FILL_U16, top, self.tolerance,
+        with ops._on(dev):
+            ws = K.workspace(who, "codon_clean_workspace_bytes", dev, p.B, p.h, p.w, batched=True)
+            L.check(L.load().codon_clean_depth(p.B, p.h, p.w, p.ptr, p.fmt, p.top, self.tolerance,
                                                self.tolerance_rel_q16, self.min_support, self.min_region, P_(out.data_ptr()),
                                                P_(counts.data_ptr()) if stats else None, P_(ws.data_ptr()), ws.numel(),
                                                ops._stream(dev)), who)
@@ -113,21 +94,16 @@ def parse_args(argv=None):
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--depth", required=True, metavar="DIR", help="the sensor's depth maps, in the depth camera's own frame")
     ap.add_argument("--out", required=True, metavar="DIR", help="where the cleaned maps go, under the same file names")
-    ap.add_argument("--depth-bits", type=int, default=8, choices=(8, 16))
-    ap.add_argument("--depth-max", type=int, default=None, metavar="N", help="the largest code of a 16-bit data set (default 65535)")
+    K.add_depth_args(ap)
     add_arguments(ap)
     ap.add_argument("--stats", action="store_true", help="print valid=, flying=, speckle= and regions= per file")
     a = ap.parse_args(argv)
-    if a.depth_max is not None and a.depth_bits != 16:
-        ap.error("--depth-max needs --depth-bits 16")
-    if a.depth_max is not None and not 1 <= a.depth_max <= 65535:
-        ap.error(f"--depth-max {a.depth_max} must be in [1, 65535]")
+    a.top = K.depth_args_of(ap, a)
     if os.path.abspath(a.out) == os.path.abspath(a.depth):
         ap.error("--out is --depth: the cleaned maps would overwrite the sensor's")
     cleaner = cleaner_of(a, ap)
-    top = 255 if a.depth_bits == 8 else 65535 if a.depth_max is None else a.depth_max
-    if cleaner.tolerance > top:
-        ap.error(f"--tolerance {cleaner.tolerance} is above the largest code {top}")
+    if cleaner.tolerance > a.top:
+        ap.error(f"--tolerance {cleaner.tolerance} is above the largest code {a.top}")
     return a, ap, cleaner
 
 
@@ -138,22 +114,13 @@ def stats_line(counts) -> str:
 
 def main(argv=None, emit=print):
     a, ap, cleaner = parse_args(argv)
-    if not os.path.isdir(a.depth):
-        ap.error(f"--depth {a.depth} is not a directory")
-    if not torch.cuda.is_available():
-        raise SystemExit("No GPU found: codon_amd has no CPU fallback")
-    depth_max = 65535 if a.depth_max is None else a.depth_max
-    dev = torch.device("cuda:0")
+    K.require_dir(ap, "depth", a.depth)
+    dev = K.require_gpu()
     os.makedirs(a.out, exist_ok=True)
-    for name in sorted(os.listdir(a.depth)):
-        plane = io.read_depth_plane(os.path.join(a.depth, name), a.depth_bits, depth_max)
-        codes = torch.from_numpy((plane.view(np.int16) if plane.dtype == np.uint16 else plane).copy()).to(dev)
-        got = cleaner(codes, depth_max if a.depth_bits == 16 else None, stats=a.stats)
+    for name, codes in K.depth_files(a.depth, a.depth_bits, a.top, dev):
+        got = cleaner(codes, a.depth_max, stats=a.stats)
         out, counts = got if a.stats else (got, None)
-        if a.depth_bits == 16:
-            io.write_depth16(os.path.join(a.out, name), out.cpu().numpy().view(np.uint16))
-        else:
-            io.write_gray(os.path.join(a.out, name), out.cpu().numpy())
+        K.write_codes(os.path.join(a.out, name), out)
         emit(f"{name} {stats_line(counts.cpu().numpy()[0])}" if a.stats else name)
     return 0
 

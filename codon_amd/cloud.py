@@ -23,17 +23,16 @@ import argparse
 import collections
 import ctypes as C
 import dataclasses
-import math
 import os
 
 import numpy as np
 import torch
 
 from . import _lib as L
-from . import io, ops
-from .clean import _integer, rel_q16
+from . import codes as K
+from . import ops
+from .codes import integer, rel_q16
 from .register import A_LIMIT, SCALES, Calibration, Camera
-from .upsample import _code_planes, _workspace
 
 MAX_RADIUS = 8
 DEFAULTS = dict(depth_unit=0.001, radius=2, tolerance=2, tolerance_rel=0.02)
@@ -89,8 +88,7 @@ def record_dtype(normals: bool, color: bool) -> np.dtype:
 
 def ply_header(count: int, normals: bool, color: bool) -> bytes:
     """The fixed header of `count` packed records"""
-    if not isinstance(count, (int, np.integer)) or isinstance(count, bool) or count < 0:
-        raise ValueError(f"ply_header: count {count!r} (an integer, 0 or more)")
+    integer("ply_header", "count", count, 0, None, "an integer, 0 or more")
     lines = ["ply", "format binary_little_endian 1.0", FRAME, f"element vertex {int(count)}"]
     lines += [f"property float {n}" for n in "xyz"]
     if normals:
@@ -151,16 +149,11 @@ class Unprojection:
                              "(python -m codon_amd.undistort --calib-out ...)")
         if scale not in SCALES:
             raise ValueError(f"{who}: scale {scale!r} (1, 4, 8 or 16)")
-        try:
-            u = float(depth_unit)
-        except (TypeError, ValueError):
-            u = float("nan")
-        if isinstance(depth_unit, bool) or not (u > 0.0 and math.isfinite(u)):
-            raise ValueError(f"{who}: depth_unit {depth_unit!r} (a positive number of metres per code)")
+        u = K.positive(who, "depth_unit", depth_unit, "a positive number of metres per code", allow_bool=False)
         self.camera = scaled_camera(camera, scale)
         self.scale, self.depth_unit, self.normals = scale, u, bool(normals)
-        self.radius = _integer(who, "radius", radius, 1, MAX_RADIUS, f"an integer in 1..{MAX_RADIUS}")
-        self.tolerance = _integer(who, "tolerance", tolerance, 0, 65535, "an integer number of codes, 0 .. the largest code")
+        self.radius = integer(who, "radius", radius, 1, MAX_RADIUS, f"an integer in 1..{MAX_RADIUS}")
+        self.tolerance = integer(who, "tolerance", tolerance, 0, 65535, "an integer number of codes, 0 .. the largest code")
         self.tolerance_rel = tolerance_rel
         self.tolerance_rel_q16 = rel_q16(who, tolerance_rel)
         self.m = u / float(1 << 20)
@@ -174,7 +167,8 @@ class Unprojection:
         object's device; color: None, or uint8 (B, h, w) grey or (B, h, w, 3) RGB of the same planes (the batch axis as in
         codes) -> Cloud.  Image b's records are body[b, :counts[b, 0] * rec].  Three launches; no host synchronisation."""
         who = "cloud_points"
-        src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
+        p = K.code_planes(who, codes, depth_max)
+        src, B, h, w, top = p.src, p.B, p.h, p.w, p.top
         cam = self.camera
         if (h, w) != (cam.height, cam.width):
             raise ValueError(f"{who}: a {h}x{w} plane, and the camera is {cam.height}x{cam.width}"
@@ -183,7 +177,7 @@ class Unprojection:
             raise ValueError(f"{who}: tolerance {self.tolerance} above the largest code {top}")
         if normal_map and not self.normals:
             raise ValueError(f"{who}: a normal map without normals")
-        dev = ops._dev(src)
+        dev = p.dev
         if dev != self.rx.device:
             raise RuntimeError(f"{who}: codes on {dev}, the tables on {self.rx.device}")
         channels = 0
@@ -201,9 +195,9 @@ class Unprojection:
         counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
         nmap = torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev) if normal_map else None
         P_ = C.c_void_p
-        with torch.cuda.device(dev):
-            ws = _workspace(who, "codon_cloud_workspace_bytes", dev, B, h, w, batched=True)
-            L.check(L.load().codon_cloud_points(B, h, w, P_(src.data_ptr()), L.FILL_U8 if bits == 8 else L.FILL_U16, top,
+        with ops._on(dev):
+            ws = K.workspace(who, "codon_cloud_workspace_bytes", dev, B, h, w, batched=True)
+            L.check(L.load().codon_cloud_points(B, h, w, p.ptr, p.fmt, top,
                                                 P_(self.rx.data_ptr()), P_(self.ry.data_ptr()), self._span, self.m, int(self.normals),
                                                 self.radius, self.tolerance, self.tolerance_rel_q16,
                                                 P_(color.data_ptr()) if channels else None, channels, P_(body.data_ptr()),
@@ -225,9 +219,7 @@ def parse_args(argv=None):
     ap.add_argument("--camera", default="color", choices=("color", "depth"),
                     help="color: a map register, infer or a label is on (default); depth: a sensor's own z-depth file")
     ap.add_argument("--scale", type=int, default=1, choices=SCALES, help="the maps are on the camera's grid over S (register --scale S)")
-    ap.add_argument("--depth-bits", type=int, default=8, choices=(8, 16))
-    ap.add_argument("--depth-max", type=int, default=None, metavar="N", help="the largest code of a 16-bit data set (default 65535)")
-    ap.add_argument("--depth-unit", type=float, default=DEFAULTS["depth_unit"], metavar="M", help="metres per code (default 0.001)")
+    K.add_depth_args(ap, depth_unit=DEFAULTS["depth_unit"])
     ap.add_argument("--no-normals", action="store_true", help="positions (and colours) alone")
     ap.add_argument("--normal-radius", type=int, default=DEFAULTS["radius"], metavar="R",
                     help="a tangent spans the pixels R steps away, 1..8 (default 2, untuned)")
@@ -238,12 +230,7 @@ def parse_args(argv=None):
     ap.add_argument("--normal-maps", default=None, metavar="DIR", help="write the normals as RGB PNGs under the files' own names")
     ap.add_argument("--stats", action="store_true", help="print points= and normals= per file")
     a = ap.parse_args(argv)
-    if a.depth_max is not None and a.depth_bits != 16:
-        ap.error("--depth-max needs --depth-bits 16")
-    if a.depth_max is not None and not 1 <= a.depth_max <= 65535:
-        ap.error(f"--depth-max {a.depth_max} must be in [1, 65535]")
-    if not (a.depth_unit > 0.0 and math.isfinite(a.depth_unit)):
-        ap.error(f"--depth-unit {a.depth_unit} must be positive")
+    a.top = K.depth_args_of(ap, a)
     if a.color is not None and a.scale != 1:
         ap.error(f"--color with --scale {a.scale}: the colour images are on the full grid; unproject a map at scale 1")
     if a.no_normals:
@@ -254,9 +241,8 @@ def parse_args(argv=None):
                 ap.error(f"--normal-{name.replace('_', '-')} with --no-normals")
     if not 1 <= a.normal_radius <= MAX_RADIUS:
         ap.error(f"--normal-radius {a.normal_radius} must be in [1, {MAX_RADIUS}]")
-    top = 255 if a.depth_bits == 8 else 65535 if a.depth_max is None else a.depth_max
-    if not 0 <= a.normal_tolerance <= top:
-        ap.error(f"--normal-tolerance {a.normal_tolerance} must be in [0, {top}], the largest code")
+    if not 0 <= a.normal_tolerance <= a.top:
+        ap.error(f"--normal-tolerance {a.normal_tolerance} must be in [0, {a.top}], the largest code")
     try:
         rel_q16("cloud", a.normal_tolerance_rel)
     except ValueError:
@@ -288,18 +274,15 @@ def main(argv=None, emit=print):
         cal = Calibration.from_json(a.calib)
     except (OSError, ValueError) as e:
         ap.error(f"--calib {a.calib}: {e}")
-    if not os.path.isdir(a.depth):
-        ap.error(f"--depth {a.depth} is not a directory")
-    if a.color is not None and not os.path.isdir(a.color):
-        ap.error(f"--color {a.color} is not a directory")
+    K.require_dir(ap, "depth", a.depth)
+    if a.color is not None:
+        K.require_dir(ap, "color", a.color)
     cam = cal.color if a.camera == "color" else cal.depth
     if any(cam.dist):
         hint = (": undistort the colour images first (python -m codon_amd.undistort --calib-out ...)" if a.camera == "color"
                 else ": register the maps to the colour camera first (python -m codon_amd.register)")
         ap.error(f"--calib {a.calib}: {a.camera}.dist {cam.dist!r} is not zero{hint}")
-    if not torch.cuda.is_available():
-        raise SystemExit("No GPU found: codon_amd has no CPU fallback")
-    depth_max = 65535 if a.depth_max is None else a.depth_max
+    K.require_gpu()
     try:
         un = Unprojection(cam, a.scale, a.depth_unit, not a.no_normals, a.normal_radius, a.normal_tolerance, a.normal_tolerance_rel)
     except ValueError as e:
@@ -307,16 +290,14 @@ def main(argv=None, emit=print):
     for d in (a.out, a.normal_maps):
         if d is not None:
             os.makedirs(d, exist_ok=True)
-    for name in sorted(os.listdir(a.depth)):
-        plane = io.read_depth_plane(os.path.join(a.depth, name), a.depth_bits, depth_max)
-        codes = torch.from_numpy((plane.view(np.int16) if plane.dtype == np.uint16 else plane).copy()).to(un.device)
+    for name, codes in K.depth_files(a.depth, a.depth_bits, a.top, un.device):
         color = None
         if a.color is not None:
             path = os.path.join(a.color, name)
             if not os.path.exists(path):
                 raise ValueError(f"{path}: no colour image for {os.path.join(a.depth, name)}")
-            color = torch.from_numpy(_read_color(path, *plane.shape)).to(un.device)
-        got = un(codes, color, depth_max if a.depth_bits == 16 else None, normal_map=a.normal_maps is not None)
+            color = torch.from_numpy(_read_color(path, *codes.shape)).to(un.device)
+        got = un(codes, color, a.depth_max, normal_map=a.normal_maps is not None)
         points, normals = (int(v) for v in got.counts.cpu().numpy().view(np.uint32)[0])      # the one host synchronisation
         body = got.body[0, :points * got.rec].cpu().numpy()
         write_ply(os.path.join(a.out, os.path.splitext(name)[0] + ".ply"), body, points, un.normals, color is not None)

@@ -84,6 +84,90 @@ static int check_crop_desc(const char* name, const codon_crop_desc* desc, int64_
   return CODON_OK;
 }
 
+// ---- the checks the code-plane entries share: `who` is the entry's name in the message.  An entry calls them in
+// the order its refusals are documented in -- of two broken rules the first is reported -- so each is one rule, and
+// check_planes is the run of four that most entries have unbroken.
+static int check_fmt(const char* who, int fmt) {
+  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "%s: fmt %d (0: u8 codes, 1: u16 codes)", who, fmt);
+  return CODON_OK;
+}
+
+static int check_batch(const char* who, int batch) {
+  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "%s: batch %d (1..65535)", who, batch);
+  return CODON_OK;
+}
+
+// noun: what the message calls the plane ("plane", "source", "target")
+static int check_side(const char* who, int height, int width, const char* noun, int limit) {
+  CODON_REQUIRE(height >= 1 && height <= limit && width >= 1 && width <= limit, CODON_ERR_BAD_ARG, "%s: a %dx%d %s (1..%d each way)",
+                who, height, width, noun, limit);
+  return CODON_OK;
+}
+
+static int check_top(const char* who, int fmt, int top) {
+  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
+                "%s: top %d (255 for u8 codes, 1..65535 otherwise)", who, top);
+  return CODON_OK;
+}
+
+// format (codes only), batch, a "plane" of at most `limit` each way, top
+static int check_planes(const char* who, int fmt, int batch, int height, int width, int limit, int top) {
+  if (const int st = check_fmt(who, fmt)) return st;
+  if (const int st = check_batch(who, batch)) return st;
+  if (const int st = check_side(who, height, width, "plane", limit)) return st;
+  return check_top(who, fmt, top);
+}
+
+// the strided guidance image of the guided filler and of the joint bilateral upsampler, and the scale it is at
+static int check_guide(const char* who, int batch, int height, int width, int scale, int64_t row_bytes, int64_t image_bytes) {
+  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_BAD_ARG, "%s: scale %d (4, 8 or 16)", who, scale);
+  CODON_REQUIRE(row_bytes >= (int64_t)width * scale, CODON_ERR_BAD_ARG,
+                "%s: guide rows of %lld bytes (at least %lld: width times scale)", who, (long long)row_bytes, (long long)width * scale);
+  CODON_REQUIRE(batch == 1 || image_bytes >= (int64_t)height * scale * row_bytes, CODON_ERR_BAD_ARG,
+                "%s: guide images %lld bytes apart (at least %lld: height times scale rows)", who, (long long)image_bytes,
+                (long long)height * scale * row_bytes);
+  return CODON_OK;
+}
+
+// the link rule's two tolerances (clean_tile.h, cloud_tile.h): codes up to top, and a Q16 fraction up to max_rel
+static int check_link_tolerances(const char* who, int tol_abs, int top, int tol_rel_q16, int max_rel) {
+  CODON_REQUIRE(tol_abs >= 0 && tol_abs <= top, CODON_ERR_BAD_ARG, "%s: tolerance %d (codes, 0..top = %d)", who, tol_abs, top);
+  CODON_REQUIRE(tol_rel_q16 >= 0 && tol_rel_q16 <= max_rel, CODON_ERR_BAD_ARG, "%s: tolerance_rel %d (Q16, 0..%d)", who, tol_rel_q16,
+                max_rel);
+  return CODON_OK;
+}
+
+// in_name: what the message calls the input ("in", "codes")
+static int check_not_same(const char* who, const void* in, const void* out, const char* in_name = "in") {
+  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "%s: %s and out are the same buffer", who, in_name);
+  return CODON_OK;
+}
+
+static int check_workspace(const char* who, size_t workspace_bytes, size_t need) {
+  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "%s: a workspace of %zu bytes is too small (%zu needed)", who,
+                workspace_bytes, need);
+  return CODON_OK;
+}
+
+static int check_code_bits(const char* who, int code_bits) {
+  CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "%s: code_bits %d (8 or 16)", who, code_bits);
+  return CODON_OK;
+}
+
+// the low-resolution code planes of the lr_codes_* entries and their output at `scale`: grid, shape, alignment
+static int check_lr_codes(const char* who, int batch, int lr_height, int lr_width, int scale, const void* codes, int code_bits,
+                          int depth_max, const void* out) {
+  if (const int st = check_code_bits(who, code_bits)) return st;
+  CODON_REQUIRE(code_bits == 16 ? (depth_max >= 1 && depth_max <= 65535) : depth_max == 255, CODON_ERR_BAD_ARG,
+                "%s: depth_max %d (255 for 8-bit codes, 1..65535 for 16-bit codes)", who, depth_max);
+  CODON_REQUIRE(lr_height >= 1 && lr_width >= 1 && lr_height <= 65536 && lr_width <= 65536 &&
+                    shape_ok(batch, lr_height * scale, lr_width * scale),
+                CODON_ERR_BAD_ARG, "%s: bad shape", who);
+  CODON_REQUIRE(((uintptr_t)out & 15) == 0 && (code_bits == 8 || ((uintptr_t)codes & 1) == 0), CODON_ERR_BAD_ARG,
+                "%s: out must be 16-byte aligned and u16 codes 2-byte aligned", who);
+  return CODON_OK;
+}
+
 }  // namespace codon
 
 using namespace codon;
@@ -903,14 +987,7 @@ int codon_lr_codes_to_input(int32_t batch, int32_t lr_height, int32_t lr_width, 
   CODON_REQUIRE(codes && lut && phase_weights && out, CODON_ERR_BAD_ARG, "lr_codes_to_input: null pointer");
   CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "lr_codes_to_input: scale %d", scale);
   CODON_REQUIRE(dtype_known(dtype), CODON_ERR_UNSUPPORTED, "lr_codes_to_input: dtype %d (fp32, fp16 or bf16)", dtype);
-  CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "lr_codes_to_input: code_bits %d (8 or 16)", code_bits);
-  CODON_REQUIRE(code_bits == 16 ? (depth_max >= 1 && depth_max <= 65535) : depth_max == 255, CODON_ERR_BAD_ARG,
-                "lr_codes_to_input: depth_max %d (255 for 8-bit codes, 1..65535 for 16-bit codes)", depth_max);
-  CODON_REQUIRE(lr_height >= 1 && lr_width >= 1 && lr_height <= 65536 && lr_width <= 65536 &&
-                    shape_ok(batch, lr_height * scale, lr_width * scale),
-                CODON_ERR_BAD_ARG, "lr_codes_to_input: bad shape");
-  CODON_REQUIRE(((uintptr_t)out & 15) == 0 && (code_bits == 8 || ((uintptr_t)codes & 1) == 0), CODON_ERR_BAD_ARG,
-                "lr_codes_to_input: out must be 16-byte aligned and u16 codes 2-byte aligned");
+  if (const int st = check_lr_codes("lr_codes_to_input", batch, lr_height, lr_width, scale, codes, code_bits, depth_max, out)) return st;
   return lr_codes_to_input(batch, lr_height, lr_width, scale, codes, code_bits, lut, depth_max, phase_weights, out, dtype,
                            (hipStream_t)stream);
 }
@@ -920,15 +997,8 @@ int codon_lr_codes_upsample(int32_t batch, int32_t lr_height, int32_t lr_width, 
                             codon_stream_t stream) {
   CODON_REQUIRE(codes && lut && phase_weights && out, CODON_ERR_BAD_ARG, "lr_codes_upsample: null pointer");
   CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_UNSUPPORTED, "lr_codes_upsample: scale %d", scale);
-  CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "lr_codes_upsample: code_bits %d (8 or 16)", code_bits);
-  CODON_REQUIRE(code_bits == 16 ? (depth_max >= 1 && depth_max <= 65535) : depth_max == 255, CODON_ERR_BAD_ARG,
-                "lr_codes_upsample: depth_max %d (255 for 8-bit codes, 1..65535 for 16-bit codes)", depth_max);
-  CODON_REQUIRE(lr_height >= 1 && lr_width >= 1 && lr_height <= 65536 && lr_width <= 65536 &&
-                    shape_ok(batch, lr_height * scale, lr_width * scale),
-                CODON_ERR_BAD_ARG, "lr_codes_upsample: bad shape");
-  CODON_REQUIRE(((uintptr_t)out & 15) == 0 && (code_bits == 8 || ((uintptr_t)codes & 1) == 0), CODON_ERR_BAD_ARG,
-                "lr_codes_upsample: out must be 16-byte aligned and u16 codes 2-byte aligned");
-  CODON_REQUIRE(codes != out, CODON_ERR_BAD_ARG, "lr_codes_upsample: codes and out are the same buffer");
+  if (const int st = check_lr_codes("lr_codes_upsample", batch, lr_height, lr_width, scale, codes, code_bits, depth_max, out)) return st;
+  if (const int st = check_not_same("lr_codes_upsample", codes, out, "codes")) return st;
   return lr_codes_upsample(batch, lr_height, lr_width, scale, codes, code_bits, lut, depth_max, phase_weights, out,
                            (hipStream_t)stream);
 }
@@ -1065,20 +1135,17 @@ size_t codon_fill_holes_workspace_bytes(int32_t height, int32_t width) { return 
 int codon_fill_holes(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, const float* tab, int32_t top,
                      void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
   CODON_REQUIRE(in && out && workspace, CODON_ERR_BAD_ARG, "fill_holes: null pointer");
+  const char* who = "fill_holes";
   CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16 || fmt == FL_F32, CODON_ERR_BAD_ARG,
                 "fill_holes: fmt %d (0: u8 codes, 1: u16 codes, 2: fp32 on the code grid)", fmt);
   CODON_REQUIRE(fmt != FL_F32 || tab, CODON_ERR_BAD_ARG, "fill_holes: null pointer (the fp32 format needs tab)");
-  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "fill_holes: batch %d (1..65535)", batch);
-  CODON_REQUIRE(height >= 1 && height <= FL_MAX_SIDE && width >= 1 && width <= FL_MAX_SIDE, CODON_ERR_BAD_ARG,
-                "fill_holes: a %dx%d plane (1..%d each way)", height, width, FL_MAX_SIDE);
-  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
-                "fill_holes: top %d (255 for u8 codes, 1..65535 otherwise)", top);
-  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "fill_holes: in and out are the same buffer");
+  if (const int st = check_batch(who, batch)) return st;
+  if (const int st = check_side(who, height, width, "plane", FL_MAX_SIDE)) return st;
+  if (const int st = check_top(who, fmt, top)) return st;
+  if (const int st = check_not_same(who, in, out)) return st;
   CODON_REQUIRE((((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0 && ((uintptr_t)workspace & 1) == 0,
                 CODON_ERR_BAD_ARG, "fill_holes: unaligned plane or workspace");
-  const size_t need = (size_t)batch * fill_holes_workspace_bytes(height, width);
-  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "fill_holes: a workspace of %zu bytes is too small (%zu needed)",
-                workspace_bytes, need);
+  if (const int st = check_workspace(who, workspace_bytes, (size_t)batch * fill_holes_workspace_bytes(height, width))) return st;
   return fill_holes(batch, height, width, in, fmt, tab, top, out, workspace, (hipStream_t)stream);
 }
 
@@ -1089,26 +1156,14 @@ int codon_fill_holes_guided(int32_t batch, int32_t height, int32_t width, const 
                             const uint8_t* guide, int64_t guide_row_bytes, int64_t guide_image_bytes, int32_t scale,
                             const uint16_t* range_tab, void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
   CODON_REQUIRE(in && out && workspace && guide && range_tab, CODON_ERR_BAD_ARG, "fill_holes_guided: null pointer");
-  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "fill_holes_guided: fmt %d (0: u8 codes, 1: u16 codes)", fmt);
-  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "fill_holes_guided: batch %d (1..65535)", batch);
-  CODON_REQUIRE(height >= 1 && height <= FL_MAX_SIDE && width >= 1 && width <= FL_MAX_SIDE, CODON_ERR_BAD_ARG,
-                "fill_holes_guided: a %dx%d plane (1..%d each way)", height, width, FL_MAX_SIDE);
-  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
-                "fill_holes_guided: top %d (255 for u8 codes, 1..65535 otherwise)", top);
-  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_BAD_ARG, "fill_holes_guided: scale %d (4, 8 or 16)", scale);
-  CODON_REQUIRE(guide_row_bytes >= (int64_t)width * scale, CODON_ERR_BAD_ARG,
-                "fill_holes_guided: guide rows of %lld bytes (at least %lld: width times scale)", (long long)guide_row_bytes,
-                (long long)width * scale);
-  CODON_REQUIRE(batch == 1 || guide_image_bytes >= (int64_t)height * scale * guide_row_bytes, CODON_ERR_BAD_ARG,
-                "fill_holes_guided: guide images %lld bytes apart (at least %lld: height times scale rows)",
-                (long long)guide_image_bytes, (long long)height * scale * guide_row_bytes);
-  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "fill_holes_guided: in and out are the same buffer");
+  const char* who = "fill_holes_guided";
+  if (const int st = check_planes(who, fmt, batch, height, width, FL_MAX_SIDE, top)) return st;
+  if (const int st = check_guide(who, batch, height, width, scale, guide_row_bytes, guide_image_bytes)) return st;
+  if (const int st = check_not_same(who, in, out)) return st;
   const bool planes_ok = (((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;      // u16 codes: 2 bytes
   const bool tab_ok = ((uintptr_t)range_tab & 1) == 0, ws_ok = ((uintptr_t)workspace & 15) == 0;             // u16 entries; 16 bytes
   CODON_REQUIRE(planes_ok && tab_ok && ws_ok, CODON_ERR_BAD_ARG, "fill_holes_guided: unaligned plane, table or workspace");
-  const size_t need = (size_t)batch * fill_guided_workspace_bytes(height, width);
-  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "fill_holes_guided: a workspace of %zu bytes is too small (%zu needed)",
-                workspace_bytes, need);
+  if (const int st = check_workspace(who, workspace_bytes, (size_t)batch * fill_guided_workspace_bytes(height, width))) return st;
   return fill_holes_guided(batch, height, width, in, fmt, top, guide, (long)guide_row_bytes,
                            batch == 1 ? 0L : (long)guide_image_bytes, scale, range_tab, out, workspace, (hipStream_t)stream);
 }
@@ -1120,26 +1175,14 @@ int codon_jbu_upsample(int32_t batch, int32_t height, int32_t width, const void*
                        int64_t guide_row_bytes, int64_t guide_image_bytes, int32_t scale, const uint16_t* range_tab,
                        const uint16_t* spatial_tab, void* out, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
   CODON_REQUIRE(in && out && workspace && guide && range_tab && spatial_tab, CODON_ERR_BAD_ARG, "jbu_upsample: null pointer");
-  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "jbu_upsample: fmt %d (0: u8 codes, 1: u16 codes)", fmt);
-  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "jbu_upsample: batch %d (1..65535)", batch);
-  CODON_REQUIRE(height >= 1 && height <= FL_MAX_SIDE && width >= 1 && width <= FL_MAX_SIDE, CODON_ERR_BAD_ARG,
-                "jbu_upsample: a %dx%d plane (1..%d each way)", height, width, FL_MAX_SIDE);
-  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
-                "jbu_upsample: top %d (255 for u8 codes, 1..65535 otherwise)", top);
-  CODON_REQUIRE(scale == 4 || scale == 8 || scale == 16, CODON_ERR_BAD_ARG, "jbu_upsample: scale %d (4, 8 or 16)", scale);
-  CODON_REQUIRE(guide_row_bytes >= (int64_t)width * scale, CODON_ERR_BAD_ARG,
-                "jbu_upsample: guide rows of %lld bytes (at least %lld: width times scale)", (long long)guide_row_bytes,
-                (long long)width * scale);
-  CODON_REQUIRE(batch == 1 || guide_image_bytes >= (int64_t)height * scale * guide_row_bytes, CODON_ERR_BAD_ARG,
-                "jbu_upsample: guide images %lld bytes apart (at least %lld: height times scale rows)",
-                (long long)guide_image_bytes, (long long)height * scale * guide_row_bytes);
-  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "jbu_upsample: in and out are the same buffer");
+  const char* who = "jbu_upsample";
+  if (const int st = check_planes(who, fmt, batch, height, width, FL_MAX_SIDE, top)) return st;
+  if (const int st = check_guide(who, batch, height, width, scale, guide_row_bytes, guide_image_bytes)) return st;
+  if (const int st = check_not_same(who, in, out)) return st;
   const bool planes_ok = ((uintptr_t)in & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0 && ((uintptr_t)out & 15) == 0;
   const bool tab_ok = (((uintptr_t)range_tab | (uintptr_t)spatial_tab) & 1) == 0, ws_ok = ((uintptr_t)workspace & 15) == 0;
   CODON_REQUIRE(planes_ok && tab_ok && ws_ok, CODON_ERR_BAD_ARG, "jbu_upsample: unaligned plane, table or workspace");
-  const size_t need = (size_t)batch * jbu_workspace_bytes(height, width);
-  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "jbu_upsample: a workspace of %zu bytes is too small (%zu needed)",
-                workspace_bytes, need);
+  if (const int st = check_workspace(who, workspace_bytes, (size_t)batch * jbu_workspace_bytes(height, width))) return st;
   return jbu_upsample(batch, height, width, in, fmt, guide, (long)guide_row_bytes, batch == 1 ? 0L : (long)guide_image_bytes, scale,
                       range_tab, spatial_tab, out, workspace, (hipStream_t)stream);
 }
@@ -1151,14 +1194,12 @@ int codon_register_depth(int32_t batch, int32_t src_height, int32_t src_width, c
                          const int32_t* rays, const int64_t* trans, const int32_t* proj, int32_t out_height, int32_t out_width,
                          void* out, uint32_t* stats, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
   CODON_REQUIRE(in && out && workspace && rays && trans && proj, CODON_ERR_BAD_ARG, "register_depth: null pointer");
-  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "register_depth: fmt %d (0: u8 codes, 1: u16 codes)", fmt);
-  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "register_depth: batch %d (1..65535)", batch);
-  CODON_REQUIRE(src_height >= 1 && src_height <= RG_MAX_SIDE && src_width >= 1 && src_width <= RG_MAX_SIDE, CODON_ERR_BAD_ARG,
-                "register_depth: a %dx%d source (1..%d each way)", src_height, src_width, RG_MAX_SIDE);
-  CODON_REQUIRE(out_height >= 1 && out_height <= RG_MAX_SIDE && out_width >= 1 && out_width <= RG_MAX_SIDE, CODON_ERR_BAD_ARG,
-                "register_depth: a %dx%d target (1..%d each way)", out_height, out_width, RG_MAX_SIDE);
-  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
-                "register_depth: top %d (255 for u8 codes, 1..65535 otherwise)", top);
+  const char* who = "register_depth";
+  if (const int st = check_fmt(who, fmt)) return st;
+  if (const int st = check_batch(who, batch)) return st;
+  if (const int st = check_side(who, src_height, src_width, "source", RG_MAX_SIDE)) return st;
+  if (const int st = check_side(who, out_height, out_width, "target", RG_MAX_SIDE)) return st;
+  if (const int st = check_top(who, fmt, top)) return st;
   for (int q = 0; q < 3; ++q)
     CODON_REQUIRE(trans[q] > -RG_T_LIMIT && trans[q] < RG_T_LIMIT, CODON_ERR_BAD_ARG,
                   "register_depth: translation %d is %lld (Q20 codes, below 2^38 in magnitude)", q, (long long)trans[q]);
@@ -1166,13 +1207,11 @@ int codon_register_depth(int32_t batch, int32_t src_height, int32_t src_width, c
                 "register_depth: projection FX %d, FY %d (Q8 pixels, 1 .. 2^20 - 1)", proj[0], proj[1]);
   CODON_REQUIRE(proj[2] > -RG_C_LIMIT && proj[2] < RG_C_LIMIT && proj[3] > -RG_C_LIMIT && proj[3] < RG_C_LIMIT, CODON_ERR_BAD_ARG,
                 "register_depth: projection CX %d, CY %d (Q8 pixels, below 2^21 in magnitude)", proj[2], proj[3]);
-  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "register_depth: in and out are the same buffer");
+  if (const int st = check_not_same(who, in, out)) return st;
   const bool planes_ok = (((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
   const bool words_ok = (((uintptr_t)rays | (uintptr_t)stats) & 3) == 0 && ((uintptr_t)workspace & 15) == 0;
   CODON_REQUIRE(planes_ok && words_ok, CODON_ERR_BAD_ARG, "register_depth: unaligned plane, table, statistics or workspace");
-  const size_t need = (size_t)batch * register_workspace_bytes(out_height, out_width);
-  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "register_depth: a workspace of %zu bytes is too small (%zu needed)",
-                workspace_bytes, need);
+  if (const int st = check_workspace(who, workspace_bytes, (size_t)batch * register_workspace_bytes(out_height, out_width))) return st;
   return register_depth(batch, src_height, src_width, in, fmt, top, rays, (const long long*)trans, proj, out_height, out_width, out,
                         stats, workspace, (hipStream_t)stream);
 }
@@ -1184,26 +1223,18 @@ int codon_clean_depth(int32_t batch, int32_t height, int32_t width, const void* 
                       int32_t tol_rel_q16, int32_t min_support, int32_t min_region, void* out, uint32_t* counts, void* workspace,
                       size_t workspace_bytes, codon_stream_t stream) {
   CODON_REQUIRE(in && out && workspace, CODON_ERR_BAD_ARG, "clean_depth: null pointer");
-  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "clean_depth: fmt %d (0: u8 codes, 1: u16 codes)", fmt);
-  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "clean_depth: batch %d (1..65535)", batch);
-  CODON_REQUIRE(height >= 1 && height <= CL_MAX_SIDE && width >= 1 && width <= CL_MAX_SIDE, CODON_ERR_BAD_ARG,
-                "clean_depth: a %dx%d plane (1..%d each way)", height, width, CL_MAX_SIDE);
-  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
-                "clean_depth: top %d (255 for u8 codes, 1..65535 otherwise)", top);
-  CODON_REQUIRE(tol_abs >= 0 && tol_abs <= top, CODON_ERR_BAD_ARG, "clean_depth: tolerance %d (codes, 0..top = %d)", tol_abs, top);
-  CODON_REQUIRE(tol_rel_q16 >= 0 && tol_rel_q16 <= CL_MAX_REL, CODON_ERR_BAD_ARG,
-                "clean_depth: tolerance_rel %d (Q16, 0..%d)", tol_rel_q16, CL_MAX_REL);
+  const char* who = "clean_depth";
+  if (const int st = check_planes(who, fmt, batch, height, width, CL_MAX_SIDE, top)) return st;
+  if (const int st = check_link_tolerances(who, tol_abs, top, tol_rel_q16, CL_MAX_REL)) return st;
   CODON_REQUIRE(min_support >= 0 && min_support <= CL_MAX_SUPPORT, CODON_ERR_BAD_ARG, "clean_depth: min_support %d (0..%d)",
                 min_support, CL_MAX_SUPPORT);
   CODON_REQUIRE(min_region >= 0 && min_region <= CL_MAX_REGION, CODON_ERR_BAD_ARG, "clean_depth: min_region %d (0..%d)", min_region,
                 CL_MAX_REGION);
-  CODON_REQUIRE(in != out, CODON_ERR_BAD_ARG, "clean_depth: in and out are the same buffer");
+  if (const int st = check_not_same(who, in, out)) return st;
   const bool planes_ok = (((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
   const bool words_ok = ((uintptr_t)counts & 3) == 0 && ((uintptr_t)workspace & 15) == 0;
   CODON_REQUIRE(planes_ok && words_ok, CODON_ERR_BAD_ARG, "clean_depth: unaligned plane, statistics or workspace");
-  const size_t need = clean_workspace_bytes(batch, height, width);
-  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "clean_depth: a workspace of %zu bytes is too small (%zu needed)",
-                workspace_bytes, need);
+  if (const int st = check_workspace(who, workspace_bytes, clean_workspace_bytes(batch, height, width))) return st;
   return clean_depth(batch, height, width, in, fmt, tol_abs, tol_rel_q16, min_support, min_region, out, counts, workspace,
                      (hipStream_t)stream);
 }
@@ -1216,17 +1247,11 @@ int codon_cloud_points(int32_t batch, int32_t height, int32_t width, const void*
                        int32_t tol_rel_q16, const uint8_t* color, int32_t color_channels, uint8_t* body, uint32_t* counts,
                        uint8_t* normal_map, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
   CODON_REQUIRE(codes && rx && ry && ray_span && body && counts && workspace, CODON_ERR_BAD_ARG, "cloud_points: null pointer");
-  CODON_REQUIRE(fmt == FL_U8 || fmt == FL_U16, CODON_ERR_BAD_ARG, "cloud_points: fmt %d (0: u8 codes, 1: u16 codes)", fmt);
-  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "cloud_points: batch %d (1..65535)", batch);
-  CODON_REQUIRE(height >= 1 && height <= CD_MAX_SIDE && width >= 1 && width <= CD_MAX_SIDE, CODON_ERR_BAD_ARG,
-                "cloud_points: a %dx%d plane (1..%d each way)", height, width, CD_MAX_SIDE);
-  CODON_REQUIRE(top >= 1 && top <= 65535 && (fmt != FL_U8 || top == 255), CODON_ERR_BAD_ARG,
-                "cloud_points: top %d (255 for u8 codes, 1..65535 otherwise)", top);
+  const char* who = "cloud_points";
+  if (const int st = check_planes(who, fmt, batch, height, width, CD_MAX_SIDE, top)) return st;
   CODON_REQUIRE(normals == 0 || normals == 1, CODON_ERR_BAD_ARG, "cloud_points: normals %d (0 or 1)", normals);
   CODON_REQUIRE(radius >= 1 && radius <= CD_MAX_RADIUS, CODON_ERR_BAD_ARG, "cloud_points: radius %d (1..%d)", radius, CD_MAX_RADIUS);
-  CODON_REQUIRE(tol_abs >= 0 && tol_abs <= top, CODON_ERR_BAD_ARG, "cloud_points: tolerance %d (codes, 0..top = %d)", tol_abs, top);
-  CODON_REQUIRE(tol_rel_q16 >= 0 && tol_rel_q16 <= CD_MAX_REL, CODON_ERR_BAD_ARG, "cloud_points: tolerance_rel %d (Q16, 0..%d)",
-                tol_rel_q16, CD_MAX_REL);
+  if (const int st = check_link_tolerances(who, tol_abs, top, tol_rel_q16, CD_MAX_REL)) return st;
   for (int q = 0; q < 4; ++q)
     CODON_REQUIRE(ray_span[q] > -CD_RAY_LIMIT && ray_span[q] < CD_RAY_LIMIT, CODON_ERR_BAD_ARG,
                   "cloud_points: ray %d of the span is %d (Q20, below 2^22 in magnitude)", q, ray_span[q]);
@@ -1237,9 +1262,7 @@ int codon_cloud_points(int32_t batch, int32_t height, int32_t width, const void*
   const bool planes_ok = ((uintptr_t)codes & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
   const bool words_ok = (((uintptr_t)rx | (uintptr_t)ry | (uintptr_t)counts) & 3) == 0 && ((uintptr_t)workspace & 15) == 0;
   CODON_REQUIRE(planes_ok && words_ok, CODON_ERR_BAD_ARG, "cloud_points: unaligned plane, table, counts or workspace");
-  const size_t need = cloud_workspace_bytes(batch, height, width);
-  CODON_REQUIRE(workspace_bytes >= need, CODON_ERR_BAD_ARG, "cloud_points: a workspace of %zu bytes is too small (%zu needed)",
-                workspace_bytes, need);
+  if (const int st = check_workspace(who, workspace_bytes, cloud_workspace_bytes(batch, height, width))) return st;
   return cloud_points(batch, height, width, codes, fmt, rx, ry, m, normals ? radius : 0, tol_abs, tol_rel_q16, color, color_channels,
                       body, counts, normal_map, workspace, (hipStream_t)stream);
 }
@@ -1283,10 +1306,9 @@ int codon_undistort(int32_t batch, int32_t src_height, int32_t src_width, int32_
 int codon_code_range(int32_t batch, int32_t height, int32_t width, const void* codes, int32_t code_bits, int32_t* lo_hi,
                      codon_stream_t stream) {
   CODON_REQUIRE(codes && lo_hi, CODON_ERR_BAD_ARG, "code_range: null pointer");
-  CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "code_range: code_bits %d (8 or 16)", code_bits);
-  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "code_range: batch %d (1..65535)", batch);
-  CODON_REQUIRE(height >= 1 && height <= ST_MAX_SIDE && width >= 1 && width <= ST_MAX_SIDE, CODON_ERR_BAD_ARG,
-                "code_range: a %dx%d plane (1..%d each way)", height, width, ST_MAX_SIDE);
+  if (const int st = check_code_bits("code_range", code_bits)) return st;
+  if (const int st = check_batch("code_range", batch)) return st;
+  if (const int st = check_side("code_range", height, width, "plane", ST_MAX_SIDE)) return st;
   CODON_REQUIRE(((uintptr_t)codes & (uintptr_t)(code_bits / 8 - 1)) == 0 && ((uintptr_t)lo_hi & 3) == 0, CODON_ERR_BAD_ARG,
                 "code_range: unaligned plane or range");
   return code_range(batch, (long)height * width, codes, code_bits == 8 ? ST_U8 : ST_U16, lo_hi, (hipStream_t)stream);
@@ -1295,10 +1317,9 @@ int codon_code_range(int32_t batch, int32_t height, int32_t width, const void* c
 static int map_codes_checked(const char* who, int dir, int32_t batch, int32_t height, int32_t width, const void* in,
                              int32_t code_bits, int32_t top, const int32_t* lo_hi, void* out, codon_stream_t stream) {
   CODON_REQUIRE(in && lo_hi && out, CODON_ERR_BAD_ARG, "%s: null pointer", who);
-  CODON_REQUIRE(code_bits == 8 || code_bits == 16, CODON_ERR_BAD_ARG, "%s: code_bits %d (8 or 16)", who, code_bits);
-  CODON_REQUIRE(batch >= 1 && batch <= 65535, CODON_ERR_BAD_ARG, "%s: batch %d (1..65535)", who, batch);
-  CODON_REQUIRE(height >= 1 && height <= ST_MAX_SIDE && width >= 1 && width <= ST_MAX_SIDE, CODON_ERR_BAD_ARG,
-                "%s: a %dx%d plane (1..%d each way)", who, height, width, ST_MAX_SIDE);
+  if (const int st = check_code_bits(who, code_bits)) return st;
+  if (const int st = check_batch(who, batch)) return st;
+  if (const int st = check_side(who, height, width, "plane", ST_MAX_SIDE)) return st;
   CODON_REQUIRE(code_bits == 16 ? (top >= 2 && top <= 65535) : top == 255, CODON_ERR_BAD_ARG,
                 "%s: top %d (255 for 8-bit codes, 2..65535 for 16-bit codes)", who, top);
   CODON_REQUIRE((((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(code_bits / 8 - 1)) == 0 && ((uintptr_t)lo_hi & 3) == 0,

@@ -10,7 +10,6 @@ import torch
 from . import _lib as L
 from . import ops
 
-_ABI_DTYPE = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}
 _P = C.c_void_p
 
 
@@ -19,13 +18,13 @@ def d4_views(x: torch.Tensor, y: torch.Tensor = None):
     in the same launch -- as an upright batch (4B,1,H,W) of codes 0, 2, 4, 6 and a transposed batch (4B,1,W,H) of codes 1, 3, 5,
     7; view k of image b is image 4*b + (k >> 1) of its batch.  Bits are copied, nothing is computed."""
     dev = ops._dev(x, y)
-    if x.dim() != 4 or x.shape[1] != 1 or x.dtype not in _ABI_DTYPE or (y is not None and (y.shape != x.shape or y.dtype != x.dtype)):
+    if x.dim() != 4 or x.shape[1] != 1 or x.dtype not in ops.DTYPE_CODE or (y is not None and (y.shape != x.shape or y.dtype != x.dtype)):
         raise RuntimeError("d4_views expects (B,1,H,W) planes of one shape and one dtype (fp32, fp16 or bf16)")
     B, _, H, W = x.shape
     outs = [torch.empty((4 * B, 1) + hw, dtype=x.dtype, device=dev) for _ in ((x,) if y is None else (x, y)) for hw in ((H, W), (W, H))]
     ptrs = [_P(t.data_ptr()) for t in outs] + [None, None]
     with ops._on(dev):
-        L.check(L.load().codon_d4_views(B, H, W, _P(x.data_ptr()), _P(y.data_ptr()) if y is not None else None, _ABI_DTYPE[x.dtype],
+        L.check(L.load().codon_d4_views(B, H, W, _P(x.data_ptr()), _P(y.data_ptr()) if y is not None else None, ops.DTYPE_CODE[x.dtype],
                                         ptrs[0], ptrs[1], ptrs[2], ptrs[3], ops._stream(dev)), "d4_views")
     return tuple(outs)
 
@@ -36,13 +35,13 @@ def d4_merge(upright: torch.Tensor, transposed: torch.Tensor) -> torch.Tensor:
     dev = ops._dev(upright, transposed)
     n = upright.shape[0] if upright.dim() == 4 else -1
     if (n < 0 or n % 4 or upright.shape[1] != 1 or transposed.shape != (n, 1, upright.shape[3], upright.shape[2])
-            or upright.dtype not in _ABI_DTYPE or transposed.dtype != upright.dtype):
+            or upright.dtype not in ops.DTYPE_CODE or transposed.dtype != upright.dtype):
         raise RuntimeError(f"d4_merge expects (4B,1,H,W) and (4B,1,W,H) of one dtype (fp32, fp16 or bf16), got "
                            f"{tuple(upright.shape)} {upright.dtype} and {tuple(transposed.shape)} {transposed.dtype}")
     _, _, H, W = upright.shape
     out = torch.empty((n // 4, 1, H, W), dtype=torch.float32, device=dev)
     with ops._on(dev):
-        L.check(L.load().codon_d4_merge(n // 4, H, W, _P(upright.data_ptr()), _P(transposed.data_ptr()), _ABI_DTYPE[upright.dtype],
+        L.check(L.load().codon_d4_merge(n // 4, H, W, _P(upright.data_ptr()), _P(transposed.data_ptr()), ops.DTYPE_CODE[upright.dtype],
                                         _P(out.data_ptr()), ops._stream(dev)), "d4_merge")
     return out
 
@@ -61,7 +60,7 @@ def self_ensemble(model, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         raise RuntimeError(f"self_ensemble expects two (B,1,H,W) tensors, got {tuple(x.shape)} and {tuple(y.shape)}")
     if not (x.is_cuda and y.is_cuda):
         raise RuntimeError("self_ensemble runs on MI355X only: move the model and inputs to 'cuda' (there is no CPU fallback)")
-    if x.dtype not in _ABI_DTYPE or y.dtype != x.dtype:
+    if x.dtype not in ops.DTYPE_CODE or y.dtype != x.dtype:
         raise NotImplementedError(f"self_ensemble: input dtypes {x.dtype} and {y.dtype} not supported (one of fp32, bf16, fp16 for both)")
     if getattr(model, "training", False):
         raise RuntimeError("self_ensemble is inference only: the model is in training mode, call .eval() first")

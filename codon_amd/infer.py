@@ -28,10 +28,11 @@ import numpy as np
 import torch
 
 from . import CODONNet, CODONNet16, io, metrics
+from .codes import codes_tensor
 from .io import check_depth_max, list_pairs, read_depth_plane
 from .prep import LrPrep, add_prep_args, prep_of
-from .upsample import (FILL_SIGMA, JBU_SIGMA_S, _code_planes, _on_device, bicubic_upsample_codes, check_fill_sigma,
-                       check_jbu_sigma_s, code_table, joint_bilateral_upsample, phase_weights, unstretch_codes)
+from .upsample import (FILL_SIGMA, JBU_SIGMA_S, bicubic_upsample_codes, check_fill_sigma, check_jbu_sigma_s, codes_to_input,
+                       joint_bilateral_upsample, unstretch_codes)
 
 BASELINES = ("bicubic", "jbu")
 
@@ -50,14 +51,8 @@ def _load_host(a_depth, a_color, a_label, f, tdt, depth_bits=8, depth_max=65535)
     h, w = min(px.shape[0], py.shape[0]), min(px.shape[1], py.shape[1])
     lab = None
     if a_label:
-        lab = _codes(read_depth_plane(os.path.join(a_label, f), depth_bits, depth_max))
+        lab = codes_tensor(read_depth_plane(os.path.join(a_label, f), depth_bits, depth_max))
     return _plane(px[:h, :w], depth_max if depth_bits == 16 else 255, tdt), _plane(py[:h, :w], 255, tdt), lab, h, w
-
-
-def _codes(a):
-    """A host tensor of a writable, contiguous copy of a code plane: uint8, or the bits of u16 codes as int16."""
-    a = np.array(a)
-    return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a)
 
 
 def _plane(p_, top, tdt):
@@ -72,17 +67,12 @@ def _plane(p_, top, tdt):
     return torch.from_numpy(b16.view(np.int16)).view(torch.bfloat16)[None, None]
 
 
-def _load_host_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits=8, depth_max=65535):
+def _load_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits=8, depth_max=65535, with_guide=False):
     """Host side of one image under --lr-depth: the depth file is a LOW-RESOLUTION map of codes (0 a hole), read
     through io.read_depth_plane and returned AS CODES -- (h,w) uint8, or the u16 bits as int16 -- for codes_to_input; the
     HR size is (h * scale, w * scale), and the guidance and the label are cropped top-left to it.  A smaller guidance or label
-    raises ValueError naming the file."""
-    return _load_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits, depth_max)[:5]
-
-
-def _load_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits=8, depth_max=65535, with_guide=False):
-    """_load_host_lr's five items and a sixth, always there: with_guide the cropped guidance AS CODES, (H, W)
-    uint8, for the guided hole filler, else None."""
+    raises ValueError naming the file.  -> (codes, guidance, label or None, h, w) and a sixth, always there: with_guide
+     the cropped guidance AS CODES, (H, W) uint8, for the guided hole filler, else None."""
     px = read_depth_plane(os.path.join(a_lr, f), depth_bits, depth_max)
     py = io.read_gray(os.path.join(a_color, f))
     h, w = px.shape[0] * scale, px.shape[1] * scale
@@ -95,38 +85,9 @@ def _load_lr(a_lr, a_color, a_label, f, tdt, scale, depth_bits=8, depth_max=6553
         if lab.shape[0] < h or lab.shape[1] < w:
             raise ValueError(f"{os.path.join(a_label, f)}: {lab.shape[0]}x{lab.shape[1]}, smaller than the {h}x{w} that "
                              f"{os.path.join(a_lr, f)} gives at x{scale}")
-        lab = _codes(lab[:h, :w])
+        lab = codes_tensor(lab[:h, :w])
     guide = torch.from_numpy(np.array(py[:h, :w])) if with_guide else None
-    return _codes(px), _plane(py[:h, :w], 255, tdt), lab, h, w, guide
-
-
-def codes_to_input(codes: torch.Tensor, scale: int, tdt, depth_max: int = None) -> torch.Tensor:
-    """The network's depth input from a low-resolution code plane on the device, ONE launch (codon_lr_codes_to_input):
-    codes (h,w) or (B,h,w), uint8 (value = code / 255) or the bits of u16 codes as int16 / uint16 (value = code / depth_max,
-    default 65535), code 0 a hole -> the mask-normalised bicubic x`scale` (upsample.bicubic_upsample_masked) -> back onto the
-    code grid -> tdt, as (B,1,h*scale,w*scale).  Bit for bit what train.synthesize(degrade_holes=True) builds from the same
-    low-resolution values."""
-    from . import _lib as L
-    from . import ops
-    import ctypes as C
-    codes, B, h, w, bits, top = _code_planes("codes_to_input", codes, depth_max)
-    if scale not in (4, 8, 16):
-        raise ValueError(f"codes_to_input: scale {scale!r} (4, 8 or 16)")
-    if tdt not in _ABI_DTYPE:
-        raise ValueError(f"codes_to_input: dtype {tdt!r} (float32, float16 or bfloat16)")
-    dev = ops._dev(codes)
-    lut, top = code_table(bits, top, dev)
-    wt = _on_device(("up", scale), lambda: phase_weights(scale), dev)
-    out = torch.empty((B, 1, h * scale, w * scale), dtype=tdt, device=dev)
-    P_ = C.c_void_p
-    with ops._on(dev):
-        L.check(L.load().codon_lr_codes_to_input(B, h, w, scale, P_(codes.data_ptr()), bits, P_(lut.data_ptr()), top,
-                                                 P_(wt.data_ptr()), P_(out.data_ptr()), _ABI_DTYPE[tdt], ops._stream(dev)),
-                "lr_codes_to_input")
-    return out
-
-
-_ABI_DTYPE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}      # codon_dtype
+    return codes_tensor(px), _plane(py[:h, :w], 255, tdt), lab, h, w, guide
 
 
 READERS = int(os.environ.get("CODON_INFER_READERS", "3"))

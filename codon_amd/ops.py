@@ -10,17 +10,14 @@ import torch
 from . import _lib as L
 
 
+DTYPE_CODE = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}      # torch dtype -> codon_dtype, the one map
+
+
 def _dt(t: torch.Tensor) -> int:
-    if t.dtype == torch.float32:
-        return L.F32
-    if t.dtype == torch.bfloat16:
-        return L.BF16
-    if t.dtype == torch.float16:
-        return L.F16
-    raise TypeError(f"codon_amd: unsupported dtype {t.dtype} (fp32, bf16, fp16)")
-
-
-_DT_CODE = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}
+    code = DTYPE_CODE.get(t.dtype)
+    if code is None:
+        raise TypeError(f"codon_amd: unsupported dtype {t.dtype} (fp32, bf16, fp16)")
+    return code
 
 
 def _dev(*ts):
@@ -157,7 +154,7 @@ def packed_weight(w: torch.Tensor, mode: int = L.PACK_FWD, dtype: Optional[torch
     dtype = dtype or torch.float32
     out = torch.empty(w.numel(), dtype=dtype, device=dev)
     with _on(dev):
-        L.check(lib.codon_conv_pack_weight(_ptr(w), _ptr(out), cout, cin, k, mode, _DT_CODE[dtype], _stream(dev)),
+        L.check(lib.codon_conv_pack_weight(_ptr(w), _ptr(out), cout, cin, k, mode, DTYPE_CODE[dtype], _stream(dev)),
                 "conv_pack_weight")
     return out
 
@@ -484,7 +481,7 @@ def cac_fused_tiles(H: int, W: int) -> int:
 
 def cac_fused_parts(H: int, W: int, dtype) -> int:
     """Rows per image of the fused-statistics partials for activations of `dtype` (codon_cac_fused_parts)."""
-    return L.load().codon_cac_fused_parts(H, W, _DT_CODE[dtype])
+    return L.load().codon_cac_fused_parts(H, W, DTYPE_CODE[dtype])
 
 
 def params_f32(tensors):

@@ -29,8 +29,8 @@ import torch
 
 from . import _lib as L
 from . import clean as cleaning
-from . import io, ops
-from .upsample import _code_planes, _workspace
+from . import codes as K
+from . import ops
 
 A_LIMIT, T_LIMIT, F_LIMIT, C_LIMIT = 1 << 22, 1 << 38, 1 << 20, 1 << 21
 UNDISTORT_ITERS = 40
@@ -63,9 +63,7 @@ class Camera:
     def __post_init__(self):
         who = "Camera"
         for n in ("width", "height"):
-            v = getattr(self, n)
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= v <= MAX_SIDE:
-                raise ValueError(f"{who}: {n} {v!r} (an integer in 1..{MAX_SIDE})")
+            K.integer(who, n, getattr(self, n), 1, MAX_SIDE, f"an integer in 1..{MAX_SIDE}")
         fx, fy, cx, cy = _finite(who, "fx, fy, cx, cy", (self.fx, self.fy, self.cx, self.cy))
         if fx <= 0 or fy <= 0:
             raise ValueError(f"{who}: focal lengths {self.fx!r}, {self.fy!r} must be positive")
@@ -188,12 +186,7 @@ def ray_table(cal: Calibration, radial: bool = False) -> np.ndarray:
 
 def translation_q20(cal: Calibration, unit: float) -> np.ndarray:
     """T: int64[3], rint(2^20 t / unit) with t in metres and unit in metres per code"""
-    try:
-        u = float(unit)
-    except (TypeError, ValueError):
-        u = float("nan")
-    if not (u > 0.0 and math.isfinite(u)):
-        raise ValueError(f"translation_q20: depth_unit {unit!r} (a positive number of metres per code)")
+    u = K.positive("translation_q20", "depth_unit", unit, "a positive number of metres per code")
     v = np.rint(float(1 << 20) * np.asarray(cal.translation, dtype=np.float64) / u)
     if not np.isfinite(v).all() or np.abs(v).max() >= T_LIMIT:
         raise ValueError(f"translation_q20: a translation of {cal.translation!r} m is 2^18 codes or more at {u!r} m per code")
@@ -242,20 +235,20 @@ class Registration:
         landed; the argument is not modified.  stats=True: (codes, int32 (B, 4) on the device: valid source pixels, pixels wholly
         outside the plane, dropped pixels, filled target pixels).  Three launches; no host synchronisation."""
         who = "register_depth"
-        src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
+        p = K.code_planes(who, codes, depth_max)
         d = self.cal.depth
-        if (h, w) != (d.height, d.width):
-            raise ValueError(f"{who}: a {h}x{w} plane, and the depth camera of the calibration is {d.height}x{d.width}")
-        dev = ops._dev(src)
+        if (p.h, p.w) != (d.height, d.width):
+            raise ValueError(f"{who}: a {p.h}x{p.w} plane, and the depth camera of the calibration is {d.height}x{d.width}")
+        dev = p.dev
         if dev != self.rays.device:
             raise RuntimeError(f"{who}: codes on {dev}, the tables on {self.rays.device}")
         ho, wo = self.out_size
-        out = torch.empty((*src.shape[:-2], ho, wo), dtype=src.dtype, device=dev)
-        counts = torch.empty((B, 4), dtype=torch.int32, device=dev) if stats else None
+        out = p.out(ho, wo)
+        counts = torch.empty((p.B, 4), dtype=torch.int32, device=dev) if stats else None
         P_ = C.c_void_p
-        with torch.cuda.device(dev):
-            ws = _workspace(who, "codon_register_workspace_bytes", dev, B, ho, wo)
-            L.check(L.load().codon_register_depth(B, h, w, P_(src.data_ptr()), L.FILL_U8 if bits == 8 else L.FILL_U16, top,
+        with ops._on(dev):
+            ws = K.workspace(who, "codon_register_workspace_bytes", dev, p.B, ho, wo)
+            L.check(L.load().codon_register_depth(p.B, p.h, p.w, p.ptr, p.fmt, p.top,
                                                   P_(self.rays.data_ptr()), self._trans, self._proj, ho, wo, P_(out.data_ptr()),
                                                   P_(counts.data_ptr()) if stats else None, P_(ws.data_ptr()), ws.numel(),
                                                   ops._stream(dev)), who)
@@ -273,29 +266,21 @@ def parse_args(argv=None):
     ap.add_argument("--out", required=True, metavar="DIR", help="where the registered maps go, under the same file names")
     ap.add_argument("--scale", type=int, default=1, choices=SCALES,
                     help="1: the colour camera's grid (a --train-depth target, a --label); S: colour / S, what --lr-depth reads")
-    ap.add_argument("--depth-bits", type=int, default=8, choices=(8, 16))
-    ap.add_argument("--depth-max", type=int, default=None, metavar="N", help="the largest code of a 16-bit data set (default 65535)")
-    ap.add_argument("--depth-unit", type=float, default=0.001, metavar="M", help="metres per code (default 0.001)")
+    K.add_depth_args(ap, depth_unit=0.001)
     ap.add_argument("--radial", action="store_true", help="the files hold ranges along the ray, not z")
     ap.add_argument("--stats", action="store_true", help="print valid=, outside=, dropped= and filled= per file")
     ap.add_argument("--clean", action="store_true", help="remove flying pixels and speckles first (python -m codon_amd.clean); "
                     "--stats then also prints valid=, flying=, speckle= and regions= of the cleaning")
     cleaning.add_arguments(ap, "clean-")
     a = ap.parse_args(argv)
-    if a.depth_max is not None and a.depth_bits != 16:
-        ap.error("--depth-max needs --depth-bits 16")
-    if a.depth_max is not None and not 1 <= a.depth_max <= 65535:
-        ap.error(f"--depth-max {a.depth_max} must be in [1, 65535]")
-    if not (a.depth_unit > 0.0 and math.isfinite(a.depth_unit)):
-        ap.error(f"--depth-unit {a.depth_unit} must be positive")
+    a.top = K.depth_args_of(ap, a)
     if os.path.abspath(a.out) == os.path.abspath(a.depth):
         ap.error("--out is --depth: the registered maps would overwrite the sensor's")
     a.cleaner = None
     if a.clean:
         a.cleaner = cleaning.cleaner_of(a, ap, "clean-")
-        top = 255 if a.depth_bits == 8 else 65535 if a.depth_max is None else a.depth_max
-        if a.cleaner.tolerance > top:
-            ap.error(f"--clean-tolerance {a.cleaner.tolerance} is above the largest code {top}")
+        if a.cleaner.tolerance > a.top:
+            ap.error(f"--clean-tolerance {a.cleaner.tolerance} is above the largest code {a.top}")
     else:
         for name, default in cleaning.DEFAULTS.items():
             if getattr(a, "clean_" + name) != default:
@@ -309,26 +294,18 @@ def main(argv=None, emit=print):
         cal = Calibration.from_json(a.calib)
     except (OSError, ValueError) as e:
         ap.error(f"--calib {a.calib}: {e}")
-    if not os.path.isdir(a.depth):
-        ap.error(f"--depth {a.depth} is not a directory")
-    if not torch.cuda.is_available():
-        raise SystemExit("No GPU found: codon_amd has no CPU fallback")
-    depth_max = 65535 if a.depth_max is None else a.depth_max
+    K.require_dir(ap, "depth", a.depth)
+    K.require_gpu()
     reg = Registration(cal, a.scale, a.depth_unit, a.radial)
     os.makedirs(a.out, exist_ok=True)
-    for name in sorted(os.listdir(a.depth)):
-        plane = io.read_depth_plane(os.path.join(a.depth, name), a.depth_bits, depth_max)
-        codes = torch.from_numpy((plane.view(np.int16) if plane.dtype == np.uint16 else plane).copy()).to(reg.device)
+    for name, codes in K.depth_files(a.depth, a.depth_bits, a.top, reg.device):
         cleaned = None
         if a.cleaner is not None:
-            codes = a.cleaner(codes, depth_max if a.depth_bits == 16 else None, stats=a.stats)
+            codes = a.cleaner(codes, a.depth_max, stats=a.stats)
             codes, cleaned = codes if a.stats else (codes, None)
-        got = reg(codes, depth_max if a.depth_bits == 16 else None, stats=a.stats)
+        got = reg(codes, a.depth_max, stats=a.stats)
         out, counts = got if a.stats else (got, None)
-        if a.depth_bits == 16:
-            io.write_depth16(os.path.join(a.out, name), out.cpu().numpy().view(np.uint16))
-        else:
-            io.write_gray(os.path.join(a.out, name), out.cpu().numpy())
+        K.write_codes(os.path.join(a.out, name), out)
         if a.stats:
             c = counts.cpu().numpy().view(np.uint32)[0]
             tail = "" if cleaned is None else " cleaned: " + cleaning.stats_line(cleaned.cpu().numpy()[0])

@@ -46,8 +46,8 @@ from . import ops
 from .infer import add_report_args, report_of, run_loop
 from .io import check_depth_max, list_pairs, read_depth_plane
 from .metrics import report_tokens
-from .upsample import (_fill_launch, _on_device, code_table, down_weights, gauss_table, lut16,      # noqa: F401 (lut16: for
-                       phase_weights, u8_lut)                                                      # importers)
+from .codes import code_table, on_device
+from .upsample import (_fill_launch, down_weights, gauss_table, lut16, phase_weights, u8_lut)      # noqa: F401 (lut16: for importers)
 from .prep import LrPrep, add_prep_args, prep_of
 from .upsample import FILL_SIGMA, code_range, stretch_codes
 
@@ -387,8 +387,8 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
         s.offset, s.height, s.width, s.y0, s.x0, s.op = off, h, w, y0, x0, op
     deep = trainset.depth_bits == 16
     tab, top = code_table(trainset.depth_bits, trainset.depth_max, dev)      # the depth codes' table (the set's own grid)
-    lut = _on_device("lut", u8_lut, dev)                                     # the guidance's
-    wup = _on_device(("up", scale), lambda: phase_weights(scale), dev)
+    lut = on_device("lut", u8_lut, dev)                                     # the guidance's
+    wup = on_device(("up", scale), lambda: phase_weights(scale), dev)
     P_ = C.c_void_p
     pool = (C.byref(d), P_(trainset.pool.data_ptr()), trainset.pool.numel())
     t = torch.empty((B, 1, crop, crop), dtype=torch.float32, device=dev)
@@ -400,7 +400,7 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
                                              P_(wup.data_ptr()), P_(x.data_ptr()), P_(y.data_ptr()), P_(t.data_ptr()), st),
                     "train_crops_lr")
             return x, y, t
-        wdown = _on_device(("down", crop, scale), lambda: down_weights(crop, scale), dev)
+        wdown = on_device(("down", crop, scale), lambda: down_weights(crop, scale), dev)
         p = crop // scale
         src = torch.empty_like(t) if trainset.has_label else t        # what the degradation reads
         lr = torch.empty((B, 1, p, p), dtype=torch.float32, device=dev)
@@ -430,7 +430,7 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
             sd.sigma, sd.quad, sd.edge_thr = (np.float32(np.float64(c) / top) for c in
                                               (sensor.noise, sensor.noise_quad, sensor.edge_threshold))
             sd.p_drop, sd.p_edge = sensor.dropout, sensor.edge_dropout
-            gauss = _on_device("gauss", gauss_table, dev)
+            gauss = on_device("gauss", gauss_table, dev)
             L.check(lib.codon_lr_sensor(C.byref(sd), P_(lr.data_ptr()), P_(gauss.data_ptr()), P_(tab.data_ptr()), top,
                                         P_(noisy.data_ptr()), st), "lr_sensor")
         if fill_holes:                                  # degrade_holes: refused otherwise

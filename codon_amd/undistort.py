@@ -22,6 +22,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .codes import require_dir, require_gpu
 from .register import MAX_SIDE, Camera, distort
 
 OUTSIDE = -(1 << 20)
@@ -196,10 +197,8 @@ def main(argv=None, emit=print):
         src = Camera.from_mapping(mapping["color"], "color")
     except (OSError, ValueError) as e:                                   # json.JSONDecodeError is a ValueError
         ap.error(f"--calib {a.calib}: {e}")
-    if not os.path.isdir(a.color):
-        ap.error(f"--color {a.color} is not a directory")
-    if not torch.cuda.is_available():
-        raise SystemExit("No GPU found: codon_amd has no CPU fallback")
+    require_dir(ap, "color", a.color)
+    require_gpu()
     und = Undistortion(src, focal_scale=a.focal_scale)
     os.makedirs(a.out, exist_ok=True)
     for name in sorted(os.listdir(a.color)):

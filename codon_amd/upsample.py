@@ -9,6 +9,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .codes import code_planes, code_table, on_device, positive, workspace
 from .io import check_depth_max
 
 
@@ -75,26 +76,6 @@ def down_weights(size: int, scale: int) -> np.ndarray:
     return tab.astype(np.float32)
 
 
-_dev_tabs: dict = {}
-
-
-def _on_device(key, make, dev):
-    k = (key, str(dev))
-    t = _dev_tabs.get(k)
-    if t is None:
-        t = _dev_tabs[k] = torch.from_numpy(np.ascontiguousarray(make())).to(dev)
-    return t
-
-
-def code_table(depth_bits: int, depth_max: int, dev):
-    """(table, top) on `dev` for codes of depth_bits bits: value = table[code], and top is the code of 1.0 -- u8_lut and 255,
-    or lut16(depth_max) and depth_max."""
-    if depth_bits == 16:
-        top = int(depth_max)
-        return _on_device(("lut16", top), lambda: lut16(top), dev), top
-    return _on_device("lut", u8_lut, dev), 255
-
-
 def bicubic_upsample(lr: torch.Tensor, scale: int) -> torch.Tensor:
     lib = L.load()
     if lr.dim() != 4 or lr.shape[1] != 1 or lr.dtype != torch.float32:
@@ -129,51 +110,12 @@ def bicubic_upsample_masked(lr: torch.Tensor, scale: int):
     return out, valid
 
 
-# ---- code planes: the one checker of the argument, the fillers' workspaces ---------------------------------------------------------
-
-CODES = "(h,w) or (B,h,w) uint8 codes, or u16 codes as int16 / uint16"
-
-
-def _code_planes(who: str, codes: torch.Tensor, depth_max, expects: str = CODES):
-    """-> (contiguous codes, B, h, w, code_bits, top) of (h,w) / (B,h,w) uint8, int16 or uint16 codes; refusals by name"""
-    if codes.dim() not in (2, 3) or codes.dtype not in (torch.uint8, torch.int16, torch.uint16):
-        raise RuntimeError(f"{who} expects {expects}")
-    if codes.dtype == torch.uint8:
-        if depth_max not in (None, 255):
-            raise ValueError(f"{who}: depth_max {depth_max!r} with 8-bit codes")
-        bits, top = 8, 255
-    else:
-        bits, top = 16, 65535 if depth_max is None else depth_max
-    check_depth_max(top)
-    src = codes.contiguous()
-    h, w = src.shape[-2:]
-    B = src.numel() // (h * w) if h * w else 0
-    if B < 1:
-        raise ValueError(f"{who}: an empty map {tuple(codes.shape)}")
-    return src, B, h, w, bits, int(top)
-
-
-_ws: dict = {}              # filler -> (guards.PerStream -> uint8 workspace of the (device, stream, thread), those made under a capture)
-
-
-def _workspace(who: str, query: str, dev, B: int, h: int, w: int, batched: bool = False):
-    """Filler `who`'s workspace for B planes of h x w on dev's current stream, sized by the library's `query` (capture-safe:
-    guards.PerStream); the two fillers never share one.  `query` answers for one plane, or (batched) for all B.  Call it with
-    `dev` current."""
-    from .guards import PerStream
-    need = getattr(L.load(), query)(B, h, w) if batched else B * getattr(L.load(), query)(h, w)
-    if need == 0:
-        raise ValueError(f"{who}: a {h}x{w} plane (1..4096 each way)")
-    per_stream, held = _ws.setdefault(who, (PerStream(), []))
-    return per_stream.get(dev, lambda capturing: torch.empty(need, dtype=torch.uint8, device=dev), need=need, hold=held)
-
-
 # ---- pull-push hole filling of low-resolution maps (DESIGN 12.9) --------------------------------------------------------------
 
 def _fill_launch(dev, B: int, h: int, w: int, src_ptr: int, fmt: int, tab, top: int, out_ptr: int):
     """codon_fill_holes on dev's current stream, with the per-stream workspace"""
-    with torch.cuda.device(dev):
-        ws = _workspace("fill_holes", "codon_fill_holes_workspace_bytes", dev, B, h, w)
+    with ops._on(dev):
+        ws = workspace("fill_holes", "codon_fill_holes_workspace_bytes", dev, B, h, w)
         L.check(L.load().codon_fill_holes(B, h, w, C.c_void_p(src_ptr), fmt, C.c_void_p(tab.data_ptr()) if tab is not None else None,
                                           top, C.c_void_p(out_ptr), C.c_void_p(ws.data_ptr()), ws.numel(), ops._stream(dev)),
                 "fill_holes")
@@ -197,12 +139,13 @@ def fill_holes(codes: torch.Tensor, depth_max: int = None) -> torch.Tensor:
         B, _, h, w = src.shape
         if B * h * w == 0:
             raise ValueError(f"fill_holes: an empty map {tuple(codes.shape)}")
-        fmt, tab = L.FILL_F32, code_table(bits, top, ops._dev(src))[0]
+        dev = ops._dev(src)
+        fmt, tab = L.FILL_F32, code_table(bits, top, dev)[0]
     else:
-        src, B, h, w, bits, top = _code_planes("fill_holes", codes, depth_max, expects)
-        fmt, tab = L.FILL_U8 if bits == 8 else L.FILL_U16, None
+        p = code_planes("fill_holes", codes, depth_max, expects)
+        src, B, h, w, top, fmt, tab, dev = p.src, p.B, p.h, p.w, p.top, p.fmt, None, p.dev
     out = torch.empty_like(src)
-    _fill_launch(ops._dev(src), B, h, w, src.data_ptr(), fmt, tab, int(top), out.data_ptr())
+    _fill_launch(dev, B, h, w, src.data_ptr(), fmt, tab, int(top), out.data_ptr())
     return out
 
 
@@ -213,13 +156,7 @@ FILL_SIGMA = 10.0           # the default range sigma in guidance codes: the pro
 
 def check_fill_sigma(who: str, sigma) -> float:
     """sigma as a float; anything but a finite positive number is refused by name"""
-    try:
-        s = float(sigma)
-    except (TypeError, ValueError):
-        s = float("nan")
-    if not (s > 0.0 and s != float("inf")):
-        raise ValueError(f"{who}: fill_sigma {sigma!r} (a positive number of guidance codes)")
-    return s
+    return positive(who, "fill_sigma", sigma, "a positive number of guidance codes")
 
 
 @functools.lru_cache(maxsize=None)
@@ -237,16 +174,17 @@ def range_table(sigma: float = FILL_SIGMA, device=None):
     s = check_fill_sigma("range_table", sigma)
     if device is None:
         return _range_table(s)
-    return _on_device(("range", s), lambda: _range_table(s).view(np.int16).copy(), torch.device(device))
+    return on_device(("range", s), lambda: _range_table(s).view(np.int16).copy(), torch.device(device))
 
 
 def _guided_args(who: str, codes, guide, scale, sigma, depth_max, _table):
     """The argument checks and the strided-guide rules the guided filler and the joint bilateral upsampler share ->
-    (contiguous codes, B, h, w, code_bits, top, device, guide row bytes, guide image bytes, range table on the device)"""
-    src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
+    (the codes' Planes, guide row bytes, guide image bytes, range table on the device)"""
+    p = code_planes(who, codes, depth_max)
+    src, B, h, w = p.src, p.B, p.h, p.w
     if scale not in (4, 8, 16):
         raise ValueError(f"{who}: scale {scale!r} (4, 8 or 16)")
-    dev = ops._dev(src)
+    dev = p.dev
     if guide.dtype != torch.uint8 or guide.dim() != codes.dim() or guide.device != src.device:
         raise RuntimeError(f"{who} expects a uint8 guide on the codes' device, (H,W) for (h,w) codes and (B,H,W) for (B,h,w) codes")
     if guide.dim() == 3 and guide.shape[0] != B:
@@ -265,7 +203,7 @@ def _guided_args(who: str, codes, guide, scale, sigma, depth_max, _table):
         raise RuntimeError(f"{who}: _table must be a contiguous (256,) int16 / uint16 tensor on the codes' device")
     else:
         table = _table
-    return src, B, h, w, bits, top, dev, row_bytes, image_bytes, table
+    return p, row_bytes, image_bytes, table
 
 
 def fill_holes_guided(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigma: float = FILL_SIGMA, depth_max: int = None,
@@ -284,12 +222,12 @@ def fill_holes_guided(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigm
     a hole never takes a value above the largest valid code.  Integer arithmetic, bit-exact: tests/guided_fill_ref.py.  One
     launch up to 64 x 64, three beyond; no host synchronisation."""
     who = "fill_holes_guided"
-    src, B, h, w, bits, top, dev, row_bytes, image_bytes, table = _guided_args(who, codes, guide, scale, sigma, depth_max, _table)
-    out = torch.empty_like(src)
+    p, row_bytes, image_bytes, table = _guided_args(who, codes, guide, scale, sigma, depth_max, _table)
+    dev, out = p.src.device, p.out()              # the device _guided_args has checked
     P_ = C.c_void_p
-    with torch.cuda.device(dev):
-        ws = _workspace(who, "codon_fill_guided_workspace_bytes", dev, B, h, w)
-        L.check(L.load().codon_fill_holes_guided(B, h, w, P_(src.data_ptr()), L.FILL_U8 if bits == 8 else L.FILL_U16, top,
+    with ops._on(dev):
+        ws = workspace(who, "codon_fill_guided_workspace_bytes", dev, p.B, p.h, p.w)
+        L.check(L.load().codon_fill_holes_guided(p.B, p.h, p.w, p.ptr, p.fmt, p.top,
                                                  P_(guide.data_ptr()), row_bytes, image_bytes, scale, P_(table.data_ptr()),
                                                  P_(out.data_ptr()), P_(ws.data_ptr()), ws.numel(), ops._stream(dev)), who)
     return out
@@ -302,13 +240,7 @@ JBU_SIGMA_S = 1.0           # the default spatial sigma of the joint bilateral u
 
 def check_jbu_sigma_s(who: str, sigma_s) -> float:
     """sigma_s as a float; anything but a finite positive number is refused by name"""
-    try:
-        s = float(sigma_s)
-    except (TypeError, ValueError):
-        s = float("nan")
-    if not (s > 0.0 and s != float("inf")):
-        raise ValueError(f"{who}: sigma_s {sigma_s!r} (a positive number of low-resolution pixels)")
-    return s
+    return positive(who, "sigma_s", sigma_s, "a positive number of low-resolution pixels")
 
 
 @functools.lru_cache(maxsize=None)
@@ -333,7 +265,7 @@ def spatial_table(scale: int, sigma_s: float = JBU_SIGMA_S, device=None):
     s = check_jbu_sigma_s("spatial_table", sigma_s)
     if device is None:
         return _spatial_table(scale, s)
-    return _on_device(("spatial", scale, s), lambda: _spatial_table(scale, s).view(np.int16).copy(), torch.device(device))
+    return on_device(("spatial", scale, s), lambda: _spatial_table(scale, s).view(np.int16).copy(), torch.device(device))
 
 
 def joint_bilateral_upsample(codes: torch.Tensor, guide: torch.Tensor, scale: int, sigma_s: float = JBU_SIGMA_S,
@@ -347,13 +279,14 @@ def joint_bilateral_upsample(codes: torch.Tensor, guide: torch.Tensor, scale: in
     fill_holes_guided takes them, the guide read IN PLACE through its strides.  sigma_s: in low-resolution pixels; sigma_r: in
     guidance codes.  Integer arithmetic, bit-exact: tests/jbu_ref.py.  Two launches; no host synchronisation."""
     who = "joint_bilateral_upsample"
-    src, B, h, w, bits, top, dev, row_bytes, image_bytes, table = _guided_args(who, codes, guide, scale, sigma_r, depth_max, _table)
+    p, row_bytes, image_bytes, table = _guided_args(who, codes, guide, scale, sigma_r, depth_max, _table)
+    dev = p.src.device                            # the device _guided_args has checked
     stab = spatial_table(scale, check_jbu_sigma_s(who, sigma_s), dev)
-    out = torch.empty((*src.shape[:-2], h * scale, w * scale), dtype=src.dtype, device=dev)
+    out = p.out(p.h * scale, p.w * scale)
     P_ = C.c_void_p
-    with torch.cuda.device(dev):
-        ws = _workspace(who, "codon_jbu_workspace_bytes", dev, B, h, w)
-        L.check(L.load().codon_jbu_upsample(B, h, w, P_(src.data_ptr()), L.FILL_U8 if bits == 8 else L.FILL_U16, top,
+    with ops._on(dev):
+        ws = workspace(who, "codon_jbu_workspace_bytes", dev, p.B, p.h, p.w)
+        L.check(L.load().codon_jbu_upsample(p.B, p.h, p.w, p.ptr, p.fmt, p.top,
                                             P_(guide.data_ptr()), row_bytes, image_bytes, scale, P_(table.data_ptr()),
                                             P_(stab.data_ptr()), P_(out.data_ptr()), P_(ws.data_ptr()), ws.numel(),
                                             ops._stream(dev)), who)
@@ -361,22 +294,38 @@ def joint_bilateral_upsample(codes: torch.Tensor, guide: torch.Tensor, scale: in
 
 
 def bicubic_upsample_codes(codes: torch.Tensor, scale: int, depth_max: int = None) -> torch.Tensor:
-    """The bicubic baseline: the hole-aware bicubic of infer.codes_to_input, written as the INTEGER that function
+    """The bicubic baseline: the hole-aware bicubic of codes_to_input, written as the INTEGER that function
     looks up before its cast, rint(clamp(up) * top) -- codes of shape (..., h * scale, w * scale) and the input's dtype, a hole
     of the rule staying 0.  (Not the float input truncated back: float32(k / 255) * 255 truncates to k - 1 for some k.)  codes:
     (h,w) or (B,h,w) uint8 codes, or the bits of u16 codes as int16 / uint16 (depth_max: default 65535).  One launch."""
-    who = "bicubic_upsample_codes"
-    src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
+    return _lr_codes("bicubic_upsample_codes", "codon_lr_codes_upsample", "bicubic_upsample_codes", codes, scale, depth_max)
+
+
+def codes_to_input(codes: torch.Tensor, scale: int, tdt, depth_max: int = None) -> torch.Tensor:
+    """The network's depth input from a low-resolution code plane on the device, ONE launch (codon_lr_codes_to_input):
+    codes (h,w) or (B,h,w), uint8 (value = code / 255) or the bits of u16 codes as int16 / uint16 (value = code / depth_max,
+    default 65535), code 0 a hole -> the mask-normalised bicubic x`scale` (bicubic_upsample_masked) -> back onto the
+    code grid -> tdt, as (B,1,h*scale,w*scale).  Bit for bit what train.synthesize(degrade_holes=True) builds from the same
+    low-resolution values."""
+    return _lr_codes("codes_to_input", "codon_lr_codes_to_input", "lr_codes_to_input", codes, scale, depth_max, tdt)
+
+
+def _lr_codes(who: str, entry: str, label: str, codes, scale, depth_max, tdt=None):
+    """The one body of the two: the hole-aware bicubic x`scale` of a code plane through `entry` -- codes of the argument's dtype
+    and leading shape, or with tdt the (B,1,H,W) input of that dtype"""
+    p = code_planes(who, codes, depth_max)
     if scale not in (4, 8, 16):
         raise ValueError(f"{who}: scale {scale!r} (4, 8 or 16)")
-    dev = ops._dev(src)
-    lut, top = code_table(bits, top, dev)
-    wt = _on_device(("up", scale), lambda: phase_weights(scale), dev)
-    out = torch.empty((*src.shape[:-2], h * scale, w * scale), dtype=src.dtype, device=dev)
-    P_ = C.c_void_p
-    with ops._on(dev):
-        L.check(L.load().codon_lr_codes_upsample(B, h, w, scale, P_(src.data_ptr()), bits, P_(lut.data_ptr()), top, P_(wt.data_ptr()),
-                                                 P_(out.data_ptr()), ops._stream(dev)), who)
+    if tdt is not None and tdt not in ops.DTYPE_CODE:
+        raise ValueError(f"{who}: dtype {tdt!r} (float32, float16 or bfloat16)")
+    dev = p.dev
+    lut, top = code_table(p.bits, p.top, dev)
+    wt = on_device(("up", scale), lambda: phase_weights(scale), dev)
+    H, W = p.h * scale, p.w * scale
+    out = p.out(H, W) if tdt is None else torch.empty((p.B, 1, H, W), dtype=tdt, device=dev)
+    with ops._on(dev):                                # addresses as ints: ctypes takes them for a void*
+        L.check(getattr(L.load(), entry)(p.B, p.h, p.w, scale, p.ptr, p.bits, lut.data_ptr(), top, wt.data_ptr(), out.data_ptr(),
+                                         *(() if tdt is None else (ops.DTYPE_CODE[tdt],)), ops._stream(dev)), label)
     return out
 
 
@@ -392,32 +341,30 @@ def code_range(codes: torch.Tensor) -> torch.Tensor:
     """(B, 2) int32 on the codes' device: per image (lo, hi), the smallest non-zero and the largest code of the plane, (0, 0)
     for a plane without a valid code.  codes: (h,w) or (B,h,w) uint8 codes, or the bits of u16 codes as
     int16 / uint16, code 0 a hole.  One launch, one workgroup per image; nothing is read back."""
-    src, B, h, w, bits, _ = _code_planes("code_range", codes, None)
-    dev = ops._dev(src)
-    lo_hi = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    p = code_planes("code_range", codes, None)
+    dev = p.dev
+    lo_hi = torch.empty((p.B, 2), dtype=torch.int32, device=dev)
     with ops._on(dev):
-        L.check(L.load().codon_code_range(B, h, w, C.c_void_p(src.data_ptr()), bits, C.c_void_p(lo_hi.data_ptr()),
-                                          ops._stream(dev)), "code_range")
+        L.check(L.load().codon_code_range(p.B, p.h, p.w, p.ptr, p.bits, lo_hi.data_ptr(), ops._stream(dev)), "code_range")
     return lo_hi
 
 
 def _map_codes(who: str, entry: str, codes, lo_hi, depth_max, out):
-    src, B, h, w, bits, top = _code_planes(who, codes, depth_max)
-    check_stretch_top(who, top)
-    dev = ops._dev(src)
+    p = code_planes(who, codes, depth_max)
+    check_stretch_top(who, p.top)
+    dev = p.dev
     if lo_hi is None:
-        lo_hi = code_range(src)
+        lo_hi = code_range(p.src)
     else:
         lo_hi = torch.as_tensor(lo_hi, dtype=torch.int32, device=dev).reshape(-1, 2).contiguous()
-        if lo_hi.shape[0] != B:
-            raise ValueError(f"{who}: {lo_hi.shape[0]} ranges for {B} images")
+        if lo_hi.shape[0] != p.B:
+            raise ValueError(f"{who}: {lo_hi.shape[0]} ranges for {p.B} images")
     if out is None:
-        out = torch.empty_like(src)
-    elif out.shape != codes.shape or out.dtype != codes.dtype or out.device != src.device or not out.is_contiguous():
+        out = p.out()
+    elif out.shape != codes.shape or out.dtype != codes.dtype or out.device != p.src.device or not out.is_contiguous():
         raise ValueError(f"{who}: out must be a contiguous tensor of the codes' shape, dtype and device")
     with ops._on(dev):
-        L.check(getattr(L.load(), entry)(B, h, w, C.c_void_p(src.data_ptr()), bits, top, C.c_void_p(lo_hi.data_ptr()),
-                                         C.c_void_p(out.data_ptr()), ops._stream(dev)), who)
+        L.check(getattr(L.load(), entry)(p.B, p.h, p.w, p.ptr, p.bits, p.top, lo_hi.data_ptr(), out.data_ptr(), ops._stream(dev)), who)
     return out, lo_hi
 
 

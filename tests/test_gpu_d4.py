@@ -216,7 +216,7 @@ def test_infer_cli_self_ensemble(tmp_path, capsys):
         return res
 
     hr = (lambda f, tdt: infer._load_host(dd, cd, None, f, tdt), lambda x, tdt: x, ["--input-depth", dd])
-    lr4 = (lambda f, tdt: infer._load_host_lr(lrd, cd, None, f, tdt, 4), lambda c, tdt: infer.codes_to_input(c, 4, tdt), ["--lr-depth", lrd])
+    lr4 = (lambda f, tdt: infer._load_lr(lrd, cd, None, f, tdt, 4)[:5], lambda c, tdt: infer.codes_to_input(c, 4, tdt), ["--lr-depth", lrd])
     for dt, (load, to_x, src) in [("f32", hr), ("f16", hr), ("f16", lr4)]:
         base = ["--scale", "4", "--input-color", cd, "--weights", ck, "--dtype", dt] + src
         tag = f"{dt}_{src[0].strip('-')}"

@@ -239,7 +239,7 @@ def test_inference_input_is_trainings_input(tmp_path, bits, depth_max, s, P):
     os.makedirs(lrd)
     (io.write_gray if bits == 8 else io.write_depth16)(os.path.join(lrd, "00.png"), codes.astype(np.uint8 if bits == 8 else np.uint16))
     for dt, tdt in TORCH_DT.items():
-        c, y, lab, H, W = infer._load_host_lr(lrd, cd, None, "00.png", tdt, s, bits, depth_max if bits == 16 else 65535)
+        c, y, lab, H, W = infer._load_lr(lrd, cd, None, "00.png", tdt, s, bits, depth_max if bits == 16 else 65535)[:5]
         assert (H, W) == (P, P) and lab is None and y.shape == (1, 1, P, P) and y.dtype == tdt
         got = infer.codes_to_input(c.cuda(), s, tdt, depth_max if bits == 16 else None)
         _same(_cast_bits(got), _cast_bits(x.to(tdt)), f"x{s} {bits}-bit {dt}")

@@ -233,7 +233,7 @@ def test_loop_equals_the_composition(tmp_path, net, bits, depth_max, fill):
     hand = tmp_path / "hand"
     os.makedirs(hand)
     for f in names:
-        codes, y, lab, h, w = infer._load_host_lr(lrd, cd, ld, f, torch.float32, 4, bits, dmax)
+        codes, y, lab, h, w = infer._load_lr(lrd, cd, ld, f, torch.float32, 4, bits, dmax)[:5]
         c = codes.cuda()
         c = fill_holes(c, dm) if fill else c
         s, r = stretch_codes(c, dm)
