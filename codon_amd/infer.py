@@ -3,14 +3,16 @@ for every image: read depth (already HR-sized) + guidance, forward, clip/*255/ui
 vs the label, SSIM vs the label; print per-image values and the means.  Everything numeric runs in HIP kernels
 (codon_amd.CODONNet, codon_amd.metrics); this file is I/O glue.
 
-Round 6: the loop is a PIPELINE.  One forward of a Middlebury image takes 2.3 ms; decoding its two PNGs, the float
-conversion, the upload, the download and the PNG encode take several times that on the host, and the reference's loop
-(test.py:109-145) does all of it serially per image.  Here
-  reader thread : decode image i+1 (PIL releases the GIL), /255, cast, pinned host tensors, upload on a SIDE stream
-  main thread   : forward + post-processing + metrics of image i on the caller's stream (waits for the upload's event)
+What is done with one image is written ONCE (_Plan: load -> enqueue -> settle, write) and the loop has two shapes.  One forward
+of a Middlebury image takes 2.3 ms; decoding its two PNGs, the float conversion, the upload, the download and the PNG encode take
+several times that on the host, and the reference's loop (test.py:109-145) does all of it serially per image.  By default the
+steps sit on codon_amd.pipeline.run_pipeline, a torch-free skeleton with CPU tests of its own:
+  reader threads: decode image i+1 (PIL releases the GIL), /255, cast, pinned host tensors, upload on a SIDE stream
+  main thread   : launches and downloads of image i on the caller's stream (waits for the upload's event), then the host
+                  arithmetic of image i-1, whose numbers have landed meanwhile
   writer thread : download of image i-1 has landed in pinned memory (event) -> PNG encode + write
-Same arithmetic per image in the same order: outputs are byte-identical to the serial loop (`--serial`, kept for the A/B
-and the test).
+A stage that fails -- the writer on a full disk, say -- raises in the caller; nothing hangs.  `--serial` is the same steps in turn
+on the calling thread, uploads synchronous, no threads, no side stream: byte-identical outputs and lines by construction.
 
 --lr-depth DIR instead of --input-depth: the depth files are LOW-RESOLUTION maps as a sensor writes them, code 0 a
 hole.  The reader uploads the codes and the main stream turns them into the network's input with one launch
@@ -20,9 +22,8 @@ from __future__ import annotations
 import argparse
 import math
 import os
-import queue
-import threading
 import time
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -30,6 +31,7 @@ import torch
 from . import CODONNet, CODONNet16, io, metrics
 from .codes import codes_tensor
 from .io import check_depth_max, list_pairs, read_depth_plane
+from .pipeline import run_pipeline
 from .prep import LrPrep, add_prep_args, prep_of
 from .upsample import (FILL_SIGMA, JBU_SIGMA_S, bicubic_upsample_codes, check_fill_sigma, check_jbu_sigma_s, codes_to_input,
                        joint_bilateral_upsample, unstretch_codes)
@@ -105,6 +107,148 @@ def _pinned_copy(t: torch.Tensor) -> torch.Tensor:
     return hp
 
 
+# What the depth format (depth_bits, depth_max, depth_unit) decides, chosen once: post_codes(the network's map) -> codes;
+# sqerr: (label, codes) -> int64[2] on the device; write(path, numpy codes); unit(codes) -> fp32 in [0, 1], what SSIM compares; the
+# printed RMSE and the report are in codes times rmse_scale; depth_max as the upsample functions take it (None for 8-bit)
+_Format = namedtuple("_Format", "post_codes sqerr write unit rmse_scale depth_max")
+
+
+def _format(depth_bits, depth_max, depth_unit):
+    if depth_bits == 16:
+        top = float(depth_max)
+        return _Format(lambda o: metrics.postprocess_u16(o, depth_max), metrics.masked_sqerr_u16_dev, io.write_depth16,
+                       lambda t: metrics.codes_to_float(t) / top, float(depth_unit), depth_max)
+    return _Format(metrics.postprocess_u8, metrics.masked_sqerr_dev, io.write_gray, lambda t: t.float() / 255, 1.0, None)
+
+
+def _checked(model, input_depth, input_color, label, files, depth_bits, depth_max, lr_depth, scale, self_ensemble, report,
+             fill_holes, normalize, fill_guided, fill_sigma, baseline, jbu_sigma_s, jbu_sigma_r):
+    """Every refusal of run_loop, in their order of precedence -> (the preparation's record, the two checked jbu sigmas, the
+    files: listed here, between the checks, where a missing directory has always been reported)."""
+    if (lr_depth is None) == (input_depth is None):
+        raise ValueError("run_loop: exactly one of input_depth and lr_depth")
+    if depth_bits not in (8, 16):
+        raise ValueError(f"run_loop: depth_bits {depth_bits!r} (8 or 16)")
+    if depth_bits == 16:
+        check_depth_max(depth_max)
+    prep = LrPrep.checked("run_loop", fill_holes, fill_guided, fill_sigma, normalize, lr=("lr_depth", lr_depth is not None),
+                          top=depth_max if depth_bits == 16 else 255)
+    if baseline is not None:
+        if baseline not in BASELINES:
+            raise ValueError(f"run_loop: baseline {baseline!r} ({' or '.join(BASELINES)})")
+        if lr_depth is None:
+            raise ValueError("run_loop: baseline needs lr_depth (a baseline upsamples low-resolution code planes)")
+        if self_ensemble:
+            raise ValueError("run_loop: baseline with self_ensemble (there is no network to ensemble)")
+        if baseline == "jbu":
+            jbu_sigma_s, jbu_sigma_r = check_jbu_sigma_s("run_loop", jbu_sigma_s), check_fill_sigma("run_loop", jbu_sigma_r)
+    if lr_depth is not None and scale not in (4, 8, 16):
+        raise ValueError(f"run_loop: lr_depth needs scale 4, 8 or 16 (got {scale!r})")
+    if model is None and baseline is None:
+        raise ValueError("run_loop: model is None without a baseline")
+    files = list_pairs(lr_depth or input_depth, input_color) if files is None else files
+    if report is not None and not label:
+        raise ValueError("run_loop: report needs label")
+    return prep, jbu_sigma_s, jbu_sigma_r, files
+
+
+# One image whose launches are enqueued: its name, the event recorded behind its downloads, and the pinned host buffers they land
+# in -- the output codes, int64[2] squared error and count, float64[1] SSIM, the report's words, the error map; None where there is none
+Pending = namedtuple("Pending", "f event codes acc ss words emap")
+
+
+def _download(t: torch.Tensor) -> torch.Tensor:
+    """A pinned host buffer that t is being copied into behind the launches enqueued so far."""
+    hp = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    hp.copy_(t, non_blocking=True)
+    return hp
+
+
+class _Plan:
+    """What is done with one image, each step written once: load -> enqueue -> settle, write.  The serial loop calls them in turn
+    on the calling thread; the pipelined loop hands the same four to pipeline.run_pipeline."""
+
+    def __init__(self, dev, fmt, load_host, codes_of, out_dir, emit, report):
+        """load_host(f) -> (x or codes, y, label or None, h, w, guidance codes or None) on the host; codes_of(x or codes, y,
+        guidance codes) -> the output codes on the device; report: run_loop's, or None."""
+        self.dev, self.fmt, self.load_host, self.codes_of, self.out_dir, self.emit = dev, fmt, load_host, codes_of, out_dir, emit
+        self.stream = torch.cuda.current_stream(dev)
+        self.rp_kw = self.err_dir = None
+        if report is not None:
+            self.rp_kw = {"thresholds": tuple(report.get("thresholds", ())), "edge_threshold": report.get("edge_threshold"),
+                          "edge_radius": report.get("edge_radius", 1)}
+            self.err_dir = report.get("error_maps")
+        self.reports = []
+        self.rm_sum = self.ss_sum = 0.0
+        self.n = 0
+
+    def load(self, f, up_s=None):
+        """Image f on the device -> (f, [x or codes, y, label or None, guidance codes or None], the upload's event, h, w, the
+        pinned sources).  up_s None: synchronous uploads on the current stream.  Else, for a reader thread: pinned buffers
+        filled by numpy, uploads on the side stream up_s with an event behind them; the pinned sources ride along until the
+        item is consumed."""
+        x, y, lab, h, w, g = self.load_host(f)
+        host = [x, y, lab, g]
+        if up_s is None:
+            return f, [t.to(self.dev) if t is not None else None for t in host], None, h, w, None
+        torch.cuda.set_device(self.dev)
+        host = [_pinned_copy(t) if t is not None else None for t in host]
+        with torch.cuda.stream(up_s):
+            devs = [t.to(self.dev, non_blocking=True) if t is not None else None for t in host]
+            ev = torch.cuda.Event()
+            ev.record(up_s)
+        return f, devs, ev, h, w, host
+
+    def enqueue(self, loaded):
+        """Every launch of one image, in order -- [preparation ->] forward -> post-processing -> squared error -> SSIM -> report
+        -- the downloads of what they give behind them, and one event behind those.  No host synchronisation."""
+        f, (x, y, lab, g), ev, h, w, _host = loaded
+        if ev is not None:
+            self.stream.wait_event(ev)
+            for t in (x, y, lab, g):
+                if t is not None:
+                    t.record_stream(self.stream)            # allocated on the upload stream, consumed on this one
+        fmt = self.fmt
+        codes = self.codes_of(x, y, g)
+        acc = ss = words = emap = None
+        if lab is not None:                                 # metrics stay on the device until settle()
+            acc = fmt.sqerr(lab, codes)
+            ss = metrics.ssim_dev(fmt.unit(lab[:h, :w]), fmt.unit(codes))
+            acc, ss = _download(acc), _download(ss)
+            if self.rp_kw is not None:                      # sixteen more words (and the error map) behind the same kernels
+                r_ = metrics.depth_errors(lab, codes, error_map=bool(self.err_dir), **self.rp_kw)
+                words = _download(r_[0][0] if self.err_dir else r_[0])
+                emap = _download(r_[1]) if self.err_dir else None
+        codes = _download(codes)
+        event = torch.cuda.Event()
+        event.record(self.stream)
+        return Pending(f, event, codes, acc, ss, words, emap)
+
+    def settle(self, p):
+        """The host arithmetic of an enqueued image (metrics.masked_rmse's and metrics.ssim's), its line and its report."""
+        line = p.f
+        if p.acc is not None:
+            p.event.synchronize()
+            s_, c_ = (int(v) for v in p.acc)
+            rm, ss = math.sqrt(s_ / c_) * self.fmt.rmse_scale, float(p.ss.item())
+            self.rm_sum += rm
+            self.ss_sum += ss
+            line += f" {rm} {ss}"
+            if p.words is not None:
+                rep = metrics.depth_report(p.words, unit=self.fmt.rmse_scale, thresholds=self.rp_kw["thresholds"])
+                self.reports.append({"file": p.f, **rep})
+                line += " " + metrics.report_tokens(rep)
+        self.n += 1
+        self.emit(line)
+
+    def write(self, p):
+        """The output file and the error-map file of an enqueued image, once its downloads have landed."""
+        for d, t in ((self.out_dir, p.codes), (self.err_dir, p.emap)):
+            if d and t is not None:
+                p.event.synchronize()
+                self.fmt.write(os.path.join(d, p.f), t.numpy())
+
+
 def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None,
              depth_bits=8, depth_max=65535, depth_unit=1.0, lr_depth=None, scale=None, self_ensemble=False, report=None, fill_holes=False,
              normalize=False, fill_guided=False, fill_sigma=FILL_SIGMA, baseline=None, jbu_sigma_s=JBU_SIGMA_S, jbu_sigma_r=FILL_SIGMA):
@@ -132,40 +276,13 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     upsample.joint_bilateral_upsample under jbu_sigma_s (low-resolution pixels) and jbu_sigma_r (guidance codes), for which the
     loader hands over the guidance codes as for fill_guided; what comes out already is codes, so post-processing is skipped, and
     unstretching, metrics, report, error maps and files are the network path's.  tdt then only types the guidance nothing reads."""
-    if (lr_depth is None) == (input_depth is None):
-        raise ValueError("run_loop: exactly one of input_depth and lr_depth")
-    if depth_bits not in (8, 16):
-        raise ValueError(f"run_loop: depth_bits {depth_bits!r} (8 or 16)")
-    deep = depth_bits == 16
-    if deep:
-        check_depth_max(depth_max)
-    prep = LrPrep.checked("run_loop", fill_holes, fill_guided, fill_sigma, normalize, lr=("lr_depth", lr_depth is not None),
-                          top=depth_max if deep else 255)
-    if baseline is not None:
-        if baseline not in BASELINES:
-            raise ValueError(f"run_loop: baseline {baseline!r} ({' or '.join(BASELINES)})")
-        if lr_depth is None:
-            raise ValueError("run_loop: baseline needs lr_depth (a baseline upsamples low-resolution code planes)")
-        if self_ensemble:
-            raise ValueError("run_loop: baseline with self_ensemble (there is no network to ensemble)")
-        if baseline == "jbu":
-            jbu_sigma_s, jbu_sigma_r = check_jbu_sigma_s("run_loop", jbu_sigma_s), check_fill_sigma("run_loop", jbu_sigma_r)
-    if lr_depth is not None and scale not in (4, 8, 16):
-        raise ValueError(f"run_loop: lr_depth needs scale 4, 8 or 16 (got {scale!r})")
-    if model is None and baseline is None:
-        raise ValueError("run_loop: model is None without a baseline")
-    files = list_pairs(lr_depth or input_depth, input_color) if files is None else files
-    if deep:
-        post_codes = lambda o: metrics.postprocess_u16(o, depth_max)                             # noqa: E731
-        sqerr, write, top = metrics.masked_sqerr_u16_dev, io.write_depth16, float(depth_max)
-        unit = lambda t: metrics.codes_to_float(t) / top                                         # noqa: E731
-    else:
-        post_codes, sqerr, write = metrics.postprocess_u8, metrics.masked_sqerr_dev, io.write_gray
-        unit = lambda t: t.float() / 255                                                         # noqa: E731
-    scale_rm = float(depth_unit) if deep else None
-    dm = depth_max if deep else None                    # as the upsample functions take it
+    prep, jbu_sigma_s, jbu_sigma_r, files = _checked(model, input_depth, input_color, label, files, depth_bits, depth_max, lr_depth,
+                                                     scale, self_ensemble, report, fill_holes, normalize, fill_guided, fill_sigma,
+                                                     baseline, jbu_sigma_s, jbu_sigma_r)
+    fmt = _format(depth_bits, depth_max, depth_unit)
+    dm = fmt.depth_max
     # every load gives (x, y, label or None, h, w, guidance codes or None), guidance codes with fill_guided only; to_x(x or codes,
-    # guidance codes) gives (the depth input, the range it was stretched by or None), and that range rides to post
+    # guidance codes) gives (the depth input, the range it was stretched by or None), and that range rides to the post-processing
     if lr_depth is not None:
         load = lambda f: _load_lr(lr_depth, input_color, label, f, tdt, scale, depth_bits, depth_max,            # noqa: E731
                                   with_guide=prep.fill_guided or baseline == "jbu")
@@ -176,197 +293,48 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
                 return codes_to_input(c, scale, tdt, dm), lo_hi
             up = (bicubic_upsample_codes(c, scale, dm) if baseline == "bicubic" else
                   joint_bilateral_upsample(c, g, scale, jbu_sigma_s, jbu_sigma_r, dm))
-            return (up.view(torch.uint16) if deep else up), lo_hi
+            return (up.view(torch.uint16) if depth_bits == 16 else up), lo_hi
     else:
         load = lambda f: (*_load_host(input_depth, input_color, label, f, tdt, depth_bits, depth_max), None)    # noqa: E731
         to_x = lambda x, g: (x, None)                                                                          # noqa: E731
-
-    def post(o, lo_hi):
-        o = post_codes(o) if baseline is None else o    # a baseline's output already is codes
-        return o if lo_hi is None else unstretch_codes(o, lo_hi, dm)
-
     if baseline is not None:
-        forward = lambda x, y: x[None, None]                                                                   # noqa: E731
+        forward = lambda x, y: x                        # a baseline's output already is codes              # noqa: E731
     elif self_ensemble:
         from .ensemble import self_ensemble as _ensemble
-        forward = lambda x, y: _ensemble(model, x, y)                                                          # noqa: E731
+        forward = lambda x, y: fmt.post_codes(_ensemble(model, x, y)[0, 0])                                    # noqa: E731
     else:
-        forward = model
-    if report is not None:
-        if not label:
-            raise ValueError("run_loop: report needs label")
-        rp_kw = {"thresholds": tuple(report.get("thresholds", ())), "edge_threshold": report.get("edge_threshold"),
-                 "edge_radius": report.get("edge_radius", 1)}
-        err_dir = report.get("error_maps")
-        reports = []
+        forward = lambda x, y: fmt.post_codes(model(x, y)[0, 0])                                               # noqa: E731
 
-        def errors(lab, out_u8):
-            """-> (the image's sixteen words on the device, its error map or None)"""
-            r_ = metrics.depth_errors(lab, out_u8, error_map=bool(err_dir), **rp_kw)
-            return (r_[0][0], r_[1]) if err_dir else (r_[0], None)
+    def codes_of(x, y, g):
+        with torch.no_grad():
+            x, lo_hi = to_x(x, g)
+            o = forward(x, y)
+        return o if lo_hi is None else unstretch_codes(o, lo_hi, dm)
 
-        def tokens(f, words):
-            rep = metrics.depth_report(words, unit=1.0 if scale_rm is None else scale_rm, thresholds=rp_kw["thresholds"])
-            reports.append({"file": f, **rep})
-            return " " + metrics.report_tokens(rep)
+    plan = _Plan(dev, fmt, load, codes_of, out_dir, emit, report)
     t0 = time.perf_counter()
-    rm_sum = ss_sum = 0.0
-    n = 0
-
-    def finish(f, out, lo_hi, lab, h, w):
-        nonlocal rm_sum, ss_sum, n
-        out_u8 = post(out[0, 0], lo_hi)
-        line = f
-        if lab is not None:
-            s_, c_ = (int(v) for v in sqerr(lab, out_u8).cpu())
-            rm = math.sqrt(s_ / c_) if scale_rm is None else math.sqrt(s_ / c_) * scale_rm
-            ss = metrics.ssim(unit(lab[:h, :w]), unit(out_u8))
-            rm_sum += rm; ss_sum += ss
-            line += f" {rm} {ss}"
-            if report is not None:
-                words, emap = errors(lab, out_u8)
-                line += tokens(f, words.cpu())
-                if err_dir:
-                    write(os.path.join(err_dir, f), emap.cpu().numpy())
-        n += 1
-        return out_u8, line
-
-    if not pipelined:
-        for f in files:
-            x, y, lab, h, w, g = load(f)
-            with torch.no_grad():
-                x, lo_hi = to_x(x.to(dev), g.to(dev) if g is not None else None)
-                out = forward(x, y.to(dev))
-            out_u8, line = finish(f, out, lo_hi, lab.to(dev) if lab is not None else None, h, w)
-            if out_dir:
-                write(os.path.join(out_dir, f), out_u8.cpu().numpy())
-            emit(line)
-    else:
-        main_s = torch.cuda.current_stream(dev)
-        up_s = torch.cuda.Stream(device=dev)
+    if pipelined:
         # READERS reader threads take every READERS-th image each (decoding two PNGs is the longest stage: 3.1 ms against a
-        # 2.3 ms forward); the main thread takes their queues in turn, so images are consumed in order
-        q_ins = [queue.Queue(maxsize=2) for _ in range(READERS)]
-        q_out: "queue.Queue" = queue.Queue(maxsize=4)
-        errs = []
-        stop = threading.Event()
+        # 2.3 ms forward); uploads go on one side stream
+        up_s = torch.cuda.Stream(device=dev)
 
-        def reader(k):
-            q_in = q_ins[k]
-            try:
-                torch.cuda.set_device(dev)
-                for f in files[k::READERS]:
-                    if stop.is_set():
-                        break
-                    x, y, lab, h, w, g = load(f)
-                    host = [_pinned_copy(t) if t is not None else None for t in (x, y, lab, g)]
-                    with torch.cuda.stream(up_s):             # devs: (x, y, label or None, guidance codes or None)
-                        devs = [t.to(dev, non_blocking=True) if t is not None else None for t in host]
-                        ev = torch.cuda.Event()
-                        ev.record(up_s)
-                    q_in.put((f, devs, host, ev, h, w))          # `host` rides along: pinned sources stay alive until consumed
-            except BaseException as e:      # noqa: BLE001 -- re-raised in the main thread
-                errs.append(e)
-            finally:
-                q_in.put(None)
+        def step(loaded):
+            p = plan.enqueue(loaded)
+            return p, p
 
-        def writer():
-            try:
-                while True:
-                    item = q_out.get()
-                    if item is None:
-                        return
-                    f, host_u8, ev, *host_err = item
-                    ev.synchronize()                               # the download of this image has landed
-                    if out_dir:
-                        write(os.path.join(out_dir, f), host_u8.numpy())
-                    if host_err:
-                        write(os.path.join(err_dir, f), host_err[0].numpy())
-            except BaseException as e:      # noqa: BLE001
-                errs.append(e)
-
-        def settle(pend):
-            """Metrics of an image whose launches were enqueued one image ago: its three numbers have been downloaded behind
-            its kernels; the same host arithmetic as metrics.masked_rmse / metrics.ssim."""
-            nonlocal rm_sum, ss_sum, n
-            f, h_acc, h_ss, ev, *h_rep = pend
-            line = f
-            if h_acc is not None:
-                ev.synchronize()
-                s_, c_ = (int(v) for v in h_acc)
-                rm, ss = math.sqrt(s_ / c_) if scale_rm is None else math.sqrt(s_ / c_) * scale_rm, float(h_ss.item())
-                rm_sum += rm; ss_sum += ss
-                line += f" {rm} {ss}"
-                if h_rep:
-                    line += tokens(f, h_rep[0])
-            n += 1
-            emit(line)
-
-        trs = [threading.Thread(target=reader, args=(k,), name=f"codon_infer_reader{k}") for k in range(READERS)]
-        tw = threading.Thread(target=writer, name="codon_infer_writer")
-        for t_ in trs + [tw]:
-            t_.start()
-        pending = None
-        try:
-            for i in range(len(files)):
-                item = q_ins[i % READERS].get()
-                if item is None:                                   # that reader failed: its error is re-raised below
-                    break
-                f, devs, _host, ev, h, w = item
-                main_s.wait_event(ev)
-                for t in devs:
-                    if t is not None:
-                        t.record_stream(main_s)                    # allocated on the upload stream, consumed on this one
-                with torch.no_grad():
-                    x, lo_hi = to_x(devs[0], devs[3])
-                    out = forward(x, devs[1])
-                out_u8 = post(out[0, 0], lo_hi)
-                h_acc = h_ss = None
-                h_rep, host_err = [], []
-                if devs[2] is not None:                            # metrics stay on the device; read back one image later
-                    lab = devs[2]
-                    acc = sqerr(lab, out_u8)
-                    ssv = metrics.ssim_dev(unit(lab[:h, :w]), unit(out_u8))
-                    h_acc = torch.empty(2, dtype=torch.int64, pin_memory=True)
-                    h_ss = torch.empty(1, dtype=torch.float64, pin_memory=True)
-                    h_acc.copy_(acc, non_blocking=True)
-                    h_ss.copy_(ssv, non_blocking=True)
-                    if report is not None:                         # sixteen more words (and the error map) behind the same kernels
-                        words, emap = errors(lab, out_u8)
-                        h_rep = [torch.empty(metrics.EVAL_WORDS, dtype=torch.int64, pin_memory=True)]
-                        h_rep[0].copy_(words, non_blocking=True)
-                        if emap is not None:
-                            host_err = [torch.empty(emap.shape, dtype=emap.dtype, pin_memory=True)]
-                            host_err[0].copy_(emap, non_blocking=True)
-                host_u8 = torch.empty(out_u8.shape, dtype=out_u8.dtype, pin_memory=True)
-                host_u8.copy_(out_u8, non_blocking=True)
-                dv = torch.cuda.Event()
-                dv.record(main_s)
-                q_out.put((f, host_u8, dv, *host_err))
-                if pending is not None:
-                    settle(pending)                                # image i-1, while image i runs
-                pending = (f, h_acc, h_ss, dv, *h_rep)
-            if pending is not None:
-                settle(pending)
-        finally:
-            q_out.put(None)
-            stop.set()
-            for t_, q_ in zip(trs, q_ins):                         # error paths: a reader may be blocked on a full queue
-                while t_.is_alive():
-                    try:
-                        q_.get_nowait()
-                    except queue.Empty:
-                        pass
-                    t_.join(0.02)
-            tw.join()
-        if errs:
-            raise errs[0]
+        run_pipeline(files, lambda f: plan.load(f, up_s), step, plan.settle, plan.write, READERS, "codon_infer")
+    else:
+        for f in files:
+            p = plan.enqueue(plan.load(f))
+            plan.write(p)
+            plan.settle(p)
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
-    res = {"n": n, "rmse_mean": rm_sum / n if (label and n) else None, "ssim_mean": ss_sum / n if (label and n) else None,
+    n = plan.n
+    res = {"n": n, "rmse_mean": plan.rm_sum / n if (label and n) else None, "ssim_mean": plan.ss_sum / n if (label and n) else None,
            "seconds": dt, "images_per_s": n / dt if dt > 0 else 0.0}
     if report is not None:
-        res.update(reports=reports, report_means=metrics.report_means(reports))
+        res.update(reports=plan.reports, report_means=metrics.report_means(plan.reports))
     return res
 
 

@@ -41,8 +41,8 @@ class Stub:
         return self
 
 
-def write_set(root, bits, top):
-    """Two pairs of 40 x 48 with 10 x 12 low-resolution maps that carry holes, and the depth maps once more with holes of their
+def write_set(root, bits, top, n=2):
+    """n (two) pairs of 40 x 48 with 10 x 12 low-resolution maps that carry holes, and the depth maps once more with holes of their
     own: [depth dir, color dir, lr dir, holey depth dir]"""
     from codon_amd import io
     g = np.random.default_rng(1)
@@ -51,10 +51,10 @@ def write_set(root, bits, top):
         os.makedirs(d)
     write = io.write_gray if bits == 8 else io.write_depth16
     dt = np.uint8 if bits == 8 else np.uint16
-    for i in range(2):
+    for i in range(n):
         lr = g.integers(1, top + 1, size=(10, 12))
         lr[g.random((10, 12)) < 0.25] = 0
-        lr[3 + i:6, 2:5 + i] = 0                                      # and a hole wider than one pixel
+        lr[3 + i % 2:6, 2:5 + i % 2] = 0                              # and a hole wider than one pixel
         write(os.path.join(dirs[0], f"{i:02d}.png"), g.integers(1, top + 1, size=(40, 48)).astype(dt))
         io.write_gray(os.path.join(dirs[1], f"{i:02d}.png"), g.integers(0, 256, size=(40, 48)).astype(np.uint8))
         write(os.path.join(dirs[2], f"{i:02d}.png"), lr.astype(dt))
