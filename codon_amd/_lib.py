@@ -194,6 +194,8 @@ SIGNATURES = {
     "codon_d4_views": (C.c_int, [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     "codon_d4_merge": (C.c_int, [_I, _I, _I, _P, _P, _I, _P, _P]),
     "codon_depth_errors": (C.c_int, [C.POINTER(DepthErrorsDesc), _P, _P, _P, _P, _P, _P]),
+    "codon_normal_errors": (C.c_int, [_I, _I, _I, _P, _I, _I, C.c_int64, C.c_int64, _P, _I, _I, _P, _P, C.POINTER(C.c_int32), _P, _P,
+                                      _I, _I, _I, _P, _P, _P]),
     "codon_fill_holes_workspace_bytes": (_S, [_I, _I]),
     "codon_fill_holes": (C.c_int, [_I, _I, _I, _P, _I, _P, _I, _P, _P, _S, _P]),
     "codon_fill_guided_workspace_bytes": (_S, [_I, _I]),

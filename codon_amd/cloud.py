@@ -15,8 +15,8 @@ pixel without a tangent on either axis has no normal (three zeros) and is still 
 row-major order of the pixels -- count, scan, emit: three launches -- and the file's body is the device's bytes; the only host
 synchronisation is the read of the counts, which sizes the download.  The four defaults (radius, tolerance, tolerance-rel, unit)
 are untuned.  Not handled: triangles (a mesh); a distorted camera (undistort first); ranges along the ray (`register --radial`
-converts them); normals smoothed over more than two pixels per axis; a normal-angle error in `infer --report`; any format other
-than PLY."""
+converts them); normals smoothed over more than two pixels per axis; any format other than PLY.  (The normal-angle error
+between a label's normals and an output's is `infer --report --report-normals`, DESIGN 12.20: the same cd_normal.)"""
 from __future__ import annotations
 
 import argparse

@@ -112,14 +112,22 @@ CODON_FL_HD void cd_p8(unsigned k, int x, int y, int* p) {
   p[2] = (int)(k << 8);
 }
 
+// A loader gives the code at element `at` = i a.w + j of the a.h x a.w plane the tangents are formed on: CdPlane reads a plane of
+// codes in global memory (cloud's bodies); normal_tile.h passes a loader over a tile in LDS
+template <int FMT>
+struct CdPlane {
+  const void* in;
+  CODON_FL_HD unsigned operator()(long at) const { return (unsigned)fl_load<FMT>(in, at, 0); }
+};
+
 // the tangent at pixel (i, j), code k, P8 `own`, along (di, dj): false if neither the pixel ahead nor the one behind counts;
 // |d| < 2^27
-template <int FMT>
-CODON_FL_HD bool cd_tangent(const void* in, const CdArgs& a, const int* rx, const int* ry, int i, int j, int di, int dj, unsigned k,
+template <class LD>
+CODON_FL_HD bool cd_tangent(const LD& ld, const CdArgs& a, const int* rx, const int* ry, int i, int j, int di, int dj, unsigned k,
                             const int* own, int* d) {
   const int ia = i + di, ja = j + dj, ib = i - di, jb = j - dj;
-  const unsigned ka = ia < a.h && ja < a.w ? (unsigned)fl_load<FMT>(in, (long)ia * a.w + ja, 0) : 0u;
-  const unsigned kb = ib >= 0 && jb >= 0 ? (unsigned)fl_load<FMT>(in, (long)ib * a.w + jb, 0) : 0u;
+  const unsigned ka = ia < a.h && ja < a.w ? ld((long)ia * a.w + ja) : 0u;
+  const unsigned kb = ib >= 0 && jb >= 0 ? ld((long)ib * a.w + jb) : 0u;
   const bool fa = cl_linked(k, ka, a.tol_abs, a.tol_rel), fb = cl_linked(k, kb, a.tol_abs, a.tol_rel);       // a hole links to nothing
   if (!fa && !fb) return false;
   int hi[3] = {own[0], own[1], own[2]}, lo[3] = {own[0], own[1], own[2]};
@@ -130,13 +138,13 @@ CODON_FL_HD bool cd_tangent(const void* in, const CdArgs& a, const int* rx, cons
 }
 
 // the normal of pixel (i, j), code k: N in Q14; false: none, and N is three zeros.  Every product is of two ints, 32 x 32 -> 64
-template <int FMT>
-CODON_FL_HD bool cd_normal(const void* in, const CdArgs& a, const int* rx, const int* ry, int i, int j, unsigned k, int* N) {
+template <class LD>
+CODON_FL_HD bool cd_normal(const LD& ld, const CdArgs& a, const int* rx, const int* ry, int i, int j, unsigned k, int* N) {
   N[0] = N[1] = N[2] = 0;
   int own[3], du[3], dv[3];
   cd_p8(k, rx[j], ry[i], own);
-  if (!cd_tangent<FMT>(in, a, rx, ry, i, j, 0, a.radius, k, own, du)) return false;
-  if (!cd_tangent<FMT>(in, a, rx, ry, i, j, a.radius, 0, k, own, dv)) return false;
+  if (!cd_tangent(ld, a, rx, ry, i, j, 0, a.radius, k, own, du)) return false;
+  if (!cd_tangent(ld, a, rx, ry, i, j, a.radius, 0, k, own, dv)) return false;
   const long long n[3] = {(long long)du[1] * dv[2] - (long long)du[2] * dv[1], (long long)du[2] * dv[0] - (long long)du[0] * dv[2],
                           (long long)du[0] * dv[1] - (long long)du[1] * dv[0]};
   unsigned long long mx = 0;
@@ -186,7 +194,7 @@ CODON_FL_HD unsigned cd_record(const void* in, const CdArgs& a, const int* rx, c
   unsigned has = 0;
   if (cd_rec_normals(REC)) {
     int N[3];
-    has = cd_normal<FMT>(in, a, rx, ry, i, j, k, N);
+    has = cd_normal(CdPlane<FMT>{in}, a, rx, ry, i, j, k, N);
     for (int c = 0; c < 3; ++c) cd_put32(p + 12 + 4 * c, cd_bits((float)N[c] * (1.0f / CD_ONE)), word);
     if (nmap && has)
       for (int c = 0; c < 3; ++c) nmap[at * 3 + c] = (unsigned char)(128 + ((127 * N[c] + CD_ONE / 2) >> 14));

@@ -14,6 +14,7 @@
 #include "register_tile.h"
 #include "clean_tile.h"
 #include "cloud_tile.h"
+#include "normal_tile.h"
 #include "sensor_pixel.h"
 #include "stretch_tile.h"
 #include "train_record.h"
@@ -1127,6 +1128,37 @@ int codon_depth_errors(const codon_depth_errors_desc* desc, const void* label, c
   a.r = a.edge ? desc->edge_radius : 0;
   return depth_errors(a, desc->batch, desc->bits, label, out, error_map, region_map, (unsigned long long*)acc,
                       (hipStream_t)stream);
+}
+
+// ---- surface-normal angle error -----------------------------------------------------------------------------------
+int codon_normal_errors(int32_t batch, int32_t height, int32_t width, const void* label, int32_t label_height, int32_t label_width,
+                        int64_t label_row_stride, int64_t label_image_stride, const void* out, int32_t fmt, int32_t top,
+                        const int32_t* rx, const int32_t* ry, const int32_t* ray_span, const int32_t* cos_table,
+                        const int32_t* sin_table, int32_t radius, int32_t tol_abs, int32_t tol_rel_q16, uint32_t* words,
+                        uint16_t* angle_map, codon_stream_t stream) {
+  CODON_REQUIRE(label && out && rx && ry && ray_span && cos_table && sin_table && words, CODON_ERR_BAD_ARG,
+                "normal_errors: null pointer");
+  const char* who = "normal_errors";
+  if (const int st = check_planes(who, fmt, batch, height, width, NE_MAX_SIDE, top)) return st;
+  CODON_REQUIRE(label_height >= height && label_width >= width, CODON_ERR_BAD_ARG,
+                "normal_errors: a %dx%d label is smaller than the %dx%d output", label_height, label_width, height, width);
+  CODON_REQUIRE(label_row_stride >= label_width && label_image_stride >= 0 &&
+                    (batch == 1 || label_image_stride >= label_row_stride * (label_height - 1) + label_width),
+                CODON_ERR_BAD_ARG, "normal_errors: label strides %lld (row), %lld (image) for %dx%d planes",
+                (long long)label_row_stride, (long long)label_image_stride, label_height, label_width);
+  CODON_REQUIRE(radius >= 1 && radius <= NE_RMAX, CODON_ERR_BAD_ARG, "normal_errors: radius %d (1..%d)", radius, NE_RMAX);
+  if (const int st = check_link_tolerances(who, tol_abs, top, tol_rel_q16, CD_MAX_REL)) return st;
+  for (int q = 0; q < 4; ++q)
+    CODON_REQUIRE(ray_span[q] > -CD_RAY_LIMIT && ray_span[q] < CD_RAY_LIMIT, CODON_ERR_BAD_ARG,
+                  "normal_errors: ray %d of the span is %d (Q20, below 2^22 in magnitude)", q, ray_span[q]);
+  const bool planes_ok = (((uintptr_t)label | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
+  const bool words_ok = (((uintptr_t)rx | (uintptr_t)ry | (uintptr_t)cos_table | (uintptr_t)sin_table | (uintptr_t)words) & 3) == 0 &&
+                        ((uintptr_t)angle_map & 1) == 0;
+  CODON_REQUIRE(planes_ok && words_ok, CODON_ERR_BAD_ARG, "normal_errors: unaligned plane, table, words or map");
+  NeArgs a;
+  a.H = height, a.W = width, a.label_row = (long)label_row_stride, a.label_image = (long)label_image_stride;
+  a.radius = radius, a.tol_abs = (unsigned)(radius * tol_abs), a.tol_rel = (unsigned)tol_rel_q16;
+  return normal_errors(a, batch, fmt, label, out, rx, ry, cos_table, sin_table, words, angle_map, (hipStream_t)stream);
 }
 
 // ---- pull-push hole filling -----------------------------------------------------------------------------------

@@ -8,6 +8,7 @@ namespace codon {
 
 struct SensorArgs;   // sensor_pixel.h
 struct EvalArgs;     // eval_tile.h
+struct NeArgs;       // normal_tile.h
 
 // GB operands of conv1x1_bwd_16 (see WgradC8Params in conv_wgrad_c8.hip); a null pointer = plain codon_conv1x1_bwd
 struct Conv1x1GateBwd {
@@ -161,6 +162,10 @@ int d4_merge(int B, int H, int W, const void* upright, const void* transposed, i
 // eval.hip
 int depth_errors(const EvalArgs& a, int B, int bits, const void* label, const void* out, void* err, unsigned char* region,
                  unsigned long long* acc, hipStream_t stream);
+
+// normal_errors.hip; rx (W), ry (H), ctab and stab (1440 each): int32 on the device; words: (B, 1448) u32; amap: null or (B, H, W) u16
+int normal_errors(const NeArgs& a, int B, int fmt, const void* label, const void* out, const int* rx, const int* ry, const int* ctab,
+                  const int* stab, unsigned* words, unsigned short* amap, hipStream_t stream);
 
 // fill_holes.hip
 size_t fill_holes_workspace_bytes(int h, int w);

@@ -12,12 +12,13 @@
 //             array.  Hence: WG_EACH takes one statement or a braced block, and never stands before an `else`;
 //             atomic_min / atomic_add are the device's atomics on global memory, results not returned; atomic_min_old is the
 //             same minimum and RETURNS what the word held, load_relaxed a relaxed load at agent scope (served by L2, never a
-//             stale L1 line): the pair a lock-free union-find needs (clean_tile.h)
+//             stale L1 line): the pair a lock-free union-find needs (clean_tile.h); lds_add is the add on a word
+//             of an LDS array (normal_tile.h's histogram)
 //   WgHost    WG_EACH runs tid over all threads, forwards or (reverse) backwards, so that a phase that reads what another thread
 //             of the SAME phase writes gives different bytes in the two orders; sync() does nothing; Regs<T, N> is one
 //             separately allocated row of exactly N elements per thread: a thread that writes past its registers is a report;
-//             atomic_min / atomic_add / atomic_min_old are a plain minimum and a plain add, load_relaxed a plain load (one
-//             thread runs at a time)
+//             atomic_min / atomic_add / lds_add / atomic_min_old are a plain minimum and a plain add, load_relaxed a plain load
+//             (one thread runs at a time)
 #pragma once
 
 #if defined(__HIPCC__)
@@ -37,6 +38,7 @@ struct WgDevice {
   __device__ __forceinline__ void sync() const { __syncthreads(); }
   __device__ __forceinline__ void atomic_min(unsigned* p, unsigned v) const { atomicMin(p, v); }
   __device__ __forceinline__ void atomic_add(unsigned* p, unsigned v) const { atomicAdd(p, v); }
+  __device__ __forceinline__ void lds_add(unsigned* p, unsigned v) const { atomicAdd(p, v); }
   __device__ __forceinline__ unsigned atomic_min_old(unsigned* p, unsigned v) const { return atomicMin(p, v); }
   __device__ __forceinline__ unsigned load_relaxed(const unsigned* p) const {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -77,6 +79,7 @@ struct WgHost {
   void sync() const {}
   void atomic_min(unsigned* p, unsigned v) const { *p = v < *p ? v : *p; }
   void atomic_add(unsigned* p, unsigned v) const { *p += v; }
+  void lds_add(unsigned* p, unsigned v) const { *p += v; }
   unsigned atomic_min_old(unsigned* p, unsigned v) const {
     const unsigned old = *p;
     *p = v < old ? v : old;

@@ -153,8 +153,15 @@ def _checked(model, input_depth, input_color, label, files, depth_bits, depth_ma
 
 
 # One image whose launches are enqueued: its name, the event recorded behind its downloads, and the pinned host buffers they land
-# in -- the output codes, int64[2] squared error and count, float64[1] SSIM, the report's words, the error map; None where there is none
-Pending = namedtuple("Pending", "f event codes acc ss words emap")
+# in -- the output codes, int64[2] squared error and count, float64[1] SSIM, the report's words, the error map, the normal report's
+# words and its angle map; None where there is none
+Pending = namedtuple("Pending", "f event codes acc ss words emap nwords nmap", defaults=(None, None))
+
+
+def _write_angle_map(path, a):
+    """An angle map of metrics.normal_errors as an 8-bit PNG: min(254, a // 8) degrees, 255 where the pixel is not compared"""
+    a = np.asarray(a)
+    io.write_gray(path, np.where(a == metrics.NORMAL_NONE, 255, np.minimum(254, a // 8)).astype(np.uint8))
 
 
 def _download(t: torch.Tensor) -> torch.Tensor:
@@ -173,11 +180,17 @@ class _Plan:
         guidance codes) -> the output codes on the device; report: run_loop's, or None."""
         self.dev, self.fmt, self.load_host, self.codes_of, self.out_dir, self.emit = dev, fmt, load_host, codes_of, out_dir, emit
         self.stream = torch.cuda.current_stream(dev)
-        self.rp_kw = self.err_dir = None
+        self.rp_kw = self.err_dir = self.nm_kw = self.nm_dir = None
         if report is not None:
             self.rp_kw = {"thresholds": tuple(report.get("thresholds", ())), "edge_threshold": report.get("edge_threshold"),
                           "edge_radius": report.get("edge_radius", 1)}
             self.err_dir = report.get("error_maps")
+            nm = report.get("normals")
+            if nm is not None:                              # the normal report (DESIGN 12.20): one more launch behind depth_errors
+                self.nm_kw = {"camera": nm["camera"], "depth_max": fmt.depth_max,
+                              **{k: nm[k] for k in ("radius", "tolerance", "tolerance_rel") if k in nm}}
+                self.nm_thresholds = metrics.normal_thresholds(nm.get("thresholds", metrics.NORMAL_THRESHOLDS), "run_loop")
+                self.nm_dir = nm.get("error_maps")
         self.reports = []
         self.rm_sum = self.ss_sum = 0.0
         self.n = 0
@@ -210,7 +223,7 @@ class _Plan:
                     t.record_stream(self.stream)            # allocated on the upload stream, consumed on this one
         fmt = self.fmt
         codes = self.codes_of(x, y, g)
-        acc = ss = words = emap = None
+        acc = ss = words = emap = nwords = nmap = None
         if lab is not None:                                 # metrics stay on the device until settle()
             acc = fmt.sqerr(lab, codes)
             ss = metrics.ssim_dev(fmt.unit(lab[:h, :w]), fmt.unit(codes))
@@ -219,10 +232,14 @@ class _Plan:
                 r_ = metrics.depth_errors(lab, codes, error_map=bool(self.err_dir), **self.rp_kw)
                 words = _download(r_[0][0] if self.err_dir else r_[0])
                 emap = _download(r_[1]) if self.err_dir else None
+                if self.nm_kw is not None:
+                    n_ = metrics.normal_errors(lab, codes, angle_map=bool(self.nm_dir), **self.nm_kw)
+                    nwords = _download(n_[0][0] if self.nm_dir else n_[0])
+                    nmap = _download(n_[1]) if self.nm_dir else None
         codes = _download(codes)
         event = torch.cuda.Event()
         event.record(self.stream)
-        return Pending(f, event, codes, acc, ss, words, emap)
+        return Pending(f, event, codes, acc, ss, words, emap, nwords, nmap)
 
     def settle(self, p):
         """The host arithmetic of an enqueued image (metrics.masked_rmse's and metrics.ssim's), its line and its report."""
@@ -236,17 +253,20 @@ class _Plan:
             line += f" {rm} {ss}"
             if p.words is not None:
                 rep = metrics.depth_report(p.words, unit=self.fmt.rmse_scale, thresholds=self.rp_kw["thresholds"])
+                if p.nwords is not None:
+                    rep.update(metrics.normal_report(p.nwords, self.nm_thresholds))
                 self.reports.append({"file": p.f, **rep})
                 line += " " + metrics.report_tokens(rep)
         self.n += 1
         self.emit(line)
 
     def write(self, p):
-        """The output file and the error-map file of an enqueued image, once its downloads have landed."""
-        for d, t in ((self.out_dir, p.codes), (self.err_dir, p.emap)):
+        """The output file, the error-map file and the normal-error-map file of an enqueued image, once its downloads have landed."""
+        for d, t, write in ((self.out_dir, p.codes, self.fmt.write), (self.err_dir, p.emap, self.fmt.write),
+                            (self.nm_dir, p.nmap, _write_angle_map)):
             if d and t is not None:
                 p.event.synchronize()
-                self.fmt.write(os.path.join(d, p.f), t.numpy())
+                write(os.path.join(d, p.f), t.numpy())
 
 
 def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None, pipelined=True, emit=print, files=None,
@@ -263,6 +283,12 @@ def run_loop(model, dev, tdt, input_depth, input_color, label=None, out_dir=None
     "error_maps": a directory or None} -- one more launch per image (metrics.depth_errors); every line gains the key=value
     tokens of metrics.depth_report (mad, rmse and max in codes times depth_unit), the error maps are written under the images'
     names, and the result gains "reports" (the per-image dicts, with "file") and "report_means" (metrics.report_means).
+    report["normals"] (optional, and a report without it behaves to the byte as before): {"camera": the
+    register.Camera of the label's grid, "radius", "tolerance", "tolerance_rel": metrics.normal_errors' (cloud's untuned defaults
+    where left out), "thresholds": up to four angles in degrees, "error_maps": a directory or None} -- a second launch behind
+    depth_errors (metrics.normal_errors), its words read back with the others; every line and every report dict gains the
+    normal_* tokens of metrics.normal_report behind the depth tokens, and the angle maps are written as 8-bit PNGs of
+    min(254, degrees), 255 where the pixel is not compared.  Right only where code is proportional to metric z.
     fill_holes, fill_guided, fill_sigma, normalize (need lr_depth): the preparation of the uploaded codes ahead of
     codes_to_input, prep.LrPrep's fields, run on the main stream in both loops.  fill_holes: the holes
     are filled by pull-push -- the network sees a dense input; fill_guided: by upsample.fill_holes_guided under
@@ -380,7 +406,80 @@ def report_of(ap, a, prefix=""):
     return {"thresholds": thr, "edge_threshold": edge, "edge_radius": rad}
 
 
-def main(argv=None):
+def add_normal_args(ap):
+    """The flags of the normal report"""
+    d = metrics.NORMAL_DEFAULTS
+    ap.add_argument("--report-normals", action="store_true",
+                    help="with --report and --calib: append the surface-normal angle error to the report -- normal_n, normal_coverage, "
+                         "normal_mean, normal_rmse, normal_median in degrees and the fractions within --normal-thresholds -- between "
+                         "the label's normals and the output's (cloud's integer normals, the output masked by the label's holes).  "
+                         "Right only where code is proportional to metric z: not for disparity files")
+    ap.add_argument("--calib", default=None, metavar="FILE",
+                    help="report-normals: the rig's calibration, as python -m codon_amd.register reads it; the camera is the one the "
+                         "LABEL's grid is on, without distortion, at least as large as the output")
+    ap.add_argument("--camera", default=None, choices=("color", "depth"), help="report-normals: which camera of --calib (default color)")
+    ap.add_argument("--normal-radius", type=int, default=None, metavar="R",
+                    help=f"report-normals: a tangent spans the pixels R steps away, 1..8 (default {d['radius']}: cloud's, untuned)")
+    ap.add_argument("--normal-tolerance", type=int, default=None, metavar="CODES",
+                    help=f"report-normals: a far pixel counts when its code differs by at most R times this ... (default {d['tolerance']}: "
+                         "cloud's, untuned)")
+    ap.add_argument("--normal-tolerance-rel", type=float, default=None, metavar="F",
+                    help=f"... plus this fraction of the smaller code (default {d['tolerance_rel']}: cloud's, untuned)")
+    ap.add_argument("--normal-thresholds", default=None, metavar="A,B,...",
+                    help="report-normals: up to four angles in degrees, multiples of 1/8; normal<T is the fraction of compared pixels "
+                         "within T (default 11.25,22.5,30)")
+    ap.add_argument("--normal-error-maps", default=None, metavar="DIR",
+                    help="report-normals: write every image's angle map as an 8-bit PNG: min(254, degrees), 255 where the pixel is "
+                         "not compared")
+
+
+def normals_of(ap, a, top):
+    """The parsed flags of the normal report as a dict (calib, camera, radius, tolerance, tolerance_rel, thresholds, error_maps),
+    or None without --report-normals; refusals through ap.error.  top: the largest code"""
+    from .codes import rel_q16
+    names = ("calib", "camera", "normal_radius", "normal_tolerance", "normal_tolerance_rel", "normal_thresholds", "normal_error_maps")
+    if not a.report_normals:
+        for n in names:
+            if getattr(a, n) is not None:
+                ap.error(f"--{n.replace('_', '-')} needs --report-normals")
+        return None
+    if not a.report:
+        ap.error("--report-normals needs --report")
+    if a.calib is None:
+        ap.error("--report-normals needs --calib")
+    d = metrics.NORMAL_DEFAULTS
+    radius = d["radius"] if a.normal_radius is None else a.normal_radius
+    tol = d["tolerance"] if a.normal_tolerance is None else a.normal_tolerance
+    rel = d["tolerance_rel"] if a.normal_tolerance_rel is None else a.normal_tolerance_rel
+    if not 1 <= radius <= metrics.NORMAL_MAX_RADIUS:
+        ap.error(f"--normal-radius {radius} must be in [1, {metrics.NORMAL_MAX_RADIUS}]")
+    if not 0 <= tol <= top:
+        ap.error(f"--normal-tolerance {tol} must be in [0, {top}], the largest code")
+    try:
+        rel_q16("infer", rel)
+    except ValueError:
+        ap.error(f"--normal-tolerance-rel {rel} must be in [0, 1)")
+    thr = metrics.NORMAL_THRESHOLDS
+    if a.normal_thresholds is not None:
+        try:
+            thr = tuple(float(t) for t in a.normal_thresholds.split(","))
+        except ValueError:
+            ap.error(f"--normal-thresholds {a.normal_thresholds!r}: degrees, separated by commas")
+        try:
+            thr = metrics.normal_thresholds(thr, "infer")
+        except ValueError as e:
+            ap.error(f"--normal-thresholds {a.normal_thresholds!r}: {e}")
+    if a.normal_error_maps is not None:
+        inputs = {os.path.abspath(d_) for d_ in (a.input_depth, a.lr_depth, a.input_color, a.label) if d_}
+        if os.path.abspath(a.normal_error_maps) in inputs:
+            ap.error("--normal-error-maps is a directory of inputs: the maps would overwrite them")
+    return {"calib": a.calib, "camera": a.camera or "color", "radius": radius, "tolerance": tol, "tolerance_rel": rel,
+            "thresholds": thr, "error_maps": a.normal_error_maps}
+
+
+def parse_args(argv=None):
+    """-> (the parsed flags, the parser), every refusal that needs neither a file nor the GPU made through ap.error; the flags gain
+    report_opts (run_loop's report dict, or None), prep (prep.LrPrep) and normals (normals_of's dict, or None)"""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scale", type=int, default=4, choices=[4, 8, 16])
     ap.add_argument("--input-depth", default=None, help="depth maps already at the output size (this or --lr-depth)")
@@ -437,6 +536,7 @@ def main(argv=None):
     ap.add_argument("--report-json", default=None, metavar="FILE", help="report: write the per-image values and the means here (JSON; a value over an empty set is null)")
     ap.add_argument("--error-maps", default=None, metavar="DIR",
                     help="report: write every image's error map |label - output| (0 at holes) as a PNG of the data's depth")
+    add_normal_args(ap)
     a = ap.parse_args(argv)
     if a.report and not a.label:
         ap.error("--report needs --label")
@@ -470,6 +570,25 @@ def main(argv=None):
     a.depth_max = 65535 if a.depth_max is None else a.depth_max
     if not 1 <= a.depth_max <= 65535:
         ap.error(f"--depth-max {a.depth_max} must lie in [1, 65535]")
+    a.report_opts, a.prep = report, prep
+    a.normals = normals_of(ap, a, a.depth_max if a.depth_bits == 16 else 255)
+    return a, ap
+
+
+def main(argv=None):
+    a, ap = parse_args(argv)
+    report, prep = a.report_opts, a.prep
+    if a.normals is not None:                           # the camera of the label's grid, read before the GPU is asked for
+        from .register import Calibration
+        try:
+            cal = Calibration.from_json(a.normals["calib"])
+        except (OSError, ValueError) as e:
+            ap.error(f"--calib {a.normals['calib']}: {e}")
+        cam = cal.color if a.normals["camera"] == "color" else cal.depth
+        if any(cam.dist):
+            ap.error(f"--calib {a.normals['calib']}: {a.normals['camera']}.dist {cam.dist!r} is not zero: undistort the images first "
+                     "(python -m codon_amd.undistort --calib-out ...)")
+        report = {**report, "normals": {**{k: v for k, v in a.normals.items() if k != "calib"}, "camera": cam}}
     if not torch.cuda.is_available():
         raise SystemExit("No GPU found, codon_amd has no CPU path")          # test.py:37-38
     dev = torch.device("cuda:0")
@@ -489,8 +608,9 @@ def main(argv=None):
         extra = {}
     if a.out:
         os.makedirs(a.out, exist_ok=True)
-    if a.error_maps:
-        os.makedirs(a.error_maps, exist_ok=True)
+    for d in (a.error_maps, a.normals and a.normals["error_maps"]):
+        if d:
+            os.makedirs(d, exist_ok=True)
     r = run_loop(model, dev, tdt, a.input_depth, a.input_color, a.label, a.out, pipelined=not a.serial,
                  depth_bits=a.depth_bits, depth_max=a.depth_max, depth_unit=a.depth_unit,
                  **({"self_ensemble": True} if a.self_ensemble else {}), **({"report": report} if report else {}),

@@ -120,6 +120,37 @@ def masked_rmse_u16(label_u16: torch.Tensor, out_u16: torch.Tensor) -> float:
 EVAL_WORDS, EVAL_MAX_THRESHOLDS, EVAL_MAX_RADIUS = 16, 4, 8
 
 
+def _label_and_output(who, label, out):
+    """The dtype and shape rules of depth_errors' two planes -> (label, out) as (B, H, W), whether a single (H, W) plane came in,
+    and the output's own dtype"""
+    if label.dtype != out.dtype and {label.dtype, out.dtype} == {torch.int16, torch.uint16}:
+        label = label.view(out.dtype)                 # the same bits
+    if label.dtype != out.dtype or out.dtype not in (torch.uint8, torch.uint16, torch.int16):
+        raise ValueError(f"{who}: label {label.dtype} and output {out.dtype} (both uint8, or both u16 codes as uint16 / int16)")
+    if label.dim() != out.dim() or out.dim() not in (2, 3):
+        raise ValueError(f"{who}: planes of shape {tuple(label.shape)} and {tuple(out.shape)} ((H, W) or (B, H, W))")
+    single = out.dim() == 2
+    if single:
+        label, out = label[None], out[None]
+    if label.shape[0] != out.shape[0]:
+        raise ValueError(f"{who}: {label.shape[0]} labels for {out.shape[0]} outputs")
+    return label, out, single, out.dtype
+
+
+def _label_by_strides(label, out, wide):
+    """The layout rules of depth_errors' two planes -> (label, read through its own strides; out, contiguous; their device)"""
+    if wide:
+        label, out = label.view(torch.int16), out.view(torch.int16)     # the same bits, in a dtype every device op takes
+    Bl, Hl, Wl = label.shape
+    if label.stride(2) != 1 or label.stride(1) < Wl or (Bl > 1 and label.stride(0) < label.stride(1) * (Hl - 1) + Wl):
+        label = label.contiguous()                    # a layout the entry does not take (an expanded batch, a transposed plane)
+    out = out.contiguous()
+    dev = ops._dev(out)                               # the label goes by its strides: a window of a larger plane is welcome
+    if label.device != dev:
+        raise RuntimeError("codon_amd: tensors on different devices")
+    return label, out, dev
+
+
 def depth_errors(label: torch.Tensor, out: torch.Tensor, *, thresholds=(), edge_threshold=None, edge_radius=1,
                  error_map=False, region_map=False):
     """The evaluation words of (H, W) or (B, H, W) code planes in ONE launch (codon_depth_errors), no host synchronisation:
@@ -134,31 +165,13 @@ def depth_errors(label: torch.Tensor, out: torch.Tensor, *, thresholds=(), edge_
     Returns the words alone, or (words, error map, region map) with the maps asked for: the error map has the codes' own dtype
     (e where valid, else 0), the region map is uint8 (0 hole, 1 valid and flat, 2 valid and in the edge region)."""
     lib = L.load()
-    if label.dtype != out.dtype and {label.dtype, out.dtype} == {torch.int16, torch.uint16}:
-        label = label.view(out.dtype)                 # the same bits
-    if label.dtype != out.dtype or out.dtype not in (torch.uint8, torch.uint16, torch.int16):
-        raise ValueError(f"depth_errors: label {label.dtype} and output {out.dtype} (both uint8, or both u16 codes as uint16 / int16)")
-    if label.dim() != out.dim() or out.dim() not in (2, 3):
-        raise ValueError(f"depth_errors: planes of shape {tuple(label.shape)} and {tuple(out.shape)} ((H, W) or (B, H, W))")
-    single = out.dim() == 2
-    if single:
-        label, out = label[None], out[None]
-    if label.shape[0] != out.shape[0]:
-        raise ValueError(f"depth_errors: {label.shape[0]} labels for {out.shape[0]} outputs")
+    label, out, single, carrier = _label_and_output("depth_errors", label, out)
     thresholds = tuple(thresholds)
     if any(int(t) != t for t in thresholds) or (edge_threshold is not None and int(edge_threshold) != edge_threshold) \
             or int(edge_radius) != edge_radius:
         raise ValueError("depth_errors: thresholds, edge_threshold and edge_radius are integers (codes, pixels)")
-    wide, carrier = out.dtype != torch.uint8, out.dtype
-    if wide:
-        label, out = label.view(torch.int16), out.view(torch.int16)     # the same bits, in a dtype every device op takes
-    Bl, Hl, Wl = label.shape
-    if label.stride(2) != 1 or label.stride(1) < Wl or (Bl > 1 and label.stride(0) < label.stride(1) * (Hl - 1) + Wl):
-        label = label.contiguous()                    # a layout the entry does not take (an expanded batch, a transposed plane)
-    out = out.contiguous()
-    dev = ops._dev(out)                               # the label goes by its strides: a window of a larger plane is welcome
-    if label.device != dev:
-        raise RuntimeError("codon_amd: tensors on different devices")
+    wide = carrier != torch.uint8
+    label, out, dev = _label_by_strides(label, out, wide)
     B, H, W = out.shape
     d = L.DepthErrorsDesc(B, H, W, 16 if wide else 8, label.shape[1], label.shape[2], label.stride(1), label.stride(0),
                           len(thresholds), (C.c_int32 * 4)(*(int(t) for t in thresholds[:EVAL_MAX_THRESHOLDS])),
@@ -212,6 +225,141 @@ def report_means(reports) -> dict:
 def report_tokens(r: dict) -> str:
     """ key=value tokens of a depth_report dict, or of report_means (key=mean/count)."""
     return " ".join(f"{k}={v[0]!r}/{v[1]}" if isinstance(v, list) else f"{k}={v!r}" for k, v in r.items())
+
+
+# ---- surface-normal angle error (DESIGN 12.20) -------------------------------------------------------------------------------------
+
+NORMAL_ANGLES, NORMAL_BINS, NORMAL_WORDS, NORMAL_MAX_THRESHOLDS, NORMAL_MAX_RADIUS = 1440, 1441, 1448, 4, 8
+NORMAL_VALID, NORMAL_LABEL_NORMALS, NORMAL_COMPARED, NORMAL_OUT_HOLES = 1441, 1442, 1443, 1444
+NORMAL_NONE = 65535                                   # the angle map's texel of a pixel that is not compared
+NORMAL_DEFAULTS = dict(radius=2, tolerance=2, tolerance_rel=0.02)          # cloud's, untuned
+NORMAL_THRESHOLDS = (11.25, 22.5, 30.0)
+
+
+def angle_tables():
+    """(C, S) int32 (1440 each): C[m - 1] = rint(2^30 cos t_m), S[m - 1] = rint(2^30 sin t_m) at the thresholds t_m = (m - 1/2) / 8
+    degrees, m = 1 .. 1440, between the bins of an eighth of a degree; float64 on the host, once"""
+    import numpy as np
+    t = np.radians((np.arange(1, NORMAL_ANGLES + 1, dtype=np.float64) - 0.5) / 8.0)
+    return np.rint(float(1 << 30) * np.cos(t)).astype(np.int32), np.rint(float(1 << 30) * np.sin(t)).astype(np.int32)
+
+
+def _rays_of(who, camera, H, W):
+    """(key, maker of (rx, ry) int32) of a register.Camera or of a pair of ray tables that cover an H x W window"""
+    import numpy as np
+    from .register import A_LIMIT, Camera
+    if isinstance(camera, Camera):
+        if any(camera.dist):
+            raise ValueError(f"{who}: camera.dist {camera.dist!r} is not zero: a distorted camera has no separable ray table "
+                             "(undistort the images first: python -m codon_amd.undistort --calib-out ...)")
+        if camera.height < H or camera.width < W:
+            raise ValueError(f"{who}: a {camera.height}x{camera.width} camera is smaller than the {H}x{W} output")
+        from .cloud import ray_tables
+        return ("camera", camera.width, camera.height, camera.fx, camera.fy, camera.cx, camera.cy), lambda: ray_tables(camera)
+    try:
+        rx, ry = (np.array(t.cpu() if isinstance(t, torch.Tensor) else t) for t in camera)      # copies: writable, contiguous
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: camera must be a register.Camera or a pair of int32 ray tables (RX, RY)") from None
+    if rx.dtype != np.int32 or ry.dtype != np.int32 or rx.ndim != 1 or ry.ndim != 1:
+        raise ValueError(f"{who}: camera must be a register.Camera or a pair of int32 ray tables (RX, RY)")
+    if len(ry) < H or len(rx) < W:
+        raise ValueError(f"{who}: ray tables of a {len(ry)}x{len(rx)} camera are smaller than the {H}x{W} output")
+    if max(np.abs(rx[:W].astype(np.int64)).max(), np.abs(ry[:H].astype(np.int64)).max()) >= A_LIMIT:
+        raise ValueError(f"{who}: a ray of 2^22 or more in Q20")
+    return ("tables", rx.tobytes(), ry.tobytes()), lambda: (rx, ry)
+
+
+_host_rays: dict = {}
+
+
+def normal_errors(label: torch.Tensor, out: torch.Tensor, camera, *, radius=NORMAL_DEFAULTS["radius"],
+                  tolerance=NORMAL_DEFAULTS["tolerance"], tolerance_rel=NORMAL_DEFAULTS["tolerance_rel"], depth_max=None,
+                  angle_map=False):
+    """The surface-normal angle error of (H, W) or (B, H, W) code planes in ONE launch (codon_normal_errors), no host
+    synchronisation: a DEVICE int32 (B, 1448) tensor per image -- 0 .. 1440 the histogram of a = rint(8 angle in degrees) between
+    the label's normal and the output's over the COMPARED pixels (label != 0 and both planes have a normal), 1441 the valid label
+    pixels, 1442 those whose label has a normal, 1443 the compared pixels, 1444 the pixels with label != 0 and output == 0, 1445 ..
+    1447 zero (normal_report turns a row into mean, median, RMSE and rates).  The normals are cloud's integer normals (radius,
+    tolerance per step, tolerance_rel: its link parameters and its untuned defaults) and the output is masked by the label's
+    holes first, so both see one hole set.  RIGHT ONLY WHERE CODE IS PROPORTIONAL TO METRIC z: true of every file this project
+    reads, false of disparity files.  camera: the register.Camera of the label's grid (no distortion, at least as large as the
+    output), or a pair (RX, RY) of int32 ray tables (cloud.ray_tables); a top-left crop keeps the principal point, so the first W
+    and H entries are used.  Dtypes and layouts are depth_errors': uint8, or u16 codes as uint16 / int16; the label at least as
+    large as the output, read top-left through its own strides.  depth_max: the largest code of a u16 set (default 65535);
+    tolerance may not exceed it.  Returns the words alone, or (words, angle map) with angle_map: uint16, a where the pixel is
+    compared, 65535 elsewhere."""
+    from . import codes as K
+    who = "normal_errors"
+    lib = L.load()
+    label, out, single, carrier = _label_and_output(who, label, out)
+    wide = carrier != torch.uint8
+    if not wide and depth_max not in (None, 255):
+        raise ValueError(f"{who}: depth_max {depth_max!r} with 8-bit codes")
+    top = 255 if not wide else 65535 if depth_max is None else K.integer(who, "depth_max", depth_max, 1, 65535, "1..65535")
+    radius = K.integer(who, "radius", radius, 1, NORMAL_MAX_RADIUS, f"an integer in 1..{NORMAL_MAX_RADIUS}")
+    tolerance = K.integer(who, "tolerance", tolerance, 0, top, f"an integer number of codes, 0 .. the largest code {top}")
+    rel = K.rel_q16(who, tolerance_rel)
+    B, H, W = out.shape
+    if label.shape[1] < H or label.shape[2] < W:
+        raise ValueError(f"{who}: a {label.shape[1]}x{label.shape[2]} label is smaller than the {H}x{W} output")
+    key, make = _rays_of(who, camera, H, W)
+    label, out, dev = _label_by_strides(label, out, wide)
+    host = _host_rays.get(key)                        # the host's tables once per camera, their device copies once per device
+    if host is None:
+        host = _host_rays[key] = make()
+    rx, ry = K.on_device(("normal_rx", key), lambda: host[0], dev), K.on_device(("normal_ry", key), lambda: host[1], dev)
+    span = (C.c_int32 * 4)(int(host[0][0]), int(host[0][W - 1]), int(host[1][0]), int(host[1][H - 1]))
+    ctab, stab = K.on_device("normal_cos", lambda: angle_tables()[0], dev), K.on_device("normal_sin", lambda: angle_tables()[1], dev)
+    words = torch.empty((B, NORMAL_WORDS), dtype=torch.int32, device=dev)
+    amap = torch.empty((B, H, W), dtype=torch.uint16, device=dev) if angle_map else None
+    with torch.cuda.device(dev):
+        L.check(lib.codon_normal_errors(B, H, W, _p(label), label.shape[1], label.shape[2], label.stride(1), label.stride(0), _p(out),
+                                        L.FILL_U16 if wide else L.FILL_U8, top, _p(rx), _p(ry), span, _p(ctab), _p(stab), radius,
+                                        tolerance, rel, _p(words), _p(amap), ops._stream(dev)), who)
+    if amap is None:
+        return words
+    return words, (amap[0] if single else amap)
+
+
+def normal_thresholds(thresholds, who="normal_report"):
+    """The thresholds in degrees as a tuple of floats: at most four, each a multiple of 1/8 inside 0 .. 180; refusals by name"""
+    thresholds = tuple(thresholds)
+    if len(thresholds) > NORMAL_MAX_THRESHOLDS:
+        raise ValueError(f"{who}: {len(thresholds)} thresholds (at most {NORMAL_MAX_THRESHOLDS})")
+    for t in thresholds:
+        ok = isinstance(t, (int, float)) and not isinstance(t, bool) and math.isfinite(t) and 0 <= t <= 180 and float(8 * t).is_integer()
+        if not ok:
+            raise ValueError(f"{who}: threshold {t!r} (degrees: a multiple of 1/8 in 0 .. 180)")
+    return tuple(float(t) for t in thresholds)
+
+
+def normal_report(row, thresholds=NORMAL_THRESHOLDS) -> dict:
+    """One image's 1448 words (a row of normal_errors, on the host) as numbers, all in degrees, in Python floats: normal_n (the
+    compared pixels), normal_coverage (compared / valid label pixels), normal_mean, normal_rmse, normal_median (the smallest a
+    whose cumulative count reaches ceil(n / 2), over 8) and "normal<T" for every threshold T (the fraction of compared pixels with
+    a <= 8 T).  A value over no compared pixel is nan, the report's rule, so report_means skips it."""
+    w = [int(v) & 0xFFFFFFFF for v in row]
+    if len(w) != NORMAL_WORDS:
+        raise ValueError(f"normal_report: {len(w)} words (one row of normal_errors has {NORMAL_WORDS})")
+    thresholds = normal_thresholds(thresholds)
+    hist, n, valid = w[:NORMAL_BINS], w[NORMAL_COMPARED], w[NORMAL_VALID]
+    if sum(hist) != n:
+        raise ValueError(f"normal_report: the histogram holds {sum(hist)} pixels and word {NORMAL_COMPARED} says {n}")
+    r = {"normal_n": n, "normal_coverage": n / valid if valid else math.nan}
+    if n == 0:
+        r.update(normal_mean=math.nan, normal_rmse=math.nan, normal_median=math.nan)
+    else:
+        half, run, median = (n + 1) // 2, 0, 0
+        for a, v in enumerate(hist):
+            run += v
+            if run >= half:
+                median = a
+                break
+        r.update(normal_mean=sum(a * v for a, v in enumerate(hist)) / (8 * n),
+                 normal_rmse=math.sqrt(sum(a * a * v for a, v in enumerate(hist)) / n) / 8, normal_median=median / 8)
+    for t in thresholds:
+        r[f"normal<{t:g}"] = sum(hist[:int(8 * t) + 1]) / n if n else math.nan
+    return r
 
 
 def _ssim_forward(a, b, want_maps):

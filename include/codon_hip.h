@@ -848,6 +848,35 @@ typedef struct codon_depth_errors_desc {
 int codon_depth_errors(const codon_depth_errors_desc* desc, const void* label, const void* out, uint64_t* acc,
                        void* error_map, uint8_t* region_map, codon_stream_t stream);
 
+/* ---- surface-normal angle error (codon_amd.metrics.normal_errors, infer --report-normals) -----------------------
+ * Nothing in the reference: it prints one masked RMSE per image.  A DEFINITION, in codon_amd/csrc/normal_errors.hip and
+ * normal_tile.h, restated in numpy in tests/normal_errors_ref.py, equal words and equal maps required.  Integers only.
+ *
+ * label: (batch, label_height, label_width) codes, read top-left through label_row_stride / label_image_stride (elements), as
+ * codon_depth_errors reads it; out: (batch, height, width) codes, dense; both u8 (CODON_FILL_U8) or both u16 (CODON_FILL_U16), 0 a
+ * hole.  Inside the height x width window the output counts as 0 wherever the label is 0, and both planes count as 0 outside the
+ * window.  rx (width), ry (height): int32 ON THE DEVICE, codon_cloud_points' Q20 rays (of the LABEL's camera: a top-left crop keeps
+ * the principal point, so only the first width and height entries are read); ray_span: ON THE HOST, rx[0], rx[width - 1], ry[0],
+ * ry[height - 1].  cos_table, sin_table: int32[1440] ON THE DEVICE, rint(2^30 cos t_m) and rint(2^30 sin t_m) at t_m = (m - 1/2) / 8
+ * degrees, m = 1 .. 1440, at index m - 1; trusted to be those values, as the range and Gauss tables of other entries are.  N_l and
+ * N_o: the integer normals of cloud_tile.h of the label and of the masked output under radius, tol_abs and tol_rel_q16
+ * (codon_cloud_points' link parameters).  A pixel is compared when its label is non-zero and both planes have a normal there; its
+ * index is a = #{ m : A cos_table[m] - D sin_table[m] > 0 } with D = N_l . N_o and A = isqrt(|N_l x N_o|^2): rint(8 angle in degrees).
+ * words: (batch, 1448) uint32 ON THE DEVICE, needs no initialisation (the entry zeroes it on the stream): 0 .. 1440 the histogram of
+ * a, 1441 valid label pixels in the window, 1442 those whose label has a normal, 1443 compared pixels, 1444 pixels with label != 0
+ * and out == 0, 1445 .. 1447 zero.  angle_map: NULL, or (batch, height, width) uint16: a where compared, 65535 elsewhere.
+ *
+ * ONE launch; no workspace; no host synchronisation.  Refused on the host, before any HIP call: null pointers (angle_map may be
+ * NULL), an fmt other than CODON_FILL_U8 / _U16, batch outside 1 .. 65535, a height or width outside 1 .. 4096, top outside
+ * 1 .. 65535 or not 255 for u8 codes, a label smaller than the window or strides that do not hold it, radius outside 1 .. 8,
+ * tol_abs outside 0 .. top, tol_rel_q16 outside 0 .. 65535, a ray of the span of 2^22 or more in magnitude, a u16 plane or map that
+ * is not 2-byte aligned, tables or words not 4-byte aligned. */
+int codon_normal_errors(int32_t batch, int32_t height, int32_t width, const void* label, int32_t label_height, int32_t label_width,
+                        int64_t label_row_stride, int64_t label_image_stride, const void* out, int32_t fmt, int32_t top,
+                        const int32_t* rx, const int32_t* ry, const int32_t* ray_span, const int32_t* cos_table,
+                        const int32_t* sin_table, int32_t radius, int32_t tol_abs, int32_t tol_rel_q16, uint32_t* words,
+                        uint16_t* angle_map, codon_stream_t stream);
+
 /* ---- pull-push hole filling of low-resolution code planes (codon_amd.upsample.fill_holes) -------------------
  * No reference counterpart (its depth inputs were hole-filled offline by a tool it does not ship): a DEFINITION, in
  * codon_amd/csrc/fill_holes.hip and fill_tile.h, restated in numpy in tests/fill_ref.py, equal bits required.  Integers only.

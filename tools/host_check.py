@@ -1,6 +1,6 @@
 """Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
 into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
-guided_fill, jbu, register, clean, undistort, cloud) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+guided_fill, jbu, register, clean, undistort, cloud, normal_errors) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
 address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
 restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
 
@@ -25,6 +25,7 @@ from tests import eval_ref as E  # noqa: E402
 from tests import fill_ref as F  # noqa: E402
 from tests import guided_fill_ref as R  # noqa: E402
 from tests import jbu_ref as J  # noqa: E402
+from tests import normal_errors_ref as N  # noqa: E402
 from tests import register_ref as G  # noqa: E402
 from tests import resample_masked_ref as M  # noqa: E402
 from tests import sensor_ref as S  # noqa: E402
@@ -303,6 +304,40 @@ def cloud(run, p):
                    "the largest): no report, every byte and count equals tests/cloud_ref.py")
 
 
+def normal_errors(run, p):
+    """The GPU test's cases (normal_errors_ref.cases): every shape under every pattern, radius and noise; the program runs each in
+    both thread orders.  Then the per-pair index function over pairs no scene reaches: opposite normals, pairs on a threshold,
+    D < 0"""
+    ctab, stab = (t.astype(np.int32) for t in N.angle_tables())
+    ctab.tofile(p("c")), stab.tofile(p("s"))
+    cases = 0
+    for shape in N.SHAPES:
+        B, h, w = shape
+        _, hl, wl = N.label_shape(shape)
+        rx, ry = N.tables(shape)
+        rx.tofile(p("x")), ry.tofile(p("y"))
+        for pattern, radius, noise, holes in N.cases(shape):
+            top = Q.top_of(pattern)
+            label, out = N.planes(shape, pattern, noise, holes)
+            label.tofile(p("l")), out.tofile(p("o"))
+            run("planes", 0 if top == 255 else 1, B, h, w, hl, wl, radius, N.tolerance_of(top), N.RQ, p("l"), p("o"), p("x"), p("y"),
+                p("c"), p("s"), p("r"))
+            words, maps = N.want(shape, pattern, radius, noise, holes)
+            what = (shape, pattern, radius, noise, holes)
+            assert np.fromfile(p("r.words"), dtype=np.uint32).tobytes() == words.tobytes(), (*what, "words")
+            assert np.fromfile(p("r.map"), dtype=np.uint16).tobytes() == maps.tobytes(), (*what, "angle map")
+            cases += 1
+    rows, kinds = N.pairs()
+    rows.tofile(p("q"))
+    run("pairs", len(rows), p("q"), p("c"), p("s"), p("a"))
+    got = np.fromfile(p("a"), dtype=np.int32)
+    assert np.array_equal(got, N.index_count(rows[:, :3], rows[:, 3:])), "the index of a pair"
+    assert (got[kinds["opposite"]] == N.ANGLES).all() and (got[kinds["same"]] == 0).all()
+    assert (N.dot_and_root(rows[:, :3], rows[:, 3:])[0][kinds["random"]] < 0).sum() > 1000
+    return cases, (f"over {len(N.SHAPES)} shapes, {len(N.PATTERNS)} patterns x {len(N.RADII)} radii x the noises, and {len(rows)} pairs of "
+                   "normals: no report, every word and map equals tests/normal_errors_ref.py")
+
+
 # name -> (check, extra compile flags, what the count counts)
 CHECKS = {
     "d4": (d4, ["-ffp-contract=off"], "runs"),
@@ -316,6 +351,7 @@ CHECKS = {
     "clean": (clean, [], "cases"),
     "undistort": (undistort, [], "cases"),
     "cloud": (cloud, [], "cases"),
+    "normal_errors": (normal_errors, [], "cases"),
 }
 
 
