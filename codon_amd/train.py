@@ -50,33 +50,12 @@ from .codes import code_table, on_device
 from .upsample import (_fill_launch, down_weights, gauss_table, lut16, phase_weights, u8_lut)      # noqa: F401 (lut16: for importers)
 from .prep import LrPrep, add_prep_args, prep_of
 from .upsample import FILL_SIGMA, code_range, stretch_codes
+# the options that change a run's trajectory: the table of checkpoint keys, its views, the record and the command line's mappings
+from .options import (DEGRADE_DEFAULTS, DEPTH_DEFAULTS, FILL_DEFAULTS, GUIDED_DEFAULTS, LR_DEFAULTS, NORM_DEFAULTS,      # noqa: F401
+                      RESUME_ALL_DEFAULTS, RESUME_ALL_KEYS, RESUME_DEFAULTS, RESUME_KEYS, RESUME_TABLE, SENSOR_DEFAULTS,
+                      RunOptions, SensorModel, fit_kwargs, run_args, sensor_of)
 
 DTYPES = {"bf16": torch.bfloat16, "f32": None}
-RESUME_KEYS = ("scale", "crop", "batch", "dtype", "clip_norm", "skip_nonfinite", "ema", "lr_schedule", "warmup_steps", "lr_min",
-               "lr_steps", "mask_holes", "min_valid", "train_label")
-# what a key compares as when a checkpoint's args do not carry it (one written before the option existed)
-RESUME_DEFAULTS = {"clip_norm": None, "skip_nonfinite": False, "ema": None, "lr_schedule": "constant", "warmup_steps": 0,
-                   "lr_min": 0.0, "lr_steps": None, "mask_holes": False, "min_valid": 0.0, "train_label": False}
-# compared on --resume like RESUME_KEYS, but written by a 16-bit run ONLY: an 8-bit checkpoint keeps exactly the
-# args it always had, and one without these keys compares as 8-bit
-DEPTH_DEFAULTS = {"depth_bits": 8, "depth_max": 65535}
-# the same for --degrade-holes: a resume key with default False, written by a run that sets it ONLY
-DEGRADE_DEFAULTS = {"degrade_holes": False}
-# the same for --train-lr-depth: a resume key with default False, written by a run that sets it ONLY
-LR_DEFAULTS = {"train_lr_depth": False}
-# the same for the sensor model: its fields, written by a run with a model ONLY; a checkpoint without them
-# compares as "no model"
-SENSOR_DEFAULTS = {"sensor_noise": None, "sensor_noise_quad": None, "sensor_dropout": None, "sensor_edge_dropout": None,
-                   "sensor_edge_threshold": None, "sensor_seed": None}
-# the same for the preparation of low-resolution maps: prep.LrPrep's fields with their defaults, written as
-# LrPrep.set_options() gives them -- by a run that sets the option ONLY
-FILL_DEFAULTS = LrPrep.defaults("fill_holes")
-GUIDED_DEFAULTS = LrPrep.defaults("fill_guided", "fill_sigma")
-NORM_DEFAULTS = LrPrep.defaults("normalize")
-# what load_resume compares: every key above, and what each compares as when a checkpoint's args lack it
-_LATER_DEFAULTS = (DEPTH_DEFAULTS, DEGRADE_DEFAULTS, LR_DEFAULTS, SENSOR_DEFAULTS, FILL_DEFAULTS, GUIDED_DEFAULTS, NORM_DEFAULTS)
-RESUME_ALL_KEYS = RESUME_KEYS + tuple(k for d in _LATER_DEFAULTS for k in d)
-RESUME_ALL_DEFAULTS = {k: v for d in (RESUME_DEFAULTS,) + _LATER_DEFAULTS for k, v in d.items()}
 MAX_REDRAWS = 64                                    # draw(min_valid=): per sample, before it gives up
 LR_SCHEDULES = ("constant", "cosine")
 
@@ -241,6 +220,12 @@ def valid_counts(trainset: TrainSet, descs: np.ndarray, crop: int) -> np.ndarray
     return out
 
 
+def check_min_valid(who: str, min_valid: float, mask_holes: bool):
+    """draw's threshold is a fraction, and means something under the masked loss only (draw: always; fit: with mask_holes)"""
+    if not 0.0 <= min_valid <= 1.0 or (min_valid > 0 and not mask_holes):
+        raise ValueError(f"{who}: min_valid {min_valid} must lie in [0, 1]" + ("" if mask_holes else " and needs mask_holes"))
+
+
 def draw(rng: np.random.Generator, trainset: TrainSet, batch: int, crop: int, rank: int = 0, world: int = 1,
          min_valid: float = 0.0) -> np.ndarray:
     """This rank's share of one global batch: (batch/world, 6) int64 rows (pool offset, H, W, y0, x0, D4 op).  Every rank
@@ -254,8 +239,7 @@ def draw(rng: np.random.Generator, trainset: TrainSet, batch: int, crop: int, ra
     if crop < 1 or (trainset.sizes < crop).any():
         raise ValueError(f"draw: crop {crop} does not fit the smallest image "
                          f"({int(trainset.sizes[:, 0].min())}x{int(trainset.sizes[:, 1].min())})")
-    if not 0.0 <= min_valid <= 1.0:
-        raise ValueError(f"draw: min_valid {min_valid} must lie in [0, 1]")
+    check_min_valid("draw", min_valid, True)
     idx = rng.integers(0, len(trainset.offsets), size=batch)
     hw = trainset.sizes[idx]
     y0 = rng.integers(0, hw[:, 0] - crop + 1)
@@ -279,46 +263,6 @@ def draw(rng: np.random.Generator, trainset: TrainSet, batch: int, crop: int, ra
     return d[lo:hi]
 
 
-@dataclasses.dataclass(frozen=True)
-class SensorModel:
-    """The sensor model of the synthetic degradation, applied to the low-resolution map between the two bicubics.
-    noise, noise_quad, edge_threshold are in CODES of the data's own grid (255, or depth_max): the standard deviation of a
-    valid pixel of value v is noise + noise_quad * v^2 codes (noise_quad: sensors whose noise grows with the square of the
-    range; 0 for disparity-like data).  dropout is the probability that a valid pixel becomes a hole, edge_dropout the
-    probability added where a 4-neighbour differs by more than edge_threshold codes; both need degrade_holes (a hole must be
-    left out of the upsample, not smeared through it).  seed: 64 bits, the Philox key."""
-    noise: float = 0.0
-    noise_quad: float = 0.0
-    dropout: float = 0.0
-    edge_dropout: float = 0.0
-    edge_threshold: float = 0.0
-    seed: int = 0
-
-    def __post_init__(self):
-        for n in ("noise", "noise_quad", "edge_threshold"):
-            v = getattr(self, n)
-            if not (isinstance(v, (int, float)) and math.isfinite(v) and v >= 0):
-                raise ValueError(f"SensorModel: {n} {v!r} must be finite and not negative")
-        for n in ("dropout", "edge_dropout"):
-            v = getattr(self, n)
-            if not (isinstance(v, (int, float)) and 0.0 <= v <= 1.0):
-                raise ValueError(f"SensorModel: {n} {v!r} must lie in [0, 1]")
-        if self.dropout + self.edge_dropout > 1.0:
-            raise ValueError(f"SensorModel: dropout {self.dropout} + edge_dropout {self.edge_dropout} exceeds 1")
-        if not (isinstance(self.seed, int) and 0 <= self.seed < 1 << 64):
-            raise ValueError(f"SensorModel: seed {self.seed!r} must be an integer of 64 bits, not negative")
-
-    @property
-    def drops(self) -> bool:
-        return self.dropout > 0 or self.edge_dropout > 0
-
-    def args(self) -> dict:
-        """The checkpoint keys of SENSOR_DEFAULTS."""
-        return {"sensor_noise": float(self.noise), "sensor_noise_quad": float(self.noise_quad),
-                "sensor_dropout": float(self.dropout), "sensor_edge_dropout": float(self.edge_dropout),
-                "sensor_edge_threshold": float(self.edge_threshold), "sensor_seed": int(self.seed)}
-
-
 def check_sensor(who: str, trainset: TrainSet, sensor: SensorModel, degrade_holes: bool):
     if trainset.has_lr:
         raise ValueError(f"{who}: a sensor model does not go with a TrainSet of low-resolution maps (nothing is degraded: the "
@@ -326,6 +270,12 @@ def check_sensor(who: str, trainset: TrainSet, sensor: SensorModel, degrade_hole
     if sensor.drops and not degrade_holes:
         raise ValueError(f"{who}: sensor dropout needs degrade_holes (without the masked upsample a dropped pixel would ring "
                          "instead of being left out)")
+
+
+def check_fill(who: str, trainset: TrainSet, fill_holes: bool, degrade_holes: bool):
+    if fill_holes and not (degrade_holes or (trainset.has_lr and trainset.fill_holes)):
+        raise ValueError(f"{who}: fill_holes needs degrade_holes, or a TrainSet of low-resolution maps built with fill_holes "
+                         "(the unmasked degradation has no holes to fill)")
 
 
 def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, degrade_holes: bool = False,
@@ -356,9 +306,7 @@ def synthesize(trainset: TrainSet, descs: np.ndarray, scale: int, crop: int, deg
     and the quantise launch stay as they are, return_lr returns the filled map, and x is what infer.codes_to_input builds from
     upsample.fill_holes of that map's codes.  With a TrainSet of low-resolution maps built with fill_holes it changes nothing
     (the pool is already filled).  Anything else is refused: the unmasked degradation has no holes."""
-    if fill_holes and not (degrade_holes or (trainset.has_lr and trainset.fill_holes)):
-        raise ValueError("synthesize: fill_holes needs degrade_holes, or a TrainSet of low-resolution maps built with fill_holes "
-                         "(the unmasked degradation has no holes to fill)")
+    check_fill("synthesize", trainset, fill_holes, degrade_holes)
     if sensor is not None:
         check_sensor("synthesize", trainset, sensor, degrade_holes)
         if not 0 <= step < 1 << 32 or not 0 <= first_sample <= (1 << 32) - len(descs):
@@ -515,7 +463,8 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
         fill_sigma: float = FILL_SIGMA) -> dict:
     """Train `model` (fp32 parameters on the pool's device) from step start_step + 1 to step `steps`.
     val:   {"depth", "color", "label", "every"} -- rank 0 runs infer.run_loop every `every` steps and prints the means;
-    ckpt:  {"path", "every"} -- rank 0 saves every `every` steps and after the last one;
+    ckpt:  {"path", "every"} -- rank 0 saves every `every` steps and after the last one; a checkpoint's args are `args` with
+           the run's trajectory options (options.RunOptions.of_fit of the arguments below and the TrainSet) laid over them;
     fixed: descriptors (draw's rows of this rank) used for EVERY step instead of drawing (overfit checks);
     time_synth: HIP events around synthesize and around each whole step (result["synth_ms"], ["step_ms"]);
     clip_norm, skip_nonfinite, ema_decay: FlatAdam's max_norm, skip_nonfinite, ema_decay (all off by default); with one on,
@@ -546,12 +495,15 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     rank, world = _world(process_group)
     if batch % world:
         raise ValueError(f"fit: a batch of {batch} does not split evenly over {world} ranks")
-    if not 0.0 <= min_valid <= 1.0 or (min_valid > 0 and not mask_holes):
-        raise ValueError(f"fit: min_valid {min_valid} must lie in [0, 1] and needs mask_holes")
-    prep, built = LrPrep.checked("fit", fill_holes, fill_guided, fill_sigma, normalize), trainset.prep
-    if prep.fill_holes != built.fill_holes if trainset.has_lr else (prep.fill_holes and not degrade_holes):
+    check_min_valid("fit", min_valid, mask_holes)
+    if lr_schedule == "cosine" and lr_steps is None:
+        lr_steps = steps
+    options = RunOptions.of_fit(trainset, locals())     # the keyword arguments above, by name: what the checkpoints will hold
+    prep, built = options.prep, trainset.prep
+    if trainset.has_lr and prep.fill_holes != built.fill_holes:
         raise ValueError("fit: fill_holes needs degrade_holes, or a TrainSet of low-resolution maps -- and that TrainSet must "
                          "have been built with the same fill_holes (its pool is filled once, when it is built)")
+    check_fill("fit", trainset, prep.fill_holes, degrade_holes)
     if (prep.fill_guided, prep.fill_sigma) != (built.fill_guided, built.fill_sigma):
         say = lambda p: f"fill_guided {p.fill_guided!r}" + (f" (fill_sigma {p.fill_sigma!r})" if p.fill_guided else "")   # noqa: E731
         raise ValueError(f"fit: {say(prep)} with a TrainSet built with {say(built)}"
@@ -574,25 +526,11 @@ def fit(model, trainset: TrainSet, steps: int, *, scale: int, crop: int = 128, b
     if opt_state is not None:
         opt.load_state_dict(opt_state)
     scheduled = lr_schedule != "constant" or warmup > 0
-    if lr_schedule == "cosine" and lr_steps is None:
-        lr_steps = steps
     lr_at(1, lr=lr, schedule=lr_schedule, warmup=warmup, lr_min=lr_min, lr_steps=lr_steps)       # refuses a bad curve up front
     crit = MaskedL1SSIMLoss(1.0, 1.0) if mask_holes else L1SSIMLoss(1.0, 1.0)
     if mask_holes:
         trainset.valid_integrals()                  # the one read of the pool, before the first step
-    args = dict(args or {}, scale=scale, crop=crop, batch=batch, dtype=dtype, clip_norm=clip_norm,
-                skip_nonfinite=bool(skip_nonfinite), ema=ema_decay, lr_schedule=lr_schedule, warmup_steps=warmup, lr_min=lr_min,
-                lr_steps=lr_steps if lr_schedule == "cosine" else None)
-    args.update(mask_holes=bool(mask_holes), min_valid=float(min_valid), train_label=bool(trainset.has_label))
-    if degrade_holes:                               # only then: a checkpoint of a run without it keeps the keys it always had
-        args.update(degrade_holes=True)
-    if trainset.has_lr:                             # only then, likewise
-        args.update(train_lr_depth=True)
-    if sensor is not None:                          # only then, likewise
-        args.update(sensor.args())
-    args.update(prep.set_options())                 # the options that are set only, likewise
-    if trainset.depth_bits == 16:                   # only then: an 8-bit checkpoint keeps the keys it always had
-        args.update(depth_bits=16, depth_max=int(trainset.depth_max))
+    args = {**(args or {}), **options.args()}       # keys the table does not know (lr, seed) pass through
     stream = torch.cuda.current_stream(dev)
     losses, val_log, ev = [], [], []
     t_log, s_log = time.perf_counter(), start_step
@@ -857,26 +795,6 @@ def parse_args(argv=None):
     return a
 
 
-def sensor_of(a):
-    """The SensorModel the command line asks for, or None when it names no --sensor option."""
-    f = {n: getattr(a, "sensor_" + n) for n in ("noise", "noise_quad", "dropout", "edge_dropout", "edge_threshold")}
-    if all(v is None for v in f.values()):
-        return None
-    return SensorModel(seed=a.seed, **{n: 0.0 if v is None else v for n, v in f.items()})
-
-
-def run_args(a) -> dict:
-    sensor = sensor_of(a)
-    deep = {"depth_bits": 16, "depth_max": a.depth_max} if a.depth_bits == 16 else {}
-    return {**deep, "scale": a.scale, "crop": a.crop, "batch": a.batch, "dtype": a.dtype, "lr": a.lr, "seed": a.seed,
-            "clip_norm": a.clip_norm, "skip_nonfinite": a.skip_nonfinite, "ema": a.ema, "lr_schedule": a.lr_schedule,
-            "warmup_steps": a.warmup_steps, "lr_min": a.lr_min, "lr_steps": a.lr_steps, "mask_holes": bool(a.mask_holes),
-            "min_valid": float(a.min_valid), "train_label": a.train_label is not None,
-            **({"degrade_holes": True} if a.degrade_holes else {}),
-            **({"train_lr_depth": True} if a.train_lr_depth is not None else {}),
-            **(sensor.args() if sensor is not None else {}), **a.prep.set_options()}
-
-
 def main(argv=None, emit=print) -> dict:
     a = parse_args(argv)
     prep = a.prep
@@ -925,13 +843,8 @@ def main(argv=None, emit=print) -> dict:
     if val is not None and a.val_report_params is not None:
         val.update(report=a.val_report_params)
     ckpt = {"path": a.save, "every": a.save_every} if a.save else None
-    kw = {"sensor": sensor_of(a)} if sensor_of(a) is not None else {}      # without a model fit is called as ever
-    kw.update(prep.set_options())
-    res = fit(model, ts, a.steps, scale=a.scale, crop=a.crop, batch=a.batch, lr=a.lr, dtype=a.dtype, rng=rng,
-              log_every=a.log_every, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,
-              args=args, emit=emit, clip_norm=a.clip_norm, skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema,
-              lr_schedule=a.lr_schedule, warmup=a.warmup_steps, lr_min=a.lr_min, lr_steps=a.lr_steps,
-              mask_holes=a.mask_holes, min_valid=a.min_valid, degrade_holes=a.degrade_holes, **kw)
+    res = fit(model, ts, a.steps, rng=rng, process_group=group, val=val, ckpt=ckpt, start_step=start, opt_state=opt_state,
+              args=args, emit=emit, **fit_kwargs(a))
     res["model"] = model
     return res
 
