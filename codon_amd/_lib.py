@@ -209,6 +209,8 @@ SIGNATURES = {
     "codon_cloud_workspace_bytes": (_S, [_I, _I, _I]),
     "codon_cloud_points": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _P, C.POINTER(C.c_int32), C.c_double, _I, _I, _I, _I, _P, _I, _P, _P, _P,
                                      _P, _S, _P]),
+    "codon_cloud_mesh_workspace_bytes": (_S, [_I, _I, _I]),
+    "codon_cloud_mesh": (C.c_int, [_I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _S, _P]),
     "codon_undistort_tiles_bytes": (_S, [_I, _I]),
     "codon_undistort_plan": (C.c_int, [_I, _I, _I, _I, _P, _P, _P]),
     "codon_undistort": (C.c_int, [_I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),

@@ -6,6 +6,7 @@ a binary little-endian PLY that a viewer opens.  The normal map (--normal-maps) 
     python -m codon_amd.cloud --depth DIR --calib FILE --out DIR [--color DIR] [--camera {color,depth}] [--scale {1,4,8,16}]
                               [--depth-bits {8,16}] [--depth-max N] [--depth-unit M] [--no-normals] [--normal-radius R]
                               [--normal-tolerance CODES] [--normal-tolerance-rel F] [--normal-maps DIR] [--stats]
+                              [--mesh [--mesh-tolerance CODES] [--mesh-tolerance-rel F]]
 
 The definition (tests/cloud_ref.py; csrc/cloud.hip): the camera is two int32 ray tables in Q20, float64 on the host, once; a point
 is code times ray in int64, one multiply in double and one conversion per component.  A normal is the cross product of two integer
@@ -14,9 +15,15 @@ tangents, each between the pixels --normal-radius steps away along an axis that 
 pixel without a tangent on either axis has no normal (three zeros) and is still a point.  Records are packed on the device in
 row-major order of the pixels -- count, scan, emit: three launches -- and the file's body is the device's bytes; the only host
 synchronisation is the read of the counts, which sizes the download.  The four defaults (radius, tolerance, tolerance-rel, unit)
-are untuned.  Not handled: triangles (a mesh); a distorted camera (undistort first); ranges along the ray (`register --radial`
-converts them); normals smoothed over more than two pixels per axis; any format other than PLY.  (The normal-angle error
-between a label's normals and an output's is `infer --report --report-normals`, DESIGN 12.20: the same cd_normal.)"""
+are untuned.  With --mesh the file is a triangle mesh over the same vertices (tests/mesh_ref.py; csrc/mesh_tile.h): a
+pixel quad gives up to two triangles, each when its three corners are pairwise LINKED under --mesh-tolerance (one step, sides and
+diagonals alike) and --mesh-tolerance-rel (both untuned); a quad of four takes the diagonal with the smaller code difference, a
+quad of three has one candidate.  The 13-byte face records are packed on the device in row-major order of the quads -- six more
+launches -- and the face count is read back with the point counts.  Not handled: in a mesh, hole filling, decimation, joining a
+foreground to a background (unlinked corners give no triangle), and a retry of the other diagonal; a distorted camera (undistort
+first); ranges along the ray (`register --radial` converts them); normals smoothed over more than two pixels per axis; any format
+other than PLY.  (The normal-angle error between a label's normals and an output's is `infer --report --report-normals`, DESIGN
+12.20: the same cd_normal.)"""
 from __future__ import annotations
 
 import argparse
@@ -38,10 +45,16 @@ MAX_RADIUS = 8
 DEFAULTS = dict(depth_unit=0.001, radius=2, tolerance=2, tolerance_rel=0.02)
 FRAME = "comment x right, y down, z forward, in metres"
 STATS = ("points", "normals")
+MESH_DEFAULTS = dict(tolerance=DEFAULTS["tolerance"], tolerance_rel=DEFAULTS["tolerance_rel"])       # cloud's link defaults: untuned
+FACE_REC = 13                                  # the byte 3 and three int32 vertex indices
+FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
 # the packed body (B, h w rec) uint8 and counts (B, 2) int32 (points, points with a normal) on the device, the bytes of a record,
 # the normal map (B, h, w, 3) uint8 or None
 Cloud = collections.namedtuple("Cloud", "body counts rec normal_map")
+# the packed face records (B, 2 (h - 1) (w - 1) 13) uint8 and counts (B) int32 (faces) on the device: image b's faces are
+# body[b, :counts[b] * 13], their indices positions in the body of the same codes' Cloud
+Faces = collections.namedtuple("Faces", "body counts")
 
 
 def scaled_camera(cam: Camera, scale: int) -> Camera:
@@ -86,27 +99,44 @@ def record_dtype(normals: bool, color: bool) -> np.dtype:
     return np.dtype(f)
 
 
-def ply_header(count: int, normals: bool, color: bool) -> bytes:
-    """The fixed header of `count` packed records"""
+def ply_header(count: int, normals: bool, color: bool, faces: int = None) -> bytes:
+    """The fixed header of `count` packed records; faces: None, or the number of 13-byte face records behind them"""
     integer("ply_header", "count", count, 0, None, "an integer, 0 or more")
+    if faces is not None:
+        integer("ply_header", "faces", faces, 0, None, "None, or an integer, 0 or more")
     lines = ["ply", "format binary_little_endian 1.0", FRAME, f"element vertex {int(count)}"]
     lines += [f"property float {n}" for n in "xyz"]
     if normals:
         lines += [f"property float {n}" for n in ("nx", "ny", "nz")]
     if color:
         lines += [f"property uchar {n}" for n in ("red", "green", "blue")]
+    if faces is not None:
+        lines += [f"element face {int(faces)}", "property list uchar int vertex_indices"]
     return ("\n".join(lines + ["end_header"]) + "\n").encode("ascii")
 
 
-def write_ply(path: str, body, count: int, normals: bool, color: bool):
-    """The header and the first count * rec bytes of `body` (bytes, or a uint8 array): nothing is interleaved here"""
+def write_ply(path: str, body, count: int, normals: bool, color: bool, faces=None, face_count: int = 0):
+    """The header and the first count * rec bytes of `body` (bytes, or a uint8 array): nothing is interleaved here.  faces: None,
+    or the face records (bytes, or a uint8 array): their first face_count * 13 bytes follow the vertices"""
     raw = body.tobytes() if isinstance(body, np.ndarray) else bytes(body)
     need = int(count) * record_size(normals, color)
     if len(raw) < need:
         raise ValueError(f"write_ply: {len(raw)} bytes of body, and {count} records take {need}")
+    if faces is None:
+        if face_count:
+            raise ValueError(f"write_ply: face_count {face_count} without faces")
+        with open(path, "wb") as fh:
+            fh.write(ply_header(count, normals, color))
+            fh.write(raw[:need])
+        return
+    tri = faces.tobytes() if isinstance(faces, np.ndarray) else bytes(faces)
+    take = int(face_count) * FACE_REC
+    if len(tri) < take:
+        raise ValueError(f"write_ply: {len(tri)} bytes of faces, and {face_count} faces take {take}")
     with open(path, "wb") as fh:
-        fh.write(ply_header(count, normals, color))
+        fh.write(ply_header(count, normals, color, int(face_count)))
         fh.write(raw[:need])
+        fh.write(tri[:take])
 
 
 def read_ply(path: str) -> np.ndarray:
@@ -131,6 +161,59 @@ def read_ply(path: str) -> np.ndarray:
     if len(body) != count * dt.itemsize:
         raise ValueError(f"read_ply: {path}: {len(body)} bytes of body, and {count} records take {count * dt.itemsize}")
     return np.frombuffer(body, dtype=dt)
+
+
+def read_mesh(path: str):
+    """A file `write_ply` wrote with faces -> (vertices: the structured array read_ply gives, faces: (F, 3) int32).  Anything
+    else, a file without a face element included, is refused by name"""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    end = raw.find(b"end_header\n")
+    if not raw.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"read_mesh: {path} is not a PLY file")
+    lines = raw[:end].decode("ascii", errors="replace").split("\n")
+    try:
+        count = int(next(ln for ln in lines if ln.startswith("element vertex ")).split()[2])
+        tris = int(next(ln for ln in lines if ln.startswith("element face ")).split()[2])
+    except (StopIteration, ValueError):
+        raise ValueError(f"read_mesh: {path} names no vertex count or no face count") from None
+    names = [ln.split()[-1] for ln in lines if ln.startswith("property ")]
+    normals, color = "nx" in names, "red" in names
+    body = raw[end + len(b"end_header\n"):]
+    if raw[:end + len(b"end_header\n")] != ply_header(count, normals, color, tris):
+        raise ValueError(f"read_mesh: {path}: not the header codon_amd.cloud writes")
+    dt = record_dtype(normals, color)
+    need = count * dt.itemsize + tris * FACE_REC
+    if len(body) != need:
+        raise ValueError(f"read_mesh: {path}: {len(body)} bytes of body, and {count} records with {tris} faces take {need}")
+    rec = np.frombuffer(body, dtype=FACE_DTYPE, count=tris, offset=count * dt.itemsize)
+    if not (rec["n"] == 3).all():
+        raise ValueError(f"read_mesh: {path}: a face that is no triangle")
+    return np.frombuffer(body, dtype=dt, count=count), np.ascontiguousarray(rec["v"])
+
+
+def triangulate(codes: torch.Tensor, tolerance: int = MESH_DEFAULTS["tolerance"], tolerance_rel: float = MESH_DEFAULTS["tolerance_rel"],
+                depth_max: int = None) -> Faces:
+    """codes: (h, w) or (B, h, w) uint8 codes, or u16 codes as int16 / uint16, 0 a hole, on the device -> Faces: the triangles of
+    the pixel quads whose corners are linked under tolerance (codes, for one step) and tolerance_rel, over the vertices
+    Unprojection gives for the same codes.  Faces depend on the codes alone: no camera.  Six launches (one for a plane without a
+    quad, which has no face); no host synchronisation."""
+    who = "cloud_mesh"
+    p = K.code_planes(who, codes, depth_max)
+    B, h, w, top = p.B, p.h, p.w, p.top
+    tol = integer(who, "tolerance", tolerance, 0, 65535, "an integer number of codes, 0 .. the largest code")
+    rq = rel_q16(who, tolerance_rel)
+    if tol > top:
+        raise ValueError(f"{who}: tolerance {tol} above the largest code {top}")
+    dev = p.dev
+    body = torch.empty((B, 2 * (h - 1) * (w - 1) * FACE_REC), dtype=torch.uint8, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    P_ = C.c_void_p
+    with ops._on(dev):
+        ws = K.workspace(who, "codon_cloud_mesh_workspace_bytes", dev, B, h, w, batched=True)
+        L.check(L.load().codon_cloud_mesh(B, h, w, p.ptr, p.fmt, top, tol, rq, P_(body.data_ptr()) if body.numel() else None,
+                                          P_(counts.data_ptr()), P_(ws.data_ptr()), ws.numel(), ops._stream(dev)), who)
+    return Faces(body, counts)
 
 
 class Unprojection:
@@ -228,7 +311,12 @@ def parse_args(argv=None):
     ap.add_argument("--normal-tolerance-rel", type=float, default=DEFAULTS["tolerance_rel"], metavar="F",
                     help="... plus this fraction of the smaller code (default 0.02, untuned)")
     ap.add_argument("--normal-maps", default=None, metavar="DIR", help="write the normals as RGB PNGs under the files' own names")
-    ap.add_argument("--stats", action="store_true", help="print points= and normals= per file")
+    ap.add_argument("--stats", action="store_true", help="print points= and normals= per file (and faces= with --mesh)")
+    ap.add_argument("--mesh", action="store_true", help="write triangles too: NAME.ply is a mesh over the same vertices")
+    ap.add_argument("--mesh-tolerance", type=int, default=None, metavar="CODES",
+                    help=f"the corners of a triangle differ by at most this ... (default {MESH_DEFAULTS['tolerance']}, untuned)")
+    ap.add_argument("--mesh-tolerance-rel", type=float, default=None, metavar="F",
+                    help=f"... plus this fraction of the smaller code (default {MESH_DEFAULTS['tolerance_rel']}, untuned)")
     a = ap.parse_args(argv)
     a.top = K.depth_args_of(ap, a)
     if a.color is not None and a.scale != 1:
@@ -247,6 +335,17 @@ def parse_args(argv=None):
         rel_q16("cloud", a.normal_tolerance_rel)
     except ValueError:
         ap.error(f"--normal-tolerance-rel {a.normal_tolerance_rel} must be in [0, 1)")
+    for name in ("tolerance", "tolerance_rel"):
+        if getattr(a, "mesh_" + name) is None:
+            setattr(a, "mesh_" + name, MESH_DEFAULTS[name])
+        elif not a.mesh:
+            ap.error(f"--mesh-{name.replace('_', '-')} without --mesh")
+    if not 0 <= a.mesh_tolerance <= a.top:
+        ap.error(f"--mesh-tolerance {a.mesh_tolerance} must be in [0, {a.top}], the largest code")
+    try:
+        rel_q16("cloud", a.mesh_tolerance_rel)
+    except ValueError:
+        ap.error(f"--mesh-tolerance-rel {a.mesh_tolerance_rel} must be in [0, 1)")
     for other in ("depth", "color"):
         d = getattr(a, other)
         if d is not None and os.path.abspath(a.out) == os.path.abspath(d):
@@ -298,13 +397,20 @@ def main(argv=None, emit=print):
                 raise ValueError(f"{path}: no colour image for {os.path.join(a.depth, name)}")
             color = torch.from_numpy(_read_color(path, *codes.shape)).to(un.device)
         got = un(codes, color, a.depth_max, normal_map=a.normal_maps is not None)
-        points, normals = (int(v) for v in got.counts.cpu().numpy().view(np.uint32)[0])      # the one host synchronisation
+        tri = triangulate(codes, a.mesh_tolerance, a.mesh_tolerance_rel, a.depth_max) if a.mesh else None
+        words = got.counts.reshape(-1) if tri is None else torch.cat([got.counts.reshape(-1), tri.counts])
+        points, normals, *faces = (int(v) for v in words.cpu().numpy().view(np.uint32))     # the one host synchronisation
         body = got.body[0, :points * got.rec].cpu().numpy()
-        write_ply(os.path.join(a.out, os.path.splitext(name)[0] + ".ply"), body, points, un.normals, color is not None)
+        path, line = os.path.join(a.out, os.path.splitext(name)[0] + ".ply"), f"{name} points={points} normals={normals}"
+        if tri is None:
+            write_ply(path, body, points, un.normals, color is not None)
+        else:
+            write_ply(path, body, points, un.normals, color is not None, tri.body[0, :faces[0] * FACE_REC].cpu().numpy(), faces[0])
+            line += f" faces={faces[0]}"
         if a.normal_maps is not None:
             from PIL import Image
             Image.fromarray(got.normal_map[0].cpu().numpy(), mode="RGB").save(os.path.join(a.normal_maps, name))
-        emit(f"{name} points={points} normals={normals}" if a.stats else name)
+        emit(line if a.stats else name)
     return 0
 
 

@@ -257,17 +257,18 @@ CODON_FL_HD void wg_cloud_count(G wg, long r, long b, const void* in, int h, int
   }
 }
 
-// workgroup b of grid (B), CD_SCAN_THREADS threads: the block words of image b to their exclusive scan, counts[b] = (their sum,
-// 0).  LDS: cnt CD_SCAN_THREADS words, part 16
+// The scan body, one workgroup of CD_SCAN_THREADS threads: the `blocks` words at `word` to their exclusive scan in place, a thread
+// taking `per` consecutive words (per CD_SCAN_THREADS >= blocks; blocks may be 0); *total = their sum, and *zero = 0 where zero is
+// not null.  The cloud's block words and the mesh's run words (mesh_tile.h) both go through it.  LDS: cnt CD_SCAN_THREADS words,
+// part 16
 template <class G>
-CODON_FL_HD void wg_cloud_scan(G wg, long b, int h, int w, unsigned* ws, unsigned* counts, unsigned* cnt, unsigned* part) {
-  const CdPlan p = cd_plan(h, w);
-  unsigned* word = ws + b * p.stride;
+CODON_FL_HD void wg_scan_words(G wg, unsigned* word, int blocks, int per, unsigned* total, unsigned* zero, unsigned* cnt,
+                               unsigned* part) {
   WG_EACH(wg, tid) {
     unsigned s = 0;
-    for (int q = 0; q < p.per; ++q) {
-      const int at = tid * p.per + q;
-      if (at < p.blocks) s += word[at];
+    for (int q = 0; q < per; ++q) {
+      const int at = tid * per + q;
+      if (at < blocks) s += word[at];
     }
     cnt[tid] = s;
   }
@@ -276,19 +277,28 @@ CODON_FL_HD void wg_cloud_scan(G wg, long b, int h, int w, unsigned* ws, unsigne
   wg.sync();
   WG_EACH(wg, tid) {
     unsigned s = cd_prefix<16>(tid, cnt, part);
-    for (int q = 0; q < p.per; ++q) {
-      const int at = tid * p.per + q;
-      if (at < p.blocks) {
+    for (int q = 0; q < per; ++q) {
+      const int at = tid * per + q;
+      if (at < blocks) {
         const unsigned c = word[at];
         word[at] = s;
         s += c;
       }
     }
     if (tid == 0) {
-      counts[b * CD_COUNTS + CD_POINTS] = cd_total<16>(part);
-      counts[b * CD_COUNTS + CD_NORMALS] = 0u;
+      *total = cd_total<16>(part);
+      if (zero) *zero = 0u;
     }
   }
+}
+
+// workgroup b of grid (B), CD_SCAN_THREADS threads: the block words of image b to their exclusive scan, counts[b] = (their sum,
+// 0).  LDS: cnt CD_SCAN_THREADS words, part 16
+template <class G>
+CODON_FL_HD void wg_cloud_scan(G wg, long b, int h, int w, unsigned* ws, unsigned* counts, unsigned* cnt, unsigned* part) {
+  const CdPlan p = cd_plan(h, w);
+  wg_scan_words(wg, ws + b * p.stride, p.blocks, p.per, counts + b * CD_COUNTS + CD_POINTS, counts + b * CD_COUNTS + CD_NORMALS, cnt,
+                part);
 }
 
 // workgroup (r, b) of grid (blocks, B).  body: image b's records start at byte b h w REC; color (a form with colour): (B, h, w) or

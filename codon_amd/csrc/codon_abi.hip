@@ -14,6 +14,7 @@
 #include "register_tile.h"
 #include "clean_tile.h"
 #include "cloud_tile.h"
+#include "mesh_tile.h"
 #include "normal_tile.h"
 #include "sensor_pixel.h"
 #include "stretch_tile.h"
@@ -1297,6 +1298,26 @@ int codon_cloud_points(int32_t batch, int32_t height, int32_t width, const void*
   if (const int st = check_workspace(who, workspace_bytes, cloud_workspace_bytes(batch, height, width))) return st;
   return cloud_points(batch, height, width, codes, fmt, rx, ry, m, normals ? radius : 0, tol_abs, tol_rel_q16, color, color_channels,
                       body, counts, normal_map, workspace, (hipStream_t)stream);
+}
+
+// ---- depth maps as triangle meshes ----------------------------------------------------------------------------------
+size_t codon_cloud_mesh_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
+  return cloud_mesh_workspace_bytes(batch, height, width);
+}
+
+int codon_cloud_mesh(int32_t batch, int32_t height, int32_t width, const void* codes, int32_t fmt, int32_t top, int32_t tol_abs,
+                     int32_t tol_rel_q16, uint8_t* faces, uint32_t* counts, void* workspace, size_t workspace_bytes,
+                     codon_stream_t stream) {
+  // a plane without a quad has no face: its `faces` holds no byte and may be NULL
+  CODON_REQUIRE(codes && counts && workspace && (faces || height == 1 || width == 1), CODON_ERR_BAD_ARG, "cloud_mesh: null pointer");
+  const char* who = "cloud_mesh";
+  if (const int st = check_planes(who, fmt, batch, height, width, MS_MAX_SIDE, top)) return st;
+  if (const int st = check_link_tolerances(who, tol_abs, top, tol_rel_q16, MS_MAX_REL)) return st;
+  const bool planes_ok = ((uintptr_t)codes & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
+  const bool words_ok = ((uintptr_t)counts & 3) == 0 && ((uintptr_t)workspace & 15) == 0;
+  CODON_REQUIRE(planes_ok && words_ok, CODON_ERR_BAD_ARG, "cloud_mesh: unaligned plane, counts or workspace");
+  if (const int st = check_workspace(who, workspace_bytes, cloud_mesh_workspace_bytes(batch, height, width))) return st;
+  return cloud_mesh(batch, height, width, codes, fmt, tol_abs, tol_rel_q16, faces, counts, workspace, (hipStream_t)stream);
 }
 
 // ---- undistortion of colour images ---------------------------------------------------------------------------------

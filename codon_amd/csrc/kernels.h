@@ -199,6 +199,11 @@ size_t cloud_workspace_bytes(int B, int h, int w);
 int cloud_points(int B, int h, int w, const void* in, int fmt, const int* rx, const int* ry, double m, int radius, int tol_abs,
                  int tol_rel_q16, const void* color, int channels, void* body, void* counts, void* nmap, void* workspace,
                  hipStream_t stream);
+// cloud.hip, mesh_tile.h; faces: (B, 2 (h - 1) (w - 1) 13) bytes; counts: (B) u32; workspace: the cloud's block words, a u32 per
+// 1024 quads of every image, (B, 2) u32 and the (B, h, w) int32 index plane
+size_t cloud_mesh_workspace_bytes(int B, int h, int w);
+int cloud_mesh(int B, int h, int w, const void* in, int fmt, int tol_abs, int tol_rel_q16, void* faces, void* counts, void* workspace,
+               hipStream_t stream);
 
 // undistort.hip; in: (B, hs, ws, channels) u8, out: (B, ho, wo, channels) u8; map (ho, wo, 2) int32, tiles (the words of
 // undistort_tiles_bytes) and weights (32, 4) int16 on the device.  undistort_plan: HOST -- the tile table and the four counts of a

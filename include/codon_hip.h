@@ -1047,6 +1047,37 @@ int codon_cloud_points(int32_t batch, int32_t height, int32_t width, const void*
                        int32_t tol_rel_q16, const uint8_t* color, int32_t color_channels, uint8_t* body, uint32_t* counts,
                        uint8_t* normal_map, void* workspace, size_t workspace_bytes, codon_stream_t stream);
 
+/* ---- depth maps as triangle meshes (codon_amd.cloud.triangulate) -------------------------------------------------
+ * Nothing in the reference: it stops at the depth map.  A DEFINITION, in codon_amd/csrc/cloud.hip and mesh_tile.h, restated in
+ * numpy in tests/mesh_ref.py, equal bytes required.
+ *
+ * codes: (batch, height, width) codes, u8 or u16, 0 a hole.  The vertices are codon_cloud_points' own: the index of a non-zero code
+ * is its rank among the non-zero codes of its plane in row-major order.  Quad (i, j), i < height - 1, j < width - 1, has the corners
+ * a = (i, j), b = (i, j + 1), c = (i + 1, j), d = (i + 1, j + 1); two corners are linked under codon_clean_depth's rule with tol_abs
+ * for ONE step (sides and diagonals alike) and tol_rel_q16, and a hole links to nothing.  A triangle is emitted when its three
+ * corners are pairwise linked.  Four non-zero corners: the diagonal is a-d if |k_a - k_d| <= |k_b - k_c|, else b-c; a-d gives
+ * (a, c, d) then (a, d, b), b-c gives (a, c, b) then (b, c, d); each on its own, the other diagonal is not retried.  Three: the one
+ * of those four triangles without the missing corner.  Fewer: none.  The orders face the camera (x right, y down, z forward).
+ * faces: (batch, 2 (height - 1) (width - 1) 13) bytes, no alignment needed: image b's records are the first counts[b] 13 bytes of its
+ * row, in row-major order of the quads, the first-listed triangle first; a record is the byte 3 and three little-endian int32
+ * vertex indices, packed (PLY's `property list uchar int vertex_indices`); the bytes behind them are not written.  counts: (batch)
+ * uint32 ON THE DEVICE, the faces of each image; it needs no initialisation.  A plane with height 1 or width 1 has no quad: zero
+ * faces, and faces may be NULL.
+ *
+ * codon_cloud_mesh_workspace_bytes: HOST ONLY -- the bytes the batch takes (codon_cloud_workspace_bytes' block words, a u32 per
+ * 1024 quads, 8 bytes per image and an int32 per pixel, each part rounded up to 16 bytes), 0 for a batch outside 1 .. 65535 or a
+ * height or width outside 1 .. 4096.  workspace: 16-byte aligned, private to the stream; initialised by the call itself, on the
+ * stream.  Six launches (vertex count, scan, index plane; face count, scan, emit; the face scan alone for a plane without a quad),
+ * which depend on (batch, height, width) alone; no atomic decides a position, no workgroup waits for another; no host
+ * synchronisation.  Refused on the host, before any HIP call: null pointers, an fmt other than CODON_FILL_U8 / _U16, batch outside
+ * 1 .. 65535, a height or width outside 1 .. 4096, top outside 1 .. 65535 or not 255 for u8 codes, tol_abs outside 0 .. top,
+ * tol_rel_q16 outside 0 .. 65535, a u16 plane that is not 2-byte aligned, counts not 4-byte aligned, a workspace that is not
+ * 16-byte aligned or too small. */
+size_t codon_cloud_mesh_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int codon_cloud_mesh(int32_t batch, int32_t height, int32_t width, const void* codes, int32_t fmt, int32_t top, int32_t tol_abs,
+                     int32_t tol_rel_q16, uint8_t* faces, uint32_t* counts, void* workspace, size_t workspace_bytes,
+                     codon_stream_t stream);
+
 /* ---- undistortion of colour images (codon_amd.undistort) ---------------------------------------------------------
  * Nothing in the reference: its colour images were rectified offline.  A DEFINITION, in codon_amd/csrc/undistort.hip and
  * undistort_tile.h, restated in numpy in tests/undistort_ref.py, equal bits required.  Integers only.

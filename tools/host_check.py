@@ -1,6 +1,6 @@
 """Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
 into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
-guided_fill, jbu, register, clean, undistort, cloud, normal_errors) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+guided_fill, jbu, register, clean, undistort, cloud, mesh, normal_errors) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
 address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
 restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
 
@@ -25,6 +25,7 @@ from tests import eval_ref as E  # noqa: E402
 from tests import fill_ref as F  # noqa: E402
 from tests import guided_fill_ref as R  # noqa: E402
 from tests import jbu_ref as J  # noqa: E402
+from tests import mesh_ref as H  # noqa: E402
 from tests import normal_errors_ref as N  # noqa: E402
 from tests import register_ref as G  # noqa: E402
 from tests import resample_masked_ref as M  # noqa: E402
@@ -304,6 +305,28 @@ def cloud(run, p):
                    "the largest): no report, every byte and count equals tests/cloud_ref.py")
 
 
+def mesh(run, p):
+    """The GPU test's cases (mesh_ref.cases): every shape under every pattern and tolerance; the program runs each in both thread
+    orders, with the face buffer one byte into its allocation"""
+    cases = 0
+    for shape in H.SHAPES:
+        B, h, w = shape
+        for pattern, tol in H.cases(shape):
+            top = H.top_of(pattern)
+            codes = H.plane(shape, pattern)
+            codes.tofile(p("i"))
+            run(0 if top == 255 else 1, B, h, w, H.tolerance_of(tol, top), H.RQ, p("i"), p("f"), p("n"))
+            bodies, counts = H.want(shape, pattern, tol)
+            got = np.fromfile(p("f"), dtype=np.uint8).reshape(B, H.row_bytes(h, w))
+            for b, body in enumerate(bodies):
+                assert got[b, :len(body)].tobytes() == body, (shape, pattern, tol, b)
+                assert (got[b, len(body):] == 0xEE).all(), (shape, pattern, tol, b, "bytes behind the faces")
+            assert np.fromfile(p("n"), dtype=np.uint32).tobytes() == counts.tobytes(), (shape, pattern, tol, "counts")
+            cases += 1
+    return cases, (f"over {len(H.SHAPES)} shapes, {len(H.PATTERNS)} patterns x {len(H.TOLERANCES)} tolerances ({len(H.BIG_CASES)} of them "
+                   "on the largest): no report, every byte and count equals tests/mesh_ref.py")
+
+
 def normal_errors(run, p):
     """The GPU test's cases (normal_errors_ref.cases): every shape under every pattern, radius and noise; the program runs each in
     both thread orders.  Then the per-pair index function over pairs no scene reaches: opposite normals, pairs on a threshold,
@@ -351,6 +374,7 @@ CHECKS = {
     "clean": (clean, [], "cases"),
     "undistort": (undistort, [], "cases"),
     "cloud": (cloud, [], "cases"),
+    "mesh": (mesh, [], "cases"),
     "normal_errors": (normal_errors, [], "cases"),
 }
 
