@@ -13,7 +13,8 @@ pixels among its 8 neighbours inside the plane is removed; one pass over the inp
 it removes the image's corners, above 5 its border.  Rule 2: a connected component (4-connectivity, neighbours in one component
 when linked) of fewer than --min-region pixels of what rule 1 left is removed; 0 or 1 switches it off.  The four defaults are
 untuned.  Not handled: a real structure one pixel wide (a wire) goes with the flying pixels; no confidence or amplitude image is
-read; nothing is filtered over time."""
+read.  A fixed camera's sequence is filtered over time by the step in front of this one, `python -m codon_amd.temporal` (DESIGN
+12.23): the recommended order is temporal -> clean -> register."""
 from __future__ import annotations
 
 import argparse

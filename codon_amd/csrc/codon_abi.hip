@@ -18,6 +18,7 @@
 #include "normal_tile.h"
 #include "sensor_pixel.h"
 #include "stretch_tile.h"
+#include "temporal_tile.h"
 #include "train_record.h"
 #include "undistort_tile.h"
 
@@ -1270,6 +1271,50 @@ int codon_clean_depth(int32_t batch, int32_t height, int32_t width, const void* 
   if (const int st = check_workspace(who, workspace_bytes, clean_workspace_bytes(batch, height, width))) return st;
   return clean_depth(batch, height, width, in, fmt, tol_abs, tol_rel_q16, min_support, min_region, out, counts, workspace,
                      (hipStream_t)stream);
+}
+
+// ---- temporal filter of a fixed camera's depth sequence ------------------------------------------------------------
+// the refusals a call and the chunk query share, in the order of the argument list
+static int check_sequence(const char* who, int frames, int height, int width) {
+  CODON_REQUIRE(frames >= 1 && frames <= TP_MAX_FRAMES, CODON_ERR_BAD_ARG, "%s: frames %d (1..%d)", who, frames, TP_MAX_FRAMES);
+  if (const int st = check_side(who, height, width, "plane", TP_MAX_SIDE)) return st;
+  CODON_REQUIRE((int64_t)frames * height * width < ((int64_t)1 << 31), CODON_ERR_BAD_ARG,
+                "%s: a sequence of %lld codes (%d frames of %dx%d; below 2^31)", who, (long long)frames * height * width, frames, height,
+                width);
+  return CODON_OK;
+}
+
+static int check_window(const char* who, int back, int ahead) {
+  CODON_REQUIRE(back >= 0 && ahead >= 0 && back + ahead < TP_MAX_WINDOW, CODON_ERR_BAD_ARG,
+                "%s: window back %d ahead %d (each at least 0, back + ahead at most %d)", who, back, ahead, TP_MAX_WINDOW - 1);
+  return CODON_OK;
+}
+
+int32_t codon_temporal_chunk_frames(int32_t frames, int32_t height, int32_t width, int32_t back, int32_t ahead) {
+  const char* who = "temporal_chunk_frames";
+  if (check_sequence(who, frames, height, width) || check_window(who, back, ahead)) return 0;
+  return temporal_chunk_frames(frames, height, width, back, ahead);
+}
+
+int codon_temporal_depth(int32_t frames, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top, int32_t back,
+                         int32_t ahead, int32_t tol_abs, int32_t tol_rel_q16, int32_t min_count, int32_t min_fill, void* out,
+                         uint32_t* counts, codon_stream_t stream) {
+  CODON_REQUIRE(in && out, CODON_ERR_BAD_ARG, "temporal_depth: null pointer");
+  const char* who = "temporal_depth";
+  if (const int st = check_sequence(who, frames, height, width)) return st;
+  if (const int st = check_fmt(who, fmt)) return st;
+  if (const int st = check_top(who, fmt, top)) return st;
+  if (const int st = check_window(who, back, ahead)) return st;
+  if (const int st = check_link_tolerances(who, tol_abs, top, tol_rel_q16, TP_MAX_REL)) return st;
+  CODON_REQUIRE(min_count >= 1 && min_count <= TP_MAX_WINDOW, CODON_ERR_BAD_ARG, "temporal_depth: min_count %d (1..%d)", min_count,
+                TP_MAX_WINDOW);
+  CODON_REQUIRE(min_fill >= 0 && min_fill <= TP_MAX_WINDOW, CODON_ERR_BAD_ARG, "temporal_depth: min_fill %d (0..%d)", min_fill,
+                TP_MAX_WINDOW);
+  if (const int st = check_not_same(who, in, out)) return st;
+  const bool planes_ok = (((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
+  CODON_REQUIRE(planes_ok && ((uintptr_t)counts & 3) == 0, CODON_ERR_BAD_ARG, "temporal_depth: unaligned plane or statistics");
+  return temporal_depth(frames, height, width, in, fmt, back, ahead, tol_abs, tol_rel_q16, min_count, min_fill, out, counts,
+                        (hipStream_t)stream);
 }
 
 // ---- depth maps as point clouds with normals -----------------------------------------------------------------------

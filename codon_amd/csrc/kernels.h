@@ -199,6 +199,10 @@ size_t cloud_workspace_bytes(int B, int h, int w);
 int cloud_points(int B, int h, int w, const void* in, int fmt, const int* rx, const int* ry, double m, int radius, int tol_abs,
                  int tol_rel_q16, const void* color, int channels, void* body, void* counts, void* nmap, void* workspace,
                  hipStream_t stream);
+// temporal.hip; in, out: (T, h, w) codes, T h w below 2^31; stats: (T, 4) u32 or null; no workspace
+int temporal_depth(int T, int h, int w, const void* in, int fmt, int back, int ahead, int tol_abs, int tol_rel_q16, int min_count,
+                   int min_fill, void* out, void* stats, hipStream_t stream);
+
 // cloud.hip, mesh_tile.h; faces: (B, 2 (h - 1) (w - 1) 13) bytes; counts: (B) u32; workspace: the cloud's block words, a u32 per
 // 1024 quads of every image, (B, 2) u32 and the (B, h, w) int32 index plane
 size_t cloud_mesh_workspace_bytes(int B, int h, int w);

@@ -64,4 +64,27 @@ __host__ __device__ inline int gate_slice_tiles(int ntiles) { return (ntiles + G
 constexpr int SPF_T = 32;
 constexpr int SPB_T = 32;
 
+// ---- temporal filter (temporal.hip): frames per time chunk, and the window registers of the kernel -----------
+// A workgroup owns TEMPORAL_TILE pixels (temporal_tile.h's TP_TILE) through one chunk of frames and re-reads back + ahead frames
+// at the chunk's seams.  One chunk is the fewest bytes; a small plane under a long sequence is then a handful of workgroups on
+// 256 CUs.  So: as many chunks as bring the launch to TEMPORAL_WORKGROUPS workgroups (four of 34 KiB of LDS per CU), but no
+// chunk shorter than TEMPORAL_MIN_CHUNK frames or than twice the seam (at most a third of the frames read twice).  A function of
+// (T, h, w, back, ahead) alone; codon_temporal_chunk_frames is this function called without a launch.
+constexpr int TEMPORAL_TILE = 1024;
+constexpr int TEMPORAL_WORKGROUPS = 1024;
+constexpr int TEMPORAL_MIN_CHUNK = 8;
+inline int temporal_chunk_frames(int T, int h, int w, int back, int ahead) {
+  const long groups = ((long)h * w + TEMPORAL_TILE - 1) / TEMPORAL_TILE;
+  const long want = (TEMPORAL_WORKGROUPS + groups - 1) / groups;
+  const long even = (T + want - 1) / want;
+  const long least = 2 * (back + ahead) > TEMPORAL_MIN_CHUNK ? 2 * (back + ahead) : TEMPORAL_MIN_CHUNK;
+  const long len = even > least ? even : least;
+  return (int)(len < T ? len : T);
+}
+// the window registers: the smallest of 3, 5, 9, 15 that holds back + ahead + 1 frames
+inline int temporal_cap(int back, int ahead) {
+  const int n = back + ahead + 1;
+  return n <= 3 ? 3 : n <= 5 ? 5 : n <= 9 ? 9 : 15;
+}
+
 }  // namespace codon

@@ -1015,6 +1015,35 @@ int codon_clean_depth(int32_t batch, int32_t height, int32_t width, const void* 
                       int32_t tol_rel_q16, int32_t min_support, int32_t min_region, void* out, uint32_t* counts, void* workspace,
                       size_t workspace_bytes, codon_stream_t stream);
 
+/* ---- temporal filter of a fixed camera's depth sequence (codon_amd.temporal) -------------------------------------
+ * Nothing in the reference: it reads single images.  A DEFINITION, in codon_amd/csrc/temporal.hip and temporal_tile.h, restated in
+ * numpy in tests/temporal_ref.py, equal bits required.  Integers only.
+ *
+ * in, out: (frames, height, width) codes, u8 or u16, 0 a hole, frame order being time; frames height width < 2^31.  The window of
+ * frame t is the frames s in [max(0, t - back), min(frames - 1, t + ahead)], n_w of them, at most 15.  Two codes are LINKED under
+ * codon_clean_depth's rule with tol_abs and tol_rel_q16.  Per pixel and frame, v the input code, every read of `in` (a single
+ * pass, not idempotent): 1. v != 0: Lk = the window's samples at that pixel linked to v, v among them, n = |Lk|; if n >=
+ * min(min_count, n_w), out = (2 sum Lk + n) / (2 n), the mean rounded half up; otherwise the pixel is REJECTED and goes on with
+ * 2.  min_count 1 switches rejection off.  2. v == 0, or rejected: min_fill 0: out = 0.  Otherwise S = the non-zero samples of
+ * the window, k = |S|; k < min_fill: out = 0; else m = the lower median of S (rank (k - 1) >> 1 in sorted order), Lm = the samples
+ * linked to m, out = the same rounded mean of Lm if |Lm| >= min_fill, else 0.  min_fill is not clamped by n_w.  counts: NULL, or
+ * (frames, 4) uint32 ON THE DEVICE: valid inputs, rejected pixels, non-zero outputs where the input was 0 or rejected, accepted
+ * pixels whose output differs from the input; it needs no initialisation.
+ *
+ * Two launches (the statistics to 0; the filter), which depend on (frames, height, width, back, ahead) alone and not on counts;
+ * no workspace; no host synchronisation.  A workgroup walks 1024 pixels through one chunk of frames and reads back + ahead frames
+ * beyond the chunk's ends.  codon_temporal_chunk_frames: HOST ONLY -- the frames per chunk, the launcher's own rule
+ * (csrc/launch_rules.h) called without a launch; 0 for arguments codon_temporal_depth refuses.  Refused on the host, before any
+ * HIP call, in this order: null pointers (counts may be NULL), frames outside 1 .. 4096, a height or width outside 1 .. 4096,
+ * frames height width of 2^31 or more, an fmt other than CODON_FILL_U8 / _U16, top outside 1 .. 65535 or not 255 for u8 codes,
+ * back or ahead below 0 or back + ahead above 14, tol_abs outside 0 .. top, tol_rel_q16 outside 0 .. 65535, min_count outside
+ * 1 .. 15, min_fill outside 0 .. 15, out == in (the window reads frames the call would already have overwritten), a u16 plane
+ * that is not 2-byte aligned, counts not 4-byte aligned.  `out` is untouched on a refusal. */
+int32_t codon_temporal_chunk_frames(int32_t frames, int32_t height, int32_t width, int32_t back, int32_t ahead);
+int codon_temporal_depth(int32_t frames, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top, int32_t back,
+                         int32_t ahead, int32_t tol_abs, int32_t tol_rel_q16, int32_t min_count, int32_t min_fill, void* out,
+                         uint32_t* counts, codon_stream_t stream);
+
 /* ---- depth maps as point clouds with normals (codon_amd.cloud) ---------------------------------------------------
  * Nothing in the reference: it stops at the depth map.  A DEFINITION, in codon_amd/csrc/cloud.hip and cloud_tile.h, restated in
  * numpy in tests/cloud_ref.py, equal bytes required.

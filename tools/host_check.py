@@ -1,6 +1,6 @@
 """Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
 into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
-guided_fill, jbu, register, clean, undistort, cloud, mesh, normal_errors) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+guided_fill, jbu, register, clean, undistort, cloud, mesh, normal_errors, temporal) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
 address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
 restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
 
@@ -31,6 +31,7 @@ from tests import register_ref as G  # noqa: E402
 from tests import resample_masked_ref as M  # noqa: E402
 from tests import sensor_ref as S  # noqa: E402
 from tests import stretch_ref as T  # noqa: E402
+from tests import temporal_ref as V  # noqa: E402
 from tests import undistort_ref as U  # noqa: E402
 
 FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
@@ -361,6 +362,23 @@ def normal_errors(run, p):
                    "normals: no report, every word and map equals tests/normal_errors_ref.py")
 
 
+def temporal(run, p):
+    """The GPU test's cases (temporal_ref.cases): the planes under the windows at every length, parameters, patterns and formats
+    in turn; the program runs each one element into larger buffers and on a 16-byte boundary, in both thread orders, with and
+    without statistics"""
+    rows = V.cases()
+    for case in rows:
+        T_, h, w, Bk, Ah, M_, F_, A, Rq, pattern, top = case
+        V.sequence(T_, h, w, pattern, top).tofile(p("i"))
+        run(0 if top == 255 else 1, T_, h, w, Bk, Ah, A, Rq, M_, F_, V.chunk_frames(T_, h, w, Bk, Ah), p("i"), p("o"), p("s"))
+        want, stats = V.want(case)
+        assert np.fromfile(p("o"), dtype=want.dtype).tobytes() == want.tobytes(), case
+        assert np.fromfile(p("s"), dtype=np.uint32).tobytes() == stats.tobytes(), (case, "statistics")
+    return len(rows), (f"over {len(V.PLANES)} planes x {len(V.WINDOWS)} windows at every length, the {len(V.PARAMS)} parameter forms, "
+                       f"{len(V.PATTERNS)} patterns and {len(V.FORMATS)} formats in turn: no report, every byte and count equals "
+                       "tests/temporal_ref.py")
+
+
 # name -> (check, extra compile flags, what the count counts)
 CHECKS = {
     "d4": (d4, ["-ffp-contract=off"], "runs"),
@@ -376,6 +394,7 @@ CHECKS = {
     "cloud": (cloud, [], "cases"),
     "mesh": (mesh, [], "cases"),
     "normal_errors": (normal_errors, [], "cases"),
+    "temporal": (temporal, [], "cases"),
 }
 
 
