@@ -208,6 +208,8 @@ SIGNATURES = {
     "codon_clean_depth": (C.c_int, [_I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _S, _P]),
     "codon_temporal_chunk_frames": (_I, [_I, _I, _I, _I, _I]),
     "codon_temporal_depth": (C.c_int, [_I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "codon_temporal_ring_frames": (_I, []),
+    "codon_temporal_push": (C.c_int, [_I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "codon_cloud_workspace_bytes": (_S, [_I, _I, _I]),
     "codon_cloud_points": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _P, C.POINTER(C.c_int32), C.c_double, _I, _I, _I, _I, _P, _I, _P, _P, _P,
                                      _P, _S, _P]),

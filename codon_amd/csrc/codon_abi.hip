@@ -1317,6 +1317,34 @@ int codon_temporal_depth(int32_t frames, int32_t height, int32_t width, const vo
                         (hipStream_t)stream);
 }
 
+// ---- temporal filter of a depth stream, frame by frame --------------------------------------------------------------
+int32_t codon_temporal_ring_frames(void) { return TP_SLOTS; }
+
+int codon_temporal_push(int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top, int32_t back, int32_t ahead,
+                        int32_t tol_abs, int32_t tol_rel_q16, int32_t min_count, int32_t min_fill, void* ring, uint32_t* state,
+                        void* out, uint32_t* counts, codon_stream_t stream) {
+  const char* who = "temporal_push";
+  if (const int st = check_side(who, height, width, "plane", TP_MAX_SIDE)) return st;
+  if (const int st = check_fmt(who, fmt)) return st;
+  if (const int st = check_top(who, fmt, top)) return st;
+  if (const int st = check_window(who, back, ahead)) return st;
+  if (const int st = check_link_tolerances(who, tol_abs, top, tol_rel_q16, TP_MAX_REL)) return st;
+  CODON_REQUIRE(min_count >= 1 && min_count <= TP_MAX_WINDOW, CODON_ERR_BAD_ARG, "temporal_push: min_count %d (1..%d)", min_count,
+                TP_MAX_WINDOW);
+  CODON_REQUIRE(min_fill >= 0 && min_fill <= TP_MAX_WINDOW, CODON_ERR_BAD_ARG, "temporal_push: min_fill %d (0..%d)", min_fill,
+                TP_MAX_WINDOW);
+  CODON_REQUIRE(ring && state && out, CODON_ERR_BAD_ARG, "temporal_push: null pointer");
+  if (const int st = check_not_same(who, in, out)) return st;
+  const uintptr_t plane = (uintptr_t)height * width * fl_elem_bytes(fmt), r0 = (uintptr_t)ring, r1 = r0 + TP_SLOTS * plane;
+  const bool in_hit = in && (uintptr_t)in < r1 && (uintptr_t)in + plane > r0, out_hit = (uintptr_t)out < r1 && (uintptr_t)out + plane > r0;
+  CODON_REQUIRE(!in_hit && !out_hit, CODON_ERR_BAD_ARG, "temporal_push: the ring overlaps %s", in_hit ? "in" : "out");
+  const bool planes_ok = (((uintptr_t)in | (uintptr_t)out | r0) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
+  CODON_REQUIRE(planes_ok && (((uintptr_t)state | (uintptr_t)counts) & 3) == 0, CODON_ERR_BAD_ARG,
+                "temporal_push: unaligned plane, ring, state or statistics");
+  return temporal_push(height, width, in, fmt, back, ahead, tol_abs, tol_rel_q16, min_count, min_fill, ring, state, out, counts,
+                       (hipStream_t)stream);
+}
+
 // ---- depth maps as point clouds with normals -----------------------------------------------------------------------
 size_t codon_cloud_workspace_bytes(int32_t batch, int32_t height, int32_t width) { return cloud_workspace_bytes(batch, height, width); }
 

@@ -202,6 +202,10 @@ int cloud_points(int B, int h, int w, const void* in, int fmt, const int* rx, co
 // temporal.hip; in, out: (T, h, w) codes, T h w below 2^31; stats: (T, 4) u32 or null; no workspace
 int temporal_depth(int T, int h, int w, const void* in, int fmt, int back, int ahead, int tol_abs, int tol_rel_q16, int min_count,
                    int min_fill, void* out, void* stats, hipStream_t stream);
+// temporal_push.hip; in: (h, w) codes or null (a flush step); ring: 16 planes of (h, w) codes; state: 2 u32; out: (h, w) codes;
+// stats: 4 u32 or null; no workspace
+int temporal_push(int h, int w, const void* in, int fmt, int back, int ahead, int tol_abs, int tol_rel_q16, int min_count,
+                  int min_fill, void* ring, void* state, void* out, void* stats, hipStream_t stream);
 
 // cloud.hip, mesh_tile.h; faces: (B, 2 (h - 1) (w - 1) 13) bytes; counts: (B) u32; workspace: the cloud's block words, a u32 per
 // 1024 quads of every image, (B, 2) u32 and the (B, h, w) int32 index plane

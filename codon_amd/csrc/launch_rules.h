@@ -86,5 +86,9 @@ inline int temporal_cap(int back, int ahead) {
   const int n = back + ahead + 1;
   return n <= 3 ? 3 : n <= 5 ? 5 : n <= 9 ? 9 : 15;
 }
+// ---- temporal stream (temporal_push.hip): a step is one workgroup (the counters, the statistics row to 0) and
+// then one workgroup per TEMPORAL_TILE pixels of the plane -- a function of (h, w) alone, the same for a push and a flush, for
+// every frame index and with or without statistics.  The window registers are temporal_cap's.
+inline long temporal_push_groups(int h, int w) { return ((long)h * w + TEMPORAL_TILE - 1) / TEMPORAL_TILE; }
 
 }  // namespace codon

@@ -135,6 +135,42 @@ CODON_FL_HD unsigned tp_fill(const tp_quad* wnd, int q, const TpArgs& a) {
   return n >= (unsigned)a.min_fill ? tp_mean(sum, n) : 0u;
 }
 
+// steps 1 and 2 for a thread's four pixels -- THE one text of the arithmetic, for the sequence body (tp_step) and the stream body
+// (tp_push_step): wnd the window's samples (a register beyond its nw frames is 0), cur the frame's own -> the four outputs; the
+// packed counts (valid | rejected << 16, filled | changed << 16) are added to first and second
+template <int CAP>
+CODON_FL_HD tp_quad tp_filter4(const tp_quad* wnd, tp_quad cur, int nw, const TpArgs& a, unsigned& first, unsigned& second) {
+  const unsigned need = (unsigned)(a.min_count < nw ? a.min_count : nw);
+  // Rq <= 65535 (the entry refuses more) and a code is 16 bits: with both masks in sight the product of tau is the 24-bit
+  // multiply, a full-rate instruction, where the 32-bit one runs at a quarter of it
+  const unsigned rel = a.tol_rel & 0xFFFFu;
+  tp_quad res = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int q = 0; q < TP_PER; ++q) {
+    const unsigned v = tp_code(cur, q);
+    unsigned n = 0, sum = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < CAP; ++i) {
+      const unsigned x = tp_code(wnd[i], q);
+      const bool l = cl_linked(v, x, a.tol_abs, rel);
+      n += l;
+      sum += l ? x : 0u;
+    }
+    const bool rejected = v != 0u && n < need, kept = v != 0u && !rejected;
+    unsigned o = 0;
+    if (kept) o = tp_mean(sum, n);
+    else if (a.min_fill > 0) o = tp_fill<CAP>(wnd, q, a);
+    res |= (tp_quad)o << (16 * q);
+    first += (v != 0u) + ((unsigned)rejected << 16);
+    second += (!kept && o != 0u) + ((unsigned)(kept && o != v) << 16);
+  }
+  return res;
+}
+
 // one thread's four pixels of frame t, group gx of the plane: the window from the ring, the frame to `out`, the frame read ahead
 // (up to frame `last` of this chunk) into its slot; its packed counts (valid | rejected << 16, filled | changed << 16) into
 // cnt[tid] and cnt[TP_THREADS + tid] where cnt is given
@@ -153,34 +189,7 @@ CODON_FL_HD void tp_step(int tid, long gx, int t, int last, const void* in, cons
 #endif
     for (int i = 0; i < CAP; ++i) wnd[i] = i < nw ? ring[((lo + i) & (TP_SLOTS - 1)) * TP_THREADS + tid] : (tp_quad)0;
     const tp_quad cur = ring[(t & (TP_SLOTS - 1)) * TP_THREADS + tid];
-    const unsigned need = (unsigned)(a.min_count < nw ? a.min_count : nw);
-    // Rq <= 65535 (the entry refuses more) and a code is 16 bits: with both masks in sight the product of tau is the 24-bit
-    // multiply, a full-rate instruction, where the 32-bit one runs at a quarter of it
-    const unsigned rel = a.tol_rel & 0xFFFFu;
-    tp_quad res = 0;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int q = 0; q < TP_PER; ++q) {
-      const unsigned v = tp_code(cur, q);
-      unsigned n = 0, sum = 0;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-      for (int i = 0; i < CAP; ++i) {
-        const unsigned x = tp_code(wnd[i], q);
-        const bool l = cl_linked(v, x, a.tol_abs, rel);
-        n += l;
-        sum += l ? x : 0u;
-      }
-      const bool rejected = v != 0u && n < need, kept = v != 0u && !rejected;
-      unsigned o = 0;
-      if (kept) o = tp_mean(sum, n);
-      else if (a.min_fill > 0) o = tp_fill<CAP>(wnd, q, a);
-      res |= (tp_quad)o << (16 * q);
-      first += (v != 0u) + ((unsigned)rejected << 16);
-      second += (!kept && o != 0u) + ((unsigned)(kept && o != v) << 16);
-    }
+    const tp_quad res = tp_filter4<CAP>(wnd, cur, nw, a, first, second);
     tp_store4<FMT>(out, (long)t * hw + p, hw - p, res, a.vec);
     if (nxt <= last) ring[(nxt & (TP_SLOTS - 1)) * TP_THREADS + tid] = pre;
   }
@@ -214,6 +223,96 @@ CODON_FL_HD void wg_temporal(G wg, long gx, int chunk, const void* in, const TpA
       wg.sync();
       WG_EACH(wg, tid) cl_sum_add(wg, tid, TP_STATS, part, stats + (long)t * TP_STATS);
     }
+  }
+}
+
+// ---- the stream: one frame per step, the window resident in device memory (temporal_push.hip) ----------------------
+// The same definition, one frame at a time.  The state is the caller's: a ring of TP_SLOTS planes of h x w codes in the stream's
+// format, frame s in plane s & 15, and two words, state[TP_PUSHED] = N, the frames pushed so far, and state[TP_FLUSHED] = F, the
+// flush steps taken since the last push.  A step is wg_temporal_push_begin (one workgroup) and then wg_temporal_push over
+// ceil(h w / TP_TILE) workgroups; N and F are read from the state words, never from an argument, so one recorded step serves
+// every later frame.
+//   a push step   (in given): begin makes N += 1, F = 0.  The frame goes into slot (N - 1) & 15; frame t = N - 1 - ahead, if there
+//                 is one, is final -- its window [max(0, t - back), t + ahead] ends at the frame just pushed -- and goes to `out`
+//   a flush step  (in null): begin makes F += 1.  Frame t = max(0, N - ahead) + F - 1 goes to `out` if t <= N - 1, its window cut
+//                 at the sequence's end N - 1
+// Where no frame is final `out` is not written and the statistics row stays at the zeros of begin.
+// SIXTEEN SLOTS SUFFICE.  Storing frame N - 1 overwrites frame N - 17 and no other.  The frames not yet emitted when frame
+// N - 1 arrives are t >= N - 1 - ahead; the oldest frame one of their windows reads is N - 1 - ahead - back >= N - 15 > N - 17.
+// A flush stores nothing.  (tests/test_temporal_stream_cpu.py walks the rule for every window and length.)
+// A thread reads and writes its own four pixels of every plane and nothing else: no barrier, no LDS but the statistics' sums, no
+// dependency between workgroups.  The window is gathered into CAP registers by a static index (only the slot is dynamic); the
+// frame just pushed comes from the register that holds it.  N stays below 2^31 (the wrapper counts).
+constexpr int TP_PUSHED = 0, TP_FLUSHED = 1, TP_STATE = 2;
+
+// one workgroup: the counters' step, and the four statistics words to 0 (stats may be null)
+template <class G>
+CODON_FL_HD void wg_temporal_push_begin(G wg, int push, unsigned* state, unsigned* stats) {
+  WG_EACH(wg, tid) {
+    if (tid == 0) {
+      if (push) {
+        state[TP_PUSHED] += 1u;
+        state[TP_FLUSHED] = 0u;
+      } else {
+        state[TP_FLUSHED] += 1u;
+      }
+    }
+    if (stats && tid < TP_STATS) stats[tid] = 0u;
+  }
+}
+
+// one thread's four pixels of a step: N frames are in (the new one among them where `in` is given), frame t is the one to emit
+template <int FMT, int CAP>
+CODON_FL_HD void tp_push_step(int tid, long gx, int N, int t, const void* in, const TpArgs& a, void* ring, void* out, unsigned* cnt) {
+  const long hw = (long)a.h * a.w, p = (gx * TP_THREADS + tid) * TP_PER;
+  unsigned first = 0, second = 0;
+  if (p < hw) {
+    tp_quad fresh = 0;
+    if (in) {
+      fresh = tp_load4<FMT>(in, p, hw - p, a.vec);
+      tp_store4<FMT>(ring, (long)((N - 1) & (TP_SLOTS - 1)) * hw + p, hw - p, fresh, a.vec);
+    }
+    if (t >= 0 && t <= N - 1) {
+      const int lo = t - a.back > 0 ? t - a.back : 0, nw = N - lo;     // hi = min(N - 1, t + ahead) = N - 1 in either step
+      tp_quad wnd[CAP];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+      for (int i = 0; i < CAP; ++i) {
+        const bool held = in && i == nw - 1;                             // frame N - 1 of a push step: in `fresh`
+        tp_quad word = 0;
+        if (i < nw && !held) word = tp_load4<FMT>(ring, (long)((lo + i) & (TP_SLOTS - 1)) * hw + p, hw - p, a.vec);
+        wnd[i] = held ? fresh : word;
+      }
+      tp_quad cur = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+      for (int i = 0; i < CAP; ++i) cur = i == t - lo ? wnd[i] : cur;
+      const tp_quad res = tp_filter4<CAP>(wnd, cur, nw, a, first, second);
+      tp_store4<FMT>(out, p, hw - p, res, a.vec);
+    }
+  }
+  if (cnt) {
+    cnt[tid] = first;
+    cnt[TP_THREADS + tid] = second;
+  }
+}
+
+// workgroup gx of grid (ceil(h w / TP_TILE)), after wg_temporal_push_begin.  in: the new frame, or null for a flush step; a.T and
+// a.chunk are not read; a.vec: h w is a multiple of TP_PER and in, out and the ring stand on a multiple of TP_PER elements.  LDS:
+// cnt 2 TP_THREADS words and part 32, read with statistics alone.  stats (may be null): the four words begin zeroed
+template <int FMT, int CAP, class G>
+CODON_FL_HD void wg_temporal_push(G wg, long gx, const void* in, const TpArgs& a, void* ring, const unsigned* state, void* out,
+                                  unsigned* stats, unsigned* cnt, unsigned* part) {
+  const int N = (int)state[TP_PUSHED], F = (int)state[TP_FLUSHED];
+  const int t = in ? N - 1 - a.ahead : (N > a.ahead ? N - a.ahead : 0) + F - 1;
+  WG_EACH(wg, tid) tp_push_step<FMT, CAP>(tid, gx, N, t, in, a, ring, out, stats ? cnt : nullptr);
+  if (stats) {
+    wg.sync();
+    WG_EACH(wg, tid) cl_sum32(tid, cnt, part);
+    wg.sync();
+    WG_EACH(wg, tid) cl_sum_add(wg, tid, TP_STATS, part, stats);
   }
 }
 

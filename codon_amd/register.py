@@ -6,6 +6,8 @@ out as code 0, which `--fill-holes --fill-guided` was built for.
     python -m codon_amd.register --depth DIR --calib FILE --out DIR [--scale {1,4,8,16}] [--depth-bits {8,16}] [--depth-max N]
                                  [--depth-unit M] [--radial] [--stats] [--clean [--clean-tolerance CODES]
                                  [--clean-tolerance-rel F] [--clean-min-support K] [--clean-min-region N]]
+                                 [--temporal [--temporal-window W] [--temporal-causal] [--temporal-tolerance CODES]
+                                 [--temporal-tolerance-rel F] [--temporal-min-count M] [--temporal-min-fill F]]
 
 A z-buffered forward projection in integers (tests/register_ref.py; csrc/register.hip): every valid source pixel's four corners
 are projected, the box of them takes the pixel's z in the colour camera's frame under a minimum.  Only the tables -- the corner
@@ -14,7 +16,10 @@ on the host, once.  Not handled here: distortion of the COLOUR lens (undistort t
 `python -m codon_amd.undistort`, whose --calib-out is the calibration to pass here: DESIGN 12.16), a rolling shutter, and the
 growth of a foreground silhouette by up to one target pixel (the box is conservative).  --clean removes the sensor's flying
 pixels and speckles first, in the sensor's frame (codon_amd.clean): the same bytes as `python -m codon_amd.clean`
-followed by this, on one upload."""
+followed by this, on one upload.  --temporal takes the files of --depth, in the order of their names, as ONE sequence of a
+camera that stands still and filters it over time first of all (codon_amd.temporal's TemporalStream): every file
+is uploaded once and goes stream -> (cleaner) -> registration on the device, and the bytes are those of `python -m
+codon_amd.temporal`, then clean where --clean is given, then this, run as separate commands."""
 from __future__ import annotations
 
 import argparse
@@ -31,6 +36,7 @@ from . import _lib as L
 from . import clean as cleaning
 from . import codes as K
 from . import ops
+from . import temporal as filtering
 
 A_LIMIT, T_LIMIT, F_LIMIT, C_LIMIT = 1 << 22, 1 << 38, 1 << 20, 1 << 21
 UNDISTORT_ITERS = 40
@@ -272,10 +278,22 @@ def parse_args(argv=None):
     ap.add_argument("--clean", action="store_true", help="remove flying pixels and speckles first (python -m codon_amd.clean); "
                     "--stats then also prints valid=, flying=, speckle= and regions= of the cleaning")
     cleaning.add_arguments(ap, "clean-")
+    ap.add_argument("--temporal", action="store_true", help="the files are one sequence of a fixed camera: filter it over time first "
+                    "(python -m codon_amd.temporal --stream); --stats then also prints valid=, rejected=, filled= and changed= of the filter")
+    filtering.add_arguments(ap, "temporal-")
     a = ap.parse_args(argv)
     a.top = K.depth_args_of(ap, a)
     if os.path.abspath(a.out) == os.path.abspath(a.depth):
         ap.error("--out is --depth: the registered maps would overwrite the sensor's")
+    a.temporal_filter = None
+    if a.temporal:
+        a.temporal_filter = filtering.filter_of(a, ap, "temporal-")
+        if a.temporal_filter.tolerance > a.top:
+            ap.error(f"--temporal-tolerance {a.temporal_filter.tolerance} is above the largest code {a.top}")
+    else:
+        for name, default in filtering.DEFAULTS.items():
+            if getattr(a, "temporal_" + name) != default:
+                ap.error(f"--temporal-{name.replace('_', '-')} needs --temporal")
     a.cleaner = None
     if a.clean:
         a.cleaner = cleaning.cleaner_of(a, ap, "clean-")
@@ -298,7 +316,11 @@ def main(argv=None, emit=print):
     K.require_gpu()
     reg = Registration(cal, a.scale, a.depth_unit, a.radial)
     os.makedirs(a.out, exist_ok=True)
-    for name, codes in K.depth_files(a.depth, a.depth_bits, a.top, reg.device):
+    if a.temporal_filter is not None:
+        files = filtering.stream_files(a.temporal_filter, ap, a.depth, a.depth_bits, a.top, a.depth_max, reg.device, a.stats)
+    else:
+        files = ((name, codes, None) for name, codes in K.depth_files(a.depth, a.depth_bits, a.top, reg.device))
+    for name, codes, filtered in files:
         cleaned = None
         if a.cleaner is not None:
             codes = a.cleaner(codes, a.depth_max, stats=a.stats)
@@ -308,7 +330,8 @@ def main(argv=None, emit=print):
         K.write_codes(os.path.join(a.out, name), out)
         if a.stats:
             c = counts.cpu().numpy().view(np.uint32)[0]
-            tail = "" if cleaned is None else " cleaned: " + cleaning.stats_line(cleaned.cpu().numpy()[0])
+            tail = "" if filtered is None else " temporal: " + filtering.stats_line(filtered.cpu().numpy())
+            tail += "" if cleaned is None else " cleaned: " + cleaning.stats_line(cleaned.cpu().numpy()[0])
             emit(f"{name} " + " ".join(f"{k}={int(v)}" for k, v in zip(STATS, c)) + tail)
         else:
             emit(name)

@@ -1044,6 +1044,35 @@ int codon_temporal_depth(int32_t frames, int32_t height, int32_t width, const vo
                          int32_t ahead, int32_t tol_abs, int32_t tol_rel_q16, int32_t min_count, int32_t min_fill, void* out,
                          uint32_t* counts, codon_stream_t stream);
 
+/* ---- temporal filter of a depth stream, frame by frame (codon_amd.temporal.TemporalStream) ------------------------
+ * codon_temporal_depth's definition with the window resident on the device: frames go in one per call and frame t comes out as
+ * soon as it is final, with the push of frame t + ahead or, after the last push, with a flush step.  The outputs and counts of a
+ * stream of T frames are those of codon_temporal_depth on the (T, height, width) sequence, bit for bit, for any T.
+ *
+ * The state is the caller's, ON THE DEVICE, private to one stream of frames: ring, codon_temporal_ring_frames() = 16 planes of
+ * height x width codes in the stream's format (frame s lives in plane s & 15; no initialisation needed), and state, two uint32 --
+ * the frames pushed so far and the flush steps taken since the last push -- which the caller sets to 0 to open a stream.  The
+ * parameters must be the same in every call of one stream.
+ * A PUSH step (in: height x width codes): pushed += 1, flushed = 0, the frame is stored; with t = pushed - 1 - ahead >= 0 frame t
+ * goes to out and its four counts to counts; otherwise neither is written (counts is zeroed).
+ * A FLUSH step (in NULL): flushed += 1; with t = max(0, pushed - ahead) + flushed - 1 <= pushed - 1 frame t goes to out, its
+ * window cut at the last frame pushed; otherwise nothing is written.  A push after a flush continues the sequence behind the
+ * frames already emitted, which is no sequence of the definition: the wrapper refuses it.
+ * counts: NULL, or 4 uint32 ON THE DEVICE as in codon_temporal_depth; it needs no initialisation.
+ *
+ * Two launches per step (the counters and the zeroing; the filter), which depend on (height, width, back, ahead, fmt, in NULL or
+ * not) alone -- not on the frame index, which is read from state on the device, and not on counts: a step recorded into a graph
+ * replays for every later frame.  No workspace; no host synchronisation.  Refused on the host, before any HIP call, in this
+ * order: a height or width outside 1 .. 4096, an fmt other than CODON_FILL_U8 / _U16, top outside 1 .. 65535 or not 255 for u8
+ * codes, back or ahead below 0 or back + ahead above 14, tol_abs outside 0 .. top, tol_rel_q16 outside 0 .. 65535, min_count
+ * outside 1 .. 15, min_fill outside 0 .. 15, a NULL ring, state or out, out == in, a ring that overlaps in or out, a u16 plane or
+ * ring that is not 2-byte aligned, state or counts not 4-byte aligned.  On a refusal out, the ring, state and counts are
+ * untouched. */
+int32_t codon_temporal_ring_frames(void);
+int codon_temporal_push(int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top, int32_t back, int32_t ahead,
+                        int32_t tol_abs, int32_t tol_rel_q16, int32_t min_count, int32_t min_fill, void* ring, uint32_t* state,
+                        void* out, uint32_t* counts, codon_stream_t stream);
+
 /* ---- depth maps as point clouds with normals (codon_amd.cloud) ---------------------------------------------------
  * Nothing in the reference: it stops at the depth map.  A DEFINITION, in codon_amd/csrc/cloud.hip and cloud_tile.h, restated in
  * numpy in tests/cloud_ref.py, equal bytes required.

@@ -1,6 +1,6 @@
 """Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
 into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
-guided_fill, jbu, register, clean, undistort, cloud, mesh, normal_errors, temporal) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+guided_fill, jbu, register, clean, undistort, cloud, mesh, normal_errors, temporal, temporal_push) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
 address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
 restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
 
@@ -32,6 +32,7 @@ from tests import resample_masked_ref as M  # noqa: E402
 from tests import sensor_ref as S  # noqa: E402
 from tests import stretch_ref as T  # noqa: E402
 from tests import temporal_ref as V  # noqa: E402
+from tests import temporal_stream_cases as W  # noqa: E402
 from tests import undistort_ref as U  # noqa: E402
 
 FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
@@ -379,6 +380,22 @@ def temporal(run, p):
                        "tests/temporal_ref.py")
 
 
+def temporal_push(run, p):
+    """The GPU test's cases (temporal_stream_cases.cases): the planes under the windows at every length; the program pushes each
+    sequence frame by frame and flushes it, one element into larger buffers and on a 16-byte boundary, in both thread orders, with
+    and without statistics; the expectation is the restatement of the whole sequence"""
+    rows = W.cases()
+    for case in rows:
+        T_, h, w, Bk, Ah, M_, F_, A, Rq, pattern, top = case
+        V.sequence(T_, h, w, pattern, top).tofile(p("i"))
+        run(0 if top == 255 else 1, T_, h, w, Bk, Ah, A, Rq, M_, F_, p("i"), p("o"), p("s"))
+        want, stats = V.want(case)
+        assert np.fromfile(p("o"), dtype=want.dtype).tobytes() == want.tobytes(), case
+        assert np.fromfile(p("s"), dtype=np.uint32).tobytes() == stats.tobytes(), (case, "statistics")
+    return len(rows), (f"over {len(V.PLANES)} planes x {len(V.WINDOWS)} windows at every length, pushed frame by frame and flushed: "
+                       "no report, every byte and count equals tests/temporal_ref.py")
+
+
 # name -> (check, extra compile flags, what the count counts)
 CHECKS = {
     "d4": (d4, ["-ffp-contract=off"], "runs"),
@@ -395,6 +412,7 @@ CHECKS = {
     "mesh": (mesh, [], "cases"),
     "normal_errors": (normal_errors, [], "cases"),
     "temporal": (temporal, [], "cases"),
+    "temporal_push": (temporal_push, [], "cases"),
 }
 
 
