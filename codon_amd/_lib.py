@@ -206,6 +206,9 @@ SIGNATURES = {
     "codon_register_depth": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _I, _I, _P, _P, _P, _S, _P]),
     "codon_clean_workspace_bytes": (_S, [_I, _I, _I]),
     "codon_clean_depth": (C.c_int, [_I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _S, _P]),
+    "codon_smooth_plan": (_I, [_I, _I, C.POINTER(C.c_int32)]),
+    "codon_smooth_workspace_bytes": (_S, [_I, _I, _I]),
+    "codon_smooth_depth": (C.c_int, [_I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _S, _P]),
     "codon_temporal_chunk_frames": (_I, [_I, _I, _I, _I, _I]),
     "codon_temporal_depth": (C.c_int, [_I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "codon_temporal_ring_frames": (_I, []),

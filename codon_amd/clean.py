@@ -14,7 +14,8 @@ it removes the image's corners, above 5 its border.  Rule 2: a connected compone
 when linked) of fewer than --min-region pixels of what rule 1 left is removed; 0 or 1 switches it off.  The four defaults are
 untuned.  Not handled: a real structure one pixel wide (a wire) goes with the flying pixels; no confidence or amplitude image is
 read.  A fixed camera's sequence is filtered over time by the step in front of this one, `python -m codon_amd.temporal` (DESIGN
-12.23): the recommended order is temporal -> clean -> register."""
+12.23), and what survives is smoothed in space by the step behind it, `python -m codon_amd.smooth`: the recommended
+order is temporal -> clean -> smooth -> register."""
 from __future__ import annotations
 
 import argparse

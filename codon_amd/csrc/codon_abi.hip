@@ -17,6 +17,7 @@
 #include "mesh_tile.h"
 #include "normal_tile.h"
 #include "sensor_pixel.h"
+#include "smooth_tile.h"
 #include "stretch_tile.h"
 #include "temporal_tile.h"
 #include "train_record.h"
@@ -1271,6 +1272,43 @@ int codon_clean_depth(int32_t batch, int32_t height, int32_t width, const void* 
   if (const int st = check_workspace(who, workspace_bytes, clean_workspace_bytes(batch, height, width))) return st;
   return clean_depth(batch, height, width, in, fmt, tol_abs, tol_rel_q16, min_support, min_region, out, counts, workspace,
                      (hipStream_t)stream);
+}
+
+// ---- spatial smoothing of sensor depth maps -------------------------------------------------------------------------
+static int check_smooth_window(const char* who, int radius, int passes) {
+  CODON_REQUIRE(radius >= 1 && radius <= SM_MAX_RADIUS, CODON_ERR_BAD_ARG, "%s: radius %d (1..%d)", who, radius, SM_MAX_RADIUS);
+  CODON_REQUIRE(passes >= 1 && passes <= SM_MAX_PASSES, CODON_ERR_BAD_ARG, "%s: passes %d (1..%d)", who, passes, SM_MAX_PASSES);
+  return CODON_OK;
+}
+
+int32_t codon_smooth_plan(int32_t radius, int32_t passes, int32_t* plan) {
+  if (check_smooth_window("smooth_plan", radius, passes)) return 0;
+  if (plan) plan[0] = SMOOTH_TILE, plan[1] = smooth_fuse_bound(radius), plan[2] = smooth_fused(radius, passes);
+  return smooth_launches(radius, passes);
+}
+
+size_t codon_smooth_workspace_bytes(int32_t batch, int32_t height, int32_t width) { return smooth_workspace_bytes(batch, height, width); }
+
+int codon_smooth_depth(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top, int32_t radius,
+                       int32_t passes, int32_t tol_abs, int32_t tol_rel_q16, int32_t pairs, const int32_t* weights, void* out,
+                       uint32_t* counts, void* workspace, size_t workspace_bytes, codon_stream_t stream) {
+  const char* who = "smooth_depth";
+  CODON_REQUIRE(in && out && weights, CODON_ERR_BAD_ARG, "smooth_depth: null pointer");
+  if (const int st = check_planes(who, fmt, batch, height, width, SM_MAX_SIDE, top)) return st;
+  if (const int st = check_smooth_window(who, radius, passes)) return st;
+  if (const int st = check_link_tolerances(who, tol_abs, top, tol_rel_q16, SM_MAX_REL)) return st;
+  CODON_REQUIRE(pairs == 0 || pairs == 1, CODON_ERR_BAD_ARG, "smooth_depth: pairs %d (0 or 1)", pairs);
+  if (const int st = check_not_same(who, in, out)) return st;
+  const bool planes_ok = (((uintptr_t)in | (uintptr_t)out) & (uintptr_t)(fl_elem_bytes(fmt) - 1)) == 0;
+  const bool words_ok = (((uintptr_t)counts | (uintptr_t)weights) & 3) == 0 && ((uintptr_t)workspace & 15) == 0;
+  CODON_REQUIRE(planes_ok && words_ok, CODON_ERR_BAD_ARG, "smooth_depth: unaligned plane, weights, statistics or workspace");
+  if (smooth_launches(radius, passes) > 1) {
+    CODON_REQUIRE(workspace, CODON_ERR_BAD_ARG, "smooth_depth: null workspace with %d launches", smooth_launches(radius, passes));
+    CODON_REQUIRE(workspace != in && workspace != out, CODON_ERR_BAD_ARG, "smooth_depth: the workspace is in or out");
+    if (const int st = check_workspace(who, workspace_bytes, smooth_workspace_bytes(batch, height, width))) return st;
+  }
+  return smooth_depth(batch, height, width, in, fmt, radius, passes, tol_abs, tol_rel_q16, pairs, weights, out, counts, workspace,
+                      (hipStream_t)stream);
 }
 
 // ---- temporal filter of a fixed camera's depth sequence ------------------------------------------------------------

@@ -199,6 +199,11 @@ size_t cloud_workspace_bytes(int B, int h, int w);
 int cloud_points(int B, int h, int w, const void* in, int fmt, const int* rx, const int* ry, double m, int radius, int tol_abs,
                  int tol_rel_q16, const void* color, int channels, void* body, void* counts, void* nmap, void* workspace,
                  hipStream_t stream);
+// smooth.hip; weights: (2 radius + 1)^2 int32 on the device; stats: (B, 4) u32 or null; workspace: one plane set of u16 cells,
+// read and written only where smooth_launches(radius, passes) > 1 (may be null otherwise)
+size_t smooth_workspace_bytes(int B, int h, int w);
+int smooth_depth(int B, int h, int w, const void* in, int fmt, int radius, int passes, int tol_abs, int tol_rel_q16, int pairs,
+                 const void* weights, void* out, void* stats, void* workspace, hipStream_t stream);
 // temporal.hip; in, out: (T, h, w) codes, T h w below 2^31; stats: (T, 4) u32 or null; no workspace
 int temporal_depth(int T, int h, int w, const void* in, int fmt, int back, int ahead, int tol_abs, int tol_rel_q16, int min_count,
                    int min_fill, void* out, void* stats, hipStream_t stream);

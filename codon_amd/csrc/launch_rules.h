@@ -91,4 +91,23 @@ inline int temporal_cap(int back, int ahead) {
 // every frame index and with or without statistics.  The window registers are temporal_cap's.
 inline long temporal_push_groups(int h, int w) { return ((long)h * w + TEMPORAL_TILE - 1) / TEMPORAL_TILE; }
 
+// ---- spatial smoothing (smooth.hip): tile, passes fused per launch, launches -- one rule of (R, P) --------------
+// A workgroup owns a SMOOTH_TILE x SMOOTH_TILE tile.  A launch that runs k passes loads the tile plus a halo of R k and computes
+// pass j on the tile plus a halo of R (k - j): (T + 2 R (k - j))^2 / T^2 times the work of a launch of its own, against one launch,
+// one read and one write of the plane saved per fused pass.  smooth_fuse_bound(R) is the largest k at which that pays, MEASURED
+// (tools/time_smooth.py; DESIGN 12.25 holds the numbers); a call of P passes is ceil(P / min(P, bound)) launches of the one kernel,
+// the first ones of the full bound.  codon_smooth_plan is these functions called without a launch.
+// CODON_SMOOTH_FUSE_ALL: every pass of a call in one launch, whatever R -- the other side of that measurement, never the default.
+constexpr int SMOOTH_TILE = 32;
+constexpr int SMOOTH_MAX_RADIUS = 4, SMOOTH_MAX_PASSES = 3;
+inline int smooth_fuse_bound(int radius) {
+#ifdef CODON_SMOOTH_FUSE_ALL
+  return SMOOTH_MAX_PASSES;
+#else
+  return radius == 1 ? SMOOTH_MAX_PASSES : 1;
+#endif
+}
+inline int smooth_fused(int radius, int passes) { return passes < smooth_fuse_bound(radius) ? passes : smooth_fuse_bound(radius); }
+inline int smooth_launches(int radius, int passes) { return (passes + smooth_fused(radius, passes) - 1) / smooth_fused(radius, passes); }
+
 }  // namespace codon

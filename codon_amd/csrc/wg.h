@@ -10,14 +10,14 @@
 //             with a `for` around them the compiler schedules the phases' unrolled loads differently (fill_push_kernel: 54 -> 70
 //             VGPRs), with the `if` the code is the hand-strung kernel's; sync() is __syncthreads(); Regs<T, N> is a plain local
 //             array.  Hence: WG_EACH takes one statement or a braced block, and never stands before an `else`;
-//             atomic_min / atomic_add are the device's atomics on global memory, results not returned; atomic_min_old is the
+//             atomic_min / atomic_max / atomic_add are the device's atomics on global memory, results not returned; atomic_min_old is the
 //             same minimum and RETURNS what the word held, load_relaxed a relaxed load at agent scope (served by L2, never a
 //             stale L1 line): the pair a lock-free union-find needs (clean_tile.h); lds_add is the add on a word
 //             of an LDS array (normal_tile.h's histogram)
 //   WgHost    WG_EACH runs tid over all threads, forwards or (reverse) backwards, so that a phase that reads what another thread
 //             of the SAME phase writes gives different bytes in the two orders; sync() does nothing; Regs<T, N> is one
 //             separately allocated row of exactly N elements per thread: a thread that writes past its registers is a report;
-//             atomic_min / atomic_add / lds_add / atomic_min_old are a plain minimum and a plain add, load_relaxed a plain load
+//             atomic_min / atomic_max / atomic_add / lds_add / atomic_min_old are a plain minimum, maximum and add, load_relaxed a plain load
 //             (one thread runs at a time)
 #pragma once
 
@@ -37,6 +37,7 @@ struct WgDevice {
   __device__ __forceinline__ int first() const { return threadIdx.x; }
   __device__ __forceinline__ void sync() const { __syncthreads(); }
   __device__ __forceinline__ void atomic_min(unsigned* p, unsigned v) const { atomicMin(p, v); }
+  __device__ __forceinline__ void atomic_max(unsigned* p, unsigned v) const { atomicMax(p, v); }
   __device__ __forceinline__ void atomic_add(unsigned* p, unsigned v) const { atomicAdd(p, v); }
   __device__ __forceinline__ void lds_add(unsigned* p, unsigned v) const { atomicAdd(p, v); }
   __device__ __forceinline__ unsigned atomic_min_old(unsigned* p, unsigned v) const { return atomicMin(p, v); }
@@ -78,6 +79,7 @@ struct WgHost {
   int step() const { return reverse ? -1 : 1; }
   void sync() const {}
   void atomic_min(unsigned* p, unsigned v) const { *p = v < *p ? v : *p; }
+  void atomic_max(unsigned* p, unsigned v) const { *p = v > *p ? v : *p; }
   void atomic_add(unsigned* p, unsigned v) const { *p += v; }
   void lds_add(unsigned* p, unsigned v) const { *p += v; }
   unsigned atomic_min_old(unsigned* p, unsigned v) const {

@@ -6,6 +6,8 @@ out as code 0, which `--fill-holes --fill-guided` was built for.
     python -m codon_amd.register --depth DIR --calib FILE --out DIR [--scale {1,4,8,16}] [--depth-bits {8,16}] [--depth-max N]
                                  [--depth-unit M] [--radial] [--stats] [--clean [--clean-tolerance CODES]
                                  [--clean-tolerance-rel F] [--clean-min-support K] [--clean-min-region N]]
+                                 [--smooth [--smooth-radius R] [--smooth-passes P] [--smooth-sigma S] [--smooth-tolerance CODES]
+                                 [--smooth-tolerance-rel F] [--smooth-no-pairs]]
                                  [--temporal [--temporal-window W] [--temporal-causal] [--temporal-tolerance CODES]
                                  [--temporal-tolerance-rel F] [--temporal-min-count M] [--temporal-min-fill F]]
 
@@ -16,10 +18,12 @@ on the host, once.  Not handled here: distortion of the COLOUR lens (undistort t
 `python -m codon_amd.undistort`, whose --calib-out is the calibration to pass here: DESIGN 12.16), a rolling shutter, and the
 growth of a foreground silhouette by up to one target pixel (the box is conservative).  --clean removes the sensor's flying
 pixels and speckles first, in the sensor's frame (codon_amd.clean): the same bytes as `python -m codon_amd.clean`
-followed by this, on one upload.  --temporal takes the files of --depth, in the order of their names, as ONE sequence of a
+followed by this, on one upload.  --smooth then smooths what is left, still in the sensor's frame (codon_amd.smooth):
+the same bytes as `python -m codon_amd.smooth` between the two.  --temporal takes the files of --depth, in the order of their names, as ONE sequence of a
 camera that stands still and filters it over time first of all (codon_amd.temporal's TemporalStream): every file
-is uploaded once and goes stream -> (cleaner) -> registration on the device, and the bytes are those of `python -m
-codon_amd.temporal`, then clean where --clean is given, then this, run as separate commands."""
+is uploaded once and goes stream -> (cleaner) -> (smoother) -> registration on the device, and the bytes are those of `python -m
+codon_amd.temporal`, then clean where --clean is given, then smooth where --smooth is given, then this, run as separate commands:
+the recommended order, temporal -> clean -> smooth -> register."""
 from __future__ import annotations
 
 import argparse
@@ -36,6 +40,7 @@ from . import _lib as L
 from . import clean as cleaning
 from . import codes as K
 from . import ops
+from . import smooth as smoothing
 from . import temporal as filtering
 
 A_LIMIT, T_LIMIT, F_LIMIT, C_LIMIT = 1 << 22, 1 << 38, 1 << 20, 1 << 21
@@ -278,6 +283,9 @@ def parse_args(argv=None):
     ap.add_argument("--clean", action="store_true", help="remove flying pixels and speckles first (python -m codon_amd.clean); "
                     "--stats then also prints valid=, flying=, speckle= and regions= of the cleaning")
     cleaning.add_arguments(ap, "clean-")
+    ap.add_argument("--smooth", action="store_true", help="smooth the maps in the sensor's frame, after --clean (python -m codon_amd.smooth); "
+                    "--stats then also prints valid=, changed=, alone= and max= of the smoothing")
+    smoothing.add_arguments(ap, "smooth-")
     ap.add_argument("--temporal", action="store_true", help="the files are one sequence of a fixed camera: filter it over time first "
                     "(python -m codon_amd.temporal --stream); --stats then also prints valid=, rejected=, filled= and changed= of the filter")
     filtering.add_arguments(ap, "temporal-")
@@ -303,6 +311,15 @@ def parse_args(argv=None):
         for name, default in cleaning.DEFAULTS.items():
             if getattr(a, "clean_" + name) != default:
                 ap.error(f"--clean-{name.replace('_', '-')} needs --clean")
+    a.smoother = None
+    if a.smooth:
+        a.smoother = smoothing.smoother_of(a, ap, "smooth-")
+        if a.smoother.tolerance > a.top:
+            ap.error(f"--smooth-tolerance {a.smoother.tolerance} is above the largest code {a.top}")
+    else:
+        for name, default in smoothing.DEFAULTS.items():
+            if getattr(a, "smooth_" + name) != default:
+                ap.error(f"--smooth-{'no-pairs' if name == 'pairs' else name.replace('_', '-')} needs --smooth")
     return a, ap
 
 
@@ -325,6 +342,10 @@ def main(argv=None, emit=print):
         if a.cleaner is not None:
             codes = a.cleaner(codes, a.depth_max, stats=a.stats)
             codes, cleaned = codes if a.stats else (codes, None)
+        smoothed = None
+        if a.smoother is not None:
+            codes = a.smoother(codes, a.depth_max, stats=a.stats)
+            codes, smoothed = codes if a.stats else (codes, None)
         got = reg(codes, a.depth_max, stats=a.stats)
         out, counts = got if a.stats else (got, None)
         K.write_codes(os.path.join(a.out, name), out)
@@ -332,6 +353,7 @@ def main(argv=None, emit=print):
             c = counts.cpu().numpy().view(np.uint32)[0]
             tail = "" if filtered is None else " temporal: " + filtering.stats_line(filtered.cpu().numpy())
             tail += "" if cleaned is None else " cleaned: " + cleaning.stats_line(cleaned.cpu().numpy()[0])
+            tail += "" if smoothed is None else " smoothed: " + smoothing.stats_line(smoothed.cpu().numpy()[0])
             emit(f"{name} " + " ".join(f"{k}={int(v)}" for k, v in zip(STATS, c)) + tail)
         else:
             emit(name)

@@ -1,7 +1,7 @@
 """Temporal filtering of a FIXED camera's depth sequence: the step in front of `python -m codon_amd.clean`, in the
 sensor's own frame.  Range noise on a static pixel averages out over frames; a pixel that is valid in one frame and a hole in the
 next (flicker) takes the value that stood in the frames around it; a one-frame spike is rejected by the frames around it, whatever
-its spatial support.  The recommended order is temporal -> clean -> register.
+its spatial support.  The recommended order is temporal -> clean -> smooth -> register.
 
     python -m codon_amd.temporal --depth DIR --out DIR [--depth-bits {8,16}] [--depth-max N] [--window W] [--causal]
                                  [--tolerance CODES] [--tolerance-rel F] [--min-count M] [--min-fill F] [--block FRAMES] [--stream]

@@ -1015,6 +1015,41 @@ int codon_clean_depth(int32_t batch, int32_t height, int32_t width, const void* 
                       int32_t tol_rel_q16, int32_t min_support, int32_t min_region, void* out, uint32_t* counts, void* workspace,
                       size_t workspace_bytes, codon_stream_t stream);
 
+/* ---- spatial smoothing of sensor depth maps (codon_amd.smooth) ---------------------------------------------------
+ * Nothing in the reference: its inputs were noise-free renderings.  A DEFINITION, in codon_amd/csrc/smooth.hip and smooth_tile.h,
+ * restated in numpy in tests/smooth_ref.py, equal bits required.  Integers only.
+ *
+ * in, out: (batch, height, width) codes, u8 or u16, 0 a hole.  Two codes are LINKED under codon_clean_depth's rule with tol_abs
+ * and tol_rel_q16.  One pass c -> c': a hole stays 0.  For a valid pixel p, S is the set of the positions q != p of the
+ * (2 radius + 1)^2 window around p that lie inside the plane and are linked to c_p, every code read from the pass's input; with
+ * pairs = 1, q stays in S only if its point mirror 2p - q is in S too.  N = 256 c_p + sum_S W_q c_q, D = 256 + sum_S W_q,
+ * c' = floor((2N + D) / (2D)), in unsigned 32 bits (2N + D < 2^32 for radius <= 4 and weights <= 256).  `passes` passes compose.
+ * weights: int32 (2 radius + 1)^2 ON THE DEVICE, row-major over (dy, dx): every entry 0 .. 256, symmetric under (dy, dx) ->
+ * (-dy, -dx) -- the caller's duty, nothing reads the device here; the entry of the centre is not read.  The hole set of out is
+ * that of in; a pass moves a code by at most tol_abs + ((tol_rel_q16 c_p) >> 16); with pairs = 1 a plane with an integer
+ * gradient comes back bit for bit, however holes, an occluder or the border cut the windows.  counts: NULL, or (batch, 4) uint32
+ * ON THE DEVICE: valid inputs, pixels whose output differs from the input, valid pixels whose S is empty in the first pass, the
+ * largest |out - in|; it needs no initialisation.
+ *
+ * codon_smooth_plan: HOST ONLY -- the launcher's own rule of (radius, passes) (csrc/launch_rules.h) called without a launch:
+ * returns the number of filter launches, 0 for a radius outside 1 .. 4 or passes outside 1 .. 3, and with plan != NULL writes
+ * plan[0] = the tile's side, plan[1] = the most passes one launch runs at this radius (the fusion bound), plan[2] = the passes
+ * of the call's first launch.  codon_smooth_workspace_bytes: HOST ONLY -- the bytes of one set of planes as u16 cells, a multiple
+ * of 16; 0 for a batch outside 1 .. 65535 or a height or width outside 1 .. 4096.  workspace: read and written only where
+ * codon_smooth_plan answers more than 1 (NULL otherwise is accepted): 16-byte aligned, private to the stream, no initialisation
+ * needed.  1 + codon_smooth_plan launches (the statistics to 0; the filter), which depend on (radius, passes) and the sizes
+ * alone and not on counts; no host synchronisation.  Refused on the host, before any HIP call: null pointers (counts may be
+ * NULL), an fmt other than CODON_FILL_U8 / _U16, batch outside 1 .. 65535, a height or width outside 1 .. 4096, top outside
+ * 1 .. 65535 or not 255 for u8 codes, radius outside 1 .. 4, passes outside 1 .. 3, tol_abs outside 0 .. top, tol_rel_q16
+ * outside 0 .. 65535, pairs other than 0 or 1, out == in, a u16 plane that is not 2-byte aligned, weights or counts not 4-byte
+ * aligned, and, where it is used, a workspace that is NULL, in or out, not 16-byte aligned or too small.  `out` is untouched on
+ * a refusal. */
+int32_t codon_smooth_plan(int32_t radius, int32_t passes, int32_t* plan);
+size_t codon_smooth_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int codon_smooth_depth(int32_t batch, int32_t height, int32_t width, const void* in, int32_t fmt, int32_t top, int32_t radius,
+                       int32_t passes, int32_t tol_abs, int32_t tol_rel_q16, int32_t pairs, const int32_t* weights, void* out,
+                       uint32_t* counts, void* workspace, size_t workspace_bytes, codon_stream_t stream);
+
 /* ---- temporal filter of a fixed camera's depth sequence (codon_amd.temporal) -------------------------------------
  * Nothing in the reference: it reads single images.  A DEFINITION, in codon_amd/csrc/temporal.hip and temporal_tile.h, restated in
  * numpy in tests/temporal_ref.py, equal bits required.  Integers only.

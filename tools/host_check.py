@@ -1,6 +1,6 @@
 """Host-side sanitizer checks of the kernels whose text also compiles for the host -- need no GPU and load nothing
 into Python.  Each check builds tools/NAME_host_check.cpp -- a stand-alone program around the workgroup bodies (d4, eval, fill,
-guided_fill, jbu, register, clean, undistort, cloud, mesh, normal_errors, temporal, temporal_push) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
+guided_fill, jbu, register, clean, undistort, cloud, mesh, normal_errors, temporal, temporal_push, smooth) or per-thread bodies (sensor, stretch) of a header under codon_amd/csrc/, the text the device kernels call -- with the
 address and undefined-behaviour sanitizers, runs it over the GPU tests' cases and compares every byte it writes with the numpy
 restatement tests/NAME_ref.py.  The programs that run workgroup bodies run every case with both thread orders themselves.
 
@@ -30,6 +30,7 @@ from tests import normal_errors_ref as N  # noqa: E402
 from tests import register_ref as G  # noqa: E402
 from tests import resample_masked_ref as M  # noqa: E402
 from tests import sensor_ref as S  # noqa: E402
+from tests import smooth_ref as Y  # noqa: E402
 from tests import stretch_ref as T  # noqa: E402
 from tests import temporal_ref as V  # noqa: E402
 from tests import temporal_stream_cases as W  # noqa: E402
@@ -396,6 +397,23 @@ def temporal_push(run, p):
                        "no report, every byte and count equals tests/temporal_ref.py")
 
 
+def smooth(run, p):
+    """The GPU test's cases (smooth_ref.cases): every plane under every (radius, passes) with the pair rule on and off, the rest in
+    turn; the program runs each with the passes split over the launches in every way, one element into larger buffers and on a
+    16-byte boundary, in both thread orders, with and without statistics"""
+    rows = Y.cases()
+    for case in rows:
+        B, h, w, R, P, sigma, pairs, A, Rq, pattern, top = case
+        Y.codes_of(case).tofile(p("i")), Y.weight_table(R, sigma).tofile(p("w"))
+        run(0 if top == 255 else 1, B, h, w, R, P, int(pairs), A, Rq, p("i"), p("w"), p("o"), p("s"))
+        want, stats = Y.want(case)
+        assert np.fromfile(p("o"), dtype=want.dtype).tobytes() == want.tobytes(), case
+        assert np.fromfile(p("s"), dtype=np.uint32).tobytes() == stats.tobytes(), (case, "statistics")
+    return len(rows), (f"over {len(Y.PLANES)} planes x {len(Y.RADII)} radii x {len(Y.PASSES)} pass counts x the pair rule on and off, "
+                       f"{len(Y.SIGMAS)} sigmas, {len(Y.TOLERANCES)} tolerances, {len(Y.FORMATS)} formats and {len(Y.PATTERNS)} patterns in "
+                       "turn: no report, every byte and count equals tests/smooth_ref.py")
+
+
 # name -> (check, extra compile flags, what the count counts)
 CHECKS = {
     "d4": (d4, ["-ffp-contract=off"], "runs"),
@@ -413,6 +431,7 @@ CHECKS = {
     "normal_errors": (normal_errors, [], "cases"),
     "temporal": (temporal, [], "cases"),
     "temporal_push": (temporal_push, [], "cases"),
+    "smooth": (smooth, [], "cases"),
 }
 
 
